@@ -2,6 +2,7 @@
 """Headline benchmark: env-steps/sec (+ PPO updates/sec) of the PPOV2.0 hot path on MI355X.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus 8                      # spawns 8 fresh rank processes itself (RCCL), rank 0 prints the line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -309,9 +310,10 @@ def cpu_baseline_vectorised(T=128, H=128, n_sample=4096, n_full=4096, epochs=5, 
 
 
 # ------------------------------------------------------------------------------------------------ measurement
-def measure(tr, steps, warmup, world, dev, ops, dist, timers=(), dominant=("lstm_bwd",), breakdown_iters=3):
+def measure(tr, steps, warmup, world, dev, ops, dist, timers=(), dominant=("lstm_bwd",), breakdown_iters=3, after_timed=None):
     """`warmup` untimed iterations, then exactly `steps` timed ones between barrier + synchronize pairs;
-    returns (max-over-ranks seconds, rollout ms per iteration, kernel timers).
+    returns (max-over-ranks seconds, rollout ms per iteration, kernel timers).  `after_timed(tr)`, when given, is called
+    right after the timed region, before any further iteration: it sees the state the last timed step left.
 
     Inside the timed region only the DOMINANT kernel's launches are bracketed with HIP events on the launch stream (what
     `roofline` needs, live): an event pair costs ~5 us of device idle per bracketed launch (rocprofv3 trace of round 5:
@@ -348,6 +350,8 @@ def measure(tr, steps, warmup, world, dev, ops, dist, timers=(), dominant=("lstm
         tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if after_timed is not None:
+        after_timed(tr)
     summary = ops.KERNEL_TIMER.summary() if live else {}
     ops.KERNEL_TIMER.disable()
     # per-kernel breakdown + rollout time: a few more iterations of the same loop, outside the timed region
@@ -688,6 +692,39 @@ def build_trainer(cfg, N, rank, world, dev, ops):
                          bank_sources=bank_src, trend_k=cfg.get("trend_k", 0))
 
 
+DUMP_MAX_ENVS = 1024             # --dump-outputs: per-env arrays of at most this many envs (a fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(tr, out_dir):
+    """What the last timed train_iteration() left for its caller, as <out_dir>/<name>.npy (float32, or float64 where the
+    trainer keeps f64): the loss sums it returned, the parameters and Adam moments after its update, the rollout buffers it
+    collected (with the advantages and returns it trained on) and the env / recurrent state the next iteration starts from.
+    Per-env arrays keep the rows of at most DUMP_MAX_ENVS envs, drawn with a fixed seed, so that two builds can be compared."""
+    import numpy as np
+    import torch
+    N = tr.N
+    rows = np.arange(N) if N <= DUMP_MAX_ENVS else np.sort(np.random.default_rng(0).choice(N, DUMP_MAX_ENVS, replace=False))
+    idx = torch.from_numpy(rows).to(tr.device)
+    out = {"loss_sums": tr.loss_sums, "params": tr.policy.flat, "adam_exp_avg": tr.exp_avg, "adam_exp_avg_sq": tr.exp_avg_sq,
+           "grad_norm": tr.gnorm, "cur_obs": tr.cur_obs[idx]}
+    for k in ("obs", "act", "rew", "val", "logp", "done"):
+        out[k] = tr.buf[k][idx]
+    out["adv_n"], out["ret"] = tr.adv_n[idx], tr.ret[idx]
+    if tr.kind == "lstm":
+        out["lstm_h"], out["lstm_c"] = tr.h[:, idx], tr.c[:, idx]
+    arrays = {}
+    for k, v in out.items():
+        a = v.detach().cpu().numpy()
+        arrays[k] = a if a.dtype == np.float64 else a.astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -703,7 +740,11 @@ def main():
                     help="carrier of the iteration's exchanges: torch.distributed (default) or the C ABI's own RCCL communicator (uav_allreduce)")
     ap.add_argument("--pg-timeout", type=float, default=600.0, help="seconds before a stuck collective (or a rendezvous nobody joins: a fresh box can take 1-2 min to load PyTorch) aborts the rank")
     ap.add_argument("--headline-timeout", type=float, default=0.0, help="launcher mode: seconds before the headline rank set is terminated (0 = config-dependent default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing above touched the GPU (no torch import yet),
@@ -759,7 +800,8 @@ def main():
     N = n_weak if args.scaling == "weak" else n_strong
     tr = build_trainer(cfg, N, rank, world, dev, ops)
     dt, roll_ms, timers = measure(tr, args.steps, args.warmup, world, dev, ops, dist,
-                                  timers=("lstm_bwd", "lstm_fwd", "lstm_wgrad", "rollout", "ppo_loss"))
+                                  timers=("lstm_bwd", "lstm_fwd", "lstm_wgrad", "rollout", "ppo_loss"),
+                                  after_timed=(lambda t: dump_outputs(t, args.dump_outputs)) if args.dump_outputs and rank == 0 else None)
     epochs = tr.hp["epochs"]
     env_steps = N * T * world * args.steps
     value = env_steps / dt

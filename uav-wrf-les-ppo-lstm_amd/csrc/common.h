@@ -7,6 +7,22 @@
 #include <string.h>
 #include "../../include/uavppo.h"
 
+// pointer -> small int for the last 8 buffers recorded (an entry is overwritten when its pointer is recorded again)
+struct uav_form_table {
+    struct { const void* p; int v; } e[8];
+    int next;
+    void record(const void* p, int v) {
+        for (auto& x : e)
+            if (x.p == p) { x.v = v; return; }
+        e[next] = {p, v};
+        next = (next + 1) % 8;
+    }
+    int find(const void* p) const {               // -1 = not recorded
+        for (auto& x : e)
+            if (x.p == p) return x.v;
+        return -1;
+    }
+};
 struct uav_ctx {
     int device;
     int num_cu;
@@ -23,20 +39,13 @@ struct uav_ctx {
     int comm_rank, comm_world;
     // form of the last few gate-gradient buffers uav_lstm_bwd / _bwd_stack wrote (1 = fp16 piece chunks, 0 = f32 rows): uav_lstm_wgrad
     // refuses a buffer whose recorded form is not the one the handle's CURRENT mode would read (mode changed in between)
-    struct { const void* p; int packed; } dg_form[8];
-    int dg_next;
+    uav_form_table dg_form;
+    // the same for the last few h = 256 stashes uav_lstm_fwd / the stepper wrote (1 = h_prev slot written, 0 = left out by the
+    // fp16-split path): uav_lstm_wgrad refuses to read a slot the forward pass did not write (mode changed in between)
+    uav_form_table hslot_form;
 };
-static inline void uav_dg_record(uav_ctx* ctx, const void* p, int packed) {
-    for (auto& e : ctx->dg_form)
-        if (e.p == p) { e.packed = packed; return; }
-    ctx->dg_form[ctx->dg_next] = {p, packed};
-    ctx->dg_next = (ctx->dg_next + 1) % 8;
-}
-static inline int uav_dg_form(const uav_ctx* ctx, const void* p) {       // -1 = not recorded (a buffer filled by the caller)
-    for (auto& e : ctx->dg_form)
-        if (e.p == p) return e.packed;
-    return -1;
-}
+static inline void uav_dg_record(uav_ctx* ctx, const void* p, int packed) { ctx->dg_form.record(p, packed); }
+static inline int uav_dg_form(const uav_ctx* ctx, const void* p) { return ctx->dg_form.find(p); }    // -1 = not recorded (filled by the caller)
 
 // arithmetic / debug switches of the call in flight on this thread (set from the handle by the LSTM entry points; the
 // launch helpers below them have no ctx argument).  No getenv on any call path: the UAV_LSTM_BF16X6 / UAV_LSTM_F32_MFMA
@@ -149,7 +158,8 @@ __device__ __forceinline__ unsigned short h_bits(_Float16 v) { return __builtin_
 // profiles/r05_c5_no_f32_dgates_ablation.log).  Layout, time-major so that a step's block and the GEMM's K walk are linear:
 //   halves  pieces[t][rt][s][piece][512]      rt < RT = NP / 16 (16-env row tiles, NP = N rounded up to 64; rows >= N zero),
 //                                             s < NS = 4H / 32 (32 gate rows), 512 = (kq * 16 + env) * 8 + i, row 32 s + 8 kq + i
-//   floats  isc[t][NP]                        2^-e of (env, step): dG = (p0 + 2^-11 p1) * isc; 0 for rows >= N
+//   floats  isc[t][NP]                        2^-e of (env, step): dG = (p0 + 2^-11 p1) * isc; 0 for rows >= N and for
+//                                             rows whose gate gradients are all zero (max isc is the weight-gradient block scale)
 //   floats  iscm[t][NP]                       isc * keep[env][step]: the scale under which dW_hh = dG^T h_prev takes h_prev[n][t] = y[n][t-1]
 //                                             * keep[n][t] straight from the layer's output y (h0 at t = 0) -- the forward pass then
 //                                             need not write an h_prev slot into the stash at all

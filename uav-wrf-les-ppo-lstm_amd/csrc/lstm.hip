@@ -1558,6 +1558,8 @@ int uav_lstm_fwd(uav_ctx* ctx, const float* x, const float* keep, const float* h
                          : lstm_generic_fwd(ctx, keep, h0, c0, w_hh, N, T, H, y, hn, cn, stash, st);
     }
     if (rc) return rc;
+    // h = 256: whether this stash's h_prev slot was written (the fp16-split step path with packed gate gradients leaves it out)
+    if (H == DgPack::H) ctx->hslot_form.record(stash, step256 && lstm_h3_dg_packed(H) ? 0 : 1);
     // kernels without the fused head product: heads = y W_head^T + b_head as one GEMM over the rows of y
     if (heads && !heads_done)
         return gemm_f32(ctx, (int64_t)N * T, n_heads, H, y, H, 1, w_head, 1, H, heads, n_heads, b_head, 0, st);
@@ -1649,6 +1651,11 @@ int uav_lstm_wgrad(uav_ctx* ctx, const float* x, const float* keep, const float*
             UAV_REQUIRE(form < 0 || H != DgPack::H || form == want, "uav_lstm_wgrad: this dgates buffer was written as %s but the handle's "
                         "arithmetic mode / debug flags now read %s (they must not change between uav_lstm_bwd and uav_lstm_wgrad)",
                         form ? "fp16 piece chunks" : "f32 rows", want ? "fp16 piece chunks" : "f32 rows");
+            // the f32-rows form below reads h_prev from the stash's slot: refuse a stash whose forward pass left it out
+            UAV_REQUIRE(H != DgPack::H || want || ctx->hslot_form.find(stash) != 0, "uav_lstm_wgrad: this stash was written by "
+                        "uav_lstm_fwd / the stepper on the fp16-split arithmetic, which leaves out its h_prev slot, but the handle's "
+                        "arithmetic mode / debug flags now read that slot (they must not change between the forward pass and "
+                        "uav_lstm_wgrad)");
         }
         if (lstm_h3_dg_packed(H)) {
             if ((I <= 8 || I == H) && !dx) {

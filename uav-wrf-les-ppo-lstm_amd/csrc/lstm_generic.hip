@@ -578,10 +578,15 @@ __global__ __launch_bounds__(EPW * 64) void cell_bwd_h3_kernel(const float* __re
         e = e > 100 ? 100 : (e < -100 ? -100 : e);
     }
     const float sc = __uint_as_float((unsigned)(127 + e) << 23), isc = __uint_as_float((unsigned)(127 - e) << 23);
+    // a row whose gate gradients are all zero stores scale 0, not 1: the weight-gradient product scales every row by
+    // isc / max isc (wgrad_pc.hip), and a 1 from such a row put the real rows of a small-gradient batch (1e-6: isc ~ 2^-33)
+    // below fp16's range -- dW_hh collapsed to zero.  (fmaxf drops NaN: an all-NaN row has m = 0 too, and its NaN pieces
+    // times 0 stay NaN; m = inf keeps isc = 1 and inf / NaN pieces.)
+    const float isw = m > 0.f ? isc : 0.f;
     if (lane == 0) {
         inv_scale[n] = isc * kp;                            // dh_{t-1}: the mask of step t rides on the scale
-        isc_out[n] = isc;                                   // dx_t (the gradient of the step's input), db and dW_ih are not masked
-        if (iscm_out) iscm_out[n] = isc * kp;               // dW_hh = dG^T (y[t-1] keep[t])
+        isc_out[n] = isw;                                   // dx_t (the gradient of the step's input), db and dW_ih are not masked
+        if (iscm_out) iscm_out[n] = isw * kp;               // dW_hh = dG^T (y[t-1] keep[t])
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -885,6 +890,11 @@ int uav_lstm_stepper_begin(uav_ctx* ctx, void* state, const float* w_ih, const f
     return 0;
 }
 
+// the stepper writes a stash one step at a time: its h_prev slot counts as written only if every step since step 0 wrote it
+static void stepper_hslot_record(uav_ctx* ctx, const float* stash, int t, int hslot) {
+    ctx->hslot_form.record(stash, t > 0 && ctx->hslot_form.find(stash) == 0 ? 0 : hslot);
+}
+
 int uav_lstm_stepper_step(uav_ctx* ctx, void* state, const float* x, const void* below, const float* keep_t, int N, int T, int t,
                           int I, int H, float* y, float* stash, float* hn, float* cn, uav_stream stream) {
     UAV_REQUIRE(ctx && state && x && y && stash && hn && cn, "uav_lstm_stepper_step: NULL argument");
@@ -903,6 +913,7 @@ int uav_lstm_stepper_step(uav_ctx* ctx, void* state, const float* x, const void*
     float* cs = (float*)(b + L.cs);
     const dim3 grid((N + 63) / 64, 256 / 64);
     const int hslot = h3_dg_packed(H) ? 0 : 1;
+    stepper_hslot_record(ctx, stash, t, hslot);
     // `below`: the stepper state of the layer below (same N, its H = this I = 256), already stepped to t: its piece
     // planes of h_t (parity (t + 1) & 1, not yet masked) ARE this layer's input in fragment order
     const unsigned short* xp = nullptr;
@@ -954,6 +965,8 @@ int uav_lstm_stepper_step_pair(uav_ctx* ctx, const uav_stepper_call* a, const ua
     StepFwdArgs A, B;
     int ia, ib, rc;
     if ((rc = stepper_args(*a, N, T, H, A, ia)) || (rc = stepper_args(*b, N, T, H, B, ib))) return rc;
+    stepper_hslot_record(ctx, a->stash, a->t, A.hslot);
+    stepper_hslot_record(ctx, b->stash, b->t, B.hslot);
     hipStream_t st = as_stream(stream);
     if (ia == 1 && ib == 8) {                 // (layer 1 of a narrow input, layer 2 on the layer below's planes): the one instantiated pair
         hipLaunchKernelGGL((step_fwd_h3_pair_kernel<256, 1, 8>), dim3((N + 63) / 64, 256 / 64, 2), dim3(256), 0, st, A, B);

@@ -16,7 +16,9 @@
 //                       * the per-(env, step) scales cannot ride on A (its bytes never pass a register): they ride on B --
 //                         B' = h_prev * (isc_k / max isc) is what gets split, exact powers of two, B' within fp16's range because
 //                         |h| < 1; the epilogue multiplies by max isc.  An (env, step) whose gradients are 2^-28 of the largest
-//                         loses relative -- not absolute -- accuracy, as under gemm_h3's one block scale;
+//                         loses relative -- not absolute -- accuracy, as under gemm_h3's one block scale.  Rows whose gate
+//                         gradients are all zero (and rows past N) carry isc = 0, so max isc is that of the rows with gradient:
+//                         a zero row's scale of 1 once sat 2^30 above a batch of 1e-6 gradients and flushed their B' to zero;
 //                       * B: f32 rows -> registers (two slabs ahead) -> split -> LDS piece planes, as gemm_h3_tn8_kernel.
 //                       Split-K over contiguous slab ranges, all tiles of a range on one XCD; deterministic slab reduce.
 // Results differ from the round-4 path (f32 rows through gemm_h3_tn8_kernel) only in where the power-of-two scale is applied.
@@ -216,7 +218,7 @@ __global__ __launch_bounds__(512) void gemm_pc_kernel(const PcArgs a) {
     const int64_t ldb = second ? a.ldb1 : (int64_t)H;
     const float* sc_arr = second ? a.isc : a.iscm;
     const float iscmax = __uint_as_float(*a.iscmax_bits);
-    const float to_block = 1.0f / iscmax;                                   // a power of two: exact
+    const float to_block = iscmax > 0.f ? 1.0f / iscmax : 0.f;             // a power of two: exact (0: no nonzero row at all)
 
     unsigned char* a_lds = pc_lds;
     unsigned short* b_lds = reinterpret_cast<unsigned short*>(pc_lds + A_STAGES * A_STAGE);

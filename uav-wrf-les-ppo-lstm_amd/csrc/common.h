@@ -124,7 +124,7 @@ __device__ __forceinline__ float fast_tanh(float x) {
 
 // ---- split-bf16 ("x6") arithmetic: an f32 value as three bf16 pieces a = p0 + p1 + p2 (8 significand bits each, so
 // the split is exact); products of two split operands keep the six piece products with i + j <= 2 and accumulate them
-// in f32 (v_mfma_f32_16x16x32_bf16).  Error and rate: tools/bf16x6_probe.hip; the argument: lstm.hip, lstm_fwd_x6_kernel.
+// in f32 (v_mfma_f32_16x16x32_bf16).  Error and rate: tools/bf16x6_probe.hip; the argument: lstm.hip, FwdSplitGeom.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void split3(float a, __bf16& p0, __bf16& p1, __bf16& p2) {
     p0 = (__bf16)a;
@@ -149,6 +149,106 @@ __device__ __forceinline__ void split2h(float a, _Float16& p0, _Float16& p1) {
     p1 = (_Float16)((a - (float)p0) * 2048.0f);
 }
 __device__ __forceinline__ unsigned short h_bits(_Float16 v) { return __builtin_bit_cast(unsigned short, v); }
+
+// ---- the two splits as arithmetic policies of the persistent h = 64 / 128 sequence kernels (lstm.hip): the weights are
+// the A operand of a 16x16x32 MFMA, h_t (forward) or the gate gradients (backward) the B operand.  A policy fixes the
+// pieces, the order of the piece products of one K = 32 slab and the accumulator each product goes to -- and so the
+// result bits.  w(q, p) / w(p) is piece p of a weight fragment, a / b / h(p) piece p of the other operand.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct SplitF16x3 {          // UAV_ARITH_FP16X3 (the default): two fp16 pieces, three products
+    typedef _Float16 piece;
+    typedef f16x8 vec;
+    static constexpr int NP = 2;
+    // gate gradients span many binades, fp16 does not: the backward scales each env's by a power of two before the split
+    static constexpr bool BLOCK_SCALE = true;
+    // the backward's dG stores go behind the products (they drain under the partial-sum reduce, not ahead of the MFMAs)
+    static constexpr bool DG_STORES_LATE = true;
+    // the weight pieces take exactly the f32 weights' registers: nothing is parked in LDS
+    static constexpr int fwd_park(int) { return 0; }
+    static constexpr int bwd_park(int) { return 0; }
+    __device__ __forceinline__ static void split(float a, piece (&p)[NP]) { split2h(a, p[0], p[1]); }
+    __device__ __forceinline__ static unsigned short bits(piece v) { return h_bits(v); }
+    __device__ __forceinline__ static f32x4 mma(vec a, vec b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+    // forward, four gates: main products into acc, cross products into acl -- eight independent accumulators
+    template <class W>
+    __device__ __forceinline__ static void gates_slab(f32x4 (&acc)[4], f32x4 (&acl)[4], W w, const vec (&a)[NP]) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acl[q] = mma(w(q, 1), a[0], acl[q]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = mma(w(q, 0), a[0], acc[q]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acl[q] = mma(w(q, 0), a[1], acl[q]);
+    }
+    template <class W, class B>
+    __device__ __forceinline__ static void head_slab(f32x4& ha, f32x4& hb, W w, B h) {
+        hb = mma(w(1), h(0), hb);
+        hb = mma(w(0), h(1), hb);
+        ha = mma(w(0), h(0), ha);
+    }
+    template <class V> __device__ __forceinline__ static V sum(V acc, V acl) { return acc + acl * H3_LO; }
+    // backward, one partial tile: the same three products over two accumulators
+    template <class W>
+    __device__ __forceinline__ static void tile_slab(f32x4& a0, f32x4& a1, W w, const vec (&b)[NP]) {
+        a1 = mma(w(1), b[0], a1);
+        a0 = mma(w(0), b[0], a0);
+        a1 = mma(w(0), b[1], a1);
+    }
+    __device__ __forceinline__ static f32x4 tile_sum(f32x4 a0, f32x4 a1) { return a0 + a1 * H3_LO; }
+};
+
+struct SplitBf16x6 {         // UAV_ARITH_BF16X6: three bf16 pieces, six products, f32's exponent range
+    typedef __bf16 piece;
+    typedef bf16x8 vec;
+    static constexpr int NP = 3;
+    static constexpr bool BLOCK_SCALE = false;
+    static constexpr bool DG_STORES_LATE = false;
+    // three bf16 pieces of W_hh are 1.5x its f32 size = 3/4 of the CU's register file at H = 128: there the smallest
+    // piece of the first 3 gates (forward) / the first 6 (tile, slab) items (backward) lives in a wave-private LDS slab
+    static constexpr int fwd_park(int H) { return H >= 128 ? 3 : 0; }
+    static constexpr int bwd_park(int H) { return H >= 128 ? 6 : 0; }
+    __device__ __forceinline__ static void split(float a, piece (&p)[NP]) { split3(a, p[0], p[1], p[2]); }
+    __device__ __forceinline__ static unsigned short bits(piece v) { return bf_bits(v); }
+    __device__ __forceinline__ static f32x4 mma(vec a, vec b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+    // forward, four gates: the six products with i + j <= 2, smallest first, one accumulator per gate -- four
+    // independent accumulators between dependent MFMAs
+    template <class W>
+    __device__ __forceinline__ static void gates_slab(f32x4 (&acc)[4], f32x4 (&)[4], W w, const vec (&a)[NP]) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = mma(w(q, 0), a[2], acc[q]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = mma(w(q, 1), a[1], acc[q]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = mma(w(q, 2), a[0], acc[q]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = mma(w(q, 0), a[1], acc[q]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = mma(w(q, 1), a[0], acc[q]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = mma(w(q, 0), a[0], acc[q]);
+    }
+    template <class W, class B>
+    __device__ __forceinline__ static void head_slab(f32x4& ha, f32x4&, W w, B h) {
+        ha = mma(w(0), h(2), ha);
+        ha = mma(w(1), h(1), ha);
+        ha = mma(w(2), h(0), ha);
+        ha = mma(w(0), h(1), ha);
+        ha = mma(w(1), h(0), ha);
+        ha = mma(w(0), h(0), ha);
+    }
+    template <class V> __device__ __forceinline__ static V sum(V acc, V) { return acc; }
+    // backward, one partial tile: the same six products alternating between two accumulators
+    template <class W>
+    __device__ __forceinline__ static void tile_slab(f32x4& a0, f32x4& a1, W w, const vec (&b)[NP]) {
+        a0 = mma(w(0), b[2], a0);
+        a1 = mma(w(1), b[1], a1);
+        a0 = mma(w(2), b[0], a0);
+        a1 = mma(w(0), b[1], a1);
+        a0 = mma(w(1), b[0], a0);
+        a1 = mma(w(0), b[0], a1);
+    }
+    __device__ __forceinline__ static f32x4 tile_sum(f32x4 a0, f32x4 a1) { return a0 + a1; }
+};
 
 // ---- gate gradients of the h = 256 fp16-split step path, stored ONCE (round 5): the `dgates` buffer that travels from
 // uav_lstm_bwd / _bwd_stack to uav_lstm_wgrad holds what the BPTT's recurrent product consumes -- the two fp16 pieces of

@@ -11,11 +11,15 @@
 //   * the i,f,g,o pre-activations of one (env, unit) land in ONE lane's accumulators, so the gate pointwise and the
 //     cell state never leave registers; h_t / the gate gradients are exchanged through LDS, one or two barriers a step.
 // Kernel families in this file (dispatch: launch_fwd, lstm_bwd_seq):
-//   DEFAULT  lstm_fwd_h3_kernel, lstm_bwd_h3k_kernel: the matrix products on the fp16 pipe at f32 accuracy (two-piece
-//            operand split, three products, common.h split2h; gate gradients block-scaled per env), weights-as-A
-//            orientation (a lane owns one env and four consecutive units: dwordx4 stores), stash by LDS-DMA in the backward;
-//   BF16 SPLIT lstm_fwd_x6_kernel, lstm_bwd_x6k_kernel: the same kernels with a three-piece bf16 split and six
-//            products (f32's exponent range: no operand limits, twice the matrix work); uav_set_lstm_arith(UAV_ARITH_BF16X6);
+//   SPLIT    one forward body (lstm_fwd_split) and one backward body (lstm_bwd_split), templated on the arithmetic of
+//            their matrix products: the 16-bit matrix pipe at f32 accuracy with every operand split into pieces
+//            (common.h: SplitF16x3, SplitBf16x6).  Weights-as-A orientation (a lane owns one env and four consecutive
+//            units: dwordx4 stores), the head product fused into the forward, stash by LDS-DMA and the K split over the
+//            waves in the backward.  Two arithmetics, each with its own entry points:
+//              fp16 split (DEFAULT): lstm_fwd_h3_kernel, lstm_bwd_h3k_kernel -- two pieces, three products; the gate
+//                gradients are block-scaled per env;
+//              bf16 split: lstm_fwd_x6_kernel, lstm_bwd_x6k_kernel -- three pieces, six products (f32's exponent range:
+//                no operand limits, twice the matrix work); uav_set_lstm_arith(UAV_ARITH_BF16X6);
 //   EXACT-F32 lstm_fwd_kernel, lstm_bwd_kernel (also the plain-dy backward of stacked layers): v_mfma_f32_16x16x4_f32
 //            with 128 weight VGPRs per lane; uav_set_lstm_arith(UAV_ARITH_F32_MFMA).
 //   (Earlier generations -- an output-split bf16 backward exchanging dG through three LDS planes, an LDS-DMA form of
@@ -25,9 +29,8 @@
 //   * the K=I<=8 input projection rides along as two exact-f32 MFMA k-steps; wider inputs (stacked layers) use a
 //     time-batched GEMM into the stash first.
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 int gemm_f32(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k,
              const float* B, int64_t sb_k, int64_t sb_n, float* C, int64_t ldc, const float* bias,
@@ -66,9 +69,6 @@ int lstm_wgrad_fused(uav_ctx* ctx, const float* dgates, const float* y_prev_src,
                      float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, hipStream_t st);
 
 constexpr int MT = 16;      // env rows per workgroup (MFMA M)
-// UAV_LSTM_F32_MFMA=1 selects the exact v_mfma_f32_16x16x4_f32 kernels (the A/B reference of the split ones)
-static bool f32_mfma_requested() { return uav_want_f32_mfma(); }   // the handle's mode (uav_set_lstm_arith)
-static bool bf16x6_requested() { return uav_want_bf16x6(); }        // the predecessor of the fp16 split
 constexpr int TC = 32;      // time steps staged per chunk
 
 #define sigmoidf_ fast_sigmoid
@@ -237,32 +237,33 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_kernel(
     }
 }
 
-// ------------------------------------------------------------------------- forward, split-bf16 MFMA
-// Same recurrence, but the h W_hh^T product runs on the bf16 matrix pipe at f32 accuracy: every f32 operand is
-// split into three bf16 pieces (a = a0 + a1 + a2, 8 significand bits each, so the split is exact) and the six
-// piece products a_i b_j with i + j <= 2 are accumulated in f32 by v_mfma_f32_16x16x32_bf16.  The dropped
-// products are below 2^-24 |a b|, i.e. under the rounding of the f32 accumulation itself: measured error equals
-// the exact-f32 MFMA chain's (tools/bf16x6_probe.hip: 2.69e-7 vs 2.75e-7 on a K=128 dot product) at 2.6x its
-// rate (6 x 16 cycles per K=32 slab against 8 x 32).  W_hh pieces stay in VGPRs (192 at H=128); h_t is split
-// once by the lane that produces it and exchanged through three bf16 LDS planes.
-
-
-template <int H>
-struct FwdX6Geom {
+// ---------------------------------------------------------------------------- forward, split MFMA (fp16 / bf16 pieces)
+// Same recurrence, but the h W_hh^T product runs on the 16-bit matrix pipe at f32 accuracy: W_hh and h_t are carried as
+// P::NP pieces each and the piece products accumulate in f32 (common.h: SplitF16x3, SplitBf16x6).  h_t is split once by
+// the lane that produces it and exchanged through NP piece planes in LDS.
+//   fp16 split (default): two pieces, three products per K = 32 slab; main and cross products accumulate separately and
+//     are combined once per step.  Half the matrix instructions of the bf16 split, the weight pieces take exactly the f32
+//     weights' 128 VGPRs (no LDS slab) -- and a smaller error (tools/f16x3_probe.hip).  h is in (-1, 1) and the weights
+//     are O(1), far inside fp16's range; values below its normal range lose relative, not absolute, accuracy (absolute
+//     error <= 2^-36), which is what a dot product needs.
+//   bf16 split: three pieces (a = a0 + a1 + a2, 8 significand bits each, so the split is exact) and the six piece
+//     products a_i b_j with i + j <= 2.  The dropped products are below 2^-24 |a b|, i.e. under the rounding of the f32
+//     accumulation itself: measured error equals the exact-f32 MFMA chain's (tools/bf16x6_probe.hip: 2.69e-7 vs 2.75e-7
+//     on a K=128 dot product) at 2.6x its rate (6 x 16 cycles per K=32 slab against 8 x 32).  W_hh pieces take 192 VGPRs
+//     at H=128, so part of them is parked in LDS (SplitBf16x6::fwd_park).
+template <class P, int H>
+struct FwdSplitGeom {
     static constexpr int NS = H / 32;          // K = 32 slabs over the hidden dimension
-    static constexpr int RS = H + 8;           // bf16 elements per padded row: 16 lanes x ds_read_b128 conflict-free
+    static constexpr int RS = H + 8;           // 16-bit elements per padded row: 16 lanes x ds_read_b128 conflict-free
     static constexpr int PLANE = MT * RS;
-    // three bf16 pieces of W_hh are 1.5x its f32 size = 3/4 of the CU's register file at H=128: the smallest
-    // piece of QL of the four gates lives in a wave-private LDS slab instead (read back as lane-contiguous b128)
-    static constexpr int QL = (H >= 128) ? 3 : 0;
-    static constexpr int WPARK = QL * NS * 64 * 8;                       // bf16 elements per wave
+    static constexpr int QL = P::fwd_park(H);                            // gates whose smallest weight piece is in LDS
+    static constexpr int WPARK = QL * NS * 64 * 8;                       // 16-bit elements per wave
     static constexpr int TCX = 8;                                        // steps of x / keep staged per chunk
     static constexpr int XPT = (MT * TCX * 8 + H * 4 - 1) / (H * 4);     // staged x elements per thread
     static constexpr int HPL = 8 * RS;                                   // one piece plane of the (<= 8) head weight rows
-    static constexpr size_t LDS = (2 * 3 * PLANE + (H / 16) * WPARK + 3 * HPL) * sizeof(unsigned short) +
+    static constexpr size_t LDS = (2 * P::NP * PLANE + (H / 16) * WPARK + P::NP * HPL) * sizeof(unsigned short) +
                                   (2 * TCX * MT * 8 + 2 * TCX * MT + (H / 16) * 8 * 64 + 4 * H + 8) * sizeof(float);
 };
-
 #ifdef UAV_X6_PROFILE
 // phase timing of the split-bf16 forward (instrumented build only, -DUAV_X6_PROFILE): s_memtime at four marks
 // per step, summed over the sequence by wave 0 and the last wave of workgroup 0
@@ -290,24 +291,26 @@ extern "C" int uav_x6_prof_read(unsigned long long* out) {
 // stash values leave as dwordx4 stores (6 per step instead of 24 dword stores -- the vector-memory issue rate,
 // 16 cycles per wave-instruction, paced the step as much as the MFMAs did), h_t is parked with one ds_write_b64
 // per piece, and keep is one value per lane.
-template <int H, bool FUSE_X>
-__global__ __launch_bounds__(H * 4) void lstm_fwd_x6_kernel(
+template <class P, int H, bool FUSE_X>
+__device__ __forceinline__ void lstm_fwd_split(
     const float* __restrict__ x, const float* __restrict__ keep, const float* __restrict__ h0,
     const float* __restrict__ c0, const float* __restrict__ w_ih, const float* __restrict__ w_hh,
     const float* __restrict__ b_ih, const float* __restrict__ b_hh, int N, int T, int I,
     float* __restrict__ y, float* __restrict__ hn, float* __restrict__ cn, float* __restrict__ stash,
     const float* __restrict__ w_head, const float* __restrict__ b_head, int NHD, float* __restrict__ heads) {
-    using G = FwdX6Geom<H>;
-    constexpr int NS = G::NS, RS = G::RS, PLANE = G::PLANE, QL = G::QL, WPARK = G::WPARK, TC = G::TCX, XPT = G::XPT;
-    constexpr int NT = H * 4, HPL = G::HPL, NW = H / 16;
+    using G = FwdSplitGeom<P, H>;
+    using vec = typename P::vec;
+    using piece = typename P::piece;
+    constexpr int NP = P::NP, NS = G::NS, RS = G::RS, PLANE = G::PLANE, QL = G::QL, WPARK = G::WPARK, TC = G::TCX;
+    constexpr int XPT = G::XPT, NT = H * 4, HPL = G::HPL, NW = H / 16;
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    unsigned short* hpl = reinterpret_cast<unsigned short*>(smem);       // [2][3 pieces][MT][RS] bf16
-    unsigned short* wpark = hpl + 2 * 3 * PLANE;                         // [waves][QL][NS][64 lanes][8] bf16
+    unsigned short* hpl = reinterpret_cast<unsigned short*>(smem);       // [2][NP pieces][MT][RS]
+    unsigned short* wpark = hpl + 2 * NP * PLANE;                        // [waves][QL][NS][64 lanes][8]
     float* xbuf = reinterpret_cast<float*>(wpark + (H / 16) * WPARK);    // [2][TC][MT][8]
     float* kbuf = xbuf + 2 * TC * MT * 8;                                // [2][TC][MT]: keep[t + 1] of the chunk's steps
     float* wxl = kbuf + 2 * TC * MT;                                     // [waves][4 gates][2 k-steps][64 lanes]
     float* bl = wxl + (H / 16) * 512;                                    // [4H] b_ih + b_hh | [8] head bias
-    unsigned short* whp = reinterpret_cast<unsigned short*>(bl + 4 * H + 8);   // [3 pieces][8 heads][RS] bf16
+    unsigned short* whp = reinterpret_cast<unsigned short*>(bl + 4 * H + 8);   // [NP pieces][8 heads][RS]
 
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int j = lane & 15, kq = lane >> 4;
@@ -317,9 +320,10 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_x6_kernel(
     const int n = min(n0 + j, N - 1);
     const bool live = n0 + j < N;
 
-    // A fragments of 16x16x32: lane (j, kq) holds k = 32 s + 8 kq .. + 7 of unit uw, per gate q and piece p
-    bf16x8 wb[4][NS][2], wb2[4 - QL][NS];
-    bf16x8* const wpk = reinterpret_cast<bf16x8*>(wpark + w * WPARK) + lane;      // + (q * NS + s) * 64
+    // A fragments of 16x16x32: lane (j, kq) holds k = 32 s + 8 kq .. + 7 of unit uw, per gate q and piece p; the
+    // smallest piece of the first QL gates lives in this wave's LDS slab instead (read back as lane-contiguous b128)
+    vec wb[4][NS][NP];
+    vec* const wpk = reinterpret_cast<vec*>(wpark + w * WPARK) + lane;  // + (q * NS + s) * 64
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
@@ -327,15 +331,14 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_x6_kernel(
             const float* src = w_hh + (size_t)(q * H + uw) * H + 32 * s + 8 * kq;
             const float4 v0 = *reinterpret_cast<const float4*>(src), v1 = *reinterpret_cast<const float4*>(src + 4);
             const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-            bf16x8 p2v;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                __bf16 p0, p1, p2;
-                split3(v[i], p0, p1, p2);
-                wb[q][s][0][i] = p0; wb[q][s][1][i] = p1; p2v[i] = p2;
+                piece p[NP];
+                P::split(v[i], p);
+#pragma unroll
+                for (int pc = 0; pc < NP; ++pc) wb[q][s][pc][i] = p[pc];
             }
-            if (q < QL) wpk[(q * NS + s) * 64] = p2v;
-            else wb2[q < QL ? 0 : q - QL][s] = p2v;
+            if (q < QL) wpk[(q * NS + s) * 64] = wb[q][s][NP - 1];
         }
     float* const wxw = wxl + w * 512 + lane;                             // this lane's W_ih fragments: + (2 q + s) * 64
     if (FUSE_X) {
@@ -348,13 +351,14 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_x6_kernel(
             }
         for (int idx = threadIdx.x; idx < 4 * H; idx += NT) bl[idx] = b_ih[idx] + b_hh[idx];
     }
-    if (heads) {                                                         // actor / critic head rows as bf16 piece planes
+    if (heads) {                                                         // actor / critic head rows as piece planes
         for (int idx = threadIdx.x; idx < 8 * H; idx += NT) {
             const int hdx = idx / H, uu = idx % H;
-            __bf16 p0, p1, p2;
-            split3((hdx < NHD) ? w_head[(size_t)hdx * H + uu] : 0.f, p0, p1, p2);
+            piece p[NP];
+            P::split((hdx < NHD) ? w_head[(size_t)hdx * H + uu] : 0.f, p);
             unsigned short* d = whp + hdx * RS + uu;
-            d[0] = bf_bits(p0); d[HPL] = bf_bits(p1); d[2 * HPL] = bf_bits(p2);
+#pragma unroll
+            for (int pc = 0; pc < NP; ++pc) d[pc * HPL] = P::bits(p[pc]);
         }
         if (threadIdx.x < 8) bl[4 * H + threadIdx.x] = (int)threadIdx.x < NHD ? b_head[threadIdx.x] : 0.f;
     }
@@ -362,38 +366,33 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_x6_kernel(
     // heads[env][t][NHD].  One wave does it, beside its own recurrent MFMAs of the next step; the loss then reads
     // NHD floats per sample instead of the H floats of y.
     auto emit_heads = [&](int buf, int t) {
-        f32x4 ha = {0.f, 0.f, 0.f, 0.f};
-        const unsigned short* hrow = hpl + buf * 3 * PLANE + j * RS + 8 * kq;
+        f32x4 ha = {0.f, 0.f, 0.f, 0.f}, hb = ha;
+        const unsigned short* hrow = hpl + buf * NP * PLANE + j * RS + 8 * kq;
         const unsigned short* wrow = whp + (j & 7) * RS + 8 * kq;
-        auto hp = [&](int pc, int s) { return *reinterpret_cast<const bf16x8*>(hrow + pc * PLANE + 32 * s); };
-        auto wp = [&](int pc, int s) { return *reinterpret_cast<const bf16x8*>(wrow + pc * HPL + 32 * s); };
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-            ha = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp(0, s), hp(2, s), ha, 0, 0, 0);
-            ha = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp(1, s), hp(1, s), ha, 0, 0, 0);
-            ha = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp(2, s), hp(0, s), ha, 0, 0, 0);
-            ha = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp(0, s), hp(1, s), ha, 0, 0, 0);
-            ha = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp(1, s), hp(0, s), ha, 0, 0, 0);
-            ha = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp(0, s), hp(0, s), ha, 0, 0, 0);
+            P::head_slab(ha, hb, [&](int pc) { return *reinterpret_cast<const vec*>(wrow + pc * HPL + 32 * s); },
+                         [&](int pc) { return *reinterpret_cast<const vec*>(hrow + pc * PLANE + 32 * s); });
             asm volatile("" ::: "memory");               // one slab's fragments at a time
         }
         if (live && kq < 2) {
             float* dst = heads + ((size_t)n * T + t) * NHD;
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-                if (4 * kq + r < NHD) dst[4 * kq + r] = ha[r] + bl[4 * H + 4 * kq + r];
+                if (4 * kq + r < NHD) dst[4 * kq + r] = P::sum(ha[r], hb[r]) + bl[4 * H + 4 * kq + r];
         }
     };
     auto put_h = [&](unsigned short* plane0, const float (&hv)[4]) {     // split and park h[env j][uo .. uo+3]
-        unsigned short b[3][4];
+        unsigned short b[NP][4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            __bf16 p0, p1, p2;
-            split3(hv[r], p0, p1, p2);
-            b[0][r] = bf_bits(p0); b[1][r] = bf_bits(p1); b[2][r] = bf_bits(p2);
+            piece p[NP];
+            P::split(hv[r], p);
+#pragma unroll
+            for (int pc = 0; pc < NP; ++pc) b[pc][r] = P::bits(p[pc]);
         }
 #pragma unroll
-        for (int pc = 0; pc < 3; ++pc) {
+        for (int pc = 0; pc < NP; ++pc) {
             uint2 v;
             v.x = (unsigned)b[pc][0] | ((unsigned)b[pc][1] << 16);
             v.y = (unsigned)b[pc][2] | ((unsigned)b[pc][3] << 16);
@@ -460,37 +459,23 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_x6_kernel(
             if (heads && w == NW - 1 && t > 0) emit_heads(cur, t - 1);   // heads of h_{t-1}, while no accumulator is live
             // the planes hold h_{t-1} UNMASKED (the heads need it so); the episode mask k_t is a per-env scalar, so it
             // is applied to the finished h-part of the accumulator: acc = k_t (W_hh h_{t-1}) + bias + W_ih x_t
-            f32x4 acc[4];
+            f32x4 acc[4], acl[4];                                         // the policy's two accumulators per gate
 #pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const unsigned short* hrow = hpl + cur * 3 * PLANE + j * RS + 8 * kq;
+            for (int q = 0; q < 4; ++q) acc[q] = acl[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const unsigned short* hrow = hpl + cur * NP * PLANE + j * RS + 8 * kq;
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
-                const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(hrow + 32 * s);
-                const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(hrow + PLANE + 32 * s);
-                const bf16x8 a2 = *reinterpret_cast<const bf16x8*>(hrow + 2 * PLANE + 32 * s);
-                // smallest products first; four independent accumulators between dependent MFMAs
+                vec a[NP];
 #pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[q][s][0], a2, acc[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[q][s][1], a1, acc[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bf16x8 b2 = (q < QL) ? wpk[(q * NS + s) * 64] : wb2[q < QL ? 0 : q - QL][s];
-                    acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b2, a0, acc[q], 0, 0, 0);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[q][s][0], a1, acc[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[q][s][1], a0, acc[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wb[q][s][0], a0, acc[q], 0, 0, 0);
+                for (int pc = 0; pc < NP; ++pc) a[pc] = *reinterpret_cast<const vec*>(hrow + pc * PLANE + 32 * s);
+                auto wf = [&](int q, int p) { return (p == NP - 1 && q < QL) ? wpk[(q * NS + s) * 64] : wb[q][s][p]; };
+                P::gates_slab(acc, acl, wf, a);
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const float4 v = FUSE_X ? *reinterpret_cast<const float4*>(bl + q * H + uo)
                                         : *reinterpret_cast<const float4*>(stash + row * (6 * H) + q * H + uo);
-                acc[q] = acc[q] * kcur + f32x4{v.x, v.y, v.z, v.w};
+                acc[q] = P::sum(acc[q], acl[q]) * kcur + f32x4{v.x, v.y, v.z, v.w};
             }
             if (FUSE_X) {       // K = I <= 8 input projection: two exact-f32 k-steps
                 const float2 ax = *reinterpret_cast<const float2*>(&xbuf[((xb * TC + tt) * MT + j) * 8 + 2 * kq]);
@@ -504,14 +489,18 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_x6_kernel(
             X6_PROF_MARK(1);
             const float kn = kbuf[(xb * TC + tt) * MT + j];              // keep of step t+1 (1 past the end)
             // the stash stores are issued as soon as their values exist, so the write stream starts under the rest of
-            // the gate math instead of in one burst before the barrier
+            // the gate math instead of in one burst before the barrier.
+            // c = f c_prev + i g fuses one of its two products into an fma.  Which one was left to -ffp-contract=fast, and
+            // the choice (it changes the last bit of c, and so the whole sequence) followed unrelated code around it; it is
+            // spelled out as the compiler had made it (forward: by H; backward: f c_prev), so the bits are the source's.
             float gi[4], gf[4], gg[4], go[4], cp[4], hh[4], hm[4], cc[4];
             float* sp = stash + row * (6 * H) + uo;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 gi[r] = sigmoidf_(acc[0][r]); gf[r] = sigmoidf_(acc[1][r]); gg[r] = tanhf_(acc[2][r]);
                 cp[r] = c_reg[r];
-                cc[r] = gf[r] * cp[r] + gi[r] * gg[r];
+                cc[r] = H >= 128 ? __builtin_fmaf(gi[r], gg[r], gf[r] * cp[r])
+                                 : __builtin_fmaf(gf[r], cp[r], gi[r] * gg[r]);
             }
             if (live && stash) {
                 *reinterpret_cast<float4*>(sp) = float4{gi[0], gi[1], gi[2], gi[3]};
@@ -526,7 +515,7 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_x6_kernel(
                 hm[r] = hh[r] * kn;
                 c_reg[r] = (t == T - 1) ? cc[r] : cc[r] * kn;            // cn is the unmasked final cell state
             }
-            put_h(hpl + (cur ^ 1) * 3 * PLANE, hh);
+            put_h(hpl + (cur ^ 1) * NP * PLANE, hh);
             kcur = kn;
             if (live) {
                 *reinterpret_cast<float4*>(y + row * H + uo) = float4{hh[0], hh[1], hh[2], hh[3]};
@@ -554,26 +543,7 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_x6_kernel(
     X6_PROF_FLUSH();
 }
 
-
-// ------------------------------------------------------------------------- forward, split-fp16 MFMA ("h3")
-// The same kernel with the recurrent product as THREE fp16 MFMA products per K = 32 slab (common.h, split2h): W_hh and
-// h_t are carried as two fp16 pieces each, main and cross products accumulate separately and are combined once per step.
-// Half the matrix instructions of the bf16 split, the weight pieces take exactly the f32 weights' 128 VGPRs (no LDS
-// slab), two h planes instead of three -- and a smaller error (tools/f16x3_probe.hip).  h is in (-1, 1) and the
-// weights are O(1), far inside fp16's range; values below its normal range lose relative, not absolute, accuracy
-// (absolute error <= 2^-36), which is what a dot product needs.
-template <int H>
-struct FwdH3Geom {
-    static constexpr int NS = H / 32;
-    static constexpr int RS = H + 8;
-    static constexpr int PLANE = MT * RS;
-    static constexpr int TCX = 8;
-    static constexpr int XPT = (MT * TCX * 8 + H * 4 - 1) / (H * 4);
-    static constexpr int HPL = 8 * RS;
-    static constexpr size_t LDS = (2 * 2 * PLANE + 2 * HPL) * sizeof(unsigned short) +
-                                  (2 * TCX * MT * 8 + 2 * TCX * MT + (H / 16) * 8 * 64 + 4 * H + 8) * sizeof(float);
-};
-
+// the entry points, one per arithmetic: profiles and bench.py find the kernels by these names in a kernel trace
 template <int H, bool FUSE_X>
 __global__ __launch_bounds__(H * 4) void lstm_fwd_h3_kernel(
     const float* __restrict__ x, const float* __restrict__ keep, const float* __restrict__ h0,
@@ -581,240 +551,18 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_h3_kernel(
     const float* __restrict__ b_ih, const float* __restrict__ b_hh, int N, int T, int I,
     float* __restrict__ y, float* __restrict__ hn, float* __restrict__ cn, float* __restrict__ stash,
     const float* __restrict__ w_head, const float* __restrict__ b_head, int NHD, float* __restrict__ heads) {
-    using G = FwdH3Geom<H>;
-    constexpr int NS = G::NS, RS = G::RS, PLANE = G::PLANE, TC = G::TCX, XPT = G::XPT;
-    constexpr int NT = H * 4, HPL = G::HPL, NW = H / 16;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    unsigned short* hpl = reinterpret_cast<unsigned short*>(smem);       // [2][2 pieces][MT][RS] fp16
-    float* xbuf = reinterpret_cast<float*>(hpl + 2 * 2 * PLANE);         // [2][TC][MT][8]
-    float* kbuf = xbuf + 2 * TC * MT * 8;                                // [2][TC][MT]: keep[t + 1] of the chunk's steps
-    float* wxl = kbuf + 2 * TC * MT;                                     // [waves][4 gates][2 k-steps][64 lanes]
-    float* bl = wxl + (H / 16) * 512;                                    // [4H] b_ih + b_hh | [8] head bias
-    unsigned short* whp = reinterpret_cast<unsigned short*>(bl + 4 * H + 8);   // [2 pieces][8 heads][RS] fp16
-
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int j = lane & 15, kq = lane >> 4;
-    const int uw = 16 * w + j;                 // unit whose weight row this lane holds (A operand row)
-    const int uo = 16 * w + 4 * kq;            // first of this lane's four output units; its env is j
-    const int n0 = blockIdx.x * MT;
-    const int n = min(n0 + j, N - 1);
-    const bool live = n0 + j < N;
-
-    // A fragments of 16x16x32: lane (j, kq) holds k = 32 s + 8 kq .. + 7 of unit uw, per gate q and piece p
-    f16x8 wb[4][NS][2];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            const float* src = w_hh + (size_t)(q * H + uw) * H + 32 * s + 8 * kq;
-            const float4 v0 = *reinterpret_cast<const float4*>(src), v1 = *reinterpret_cast<const float4*>(src + 4);
-            const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                _Float16 p0, p1;
-                split2h(v[i], p0, p1);
-                wb[q][s][0][i] = p0; wb[q][s][1][i] = p1;
-            }
-        }
-    float* const wxw = wxl + w * 512 + lane;                             // this lane's W_ih fragments: + (2 q + s) * 64
-    if (FUSE_X) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int k = 2 * kq + s;
-                wxw[(2 * q + s) * 64] = (k < I) ? w_ih[(size_t)(q * H + uw) * I + k] : 0.f;
-            }
-        for (int idx = threadIdx.x; idx < 4 * H; idx += NT) bl[idx] = b_ih[idx] + b_hh[idx];
-    }
-    if (heads) {                                                         // actor / critic head rows as fp16 piece planes
-        for (int idx = threadIdx.x; idx < 8 * H; idx += NT) {
-            const int hdx = idx / H, uu = idx % H;
-            _Float16 p0, p1;
-            split2h((hdx < NHD) ? w_head[(size_t)hdx * H + uu] : 0.f, p0, p1);
-            unsigned short* d = whp + hdx * RS + uu;
-            d[0] = h_bits(p0); d[HPL] = h_bits(p1);
-        }
-        if (threadIdx.x < 8) bl[4 * H + threadIdx.x] = (int)threadIdx.x < NHD ? b_head[threadIdx.x] : 0.f;
-    }
-    // heads of the h held in plane set `buf` (= h_t, UNMASKED): D[head 4kq + r][env j] = W_head h^T + b, stored to
-    // heads[env][t][NHD].  One wave does it, beside its own recurrent MFMAs of the next step.
-    auto emit_heads = [&](int buf, int t) {
-        f32x4 ha = {0.f, 0.f, 0.f, 0.f}, hb = ha;
-        const unsigned short* hrow = hpl + buf * 2 * PLANE + j * RS + 8 * kq;
-        const unsigned short* wrow = whp + (j & 7) * RS + 8 * kq;
-        auto hp = [&](int pc, int s) { return *reinterpret_cast<const f16x8*>(hrow + pc * PLANE + 32 * s); };
-        auto wp = [&](int pc, int s) { return *reinterpret_cast<const f16x8*>(wrow + pc * HPL + 32 * s); };
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            hb = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp(1, s), hp(0, s), hb, 0, 0, 0);
-            hb = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp(0, s), hp(1, s), hb, 0, 0, 0);
-            ha = __builtin_amdgcn_mfma_f32_16x16x32_f16(wp(0, s), hp(0, s), ha, 0, 0, 0);
-            asm volatile("" ::: "memory");               // one slab's fragments at a time
-        }
-        if (live && kq < 2) {
-            float* dst = heads + ((size_t)n * T + t) * NHD;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (4 * kq + r < NHD) dst[4 * kq + r] = (ha[r] + H3_LO * hb[r]) + bl[4 * H + 4 * kq + r];
-        }
-    };
-    auto put_h = [&](unsigned short* plane0, const float (&hv)[4]) {     // split and park h[env j][uo .. uo+3]
-        unsigned short b[2][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            _Float16 p0, p1;
-            split2h(hv[r], p0, p1);
-            b[0][r] = h_bits(p0); b[1][r] = h_bits(p1);
-        }
-#pragma unroll
-        for (int pc = 0; pc < 2; ++pc) {
-            uint2 v;
-            v.x = (unsigned)b[pc][0] | ((unsigned)b[pc][1] << 16);
-            v.y = (unsigned)b[pc][2] | ((unsigned)b[pc][3] << 16);
-            *reinterpret_cast<uint2*>(plane0 + pc * PLANE + j * RS + uo) = v;
-        }
-    };
-
-    // chunk staging through registers: chunk c + 1 is loaded while chunk c runs, committed to the other buffer
-    float xr[XPT], kr = 1.f;
-    auto stage_load = [&](int t0) {
-        if (FUSE_X) {
-#pragma unroll
-            for (int i = 0; i < XPT; ++i) {
-                const int idx = threadIdx.x + i * NT;                    // (e, tt, f) with f fastest
-                const int e = min(idx / (TC * 8), MT - 1), tt = (idx >> 3) % TC, f = idx & 7;
-                const int ne = min(n0 + e, N - 1), t = min(t0 + tt, T - 1);
-                xr[i] = (f < I) ? x[((size_t)ne * T + t) * I + f] : 0.f;
-            }
-        }
-        if (threadIdx.x < TC * MT) {
-            const int e = threadIdx.x / TC, tt = threadIdx.x % TC;
-            const int ne = min(n0 + e, N - 1), t = t0 + tt + 1;
-            kr = (keep && t < T) ? keep[(size_t)ne * T + t] : 1.f;
-        }
-    };
-    auto stage_commit = [&](int buf) {
-        if (FUSE_X) {
-#pragma unroll
-            for (int i = 0; i < XPT; ++i) {
-                const int idx = threadIdx.x + i * NT;
-                const int e = idx / (TC * 8), tt = (idx >> 3) % TC, f = idx & 7;
-                if (e < MT) xbuf[((buf * TC + tt) * MT + e) * 8 + f] = xr[i];
-            }
-        }
-        if (threadIdx.x < TC * MT) kbuf[(buf * TC + threadIdx.x % TC) * MT + threadIdx.x / TC] = kr;
-    };
-
-    float c_reg[4];
-    {
-        const float k0 = keep ? keep[(size_t)n * T] : 1.f;
-        const float4 cv = *reinterpret_cast<const float4*>(c0 + (size_t)n * H + uo);
-        const float4 hv4 = *reinterpret_cast<const float4*>(h0 + (size_t)n * H + uo);
-        c_reg[0] = cv.x * k0; c_reg[1] = cv.y * k0; c_reg[2] = cv.z * k0; c_reg[3] = cv.w * k0;
-        const float hv[4] = {hv4.x * k0, hv4.y * k0, hv4.z * k0, hv4.w * k0};
-        put_h(hpl, hv);
-        if (stash && I > 6 && live)                                      // h_prev of step 0 (generic wgrad path)
-            *reinterpret_cast<float4*>(stash + ((size_t)n * T) * (6 * H) + 5 * H + uo) = float4{hv[0], hv[1], hv[2], hv[3]};
-    }
-    stage_load(0);
-    stage_commit(0);
-    int cur = 0;
-    float kcur = 1.f;            // keep of the step about to run (the mask on the incoming h); h0 is masked above
-    X6_PROF_DECL;
-    lds_barrier();
-
-    const int nchunk = (T + TC - 1) / TC;
-    for (int ch = 0; ch < nchunk; ++ch) {
-        const int t0 = ch * TC, tc = min(TC, T - t0), xb = ch & 1;
-        if (ch + 1 < nchunk) stage_load(t0 + TC);
-        for (int tt = 0; tt < tc; ++tt) {
-            const int t = t0 + tt;
-            const size_t row = (size_t)n * T + t;
-            X6_PROF_MARK(0);
-            if (heads && w == NW - 1 && t > 0) emit_heads(cur, t - 1);   // heads of h_{t-1}, while no accumulator is live
-            // the planes hold h_{t-1} UNMASKED (the heads need it so); the episode mask k_t is a per-env scalar, so it
-            // is applied to the finished h-part of the accumulator: acc = k_t (W_hh h_{t-1}) + bias + W_ih x_t
-            f32x4 acc[4], acl[4];                                         // main products | cross products (x 2^-11)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q] = acl[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const unsigned short* hrow = hpl + cur * 2 * PLANE + j * RS + 8 * kq;
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const f16x8 a0 = *reinterpret_cast<const f16x8*>(hrow + 32 * s);
-                const f16x8 a1 = *reinterpret_cast<const f16x8*>(hrow + PLANE + 32 * s);
-                // eight independent accumulators between dependent MFMAs
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acl[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[q][s][1], a0, acl[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[q][s][0], a0, acc[q], 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acl[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wb[q][s][0], a1, acl[q], 0, 0, 0);
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float4 v = FUSE_X ? *reinterpret_cast<const float4*>(bl + q * H + uo)
-                                        : *reinterpret_cast<const float4*>(stash + row * (6 * H) + q * H + uo);
-                acc[q] = (acc[q] + acl[q] * H3_LO) * kcur + f32x4{v.x, v.y, v.z, v.w};
-            }
-            if (FUSE_X) {       // K = I <= 8 input projection: two exact-f32 k-steps
-                const float2 ax = *reinterpret_cast<const float2*>(&xbuf[((xb * TC + tt) * MT + j) * 8 + 2 * kq]);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wxw[(2 * q) * 64], ax.x, acc[q], 0, 0, 0);
-                    acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wxw[(2 * q + 1) * 64], ax.y, acc[q], 0, 0, 0);
-                }
-            }
-            X6_PROF_DEP(acc[0][0]); X6_PROF_DEP(acc[1][1]); X6_PROF_DEP(acc[2][2]); X6_PROF_DEP(acc[3][3]);
-            X6_PROF_MARK(1);
-            const float kn = kbuf[(xb * TC + tt) * MT + j];              // keep of step t+1 (1 past the end)
-            float gi[4], gf[4], gg[4], go[4], cp[4], hh[4], hm[4], cc[4];
-            float* sp = stash + row * (6 * H) + uo;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                gi[r] = sigmoidf_(acc[0][r]); gf[r] = sigmoidf_(acc[1][r]); gg[r] = tanhf_(acc[2][r]);
-                cp[r] = c_reg[r];
-                cc[r] = gf[r] * cp[r] + gi[r] * gg[r];
-            }
-            if (live && stash) {
-                *reinterpret_cast<float4*>(sp) = float4{gi[0], gi[1], gi[2], gi[3]};
-                *reinterpret_cast<float4*>(sp + H) = float4{gf[0], gf[1], gf[2], gf[3]};
-                *reinterpret_cast<float4*>(sp + 2 * H) = float4{gg[0], gg[1], gg[2], gg[3]};
-                *reinterpret_cast<float4*>(sp + 4 * H) = float4{cp[0], cp[1], cp[2], cp[3]};
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                go[r] = sigmoidf_(acc[3][r]);
-                hh[r] = go[r] * tanhf_(cc[r]);
-                hm[r] = hh[r] * kn;
-                c_reg[r] = (t == T - 1) ? cc[r] : cc[r] * kn;            // cn is the unmasked final cell state
-            }
-            put_h(hpl + (cur ^ 1) * 2 * PLANE, hh);
-            kcur = kn;
-            if (live) {
-                *reinterpret_cast<float4*>(y + row * H + uo) = float4{hh[0], hh[1], hh[2], hh[3]};
-                if (stash) {
-                    *reinterpret_cast<float4*>(sp + 3 * H) = float4{go[0], go[1], go[2], go[3]};
-                    if (I > 6 && t + 1 < T)                              // h_prev of step t+1 (generic wgrad path)
-                        *reinterpret_cast<float4*>(sp + 6 * H + 5 * H) = float4{hm[0], hm[1], hm[2], hm[3]};
-                }
-                if (t == T - 1) {
-                    *reinterpret_cast<float4*>(hn + (size_t)n * H + uo) = float4{hh[0], hh[1], hh[2], hh[3]};
-                    *reinterpret_cast<float4*>(cn + (size_t)n * H + uo) = float4{c_reg[0], c_reg[1], c_reg[2], c_reg[3]};
-                }
-            }
-            cur ^= 1;
-            X6_PROF_MARK(2);
-            lds_barrier();
-            X6_PROF_MARK(3);
-        }
-        if (ch + 1 < nchunk) {
-            stage_commit(xb ^ 1);
-            lds_barrier();
-        }
-    }
-    if (heads && w == NW - 1) emit_heads(cur, T - 1);                     // planes `cur` hold h_{T-1}
-    X6_PROF_FLUSH();
+    lstm_fwd_split<SplitF16x3, H, FUSE_X>(x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash, w_head,
+                                          b_head, NHD, heads);
+}
+template <int H, bool FUSE_X>
+__global__ __launch_bounds__(H * 4) void lstm_fwd_x6_kernel(
+    const float* __restrict__ x, const float* __restrict__ keep, const float* __restrict__ h0,
+    const float* __restrict__ c0, const float* __restrict__ w_ih, const float* __restrict__ w_hh,
+    const float* __restrict__ b_ih, const float* __restrict__ b_hh, int N, int T, int I,
+    float* __restrict__ y, float* __restrict__ hn, float* __restrict__ cn, float* __restrict__ stash,
+    const float* __restrict__ w_head, const float* __restrict__ b_head, int NHD, float* __restrict__ heads) {
+    lstm_fwd_split<SplitBf16x6, H, FUSE_X>(x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash, w_head,
+                                           b_head, NHD, heads);
 }
 
 // ---------------------------------------------------------------------------------------- backward
@@ -957,12 +705,12 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_kernel(
     }
 }
 
-// ------------------------------------------------------- backward, split-bf16 MFMA, K split over the waves
-// dh_{t-1}^T = W_hh^T dG_t^T on the bf16 matrix pipe at f32 accuracy (3-way split, six products; see
-// lstm_fwd_x6_kernel), weights as the A operand: lane (j, kq) owns env j and the four consecutive units uo..uo+3.
-// Giving every wave 16 OUTPUT units and the whole K = 4H of dG (the first form built) makes each wave read all three
-// piece planes of the step's gate gradients back from LDS (48 b128 fragments, 384 KB per step and CU -- as many cycles
-// of LDS bandwidth as the MFMAs take) behind a barrier: 0.52 of 0.62 ms with HBM taken out of the picture.
+// ---------------------------------------------------------------- backward, split MFMA, K split over the waves
+// dh_{t-1}^T = W_hh^T dG_t^T on the 16-bit matrix pipe at f32 accuracy (the split of the forward pass, P), weights as
+// the A operand: lane (j, kq) owns env j and the four consecutive units uo..uo+3.
+// Giving every wave 16 OUTPUT units and the whole K = 4H of dG (the first form built, on the bf16 split) makes each wave
+// read all three piece planes of the step's gate gradients back from LDS (48 b128 fragments, 384 KB per step and CU -- as
+// many cycles of LDS bandwidth as the MFMAs take) behind a barrier: 0.52 of 0.62 ms with HBM taken out of the picture.
 // Here the K dimension is split instead: wave w multiplies ONLY the 64 gate gradients it produced itself
 // (gates x its 16 units -- they already sit in the right lanes: the MFMA's k order is free, so lane (j, kq)
 // supplies k = (gate, unit 16w + 4kq + r) of its own env j) against W_hh[those 64 rows][all H units], and writes
@@ -973,25 +721,27 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_kernel(
 // Stash by LDS-DMA (global_load_lds: no VGPR destination): each wave gathers exactly what its own lanes read back, so
 // the only ordering needed is the wave's own counted s_waitcnt vmcnt(k) = "everything but the k ops issued last has
 // landed" (loads, stores and LDS-DMA retire in issue order; the DMA ops of a step are issued unconditionally).
-template <int H>
-struct BwdKGeom {
+template <class P, int H>
+struct BwdSplitGeom {
     static constexpr int NW = H / 16;
     static constexpr int SLOT = 5 * MT * 16;                         // floats per wave in the stash ring (one slot)
     static constexpr int SMALL = 128;                                // floats per small slot: dheads[16][6] | keep[16]
-    static constexpr int PK = (H >= 128) ? 6 : 0;                    // (tile, slab) items whose smallest weight piece is LDS-parked
-    static constexpr int WPARK = PK * 64 * 8;                        // bf16 elements per wave
+    static constexpr int PK = P::bwd_park(H);                        // (tile, slab) items whose smallest weight piece is in LDS
+    static constexpr int WPARK = PK * 64 * 8;                        // 16-bit elements per wave
     static constexpr size_t LDS = (NW * NW * 64 * 4 /*partials*/ + NW * SLOT + 2 * SMALL) * sizeof(float) +
                                   NW * WPARK * sizeof(unsigned short);
 };
 
-template <int H>
-__global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel(
+template <class P, int H>
+__device__ __forceinline__ void lstm_bwd_split(
     const float* __restrict__ keep, const float* __restrict__ stash, const float* __restrict__ w_hh,
     const float* __restrict__ dheads, const float* __restrict__ w_head, int NH, const float* __restrict__ dhn,
     const float* __restrict__ dcn, int N, int T, float* __restrict__ dgates, float* __restrict__ dh0,
     float* __restrict__ dc0) {
-    using G = BwdKGeom<H>;
-    constexpr int SLOT = G::SLOT, NW = G::NW, SMALL = G::SMALL, PK = G::PK, WPARK = G::WPARK;
+    using G = BwdSplitGeom<P, H>;
+    using vec = typename P::vec;
+    using piece = typename P::piece;
+    constexpr int NP = P::NP, SLOT = G::SLOT, NW = G::NW, SMALL = G::SMALL, PK = G::PK, WPARK = G::WPARK;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     f32x4* part = reinterpret_cast<f32x4*>(smem);                           // [tile m][wave w][64 lanes]
     float* ring = smem + NW * NW * 64 * 4;                                  // [NW][SLOT]
@@ -1008,24 +758,23 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel(
     const bool live = n0 + j < N;
 
     // A fragments: tile m (units 16m..16m+15), slab sb (gates 2sb, 2sb+1): lane (i = j, kq), element e holds
-    // W_hh[(2sb + e/4) H + 16w + 4kq + e%4][16m + j] -- the k order of this wave's own gate gradients
-    bf16x8 wa[NW][2][2], wa2[2 * NW - PK];
-    bf16x8* const wpk = reinterpret_cast<bf16x8*>(wpark + w * WPARK) + lane;           // + item * 64
+    // W_hh[(2sb + e/4) H + 16w + 4kq + e%4][16m + j] -- the k order of this wave's own gate gradients.  The smallest
+    // piece of the first PK items (item = 2m + sb) lives in this wave's LDS slab instead.
+    vec wa[NW][2][NP];
+    vec* const wpk = reinterpret_cast<vec*>(wpark + w * WPARK) + lane;      // + item * 64
 #pragma unroll
     for (int m = 0; m < NW; ++m)
 #pragma unroll
         for (int sb = 0; sb < 2; ++sb) {
-            bf16x8 p2v;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int k = (2 * sb + e / 4) * H + 16 * w + 4 * kq + (e % 4);
-                __bf16 p0, p1, p2;
-                split3(w_hh[(size_t)k * H + 16 * m + j], p0, p1, p2);
-                wa[m][sb][0][e] = p0; wa[m][sb][1][e] = p1; p2v[e] = p2;
+                piece p[NP];
+                P::split(w_hh[(size_t)k * H + 16 * m + j], p);
+#pragma unroll
+                for (int pc = 0; pc < NP; ++pc) wa[m][sb][pc][e] = p[pc];
             }
-            const int item = 2 * m + sb;
-            if (item < PK) wpk[item * 64] = p2v;
-            else wa2[item < PK ? 0 : item - PK] = p2v;
+            if (2 * m + sb < PK) wpk[(2 * m + sb) * 64] = wa[m][sb][NP - 1];
         }
     float whb[2];
 #pragma unroll
@@ -1040,7 +789,7 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel(
     }
     const size_t srow = (size_t)n * T;
 
-    // ---- LDS-DMA (inline asm; ordering: comment above BwdKGeom): stash gather [q][env lane/4][units 4 (lane%4) ..]
+    // ---- LDS-DMA (inline asm; ordering: comment above BwdSplitGeom): stash gather [q][env lane/4][units 4 (lane%4) ..]
     typedef __attribute__((address_space(3))) float lds_f;
     const int e_d = lane >> 2, g4 = lane & 3;
     const size_t drow = (size_t)min(n0 + e_d, N - 1) * T;
@@ -1122,7 +871,7 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel(
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const float dh = dyacc[r] + dh_rec[r];
-            const float c = gf[r] * cp[r] + gi[r] * gg[r];
+            const float c = __builtin_fmaf(gf[r], cp[r], gi[r] * gg[r]);    // the fused product: comment at lstm_fwd_split
             const float tch = tanhf_(c);
             const float dc = dh * go[r] * (1.0f - tch * tch) + dc_next[r];
             dg[0][r] = dc * gg[r] * gi[r] * (1.0f - gi[r]);
@@ -1131,21 +880,50 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel(
             dg[3][r] = dh * tch * go[r] * (1.0f - go[r]);
             dc_next[r] = dc * gf[r] * kp;
         }
+        int ex = 0;                  // the gate gradients enter the products as dG 2^ex, the partial tiles leave times 2^-ex
+        float unscale = 1.f;
+        if constexpr (P::BLOCK_SCALE) {
+            // Gate gradients span many binades, fp16 does not: each env's 64 values of this wave are scaled by a power of
+            // two that puts their largest magnitude in [2^13, 2^14) (exact), and the env's column of the partial tiles --
+            // it sits in these same lanes -- is scaled back.  max over the lane's 16 values, then over the four kq rows of
+            // env j with the two gfx950 row-swap instructions.
+            float mx = 0.f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) mx = fmaxf(mx, fabsf(dg[q][r]));
+            {
+                const unsigned u = __builtin_bit_cast(unsigned, mx);
+                const auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+                mx = fmaxf(__builtin_bit_cast(float, (unsigned)s16[0]), __builtin_bit_cast(float, (unsigned)s16[1]));
+                const unsigned v = __builtin_bit_cast(unsigned, mx);
+                const auto s32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
+                mx = fmaxf(__builtin_bit_cast(float, (unsigned)s32[0]), __builtin_bit_cast(float, (unsigned)s32[1]));
+            }
+            ex = 14 - __builtin_amdgcn_frexp_expf(mx);                      // mx = f 2^e, f in [0.5, 1)  ->  mx 2^ex in [2^13, 2^14)
+            ex = mx > 0.f ? min(max(ex, -100), 100) : 0;
+            unscale = __builtin_amdgcn_ldexpf(1.0f, -ex);
+        }
+        // the step's four dG stores, between the ring DMA and the small piece in the wave's issue order (the counted waits
+        // above rely on that): ahead of the products, or behind them where they drain under the partial-sum reduce
+        // instead of queueing in front of the products of the slowest wave, which everybody then waits for at b1
+        auto store_dg = [&](int q) {
+            if (live) *reinterpret_cast<float4*>(dgates + (srow + t) * (4 * H) + q * H + uo) = float4{dg[q][0], dg[q][1], dg[q][2], dg[q][3]};
+        };
         // this wave's 64 gate gradients as B fragments: slab sb = gates 2sb, 2sb+1; element e = (gate 2sb + e/4, unit e%4)
-        bf16x8 bp[2][3];
+        vec bp[2][NP];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                __bf16 p0, p1, p2;
-                split3(dg[q][r], p0, p1, p2);
-                bp[q >> 1][0][4 * (q & 1) + r] = p0; bp[q >> 1][1][4 * (q & 1) + r] = p1; bp[q >> 1][2][4 * (q & 1) + r] = p2;
+                piece p[NP];
+                P::split(P::BLOCK_SCALE ? __builtin_amdgcn_ldexpf(dg[q][r], ex) : dg[q][r], p);
+#pragma unroll
+                for (int pc = 0; pc < NP; ++pc) bp[q >> 1][pc][4 * (q & 1) + r] = p[pc];
             }
-            if (live)
-                *reinterpret_cast<float4*>(dgates + (srow + t) * (4 * H) + q * H + uo) =
-                    float4{dg[q][0], dg[q][1], dg[q][2], dg[q][3]};
+            if constexpr (!P::DG_STORES_LATE) store_dg(q);
         }
-        X6_PROF_DEP(bp[1][2]); X6_PROF_DEP(bp[0][0]);
+        X6_PROF_DEP(bp[1][NP - 1]); X6_PROF_DEP(bp[0][0]);
         X6_PROF_MARK(3);
         // partial dh^T tiles: D_m[unit 16m + 4kq + r][env j] over this wave's K range
 #pragma unroll
@@ -1154,15 +932,13 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel(
 #pragma unroll
             for (int sb = 0; sb < 2; ++sb) {
                 const int item = 2 * m + sb;
-                const bf16x8 w2 = (item < PK) ? wpk[item * 64] : wa2[item < PK ? 0 : item - PK];
-                a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[m][sb][0], bp[sb][2], a0, 0, 0, 0);
-                a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[m][sb][1], bp[sb][1], a1, 0, 0, 0);
-                a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2, bp[sb][0], a0, 0, 0, 0);
-                a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[m][sb][0], bp[sb][1], a1, 0, 0, 0);
-                a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[m][sb][1], bp[sb][0], a0, 0, 0, 0);
-                a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa[m][sb][0], bp[sb][0], a1, 0, 0, 0);
+                P::tile_slab(a0, a1, [&](int p) { return (p == NP - 1 && item < PK) ? wpk[item * 64] : wa[m][sb][p]; }, bp[sb]);
             }
-            part[(m * NW + w) * 64 + lane] = a0 + a1;
+            part[(m * NW + w) * 64 + lane] = P::tile_sum(a0, a1) * unscale;
+        }
+        if constexpr (P::DG_STORES_LATE) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) store_dg(q);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         X6_PROF_MARK(4);
@@ -1184,17 +960,6 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel(
         if (dc0) *reinterpret_cast<float4*>(dc0 + (size_t)n * H + uo) = float4{dc_next[0], dc_next[1], dc_next[2], dc_next[3]};
     }
 }
-
-// lstm_bwd_h3k_kernel: the K-split backward with the recurrent product as three fp16 MFMA products (common.h, split2h)
-// instead of the bf16 split's six: W_hh as two fp16 pieces in exactly the f32 weights' 128 VGPRs (no LDS slab), and this
-// step's gate gradients block-scaled per env by a power of two before the split (below).
-template <int H>
-struct BwdH3Geom {
-    static constexpr int NW = H / 16;
-    static constexpr int SLOT = 5 * MT * 16;                         // floats per wave in the stash ring (one slot)
-    static constexpr int SMALL = 128;                                // floats per small slot: dheads[16][6] | keep[16]
-    static constexpr size_t LDS = (NW * NW * 64 * 4 /*partials*/ + NW * SLOT + 2 * SMALL) * sizeof(float);
-};
 
 template <int H>
 __global__ __launch_bounds__(H * 4) void lstm_bwd_h3k_kernel(
@@ -1202,235 +967,60 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_h3k_kernel(
     const float* __restrict__ dheads, const float* __restrict__ w_head, int NH, const float* __restrict__ dhn,
     const float* __restrict__ dcn, int N, int T, float* __restrict__ dgates, float* __restrict__ dh0,
     float* __restrict__ dc0) {
-    using G = BwdH3Geom<H>;
-    constexpr int SLOT = G::SLOT, NW = G::NW, SMALL = G::SMALL;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    f32x4* part = reinterpret_cast<f32x4*>(smem);                           // [tile m][wave w][64 lanes]
-    float* ring = smem + NW * NW * 64 * 4;                                  // [NW][SLOT]
-    float* small = ring + NW * SLOT;                                        // [2 slots][SMALL]
-
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int j = lane & 15, kq = lane >> 4;
-    const int uw = 16 * w + j;                 // A row of the dy product (head weights of unit uw)
-    const int uo = 16 * w + 4 * kq;            // first of this lane's four units; its env is j
-    const int n0 = blockIdx.x * MT;
-    const int n = min(n0 + j, N - 1);
-    const bool live = n0 + j < N;
-
-    // A fragments: tile m (units 16m..16m+15), slab sb (gates 2sb, 2sb+1): lane (i = j, kq), element e holds
-    // W_hh[(2sb + e/4) H + 16w + 4kq + e%4][16m + j] -- the k order of this wave's own gate gradients
-    f16x8 wa[NW][2][2];                                                      // two fp16 pieces: the f32 weights' 128 VGPRs
-#pragma unroll
-    for (int m = 0; m < NW; ++m)
-#pragma unroll
-        for (int sb = 0; sb < 2; ++sb) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const int k = (2 * sb + e / 4) * H + 16 * w + 4 * kq + (e % 4);
-                _Float16 p0, p1;
-                split2h(w_hh[(size_t)k * H + 16 * m + j], p0, p1);
-                wa[m][sb][0][e] = p0; wa[m][sb][1][e] = p1;
-            }
-        }
-    float whb[2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a) whb[a] = (4 * a + kq < NH) ? w_head[(size_t)(4 * a + kq) * H + uw] : 0.f;
-
-    float dh_rec[4], dc_next[4];
-    {
-        const float4 a4 = dhn ? *reinterpret_cast<const float4*>(dhn + (size_t)n * H + uo) : float4{0.f, 0.f, 0.f, 0.f};
-        const float4 c4 = dcn ? *reinterpret_cast<const float4*>(dcn + (size_t)n * H + uo) : float4{0.f, 0.f, 0.f, 0.f};
-        dh_rec[0] = a4.x; dh_rec[1] = a4.y; dh_rec[2] = a4.z; dh_rec[3] = a4.w;
-        dc_next[0] = c4.x; dc_next[1] = c4.y; dc_next[2] = c4.z; dc_next[3] = c4.w;
-    }
-    const size_t srow = (size_t)n * T;
-
-    // ---- LDS-DMA (inline asm; ordering: comment above BwdKGeom): stash gather [q][env lane/4][units 4 (lane%4) ..]
-    typedef __attribute__((address_space(3))) float lds_f;
-    const int e_d = lane >> 2, g4 = lane & 3;
-    const size_t drow = (size_t)min(n0 + e_d, N - 1) * T;
-    const unsigned ring_base = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)((lds_f*)(ring + w * SLOT)));
-    const unsigned small_base = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)((lds_f*)small));
-    auto issue = [&](int t) {
-        const float* src = stash + (drow + t) * (6 * H) + 16 * w + 4 * g4;
-        unsigned m0save;
-        asm volatile(
-            "s_mov_b32 %0, m0\n\t"
-            "s_mov_b32 m0, %6\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-            "s_add_u32 m0, m0, 1024\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\t"
-            "s_add_u32 m0, m0, 1024\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %3, off\n\t"
-            "s_add_u32 m0, m0, 1024\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %4, off\n\t"
-            "s_add_u32 m0, m0, 1024\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %5, off\n\t"
-            "s_mov_b32 m0, %0"
-            : "=&s"(m0save)
-            : "v"(src), "v"(src + H), "v"(src + 2 * H), "v"(src + 3 * H), "v"(src + 4 * H), "s"(ring_base)
-            : "memory", "scc");
-    };
-    // waves 0 / 1: one 256-B piece each of the step's small image  [dheads(16 envs x NH, env-major) | keep(16)].
-    // The lane's element of step 0 and its per-step stride are fixed: only `+ t * stride` is left in the loop
-    // (the division by NH used to run every step on the two waves everybody waits for).
-    const float* small_at0;
-    unsigned small_stride;
-    {
-        const int e = w * 64 + lane;
-        if (e < 16 * NH) { small_at0 = dheads + (size_t)min(n0 + e / NH, N - 1) * T * NH + e % NH; small_stride = (unsigned)NH; }
-        else if (e >= 112 && keep) { small_at0 = keep + (size_t)min(n0 + e - 112, N - 1) * T; small_stride = 1u; }
-        else { small_at0 = w_hh + (lane & 15); small_stride = 0u; }         // padding: any readable dwords
-    }
-    auto issue_small = [&](int t, int slot) {
-        const float* src = small_at0 + (size_t)((unsigned)t * small_stride);
-        const unsigned dst = small_base + (unsigned)((slot * SMALL + w * 64) * 4);
-        unsigned m0save;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(m0save) : "v"(src), "s"(dst) : "memory");
-    };
-    const bool small_wave = w < 2;
-    // vector-memory operations of this wave, in issue order (all retire in order):
-    //   prologue  ring(T-1) [small(T-1)] [small(T-2)]
-    //   step t    wait . ring(t-1) . 4 dG stores . [small(t-2)]
-    // so at the top of step t everything but the 4 stores (and one small piece) of step t+1 must have landed
-    issue(T - 1);
-    if (small_wave) {
-        issue_small(T - 1, (T - 1) & 1);
-        issue_small(T >= 2 ? T - 2 : 0, (T - 2) & 1);
-    }
-    bool first = true;
-    X6_PROF_DECL;
-    for (int t = T - 1; t >= 0; --t) {
-        X6_PROF_MARK(0);
-        if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (small_wave) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        first = false;
-        const float* sl = ring + w * SLOT + j * 16 + 4 * kq;
-        float4 pf[5];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) pf[q] = *reinterpret_cast<const float4*>(sl + q * 256);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the slot is in registers: refill it with step t-1
-        issue(t >= 1 ? t - 1 : 0);
-        X6_PROF_MARK(1);
-        lds_barrier();           // b2: the partials of step t+1 have been summed by everyone; small image of step t landed
-        X6_PROF_MARK(2);
-        const float* sm = small + (t & 1) * SMALL;
-        f32x4 dyacc = {0.f, 0.f, 0.f, 0.f};
-        {
-            const float d0 = (kq < NH) ? sm[j * NH + kq] : 0.f;
-            const float d1 = (4 + kq < NH) ? sm[j * NH + 4 + kq] : 0.f;
-            dyacc = __builtin_amdgcn_mfma_f32_16x16x4f32(whb[0], d0, dyacc, 0, 0, 0);
-            dyacc = __builtin_amdgcn_mfma_f32_16x16x4f32(whb[1], d1, dyacc, 0, 0, 0);
-        }
-        const float kp = keep ? sm[112 + j] : 1.f;                           // keep[env j][t]
-        const float gi[4] = {pf[0].x, pf[0].y, pf[0].z, pf[0].w}, gf[4] = {pf[1].x, pf[1].y, pf[1].z, pf[1].w};
-        const float gg[4] = {pf[2].x, pf[2].y, pf[2].z, pf[2].w}, go[4] = {pf[3].x, pf[3].y, pf[3].z, pf[3].w};
-        const float cp[4] = {pf[4].x, pf[4].y, pf[4].z, pf[4].w};
-        float dg[4][4];                                                      // [gate][unit r]
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float dh = dyacc[r] + dh_rec[r];
-            const float c = gf[r] * cp[r] + gi[r] * gg[r];
-            const float tch = tanhf_(c);
-            const float dc = dh * go[r] * (1.0f - tch * tch) + dc_next[r];
-            dg[0][r] = dc * gg[r] * gi[r] * (1.0f - gi[r]);
-            dg[1][r] = dc * cp[r] * gf[r] * (1.0f - gf[r]);
-            dg[2][r] = dc * gi[r] * (1.0f - gg[r] * gg[r]);
-            dg[3][r] = dh * tch * go[r] * (1.0f - go[r]);
-            dc_next[r] = dc * gf[r] * kp;
-        }
-        // Gate gradients span many binades, fp16 does not: each env's 64 values of this wave are scaled by a power of two
-        // that puts their largest magnitude in [2^13, 2^14) (exact), and the env's column of the partial tiles -- it sits
-        // in these same lanes -- is scaled back.  max over the lane's 16 values, then over the four kq rows of env j with
-        // the two gfx950 row-swap instructions.
-        float mx = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) mx = fmaxf(mx, fabsf(dg[q][r]));
-        {
-            const unsigned u = __builtin_bit_cast(unsigned, mx);
-            const auto s16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-            mx = fmaxf(__builtin_bit_cast(float, (unsigned)s16[0]), __builtin_bit_cast(float, (unsigned)s16[1]));
-            const unsigned v = __builtin_bit_cast(unsigned, mx);
-            const auto s32 = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-            mx = fmaxf(__builtin_bit_cast(float, (unsigned)s32[0]), __builtin_bit_cast(float, (unsigned)s32[1]));
-        }
-        int ex = 14 - __builtin_amdgcn_frexp_expf(mx);                      // mx = f 2^e, f in [0.5, 1)  ->  mx 2^ex in [2^13, 2^14)
-        ex = mx > 0.f ? min(max(ex, -100), 100) : 0;
-        const float unscale = __builtin_amdgcn_ldexpf(1.0f, -ex);
-        // this wave's 64 gate gradients as B fragments: slab sb = gates 2sb, 2sb+1; element e = (gate 2sb + e/4, unit e%4)
-        f16x8 bp[2][2];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                _Float16 p0, p1;
-                split2h(__builtin_amdgcn_ldexpf(dg[q][r], ex), p0, p1);
-                bp[q >> 1][0][4 * (q & 1) + r] = p0; bp[q >> 1][1][4 * (q & 1) + r] = p1;
-            }
-        }
-        X6_PROF_DEP(bp[1][1]); X6_PROF_DEP(bp[0][0]);
-        X6_PROF_MARK(3);
-        // partial dh^T tiles: D_m[unit 16m + 4kq + r][env j] over this wave's K range
-#pragma unroll
-        for (int m = 0; m < NW; ++m) {
-            f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0;
-#pragma unroll
-            for (int sb = 0; sb < 2; ++sb) {
-                a1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[m][sb][1], bp[sb][0], a1, 0, 0, 0);
-                a0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[m][sb][0], bp[sb][0], a0, 0, 0, 0);
-                a1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[m][sb][0], bp[sb][1], a1, 0, 0, 0);
-            }
-            part[(m * NW + w) * 64 + lane] = (a0 + a1 * H3_LO) * unscale;
-        }
-        // the step's four dG stores behind the products (same place in the wave's issue order as before: between the ring DMA
-        // and the small piece, so the counted waits are unchanged): they queued in front of the products for the slowest
-        // wave, which everybody then waited for at b1; here they drain under the partial-sum reduce
-        if (live) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                *reinterpret_cast<float4*>(dgates + (srow + t) * (4 * H) + q * H + uo) = float4{dg[q][0], dg[q][1], dg[q][2], dg[q][3]};
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        X6_PROF_MARK(4);
-        lds_barrier();           // b1: all partials written; nobody reads the small image of step t any more
-        X6_PROF_MARK(5);
-        if (small_wave) issue_small(t >= 2 ? t - 2 : 0, t & 1);
-        f32x4 sum = part[(w * NW) * 64 + lane];
-#pragma unroll
-        for (int ww = 1; ww < NW; ++ww) sum += part[(w * NW + ww) * 64 + lane];      // fixed order: deterministic
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dh_rec[r] = sum[r] * kp;
-        X6_PROF_DEP(dh_rec[3]);
-        X6_PROF_MARK(6);
-    }
-    X6_PROF_FLUSH8();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // retire the clamped tail DMAs before the LDS is released
-    if (live) {
-        if (dh0) *reinterpret_cast<float4*>(dh0 + (size_t)n * H + uo) = float4{dh_rec[0], dh_rec[1], dh_rec[2], dh_rec[3]};
-        if (dc0) *reinterpret_cast<float4*>(dc0 + (size_t)n * H + uo) = float4{dc_next[0], dc_next[1], dc_next[2], dc_next[3]};
-    }
+    lstm_bwd_split<SplitF16x3, H>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0);
+}
+template <int H>
+__global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel(
+    const float* __restrict__ keep, const float* __restrict__ stash, const float* __restrict__ w_hh,
+    const float* __restrict__ dheads, const float* __restrict__ w_head, int NH, const float* __restrict__ dhn,
+    const float* __restrict__ dcn, int N, int T, float* __restrict__ dgates, float* __restrict__ dh0,
+    float* __restrict__ dc0) {
+    lstm_bwd_split<SplitBf16x6, H>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0);
 }
 
-template <int H>
-static int launch_bwd_h3k(const float* keep, const float* stash, const float* w_hh, const float* dheads,
-                          const float* w_head, int NH, const float* dhn, const float* dcn, int N, int T, float* dgates,
-                          float* dh0, float* dc0, hipStream_t st) {
+// the entry points of arithmetic P
+template <class P, int H, bool FUSE_X>
+static constexpr auto fwd_split_kernel() {
+    if constexpr (std::is_same<P, SplitF16x3>::value) return &lstm_fwd_h3_kernel<H, FUSE_X>;
+    else return &lstm_fwd_x6_kernel<H, FUSE_X>;
+}
+template <class P, int H>
+static constexpr auto bwd_split_kernel() {
+    if constexpr (std::is_same<P, SplitF16x3>::value) return &lstm_bwd_h3k_kernel<H>;
+    else return &lstm_bwd_x6k_kernel<H>;
+}
+
+// f(P{}) with the split policy of the handle's mode
+template <class F>
+static int with_split(F&& f) {
+    return uav_want_bf16x6() ? f(SplitBf16x6{}) : f(SplitF16x3{});
+}
+
+template <class P, int H>
+static int launch_bwd_split(const float* keep, const float* stash, const float* w_hh, const float* dheads,
+                            const float* w_head, int NH, const float* dhn, const float* dcn, int N, int T, float* dgates,
+                            float* dh0, float* dc0, hipStream_t st) {
     const dim3 grid((N + MT - 1) / MT), block(H * 4);
-    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&lstm_bwd_h3k_kernel<H>), (int)BwdH3Geom<H>::LDS));
-    hipLaunchKernelGGL((lstm_bwd_h3k_kernel<H>), grid, block, BwdH3Geom<H>::LDS, st, keep, stash, w_hh, dheads, w_head,
-                       NH, dhn, dcn, N, T, dgates, dh0, dc0);
+    const size_t lx = BwdSplitGeom<P, H>::LDS;
+    constexpr auto kern = bwd_split_kernel<P, H>();
+    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(kern), (int)lx));
+    hipLaunchKernelGGL(kern, grid, block, lx, st, keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0);
     UAV_LAUNCH_CHECK();
     return 0;
 }
 
-template <int H>
-static int launch_bwd_x6k(const float* keep, const float* stash, const float* w_hh, const float* dheads,
-                          const float* w_head, int NH, const float* dhn, const float* dcn, int N, int T, float* dgates,
-                          float* dh0, float* dc0, hipStream_t st) {
+template <class P, int H>
+static int launch_fwd_split(bool fuse, const float* x, const float* keep, const float* h0, const float* c0,
+                            const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int N, int T, int I,
+                            float* y, float* hn, float* cn, float* stash, const float* w_head, const float* b_head, int NHD,
+                            float* heads, hipStream_t st) {
     const dim3 grid((N + MT - 1) / MT), block(H * 4);
-    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&lstm_bwd_x6k_kernel<H>), (int)BwdKGeom<H>::LDS));
-    hipLaunchKernelGGL((lstm_bwd_x6k_kernel<H>), grid, block, BwdKGeom<H>::LDS, st, keep, stash, w_hh, dheads, w_head,
-                       NH, dhn, dcn, N, T, dgates, dh0, dc0);
+    const size_t lx = FwdSplitGeom<P, H>::LDS;
+    constexpr auto fused = fwd_split_kernel<P, H, true>(), unfused = fwd_split_kernel<P, H, false>();
+    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(fused), (int)lx));
+    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(unfused), (int)lx));
+    hipLaunchKernelGGL(fuse ? fused : unfused, grid, block, lx, st, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn,
+                       cn, stash, w_head, b_head, NHD, heads);
     UAV_LAUNCH_CHECK();
     return 0;
 }
@@ -1440,35 +1030,14 @@ static int launch_fwd(bool fuse, const float* x, const float* keep, const float*
                       const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int N, int T, int I,
                       float* y, float* hn, float* cn, float* stash, const float* w_head, const float* b_head, int NHD,
                       float* heads, bool* heads_done, hipStream_t st) {
+    if (!uav_want_f32_mfma()) {          // the matrix products as 16-bit piece products at f32 accuracy, heads fused
+        *heads_done = heads != nullptr;
+        return with_split([&](auto p) {
+            return launch_fwd_split<decltype(p), H>(fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash,
+                                                    w_head, b_head, NHD, heads, st);
+        });
+    }
     const dim3 grid((N + MT - 1) / MT), block(H * 4);
-    if (!f32_mfma_requested() && !bf16x6_requested()) {   // default: three fp16 piece products on the matrix pipe (f32 accuracy)
-        const size_t lx = FwdH3Geom<H>::LDS;
-        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&lstm_fwd_h3_kernel<H, true>), (int)lx));
-        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&lstm_fwd_h3_kernel<H, false>), (int)lx));
-        if (fuse)
-            hipLaunchKernelGGL((lstm_fwd_h3_kernel<H, true>), grid, block, lx, st, x, keep, h0, c0, w_ih, w_hh, b_ih,
-                               b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, NHD, heads);
-        else
-            hipLaunchKernelGGL((lstm_fwd_h3_kernel<H, false>), grid, block, lx, st, x, keep, h0, c0, w_ih, w_hh, b_ih,
-                               b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, NHD, heads);
-        *heads_done = heads != nullptr;
-        UAV_LAUNCH_CHECK();
-        return 0;
-    }
-    if (!f32_mfma_requested()) {         // UAV_LSTM_BF16X6=1: the six-product bf16 split
-        const size_t lx = FwdX6Geom<H>::LDS;
-        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&lstm_fwd_x6_kernel<H, true>), (int)lx));
-        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&lstm_fwd_x6_kernel<H, false>), (int)lx));
-        if (fuse)
-            hipLaunchKernelGGL((lstm_fwd_x6_kernel<H, true>), grid, block, lx, st, x, keep, h0, c0, w_ih, w_hh, b_ih,
-                               b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, NHD, heads);
-        else
-            hipLaunchKernelGGL((lstm_fwd_x6_kernel<H, false>), grid, block, lx, st, x, keep, h0, c0, w_ih, w_hh, b_ih,
-                               b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, NHD, heads);
-        *heads_done = heads != nullptr;
-        UAV_LAUNCH_CHECK();
-        return 0;
-    }
     const size_t lds = FwdGeom<H>::LDS;
     if (fuse)
         hipLaunchKernelGGL((lstm_fwd_kernel<H, true>), grid, block, lds, st, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N,
@@ -1501,17 +1070,12 @@ __global__ void add2_kernel(const float* a0, const float* a1, float* b, int n) {
 static int lstm_bwd_seq(const float* keep, const float* stash, const float* w_hh, const float* dy,
                         const float* dheads, const float* w_head, int NH, const float* dhn, const float* dcn, int N,
                         int T, int H, float* dgates, float* dh0, float* dc0, hipStream_t st) {
-    if (dheads && NH <= 7 && !f32_mfma_requested() && !bf16x6_requested()) {   // the PPO path: split-fp16, K split over waves
-        switch (H) {
-            case 64: return launch_bwd_h3k<64>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0, st);
-            case 128: return launch_bwd_h3k<128>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0, st);
-        }
-    }
-    if (dheads && NH <= 7 && !f32_mfma_requested()) {   // UAV_ARITH_BF16X6: split-bf16 (f32's exponent range), K split over waves
-        switch (H) {
-            case 64: return launch_bwd_x6k<64>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0, st);
-            case 128: return launch_bwd_x6k<128>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0, st);
-        }
+    if (dheads && NH <= 7 && !uav_want_f32_mfma()) {   // the PPO path: split MFMA, K split over waves
+        return with_split([&](auto p) {
+            using P = decltype(p);
+            return H == 64 ? launch_bwd_split<P, 64>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0, st)
+                           : launch_bwd_split<P, 128>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0, st);
+        });
     }
     // exact-f32 MFMA (UAV_ARITH_F32_MFMA), plain dy (stacked layers), more than 7 heads
     switch (H) {

@@ -431,6 +431,25 @@ int uav_rollout(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg
                 const int32_t* forced_act, const double* noise, int32_t* nan_count,
                 float* stash, float* y_out, float* info, float* heads, uav_stream stream);
 
+/* Greedy evaluation episodes on the fused rollout kernels (evaluate_with_lstm.py's loop for n_env environments): per step,
+ * for every env still active, the policy heads of cur_obs (and h, c) in the fp16-split arithmetic of uav_rollout, a = the
+ * first index of the largest logit (torch.argmax), one env step WITHOUT auto-reset (noise f64 [N][steps][2] standard normals,
+ * or NULL: the counter RNG keyed by (env, episode, step) as uav_env_step), and the step's record.  When the episode ends the
+ * env's active[n] is cleared and its state blob, h and c are left as that step left them; envs that come in with
+ * active[n] = 0 are never stepped.  State (env blob, cur_obs, h, c, active) carries across calls: k calls of steps / k steps
+ * give what one call of `steps` gives.
+ * policy_kind 0 = the reference's MLP 6-256-128 (params as uav_mlp_fwd; h, c NULL, `hidden` ignored), 1 = single-layer LSTM
+ * (params as uav_rollout), hidden 64 or 128.  cur_obs f32 [N][6], h, c f32 [N][hidden], active u8 [N]: in/out.
+ * Records: act i32 [N][steps], obs f32 [N][steps][6] (the observation the step returned -- the terminal one when done),
+ * pos f32 [N][steps][2] (agent_pos after the move), flags u8 [N][steps] (bit0 done, bit1 reached, bit2 not stepped: then
+ * act = -1, obs and pos 0).  nan_count (i32, device) += number of stepped env-steps with a NaN logit.
+ * Refused (non-zero status, uav_last_error names the reason): a handle not in UAV_ARITH_FP16X3, trend_k != 0, hidden not 64
+ * or 128. */
+int uav_greedy_episodes(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg /*host*/, int policy_kind,
+                        const float* params, int hidden, int steps, float* cur_obs, float* h, float* c, uint8_t* active,
+                        const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags, int32_t* nan_count,
+                        uav_stream stream);
+
 /* The tail of step t of a step-wise rollout as ONE launch (train_ppo2.0.py:165-198 after the recurrent layers): policy heads of
  * the top layer (heads[:, t] = y_t W_head^T + b_head, the sums of uav_gemm_f32's few-column kernel bit for bit; y = row t of a
  * [n][T][hidden] array given as the pointer to y[0][t] and its row stride y_stride floats, likewise heads / heads_stride),

@@ -462,13 +462,16 @@ __device__ __forceinline__ void heads_fwd(const Tiles<NC>& L, const float (&wh)[
 struct MlpRollBufs {
     float* cur_obs; float* obs; int32_t* act; float* rew; float* val; float* logp; float* done; uint8_t* flags;
     float* last_val; const int32_t* forced_act; const double* noise; int32_t* nan_count; float* info; float* heads;
+    uint8_t* active; float* pos;    // greedy episodes only: active u8 [N] in/out, agent_pos record [N][T][2]
 };
 
 constexpr size_t ROLL_LDS = (size_t)(Tiles<1>::FLOATS + 16 * WS2) * sizeof(float);
 
 // H3: the 256 x 128 layer on the fp16 matrix pipe (layer2_h3) -- the update kernel of the same arithmetic runs the same
 // code, so the rollout's log-probabilities stay bit-identical to the update's first forward pass.
-template <bool H3>
+// GREEDY: greedy evaluation episodes (uav_greedy_episodes; see rollout_lstm_kernel in rollout.hip for the record format):
+// argmax of the logits, no auto-reset, an ended or inactive env is never stepped.  GREEDY = false is the trainer's rollout.
+template <bool H3, bool GREEDY = false>
 __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBlob blob, int N, int T, uint64_t iter,
                                                             const float* __restrict__ params, MlpRollBufs B) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -526,12 +529,14 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
     for (int s = 0; s < 4; ++s) wh[s] = j < NH ? params[O_WH + j * H2 + 16 * w + 4 * s + kq] : 0.f;
     const float* bh = params + O_BH;
 
+    bool on = true, ran = true;                                  // GREEDY, wave 0: env active now / at entry
     if (w == 0 && lane < MT) {
         const int n = min(my_env, N - 1);
         es_s[lane] = env_load(blob, n);
         for (int k = 0; k < NVIS; ++k) myvis[k] = blob.visited[(size_t)n * NVIS + k];
 #pragma unroll
         for (int f = 0; f < 8; ++f) L.X[lane * 8 + f] = f < IN ? B.cur_obs[(size_t)n * IN + f] : 0.f;
+        if constexpr (GREEDY) on = ran = my_env < N && B.active[n] != 0;
     }
     lds_barrier();
 
@@ -592,6 +597,48 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
                     const float V = L.HD[lane * 8 + NA];
                     if (value_only) {
                         if (env_lane) B.last_val[my_env] = V;
+                    } else if constexpr (GREEDY) {
+                        // argmax of the logits (torch.argmax: the first of equal maxima), then the environment step without reset
+                        int a_sel = 0;
+                        float m = z[0];
+                        bool bad = (z[0] != z[0]);
+#pragma unroll
+                        for (int a = 1; a < NA; ++a) {
+                            bad |= (z[a] != z[a]);
+                            if (z[a] > m) { m = z[a]; a_sel = a; }
+                        }
+                        if (bad && env_lane && on) atomicAdd(B.nan_count, 1);
+                        const size_t row = (size_t)min(my_env, N - 1) * T + t;
+                        if (on) {
+                            const int eg = P.env_offset + my_env;
+                            EnvState es = es_s[lane];
+                            double z0, z1, wind_x, wind_y;
+                            if (B.noise) { z0 = B.noise[2 * row]; z1 = B.noise[2 * row + 1]; }
+                            else env_step_noise(P, eg, es, z0, z1);
+                            env_step_wind(es, z0, z1, wind_x, wind_y);
+                            StepOut so;
+                            env_step_core(P, eg, es, myvis, a_sel, wind_x, wind_y, so);
+                            if (env_lane) {
+#pragma unroll
+                                for (int f = 0; f < IN; ++f) B.obs[row * IN + f] = so.obs[f];
+                                B.act[row] = a_sel;
+                                B.flags[row] = (uint8_t)((so.done ? 1 : 0) | (so.reached ? 2 : 0));
+                                B.pos[row * 2] = es.px;
+                                B.pos[row * 2 + 1] = es.py;
+                            }
+#pragma unroll
+                            for (int f = 0; f < IN; ++f) L.X[lane * 8 + f] = so.obs[f];
+                            es_s[lane] = es;
+                            if (so.done) on = false;
+                        } else if (env_lane) {
+#pragma unroll
+                            for (int f = 0; f < IN; ++f) B.obs[row * IN + f] = 0.f;
+                            B.act[row] = -1;
+                            B.flags[row] = 4;
+                            B.pos[row * 2] = 0.f;
+                            B.pos[row * 2 + 1] = 0.f;
+                        }
+                        (void)V;
                     } else {
                         // softmax + Categorical(probs) sample / log_prob (train_ppo2.0.py:161-163,189), as rollout.hip
                         float m = z[0];
@@ -673,7 +720,8 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
             lds_barrier();                                       // next observations visible; HD / HP free again
         }
     }
-    if (env_lane) {
+    if (GREEDY && env_lane) B.active[my_env] = on ? 1 : 0;
+    if (env_lane && ran) {
         env_store(blob, my_env, es_s[lane]);
         for (int k = 0; k < NVIS; ++k) blob.visited[(size_t)my_env * NVIS + k] = myvis[k];
 #pragma unroll
@@ -1256,6 +1304,20 @@ int launch_rollout_mlp(uav_ctx* ctx, void* env_state, int n_env, const uav_env_c
         hipLaunchKernelGGL(rollout_mlp_kernel<false>, dim3((n_env + MT - 1) / MT), dim3(512), ROLL_LDS, st, P, blob, n_env, horizon,
                            iter, params, B);
     }
+    UAV_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- entry used by uav_greedy_episodes (rollout.hip) for policy_kind 0: the fp16-split form only (the caller checked the mode)
+int launch_greedy_mlp(const EnvParams& P, void* env_state, int n_env, const float* params, int steps, float* cur_obs,
+                      uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
+                      int32_t* nan_count, hipStream_t st) {
+    MlpRollBufs B{cur_obs, obs, act, nullptr, nullptr, nullptr, nullptr, flags, nullptr, nullptr, noise, nan_count, nullptr, nullptr,
+                  active, pos};
+    EnvBlob blob = env_blob_view(env_state, n_env);
+    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_mlp_kernel<true, true>), (int)ROLL_LDS));
+    hipLaunchKernelGGL((rollout_mlp_kernel<true, true>), dim3((n_env + MT - 1) / MT), dim3(512), ROLL_LDS, st, P, blob, n_env, steps,
+                       0, params, B);
     UAV_LAUNCH_CHECK();
     return 0;
 }

@@ -29,6 +29,9 @@ int launch_rollout_mlp(uav_ctx* ctx, void* env_state, int n_env, const uav_env_c
                        uint64_t iter, float* cur_obs, float* obs, int32_t* act, float* rew, float* val, float* logp,
                        float* done, uint8_t* flags, float* last_val, const int32_t* forced_act, const double* noise,
                        int32_t* nan_count, float* info, float* heads, hipStream_t st);
+int launch_greedy_mlp(const EnvParams& P, void* env_state, int n_env, const float* params, int steps, float* cur_obs,
+                      uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
+                      int32_t* nan_count, hipStream_t st);
 
 constexpr int RMT = 16;
 
@@ -71,6 +74,7 @@ struct RolloutBufs {
     float* info;                // optional [N][T][10]: 5 reward parts of environment.py:161-167, obs[2], agent_pos, source_pos of the step
     float* heads;               // optional [N][T][NA+1]: logits | value of the step
     float* stash; float* y;     // optional: BPTT stash [N][T][6H] + y [N][T][H], so PPO epoch 0 skips its forward pass
+    uint8_t* active; float* pos;  // greedy episodes only: active u8 [N] in/out, agent_pos record [N][T][2]
 };
 
 // The recurrent product h W_hh^T runs on the fp16 matrix pipe at f32 accuracy (two-piece operand split, three piece
@@ -80,7 +84,12 @@ struct RolloutBufs {
 // pieces of its slice sit in LDS and are read back as lane-contiguous b128 fragments -- so the f64 env chain has the
 // register file to itself; the two roles run separate, barrier-matched time loops, which keeps the other waves' 128
 // weight VGPRs out of wave 0's live set.
-template <int H, int NA>
+// GREEDY: one greedy evaluation episode per env (evaluate_with_lstm.py's loop) instead of a training rollout -- argmax of the
+// logits instead of a sample, no auto-reset, and an env whose episode has ended (or that came in with active[n] = 0) is never
+// stepped again: its blob, h and c keep the values of its last step.  kbuf holds the per-env active flag then.  The record
+// per step is the action, the observation the step returned (the terminal one when done), agent_pos after the move, and flags
+// (bit0 done, bit1 reached, bit2 not stepped: act -1, obs and pos 0).  GREEDY = false is the trainer's rollout, unchanged.
+template <int H, int NA, bool GREEDY = false>
 __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, EnvBlob blob, int N, int T,
                                                                         uint64_t iter, const float* __restrict__ params,
                                                                         RolloutBufs B) {
@@ -193,13 +202,19 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         const float h_in[4] = {hv.x, hv.y, hv.z, hv.w};
         put_h(h_in);
     }
+    bool ran = true;                           // GREEDY: the env came in active (else its state is never written back)
     if (is_env_wave && lane < RMT) {
         const int n = min(my_env, N - 1);
         es_s[lane] = env_load(blob, n);
         for (int k = 0; k < NVIS; ++k) myvis[k] = blob.visited[(size_t)n * NVIS + k];
 #pragma unroll
         for (int f = 0; f < 8; ++f) xbuf[lane * 8 + f] = f < 6 ? B.cur_obs[(size_t)n * 6 + f] : 0.f;
-        kbuf[lane] = 1.f;
+        if constexpr (GREEDY) {
+            ran = my_env < N && B.active[n] != 0;
+            kbuf[lane] = ran ? 1.f : 0.f;
+        } else {
+            kbuf[lane] = 1.f;
+        }
     }
     lds_barrier();
 
@@ -281,7 +296,8 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
             acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wxw[(2 * q) * 64], ax.x, acc[q], 0, 0, 0);
             acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wxw[(2 * q + 1) * 64], ax.y, acc[q], 0, 0, 0);
         }
-        const bool st = B.stash && !value_only && live;       // the update's first epoch reuses this forward pass
+        const bool st = !GREEDY && B.stash && !value_only && live;       // the update's first epoch reuses this forward pass
+        const bool on = !GREEDY || kbuf[j] != 0.f;            // GREEDY: an ended env's h and c stay as they are
         const unsigned row = (unsigned)(n0 + j) * T + t;       // N*T*6H < 2^32 elements is checked at launch
         float* sp = B.stash + (size_t)row * (6 * H) + uo;
         float gi[4], gf[4], gg[4], cc[4];
@@ -301,19 +317,22 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         for (int r = 0; r < 4; ++r) {
             go[r] = r_sigmoid(acc[3][r]);
             hh[r] = go[r] * r_tanh(cc[r]);
-            if (!value_only) c_reg[r] = cc[r];
+            if (!value_only && on) c_reg[r] = cc[r];
         }
-        put_h(hh);
+        if (on) put_h(hh);
+        // GREEDY: h of every stepped step goes straight to B.h (4 more live VGPRs beside the gate waves' 128 weight registers spill)
+        if (GREEDY && on && live)
+            *reinterpret_cast<float4*>(B.h + (size_t)(n0 + j) * H + uo) = float4{hh[0], hh[1], hh[2], hh[3]};
         if (st) {
             *reinterpret_cast<float4*>(sp + 3 * H) = float4{go[0], go[1], go[2], go[3]};
             *reinterpret_cast<float4*>(B.y + (size_t)row * H + uo) = float4{hh[0], hh[1], hh[2], hh[3]};
         }
-        if (t == T - 1 && live)
+        if (!GREEDY && t == T - 1 && live)
             *reinterpret_cast<float4*>(B.h + (size_t)(n0 + j) * H + uo) = float4{hh[0], hh[1], hh[2], hh[3]};
     };
     // episode ended at step t: the recurrent state restarts from zero (acc falls back to the bias)
     auto keep_fixup = [&](int t) {
-        if (kbuf[j] == 0.f) {
+        if (!GREEDY && kbuf[j] == 0.f) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) c_reg[r] = 0.f;
             bias_acc();
@@ -327,7 +346,16 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
     // of the next step, which that wave passes after its reads have completed.  (Spreading the stores over three gate
     // waves measured slower, 792 vs 773 us per rollout.)
     auto store_transition = [&](int t) {
-        if (lane < RMT && n0 + lane < N) {
+        if (GREEDY && lane < RMT && n0 + lane < N) {                   // [action, -, -, -, -, flags, -, -] | [obs 6, agent_pos 2]
+            const size_t row = (size_t)(n0 + lane) * T + t;
+            const float* to = trs + RMT * 8 + lane * 8;
+#pragma unroll
+            for (int f = 0; f < 6; ++f) B.obs[row * 6 + f] = to[f];
+            B.pos[row * 2] = to[6];
+            B.pos[row * 2 + 1] = to[7];
+            B.act[row] = __float_as_int(trs[lane * 8]);
+            B.flags[row] = (uint8_t)__float_as_int(trs[lane * 8 + 5]);
+        } else if (!GREEDY && lane < RMT && n0 + lane < N) {
             const size_t row = (size_t)(n0 + lane) * T + t;
             const float* tq = trs + lane * 8;
 #pragma unroll
@@ -393,7 +421,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                 double z0, z1;
                 const int eg = P.env_offset + my_env;
                 const size_t row = (size_t)min(my_env, N - 1) * T + t;
-                if (!B.forced_act) u_act = philox4x32_10(P.seed, (uint32_t)t, (uint32_t)eg, (uint32_t)iter, RNG_ACTION).x;
+                if (!GREEDY && !B.forced_act) u_act = philox4x32_10(P.seed, (uint32_t)t, (uint32_t)eg, (uint32_t)iter, RNG_ACTION).x;
                 if (B.noise) { z0 = B.noise[2 * row]; z1 = B.noise[2 * row + 1]; }
                 else env_step_noise(P, eg, es_s[lane], z0, z1);
                 env_step_wind(es_s[lane], z0, z1, wind_x, wind_y);
@@ -432,6 +460,39 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                 const float V = hd[lane * 16 + NA] + bh[NA];
                 if (value_only) {
                     if (env_lane) B.last_val[my_env] = V;
+                } else if constexpr (GREEDY) {
+                    // argmax of the logits (torch.argmax: the first of equal maxima), then the environment step without reset
+                    const bool on = kbuf[lane] != 0.f;
+                    int a_sel = 0;
+                    float m = z[0];
+                    bool bad = (z[0] != z[0]);
+#pragma unroll
+                    for (int a = 1; a < NA; ++a) {
+                        bad |= (z[a] != z[a]);
+                        if (z[a] > m) { m = z[a]; a_sel = a; }
+                    }
+                    if (bad && env_lane && on) atomicAdd(B.nan_count, 1);
+                    float* tr = trs + lane * 8;
+                    float* to = trs + RMT * 8 + lane * 8;
+                    if (on) {
+                        EnvState es = es_s[lane];
+                        StepOut so;
+                        env_step_core(P, P.env_offset + my_env, es, myvis, a_sel, wind_x, wind_y, so);
+                        tr[0] = __int_as_float(a_sel);
+                        tr[5] = __int_as_float((so.done ? 1 : 0) | (so.reached ? 2 : 0));
+#pragma unroll
+                        for (int f = 0; f < 6; ++f) { to[f] = so.obs[f]; xbuf[lane * 8 + f] = so.obs[f]; }
+                        to[6] = es.px;
+                        to[7] = es.py;
+                        es_s[lane] = es;
+                        if (so.done) kbuf[lane] = 0.f;
+                    } else {
+                        tr[0] = __int_as_float(-1);
+                        tr[5] = __int_as_float(4);
+#pragma unroll
+                        for (int f = 0; f < 8; ++f) to[f] = 0.f;
+                    }
+                    (void)V;
                 } else {
                     // softmax + Categorical(probs) sample / log_prob (train_ppo2.0.py:161-163,189)
                     float m = z[0];
@@ -523,7 +584,8 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
     }
     // ------------------------------------------------------------------ write back persistent state
     if (live) *reinterpret_cast<float4*>(B.c + (size_t)(n0 + j) * H + uo) = float4{c_reg[0], c_reg[1], c_reg[2], c_reg[3]};
-    if (env_lane) {
+    if (GREEDY && env_lane) B.active[my_env] = kbuf[lane] != 0.f ? 1 : 0;
+    if (env_lane && ran) {
         env_store(blob, my_env, es_s[lane]);
         for (int k = 0; k < NVIS; ++k) blob.visited[(size_t)my_env * NVIS + k] = myvis[k];
 #pragma unroll
@@ -531,12 +593,12 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
     }
 }
 
-template <int H>
+template <int H, bool GREEDY = false>
 static int launch_rollout(const EnvParams& P, EnvBlob blob, int N, int T, uint64_t iter, const float* params,
                           const RolloutBufs& B, hipStream_t st) {
     const dim3 grid((N + RMT - 1) / RMT), block(H * 4);
-    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_lstm_kernel<H, 5>), (int)RGeom<H>::LDS));
-    hipLaunchKernelGGL((rollout_lstm_kernel<H, 5>), grid, block, RGeom<H>::LDS, st, P, blob, N, T, iter, params, B);
+    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_lstm_kernel<H, 5, GREEDY>), (int)RGeom<H>::LDS));
+    hipLaunchKernelGGL((rollout_lstm_kernel<H, 5, GREEDY>), grid, block, RGeom<H>::LDS, st, P, blob, N, T, iter, params, B);
     UAV_LAUNCH_CHECK();
     return 0;
 }
@@ -687,4 +749,34 @@ extern "C" int uav_rollout(uav_ctx* ctx, void* env_state, int n_env, const uav_e
         case 128: return launch_rollout<128>(P, blob, n_env, horizon, iter, params, B, as_stream(stream));
     }
     UAV_REQUIRE(false, "uav_rollout: hidden=%d unsupported (64, 128)", hidden);
+}
+
+extern "C" int uav_greedy_episodes(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg, int policy_kind,
+                                   const float* params, int hidden, int steps, float* cur_obs, float* h, float* c,
+                                   uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
+                                   int32_t* nan_count, uav_stream stream) {
+    UAV_REQUIRE(ctx && env_state && params && cur_obs && active && act && obs && pos && flags && nan_count,
+                "uav_greedy_episodes: NULL argument");
+    UAV_REQUIRE(n_env > 0 && steps > 0, "uav_greedy_episodes: n_env=%d steps=%d", n_env, steps);
+    UAV_REQUIRE(policy_kind == 0 || policy_kind == 1, "uav_greedy_episodes: policy_kind %d (0 = MLP, 1 = LSTM)", policy_kind);
+    UAV_REQUIRE(ctx->lstm_arith == UAV_ARITH_FP16X3,
+                "uav_greedy_episodes: the fused greedy kernels exist in the fp16x3 arithmetic only (handle mode %d)", ctx->lstm_arith);
+    EnvParams P;
+    int rc = env_params_from_cfg(ctx, cfg, n_env, P);
+    if (rc) return rc;
+    UAV_REQUIRE(P.trend_k == 0, "uav_greedy_episodes: trend_k=%d unsupported (the fused kernels take 6 observation features)",
+                P.trend_k);
+    UAV_REQUIRE((int64_t)n_env * steps * 6 < (1ll << 31), "uav_greedy_episodes: n_env * steps too large");
+    if (policy_kind == 0)
+        return launch_greedy_mlp(P, env_state, n_env, params, steps, cur_obs, active, noise, act, obs, pos, flags, nan_count,
+                                 as_stream(stream));
+    UAV_REQUIRE(h && c, "uav_greedy_episodes: LSTM policy needs h, c");
+    RolloutBufs B{cur_obs, h, c, obs, act, nullptr, nullptr, nullptr, nullptr, flags, nullptr, nullptr, nullptr, noise, nan_count,
+                  nullptr, nullptr, nullptr, nullptr, active, pos};
+    EnvBlob blob = env_blob_view(env_state, n_env);
+    switch (hidden) {
+        case 64: return launch_rollout<64, true>(P, blob, n_env, steps, 0, params, B, as_stream(stream));
+        case 128: return launch_rollout<128, true>(P, blob, n_env, steps, 0, params, B, as_stream(stream));
+    }
+    UAV_REQUIRE(false, "uav_greedy_episodes: hidden=%d unsupported by the fused kernel (64, 128)", hidden);
 }

@@ -6,9 +6,15 @@ and PPOV2.1/evaluate_with_lstm.py (PeakAndStopPredictor :11-27; stop rule :69-77
 one uav_mlp_fwd / LSTM step per time step, and the stop predictors run through uav_lstm_fwd + uav_gemm_f32 +
 uav_ln_relu.  Same class names, state_dict keys, metrics keys and decision rules as the reference; per-episode
 Python scalars become device tensors of length N.  No CPU fallback: everything goes through uavppo.ops.
+
+evaluate() also takes a policy object (the vectorised trainer's LSTMActorCritic / MLPActorCritic, or model.PPOActorCritic).
+Where uav_greedy_episodes covers it (single-layer LSTM h = 64 / 128 or the reference's MLP, 6 observation features, the
+fp16-split arithmetic, parameters inside that arithmetic's range) whole chunks of steps run in one launch each and the stop
+controllers are replayed over the chunk's records; everything else steps one launch sequence per time step.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 
@@ -19,6 +25,9 @@ from config import EVALUATE_SIZE, SUCCESS_DISTANCE_THRESHOLD
 from uavppo import ops
 
 F32 = torch.float32
+
+
+_MLP_SHAPE = (6, 256, 128, 5)            # in, h1, h2, n_act of the fused MLP kernels
 
 
 def _xavier(shape, gen):
@@ -175,15 +184,110 @@ class ThresholdController:
         return (step_count >= self.min_activate_steps) & has & ((current_conc >= thr) | (mean >= thr))
 
 
+def _policy_core(policy):
+    """(kind, policy) of a policy object: "lstm" for LSTMActorCritic, "mlp" for MLPActorCritic or model.PPOActorCritic (an
+    nn.Module, hence callable: the policy classes are recognised before anything is taken for a policy_probs function)."""
+    from uavppo.policy import LSTMActorCritic, MLPActorCritic
+    core = getattr(policy, "core", policy)
+    if isinstance(core, LSTMActorCritic):
+        return "lstm", core
+    if isinstance(core, MLPActorCritic):
+        return "mlp", core
+    if callable(policy):
+        return None
+    raise TypeError(f"evaluate: expected a callable, LSTMActorCritic, MLPActorCritic or PPOActorCritic, got {type(policy).__name__}")
+
+
+def _out_of_range(kind, core):
+    """max |param| (NaN not counted) against the trainer's fp16-split limit: (value, limit, out of range)."""
+    from uavppo.trainer import MLP_RANGE_LIMITS, RANGE_LIMITS
+    limit = RANGE_LIMITS[0] if kind == "lstm" else MLP_RANGE_LIMITS[0]
+    a = core.flat.detach().abs()
+    pmax = float(torch.where(torch.isnan(a), torch.zeros_like(a), a).max())
+    return pmax, limit, not pmax < limit
+
+
+def fused_refusal(policy, env):
+    """Why uav_greedy_episodes cannot run `policy` on `env` (None when it can)."""
+    kind, core = _policy_core(policy)
+    mode = ops.get_lstm_arith(env.device)
+    if mode != "fp16x3":
+        return f"the handle's arithmetic is {mode}; the fused greedy kernels exist in fp16x3 only"
+    if env.trend_k:
+        return f"trend_k = {env.trend_k}; the fused greedy kernels take 6 observation features"
+    if kind == "lstm":
+        if core.num_layers != 1 or core.hidden not in (64, 128) or core.obs_dim != 6 or core.n_act != 5:
+            return (f"LSTM {core.num_layers} layer(s), hidden {core.hidden}, obs_dim {core.obs_dim}, {core.n_act} actions; "
+                    f"the fused kernel covers one layer of hidden 64 / 128, obs_dim 6, 5 actions")
+    elif (core.in_dim, core.h1, core.h2, core.n_act) != _MLP_SHAPE:
+        return f"MLP {core.in_dim}-{core.h1}-{core.h2}-{core.n_act}; the fused kernel covers 6-256-128-5 only"
+    # NaN parameters are not out of range: they reach the kernel and come back as nan_count ("NaN in probs")
+    pmax, limit, out = _out_of_range(kind, core)
+    if out:
+        return f"max |param| = {pmax:g} is not below {limit:g}, the fp16-split range limit (uavppo/trainer.py)"
+    return None
+
+
+def _stepwise_policy_probs(kind, core, env):
+    """policy_probs for the step-wise loop: the LSTM's (h, c) start at zero and are carried through LSTMActorCritic.step.
+    nan[0] counts steps whose logits hold a NaN among envs whose episode has not ended (env.done of the previous step).
+    Parameters beyond the fp16-split range on a handle in that mode: the policy's own calls run in bf16x6, as the trainer
+    switches (VecPPOTrainer._decide); the handle's mode is restored after each call, so the stop predictors keep theirs."""
+    N, A = env.num_envs, core.n_act
+    wide = ops.get_lstm_arith(env.device) == "fp16x3" and _out_of_range(kind, core)[2]
+    nan = torch.zeros(1, dtype=torch.int64, device=env.device)
+    live = torch.ones(N, dtype=torch.bool, device=env.device)
+    state = core.zero_state(N) if kind == "lstm" else None
+    work, calls = {}, [0]
+
+    def probs(obs):
+        if calls[0]:
+            live.logical_and_(env.done <= 0.5)       # env.done of the previous step (stale before the first one)
+        calls[0] += 1
+        with ops.lstm_arith("bf16x6", env.device) if wide else contextlib.nullcontext():
+            if kind == "lstm":
+                logits = core.step(obs, state[0], state[1], work=work)[:, :A]
+            else:
+                logits = core.heads(obs.contiguous())[:, :A]
+        nan.add_((torch.isnan(logits).any(1) & live).sum())
+        return logits
+
+    return probs, nan
+
+
 @torch.no_grad()
 def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21=20, noise=None, max_steps=None,
-             success_distance=SUCCESS_DISTANCE_THRESHOLD):
+             success_distance=SUCCESS_DISTANCE_THRESHOLD, fused=None, chunk=None):
     """One greedy episode per environment of `env` (a uavppo VecMethaneEnv), all N together.
 
-    policy_probs(obs [N, obs_dim]) -> probs or logits [N, 5] (argmax is taken);
+    policy_probs(obs [N, obs_dim]) -> probs or logits [N, 5] (argmax is taken), or a policy object: LSTMActorCritic,
+    MLPActorCritic or model.PPOActorCritic (the LSTM starts every episode from zero state);
     controller: ThresholdController (PPOV2.0 rule) or None; peak_stop: PeakAndStopPredictor (PPOV2.1 rule) or None;
     noise: optional f64 [steps, N, 2] (parity tests).  Returns the reference's metrics dict (deviations, steps, success,
-    stopped_early [, peak_pred]) as numpy arrays of length N."""
+    stopped_early [, peak_pred]) as numpy arrays of length N.
+    fused (policy objects): None = uav_greedy_episodes where it covers the policy (fused_refusal), else step-wise (parameters
+    beyond the fp16-split range then run in bf16x6); True = the fused kernel or a RuntimeError naming why not; False =
+    step-wise.  chunk: steps per fused launch (default: 250, or 50 with a stop controller, whose rules are replayed over each
+    chunk's records).  A NaN logit of a policy object raises RuntimeError("NaN in probs").  A policy_probs function takes
+    neither fused=True nor chunk."""
+    pc = _policy_core(policy_probs)
+    if pc is None and fused:
+        raise RuntimeError("evaluate(fused=True): a policy_probs function has no fused kernel; pass the policy object")
+    if pc is None and chunk is not None:
+        raise ValueError("evaluate(chunk=...): chunks belong to the fused path of a policy object")
+    if pc is not None:
+        kind, core = pc
+        why = fused_refusal(policy_probs, env) if fused is not False else "fused=False"
+        if fused and why is not None:
+            raise RuntimeError(f"evaluate(fused=True): {why}")
+        if why is None:
+            return _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
+                                   chunk)
+        probs, nan = _stepwise_policy_probs(kind, core, env)
+        out = evaluate(probs, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance)
+        if int(nan.item()) > 0:
+            raise RuntimeError("NaN in probs")                                   # model.py:47-49
+        return out
     N, dev = env.num_envs, env.device
     obs = env.reset()
     _, src, _, _ = env.peek()
@@ -238,22 +342,134 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     return out
 
 
-def main(num_envs=1000, model_dir="model", device="cuda"):
-    """The reference's main() (evaluate_with_lstm.py:39-134) with its 1000 episodes run as 1000 parallel environments."""
+def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance, chunk):
+    """evaluate() on uav_greedy_episodes: `chunk` steps per launch; the metrics (and the stop controllers) are computed from
+    the records with the formulas of evaluate()'s step-wise loop, so the same actions give the same arrays bit for bit.  An
+    env the kernel has ended stays frozen (no auto-reset); an env a controller stopped is passed as inactive to the next chunk."""
+    N, dev = env.num_envs, env.device
+    H = core.hidden if kind == "lstm" else 0
+    env.reset()
+    _, src, _, _ = env.peek()
+    src = src.clone()
+    cur_obs = env.obs
+    h = torch.zeros(N, H, dtype=F32, device=dev) if H else None
+    c = torch.zeros(N, H, dtype=F32, device=dev) if H else None
+    kernel_active = torch.ones(N, dtype=torch.uint8, device=dev)
+    nan_count = torch.zeros(1, dtype=torch.int32, device=dev)
+    active = torch.ones(N, dtype=torch.bool, device=dev)
+    steps = torch.zeros(N, dtype=torch.int64, device=dev)
+    stopped = torch.zeros(N, dtype=torch.bool, device=dev)
+    final_pos = torch.zeros(N, 2, dtype=torch.float64, device=dev)
+    peak_pred = torch.full((N,), float("nan"), dtype=torch.float64, device=dev)
+    if controller is not None:
+        controller.reset()
+    traj = torch.zeros(N, window_size_v21, dtype=torch.float64, device=dev) if peak_stop is not None else None
+    replay = controller is not None or peak_stop is not None
+    limit = max_steps or env.max_steps
+    chunk = int(chunk or (50 if replay else 250))
+    last_pos = None
+    t0 = 0
+    while t0 < limit:
+        k = min(chunk, limit - t0)
+        recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, 6, dtype=F32, device=dev),
+                "pos": torch.empty(N, k, 2, dtype=F32, device=dev), "flags": torch.empty(N, k, dtype=torch.uint8, device=dev)}
+        nz = None if noise is None else noise[t0:t0 + k].transpose(0, 1).contiguous()
+        ops.greedy_episodes(env.state, N, env.cfg(), core.flat, H, k, cur_obs, h, c, kernel_active, recs, noise=nz,
+                            nan_count=nan_count)
+        done_c = (recs["flags"] & 1) != 0
+        if replay:
+            for i in range(k):                   # evaluate()'s loop body, step t = t0 + i + 1, on the records
+                t = t0 + i + 1
+                done_b = done_c[:, i]
+                cur = recs["obs"][:, i, 2].to(torch.float64) * 100.0          # the record is the terminal obs where done
+                pos_end = torch.where(done_b[:, None], recs["obs"][:, i, :2].to(torch.float64) * 500.0,
+                                      recs["pos"][:, i].to(torch.float64))
+                stop_now = torch.zeros(N, dtype=torch.bool, device=dev)
+                if controller is not None:
+                    controller.push(cur)
+                    if t % 10 == 0:
+                        controller.update_threshold(active)
+                    stop_now |= controller.should_stop(cur, t)
+                if peak_stop is not None:
+                    traj = torch.roll(traj, -1, dims=1)
+                    traj[:, -1] = cur
+                    if t >= window_size_v21:
+                        peak, prob = peak_stop((traj / 100.0).to(F32))
+                        hit = prob > 0.8
+                        peak_pred = torch.where(hit & active, peak.to(torch.float64), peak_pred)
+                        stop_now |= hit
+                ended = active & (done_b | stop_now)
+                steps = torch.where(ended, torch.full_like(steps, t), steps)
+                stopped |= ended & stop_now
+                final_pos = torch.where(ended[:, None], pos_end, final_pos)
+                active &= ~ended
+            kernel_active &= active.to(torch.uint8)
+        else:                                    # no controller: an episode ends exactly at its first done record
+            ended = active & done_c.any(1)
+            first = done_c.to(torch.int32).argmax(1)
+            rows = torch.arange(N, device=dev)
+            pos_end = recs["obs"][rows, first, :2].to(torch.float64) * 500.0
+            steps = torch.where(ended, (first + (t0 + 1)).to(torch.int64), steps)
+            final_pos = torch.where(ended[:, None], pos_end, final_pos)
+            active &= ~ended
+        last_pos = recs["pos"][:, k - 1]
+        t0 += k
+        if not bool(active.any()):
+            break
+    if int(nan_count.item()) > 0:
+        raise RuntimeError("NaN in probs")                                       # model.py:47-49
+    # episodes cut off by `max_steps`: still active, so stepped through the last record
+    if bool(active.any()):
+        final_pos = torch.where(active[:, None], last_pos.to(torch.float64), final_pos)
+        steps = torch.where(active, torch.full_like(steps, limit), steps)
+    deviation = torch.linalg.norm(final_pos - src, dim=1)
+    out = {"deviations": deviation.cpu().numpy(), "steps": steps.cpu().numpy(),
+           "success": (deviation <= success_distance).cpu().numpy(), "stopped_early": stopped.cpu().numpy()}
+    if peak_stop is not None:
+        out["peak_pred"] = peak_pred.cpu().numpy()
+    return out
+
+
+def load_lstm_policy(path, device="cuda"):
+    """An LSTMActorCritic from a vectorised-trainer checkpoint (train_ppo2.0.py's _save: lstm.*, actor.*, critic.*), its
+    obs_dim / hidden / layers / actions read off the tensor shapes."""
+    from uavppo.policy import LSTMActorCritic
+    sd = torch.load(path, map_location="cpu")
+    layers = sum(1 for k in sd if k.startswith("lstm.weight_ih_l"))
+    w0 = sd["lstm.weight_ih_l0"]
+    pol = LSTMActorCritic(obs_dim=int(w0.shape[1]), hidden=int(w0.shape[0]) // 4, num_layers=layers,
+                          n_act=int(sd["actor.weight"].shape[0]), device=device)
+    pol.load_state_dict(sd)
+    return pol
+
+
+def main(num_envs=1000, model_dir="model", device="cuda", policy="mlp"):
+    """The reference's main() (evaluate_with_lstm.py:39-134) with its 1000 episodes run as 1000 parallel environments.
+    policy="mlp": the reference's PPOActorCritic; "lstm": the vectorised trainer's LSTM actor-critic (same file name)."""
     from model import PPOActorCritic
     from uavppo.vec_env import VecMethaneEnv
-    ppo_model = PPOActorCritic(6, 5, device=device)
+    if policy not in ("mlp", "lstm"):
+        raise ValueError(f"main: policy must be 'mlp' or 'lstm', got {policy!r}")
     lstm_model = ConcentrationThresholdPredictor(device=device)
     try:
-        ppo_model.load_state_dict(torch.load(os.path.join(model_dir, "ppo_successful_models.pth"), map_location="cpu"))
+        path = os.path.join(model_dir, "ppo_successful_models.pth")
+        if policy == "lstm":
+            ppo_model = load_lstm_policy(path, device)
+        else:
+            ppo_model = PPOActorCritic(6, 5, device=device)
+            ppo_model.load_state_dict(torch.load(path, map_location="cpu"))
         lstm_model.load_state_dict(torch.load(os.path.join(model_dir, "lstm_threshold_predictor.pth"), map_location="cpu"))
         scaler_params = np.load(os.path.join(model_dir, "scaler_params.npy"))
     except FileNotFoundError as e:
         print(f"model files missing: {e}")
         return None
-    env = VecMethaneEnv(num_envs, "v2.0", device)
+    trend_k = ppo_model.obs_dim - 6 if policy == "lstm" else 0
+    env = VecMethaneEnv(num_envs, "v2.0", device, trend_k=trend_k)
     controller = ThresholdController(lstm_model, (scaler_params.min(), scaler_params.max()), num_envs, device=device)
-    metrics = evaluate(lambda o: ppo_model.core.heads(o)[:, :5], env, controller)     # argmax of logits == argmax of probs
+    if policy == "lstm":
+        metrics = evaluate(ppo_model, env, controller)
+    else:
+        metrics = evaluate(lambda o: ppo_model.core.heads(o)[:, :5], env, controller)     # argmax of logits == argmax of probs
     ok = metrics["success"]
     print("===== validation =====")
     print(f"mean deviation: {metrics['deviations'].mean():.2f} +- {metrics['deviations'].std():.2f} px")
@@ -267,4 +483,5 @@ def main(num_envs=1000, model_dir="model", device="cuda"):
 
 
 if __name__ == "__main__":
-    main()
+    import sys
+    main(policy="lstm" if "--lstm" in sys.argv[1:] else "mlp")

@@ -93,6 +93,7 @@ SIGNATURES = {
     "uav_env_materialise": (I32, [P, P, I32, C.POINTER(EnvCfg), I32, P, P]),
     "uav_rollout": (I32, [P, P, I32, C.POINTER(EnvCfg), I32, P, I32, I32, U64, P, P, P, P, P, P, P, P, P, P,
                           P, P, P, P, P, P, P, P, P, P]),
+    "uav_greedy_episodes": (I32, [P, P, I32, C.POINTER(EnvCfg), I32, P, I32, I32, P, P, P, P, P, P, P, P, P, P, P]),
     "uav_rccl_version": (I32, [C.POINTER(C.c_int)]),
     "uav_comm_unique_id": (I32, [P]),
     "uav_comm_init": (I32, [P, P, I32, I32]),

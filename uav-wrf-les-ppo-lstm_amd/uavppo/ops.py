@@ -867,3 +867,25 @@ def rollout_mlp(env_state, n_env, cfg, params, horizon, it, cur_obs, bufs, last_
                             _p(heads, F32, (N, T, 6), "heads"), _stream()), "uav_rollout")
     if _t is not None:
         _t.record()
+
+
+def greedy_episodes(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise=None, nan_count=None):
+    """`steps` steps of greedy evaluation episodes on the fused rollout kernels (uav_greedy_episodes): argmax action, no
+    auto-reset, ended / inactive envs frozen.  hidden = 0 (h, c None): the reference's MLP; 64 / 128: the single-layer LSTM.
+    cur_obs [N,6], h, c [N,H], active u8 [N] are in/out; recs: dict act i32 [N,steps], obs [N,steps,6], pos [N,steps,2],
+    flags u8 [N,steps] (bit0 done, bit1 reached, bit2 not stepped); noise f64 [N,steps,2] or None."""
+    N, T = n_env, steps
+    kind = 0 if hidden == 0 else 1
+    if nan_count is None:
+        nan_count = torch.zeros(1, dtype=I32, device=cur_obs.device)
+    _t = KERNEL_TIMER.bracket("greedy")
+    check(lib().uav_greedy_episodes(_h(cur_obs), _p(env_state, U8, name="env state"), N, C.byref(cfg), kind,
+                                    _p(params, F32, name="params"), int(hidden), T, _p(cur_obs, F32, (N, 6), "cur_obs"),
+                                    _p(h, F32, (N, hidden), "h") if kind else None,
+                                    _p(c, F32, (N, hidden), "c") if kind else None,
+                                    _p(active, U8, (N,), "active"), _p(noise, F64, (N, T, 2), "noise"),
+                                    _p(recs["act"], I32, (N, T), "act"), _p(recs["obs"], F32, (N, T, 6), "obs"),
+                                    _p(recs["pos"], F32, (N, T, 2), "pos"), _p(recs["flags"], U8, (N, T), "flags"),
+                                    _p(nan_count, I32, (1,), "nan_count"), _stream()), "uav_greedy_episodes")
+    if _t is not None:
+        _t.record()

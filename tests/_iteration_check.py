@@ -48,6 +48,76 @@ def _oracle_step(p, x, k, h0, c0, act, logp, adv, ret, val, sl, nbT):
     return {n: leaf[n].grad.detach() for n in p}, [float(pl.detach()), float(vl.detach()), float(ent.detach())]
 
 
+def oracle_gradient_chunked(params, buf, h0, c0, adv_n, ret, chunk=256, envs=None):
+    """The PPO loss and its gradient at parameters `params` (a policy, or the oracle's named tensors) over the rollout `buf`
+    (obs [N,T,I], keep / act / logp / val [N,T]; numpy or torch, any device), evaluated in float64 env chunk by env chunk.
+    Env rows are independent problems and the loss is a mean of per-sample terms with one global 1/n, n = N*T, so the
+    gradient of the samples of env set S is the chunk's own mean gradient times |S|*T / n, and the full-batch gradient is
+    the f64 sum of those.  `envs`: a list of env index sets (ranges, lists, arrays), one chunk each; default: consecutive
+    chunks of `chunk` envs covering all N.  adv_n, ret: [N*T] or [N,T], fed as given (the caller decides whose).
+
+    Returns a dict: 'grad' (the chunks' sum) and 'chunks' (one per env set, already scaled by |S|*T / n), named as
+    named_from_flat; 'logits' [N,T,A] and 'value' [N,T] (NaN for envs outside every set); 'losses' [policy, value, entropy]
+    and 'total' (the same weights as po.ppo_losses), each summed over the sets with the same |S|*T / n; 'seconds'."""
+    import time
+    t0 = time.perf_counter()
+    p = cpu_params(params) if hasattr(params, "named_views") else params
+    p = {n: torch.as_tensor(v).detach().cpu().double() for n, v in p.items()}
+
+    def host(a, dtype):
+        return torch.as_tensor(a).detach().cpu().to(dtype)
+
+    obs = host(buf["obs"], torch.float64)
+    N, T = obs.shape[:2]
+    keep = host(buf["keep"], torch.float64)
+    act = host(buf["act"], torch.int64)
+    logp, val = host(buf["logp"], torch.float64), host(buf["val"], torch.float64)
+    adv, rt = host(adv_n, torch.float64).reshape(N, T), host(ret, torch.float64).reshape(N, T)
+    h0, c0 = host(h0, torch.float64), host(c0, torch.float64)
+    A = p["actor.weight"].shape[0]
+    if envs is None:
+        envs = [range(s, min(s + chunk, N)) for s in range(0, N, chunk)]
+    n = N * T
+    names = list(p)
+    out = {"grad": {k: torch.zeros_like(v) for k, v in p.items()}, "chunks": [],
+           "logits": torch.full((N, T, A), float("nan"), dtype=torch.float64),
+           "value": torch.full((N, T), float("nan"), dtype=torch.float64), "losses": [0.0, 0.0, 0.0], "total": 0.0}
+    for s in envs:
+        idx = torch.as_tensor(list(s) if isinstance(s, range) else s, dtype=torch.int64).reshape(-1)
+        w = idx.numel() * T / n
+        leaf = {k: v.clone().requires_grad_(True) for k, v in p.items()}
+        probs, value, logits, _ = po.lstm_policy_forward(leaf, obs[idx].transpose(0, 1), h0[:, idx], c0[:, idx],
+                                                         keep=keep[idx].transpose(0, 1))
+        probs, value, logits = probs.transpose(0, 1), value.transpose(0, 1), logits.transpose(0, 1)     # [n_s, T, ...]
+        total, pl, vl, ent = po.ppo_losses(probs.reshape(-1, A), value.reshape(-1), act[idx].reshape(-1),
+                                           logp[idx].reshape(-1), adv[idx].reshape(-1), rt[idx].reshape(-1),
+                                           val[idx].reshape(-1))
+        grads = torch.autograd.grad(total, [leaf[k] for k in names])          # frees this chunk's graph
+        g = {k: gk * w for k, gk in zip(names, grads)}
+        for k in names:
+            out["grad"][k] += g[k]
+        out["chunks"].append(g)
+        out["logits"][idx] = logits.detach()
+        out["value"][idx] = value.detach()
+        for i, l in enumerate((pl, vl, ent)):
+            out["losses"][i] += float(l.detach()) * w
+        out["total"] += float(total.detach()) * w
+        del leaf, logits, value, probs, total, pl, vl, ent, grads
+    out["seconds"] = time.perf_counter() - t0
+    return out
+
+
+def grad_errors(got, want, gmax=None):
+    """Per tensor: max |got - want| over max |want|, with a floor of 1e-2 of the whole gradient's largest entry `gmax` (a
+    tensor whose gradient cancels to rounding noise -- the critic bias at Σ adv_n = 0 -- is measured against that); and the
+    relative L2 over all tensors.  The metric of update_vs_oracle (a)."""
+    if gmax is None:
+        gmax = max(float(g.abs().max()) for g in want.values())
+    per = {n: float((got[n].double() - want[n].double()).abs().max()) / max(float(want[n].abs().max()), 1e-2 * gmax)
+           for n in want}
+    return per, _rel_l2(got, want)
+
+
 def _rel_l2(got, want):
     num = sum(float(((got[k].double() - want[k].double()) ** 2).sum()) for k in want)
     den = sum(float((want[k].double() ** 2).sum()) for k in want)

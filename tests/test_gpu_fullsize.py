@@ -128,9 +128,9 @@ def test_lstm_fullsize_scaling_causality_and_heads(trainer):
 
 
 def test_fullsize_gradient_split_bf16_equals_exact_f32_kernels(trainer):
-    """At the full C3 size the whole-batch PPO gradient computed by the default kernels (bf16 matrix pipe, three-piece
-    operand split) equals the one from the exact-f32-MFMA kernels to f32 summation noise: the claim `dtype: f32` of the
-    bench line, checked where the oracle cannot run."""
+    """At the full C3 size the whole-batch PPO gradient computed by the default kernels (`fp16x3`: fp16 matrix pipe, each
+    f32 operand split into three fp16 pieces; the test's name predates that default) equals the one from the exact-f32-MFMA
+    kernels to f32 summation noise: the claim `dtype: f32` of the bench line."""
     from uavppo import ops
     b, pol = trainer.buf, trainer.policy
     n = N * T

@@ -5,7 +5,9 @@
       uav_env_materialise, through rollout_lstm_kernel    oracle rows + invariants + whole iteration against the oracle
   C5  4096 envs x 256 steps per GPU, h=256 x 2, obs 6+2   tile independence, determinism, fp16-split vs exact-f32
       gradient, pipelined vs per-layer backward bit-equality -- properties at 1 M samples; ONE step-kernel tile of it
-      (64 envs x 256 steps, the same kernels) whole iteration against the oracle
+      (64 envs x 256 steps, the same kernels) whole iteration against the oracle; at the full shape, the first optimiser
+      step's gradient -- whole batch, every aligned 256-env chunk, two unaligned env sets -- against an f64 oracle streamed
+      over env chunks, and the update's own first gradient bit-equal to it
 
 Reference shapes: PPOV2.1/environment.py:52-69 (sigma = 15 field), nn.LSTM stack PPOV2.0/model.py:206-212,
 update loop PPOV2.0/train_ppo2.0.py:15-88.  -m gpu."""
@@ -221,13 +223,17 @@ def c5():
     tr.collect()
     tr.compute_advantages()
     tr.rollout_heads = tr.work["heads"].clone()          # what the stepper rollout wrote (pol.heads() reuses the buffer)
+    # ... and the stash / y of every layer, which PPO epoch 0 adopts (restored by the last test of the module)
+    tr.rollout_forward = {f"{k}{l}": tr.work[f"{k}{l}"].clone() for k in ("stash", "y") for l in range(C5["L"])}
     yield tr
     del tr
     torch.cuda.empty_cache()
 
 
-def _c5_gradient(tr, arith=None, stack=True):
-    """PPO gradient of the collected buffers: forward over the stored observations, loss, backward."""
+def _c5_gradient(tr, arith=None, stack=True, rows=None):
+    """PPO gradient of the collected buffers: forward over the stored observations, loss, backward.  rows: an env index
+    set; the loss gradient of every other env is zeroed before the backward (the loss itself, its 1/n and the forward stay
+    whole-batch), and the head-bias gradient is summed from the remaining rows -- the gradient of those envs' samples alone."""
     from uavppo import ops
     b, pol = tr.buf, tr.policy
     n = tr.N * tr.T
@@ -241,7 +247,11 @@ def _c5_gradient(tr, arith=None, stack=True):
         dheads = torch.empty(n, 6, device=DEV)
         dbias = torch.empty(6, device=DEV)
         ops.ppo_loss_heads(heads.view(n, -1), *args, loss, dheads, dbias)
-        g = pol.backward(dheads, tr.work, dbias).clone()
+        if rows is not None:
+            live = torch.zeros(tr.N, dtype=torch.bool, device=DEV)
+            live[torch.as_tensor(np.asarray(rows), dtype=torch.int64, device=DEV)] = True
+            dheads.view(tr.N, tr.T, -1)[~live] = 0.0
+        g = pol.backward(dheads, tr.work, None if rows is not None else dbias).clone()
     finally:
         ops.set_lstm_arith("fp16x3")
         pol.use_stack_bwd = True
@@ -299,3 +309,159 @@ def test_c5_gradient_fp16_split_equals_exact_f32_and_pipelined_equals_per_layer(
     assert rel < 3e-5, rel                                                                    # (a)
     assert torch.allclose(heads_a, heads_f, atol=2e-5, rtol=1e-4)
     assert torch.allclose(loss_a[1:3], loss_f[1:3], rtol=1e-6)
+
+
+# ------------------------------------------------------------------------------------------- C5 full shape against f64
+# The tests above compare C5's kernels with each other (or meet the oracle at one 64-env tile).  These meet an f64 oracle
+# at the full shape -- 64 step-kernel tiles, weight-gradient reductions over K = N T = 1,048,576 rows of per-(env, step)
+# power-of-two scales normalised by the batch-wide maximum, per-sample loss gradients of 1/n ~ 1e-6 -- streamed over env
+# chunks (tests/_iteration_check.oracle_gradient_chunked).  Bars, per tensor (max |got - want| over max |want|, floored at
+# 1e-2 of the largest entry, as update_vs_oracle (a)): the fp16-split default no worse than 2 x the exact-f32 MFMA path's
+# error + 2e-7 (tests/test_gpu_lstm_h256.py), both paths <= 1e-3 per tensor and <= 2e-5 relative L2 (update_vs_oracle (a)).
+C5_CHUNK = 256
+C5_SUBSETS = {"odd_envs_0_255": np.arange(1, 256, 2),     # zero-gradient rows inside every tile of the first four
+              "env_4095": np.array([4095])}              # one live env among 4096: it alone sets the batch-wide scale
+
+
+def _c5_record(key, value):
+    """Print a measurement as one JSON line (pytest -s shows it)."""
+    import json
+    print(f"[c5_full] {key}: {json.dumps(value)}")
+
+
+@pytest.fixture(scope="module")
+def c5_oracle(c5):
+    """The f64 oracle of the C5 buffers at the rollout's parameters (= the first optimiser step's): the 16 aligned 256-env
+    chunks, whose sum is the full-batch gradient, and the env sets of C5_SUBSETS.  It is fed the trainer's own advantages and
+    returns (test_c5_full_gradient_matches_f64_oracle checks them against the oracle's GAE + normalise), so that the gradient
+    comparisons measure the forward, loss and backward kernels alone."""
+    from _iteration_check import oracle_gradient_chunked
+    tr = c5
+    args = (tr.policy, tr.buf, tr.h0, tr.c0, tr.adv_n, tr.ret)
+    full = oracle_gradient_chunked(*args, chunk=C5_CHUNK)
+    sub = oracle_gradient_chunked(*args, envs=list(C5_SUBSETS.values()))
+    _c5_record("oracle", {"chunk_envs": C5_CHUNK, "chunks": len(full["chunks"]), "host_seconds_full": round(full["seconds"], 1),
+                          "host_seconds_subsets": round(sub["seconds"], 1), "torch_threads": torch.get_num_threads()})
+    return full, dict(zip(C5_SUBSETS, sub["chunks"]))
+
+
+def _c5_errors(tr, g, want):
+    from _iteration_check import grad_errors, named_from_flat
+    return grad_errors(named_from_flat(tr.policy, g.cpu()), want)
+
+
+def _c5_check_bars(e16, e32, tag):
+    (p16, r16), (p32, r32) = e16, e32
+    for k in p16:
+        assert p16[k] <= 2.0 * p32[k] + 2e-7, (tag, k, p16[k], p32[k])
+        assert p16[k] <= 1e-3 and p32[k] <= 1e-3, (tag, k, p16[k], p32[k])
+    assert r16 <= 2e-5 and r32 <= 2e-5, (tag, r16, r32)
+
+
+def _c5_round(per):
+    return {k: float(f"{v:.3g}") for k, v in per.items()}
+
+
+def test_c5_full_gradient_matches_f64_oracle(c5, c5_oracle):
+    """The whole-batch gradient at C5's full shape, at the rollout's parameters, against the f64 oracle: GAE + normalise over
+    the 4096 x 256 buffer, the heads of all 1 M samples, the three losses, and every gradient tensor -- the 8 LSTM tensors
+    and the actor / critic weight and bias -- under the default fp16-split arithmetic and the exact-f32 MFMA one."""
+    import time
+    t0 = time.perf_counter()
+    tr = c5
+    full, _ = c5_oracle
+    N, T = tr.N, tr.T
+    n = N * T
+    b = {k: tr.buf[k].cpu().numpy() for k in ("rew", "val", "done")}
+    assert tr.gae_mode == "reference_exact"
+    adv_n, ret = po.normalise(po.gae_reference_exact(b["rew"], b["val"], b["done"]), b["val"])
+    got_adv, got_ret = tr.adv_n.cpu().numpy().reshape(-1), tr.ret.cpu().numpy().reshape(-1)
+    m = {"adv_max_abs_diff": float(np.abs(got_adv - adv_n.numpy()).max()),
+         "ret_max_abs_diff": float(np.abs(got_ret - ret.numpy()).max())}
+    assert np.allclose(got_adv, adv_n.numpy(), atol=3e-5, rtol=1e-4), m
+    assert np.allclose(got_ret, ret.numpy(), atol=3e-5, rtol=1e-4), m
+    want_heads = {"logits": full["logits"], "value": full["value"]}
+    e, heads_e, losses = {}, {}, {}
+    for mode in ("fp16x3", "f32_mfma"):
+        g, loss, heads = _c5_gradient(tr, arith=mode)
+        assert torch.isfinite(g).all()
+        heads = heads.view(N, T, -1).cpu().double()
+        got_heads = {"logits": heads[..., :-1], "value": heads[..., -1]}
+        heads_e[mode] = {k: float((got_heads[k] - w).abs().max() / w.abs().max()) for k, w in want_heads.items()}
+        losses[mode] = (loss.cpu().numpy()[:3] / n).tolist()
+        e[mode] = _c5_errors(tr, g, full["grad"])
+        m[mode] = {"grad_rel_l2": e[mode][1], "grad_max_rel_per_tensor": _c5_round(e[mode][0]), "heads": heads_e[mode],
+                   "losses": losses[mode]}
+    m["losses_oracle"] = full["losses"]
+    m["seconds_without_oracle"] = round(time.perf_counter() - t0, 1)
+    _c5_record("full_batch", m)
+    for mode in e:
+        # the policy loss is a mean of O(1) terms that cancels to ~1e-5: absolute tolerance (update_vs_oracle (a))
+        assert np.allclose(losses[mode], full["losses"], rtol=2e-6, atol=2e-7), (mode, losses[mode], full["losses"])
+    for k in want_heads:
+        e16, e32 = heads_e["fp16x3"][k], heads_e["f32_mfma"][k]
+        assert e16 <= 2.0 * e32 + 2e-7, (k, e16, e32)
+        if e32 <= 5e-6:
+            assert e16 <= 5e-6, (k, e16, e32)
+    _c5_check_bars(e["fp16x3"], e["f32_mfma"], "full batch")
+
+
+def test_c5_env_subset_gradients_match_f64_oracle(c5, c5_oracle):
+    """The gradient of a subset of the envs' samples at the full shape: forward and loss over the whole batch, the loss
+    gradient zeroed outside the subset, the backward over all 4096 envs.  15/16 or more of the 1 M (env, step) rows then
+    carry exactly zero gate gradients, the regime of the zero-row block-scale fix, at K = 1 M instead of a few thousand.
+    Each of the 16 aligned 256-env chunks, the odd envs of envs 0-255 (zero rows inside every tile) and env 4095 alone
+    (one env's scale is the batch-wide maximum), under both arithmetics, against that set's f64 oracle gradient."""
+    import time
+    t0 = time.perf_counter()
+    tr = c5
+    full, subs = c5_oracle
+    sets = [(f"chunk{c}", np.arange(c * C5_CHUNK, (c + 1) * C5_CHUNK), want) for c, want in enumerate(full["chunks"])]
+    sets += [(k, C5_SUBSETS[k], subs[k]) for k in C5_SUBSETS]
+    assert len(sets) == 18
+    e = {}
+    for mode in ("f32_mfma", "fp16x3"):
+        for name, rows, want in sets:
+            g, _, _ = _c5_gradient(tr, arith=mode, rows=rows)
+            assert torch.isfinite(g).all(), (name, mode)
+            e[name, mode] = _c5_errors(tr, g, want)
+    m = {}
+    for mode in ("fp16x3", "f32_mfma"):
+        chunks = [e[name, mode] for name, _, _ in sets[:-2]]
+        worst = {k: max(range(len(chunks)), key=lambda c: chunks[c][0][k]) for k in chunks[0][0]}
+        m[f"chunks_{mode}"] = {"worst_grad_rel_l2": max(c[1] for c in chunks),
+                               "worst_max_rel_per_tensor": {k: [float(f"{chunks[c][0][k]:.3g}"), f"chunk{c}"] for k, c in worst.items()}}
+        for name in C5_SUBSETS:
+            m[f"{name}_{mode}"] = {"grad_rel_l2": e[name, mode][1], "grad_max_rel_per_tensor": _c5_round(e[name, mode][0])}
+    m["seconds_without_oracle"] = round(time.perf_counter() - t0, 1)
+    _c5_record("env_subsets", m)
+    for name, _, _ in sets:
+        _c5_check_bars(e[name, "fp16x3"], e[name, "f32_mfma"], name)
+
+
+def test_c5_update_first_gradient_is_the_checked_gradient(c5):
+    """LAST in the module: it runs the update, which changes the fixture's parameters.  The first optimiser step of
+    tr.update() -- epoch 0 adopting the stash, y and heads the stepper ROLLOUT wrote -- produces, bit for bit, the default
+    gradient the tests above checked against the f64 oracle (which recomputes the forward pass)."""
+    tr = c5
+    # the checked gradient (recomputing is deterministic: test (c) above).  Running the fp16-split forward last also leaves
+    # the library's record of the work stash's h_prev slot as the stepper's, which is how the rollout left it
+    g16, loss16, heads16 = _c5_gradient(tr)
+    assert torch.equal(heads16.view(-1), tr.rollout_heads.view(-1))
+    for l in range(C5["L"]):
+        assert torch.equal(tr.work[f"y{l}"], tr.rollout_forward[f"y{l}"]), l
+    for k, v in tr.rollout_forward.items():              # what epoch 0 adopts is what the rollout wrote
+        tr.work[k].copy_(v)
+    tr.work["heads"].copy_(tr.rollout_heads)
+    assert tr._rollout_forward_valid
+    p_before = tr.policy.flat.clone()
+    tr.record = tr.record_grads = True
+    tr.log.clear()
+    tr.grad_log.clear()
+    tr.update()
+    torch.cuda.synchronize()
+    assert not tr._rollout_forward_valid and len(tr.grad_log) == tr.hp["epochs"]
+    g0, p0 = tr.grad_log[0]
+    assert torch.equal(p0, p_before)
+    assert torch.equal(tr.log[0][0][:3], loss16[:3])
+    assert torch.equal(g0, g16), float((g0 - g16).abs().max())

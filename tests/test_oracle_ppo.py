@@ -125,3 +125,63 @@ def test_lstm_matches_torch_nn_lstm():
         probs, value, logits, (h2, c2) = po.lstm_policy_forward(p, x, h0, c0)
         assert torch.allclose(hn, h2, atol=1e-6) and torch.allclose(cn, c2, atol=1e-6)
         assert torch.allclose(logits, y @ p["actor.weight"].T, atol=1e-5)
+
+
+def test_chunked_oracle_gradient_equals_one_pass():
+    """tests/_iteration_check.oracle_gradient_chunked (the f64 oracle the full-size C5 gradient test streams over env
+    chunks) against ONE f64 pass over the whole batch: two stacked layers, restarts inside the sequences, clipped and
+    unclipped samples.  Chunks of 8, 24 (a ragged last chunk) and 64 (= one chunk), and unaligned env sets, must give the
+    same gradient, heads and losses to 1e-12 relative: the per-chunk scaling |S| T / n is exact."""
+    from _iteration_check import grad_errors, oracle_gradient_chunked
+    N, T, I, H, L, A = 64, 16, 8, 32, 2, 5
+    g = torch.Generator().manual_seed(7)
+    p = po.init_lstm_policy(I, H, L, seed=3)
+    p["actor.weight"] = p["actor.weight"] * 30                   # logits of O(1): ratios on both sides of the clip
+    p["critic.bias"] = torch.full((1,), 0.1)
+    obs = torch.randn(N, T, I, generator=g)
+    done = (torch.rand(N, T, generator=g) < 0.08).float()
+    keep = torch.ones(N, T)
+    keep[:, 1:] = 1 - done[:, :-1]
+    assert int((keep == 0).sum()) >= 20
+    act = torch.randint(0, A, (N, T), generator=g)
+    logp = (torch.log(torch.tensor(0.2)) + 0.4 * torch.randn(N, T, generator=g)).float()
+    val = 0.5 * torch.randn(N, T, generator=g)
+    adv_n, ret = po.normalise(torch.randn(N * T, generator=g), val.reshape(-1))
+    h0, c0 = 0.3 * torch.randn(L, N, H, generator=g), 0.3 * torch.randn(L, N, H, generator=g)
+    buf = {"obs": obs, "keep": keep, "act": act, "logp": logp, "val": val}
+    # one pass over all 64 envs, time-major, f64
+    leaf = {k: v.double().requires_grad_(True) for k, v in p.items()}
+    probs, value, logits, _ = po.lstm_policy_forward(leaf, obs.double().transpose(0, 1), h0.double(), c0.double(),
+                                                     keep=keep.double().transpose(0, 1))
+    total, pl, vl, ent = po.ppo_losses(probs.transpose(0, 1).reshape(-1, A), value.transpose(0, 1).reshape(-1),
+                                       act.reshape(-1), logp.double().reshape(-1), adv_n.double(), ret.double(),
+                                       val.double().reshape(-1))
+    total.backward()
+    want = {k: v.grad for k, v in leaf.items()}
+    ratio = (po.categorical_logp(probs.transpose(0, 1).reshape(-1, A), act.reshape(-1)) - logp.double().reshape(-1)).exp()
+    assert 0.05 < float(((ratio - 1).abs() > 0.2).double().mean()) < 0.95          # both sides of the clip
+    want_losses = [float(pl.detach()), float(vl.detach()), float(ent.detach())]
+    cases = [dict(chunk=8), dict(chunk=24), dict(chunk=64), dict(envs=[range(1, N, 2), range(0, N, 2)]),
+             dict(envs=[np.array([63]), np.arange(0, 63)])]
+    for case in cases:
+        o = oracle_gradient_chunked(p, buf, h0, c0, adv_n, ret, **case)
+        per, rel = grad_errors(o["grad"], want)
+        assert max(per.values()) <= 1e-12 and rel <= 1e-12, (case, per, rel)
+        assert sum(ch["critic.bias"] for ch in o["chunks"]).sub(o["grad"]["critic.bias"]).abs().max() <= 1e-15
+        assert len(o["chunks"]) == (len(case["envs"]) if "envs" in case else -(-N // case["chunk"]))
+        assert torch.allclose(o["logits"], logits.detach().transpose(0, 1), rtol=1e-12, atol=0)
+        assert torch.allclose(o["value"], value.detach().transpose(0, 1), rtol=1e-12, atol=0)
+        assert np.allclose(o["losses"], want_losses, rtol=1e-12, atol=1e-15), (case, o["losses"], want_losses)
+        assert np.isclose(o["total"], float(total.detach()), rtol=1e-12, atol=1e-15)
+    # a set that leaves envs out: its gradient is |S| T / n times the mean gradient over the set alone
+    sub = [5, 17, 40]
+    o = oracle_gradient_chunked(p, buf, h0, c0, adv_n, ret, envs=[sub])
+    assert torch.isnan(o["logits"][0]).all() and not torch.isnan(o["logits"][sub]).any()
+    leaf = {k: v.double().requires_grad_(True) for k, v in p.items()}
+    probs, value, _, _ = po.lstm_policy_forward(leaf, obs[sub].double().transpose(0, 1), h0[:, sub].double(),
+                                                c0[:, sub].double(), keep=keep[sub].double().transpose(0, 1))
+    po.ppo_losses(probs.transpose(0, 1).reshape(-1, A), value.transpose(0, 1).reshape(-1), act[sub].reshape(-1),
+                  logp[sub].double().reshape(-1), adv_n.reshape(N, T)[sub].double().reshape(-1),
+                  ret.reshape(N, T)[sub].double().reshape(-1), val[sub].double().reshape(-1))[0].backward()
+    per, rel = grad_errors(o["grad"], {k: v.grad * (len(sub) / N) for k, v in leaf.items()})
+    assert max(per.values()) <= 1e-12 and rel <= 1e-12, (per, rel)

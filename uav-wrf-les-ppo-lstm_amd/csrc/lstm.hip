@@ -64,8 +64,8 @@ int lstm_pc_wgrad(uav_ctx* ctx, const float* x, const float* y, const float* h0,
                   float* dw_hh, float* db, float* db_hh, hipStream_t st);
 int lstm_h3_bwd_stack(uav_ctx* ctx, int nl, const uav_lstm_bwd_layer* layers, const float* dy, const float* dheads,
                       const float* w_head, int n_heads, int N, int T, hipStream_t st);
-int lstm_wgrad_fused(uav_ctx* ctx, const float* dgates, const float* y_prev_src, const float* keep, const float* h0,
-                     const float* x, int I, const float* ytop, const float* dheads, int NH, int N, int T, int H,
+int lstm_wgrad_fused(uav_ctx* ctx, const float* dgates, const float* y, const float* keep, const float* h0,
+                     const float* x, int I, const float* dheads, int NH, int N, int T, int H,
                      float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, hipStream_t st);
 
 constexpr int MT = 16;      // env rows per workgroup (MFMA M)
@@ -1194,8 +1194,8 @@ int uav_lstm_wgrad(uav_ctx* ctx, const float* x, const float* keep, const float*
     const int64_t NT = (int64_t)N * T;
     int rc;
     if (I <= 6 && (H == 64 || H == 128)) {
-        if ((rc = lstm_wgrad_fused(ctx, dgates, y, keep, h0, x, I, dheads ? y : nullptr, dheads, n_heads, N, T, H, dw_ih,
-                                   dw_hh, db, db_hh, dw_head, st))) return rc;
+        if ((rc = lstm_wgrad_fused(ctx, dgates, y, keep, h0, x, I, dheads, n_heads, N, T, H, dw_ih, dw_hh, db, db_hh,
+                                   dw_head, st))) return rc;
     } else {
         // generic path: column sums use the tail of the workspace, the split-K slabs everything in front of it
         UAV_REQUIRE(stash, "uav_lstm_wgrad: stash is required when I > 6");

@@ -3,6 +3,7 @@
 
     python bench.py --gpus 1 --steps 10 --warmup 3
     python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full                # + everything beyond the headline (below)
     python bench.py --gpus 8                      # spawns 8 fresh rank processes itself (RCCL), rank 0 prints the line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
@@ -13,10 +14,15 @@ LSTM(h=128) actor-critic, the GAE scan + whole-buffer normalisation, 5 epochs of
 update (forward, loss, BPTT, weight gradients, grad all-reduce, clip+Adam) and the curriculum
 update.
 
+A plain run does only what the headline needs: set up, warm up, time the steps, dump the outputs if asked, print the
+line (with the roofline of the kernel timed live inside the timed region).  --full adds what takes work of its own:
+the per-kernel breakdown and rollout time over extra iterations, the exchange probe, the CPU baselines and, in launcher
+mode, the strong-scaling rank set.
+
 --scaling weak (default): every rank owns the config's env count (4096 at C3); value = all ranks' env-steps /
-max-over-ranks time.  Started plainly with --gpus N > 1 (launcher mode) the strong-scaling shape (the config's env count
-split over the ranks, SURVEY 8d "strong scaling for C3") is timed afterwards in a SECOND set of fresh rank processes and
-reported under "strong_scaling"; rank processes themselves (torchrun) time exactly one shape.
+max-over-ranks time.  Started plainly with --gpus N > 1 --full (launcher mode) the strong-scaling shape (the config's env
+count split over the ranks, SURVEY 8d "strong scaling for C3") is timed afterwards in a SECOND set of fresh rank processes
+and reported under "strong_scaling"; rank processes themselves (torchrun) time exactly one shape.
 --scaling strong: the split shape is the headline value.
 """
 import argparse
@@ -128,8 +134,8 @@ def last_json_line(text):
 
 def launch(args, argv):
     """Plain `python bench.py --gpus N` (N > 1): this process never touches the GPU and becomes the launcher.  The headline
-    phase runs in one set of fresh rank processes; the strong-scaling shape, when the headline is weak, in a
-    SECOND set of fresh processes -- so neither phase can slow down, hang or lose the other (round 2's in-process
+    phase runs in one set of fresh rank processes; with --full the strong-scaling shape, when the headline is
+    weak, in a SECOND set of fresh processes -- so neither phase can slow down, hang or lose the other (round 2's in-process
     weak -> strong sequence stalled in a shared-GPU rehearsal: DESIGN.md 6).  One JSON line on stdout."""
     me = [sys.executable, os.path.abspath(__file__)]
     t0 = time.time()
@@ -144,12 +150,12 @@ def launch(args, argv):
         why = f"timed out after {limit:.0f} s; rank processes terminated" if rc == 124 else f"rc {rc}"
         sys.stderr.write(f"[bench] headline phase failed ({why})\n")
         return rc or 1
-    if args.scaling == "weak" and not args.no_strong_phase and CONFIGS[args.config]["num_envs"] % args.gpus == 0:
+    if args.full and args.scaling == "weak" and not args.no_strong_phase and CONFIGS[args.config]["num_envs"] % args.gpus == 0:
         wall = time.time() - t0
         k2, w2 = max(3, args.steps // 2), min(args.warmup, 2)
         argv2 = ["--gpus", str(args.gpus), "--config", args.config, "--backend", args.backend, "--collectives", args.collectives,
                  "--pg-timeout", str(args.pg_timeout), "--scaling", "strong",
-                 "--steps", str(k2), "--warmup", str(w2), "--no-cpu-baseline"]
+                 "--steps", str(k2), "--warmup", str(w2), "--no-cpu-baseline", "--full"]
         rc2, text2 = spawn_ranks(args.gpus, me + argv2, capture_rank0=True, timeout=max(180.0, 4.0 * wall), shared_gpu=shared)
         o2 = last_json_line(text2)
         if rc2 == 0 and o2:
@@ -318,7 +324,8 @@ def measure(tr, steps, warmup, world, dev, ops, dist, timers=(), dominant=("lstm
     Inside the timed region only the DOMINANT kernel's launches are bracketed with HIP events on the launch stream (what
     `roofline` needs, live): an event pair costs ~5 us of device idle per bracketed launch (rocprofv3 trace of round 5:
     profiles/r05_trace_gaps_*.txt -- 20 brackets were 0.11 ms of a 7 ms C3 iteration, 7 % of a C2 iteration).  The other kernels
-    of `timers` and the rollout are timed the same way over `breakdown_iters` EXTRA iterations after the timed region."""
+    of `timers` and the rollout are timed the same way over `breakdown_iters` EXTRA iterations after the timed region (none
+    when `breakdown_iters` is 0: rollout ms is then None and only the dominant kernel is in the summary)."""
     import torch
 
     def barrier():
@@ -354,20 +361,22 @@ def measure(tr, steps, warmup, world, dev, ops, dist, timers=(), dominant=("lstm
         after_timed(tr)
     summary = ops.KERNEL_TIMER.summary() if live else {}
     ops.KERNEL_TIMER.disable()
-    # per-kernel breakdown + rollout time: a few more iterations of the same loop, outside the timed region
-    rest = tuple(t for t in timers if t not in live)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(breakdown_iters)]
-    if rest:
-        ops.KERNEL_TIMER.enable(rest)
-    tr.time_rollouts(ev)           # an event pair around each of those iterations' rollouts, recorded inside train_iteration()
-    for _ in range(breakdown_iters):
-        tr.train_iteration()
-    barrier()
-    if rest:
-        summary.update(ops.KERNEL_TIMER.summary())
-        ops.KERNEL_TIMER.disable()
+    roll_ms = None
+    if breakdown_iters:
+        # per-kernel breakdown + rollout time: a few more iterations of the same loop, outside the timed region
+        rest = tuple(t for t in timers if t not in live)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(breakdown_iters)]
+        if rest:
+            ops.KERNEL_TIMER.enable(rest)
+        tr.time_rollouts(ev)       # an event pair around each of those iterations' rollouts, recorded inside train_iteration()
+        for _ in range(breakdown_iters):
+            tr.train_iteration()
+        barrier()
+        if rest:
+            summary.update(ops.KERNEL_TIMER.summary())
+            ops.KERNEL_TIMER.disable()
+        roll_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
     tr.losses()     # raises (on every rank) if any NaN probability was seen (reference convention)
-    roll_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
     return dt, roll_ms, summary
 
 
@@ -732,10 +741,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
     ap.add_argument("--scaling", default="weak", choices=("weak", "strong"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-strong-phase", action="store_true", help="launcher mode: skip the second (strong-scaling) set of ranks")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel breakdown and rollout time over extra iterations, "
+                         "the exchange probe, the CPU baselines, and (launcher mode) the strong-scaling rank set")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-strong-phase", action="store_true", help="launcher mode with --full: skip the second (strong-scaling) set of ranks")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
-    ap.add_argument("--no-exchange-probe", action="store_true", help="skip timing the iteration's collectives after the timed region")
+    ap.add_argument("--no-exchange-probe", action="store_true", help="with --full: skip timing the iteration's collectives after the timed region")
     ap.add_argument("--collectives", default="torch", choices=("torch", "abi"),
                     help="carrier of the iteration's exchanges: torch.distributed (default) or the C ABI's own RCCL communicator (uav_allreduce)")
     ap.add_argument("--pg-timeout", type=float, default=600.0, help="seconds before a stuck collective (or a rendezvous nobody joins: a fresh box can take 1-2 min to load PyTorch) aborts the rank")
@@ -801,6 +813,7 @@ def main():
     tr = build_trainer(cfg, N, rank, world, dev, ops)
     dt, roll_ms, timers = measure(tr, args.steps, args.warmup, world, dev, ops, dist,
                                   timers=("lstm_bwd", "lstm_fwd", "lstm_wgrad", "rollout", "ppo_loss"),
+                                  breakdown_iters=3 if args.full else 0,
                                   after_timed=(lambda t: dump_outputs(t, args.dump_outputs)) if args.dump_outputs and rank == 0 else None)
     epochs = tr.hp["epochs"]
     env_steps = N * T * world * args.steps
@@ -826,27 +839,30 @@ def main():
                                f"5 actions, reference_exact GAE, {epochs} epochs x {tr.num_minibatches} minibatch "
                                f"of {N * T} samples/GPU", "num_envs_per_gpu": N, "num_envs_total": N * world, "horizon": T, "hidden": H,
                    "minibatch_samples": N * T // tr.num_minibatches, "parallelism": f"dp{world} (env shards, RCCL grad all-reduce)"},
-        "rollout_env_steps_per_s": N * T * world / (roll_ms * 1e-3),
         "ppo_iterations_per_s": args.steps / dt, "optimizer_steps_per_s": args.steps * opt_steps / dt,
-        "rollout_ms": roll_ms, "kernel_ms": {k: v["avg_ms"] for k, v in timers.items()},
-        "kernel_ms_note": "lstm_bwd (the roofline's kernel): HIP events around its launches INSIDE the timed region; the other kernels "
-                          "and rollout_ms: the same brackets over 3 extra iterations after it (an event pair costs ~5 us of device idle)",
+        "kernel_ms": {k: v["avg_ms"] for k, v in timers.items()},
+        "kernel_ms_note": "lstm_bwd (the roofline's kernel): HIP events around its launches INSIDE the timed region"
+                          + ("; the other kernels and rollout_ms: the same brackets over 3 extra iterations after it (an event pair "
+                             "costs ~5 us of device idle)" if args.full else "; the other kernels and rollout_ms: with --full"),
         "roofline": roofline,
     }
-    # (the strong-scaling shape is NOT timed in these processes: launch() runs it in a second set of fresh ranks; under
-    #  torchrun ask for it with --scaling strong)
-    if world == 1:
-        measured = None
-        if not args.no_exchange_probe:
-            measured = (measure_exchanges(dev, tr.policy.num_params(), own_group=False) if dist.is_initialized()
-                        else measure_exchanges_isolated(local, tr.policy.num_params()))
-        out["predicted_8gpu"] = predicted_8gpu(args.config, cfg, N, T, dt / args.steps * 1e3, tr.policy.num_params(), measured)
-    elif not args.no_exchange_probe:
-        out["measured_exchange_us"] = measure_exchanges(dev, tr.policy.num_params(), own_group=False)
+    if args.full:
+        out["rollout_env_steps_per_s"] = N * T * world / (roll_ms * 1e-3)
+        out["rollout_ms"] = roll_ms
+        # (the strong-scaling shape is NOT timed in these processes: launch() runs it in a second set of fresh ranks; under
+        #  torchrun ask for it with --scaling strong)
+        if world == 1:
+            measured = None
+            if not args.no_exchange_probe:
+                measured = (measure_exchanges(dev, tr.policy.num_params(), own_group=False) if dist.is_initialized()
+                            else measure_exchanges_isolated(local, tr.policy.num_params()))
+            out["predicted_8gpu"] = predicted_8gpu(args.config, cfg, N, T, dt / args.steps * 1e3, tr.policy.num_params(), measured)
+        elif not args.no_exchange_probe:
+            out["measured_exchange_us"] = measure_exchanges(dev, tr.policy.num_params(), own_group=False)
     if rehearsal:
         out["rehearsal"] = f"one-rank {args.backend} communicator, all exchanges issued (UAVPPO_FORCE_COLLECTIVES=1)"
     out["distributed"] = distributed_block(world, rank, local, dev, args, dist)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
         out["cpu_baseline_vectorised"] = cpu_baseline_vectorised(T=128, H=128, n_full=4096)
     if rank == 0:

@@ -84,9 +84,9 @@ if os.environ["RANK"] == "0":
 '''
 
 
-def _fake_launch(tmp_path, monkeypatch, mode, backend="gloo", cap=5):
-    """bench.launch() with the rank command replaced by a stand-in: the launcher's own logic (two fresh rank sets, merge,
-    a failing or hanging strong phase never loses the headline line) without a GPU."""
+def _fake_launch(tmp_path, monkeypatch, mode, backend="gloo", cap=5, full=True):
+    """bench.launch() with the rank command replaced by a stand-in: the launcher's own logic (two fresh rank sets with --full,
+    merge, a failing or hanging strong phase never loses the headline line) without a GPU."""
     import argparse
     import bench
     fake = tmp_path / "fake_rank.py"
@@ -96,8 +96,8 @@ def _fake_launch(tmp_path, monkeypatch, mode, backend="gloo", cap=5):
     real = bench.spawn_ranks
     monkeypatch.setattr(bench, "spawn_ranks", lambda n, cmd, **kw: real(n, cmd, **dict(kw, timeout=min(kw.get("timeout") or cap, cap))))
     args = argparse.Namespace(gpus=2, scaling="weak", no_strong_phase=False, steps=4, warmup=1, config="c2", backend=backend,
-                              headline_timeout=0.0, collectives="torch", pg_timeout=600.0)
-    return bench.launch(args, ["--gpus", "2", "--config", "c2", f"--backend={backend}"])
+                              headline_timeout=0.0, collectives="torch", pg_timeout=600.0, full=full)
+    return bench.launch(args, ["--gpus", "2", "--config", "c2", f"--backend={backend}"] + (["--full"] if full else []))
 
 
 def test_launcher_runs_strong_shape_in_a_second_fresh_rank_set(tmp_path, monkeypatch, capsys):
@@ -106,6 +106,15 @@ def test_launcher_runs_strong_shape_in_a_second_fresh_rank_set(tmp_path, monkeyp
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["value"] == 1.0 and out["strong_scaling"]["value"] == 2.0 and out["strong_scaling"]["num_envs_total"] == 256
+
+
+def test_plain_launch_runs_the_headline_rank_set_alone(tmp_path, monkeypatch, capsys):
+    """Without --full the launcher starts one rank set: a strong phase that would hang is never started."""
+    assert _fake_launch(tmp_path, monkeypatch, "hang", full=False) == 0
+    lines = capsys.readouterr().out.strip().splitlines()
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["value"] == 1.0 and "strong_scaling" not in out
 
 
 def test_launcher_keeps_the_headline_when_the_strong_phase_fails_or_hangs(tmp_path, monkeypatch, capsys):

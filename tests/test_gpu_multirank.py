@@ -125,14 +125,16 @@ def test_abi_collectives_refuse_without_a_communicator():
 def test_bench_prints_exactly_one_json_line(mode):
     """The driver reads ONE JSON line from bench.py's stdout.  RCCL writes a version banner to stdout when its first
     communicator comes up, so bench.py sends everything but the line to stderr; checked with a real RCCL communicator
-    (one rank) and through bench.py's own launcher (two ranks on this one GPU, gloo)."""
+    (one rank) and through bench.py's own launcher (two ranks on this one GPU, gloo).  Both of those run with --full (the
+    breakdown iterations, the exchange probe, the strong-scaling rank set); the plain run prints the lean line."""
     import json
     env = dict(os.environ)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
     if mode == "rccl-one-rank":
         env["UAVPPO_FORCE_COLLECTIVES"] = "1"
+        cmd += ["--full"]
     if mode == "two-ranks-gloo":
-        cmd += ["--gpus", "2", "--backend", "gloo"]
+        cmd += ["--gpus", "2", "--backend", "gloo", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = r.stdout.splitlines()
@@ -140,5 +142,8 @@ def test_bench_prints_exactly_one_json_line(mode):
     out = json.loads(lines[0])
     assert out["n_gpus"] == (2 if mode == "two-ranks-gloo" else 1) and out["value"] > 0
     assert ("rehearsal" in out) == (mode == "rccl-one-rank")
+    assert ("rollout_ms" in out) == (mode != "plain")
+    if mode == "rccl-one-rank":
+        assert "error" not in out["predicted_8gpu"]["measured_one_rank_us"]
     if mode == "two-ranks-gloo":
         assert out["strong_scaling"]["num_envs_total"] == 256

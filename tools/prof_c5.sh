@@ -4,7 +4,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/prof_c5${TAG:+_$TAG}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $ROOT/bench.py --config c5 --steps 2 --warmup 1 --no-strong-phase --no-cpu-baseline > $OUT/bench.json 2> $OUT/stats.log || exit 1
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $ROOT/bench.py --config c5 --steps 2 --warmup 1 --full --no-strong-phase --no-cpu-baseline > $OUT/bench.json 2> $OUT/stats.log || exit 1
 python3 - <<P
 import csv,glob
 f=glob.glob("$OUT/stats/**/*kernel_stats.csv",recursive=True)[0]

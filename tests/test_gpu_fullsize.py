@@ -127,31 +127,33 @@ def test_lstm_fullsize_scaling_causality_and_heads(trainer):
     assert torch.equal(y2[:, :t0], y[:, :t0]) and not torch.equal(y2[:, t0:], y[:, t0:])
 
 
-def test_fullsize_gradient_split_bf16_equals_exact_f32_kernels(trainer):
-    """At the full C3 size the whole-batch PPO gradient computed by the default kernels (`fp16x3`: fp16 matrix pipe, each
-    f32 operand split into three fp16 pieces; the test's name predates that default) equals the one from the exact-f32-MFMA
-    kernels to f32 summation noise: the claim `dtype: f32` of the bench line."""
+def test_fullsize_gradient_split_modes_equal_exact_f32_kernels(trainer):
+    """At the full C3 size the whole-batch PPO gradient computed by the kernels of each split arithmetic -- `fp16x3`, the
+    default (two fp16 pieces per f32 operand, three products), and `bf16x6`, the one the trainer's range guard switches to
+    (three bf16 pieces, six products) -- equals the one from the exact-f32-MFMA kernels to f32 summation noise: the claim
+    `dtype: f32` of the bench line, in both modes."""
     from uavppo import ops
     b, pol = trainer.buf, trainer.policy
     n = N * T
     args = (b["act"].reshape(-1), b["logp"].reshape(-1), trainer.adv_n.reshape(-1), trainer.ret.reshape(-1),
             b["val"].reshape(-1), 1.0 / n, 0.2, 0.01)
-    grads, sums = [], []
-    for f32 in (False, True):
-        ops.set_lstm_arith("f32_mfma" if f32 else "fp16x3")
+    grads, sums = {}, {}
+    for mode in ("fp16x3", "bf16x6", "f32_mfma"):
+        ops.set_lstm_arith(mode)
         heads = pol.heads(b["obs"], b["keep"], trainer.h0, trainer.c0, trainer.work)
         loss = torch.zeros(4, dtype=torch.float64, device=DEV)
         dheads = torch.empty(n, 6, device=DEV)
         dbias = torch.empty(6, device=DEV)
         ops.ppo_loss_heads(heads, *args, loss, dheads, dbias)
         g = pol.backward(dheads, trainer.work, dbias).clone()
-        grads.append(g.double())
-        sums.append(loss.clone())
+        grads[mode] = g.double()
+        sums[mode] = loss.clone()
     ops.set_lstm_arith("fp16x3")
-    rel = (grads[0] - grads[1]).norm() / grads[1].norm()
-    assert rel.item() < 2e-5, rel.item()
-    assert torch.allclose(sums[0][1:3], sums[1][1:3], rtol=1e-6)              # value-loss and entropy sums
-    assert abs((sums[0][0] - sums[1][0]).item()) < 1e-4                        # policy-loss sum: ~0 by cancellation at init
+    for split in ("fp16x3", "bf16x6"):
+        rel = (grads[split] - grads["f32_mfma"]).norm() / grads["f32_mfma"].norm()
+        assert rel.item() < 2e-5, (split, rel.item())
+        assert torch.allclose(sums[split][1:3], sums["f32_mfma"][1:3], rtol=1e-6), split    # value-loss and entropy sums
+        assert abs((sums[split][0] - sums["f32_mfma"][0]).item()) < 1e-4, split             # policy-loss sum: ~0 at init
 
 
 @pytest.mark.parametrize("radius", [50.0, 140.0])

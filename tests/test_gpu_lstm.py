@@ -187,11 +187,14 @@ def test_split_kernels_have_f32_accuracy(ops, N, T, H, split):
         assert e_x6[k] <= 2.0 * e_f32[k] + 2e-7, (k, e_x6[k], e_f32[k])   # ... and no worse than the exact-f32 MFMA chain
 
 
-@pytest.mark.parametrize("H", [128, 64])
-def test_split_fp16_backward_keeps_f32_accuracy_over_40_decades(ops, H):
+# (the fp16x3 cases keep their ids from before the bf16x6 ones were added)
+@pytest.mark.parametrize("H,split", [(128, "fp16x3"), (64, "fp16x3"), (128, "bf16x6"), (64, "bf16x6")],
+                         ids=["128", "64", "bf16x6-128", "bf16x6-64"])
+def test_split_fp16_backward_keeps_f32_accuracy_over_40_decades(ops, H, split):
     """fp16 has 5 exponent bits, gradients do not care: the backward scales each env's gate gradients by a power of two
     per step before the split.  Envs whose loss gradients differ by up to 1e25 (and vary by 1e6 along their own
-    sequence) must each come out with f32 relative accuracy -- measured per env against an f64 LSTM."""
+    sequence) must each come out with f32 relative accuracy -- measured per env against an f64 LSTM.  The same holds on
+    the bf16 split (f32's exponent range, no scales), the arithmetic the trainer's range guard switches to."""
     torch.manual_seed(H)
     N, T, I, A = 40, 24, 6, 6
     ref = torch.nn.LSTM(I, H, 1).double()
@@ -207,8 +210,9 @@ def test_split_fp16_backward_keeps_f32_accuracy_over_40_decades(ops, H):
     ((y @ w_head.T) * dheads).sum().backward()
     d = lambda t: t.detach().float().to(DEV).contiguous()
     xg = d(x.transpose(0, 1))
-    yg, _, _, stash = ops.lstm_fwd(xg, None, d(h0), d(c0), d(w_ih), d(w_hh), d(b_ih), d(b_hh))
-    g = ops.lstm_bwd(xg, None, stash, d(w_ih), d(w_hh), yg, d(h0), dheads=d(dheads.transpose(0, 1)), w_head=d(w_head))
+    with ops.lstm_arith(split):
+        yg, _, _, stash = ops.lstm_fwd(xg, None, d(h0), d(c0), d(w_ih), d(w_hh), d(b_ih), d(b_hh))
+        g = ops.lstm_bwd(xg, None, stash, d(w_ih), d(w_hh), yg, d(h0), dheads=d(dheads.transpose(0, 1)), w_head=d(w_head))
     for k, want in (("dh0", h0.grad), ("dc0", c0.grad)):
         got = g[k].cpu().double()
         rel = (got - want).abs().amax(1) / want.abs().amax(1)                 # per env, against its own magnitude
@@ -269,14 +273,17 @@ def test_lstm_bwd_fused_path_fuzz_against_dy_path(ops):
             assert (a - bb).abs().max().item() <= 2e-5 * max(scale, 1.0) + 1e-4 * scale, (case, N, T, H, k)
 
 
-@pytest.mark.parametrize("H", [128, 64])
-def test_split_fp16_weight_gradients_over_a_wide_dynamic_range(ops, H):
+# (the fp16x3 cases keep their ids from before the bf16x6 ones were added)
+@pytest.mark.parametrize("H,split", [(128, "fp16x3"), (64, "fp16x3"), (128, "bf16x6"), (64, "bf16x6")],
+                         ids=["128", "64", "bf16x6-128", "bf16x6-64"])
+def test_split_fp16_weight_gradients_over_a_wide_dynamic_range(ops, H, split):
     """The weight-gradient kernel's fp16 split keeps ONE accumulator per tile (unscaled residuals) under a running
     power-of-two scale PER GATE ROW that is lowered, and that row of the accumulators rescaled, when larger gradients
     arrive.  Checked against f64 sums: (a) gate rows up to 2^31 below the largest row of their wave all come out at f32
     relative accuracy, (c) gradients that grow by 2^40 along the samples (many rescales) and (d) that start with all-zero
     slabs are handled.  (A single scale per wave, tried first, left rows 2^24 below the largest at 6e-5 and rows 2^31
-    below at 1e-2 of their own magnitude.)"""
+    below at 1e-2 of their own magnitude.)  The bf16 split (three pieces, f32's exponent range, no scales) must meet the
+    same bounds."""
     torch.manual_seed(H + 1)
     N, T, I = 32, 64, 6
     g = torch.Generator().manual_seed(H)
@@ -293,7 +300,8 @@ def test_split_fp16_weight_gradients_over_a_wide_dynamic_range(ops, H):
         want_hh = torch.einsum("ntm,ntu->mu", dg, hprev)
         want_ih = torch.einsum("ntm,nti->mi", dg, x)
         want_b = dg.sum((0, 1))
-        got = ops.lstm_wgrad(d(x), d(keep), d(h0), d(y), stash.to(DEV), d(dg), torch.zeros(4 * H, I, device=DEV), dheads=d(dheads))
+        with ops.lstm_arith(split):
+            got = ops.lstm_wgrad(d(x), d(keep), d(h0), d(y), stash.to(DEV), d(dg), torch.zeros(4 * H, I, device=DEV), dheads=d(dheads))
         dgf, hpf, xf = dg.float().double(), hprev.float().double(), x.float().double()      # what the kernel is given
         want_hh, want_ih, want_b = (torch.einsum("ntm,ntu->mu", dgf, hpf), torch.einsum("ntm,nti->mi", dgf, xf), dgf.sum((0, 1)))
         big = float(want_hh.abs().max())

@@ -171,6 +171,39 @@ int uav_smooth_l1(uav_ctx* ctx, const float* pred, const float* target, int64_t 
 int uav_mse_bce(uav_ctx* ctx, const float* out, const float* target, int64_t n, double* loss_mean, float* dout,
                 uav_stream stream);
 
+/* ---- GAIL discriminator (PPOV2.0/model.py:58-70: Linear(obs_dim + n_act, 128), ReLU, Linear(128, 1), Sigmoid over
+ * sa = [state | one_hot(action)]).  Parameters are ONE flat f32 buffer in state_dict order: net.0.weight [128][obs_dim + n_act],
+ * net.0.bias [128], net.2.weight [1][128], net.2.bias [1] -- uav_disc_param_count floats (1,665 for 6 + 5 inputs; 0, with a
+ * reason in uav_last_error, for a shape the kernels refuse).  Accepted: hidden == 128 and obs_dim + n_act + 1 <= 16; every
+ * entry point checks the shape first and answers non-zero with the reason otherwise (no GPU is touched before that).
+ * Exact f32 arithmetic (v_mfma_f32_16x16x4_f32), no atomics: two calls on the same inputs give the same bits. */
+size_t uav_disc_param_count(int obs_dim, int n_act, int hidden);
+
+/* Forward + two BCELoss means + backward of PPOV1.1/train_ppo_gail.py:157-175 (everything but optimizer_d.step(), which is
+ * uav_clip_adam with max_norm <= 0) in one pass over the expert rows (label 1, weight inv_ne) and the policy rows (label 0,
+ * weight inv_np): obs_e f32 [n_e][obs_dim], act_e i32 [n_e], obs_p / act_p likewise (a set with n = 0 may be NULL).  The weights
+ * are arguments so that ranks can pass 1 / the global counts (as uav_ppo_loss's inv_n).  With z the logit and D = sigmoid(z):
+ *   loss_sums f64[4] (device)  [0] sum over expert rows of -max(log D, -100)      [1] sum over policy rows of -max(log(1 - D), -100)
+ *                              [2] expert rows with D > 0.5 + policy rows with D < 0.5 (the accuracy numerator)
+ *                              [3] rows with a NaN logit or an action outside [0, n_act) (such an action sets no one-hot column)
+ *   grad f32 [param_count]     gradient of inv_ne * [0] + inv_np * [1], laid out as params.
+ * Both logs are taken from the logit (-log D = softplus(-z), -log(1 - D) = softplus(z)) and clamped at 100, nn.BCELoss's clamp:
+ * the value nn.BCELoss(nn.Sigmoid(z)) has in exact arithmetic.  The gradient is taken through the logit, dz = (D - y) * weight,
+ * uav_mse_bce's convention: equal to torch's BCELoss o Sigmoid backward wherever D (1 - D) is representable, and still the
+ * true gradient where torch's goes to 0 (|z| beyond ~17 in f32, ~37 in f64) -- including rows whose loss term is clamped.
+ * No per-row intermediate goes to memory; weight gradients accumulate on chip, one partial slab per workgroup goes to the handle's
+ * workspace (their number bounded by its size and by the CU count) and the slabs are added in slab order.  The result depends on
+ * the order of the concatenated rows (expert, then policy) and on the slab count, not on where the sets are split. */
+int uav_disc_grad(uav_ctx* ctx, const float* params, const float* obs_e, const int32_t* act_e, int64_t n_e, const float* obs_p,
+                  const int32_t* act_p, int64_t n_p, int obs_dim, int n_act, int hidden, float inv_ne, float inv_np,
+                  double* loss_sums, float* grad, uav_stream stream);
+
+/* The imitation reward of a rollout buffer (an extension: the reference trains its discriminator and uses it nowhere):
+ * rew_out[i] = env_coef * rew_env[i] + gail_coef * softplus(z_i), softplus(z) = -log(1 - D) = max(z, 0) + log1p(exp(-|z|)).
+ * obs f32 [n][obs_dim], act i32 [n]; rew_env may be NULL (taken as 0); rew_out may alias rew_env. */
+int uav_disc_reward(uav_ctx* ctx, const float* params, const float* obs, const int32_t* act, int64_t n, int obs_dim, int n_act,
+                    int hidden, float env_coef, float gail_coef, const float* rew_env, float* rew_out, uav_stream stream);
+
 /* ---- uav_lstm_fwd one time step per call (H = 256, fp16-split arithmetic only): the rollout of a stacked / wide LSTM
  * policy, where an environment step sits between two time steps.  Same kernels and bit-identical results to
  * uav_lstm_fwd over the same inputs; the weights are split once per rollout, the recurrent state stays on the device in

@@ -1,0 +1,121 @@
+# generate_expert_data.py -- expert (state, action) pairs for GAIL from greedy episodes of a trained policy.
+#
+# Counterpart of the reference's PPOV1.1/generate_expert_data.py: num_episodes greedy (argmax) episodes of a trained policy,
+# every (state acted on, action) pair saved as expert_data.npz with the keys `states`, `actions` (:35-58).  The episodes run as
+# that many PARALLEL environments through the evaluation path of evaluate_with_lstm.py: the fused greedy-episode kernels
+# (uav_greedy_episodes) where they cover the policy (fused_refusal), the step-wise loop otherwise; both leave the same records
+# (action, returned observation, flags per step), which expert_pairs() cuts into pairs on the host.
+import numpy as np
+import torch
+
+from config import ENV_VARIANT, SEED
+from evaluate_with_lstm import _policy_core, _stepwise_policy_probs, fused_refusal, load_lstm_policy
+from uavppo import ops
+from uavppo.vec_env import VecMethaneEnv
+
+NOT_STEPPED = 4          # bit 2 of a record's flags (include/uavppo.h, uav_greedy_episodes): the env was not stepped, act = -1
+
+
+def expert_pairs(cur_obs0, obs_rec, act_rec, flags_rec):
+    """(states f32 [M, obs_dim], actions i64 [M]) from the records of greedy episodes (host arrays).
+
+    cur_obs0 [N, obs_dim]: the reset observations; obs_rec [N, S, obs_dim], act_rec [N, S], flags_rec [N, S]: per step the
+    observation the step RETURNED, the action taken and the flags (bit0 done, bit1 reached, bit2 not stepped) -- or lists of
+    such arrays, the chunks of successive launches, joined along the step axis.  The state of step t is the observation acted
+    ON: the reset observation for t = 0, record t - 1 after that; slots flagged "not stepped" are dropped; episodes are
+    concatenated in env order, steps in time order; the terminal observation is never a state
+    (generate_expert_data.py:35-51)."""
+    def join(x):
+        return np.concatenate([np.asarray(c) for c in x], axis=1) if isinstance(x, (list, tuple)) else np.asarray(x)
+    obs_rec, act_rec, flags_rec = join(obs_rec), join(act_rec), join(flags_rec)
+    cur_obs0 = np.asarray(cur_obs0, dtype=np.float32)
+    acted_on = np.concatenate([cur_obs0[:, None, :], obs_rec[:, :-1, :].astype(np.float32, copy=False)], axis=1)
+    stepped = (flags_rec & NOT_STEPPED) == 0
+    return np.ascontiguousarray(acted_on[stepped], dtype=np.float32), act_rec[stepped].astype(np.int64)
+
+
+def load_policy(path, device="cuda"):
+    """A policy from a checkpoint train_ppo2.0.py writes: the LSTM actor-critic (keys lstm.*) or the reference's MLP
+    (keys feature.*, model.PPOActorCritic)."""
+    sd = torch.load(path, map_location="cpu")
+    if any(k.startswith("lstm.") for k in sd):
+        return load_lstm_policy(path, device)
+    from model import PPOActorCritic
+    pol = PPOActorCritic(6, 5, device=device)
+    pol.load_state_dict(sd)
+    return pol
+
+
+@torch.no_grad()
+def greedy_records(policy, env, max_steps=None, chunk=250):
+    """One greedy episode per environment of `env`: (reset observations [N, obs_dim], lists of per-chunk obs / act / flags
+    records) as host arrays, in the record format of uav_greedy_episodes whichever path produced them."""
+    kind, core = _policy_core(policy)
+    N, dev = env.num_envs, env.device
+    limit = max_steps or env.max_steps
+    env.reset()
+    cur_obs0 = env.obs.cpu().numpy().copy()
+    obs_c, act_c, flags_c = [], [], []
+    if fused_refusal(policy, env) is None:
+        H = core.hidden if kind == "lstm" else 0
+        h = torch.zeros(N, H, dtype=torch.float32, device=dev) if H else None
+        c = torch.zeros(N, H, dtype=torch.float32, device=dev) if H else None
+        active = torch.ones(N, dtype=torch.uint8, device=dev)
+        nan_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        t0 = 0
+        while t0 < limit:
+            k = min(chunk, limit - t0)
+            recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, 6, dtype=torch.float32, device=dev),
+                    "pos": torch.empty(N, k, 2, dtype=torch.float32, device=dev), "flags": torch.empty(N, k, dtype=torch.uint8, device=dev)}
+            ops.greedy_episodes(env.state, N, env.cfg(), core.flat, H, k, env.obs, h, c, active, recs, nan_count=nan_count)
+            obs_c.append(recs["obs"].cpu().numpy()), act_c.append(recs["act"].cpu().numpy()), flags_c.append(recs["flags"].cpu().numpy())
+            t0 += k
+            if not bool(active.any()):
+                break
+        if int(nan_count.item()) > 0:
+            raise RuntimeError("NaN in probs")
+    else:
+        probs, nan = _stepwise_policy_probs(kind, core, env)
+        active = torch.ones(N, dtype=torch.bool, device=dev)
+        obs, t = env.obs, 0
+        while t < limit:
+            k = min(chunk, limit - t)
+            ro = torch.zeros(N, k, env.obs_dim, dtype=torch.float32, device=dev)
+            ra = torch.full((N, k), -1, dtype=torch.int32, device=dev)
+            rf = torch.full((N, k), NOT_STEPPED, dtype=torch.uint8, device=dev)
+            for i in range(k):
+                act = torch.argmax(probs(obs), dim=1).to(torch.int32)
+                obs, _, done, _ = env.step(act)          # auto-reset: the env goes on, its later steps are not recorded
+                done_b = done > 0.5
+                ro[:, i] = torch.where(active[:, None], torch.where(done_b[:, None], env.term_obs, obs), ro[:, i])
+                ra[:, i] = torch.where(active, act, ra[:, i])
+                rf[:, i] = torch.where(active, env.flags & 3, rf[:, i])
+                active = active & ~done_b
+            obs_c.append(ro.cpu().numpy()), act_c.append(ra.cpu().numpy()), flags_c.append(rf.cpu().numpy())
+            t += k
+            if not bool(active.any()):
+                break
+        if int(nan.item()) > 0:
+            raise RuntimeError("NaN in probs")
+    return cur_obs0, obs_c, act_c, flags_c
+
+
+def generate_expert_data(policy="ppo_model.pth", num_episodes=100, variant=ENV_VARIANT, seed=SEED, max_steps=None,
+                         out="expert_data.npz", device="cuda"):
+    """num_episodes greedy episodes of `policy` (an LSTMActorCritic, MLPActorCritic or model.PPOActorCritic, or the path of a
+    checkpoint train_ppo2.0.py wrote; the reference loads 'ppo_model.pth') as num_episodes parallel environments seeded with
+    `seed`; every (state, action) pair goes to `out` (None: not written).  Returns (states f32 [M, obs_dim], actions i64 [M])."""
+    if isinstance(policy, (str, bytes)) or hasattr(policy, "__fspath__"):
+        policy = load_policy(policy, device)
+    _, core = _policy_core(policy)
+    trend_k = getattr(core, "obs_dim", 6) - 6
+    env = VecMethaneEnv(num_episodes, variant, core.device, seed=seed, trend_k=trend_k)
+    states, actions = expert_pairs(*greedy_records(policy, env, max_steps))
+    if out:
+        np.savez(out, states=states, actions=actions)
+        print(f"expert data: {num_episodes} episodes, {len(actions)} pairs -> {out}")
+    return states, actions
+
+
+if __name__ == "__main__":
+    generate_expert_data()

@@ -5,6 +5,9 @@
 # layout csrc/mlp.hip consumes; state_dict() keys are the reference's (feature.{0,1,3,4}.*,
 # actor.*, critic.*), so reference .pth files load and `torch.optim.Adam(model.parameters())`
 # works unchanged.  The LSTM policies of BASELINE.json live in uavppo/policy.py.
+#
+# Discriminator / compute_discriminator_loss / get_expert_data are the GAIL names of the same file (PPOV2.0/model.py:58-70,
+# 169-198; the same text in PPOV1.1/model.py), on the fused kernels of csrc/disc.hip (uavppo/gail.py).
 import numpy as np
 import torch
 import torch.nn as nn
@@ -13,6 +16,7 @@ from config import (DECAY_FACTOR, DEVICE, EXPLORE_BONUS, INITIAL_RADIUS, MIN_RAD
                     WINDOW_SIZE)  # noqa: F401
 from uavppo import ops
 from uavppo.curriculum import Curriculum
+from uavppo.gail import Discriminator, as_action_index  # noqa: F401  (Discriminator: model.py:58-70)
 from uavppo.policy import MLPActorCritic
 
 
@@ -103,3 +107,30 @@ class PPOTrainer:
         if full:
             print(f"Curriculum Update: radius -> {self._c.current_radius:.1f}")
         return before
+
+
+def compute_discriminator_loss(discriminator, expert_states, expert_actions, policy_states, policy_actions):
+    """PPOV2.0/model.py:169-190: BCELoss(D(expert), 1) + BCELoss(D(policy), 0), both means, as a 0-dim tensor; forward, both
+    losses and the backward pass are ONE kernel pass (uav_disc_grad), which leaves the gradient of the returned scalar in
+    `discriminator.grad` (laid out as `discriminator.flat`) -- there is no autograd graph to call .backward() on.  Actions are
+    integer indices (or one-hot rows).
+
+    The reference's quirk, not kept: it sizes BOTH one-hot matrices with `policy_actions.max().item() + 1`, so a policy batch
+    that happens not to contain the largest action gives the discriminator an input of the wrong width (a shape error in its
+    first Linear), and an expert action above that maximum an index error.  Here the width is the discriminator's own
+    action_dim.  The gradient is taken through the logit (include/uavppo.h, uav_disc_grad): it equals autograd's wherever
+    D (1 - D) is representable and stays the true gradient where autograd's rounds to 0."""
+    es, ea = discriminator._rows(expert_states, expert_actions)
+    ps, pa = discriminator._rows(policy_states, policy_actions)
+    sums, _ = ops.disc_grad(discriminator.flat, es, ea, ps, pa, discriminator.action_dim, grad=discriminator.grad)
+    s = sums.cpu()
+    if s[3] > 0:
+        raise RuntimeError("NaN in discriminator output (or an action outside the action set)")
+    return (s[0] / max(len(ea), 1) + s[1] / max(len(pa), 1)).to(torch.float32)
+
+
+def get_expert_data(path="expert_data.npz"):
+    """PPOV2.0/model.py:195-198: (states FloatTensor [M, 6], actions LongTensor [M]) from the .npz generate_expert_data.py
+    writes (keys `states`, `actions`)."""
+    data = np.load(path)
+    return torch.FloatTensor(np.asarray(data["states"], dtype=np.float32)), torch.LongTensor(np.asarray(data["actions"], dtype=np.int64))

@@ -1,0 +1,76 @@
+# train_ppo_gail.py -- PPO + GAIL on MI355X.
+#
+# Counterpart of the reference's PPOV1.1/train_ppo_gail.py: a policy trained by PPO while a discriminator learns to tell the
+# rollout's (state, action) pairs from an expert set (generate_expert_data.py), one discriminator step per policy update
+# (:150-175).  Here the loop is uavppo.gail.GAILTrainer over NUM_ENVS vectorised environments, and the discriminator's output
+# is USED: the rollout's reward is env_coef * r + gail_coef * softplus(z) (the reference computes the discriminator and feeds
+# it to nothing).  Not carried over: the V1.0-style inline PPO update of :71-148 (the policy side is the project's
+# _update_model path), the TensorBoard histograms, PPOV1.1/evaluate_model.py.
+import os
+
+import numpy as np
+import torch
+
+from config import (CLIP_EPSILON, ENTROPY_BETA, ENV_VARIANT, EPOCHS, GAE_MODE, GAMMA, HIDDEN, HORIZON, LAMBDA, LEARNING_RATE, NUM_ENVS,
+                    NUM_LAYERS, NUM_MINIBATCHES, POLICY, SEED)
+from model import Discriminator, compute_discriminator_loss, get_expert_data  # noqa: F401  (train_ppo_gail.py:24-27)
+from uavppo.gail import GAILTrainer
+
+
+def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert_path="expert_data.npz", policy=POLICY,
+                   hidden=HIDDEN, gail_coef=1.0, env_coef=1.0, disc_lr=LEARNING_RATE, disc_steps=1, seed=SEED, device="cuda",
+                   model_path="ppo_gail_model.pth", disc_path="discriminator.pth", max_iterations=None):
+    """Run GAILTrainer until num_episodes episodes have finished (the reference trains 2000, train_ppo_gail.py:49) or
+    max_iterations rollouts were collected; print the reference's progress line every 10 iterations (:201-203, its
+    `episode` read as the iteration); save the policy as ppo_gail_model.pth (:208) and the discriminator as
+    discriminator.pth.  Returns the trainer."""
+    states, actions = get_expert_data(expert_path)
+    tr = GAILTrainer(num_envs, horizon, policy, hidden=hidden, layers=NUM_LAYERS, variant=ENV_VARIANT, seed=seed, device=device,
+                     gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, gamma=GAMMA, lam=LAMBDA, clip=CLIP_EPSILON,
+                     ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, expert=(states, actions), gail_coef=gail_coef,
+                     env_coef=env_coef, disc_lr=disc_lr, disc_steps=disc_steps)
+    it, mean_rewards = 0, []
+    while tr.episodes_lagged < num_episodes and (max_iterations is None or it < max_iterations):
+        tr.train_iteration()
+        if it % 10 == 0:
+            ended = tr.buf["done"].sum().clamp(min=1.0)
+            mean_rewards.append(float(tr.buf["rew"].sum() / ended))          # reward collected per episode ended in this rollout
+            tr.losses()
+            el, pl, acc = tr.disc_losses()
+            rate = tr.successes_done / max(tr.episodes_done, 1)
+            print(f"Episode {it} | Mean Reward: {mean_rewards[-1]:.2f} | Success Rate: {rate:.2%}")
+            print(f"  episodes {tr.episodes_done} | radius {tr.radius:.1f} | D expert {el:.4f} policy {pl:.4f} accuracy {acc:.3f}")
+        it += 1
+    tr.losses()
+    tr.disc_losses()
+    for path, sd in ((model_path, tr.policy.state_dict()), (disc_path, tr.disc.state_dict())):
+        if path:
+            os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+            torch.save({k: v.cpu() for k, v in sd.items()}, path)
+    print(f"training finished: {tr.episodes_done} episodes, {it} iterations; policy saved as {model_path}, discriminator as {disc_path}")
+    return tr
+
+
+def _main(argv):
+    import argparse
+    ap = argparse.ArgumentParser(description="PPO + GAIL (vectorised)")
+    ap.add_argument("--episodes", type=int, default=2000)
+    ap.add_argument("--num-envs", type=int, default=NUM_ENVS)
+    ap.add_argument("--horizon", type=int, default=HORIZON)
+    ap.add_argument("--expert", default="expert_data.npz")
+    ap.add_argument("--policy", default=POLICY, choices=("mlp", "lstm"))
+    ap.add_argument("--hidden", type=int, default=HIDDEN)
+    ap.add_argument("--gail-coef", type=float, default=1.0)
+    ap.add_argument("--env-coef", type=float, default=1.0)
+    ap.add_argument("--max-iterations", type=int, default=None)
+    ap.add_argument("--model-path", default="ppo_gail_model.pth")
+    ap.add_argument("--disc-path", default="discriminator.pth")
+    a = ap.parse_args(argv)
+    train_ppo_gail(a.episodes, a.num_envs, a.horizon, a.expert, a.policy, a.hidden, a.gail_coef, a.env_coef,
+                   max_iterations=a.max_iterations, model_path=a.model_path, disc_path=a.disc_path)
+
+
+if __name__ == "__main__":
+    import sys
+    os.environ["KMP_DUPLICATE_LIB_OK"] = "TRUE"
+    _main(sys.argv[1:])

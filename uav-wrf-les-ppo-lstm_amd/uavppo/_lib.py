@@ -65,6 +65,9 @@ SIGNATURES = {
     "uav_clip_adamw": (I32, [P, P, P, P, P, I64, I64, F32, F32, F32, F32, F32, F32, P, P]),
     "uav_smooth_l1": (I32, [P, P, P, I64, F32, P, P, P]),
     "uav_mse_bce": (I32, [P, P, P, I64, P, P, P]),
+    "uav_disc_param_count": (SZ, [I32, I32, I32]),
+    "uav_disc_grad": (I32, [P, P, P, P, I64, P, P, I64, I32, I32, I32, F32, F32, P, P, P]),
+    "uav_disc_reward": (I32, [P, P, P, P, I64, I32, I32, I32, F32, F32, P, P, P]),
     "uav_lstm_stepper_bytes": (SZ, [I32, I32, I32]),
     "uav_lstm_stepper_begin": (I32, [P, P, P, P, P, P, P, P, I32, I32, I32, P]),
     "uav_lstm_stepper_step": (I32, [P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P]),

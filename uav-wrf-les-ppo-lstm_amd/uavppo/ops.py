@@ -889,3 +889,52 @@ def greedy_episodes(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c,
                                     _p(nan_count, I32, (1,), "nan_count"), _stream()), "uav_greedy_episodes")
     if _t is not None:
         _t.record()
+
+
+# ----------------------------------------------------------------------------- GAIL discriminator (csrc/disc.hip)
+DISC_HIDDEN = 128
+
+
+def disc_param_count(obs_dim, n_act, hidden=DISC_HIDDEN):
+    n = int(lib().uav_disc_param_count(int(obs_dim), int(n_act), int(hidden)))
+    if n == 0:
+        raise RuntimeError(f"uav_disc_param_count failed: {lib().uav_last_error().decode()}")
+    return n
+
+
+def disc_grad(params, obs_e, act_e, obs_p, act_p, n_act, inv_ne=None, inv_np=None, loss_sums=None, grad=None, ctx=None):
+    """Forward + two BCE means + backward of the discriminator over the expert rows (obs_e [n_e, obs_dim], act_e i32 [n_e],
+    label 1) and the policy rows (label 0) in one pass (uav_disc_grad).  inv_ne / inv_np default to 1 / n_e, 1 / n_p (ranks pass
+    1 / the global counts).  Returns (loss_sums f64[4]: expert sum, policy sum, correct rows, NaN / bad-action rows; grad
+    [param_count]).  ctx: a uav_ctx handle of the tensors' device to run on instead of the device's shared one."""
+    n_e, n_p = int(obs_e.shape[0]), int(obs_p.shape[0])
+    od = int(obs_p.shape[1]) if n_p else int(obs_e.shape[1])
+    P = disc_param_count(od, n_act)
+    loss_sums = torch.empty(4, dtype=F64, device=params.device) if loss_sums is None else loss_sums
+    grad = torch.empty(P, dtype=F32, device=params.device) if grad is None else grad
+    inv_ne = (1.0 / n_e if n_e else 0.0) if inv_ne is None else inv_ne
+    inv_np = (1.0 / n_p if n_p else 0.0) if inv_np is None else inv_np
+    _t = KERNEL_TIMER.bracket("disc_grad")
+    check(lib().uav_disc_grad(_h(params) if ctx is None else ctx, _p(params, F32, (P,), "params"),
+                              _p(obs_e, F32, (n_e, od), "obs_e") if n_e else None, _p(act_e, I32, (n_e,), "act_e") if n_e else None, n_e,
+                              _p(obs_p, F32, (n_p, od), "obs_p") if n_p else None, _p(act_p, I32, (n_p,), "act_p") if n_p else None, n_p,
+                              od, int(n_act), DISC_HIDDEN, float(inv_ne), float(inv_np), _p(loss_sums, F64, (4,), "loss_sums"),
+                              _p(grad, F32, (P,), "grad"), _stream()), "uav_disc_grad")
+    if _t is not None:
+        _t.record()
+    return loss_sums, grad
+
+
+def disc_reward(params, obs, act, n_act, gail_coef=1.0, env_coef=1.0, rew_env=None, out=None):
+    """out[i] = env_coef * rew_env[i] + gail_coef * softplus(z_i) over the rows obs [n, obs_dim], act i32 [n] (uav_disc_reward);
+    rew_env None = 0; out may be rew_env itself."""
+    n, od = int(obs.shape[0]), int(obs.shape[1])
+    P = disc_param_count(od, n_act)
+    out = torch.empty(n, dtype=F32, device=obs.device) if out is None else out
+    _t = KERNEL_TIMER.bracket("disc_reward")
+    check(lib().uav_disc_reward(_h(params), _p(params, F32, (P,), "params"), _p(obs, F32, (n, od), "obs"), _p(act, I32, (n,), "act"), n,
+                                od, int(n_act), DISC_HIDDEN, float(env_coef), float(gail_coef), _p(rew_env, F32, (n,), "rew_env"),
+                                _p(out, F32, (n,), "rew_out"), _stream()), "uav_disc_reward")
+    if _t is not None:
+        _t.record()
+    return out

@@ -483,6 +483,44 @@ int uav_greedy_episodes(uav_ctx* ctx, void* env_state, int n_env, const uav_env_
                         const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags, int32_t* nan_count,
                         uav_stream stream);
 
+/* The "autonomous stop" rule of PPOV1.1/evaluate_model.py:25-37 (host struct): once an env's window holds `window` agent
+ * positions (f32 pairs, one per stepped step), the episode stops when
+ *     np.std(window, axis=0).mean() < pos_std_max   and   ((conc_coef * obs[2]) * conc_peak) * conc_peak > conc_min,
+ * all in f32 and in numpy's order of operations (csrc/stop_rule_core.h).  The reference's values: 10, 2.0, 2.0 (CONC_REWARD_COEF),
+ * 100.0 (CONC_PEAK), 80.0.  window is 1 .. 16.  pos_std_max = 0 gives a rule that never fires (a std is never below 0).
+ * These entry points were added without a change of UAV_ABI_VERSION, which stays 9: they only add symbols, and nothing that
+ * existed changed its signature or its behaviour. */
+typedef struct uav_stop_rule {
+    int32_t window;
+    float   pos_std_max, conc_coef, conc_peak, conc_min;
+} uav_stop_rule;
+
+/* uav_greedy_episodes with the stop rule applied on the device after every env step: the step's agent_pos is pushed into the
+ * env's window, the rule is evaluated, and on a hit the env's active[n] is cleared exactly as `done` clears it (state blob, h
+ * and c stay as that step left them) and the step's record carries flags bit3 = stopped by the rule (beside bit0 / bit1 when
+ * the step also ended the episode).  An episode therefore ends at its first record with bit0 or bit3.
+ * The window carries across calls in stop_win f32 [N][window][2] and stop_cnt i32 [N] (in/out; zero stop_cnt starts an
+ * episode): rows 0 .. stop_cnt[n]-1 are the env's last positions in time order, oldest first; stop_cnt saturates at window;
+ * rows beyond stop_cnt[n], and the rows of an env that is not stepped, are left alone.  k calls of steps / k steps give what
+ * one call gives, bit for bit, window buffers included.
+ * rule_val (or NULL) f32 [N][steps]: pos_std of every stepped step whose window is full, NaN otherwise (tests compare the
+ * value itself; with NULL the std is only formed on steps whose concentration half holds).
+ * Refused like uav_greedy_episodes, and: rule NULL, window outside 1 .. 16, stop_win or stop_cnt NULL. */
+int uav_greedy_episodes_stop(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg /*host*/, int policy_kind,
+                             const float* params, int hidden, int steps, float* cur_obs, float* h, float* c, uint8_t* active,
+                             const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags, int32_t* nan_count,
+                             const uav_stop_rule* rule /*host*/, float* stop_win, int32_t* stop_cnt, float* rule_val,
+                             uav_stream stream);
+
+/* One step of the same rule for n envs stepped by other means (policies the fused kernels refuse): for every env with
+ * active[i] != 0, push pos[i] (f32 [n][2], agent_pos after the move) into its window (stop_win / stop_cnt as above), evaluate
+ * the rule with obs2[i * obs2_stride] (obs[2] of the observation the step returned), and write stop u8 [n] (1 = the rule
+ * fires) and value f32 [n] (pos_std, NaN while the window is not full); envs with active[i] = 0 get stop 0, value NaN and
+ * keep their window.  active NULL = all active.  The same function as the fused kernels', so the same bits. */
+int uav_stop_stability(uav_ctx* ctx, int n, const uav_stop_rule* rule /*host*/, const float* pos, const float* obs2,
+                       int64_t obs2_stride, const uint8_t* active, float* stop_win, int32_t* stop_cnt, uint8_t* stop,
+                       float* value, uav_stream stream);
+
 /* The tail of step t of a step-wise rollout as ONE launch (train_ppo2.0.py:165-198 after the recurrent layers): policy heads of
  * the top layer (heads[:, t] = y_t W_head^T + b_head, the sums of uav_gemm_f32's few-column kernel bit for bit; y = row t of a
  * [n][T][hidden] array given as the pointer to y[0][t] and its row stride y_stride floats, likewise heads / heads_stride),

@@ -16,6 +16,7 @@
 // update's first forward pass.
 #include "env_core.h"
 #include "loss_core.h"
+#include "stop_rule_core.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -463,6 +464,8 @@ struct MlpRollBufs {
     float* cur_obs; float* obs; int32_t* act; float* rew; float* val; float* logp; float* done; uint8_t* flags;
     float* last_val; const int32_t* forced_act; const double* noise; int32_t* nan_count; float* info; float* heads;
     uint8_t* active; float* pos;    // greedy episodes only: active u8 [N] in/out, agent_pos record [N][T][2]
+    // greedy episodes with the stop rule (STOP) only: window [N][window][2] + fill [N] in/out (stop_rule_core.h), optional pos_std [N][T]
+    float* stop_win; int32_t* stop_cnt; float* rule_val; StopRule rule;
 };
 
 constexpr size_t ROLL_LDS = (size_t)(Tiles<1>::FLOATS + 16 * WS2) * sizeof(float);
@@ -471,7 +474,9 @@ constexpr size_t ROLL_LDS = (size_t)(Tiles<1>::FLOATS + 16 * WS2) * sizeof(float
 // code, so the rollout's log-probabilities stay bit-identical to the update's first forward pass.
 // GREEDY: greedy evaluation episodes (uav_greedy_episodes; see rollout_lstm_kernel in rollout.hip for the record format):
 // argmax of the logits, no auto-reset, an ended or inactive env is never stepped.  GREEDY = false is the trainer's rollout.
-template <bool H3, bool GREEDY = false>
+// STOP (with GREEDY): evaluate_model.py's stop rule after every env step, as in rollout_lstm_kernel (flags bit3; a hit ends the
+// episode as `done` does).  STOP = false compiles to the kernels as they were.
+template <bool H3, bool GREEDY = false, bool STOP = false>
 __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBlob blob, int N, int T, uint64_t iter,
                                                             const float* __restrict__ params, MlpRollBufs B) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -480,7 +485,16 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
     __shared__ unsigned short vis[MT * NVIS];
     __shared__ EnvState es_s[MT];
     __shared__ double env_tab[ENV_LDS_TABLE_DOUBLES];            // pow(vc, 0.75) | ripple factors (env_core.h)
-    static_assert(ROLL_LDS + sizeof(vis) + sizeof(es_s) + sizeof(env_tab) <= 160 * 1024, "rollout_mlp_kernel: LDS over 160 KB per workgroup");
+    static_assert(!STOP || GREEDY, "rollout_mlp_kernel: the stop rule belongs to the greedy episodes");
+    constexpr size_t STOP_LDS = STOP ? MT * 2 * STOP_WIN_MAX * sizeof(float) : 0;      // the stop rule's position rings
+    static_assert(ROLL_LDS + sizeof(vis) + sizeof(es_s) + sizeof(env_tab) + STOP_LDS <= 160 * 1024, "rollout_mlp_kernel: LDS over 160 KB per workgroup");
+    float* ring = nullptr;                                       // STOP: this env lane's [STOP_WIN_MAX][2] ring
+    StopRing sr{0, 0};
+    if constexpr (STOP) {
+        __shared__ float rings[MT * 2 * STOP_WIN_MAX];
+        static_assert(sizeof(rings) == STOP_LDS, "stop rings");
+        ring = rings + (threadIdx.x & 15) * 2 * STOP_WIN_MAX;
+    }
     EnvParams P = P_arg;
     env_params_refresh(P);
     env_tables_to_lds(P, env_tab, threadIdx.x, 512);
@@ -537,6 +551,7 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
 #pragma unroll
         for (int f = 0; f < 8; ++f) L.X[lane * 8 + f] = f < IN ? B.cur_obs[(size_t)n * IN + f] : 0.f;
         if constexpr (GREEDY) on = ran = my_env < N && B.active[n] != 0;
+        if constexpr (STOP) sr = stop_ring_load(ring, B.stop_win + (size_t)n * B.rule.window * 2, B.stop_cnt[n], B.rule.window);
     }
     lds_barrier();
 
@@ -618,18 +633,24 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
                             env_step_wind(es, z0, z1, wind_x, wind_y);
                             StepOut so;
                             env_step_core(P, eg, es, myvis, a_sel, wind_x, wind_y, so);
+                            bool hit = false;                    // STOP: the rule fires on this step
+                            if constexpr (STOP) {
+                                float rv;
+                                hit = stop_rule_step(B.rule, ring, sr, es.px, es.py, so.obs[2], B.rule_val != nullptr, rv);
+                                if (B.rule_val && env_lane) B.rule_val[row] = rv;
+                            }
                             if (env_lane) {
 #pragma unroll
                                 for (int f = 0; f < IN; ++f) B.obs[row * IN + f] = so.obs[f];
                                 B.act[row] = a_sel;
-                                B.flags[row] = (uint8_t)((so.done ? 1 : 0) | (so.reached ? 2 : 0));
+                                B.flags[row] = (uint8_t)((so.done ? 1 : 0) | (so.reached ? 2 : 0) | (hit ? 8 : 0));
                                 B.pos[row * 2] = es.px;
                                 B.pos[row * 2 + 1] = es.py;
                             }
 #pragma unroll
                             for (int f = 0; f < IN; ++f) L.X[lane * 8 + f] = so.obs[f];
                             es_s[lane] = es;
-                            if (so.done) on = false;
+                            if (so.done || hit) on = false;
                         } else if (env_lane) {
 #pragma unroll
                             for (int f = 0; f < IN; ++f) B.obs[row * IN + f] = 0.f;
@@ -637,6 +658,8 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
                             B.flags[row] = 4;
                             B.pos[row * 2] = 0.f;
                             B.pos[row * 2 + 1] = 0.f;
+                            if constexpr (STOP)
+                                if (B.rule_val) B.rule_val[row] = __builtin_nanf("");
                         }
                         (void)V;
                     } else {
@@ -726,6 +749,8 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
         for (int k = 0; k < NVIS; ++k) blob.visited[(size_t)my_env * NVIS + k] = myvis[k];
 #pragma unroll
         for (int f = 0; f < IN; ++f) B.cur_obs[(size_t)my_env * IN + f] = L.X[lane * 8 + f];
+        if constexpr (STOP)
+            B.stop_cnt[my_env] = stop_ring_store(ring, sr, B.stop_win + (size_t)my_env * B.rule.window * 2, B.rule.window);
     }
 }
 
@@ -1318,6 +1343,21 @@ int launch_greedy_mlp(const EnvParams& P, void* env_state, int n_env, const floa
     UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_mlp_kernel<true, true>), (int)ROLL_LDS));
     hipLaunchKernelGGL((rollout_mlp_kernel<true, true>), dim3((n_env + MT - 1) / MT), dim3(512), ROLL_LDS, st, P, blob, n_env, steps,
                        0, params, B);
+    UAV_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- the same with the stop rule (uav_greedy_episodes_stop; the caller checked the rule and its buffers)
+int launch_greedy_mlp_stop(const EnvParams& P, void* env_state, int n_env, const float* params, int steps, float* cur_obs,
+                           uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
+                           int32_t* nan_count, const StopRule& rule, float* stop_win, int32_t* stop_cnt, float* rule_val,
+                           hipStream_t st) {
+    MlpRollBufs B{cur_obs, obs, act, nullptr, nullptr, nullptr, nullptr, flags, nullptr, nullptr, noise, nan_count, nullptr, nullptr,
+                  active, pos, stop_win, stop_cnt, rule_val, rule};
+    EnvBlob blob = env_blob_view(env_state, n_env);
+    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_mlp_kernel<true, true, true>), (int)ROLL_LDS));
+    hipLaunchKernelGGL((rollout_mlp_kernel<true, true, true>), dim3((n_env + MT - 1) / MT), dim3(512), ROLL_LDS, st, P, blob, n_env,
+                       steps, 0, params, B);
     UAV_LAUNCH_CHECK();
     return 0;
 }

@@ -21,6 +21,7 @@
 #include "env_core.h"
 #include "loss_core.h"
 #include "rows_dot_core.h"
+#include "stop_rule_core.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -32,6 +33,10 @@ int launch_rollout_mlp(uav_ctx* ctx, void* env_state, int n_env, const uav_env_c
 int launch_greedy_mlp(const EnvParams& P, void* env_state, int n_env, const float* params, int steps, float* cur_obs,
                       uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
                       int32_t* nan_count, hipStream_t st);
+int launch_greedy_mlp_stop(const EnvParams& P, void* env_state, int n_env, const float* params, int steps, float* cur_obs,
+                           uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
+                           int32_t* nan_count, const StopRule& rule, float* stop_win, int32_t* stop_cnt, float* rule_val,
+                           hipStream_t st);
 
 constexpr int RMT = 16;
 
@@ -75,6 +80,8 @@ struct RolloutBufs {
     float* heads;               // optional [N][T][NA+1]: logits | value of the step
     float* stash; float* y;     // optional: BPTT stash [N][T][6H] + y [N][T][H], so PPO epoch 0 skips its forward pass
     uint8_t* active; float* pos;  // greedy episodes only: active u8 [N] in/out, agent_pos record [N][T][2]
+    // greedy episodes with the stop rule (STOP) only: window [N][window][2] + fill [N] in/out (stop_rule_core.h), optional pos_std [N][T]
+    float* stop_win; int32_t* stop_cnt; float* rule_val; StopRule rule;
 };
 
 // The recurrent product h W_hh^T runs on the fp16 matrix pipe at f32 accuracy (two-piece operand split, three piece
@@ -89,7 +96,9 @@ struct RolloutBufs {
 // stepped again: its blob, h and c keep the values of its last step.  kbuf holds the per-env active flag then.  The record
 // per step is the action, the observation the step returned (the terminal one when done), agent_pos after the move, and flags
 // (bit0 done, bit1 reached, bit2 not stepped: act -1, obs and pos 0).  GREEDY = false is the trainer's rollout, unchanged.
-template <int H, int NA, bool GREEDY = false>
+// STOP (with GREEDY): evaluate_model.py's stop rule after every env step (stop_rule_core.h) -- the env lane keeps its window as
+// a ring in LDS, and a hit ends the episode as `done` does (flags bit3).  STOP = false compiles to the kernels as they were.
+template <int H, int NA, bool GREEDY = false, bool STOP = false>
 __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, EnvBlob blob, int N, int T,
                                                                         uint64_t iter, const float* __restrict__ params,
                                                                         RolloutBufs B) {
@@ -112,8 +121,17 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
     __shared__ double env_tab[ENV_LDS_TABLE_DOUBLES];            // pow(vc, 0.75) | ripple factors (env_core.h)
     // one workgroup per CU at h = 128 (~145 KB with the 66 KB of env tables; h = 64: ~111 KB): any growth of a table or of the
     // geometry must fail HERE, not as a launch error on the GPU box
+    static_assert(!STOP || GREEDY, "rollout_lstm_kernel: the stop rule belongs to the greedy episodes");
+    constexpr size_t STOP_LDS = STOP ? RMT * 2 * STOP_WIN_MAX * sizeof(float) : 0;     // the stop rule's position rings
     static_assert(G::LDS + sizeof(xbuf) + sizeof(kbuf) + sizeof(hd) + sizeof(vis) + sizeof(es_s) + sizeof(trs) + sizeof(acc0) +
-                      sizeof(env_tab) <= 160 * 1024, "rollout_lstm_kernel: LDS over 160 KB per workgroup");
+                      sizeof(env_tab) + STOP_LDS <= 160 * 1024, "rollout_lstm_kernel: LDS over 160 KB per workgroup");
+    float* ring = nullptr;                                       // STOP: this env lane's [STOP_WIN_MAX][2] ring
+    StopRing sr{0, 0};
+    if constexpr (STOP) {
+        __shared__ float rings[RMT * 2 * STOP_WIN_MAX];
+        static_assert(sizeof(rings) == STOP_LDS, "stop rings");
+        ring = rings + (threadIdx.x & 15) * 2 * STOP_WIN_MAX;
+    }
     EnvParams P = P_arg;
     env_params_refresh(P);
     env_tables_to_lds(P, env_tab, threadIdx.x, H * 4);
@@ -212,6 +230,8 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         if constexpr (GREEDY) {
             ran = my_env < N && B.active[n] != 0;
             kbuf[lane] = ran ? 1.f : 0.f;
+            if constexpr (STOP)
+                sr = stop_ring_load(ring, B.stop_win + (size_t)n * B.rule.window * 2, B.stop_cnt[n], B.rule.window);
         } else {
             kbuf[lane] = 1.f;
         }
@@ -478,19 +498,27 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                         EnvState es = es_s[lane];
                         StepOut so;
                         env_step_core(P, P.env_offset + my_env, es, myvis, a_sel, wind_x, wind_y, so);
+                        bool hit = false;                       // STOP: the rule fires on this step
+                        if constexpr (STOP) {
+                            float rv;
+                            hit = stop_rule_step(B.rule, ring, sr, es.px, es.py, so.obs[2], B.rule_val != nullptr, rv);
+                            if (B.rule_val && env_lane) B.rule_val[(size_t)my_env * T + t] = rv;
+                        }
                         tr[0] = __int_as_float(a_sel);
-                        tr[5] = __int_as_float((so.done ? 1 : 0) | (so.reached ? 2 : 0));
+                        tr[5] = __int_as_float((so.done ? 1 : 0) | (so.reached ? 2 : 0) | (hit ? 8 : 0));
 #pragma unroll
                         for (int f = 0; f < 6; ++f) { to[f] = so.obs[f]; xbuf[lane * 8 + f] = so.obs[f]; }
                         to[6] = es.px;
                         to[7] = es.py;
                         es_s[lane] = es;
-                        if (so.done) kbuf[lane] = 0.f;
+                        if (so.done || hit) kbuf[lane] = 0.f;
                     } else {
                         tr[0] = __int_as_float(-1);
                         tr[5] = __int_as_float(4);
 #pragma unroll
                         for (int f = 0; f < 8; ++f) to[f] = 0.f;
+                        if constexpr (STOP)
+                            if (B.rule_val && env_lane) B.rule_val[(size_t)my_env * T + t] = __builtin_nanf("");
                     }
                     (void)V;
                 } else {
@@ -590,15 +618,17 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         for (int k = 0; k < NVIS; ++k) blob.visited[(size_t)my_env * NVIS + k] = myvis[k];
 #pragma unroll
         for (int f = 0; f < 6; ++f) B.cur_obs[(size_t)my_env * 6 + f] = xbuf[lane * 8 + f];
+        if constexpr (STOP)
+            B.stop_cnt[my_env] = stop_ring_store(ring, sr, B.stop_win + (size_t)my_env * B.rule.window * 2, B.rule.window);
     }
 }
 
-template <int H, bool GREEDY = false>
+template <int H, bool GREEDY = false, bool STOP = false>
 static int launch_rollout(const EnvParams& P, EnvBlob blob, int N, int T, uint64_t iter, const float* params,
                           const RolloutBufs& B, hipStream_t st) {
     const dim3 grid((N + RMT - 1) / RMT), block(H * 4);
-    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_lstm_kernel<H, 5, GREEDY>), (int)RGeom<H>::LDS));
-    hipLaunchKernelGGL((rollout_lstm_kernel<H, 5, GREEDY>), grid, block, RGeom<H>::LDS, st, P, blob, N, T, iter, params, B);
+    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_lstm_kernel<H, 5, GREEDY, STOP>), (int)RGeom<H>::LDS));
+    hipLaunchKernelGGL((rollout_lstm_kernel<H, 5, GREEDY, STOP>), grid, block, RGeom<H>::LDS, st, P, blob, N, T, iter, params, B);
     UAV_LAUNCH_CHECK();
     return 0;
 }
@@ -751,32 +781,99 @@ extern "C" int uav_rollout(uav_ctx* ctx, void* env_state, int n_env, const uav_e
     UAV_REQUIRE(false, "uav_rollout: hidden=%d unsupported (64, 128)", hidden);
 }
 
+// uav_greedy_episodes and uav_greedy_episodes_stop: `rule` NULL = the plain greedy episodes
+static int greedy_episodes_impl(const char* who, uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg, int policy_kind,
+                                const float* params, int hidden, int steps, float* cur_obs, float* h, float* c, uint8_t* active,
+                                const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags, int32_t* nan_count,
+                                const uav_stop_rule* rule, float* stop_win, int32_t* stop_cnt, float* rule_val, hipStream_t st) {
+    UAV_REQUIRE(ctx && env_state && params && cur_obs && active && act && obs && pos && flags && nan_count,
+                "%s: NULL argument", who);
+    UAV_REQUIRE(n_env > 0 && steps > 0, "%s: n_env=%d steps=%d", who, n_env, steps);
+    UAV_REQUIRE(policy_kind == 0 || policy_kind == 1, "%s: policy_kind %d (0 = MLP, 1 = LSTM)", who, policy_kind);
+    UAV_REQUIRE(ctx->lstm_arith == UAV_ARITH_FP16X3,
+                "%s: the fused greedy kernels exist in the fp16x3 arithmetic only (handle mode %d)", who, ctx->lstm_arith);
+    StopRule R{};
+    if (rule) {
+        UAV_REQUIRE(rule->window >= 1 && rule->window <= STOP_WIN_MAX, "%s: rule window=%d (1 .. %d)", who, rule->window,
+                    STOP_WIN_MAX);
+        UAV_REQUIRE(stop_win && stop_cnt, "%s: NULL stop_win / stop_cnt (the rule's window buffers)", who);
+        R = StopRule{rule->window, rule->pos_std_max, rule->conc_coef, rule->conc_peak, rule->conc_min};
+    }
+    EnvParams P;
+    int rc = env_params_from_cfg(ctx, cfg, n_env, P);
+    if (rc) return rc;
+    UAV_REQUIRE(P.trend_k == 0, "%s: trend_k=%d unsupported (the fused kernels take 6 observation features)", who, P.trend_k);
+    UAV_REQUIRE((int64_t)n_env * steps * 6 < (1ll << 31), "%s: n_env * steps too large", who);
+    if (policy_kind == 0)
+        return rule ? launch_greedy_mlp_stop(P, env_state, n_env, params, steps, cur_obs, active, noise, act, obs, pos, flags,
+                                             nan_count, R, stop_win, stop_cnt, rule_val, st)
+                    : launch_greedy_mlp(P, env_state, n_env, params, steps, cur_obs, active, noise, act, obs, pos, flags, nan_count, st);
+    UAV_REQUIRE(h && c, "%s: LSTM policy needs h, c", who);
+    RolloutBufs B{cur_obs, h, c, obs, act, nullptr, nullptr, nullptr, nullptr, flags, nullptr, nullptr, nullptr, noise, nan_count,
+                  nullptr, nullptr, nullptr, nullptr, active, pos, stop_win, stop_cnt, rule_val, R};
+    EnvBlob blob = env_blob_view(env_state, n_env);
+    switch (hidden) {
+        case 64: return rule ? launch_rollout<64, true, true>(P, blob, n_env, steps, 0, params, B, st)
+                             : launch_rollout<64, true>(P, blob, n_env, steps, 0, params, B, st);
+        case 128: return rule ? launch_rollout<128, true, true>(P, blob, n_env, steps, 0, params, B, st)
+                              : launch_rollout<128, true>(P, blob, n_env, steps, 0, params, B, st);
+    }
+    UAV_REQUIRE(false, "%s: hidden=%d unsupported by the fused kernel (64, 128)", who, hidden);
+}
+
 extern "C" int uav_greedy_episodes(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg, int policy_kind,
                                    const float* params, int hidden, int steps, float* cur_obs, float* h, float* c,
                                    uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
                                    int32_t* nan_count, uav_stream stream) {
-    UAV_REQUIRE(ctx && env_state && params && cur_obs && active && act && obs && pos && flags && nan_count,
-                "uav_greedy_episodes: NULL argument");
-    UAV_REQUIRE(n_env > 0 && steps > 0, "uav_greedy_episodes: n_env=%d steps=%d", n_env, steps);
-    UAV_REQUIRE(policy_kind == 0 || policy_kind == 1, "uav_greedy_episodes: policy_kind %d (0 = MLP, 1 = LSTM)", policy_kind);
-    UAV_REQUIRE(ctx->lstm_arith == UAV_ARITH_FP16X3,
-                "uav_greedy_episodes: the fused greedy kernels exist in the fp16x3 arithmetic only (handle mode %d)", ctx->lstm_arith);
-    EnvParams P;
-    int rc = env_params_from_cfg(ctx, cfg, n_env, P);
-    if (rc) return rc;
-    UAV_REQUIRE(P.trend_k == 0, "uav_greedy_episodes: trend_k=%d unsupported (the fused kernels take 6 observation features)",
-                P.trend_k);
-    UAV_REQUIRE((int64_t)n_env * steps * 6 < (1ll << 31), "uav_greedy_episodes: n_env * steps too large");
-    if (policy_kind == 0)
-        return launch_greedy_mlp(P, env_state, n_env, params, steps, cur_obs, active, noise, act, obs, pos, flags, nan_count,
-                                 as_stream(stream));
-    UAV_REQUIRE(h && c, "uav_greedy_episodes: LSTM policy needs h, c");
-    RolloutBufs B{cur_obs, h, c, obs, act, nullptr, nullptr, nullptr, nullptr, flags, nullptr, nullptr, nullptr, noise, nan_count,
-                  nullptr, nullptr, nullptr, nullptr, active, pos};
-    EnvBlob blob = env_blob_view(env_state, n_env);
-    switch (hidden) {
-        case 64: return launch_rollout<64, true>(P, blob, n_env, steps, 0, params, B, as_stream(stream));
-        case 128: return launch_rollout<128, true>(P, blob, n_env, steps, 0, params, B, as_stream(stream));
+    return greedy_episodes_impl("uav_greedy_episodes", ctx, env_state, n_env, cfg, policy_kind, params, hidden, steps, cur_obs, h, c,
+                                active, noise, act, obs, pos, flags, nan_count, nullptr, nullptr, nullptr, nullptr, as_stream(stream));
+}
+
+extern "C" int uav_greedy_episodes_stop(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg, int policy_kind,
+                                        const float* params, int hidden, int steps, float* cur_obs, float* h, float* c,
+                                        uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
+                                        int32_t* nan_count, const uav_stop_rule* rule, float* stop_win, int32_t* stop_cnt,
+                                        float* rule_val, uav_stream stream) {
+    UAV_REQUIRE(rule, "uav_greedy_episodes_stop: NULL rule");
+    return greedy_episodes_impl("uav_greedy_episodes_stop", ctx, env_state, n_env, cfg, policy_kind, params, hidden, steps, cur_obs,
+                                h, c, active, noise, act, obs, pos, flags, nan_count, rule, stop_win, stop_cnt, rule_val,
+                                as_stream(stream));
+}
+
+// ---- the same rule, one step, for envs stepped by other means (uav_stop_stability): one thread per env, the window in place
+__global__ __launch_bounds__(256) void stop_stability_kernel(StopRule R, int n, const float* __restrict__ pos,
+                                                             const float* __restrict__ obs2, int64_t obs2_stride,
+                                                             const uint8_t* __restrict__ active, float* __restrict__ stop_win,
+                                                             int32_t* __restrict__ stop_cnt, uint8_t* __restrict__ stop,
+                                                             float* __restrict__ value) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (active && active[i] == 0) {
+        stop[i] = 0;
+        value[i] = __builtin_nanf("");
+        return;
     }
-    UAV_REQUIRE(false, "uav_greedy_episodes: hidden=%d unsupported by the fused kernel (64, 128)", hidden);
+    float ring[2 * STOP_WIN_MAX];
+    float* win = stop_win + (size_t)i * R.window * 2;
+    StopRing sr = stop_ring_load(ring, win, stop_cnt[i], R.window);
+    float v;
+    const bool hit = stop_rule_step(R, ring, sr, pos[2 * (size_t)i], pos[2 * (size_t)i + 1], obs2[(size_t)i * obs2_stride], true, v);
+    stop_cnt[i] = stop_ring_store(ring, sr, win, R.window);
+    stop[i] = hit ? 1 : 0;
+    value[i] = v;
+}
+
+extern "C" int uav_stop_stability(uav_ctx* ctx, int n, const uav_stop_rule* rule, const float* pos, const float* obs2,
+                                  int64_t obs2_stride, const uint8_t* active, float* stop_win, int32_t* stop_cnt, uint8_t* stop,
+                                  float* value, uav_stream stream) {
+    UAV_REQUIRE(ctx && rule && pos && obs2 && stop && value, "uav_stop_stability: NULL argument");
+    UAV_REQUIRE(n > 0 && obs2_stride >= 1, "uav_stop_stability: n=%d obs2_stride=%lld", n, (long long)obs2_stride);
+    UAV_REQUIRE(rule->window >= 1 && rule->window <= STOP_WIN_MAX, "uav_stop_stability: rule window=%d (1 .. %d)", rule->window,
+                STOP_WIN_MAX);
+    UAV_REQUIRE(stop_win && stop_cnt, "uav_stop_stability: NULL stop_win / stop_cnt (the rule's window buffers)");
+    const StopRule R{rule->window, rule->pos_std_max, rule->conc_coef, rule->conc_peak, rule->conc_min};
+    hipLaunchKernelGGL(stop_stability_kernel, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), R, n, pos, obs2, obs2_stride,
+                       active, stop_win, stop_cnt, stop, value);
+    UAV_LAUNCH_CHECK();
+    return 0;
 }

@@ -26,6 +26,12 @@ class EnvCfg(C.Structure):
                 ("seed", C.c_uint64), ("bank", C.c_void_p), ("bank_src", C.c_void_p), ("curriculum", C.c_void_p)]
 
 
+class StopRule(C.Structure):
+    """struct uav_stop_rule (include/uavppo.h)."""
+    _fields_ = [("window", C.c_int32), ("pos_std_max", C.c_float), ("conc_coef", C.c_float), ("conc_peak", C.c_float),
+                ("conc_min", C.c_float)]
+
+
 class StepperCall(C.Structure):
     """uav_stepper_call (include/uavppo.h)"""
     _fields_ = [("state", C.c_void_p), ("x", C.c_void_p), ("below", C.c_void_p), ("keep_t", C.c_void_p), ("t", C.c_int), ("I", C.c_int),
@@ -97,6 +103,9 @@ SIGNATURES = {
     "uav_rollout": (I32, [P, P, I32, C.POINTER(EnvCfg), I32, P, I32, I32, U64, P, P, P, P, P, P, P, P, P, P,
                           P, P, P, P, P, P, P, P, P, P]),
     "uav_greedy_episodes": (I32, [P, P, I32, C.POINTER(EnvCfg), I32, P, I32, I32, P, P, P, P, P, P, P, P, P, P, P]),
+    "uav_greedy_episodes_stop": (I32, [P, P, I32, C.POINTER(EnvCfg), I32, P, I32, I32, P, P, P, P, P, P, P, P, P, P,
+                                       C.POINTER(StopRule), P, P, P, P]),
+    "uav_stop_stability": (I32, [P, I32, C.POINTER(StopRule), P, P, I64, P, P, P, P, P, P]),
     "uav_rccl_version": (I32, [C.POINTER(C.c_int)]),
     "uav_comm_unique_id": (I32, [P]),
     "uav_comm_init": (I32, [P, P, I32, I32]),

@@ -891,6 +891,62 @@ def greedy_episodes(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c,
         _t.record()
 
 
+STOP_WIN_MAX = 16
+
+
+def make_stop_rule(window=10, pos_std_max=2.0, conc_coef=2.0, conc_peak=100.0, conc_min=80.0):
+    """struct uav_stop_rule; the defaults are PPOV1.1/evaluate_model.py's (window 10, std below 2.0 px, CONC_REWARD_COEF 2.0,
+    CONC_PEAK 100.0, threshold 0.8 * CONC_PEAK).  pos_std_max = 0 never fires."""
+    if not 1 <= int(window) <= STOP_WIN_MAX:
+        raise RuntimeError(f"stop rule: window {window} outside 1 .. {STOP_WIN_MAX}")
+    return _lib.StopRule(int(window), float(pos_std_max), float(conc_coef), float(conc_peak), float(conc_min))
+
+
+def greedy_episodes_stop(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, rule, stop_win, stop_cnt,
+                         noise=None, nan_count=None, rule_val=None):
+    """greedy_episodes with evaluate_model.py's stop rule applied on the device after every step (uav_greedy_episodes_stop):
+    a hit ends the env's episode as `done` does and sets flags bit3 in the step's record.  rule: make_stop_rule(...);
+    stop_win f32 [N, window, 2] (the env's last positions, oldest first) and stop_cnt i32 [N] (valid rows) are in/out and
+    carry the window across calls (zeros start an episode); rule_val: optional f32 [N, steps], pos_std of every stepped step
+    with a full window, NaN otherwise."""
+    N, T, W = n_env, steps, int(rule.window)
+    kind = 0 if hidden == 0 else 1
+    if nan_count is None:
+        nan_count = torch.zeros(1, dtype=I32, device=cur_obs.device)
+    _t = KERNEL_TIMER.bracket("greedy")
+    check(lib().uav_greedy_episodes_stop(_h(cur_obs), _p(env_state, U8, name="env state"), N, C.byref(cfg), kind,
+                                         _p(params, F32, name="params"), int(hidden), T, _p(cur_obs, F32, (N, 6), "cur_obs"),
+                                         _p(h, F32, (N, hidden), "h") if kind else None,
+                                         _p(c, F32, (N, hidden), "c") if kind else None,
+                                         _p(active, U8, (N,), "active"), _p(noise, F64, (N, T, 2), "noise"),
+                                         _p(recs["act"], I32, (N, T), "act"), _p(recs["obs"], F32, (N, T, 6), "obs"),
+                                         _p(recs["pos"], F32, (N, T, 2), "pos"), _p(recs["flags"], U8, (N, T), "flags"),
+                                         _p(nan_count, I32, (1,), "nan_count"), C.byref(rule),
+                                         _p(stop_win, F32, (N, W, 2), "stop_win"), _p(stop_cnt, I32, (N,), "stop_cnt"),
+                                         _p(rule_val, F32, (N, T), "rule_val"), _stream()), "uav_greedy_episodes_stop")
+    if _t is not None:
+        _t.record()
+
+
+def stop_stability(rule, pos, obs2, stop_win, stop_cnt, active=None, stop=None, value=None):
+    """One step of the stop rule for envs stepped by other means (uav_stop_stability): pos f32 [N, 2] (agent_pos after the
+    move), obs2 f32 [N] or a column view such as obs[:, 2] (any element stride), active u8 [N] or None (all).  Updates
+    stop_win [N, window, 2] / stop_cnt [N]; returns (stop u8 [N], value f32 [N]: pos_std, NaN while the window is not full).
+    Inactive envs: stop 0, value NaN, window untouched."""
+    N, W = pos.shape[0], int(rule.window)
+    if obs2.dim() != 1 or obs2.shape[0] != N or obs2.dtype != F32 or not obs2.is_cuda:
+        raise RuntimeError(f"obs2: expected a GPU float32 vector of {N} elements, got {tuple(obs2.shape)} {obs2.dtype}")
+    if stop is None:
+        stop = torch.empty(N, dtype=U8, device=pos.device)
+    if value is None:
+        value = torch.empty(N, dtype=F32, device=pos.device)
+    check(lib().uav_stop_stability(_h(pos), N, C.byref(rule), _p(pos, F32, (N, 2), "pos"), C.c_void_p(obs2.data_ptr()),
+                                   int(obs2.stride(0)) if N > 1 else 1, _p(active, U8, (N,), "active"),
+                                   _p(stop_win, F32, (N, W, 2), "stop_win"), _p(stop_cnt, I32, (N,), "stop_cnt"),
+                                   _p(stop, U8, (N,), "stop"), _p(value, F32, (N,), "value"), _stream()), "uav_stop_stability")
+    return stop, value
+
+
 # ----------------------------------------------------------------------------- GAIL discriminator (csrc/disc.hip)
 DISC_HIDDEN = 128
 

@@ -303,7 +303,8 @@ int uav_mlp_ppo_grad(uav_ctx* ctx, const float* params, const float* obs, const 
  * the BPTT stash f32 [N][T][6H] = gates(i,f,g,o after activation) | c_prev | h_prev.  The h_prev slot [.., 5H:6H] is opaque scratch:
  * it is written only where uav_lstm_wgrad reads h_prev from it (H other than 64 / 128 / 256, the wide-range arithmetic modes at
  * H = 256, UAV_DEBUG_DG_F32); with I <= 6 at H = 64 / 128 and at H = 256 on the fp16-split arithmetic the weight gradients take
- * h_prev[n][t] = y[n][t-1] keep[n][t] (h0 at t = 0) from y and the slot stays untouched.
+ * h_prev[n][t] = y[n][t-1] keep[n][t] (h0 at t = 0) from y and the slot stays untouched.  With I = 7 / 8 at H = 64 / 128 the slot
+ * is written (uav_lstm_wgrad reads it there), by uav_lstm_fwd and by uav_rollout's stash alike.
  * w_ih [4H][I], w_hh [4H][H], b_ih,b_hh [4H].
  * heads != NULL: also heads [N][T][n_heads] = y W_head^T + b_head (the actor | critic Linear layers of
  * model.py:44,52 applied to the top layer; w_head [n_heads][H], b_head [n_heads], n_heads <= 8), computed inside
@@ -445,12 +446,15 @@ int uav_env_materialise(uav_ctx* ctx, const void* state, int n_env, const uav_en
  * policy step + sample + env step + store, T steps in one launch; one workgroup owns a tile
  * of envs and keeps h/c in LDS/registers across the time loop.
  * policy_kind 0 = the reference's MLP 6-256-128 (params as uav_mlp_fwd; h, c, keep, stash, y_out unused / NULL; `hidden`
- * ignored), 1 = single-layer LSTM (params: w_ih w_hh b_ih b_hh Whead bhead).  Buffers (env,T,.) : obs [N][T][6], act i32, rew, val, logp, done f32
- * [N][T], flags u8 [N][T].  cur_obs [N][6] in/out (state to act on), h,c [N][H] in/out (LSTM),
+ * ignored), 1 = single-layer LSTM (params: w_ih w_hh b_ih b_hh Whead bhead).  Buffers (env,T,.) : obs [N][T][D], act i32, rew, val, logp, done f32
+ * [N][T], flags u8 [N][T].  cur_obs [N][D] in/out (state to act on), h,c [N][H] in/out (LSTM).  D = 6 + cfg->trend_k observation
+ * features: the LSTM policy takes trend_k 0, 1 or 2 with w_ih [4H][D] (so w_hh starts at 4H D); the MLP policy has 6 inputs and
+ * refuses trend_k != 0.
  * keep [N][T] out (LSTM: 0 where the state restarted), last_val [N] out or NULL (V of the state
  * after the last step, for UAV_GAE_STANDARD).  forced_act i32 [N][T] / noise f64 [N][T][2] are
  * NULL outside parity tests.  stash [N][T][6H] + y_out [N][T][H] (both or neither): the BPTT stash of
- * uav_lstm_fwd for exactly this rollout, so the first PPO epoch (same parameters) skips its forward.
+ * uav_lstm_fwd for exactly this rollout, so the first PPO epoch (same parameters) skips its forward; with trend_k != 0 that
+ * includes the stash's h_prev slot [.., 5H:6H] (h entering step t after the restart mask), which trend_k = 0 leaves alone.
  * info (or NULL) f32 [N][T][10]: the five reward parts of environment.py:161-167 (concentration, explore,
  * move, tke, boundary), obs[2] of the step, agent_pos (x, y) after the move -- what train_ppo2.0.py:166-183,203
  * accumulates / logs per episode -- and source_pos (x, y) of the episode the step belongs to (gaussian_params mu_x / mu_y,
@@ -472,12 +476,13 @@ int uav_rollout(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg
  * active[n] = 0 are never stepped.  State (env blob, cur_obs, h, c, active) carries across calls: k calls of steps / k steps
  * give what one call of `steps` gives.
  * policy_kind 0 = the reference's MLP 6-256-128 (params as uav_mlp_fwd; h, c NULL, `hidden` ignored), 1 = single-layer LSTM
- * (params as uav_rollout), hidden 64 or 128.  cur_obs f32 [N][6], h, c f32 [N][hidden], active u8 [N]: in/out.
- * Records: act i32 [N][steps], obs f32 [N][steps][6] (the observation the step returned -- the terminal one when done),
+ * (params as uav_rollout, w_ih [4H][D]), hidden 64 or 128.  cur_obs f32 [N][D], h, c f32 [N][hidden], active u8 [N]: in/out;
+ * D = 6 + cfg->trend_k, trend_k 0, 1 or 2 for the LSTM and 0 for the MLP.
+ * Records: act i32 [N][steps], obs f32 [N][steps][D] (the observation the step returned -- the terminal one when done),
  * pos f32 [N][steps][2] (agent_pos after the move), flags u8 [N][steps] (bit0 done, bit1 reached, bit2 not stepped: then
  * act = -1, obs and pos 0).  nan_count (i32, device) += number of stepped env-steps with a NaN logit.
- * Refused (non-zero status, uav_last_error names the reason): a handle not in UAV_ARITH_FP16X3, trend_k != 0, hidden not 64
- * or 128. */
+ * Refused (non-zero status, uav_last_error names the reason): a handle not in UAV_ARITH_FP16X3, trend_k != 0 with the MLP
+ * policy (the fused MLP kernels take 6 features), hidden not 64 or 128, n_env * steps * D of 2^31 or more. */
 int uav_greedy_episodes(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg /*host*/, int policy_kind,
                         const float* params, int hidden, int steps, float* cur_obs, float* h, float* c, uint8_t* active,
                         const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags, int32_t* nan_count,
@@ -502,7 +507,7 @@ typedef struct uav_stop_rule {
  * The window carries across calls in stop_win f32 [N][window][2] and stop_cnt i32 [N] (in/out; zero stop_cnt starts an
  * episode): rows 0 .. stop_cnt[n]-1 are the env's last positions in time order, oldest first; stop_cnt saturates at window;
  * rows beyond stop_cnt[n], and the rows of an env that is not stepped, are left alone.  k calls of steps / k steps give what
- * one call gives, bit for bit, window buffers included.
+ * one call gives, bit for bit, window buffers included.  Buffer shapes as uav_greedy_episodes (D = 6 + cfg->trend_k features).
  * rule_val (or NULL) f32 [N][steps]: pos_std of every stepped step whose window is full, NaN otherwise (tests compare the
  * value itself; with NULL the std is only formed on steps whose concentration half holds).
  * Refused like uav_greedy_episodes, and: rule NULL, window outside 1 .. 16, stop_win or stop_cnt NULL. */

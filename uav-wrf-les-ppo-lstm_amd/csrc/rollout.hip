@@ -98,13 +98,20 @@ struct RolloutBufs {
 // (bit0 done, bit1 reached, bit2 not stepped: act -1, obs and pos 0).  GREEDY = false is the trainer's rollout, unchanged.
 // STOP (with GREEDY): evaluate_model.py's stop rule after every env step (stop_rule_core.h) -- the env lane keeps its window as
 // a ring in LDS, and a hit ends the episode as `done` does (flags bit3).  STOP = false compiles to the kernels as they were.
-template <int H, int NA, bool GREEDY = false, bool STOP = false>
+// TREND: the observation has od = 6 + P.trend_k features (od = 7 or 8 at run time, one instantiation for both).  The x rows
+// were 8 wide all along (K = 8 in two f32 k-steps), so only what fills them changes: w_ih is [4H][od], xbuf / cur_obs / the obs
+// record carry od features, and the parked transition keeps the whole 8-wide row -- the source position moves to the spare
+// slots 5, 6 of the logits block, the greedy agent_pos to slots 1, 2 of the first block, so trs does not grow.  With a stash
+// the kernel also fills the h_prev slot [.., 5H:6H] as uav_lstm_fwd does for I > 6 (uav_lstm_wgrad reads it there): the
+// unmasked h_t goes to row t + 1 with the rest of the stash, and keep_fixup zeroes that row where step t ended the episode
+// (the same lane, the same address: program order).  TREND = false compiles to the kernels as they were.
+template <int H, int NA, bool GREEDY = false, bool STOP = false, bool TREND = false>
 __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, EnvBlob blob, int N, int T,
                                                                         uint64_t iter, const float* __restrict__ params,
                                                                         RolloutBufs B) {
     using G = RGeom<H>;
     constexpr int NS = G::NS, RS = G::RS, PLANE = G::PLANE, W0 = G::W0, NW = G::NW;
-    constexpr int I = 6, NH = NA + 1;
+    constexpr int NH = NA + 1;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned short* hpl = reinterpret_cast<unsigned short*>(smem);          // [2 pieces][RMT][RS] h_t
     unsigned short* whp = hpl + 2 * PLANE;                                  // [2 pieces][16 heads][RS] head weights
@@ -135,6 +142,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
     EnvParams P = P_arg;
     env_params_refresh(P);
     env_tables_to_lds(P, env_tab, threadIdx.x, H * 4);
+    const int I = TREND ? 6 + P.trend_k : 6;   // observation features (TREND: 7 or 8, checked at launch)
 
     const float* w_ih = params;
     const float* w_hh = w_ih + 4 * H * I;
@@ -219,6 +227,8 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         c_reg[0] = cv.x; c_reg[1] = cv.y; c_reg[2] = cv.z; c_reg[3] = cv.w;
         const float h_in[4] = {hv.x, hv.y, hv.z, hv.w};
         put_h(h_in);
+        if constexpr (TREND && !GREEDY)                                      // h_prev of step 0: h comes in masked (keep[:, 0] = 1)
+            if (B.stash && live) *reinterpret_cast<float4*>(B.stash + (size_t)(n0 + j) * T * (6 * H) + 5 * H + uo) = hv;
     }
     bool ran = true;                           // GREEDY: the env came in active (else its state is never written back)
     if (is_env_wave && lane < RMT) {
@@ -226,7 +236,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         es_s[lane] = env_load(blob, n);
         for (int k = 0; k < NVIS; ++k) myvis[k] = blob.visited[(size_t)n * NVIS + k];
 #pragma unroll
-        for (int f = 0; f < 8; ++f) xbuf[lane * 8 + f] = f < 6 ? B.cur_obs[(size_t)n * 6 + f] : 0.f;
+        for (int f = 0; f < 8; ++f) xbuf[lane * 8 + f] = f < I ? B.cur_obs[(size_t)n * I + f] : 0.f;
         if constexpr (GREEDY) {
             ran = my_env < N && B.active[n] != 0;
             kbuf[lane] = ran ? 1.f : 0.f;
@@ -346,6 +356,8 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         if (st) {
             *reinterpret_cast<float4*>(sp + 3 * H) = float4{go[0], go[1], go[2], go[3]};
             *reinterpret_cast<float4*>(B.y + (size_t)row * H + uo) = float4{hh[0], hh[1], hh[2], hh[3]};
+            if constexpr (TREND)                                 // h_prev of step t + 1, unmasked (keep_fixup applies the mask)
+                if (t + 1 < T) *reinterpret_cast<float4*>(sp + 6 * H + 5 * H) = float4{hh[0], hh[1], hh[2], hh[3]};
         }
         if (!GREEDY && t == T - 1 && live)
             *reinterpret_cast<float4*>(B.h + (size_t)(n0 + j) * H + uo) = float4{hh[0], hh[1], hh[2], hh[3]};
@@ -357,6 +369,10 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
             for (int r = 0; r < 4; ++r) c_reg[r] = 0.f;
             bias_acc();
             if (t == T - 1 && live) *reinterpret_cast<float4*>(B.h + (size_t)(n0 + j) * H + uo) = float4{0.f, 0.f, 0.f, 0.f};
+            if constexpr (TREND)                                 // h_prev of step t + 1 after the restart mask
+                if (B.stash && t + 1 < T && live)
+                    *reinterpret_cast<float4*>(B.stash + ((size_t)(n0 + j) * T + t + 1) * (6 * H) + 5 * H + uo) =
+                        float4{0.f, 0.f, 0.f, 0.f};
         }
     };
 
@@ -369,17 +385,29 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         if (GREEDY && lane < RMT && n0 + lane < N) {                   // [action, -, -, -, -, flags, -, -] | [obs 6, agent_pos 2]
             const size_t row = (size_t)(n0 + lane) * T + t;
             const float* to = trs + RMT * 8 + lane * 8;
+            if constexpr (TREND) {                                      // [action, agent_pos 2, -, -, flags, -, -] | [obs 8]
 #pragma unroll
-            for (int f = 0; f < 6; ++f) B.obs[row * 6 + f] = to[f];
-            B.pos[row * 2] = to[6];
-            B.pos[row * 2 + 1] = to[7];
+                for (int f = 0; f < 8; ++f) if (f < I) B.obs[row * I + f] = to[f];
+                B.pos[row * 2] = trs[lane * 8 + 1];
+                B.pos[row * 2 + 1] = trs[lane * 8 + 2];
+            } else {
+#pragma unroll
+                for (int f = 0; f < 6; ++f) B.obs[row * 6 + f] = to[f];
+                B.pos[row * 2] = to[6];
+                B.pos[row * 2 + 1] = to[7];
+            }
             B.act[row] = __float_as_int(trs[lane * 8]);
             B.flags[row] = (uint8_t)__float_as_int(trs[lane * 8 + 5]);
         } else if (!GREEDY && lane < RMT && n0 + lane < N) {
             const size_t row = (size_t)(n0 + lane) * T + t;
             const float* tq = trs + lane * 8;
+            if constexpr (TREND) {                                      // ... | [obs 8] | [info 8] | [logits 5, source x, y]
 #pragma unroll
-            for (int f = 0; f < 6; ++f) B.obs[row * 6 + f] = trs[RMT * 8 + lane * 8 + f];
+                for (int f = 0; f < 8; ++f) if (f < I) B.obs[row * I + f] = trs[RMT * 8 + lane * 8 + f];
+            } else {
+#pragma unroll
+                for (int f = 0; f < 6; ++f) B.obs[row * 6 + f] = trs[RMT * 8 + lane * 8 + f];
+            }
             B.act[row] = __float_as_int(tq[0]);
             B.rew[row] = tq[1];
             B.val[row] = tq[2];
@@ -395,8 +423,9 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
             if (B.info) {
 #pragma unroll
                 for (int f = 0; f < 8; ++f) B.info[row * 10 + f] = trs[2 * RMT * 8 + lane * 8 + f];
-                B.info[row * 10 + 8] = trs[RMT * 8 + lane * 8 + 6];
-                B.info[row * 10 + 9] = trs[RMT * 8 + lane * 8 + 7];
+                constexpr int SRC = TREND ? 3 * RMT * 8 + 5 : RMT * 8 + 6;
+                B.info[row * 10 + 8] = trs[SRC + lane * 8];
+                B.info[row * 10 + 9] = trs[SRC + lane * 8 + 1];
             }
         }
     };
@@ -506,10 +535,20 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                         }
                         tr[0] = __int_as_float(a_sel);
                         tr[5] = __int_as_float((so.done ? 1 : 0) | (so.reached ? 2 : 0) | (hit ? 8 : 0));
+                        if constexpr (TREND) {
 #pragma unroll
-                        for (int f = 0; f < 6; ++f) { to[f] = so.obs[f]; xbuf[lane * 8 + f] = so.obs[f]; }
-                        to[6] = es.px;
-                        to[7] = es.py;
+                            for (int f = 0; f < 8; ++f) {
+                                const float v = f < I ? so.obs[f] : 0.f;
+                                to[f] = v; xbuf[lane * 8 + f] = v;
+                            }
+                            tr[1] = es.px;
+                            tr[2] = es.py;
+                        } else {
+#pragma unroll
+                            for (int f = 0; f < 6; ++f) { to[f] = so.obs[f]; xbuf[lane * 8 + f] = so.obs[f]; }
+                            to[6] = es.px;
+                            to[7] = es.py;
+                        }
                         es_s[lane] = es;
                         if (so.done || hit) kbuf[lane] = 0.f;
                     } else {
@@ -517,6 +556,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                         tr[5] = __int_as_float(4);
 #pragma unroll
                         for (int f = 0; f < 8; ++f) to[f] = 0.f;
+                        if constexpr (TREND) tr[1] = tr[2] = 0.f;
                         if constexpr (STOP)
                             if (B.rule_val && env_lane) B.rule_val[(size_t)my_env * T + t] = __builtin_nanf("");
                     }
@@ -582,20 +622,22 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                         trs[2 * RMT * 8 + lane * 8 + 6] = es.px;          // agent_pos after the move (before any auto-reset)
                         trs[2 * RMT * 8 + lane * 8 + 7] = es.py;
                     }
-                    float ob_old[6];
+                    constexpr int OW = TREND ? 8 : 6;                     // TREND: the whole x row, source beside the logits
+                    constexpr int SRC = TREND ? 3 * RMT * 8 + 5 : RMT * 8 + 6;
+                    float ob_old[OW];
 #pragma unroll
-                    for (int f = 0; f < 6; ++f) ob_old[f] = xbuf[lane * 8 + f];
+                    for (int f = 0; f < OW; ++f) ob_old[f] = xbuf[lane * 8 + f];
 #pragma unroll
-                    for (int f = 0; f < 6; ++f) trs[RMT * 8 + lane * 8 + f] = ob_old[f];
-                    trs[RMT * 8 + lane * 8 + 6] = (float)es.sx;           // source of the episode this step belongs to
-                    trs[RMT * 8 + lane * 8 + 7] = (float)es.sy;
+                    for (int f = 0; f < OW; ++f) trs[RMT * 8 + lane * 8 + f] = ob_old[f];
+                    trs[SRC + lane * 8] = (float)es.sx;                   // source of the episode this step belongs to
+                    trs[SRC + lane * 8 + 1] = (float)es.sy;
                     if (so.done) {
                         es.episode += 1;
                         env_begin_episode(P, eg, es, myvis);
                         env_obs(P, es, myvis, so.obs);
                     }
 #pragma unroll
-                    for (int f = 0; f < 6; ++f) xbuf[lane * 8 + f] = so.obs[f];
+                    for (int f = 0; f < OW; ++f) xbuf[lane * 8 + f] = f < I ? so.obs[f] : 0.f;
                     es_s[lane] = es;
                     kbuf[lane] = so.done ? 0.f : 1.f;
                 }
@@ -617,18 +659,18 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         env_store(blob, my_env, es_s[lane]);
         for (int k = 0; k < NVIS; ++k) blob.visited[(size_t)my_env * NVIS + k] = myvis[k];
 #pragma unroll
-        for (int f = 0; f < 6; ++f) B.cur_obs[(size_t)my_env * 6 + f] = xbuf[lane * 8 + f];
+        for (int f = 0; f < (TREND ? 8 : 6); ++f) if (f < I) B.cur_obs[(size_t)my_env * I + f] = xbuf[lane * 8 + f];
         if constexpr (STOP)
             B.stop_cnt[my_env] = stop_ring_store(ring, sr, B.stop_win + (size_t)my_env * B.rule.window * 2, B.rule.window);
     }
 }
 
-template <int H, bool GREEDY = false, bool STOP = false>
+template <int H, bool GREEDY = false, bool STOP = false, bool TREND = false>
 static int launch_rollout(const EnvParams& P, EnvBlob blob, int N, int T, uint64_t iter, const float* params,
                           const RolloutBufs& B, hipStream_t st) {
     const dim3 grid((N + RMT - 1) / RMT), block(H * 4);
-    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_lstm_kernel<H, 5, GREEDY, STOP>), (int)RGeom<H>::LDS));
-    hipLaunchKernelGGL((rollout_lstm_kernel<H, 5, GREEDY, STOP>), grid, block, RGeom<H>::LDS, st, P, blob, N, T, iter, params, B);
+    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_lstm_kernel<H, 5, GREEDY, STOP, TREND>), (int)RGeom<H>::LDS));
+    hipLaunchKernelGGL((rollout_lstm_kernel<H, 5, GREEDY, STOP, TREND>), grid, block, RGeom<H>::LDS, st, P, blob, N, T, iter, params, B);
     UAV_LAUNCH_CHECK();
     return 0;
 }
@@ -774,9 +816,12 @@ extern "C" int uav_rollout(uav_ctx* ctx, void* env_state, int n_env, const uav_e
     UAV_REQUIRE(!stash || (int64_t)n_env * horizon * 6 * hidden < (1ll << 32), "uav_rollout: stash rows exceed 32-bit offsets");
     RolloutBufs B{cur_obs, h, c, obs, act, rew, val, logp, done, flags, keep, last_val, forced_act, noise, nan_count, info, heads, stash, y_out};
     EnvBlob blob = env_blob_view(env_state, n_env);
+    const bool trend = P.trend_k != 0;       // 6 + trend_k features in cur_obs, obs and w_ih: the TREND form of the kernel
     switch (hidden) {
-        case 64: return launch_rollout<64>(P, blob, n_env, horizon, iter, params, B, as_stream(stream));
-        case 128: return launch_rollout<128>(P, blob, n_env, horizon, iter, params, B, as_stream(stream));
+        case 64: return trend ? launch_rollout<64, false, false, true>(P, blob, n_env, horizon, iter, params, B, as_stream(stream))
+                              : launch_rollout<64>(P, blob, n_env, horizon, iter, params, B, as_stream(stream));
+        case 128: return trend ? launch_rollout<128, false, false, true>(P, blob, n_env, horizon, iter, params, B, as_stream(stream))
+                               : launch_rollout<128>(P, blob, n_env, horizon, iter, params, B, as_stream(stream));
     }
     UAV_REQUIRE(false, "uav_rollout: hidden=%d unsupported (64, 128)", hidden);
 }
@@ -802,8 +847,9 @@ static int greedy_episodes_impl(const char* who, uav_ctx* ctx, void* env_state, 
     EnvParams P;
     int rc = env_params_from_cfg(ctx, cfg, n_env, P);
     if (rc) return rc;
-    UAV_REQUIRE(P.trend_k == 0, "%s: trend_k=%d unsupported (the fused kernels take 6 observation features)", who, P.trend_k);
-    UAV_REQUIRE((int64_t)n_env * steps * 6 < (1ll << 31), "%s: n_env * steps too large", who);
+    UAV_REQUIRE(policy_kind == 1 || P.trend_k == 0, "%s: trend_k=%d unsupported (the fused MLP kernels take 6 observation features)",
+                who, P.trend_k);
+    UAV_REQUIRE((int64_t)n_env * steps * (6 + P.trend_k) < (1ll << 31), "%s: n_env * steps too large", who);
     if (policy_kind == 0)
         return rule ? launch_greedy_mlp_stop(P, env_state, n_env, params, steps, cur_obs, active, noise, act, obs, pos, flags,
                                              nan_count, R, stop_win, stop_cnt, rule_val, st)
@@ -812,12 +858,16 @@ static int greedy_episodes_impl(const char* who, uav_ctx* ctx, void* env_state, 
     RolloutBufs B{cur_obs, h, c, obs, act, nullptr, nullptr, nullptr, nullptr, flags, nullptr, nullptr, nullptr, noise, nan_count,
                   nullptr, nullptr, nullptr, nullptr, active, pos, stop_win, stop_cnt, rule_val, R};
     EnvBlob blob = env_blob_view(env_state, n_env);
+#define LAUNCH_G(H_)                                                                                      \
+    (P.trend_k ? (rule ? launch_rollout<H_, true, true, true>(P, blob, n_env, steps, 0, params, B, st)        \
+                       : launch_rollout<H_, true, false, true>(P, blob, n_env, steps, 0, params, B, st))      \
+               : (rule ? launch_rollout<H_, true, true>(P, blob, n_env, steps, 0, params, B, st)              \
+                       : launch_rollout<H_, true>(P, blob, n_env, steps, 0, params, B, st)))
     switch (hidden) {
-        case 64: return rule ? launch_rollout<64, true, true>(P, blob, n_env, steps, 0, params, B, st)
-                             : launch_rollout<64, true>(P, blob, n_env, steps, 0, params, B, st);
-        case 128: return rule ? launch_rollout<128, true, true>(P, blob, n_env, steps, 0, params, B, st)
-                              : launch_rollout<128, true>(P, blob, n_env, steps, 0, params, B, st);
+        case 64: return LAUNCH_G(64);
+        case 128: return LAUNCH_G(128);
     }
+#undef LAUNCH_G
     UAV_REQUIRE(false, "%s: hidden=%d unsupported by the fused kernel (64, 128)", who, hidden);
 }
 

@@ -122,7 +122,7 @@ class ModelEvaluator:
         t0 = 0
         while t0 < limit:
             k = min(chunk, limit - t0)
-            recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, 6, dtype=F32, device=dev),
+            recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, env.obs_dim, dtype=F32, device=dev),
                     "pos": torch.empty(N, k, 2, dtype=F32, device=dev), "flags": torch.empty(N, k, dtype=torch.uint8, device=dev)}
             rv = torch.empty(N, k, dtype=F32, device=dev) if want is not None else None
             nz = None if noise is None else noise[t0:t0 + k].transpose(0, 1).contiguous()

@@ -213,12 +213,16 @@ def fused_refusal(policy, env):
     mode = ops.get_lstm_arith(env.device)
     if mode != "fp16x3":
         return f"the handle's arithmetic is {mode}; the fused greedy kernels exist in fp16x3 only"
-    if env.trend_k:
-        return f"trend_k = {env.trend_k}; the fused greedy kernels take 6 observation features"
+    trend = f" (the env has trend_k = {env.trend_k})" if env.trend_k else ""      # every refusal on a trend env names trend_k
     if kind == "lstm":
-        if core.num_layers != 1 or core.hidden not in (64, 128) or core.obs_dim != 6 or core.n_act != 5:
+        if core.num_layers != 1 or core.hidden not in (64, 128) or core.n_act != 5:
             return (f"LSTM {core.num_layers} layer(s), hidden {core.hidden}, obs_dim {core.obs_dim}, {core.n_act} actions; "
-                    f"the fused kernel covers one layer of hidden 64 / 128, obs_dim 6, 5 actions")
+                    f"the fused kernel covers one layer of hidden 64 / 128, obs_dim 6 + trend_k, 5 actions{trend}")
+        if core.obs_dim != 6 + env.trend_k:
+            return (f"the policy's obs_dim is {core.obs_dim}, the env's observations have {6 + env.trend_k} features "
+                    f"(6 + trend_k, trend_k = {env.trend_k})")
+    elif env.trend_k:
+        return f"trend_k = {env.trend_k}; the fused MLP greedy kernels take 6 observation features"
     elif (core.in_dim, core.h1, core.h2, core.n_act) != _MLP_SHAPE:
         return f"MLP {core.in_dim}-{core.h1}-{core.h2}-{core.n_act}; the fused kernel covers 6-256-128-5 only"
     # NaN parameters are not out of range: they reach the kernel and come back as nan_count ("NaN in probs")
@@ -371,7 +375,7 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
     t0 = 0
     while t0 < limit:
         k = min(chunk, limit - t0)
-        recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, 6, dtype=F32, device=dev),
+        recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, env.obs_dim, dtype=F32, device=dev),
                 "pos": torch.empty(N, k, 2, dtype=F32, device=dev), "flags": torch.empty(N, k, dtype=torch.uint8, device=dev)}
         nz = None if noise is None else noise[t0:t0 + k].transpose(0, 1).contiguous()
         ops.greedy_episodes(env.state, N, env.cfg(), core.flat, H, k, cur_obs, h, c, kernel_active, recs, noise=nz,

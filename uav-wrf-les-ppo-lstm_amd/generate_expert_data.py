@@ -65,7 +65,7 @@ def greedy_records(policy, env, max_steps=None, chunk=250):
         t0 = 0
         while t0 < limit:
             k = min(chunk, limit - t0)
-            recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, 6, dtype=torch.float32, device=dev),
+            recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, env.obs_dim, dtype=torch.float32, device=dev),
                     "pos": torch.empty(N, k, 2, dtype=torch.float32, device=dev), "flags": torch.empty(N, k, dtype=torch.uint8, device=dev)}
             ops.greedy_episodes(env.state, N, env.cfg(), core.flat, H, k, env.obs, h, c, active, recs, nan_count=nan_count)
             obs_c.append(recs["obs"].cpu().numpy()), act_c.append(recs["act"].cpu().numpy()), flags_c.append(recs["flags"].cpu().numpy())

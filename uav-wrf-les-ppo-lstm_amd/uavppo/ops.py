@@ -832,13 +832,14 @@ def colsum(x, out=None):
 # ----------------------------------------------------------------------------- R1
 def rollout_lstm(env_state, n_env, cfg, params, hidden, horizon, it, cur_obs, h, c, bufs, last_val=None,
                  forced_act=None, noise=None, nan_count=None, stash=None, y=None, info=None, heads=None):
-    """Fused persistent rollout (csrc/rollout.hip).  bufs: dict obs[N,T,6] act rew val logp done flags keep."""
-    N, T = n_env, horizon
+    """Fused persistent rollout (csrc/rollout.hip).  bufs: dict obs[N,T,D] act rew val logp done flags keep, with
+    D = 6 + cfg.trend_k observation features (cur_obs [N,D]; params laid out for an input width of D)."""
+    N, T, D = n_env, horizon, 6 + cfg.trend_k
     _t = KERNEL_TIMER.bracket("rollout")
     check(lib().uav_rollout(_h(cur_obs), _p(env_state, U8, name="env state"), N, C.byref(cfg), 1,
                             _p(params, F32, name="params"), int(hidden), T, int(it),
-                            _p(cur_obs, F32, (N, 6), "cur_obs"), _p(h, F32, (N, hidden), "h"), _p(c, F32, (N, hidden), "c"),
-                            _p(bufs["obs"], F32, (N, T, 6), "obs"), _p(bufs["act"], I32, (N, T), "act"),
+                            _p(cur_obs, F32, (N, D), "cur_obs"), _p(h, F32, (N, hidden), "h"), _p(c, F32, (N, hidden), "c"),
+                            _p(bufs["obs"], F32, (N, T, D), "obs"), _p(bufs["act"], I32, (N, T), "act"),
                             _p(bufs["rew"], F32, (N, T), "rew"), _p(bufs["val"], F32, (N, T), "val"),
                             _p(bufs["logp"], F32, (N, T), "logp"), _p(bufs["done"], F32, (N, T), "done"),
                             _p(bufs["flags"], U8, (N, T), "flags"), _p(bufs["keep"], F32, (N, T), "keep"),
@@ -872,19 +873,20 @@ def rollout_mlp(env_state, n_env, cfg, params, horizon, it, cur_obs, bufs, last_
 def greedy_episodes(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise=None, nan_count=None):
     """`steps` steps of greedy evaluation episodes on the fused rollout kernels (uav_greedy_episodes): argmax action, no
     auto-reset, ended / inactive envs frozen.  hidden = 0 (h, c None): the reference's MLP; 64 / 128: the single-layer LSTM.
-    cur_obs [N,6], h, c [N,H], active u8 [N] are in/out; recs: dict act i32 [N,steps], obs [N,steps,6], pos [N,steps,2],
-    flags u8 [N,steps] (bit0 done, bit1 reached, bit2 not stepped); noise f64 [N,steps,2] or None."""
-    N, T = n_env, steps
+    cur_obs [N,D], h, c [N,H], active u8 [N] are in/out; recs: dict act i32 [N,steps], obs [N,steps,D], pos [N,steps,2],
+    flags u8 [N,steps] (bit0 done, bit1 reached, bit2 not stepped); noise f64 [N,steps,2] or None.  D = 6 + cfg.trend_k
+    (the LSTM kernels; the MLP kernels take trend_k = 0 only)."""
+    N, T, D = n_env, steps, 6 + cfg.trend_k
     kind = 0 if hidden == 0 else 1
     if nan_count is None:
         nan_count = torch.zeros(1, dtype=I32, device=cur_obs.device)
     _t = KERNEL_TIMER.bracket("greedy")
     check(lib().uav_greedy_episodes(_h(cur_obs), _p(env_state, U8, name="env state"), N, C.byref(cfg), kind,
-                                    _p(params, F32, name="params"), int(hidden), T, _p(cur_obs, F32, (N, 6), "cur_obs"),
+                                    _p(params, F32, name="params"), int(hidden), T, _p(cur_obs, F32, (N, D), "cur_obs"),
                                     _p(h, F32, (N, hidden), "h") if kind else None,
                                     _p(c, F32, (N, hidden), "c") if kind else None,
                                     _p(active, U8, (N,), "active"), _p(noise, F64, (N, T, 2), "noise"),
-                                    _p(recs["act"], I32, (N, T), "act"), _p(recs["obs"], F32, (N, T, 6), "obs"),
+                                    _p(recs["act"], I32, (N, T), "act"), _p(recs["obs"], F32, (N, T, D), "obs"),
                                     _p(recs["pos"], F32, (N, T, 2), "pos"), _p(recs["flags"], U8, (N, T), "flags"),
                                     _p(nan_count, I32, (1,), "nan_count"), _stream()), "uav_greedy_episodes")
     if _t is not None:
@@ -909,17 +911,17 @@ def greedy_episodes_stop(env_state, n_env, cfg, params, hidden, steps, cur_obs, 
     stop_win f32 [N, window, 2] (the env's last positions, oldest first) and stop_cnt i32 [N] (valid rows) are in/out and
     carry the window across calls (zeros start an episode); rule_val: optional f32 [N, steps], pos_std of every stepped step
     with a full window, NaN otherwise."""
-    N, T, W = n_env, steps, int(rule.window)
+    N, T, W, D = n_env, steps, int(rule.window), 6 + cfg.trend_k
     kind = 0 if hidden == 0 else 1
     if nan_count is None:
         nan_count = torch.zeros(1, dtype=I32, device=cur_obs.device)
     _t = KERNEL_TIMER.bracket("greedy")
     check(lib().uav_greedy_episodes_stop(_h(cur_obs), _p(env_state, U8, name="env state"), N, C.byref(cfg), kind,
-                                         _p(params, F32, name="params"), int(hidden), T, _p(cur_obs, F32, (N, 6), "cur_obs"),
+                                         _p(params, F32, name="params"), int(hidden), T, _p(cur_obs, F32, (N, D), "cur_obs"),
                                          _p(h, F32, (N, hidden), "h") if kind else None,
                                          _p(c, F32, (N, hidden), "c") if kind else None,
                                          _p(active, U8, (N,), "active"), _p(noise, F64, (N, T, 2), "noise"),
-                                         _p(recs["act"], I32, (N, T), "act"), _p(recs["obs"], F32, (N, T, 6), "obs"),
+                                         _p(recs["act"], I32, (N, T), "act"), _p(recs["obs"], F32, (N, T, D), "obs"),
                                          _p(recs["pos"], F32, (N, T, 2), "pos"), _p(recs["flags"], U8, (N, T), "flags"),
                                          _p(nan_count, I32, (1,), "nan_count"), C.byref(rule),
                                          _p(stop_win, F32, (N, W, 2), "stop_win"), _p(stop_cnt, I32, (N,), "stop_cnt"),

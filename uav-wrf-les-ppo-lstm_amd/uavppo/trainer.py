@@ -404,7 +404,7 @@ class VecPPOTrainer:
             ops.set_lstm_arith(self.arith, self.device)
             self._buffers_own = True
         wide = self._guarded() and self.arith != "fp16x3"      # uav_rollout exists in the fp16-split form only
-        if self.kind == "lstm" and (self.policy.num_layers != 1 or self.policy.hidden not in (64, 128) or self.trend_k or wide):
+        if self.kind == "lstm" and (self.policy.num_layers != 1 or self.policy.hidden not in (64, 128) or wide):
             self._state0.copy_(self._state)
             self._collect_stepwise_lstm(forced_act, noise)
         elif self.kind == "lstm":

@@ -153,21 +153,26 @@ int uav_store_transition(uav_ctx* ctx, int n, int T, int t, float* keep, const f
 
 /* ---- U3: global-norm clip + Adam on one flat f32 buffer (train_ppo2.0.py:87-88,114;
  * torch clip_grad_norm_ / optim.Adam formulas).  `step` is the 1-based optimiser step.
- * gnorm_out: f32[1] device (pre-clip global L2 norm) or NULL.  pmax_out: f32[1] device or NULL: max |param| AFTER the
- * step (the kernel touches every parameter anyway) -- the weight-range probe of uav_set_lstm_arith. */
+ * max_norm <= 0 switches the clipping off (the gradient is used as it is; the norm is still computed and reported).
+ * gnorm_out: f32[1] device (pre-clip global L2 norm) or NULL; a NaN anywhere in the gradient makes it NaN (and, with clipping
+ * on, every parameter and both moments) -- the norm is the host's signal.  pmax_out: f32[1] device or NULL: max |param| AFTER
+ * the step (the kernel touches every parameter anyway) -- the weight-range probe of uav_set_lstm_arith. */
 int uav_clip_adam(uav_ctx* ctx, float* param, const float* grad, float* exp_avg,
                   float* exp_avg_sq, int64_t n, int64_t step, float lr, float beta1, float beta2,
                   float eps, float max_norm, float* gnorm_out, float* pmax_out, uav_stream stream);
-/* AdamW (torch.optim.AdamW, PPOV2.0/train_lstm.py:67): as uav_clip_adam with the decoupled decay param *= 1 - lr*weight_decay. */
+/* AdamW (torch.optim.AdamW, PPOV2.0/train_lstm.py:67): as uav_clip_adam (max_norm <= 0 and NaN included) with the decoupled
+ * decay param *= 1 - lr*weight_decay; weight_decay = 0 gives uav_clip_adam's bits. */
 int uav_clip_adamw(uav_ctx* ctx, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                    int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm,
                    float* gnorm_out, uav_stream stream);
 /* nn.SmoothL1Loss(beta), reduction mean (train_lstm.py:66), forward + backward: loss_mean f64[1] device,
- * dpred [n] = d(loss)/d(pred). */
+ * dpred [n] = d(loss)/d(pred).  |pred - target| == beta takes the linear branch (gradient +-1/n), as in torch.  A NaN element
+ * makes the loss NaN and its own dpred NaN; the other elements' gradients are unaffected. */
 int uav_smooth_l1(uav_ctx* ctx, const float* pred, const float* target, int64_t n, float beta, double* loss_mean,
                   float* dpred, uav_stream stream);
 /* nn.MSELoss(peak, y_peak) + nn.BCELoss(sigmoid(stop_logit), y_stop), both means (PPOV2.1/train_lstm.py:110-113), forward +
- * backward: out, target, dout f32 [n][2] = (peak, stop_logit) / (y_peak, y_stop) / d(loss)/d(out); loss_mean f64[1]. */
+ * backward: out, target, dout f32 [n][2] = (peak, stop_logit) / (y_peak, y_stop) / d(loss)/d(out); loss_mean f64[1].  A NaN
+ * in either column makes the loss and that element's gradient NaN (the clamp of the logs at -100 does not swallow it). */
 int uav_mse_bce(uav_ctx* ctx, const float* out, const float* target, int64_t n, double* loss_mean, float* dout,
                 uav_stream stream);
 

@@ -174,17 +174,29 @@ def test_peak_stop_three_steps_match_the_reference_golden(tl):
 def test_mse_bce_matches_torch_including_saturated_logits():
     from uavppo import ops
     torch.manual_seed(3)
-    out = torch.randn(777, 2, device=DEV) * 3
-    out[:4, 1] = torch.tensor([60.0, -60.0, 120.0, -120.0], device=DEV)          # sigmoid saturates: BCELoss clamps log at -100
-    tgt = torch.stack([torch.randn(777, device=DEV), (torch.rand(777, device=DEV) > 0.5).float()], 1)
-    loss, dout = ops.mse_bce(out, tgt)
-    o = out.detach().cpu().double().requires_grad_(True)
-    want = torch.nn.functional.mse_loss(o[:, 0], tgt[:, 0].cpu().double()) + \
-        torch.nn.functional.binary_cross_entropy(torch.sigmoid(o[:, 1]).float().double(), tgt[:, 1].cpu().double())
-    assert np.isclose(float(loss.item()), float(want), rtol=1e-5)
-    gz = torch.autograd.grad(torch.nn.functional.mse_loss(o[:, 0], tgt[:, 0].cpu().double()) +
-                             torch.nn.functional.binary_cross_entropy_with_logits(o[:, 1], tgt[:, 1].cpu().double()), o)[0]
-    assert torch.allclose(dout.cpu().double()[4:], gz[4:], rtol=1e-4, atol=1e-8)
+    for n in (777, 1, 256, 257):                 # one block of 256 threads: a single element, a full pass, one element into the second
+        sat = 4 if n >= 4 else 0
+        out = torch.randn(n, 2, device=DEV) * 3
+        out[:sat, 1] = torch.tensor([60.0, -60.0, 120.0, -120.0], device=DEV)[:sat]      # sigmoid saturates: BCELoss clamps log at -100
+        tgt = torch.stack([torch.randn(n, device=DEV), (torch.rand(n, device=DEV) > 0.5).float()], 1)
+        loss, dout = ops.mse_bce(out, tgt)
+        o = out.detach().cpu().double().requires_grad_(True)
+        want = torch.nn.functional.mse_loss(o[:, 0], tgt[:, 0].cpu().double()) + \
+            torch.nn.functional.binary_cross_entropy(torch.sigmoid(o[:, 1]).float().double(), tgt[:, 1].cpu().double())
+        assert np.isclose(float(loss.item()), float(want), rtol=1e-5), n
+        gz = torch.autograd.grad(torch.nn.functional.mse_loss(o[:, 0], tgt[:, 0].cpu().double()) +
+                                 torch.nn.functional.binary_cross_entropy_with_logits(o[:, 1], tgt[:, 1].cpu().double()), o)[0]
+        assert torch.allclose(dout.cpu().double()[sat:], gz[sat:], rtol=1e-4, atol=1e-8), n
+    # a NaN in either column reaches the loss and that element's gradient (nn.BCELoss refuses a NaN probability outright;
+    # a clamp that swallowed it would leave the loss finite); the other gradients keep their bits
+    for col in (0, 1):
+        bad = out.clone()
+        bad[n - 1, col] = float("nan")
+        loss2, dout2 = ops.mse_bce(bad, tgt)
+        assert torch.isnan(loss2).all() and torch.isnan(dout2[n - 1, col])
+        keep = torch.ones(n, 2, dtype=torch.bool, device=DEV)
+        keep[n - 1, col] = False
+        assert torch.equal(dout2[keep], dout[keep])
 
 
 def test_train_peak_and_stop_learns_the_stop_label(tl, tmp_path):

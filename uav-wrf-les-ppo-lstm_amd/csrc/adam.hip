@@ -127,7 +127,8 @@ extern "C" int uav_clip_adamw(uav_ctx* ctx, float* param, const float* grad, flo
 }
 
 // SmoothL1Loss(beta), reduction = mean (train_lstm.py:66): loss_sum[0] += sum_i l(pred_i - target_i) (f64, one block, fixed
-// order), dpred_i = dl/dpred_i / n.  |d| < beta: 0.5 d^2 / beta, else |d| - 0.5 beta.
+// order), dpred_i = dl/dpred_i / n.  |d| < beta: 0.5 d^2 / beta, else |d| - 0.5 beta.  A NaN d fails `a < beta`: its loss
+// term is NaN and so is its dpred (the sign of a NaN is the NaN itself), as in torch.
 __global__ __launch_bounds__(256) void smooth_l1_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                         int64_t n, float beta, double* __restrict__ loss_mean,
                                                         float* __restrict__ dpred) {
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(256) void smooth_l1_kernel(const float* __restrict_
     for (int64_t i = threadIdx.x; i < n; i += 256) {
         const float d = pred[i] - target[i], a = fabsf(d);
         if (a < beta) { s += 0.5 * (double)d * d / beta; dpred[i] = d / beta * inv_n; }
-        else { s += (double)a - 0.5 * beta; dpred[i] = (d > 0.f ? 1.f : -1.f) * inv_n; }
+        else { s += (double)a - 0.5 * beta; dpred[i] = (d > 0.f ? 1.f : d < 0.f ? -1.f : d) * inv_n; }
     }
     const double r = block256_sum(s, sm);
     if (threadIdx.x == 0) loss_mean[0] = r / (double)n;
@@ -162,7 +163,8 @@ __global__ __launch_bounds__(256) void mse_bce_kernel(const float* __restrict__ 
         const float d = out[2 * i] - target[2 * i];
         const float z = out[2 * i + 1], yb = target[2 * i + 1];
         const float p = 1.0f / (1.0f + expf(-z));
-        const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(logf(1.0f - p), -100.f);
+        const float lgp = logf(p), lgq = logf(1.0f - p);
+        const float lp = lgp < -100.f ? -100.f : lgp, lq = lgq < -100.f ? -100.f : lgq;      // not fmaxf, which drops a NaN: a NaN logit must reach the loss
         s += (double)d * d - ((double)yb * lp + (1.0 - (double)yb) * lq);
         dout[2 * i] = 2.0f * d * inv_n;
         dout[2 * i + 1] = (p - yb) * inv_n;

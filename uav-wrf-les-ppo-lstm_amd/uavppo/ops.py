@@ -780,14 +780,15 @@ def ln_relu(z, gamma, beta, want_stats=False):
     return (a, rstd) if want_stats else a
 
 
-def ln_relu_bwd(d, xhat, rstd, gamma, beta):
-    """d [rows, cols] = dL/da on entry, dL/dz on return (in place); returns (d, dgamma, dbeta)."""
+def ln_relu_bwd(d, xhat, rstd, gamma, beta, dgamma=None, dbeta=None):
+    """d [rows, cols] = dL/da on entry, dL/dz on return (in place); returns (d, dgamma, dbeta), both [cols], overwritten."""
     rows, cols = d.shape
-    dg = torch.empty(cols, dtype=F32, device=d.device)
-    db = torch.empty(cols, dtype=F32, device=d.device)
+    dg = torch.empty(cols, dtype=F32, device=d.device) if dgamma is None else dgamma
+    db = torch.empty(cols, dtype=F32, device=d.device) if dbeta is None else dbeta
     check(lib().uav_ln_relu_bwd(_h(d), _p(d, F32, (rows, cols), "d"), _p(xhat, F32, (rows, cols), "xhat"),
                                 _p(rstd, F32, (rows,), "rstd"), _p(gamma, F32, (cols,), "gamma"), _p(beta, F32, (cols,), "beta"),
-                                rows, cols, _p(dg, F32), _p(db, F32), _stream()), "uav_ln_relu_bwd")
+                                rows, cols, _p(dg, F32, (cols,), "dgamma"), _p(db, F32, (cols,), "dbeta"), _stream()),
+          "uav_ln_relu_bwd")
     return d, dg, db
 
 

@@ -531,6 +531,36 @@ int uav_stop_stability(uav_ctx* ctx, int n, const uav_stop_rule* rule /*host*/, 
                        int64_t obs2_stride, const uint8_t* active, float* stop_win, int32_t* stop_cnt, uint8_t* stop,
                        float* value, uav_stream stream);
 
+/* ---- The PPOV2.1 peak-and-stop rule (PPOV2.1/evaluate_with_lstm.py:11-27: PeakAndStopPredictor = LSTM(1 -> hidden,
+ * batch_first) -> h_n -> fc_peak, and fc_stop = Linear + Sigmoid; :69-77: once the trajectory holds `window` = 20
+ * concentrations, the last 20 divided by 100 go through the predictor and the episode stops when stop_prob > 0.8), for every
+ * sliding window of a chunk of records at once (csrc/peak_stop.hip).  Parameters are ONE flat f32 buffer in the reference
+ * module's state_dict order: lstm.weight_ih_l0 [4H][1], lstm.weight_hh_l0 [4H][H], lstm.bias_ih_l0, lstm.bias_hh_l0,
+ * fc_peak.weight [1][H], fc_peak.bias, fc_stop.0.weight [1][H], fc_stop.0.bias; gate order i, f, g, o as nn.LSTM --
+ * uav_peak_stop_param_count floats (4,546 for H = 32; 0, with a reason in uav_last_error, for a hidden the kernel refuses:
+ * only 32, the reference's value everywhere, is built).  Added without a change of UAV_ABI_VERSION (symbols only). */
+size_t uav_peak_stop_param_count(int hidden);
+
+/* series[e * row_stride + i * elem_stride] (strides in floats) is env e's LSTM input at chunk step i, i < steps: obs[2] of the
+ * greedy records obs [n][steps][D] read in place is series = obs + 2, row_stride = steps * D, elem_stride = D.  (The reference
+ * feeds f32((f64(obs[2]) * 100) / 100), which is obs[2] bit for bit: tests/test_peak_stop_host.py.)
+ * For step i of an env with active[e] != 0 (active NULL = all), the window is the last `window` values of (hist rows
+ * 0 .. hist_cnt[e]-1, then series[0 .. i]); it is valid when hist_cnt[e] + i + 1 >= window.  For a valid window the LSTM runs
+ * `window` steps from zero (h, c), and peak[e][i] / prob[e][i] (f32 [n][steps], either may be NULL) get fc_peak's output and the
+ * sigmoid of fc_stop's; invalid and inactive slots get NaN.  first_hit i32 [n]: the smallest i whose window is valid and has
+ * prob > prob_min (a NaN probability is no hit), -1 if there is none or the env is inactive.
+ * hist f32 [n][window-1] and hist_cnt i32 [n] are in/out (zero hist_cnt starts an episode): on exit an active env's hist holds
+ * its last window-1 inputs in time order, oldest first, and hist_cnt saturates at window-1; inactive envs keep both.
+ * Exact f32 arithmetic (v_mfma_f32_16x16x4_f32, gates through v_exp_f32 / v_rcp_f32), no atomics.  A window's peak / prob bits
+ * depend on its own inputs only: k calls of steps / k equal one call bit for bit, hist included (first_hit then differs by the
+ * chunk offset), and two calls on the same inputs give the same bits.  One hit byte per window goes through the handle's
+ * workspace (n * steps bytes must fit it).
+ * Refused with a reason before the GPU is touched: hidden != 32, window outside 1 .. 32, steps < 1, n < 1, NULL params, series,
+ * hist, hist_cnt or first_hit. */
+int uav_peak_stop_scan(uav_ctx* ctx, const float* params, int hidden, int window, const float* series, int64_t row_stride,
+                       int64_t elem_stride, int n, int steps, const uint8_t* active, float* hist, int32_t* hist_cnt,
+                       float prob_min, float* peak, float* prob, int32_t* first_hit, uav_stream stream);
+
 /* The tail of step t of a step-wise rollout as ONE launch (train_ppo2.0.py:165-198 after the recurrent layers): policy heads of
  * the top layer (heads[:, t] = y_t W_head^T + b_head, the sums of uav_gemm_f32's few-column kernel bit for bit; y = row t of a
  * [n][T][hidden] array given as the pointer to y[0][t] and its row stride y_stride floats, likewise heads / heads_stride),

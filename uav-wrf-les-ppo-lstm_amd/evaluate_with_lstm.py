@@ -11,6 +11,8 @@ evaluate() also takes a policy object (the vectorised trainer's LSTMActorCritic 
 Where uav_greedy_episodes covers it (single-layer LSTM h = 64 / 128 or the reference's MLP, 6 observation features, the
 fp16-split arithmetic, parameters inside that arithmetic's range) whole chunks of steps run in one launch each and the stop
 controllers are replayed over the chunk's records; everything else steps one launch sequence per time step.
+With peak_stop_device=True the PPOV2.1 rule is not replayed: uav_peak_stop_scan runs the predictor over every sliding window of
+a chunk's records in one scan and hands back the first hit per env.
 """
 from __future__ import annotations
 
@@ -132,6 +134,12 @@ class PeakAndStopPredictor:
     def eval(self):
         return self
 
+    def flat_params(self):
+        """The predictor as uav_peak_stop_scan's one flat f32 buffer: the state_dict's tensors in its order (layer 0 of the LSTM)."""
+        p = self.lstm.p
+        return torch.cat([p["weight_ih_l0"].reshape(-1), p["weight_hh_l0"].reshape(-1), p["bias_ih_l0"], p["bias_hh_l0"],
+                          self.heads_w[0], self.heads_b[0:1], self.heads_w[1], self.heads_b[1:2]]).contiguous()
+
     def __call__(self, x):
         if x.dim() == 2:
             x = x.unsqueeze(-1)
@@ -232,6 +240,33 @@ def fused_refusal(policy, env):
     return None
 
 
+def peak_stop_refusal(peak_stop, window):
+    """Why uav_peak_stop_scan cannot run `peak_stop` over windows of `window` steps (None when it can)."""
+    l = peak_stop.lstm
+    if l.hidden_size != 32 or l.num_layers != 1 or l.input_size != 1:
+        return (f"the predictor has hidden {l.hidden_size}, {l.num_layers} layer(s), input_dim {l.input_size}; uav_peak_stop_scan "
+                f"covers hidden 32, one layer, input_dim 1")
+    if not 1 <= int(window) <= 32:
+        return f"window_size_v21 = {window}; uav_peak_stop_scan takes windows of 1 .. 32 steps"
+    return None
+
+
+class _DevicePeakStop:
+    """The PPOV2.1 rule on uav_peak_stop_scan: the predictor's flat parameters and the envs' last window - 1 inputs."""
+
+    def __init__(self, peak_stop, window, N, device):
+        why = peak_stop_refusal(peak_stop, window)
+        if why is not None:
+            raise RuntimeError(f"evaluate(peak_stop_device=True): {why}")
+        self.params, self.hidden, self.window = peak_stop.flat_params(), peak_stop.lstm.hidden_size, int(window)
+        self.hist = torch.zeros(N, self.window - 1, dtype=F32, device=device)
+        self.cnt = torch.zeros(N, dtype=torch.int32, device=device)
+
+    def scan(self, series, active=None):
+        """series f32 [N, k] (any strides) -> (first_hit i32 [N], peak f32 [N, k], prob f32 [N, k])"""
+        return ops.peak_stop_scan(self.params, self.hidden, self.window, series, self.hist, self.cnt, active=active, prob_min=0.8)
+
+
 def _stepwise_policy_probs(kind, core, env):
     """policy_probs for the step-wise loop: the LSTM's (h, c) start at zero and are carried through LSTMActorCritic.step.
     nan[0] counts steps whose logits hold a NaN among envs whose episode has not ended (env.done of the previous step).
@@ -261,7 +296,7 @@ def _stepwise_policy_probs(kind, core, env):
 
 @torch.no_grad()
 def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21=20, noise=None, max_steps=None,
-             success_distance=SUCCESS_DISTANCE_THRESHOLD, fused=None, chunk=None):
+             success_distance=SUCCESS_DISTANCE_THRESHOLD, fused=None, chunk=None, peak_stop_device=False):
     """One greedy episode per environment of `env` (a uavppo VecMethaneEnv), all N together.
 
     policy_probs(obs [N, obs_dim]) -> probs or logits [N, 5] (argmax is taken), or a policy object: LSTMActorCritic,
@@ -273,7 +308,13 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     beyond the fp16-split range then run in bf16x6); True = the fused kernel or a RuntimeError naming why not; False =
     step-wise.  chunk: steps per fused launch (default: 250, or 50 with a stop controller, whose rules are replayed over each
     chunk's records).  A NaN logit of a policy object raises RuntimeError("NaN in probs").  A policy_probs function takes
-    neither fused=True nor chunk."""
+    neither fused=True nor chunk.
+    peak_stop_device=True: the PPOV2.1 rule runs on uav_peak_stop_scan -- one scan over all sliding windows of a fused chunk's
+    records (an episode then ends at min(first done record, first hit), no replay loop; a ThresholdController, if also given,
+    keeps its replay), or one scan of steps = 1 per env step on the step-wise path.  Same decisions and metrics as the default,
+    which evaluates the predictor through uav_lstm_fwd + uav_gemm_f32 (peak_pred agrees to the f32 kernels' rounding); a
+    predictor the kernel does not cover (peak_stop_refusal) raises RuntimeError."""
+    peak_stop_device = bool(peak_stop_device) and peak_stop is not None
     pc = _policy_core(policy_probs)
     if pc is None and fused:
         raise RuntimeError("evaluate(fused=True): a policy_probs function has no fused kernel; pass the policy object")
@@ -286,9 +327,10 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
             raise RuntimeError(f"evaluate(fused=True): {why}")
         if why is None:
             return _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
-                                   chunk)
+                                   chunk, peak_stop_device)
         probs, nan = _stepwise_policy_probs(kind, core, env)
-        out = evaluate(probs, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance)
+        out = evaluate(probs, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
+                       peak_stop_device=peak_stop_device)
         if int(nan.item()) > 0:
             raise RuntimeError("NaN in probs")                                   # model.py:47-49
         return out
@@ -304,6 +346,7 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     if controller is not None:
         controller.reset()
     traj = torch.zeros(N, window_size_v21, dtype=torch.float64, device=dev) if peak_stop is not None else None
+    dps = _DevicePeakStop(peak_stop, window_size_v21, N, dev) if peak_stop_device else None
     limit = max_steps or env.max_steps
     for t in range(1, limit + 1):
         act = torch.argmax(policy_probs(obs), dim=1).to(torch.int32)
@@ -318,7 +361,12 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
             if t % 10 == 0:
                 controller.update_threshold(active)
             stop_now |= controller.should_stop(cur, t)
-        if peak_stop is not None:
+        if dps is not None:                  # one scan of steps = 1: NaN (no hit) until the env's window is full
+            _, peak, prob = dps.scan(torch.where(done_b, env.term_obs[:, 2], obs[:, 2]).reshape(N, 1))
+            hit = prob[:, 0] > 0.8
+            peak_pred = torch.where(hit & active, peak[:, 0].to(torch.float64), peak_pred)
+            stop_now |= hit
+        elif peak_stop is not None:
             traj = torch.roll(traj, -1, dims=1)
             traj[:, -1] = cur
             if t >= window_size_v21:
@@ -346,10 +394,13 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     return out
 
 
-def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance, chunk):
+def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance, chunk,
+                    peak_stop_device=False):
     """evaluate() on uav_greedy_episodes: `chunk` steps per launch; the metrics (and the stop controllers) are computed from
     the records with the formulas of evaluate()'s step-wise loop, so the same actions give the same arrays bit for bit.  An
-    env the kernel has ended stays frozen (no auto-reset); an env a controller stopped is passed as inactive to the next chunk."""
+    env the kernel has ended stays frozen (no auto-reset); an env a controller stopped is passed as inactive to the next chunk.
+    peak_stop_device: the PPOV2.1 rule of a whole chunk is one uav_peak_stop_scan over the records; without a ThresholdController
+    there is then no replay loop at all -- `ended = active & (done | hit)`, `stopped |= ended & hit` restated over the chunk."""
     N, dev = env.num_envs, env.device
     H = core.hidden if kind == "lstm" else 0
     env.reset()
@@ -368,9 +419,11 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
     if controller is not None:
         controller.reset()
     traj = torch.zeros(N, window_size_v21, dtype=torch.float64, device=dev) if peak_stop is not None else None
-    replay = controller is not None or peak_stop is not None
+    dps = _DevicePeakStop(peak_stop, window_size_v21, N, dev) if peak_stop_device else None
+    replay = controller is not None or (peak_stop is not None and dps is None)
     limit = max_steps or env.max_steps
-    chunk = int(chunk or (50 if replay else 250))
+    chunk = int(chunk or (50 if replay or peak_stop is not None else 250))
+    rows = torch.arange(N, device=dev)
     last_pos = None
     t0 = 0
     while t0 < limit:
@@ -381,6 +434,8 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
         ops.greedy_episodes(env.state, N, env.cfg(), core.flat, H, k, cur_obs, h, c, kernel_active, recs, noise=nz,
                             nan_count=nan_count)
         done_c = (recs["flags"] & 1) != 0
+        if dps is not None:                      # `active` is kernel_active as the launch found it (the kernel clears it at `done`)
+            first_hit, peak_c, prob_c = dps.scan(recs["obs"][:, :, 2], active.to(torch.uint8))
         if replay:
             for i in range(k):                   # evaluate()'s loop body, step t = t0 + i + 1, on the records
                 t = t0 + i + 1
@@ -394,7 +449,11 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
                     if t % 10 == 0:
                         controller.update_threshold(active)
                     stop_now |= controller.should_stop(cur, t)
-                if peak_stop is not None:
+                if dps is not None:
+                    hit = prob_c[:, i] > 0.8
+                    peak_pred = torch.where(hit & active, peak_c[:, i].to(torch.float64), peak_pred)
+                    stop_now |= hit
+                elif peak_stop is not None:
                     traj = torch.roll(traj, -1, dims=1)
                     traj[:, -1] = cur
                     if t >= window_size_v21:
@@ -408,10 +467,24 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
                 final_pos = torch.where(ended[:, None], pos_end, final_pos)
                 active &= ~ended
             kernel_active &= active.to(torch.uint8)
+        elif dps is not None:                    # an episode ends at min(first done record, first hit); k = neither in this chunk
+            at_done = torch.where(done_c.any(1), done_c.to(torch.int32).argmax(1), k)
+            at_hit = torch.where(first_hit >= 0, first_hit.to(torch.int64), k)
+            first = torch.minimum(at_done, at_hit)
+            ended = active & (first < k)
+            by_rule = ended & (at_hit <= at_done)
+            first = first.clamp(max=k - 1)
+            pos_end = torch.where((ended & (at_done <= at_hit))[:, None], recs["obs"][rows, first, :2].to(torch.float64) * 500.0,
+                                  recs["pos"][rows, first].to(torch.float64))
+            steps = torch.where(ended, first + (t0 + 1), steps)
+            stopped |= by_rule
+            peak_pred = torch.where(by_rule, peak_c[rows, first].to(torch.float64), peak_pred)
+            final_pos = torch.where(ended[:, None], pos_end, final_pos)
+            active &= ~ended
+            kernel_active &= active.to(torch.uint8)
         else:                                    # no controller: an episode ends exactly at its first done record
             ended = active & done_c.any(1)
             first = done_c.to(torch.int32).argmax(1)
-            rows = torch.arange(N, device=dev)
             pos_end = recs["obs"][rows, first, :2].to(torch.float64) * 500.0
             steps = torch.where(ended, (first + (t0 + 1)).to(torch.int64), steps)
             final_pos = torch.where(ended[:, None], pos_end, final_pos)

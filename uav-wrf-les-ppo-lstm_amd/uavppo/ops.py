@@ -997,3 +997,41 @@ def disc_reward(params, obs, act, n_act, gail_coef=1.0, env_coef=1.0, rew_env=No
     if _t is not None:
         _t.record()
     return out
+
+
+# ----------------------------------------------------------------------------- PPOV2.1 peak-and-stop rule (csrc/peak_stop.hip)
+def peak_stop_param_count(hidden=32):
+    n = int(lib().uav_peak_stop_param_count(int(hidden)))
+    if n == 0:
+        raise RuntimeError(f"uav_peak_stop_param_count failed: {lib().uav_last_error().decode()}")
+    return n
+
+
+def peak_stop_scan(params, hidden, window, series, hist, hist_cnt, active=None, prob_min=0.8, want_values=True):
+    """The PeakAndStopPredictor over every sliding window of a chunk (uav_peak_stop_scan).  params: the flat buffer of
+    PeakAndStopPredictor.flat_params(); series: f32 [N, steps] view of any strides (recs["obs"][:, :, 2] as it is): env e's LSTM
+    input at chunk step i; hist f32 [N, window - 1] / hist_cnt i32 [N]: the envs' last inputs, in / out (zero hist_cnt starts an
+    episode); active u8 [N] or None (all).  Returns (first_hit i32 [N]: first step whose window is full and has stop_prob >
+    prob_min, -1 if none; peak, prob f32 [N, steps], NaN where the window is not full or the env inactive -- None with
+    want_values=False)."""
+    if series.dim() != 2 or series.dtype != F32 or not series.is_cuda:
+        raise RuntimeError(f"series: expected a 2-D GPU float32 tensor (view), got {tuple(series.shape)} {series.dtype}")
+    N, T = int(series.shape[0]), int(series.shape[1])
+    W = int(window)
+    P = peak_stop_param_count(hidden)
+    dev = series.device
+    peak = torch.empty(N, T, dtype=F32, device=dev) if want_values else None
+    prob = torch.empty(N, T, dtype=F32, device=dev) if want_values else None
+    first_hit = torch.empty(N, dtype=I32, device=dev)
+    hist_p = _p(hist, F32, (N, max(W - 1, 0)), "hist")
+    if W == 1:          # an [N, 0] tensor has no storage, the C ABI refuses a NULL hist: any valid pointer serves, none of it is touched
+        hist_p = _p(hist_cnt, I32, (N,), "hist_cnt")
+    _t = KERNEL_TIMER.bracket("peak_stop_scan")
+    check(lib().uav_peak_stop_scan(_h(series), _p(params, F32, (P,), "params"), int(hidden), W, C.c_void_p(series.data_ptr()),
+                                   int(series.stride(0)), int(series.stride(1)), N, T, _p(active, U8, (N,), "active"),
+                                   hist_p, _p(hist_cnt, I32, (N,), "hist_cnt"), float(prob_min),
+                                   _p(peak, F32, (N, T), "peak"), _p(prob, F32, (N, T), "prob"), _p(first_hit, I32, (N,), "first_hit"),
+                                   _stream()), "uav_peak_stop_scan")
+    if _t is not None:
+        _t.record()
+    return first_hit, peak, prob

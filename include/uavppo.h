@@ -561,6 +561,49 @@ int uav_peak_stop_scan(uav_ctx* ctx, const float* params, int hidden, int window
                        int64_t elem_stride, int n, int steps, const uint8_t* active, float* hist, int32_t* hist_cnt,
                        float prob_min, float* peak, float* prob, int32_t* first_hit, uav_stream stream);
 
+/* ---- The PPOV2.0 threshold stop rule (PPOV2.0/evaluate_with_lstm.py:10-37, ThresholdController, and the episode loop :67-101)
+ * over a chunk of records: the two kernels around ONE batched call of the ConcentrationThresholdPredictor (csrc/threshold.hip).
+ * The predictor only runs at steps t % every == 0, every window starts from zero state, and the threshold is constant in
+ * between, so a chunk is: uav_threshold_windows -> the predictor over n * S rows (uav_lstm_fwd x 3, uav_gemm_f32, uav_ln_relu,
+ * uav_gemm_f32) -> uav_threshold_rule.  Added without a change of UAV_ABI_VERSION (symbols only).
+ * Both take the series and the env's state as uav_peak_stop_scan does: series[e * row_stride + i * elem_stride] (strides in
+ * floats) is obs[2] of env e's record at chunk step i, i < steps; active u8 [n] or NULL (all); hist f32 [n][window-1]: the env's
+ * last inputs, oldest first; step_cnt i32 [n]: the number of steps of the episode seen before this call (zero starts an episode).
+ * step_cnt does NOT saturate; the fill of hist is min(step_cnt, window-1).  The rule's constants are scalars: window 1 .. 32
+ * (reference 10), every >= 1 (10), min_steps (20), lo / scale f64 (the MinMaxScaler's data_min_ and data_max_ - data_min_, or 1
+ * when that is 0), conc_scale f64 (100), factor f64 (0.95).
+ * Step i of a call is the episode's step t = step_cnt[e] + i + 1.  It is an UPDATE step when t % every == 0 and
+ * t >= max(window, min_steps); env e's update steps of a call fill slots s = t / every - step_cnt[e] / every - 1 (integer
+ * division) of its S = ceil(steps / every) slots.  Slots are per env: envs may enter with different step_cnt.
+ *
+ * uav_threshold_windows writes x f32 [n][S][window]: for an update step of an active env, f32((f64(v) * conc_scale - lo) / scale)
+ * over the last `window` values v of (hist, then series[0 .. i]), oldest first -- f64 arithmetic, every operation correctly
+ * rounded, no contraction: the host's ((window - lo) / scale).to(float32).  Every other slot gets zeros.  Reads hist and
+ * step_cnt, writes neither. */
+int uav_threshold_windows(uav_ctx* ctx, const float* series, int64_t row_stride, int64_t elem_stride, int n, int steps,
+                          const uint8_t* active, const float* hist, const int32_t* step_cnt, int window, int every, int min_steps,
+                          double lo, double scale, double conc_scale, float* x, uav_stream stream);
+
+/* pred f32 [n][S]: the predictor's outputs for the rows of x; thr f64 [n] in/out: the env's threshold, NaN = none yet.  For an
+ * active env, in step order: on an update step thr = f64(pred[e][s]) * factor; then
+ *   stop = t >= min_steps && !isnan(thr) && (cur >= thr || mean >= thr),   cur = f64(series value) * conc_scale,
+ * mean = the f64 mean of the last `window` values of cur, formed only when t >= window (otherwise that half is false), summed in
+ * numpy's order (the reference calls np.mean on a list): fewer than 8 values one by one from 0; otherwise eight accumulators
+ * r[j] = a[j], r[j] += a[i + j] for i = 8, 16, .. below w - w % 8, ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), the remaining values one
+ * by one, then / (double)w.
+ * first_hit i32 [n]: the smallest i with stop, -1 for none or an inactive env.  stop u8 [n][steps] (or NULL): the flag of every
+ * step; thr_out f64 [n][steps] (or NULL): the threshold in force at every step, NaN for none.  (An inactive env's rows get 0 and
+ * its unchanged thr.)  On exit an active env has hist = its last window-1 inputs, step_cnt += steps and thr as the last step left
+ * it; inactive envs keep all three.  The kernel runs through the whole chunk (the host takes the minimum with the first `done`
+ * record).  One thread per env, no atomics, nothing depends on the launch shape: k calls of steps / k equal one call bit for bit
+ * (first_hit then differs by the chunk offset).  A NaN input makes no hit on its step and stays within its env.
+ * Both are refused with a reason before the GPU is touched: window outside 1 .. 32, every < 1, n < 1, steps < 1, NULL series,
+ * hist, step_cnt, x (windows), pred, thr, first_hit (rule), NULL handle. */
+int uav_threshold_rule(uav_ctx* ctx, const float* series, int64_t row_stride, int64_t elem_stride, int n, int steps,
+                       const uint8_t* active, float* hist, int32_t* step_cnt, int window, int every, int min_steps, double conc_scale,
+                       double factor, const float* pred, double* thr, int32_t* first_hit, uint8_t* stop, double* thr_out,
+                       uav_stream stream);
+
 /* The tail of step t of a step-wise rollout as ONE launch (train_ppo2.0.py:165-198 after the recurrent layers): policy heads of
  * the top layer (heads[:, t] = y_t W_head^T + b_head, the sums of uav_gemm_f32's few-column kernel bit for bit; y = row t of a
  * [n][T][hidden] array given as the pointer to y[0][t] and its row stride y_stride floats, likewise heads / heads_stride),

@@ -13,6 +13,9 @@ fp16-split arithmetic, parameters inside that arithmetic's range) whole chunks o
 controllers are replayed over the chunk's records; everything else steps one launch sequence per time step.
 With peak_stop_device=True the PPOV2.1 rule is not replayed: uav_peak_stop_scan runs the predictor over every sliding window of
 a chunk's records in one scan and hands back the first hit per env.
+With threshold_device=True the PPOV2.0 rule is not replayed either: the predictor only runs every 10th step, from zero state, so a
+chunk's windows are cut out of the records by uav_threshold_windows, go through the ConcentrationThresholdPredictor as the rows of
+ONE batched call, and uav_threshold_rule applies the rule to every step and hands back the first hit per env.
 """
 from __future__ import annotations
 
@@ -267,6 +270,44 @@ class _DevicePeakStop:
         return ops.peak_stop_scan(self.params, self.hidden, self.window, series, self.hist, self.cnt, active=active, prob_min=0.8)
 
 
+class _DeviceThreshold:
+    """The PPOV2.0 rule on uav_threshold_windows / uav_threshold_rule around one batched call of the controller's predictor: the
+    envs' last window - 1 inputs, their step counts and their thresholds (f64, NaN = none yet)."""
+    EVERY = 10          # the episode loop's `step_count % 10 == 0` (PPOV2.0/evaluate_with_lstm.py:87)
+
+    def __init__(self, controller, N, device):
+        self.model, self.lo, self.scale = controller.model, float(controller.lo), float(controller.scale)
+        self.window, self.min_steps = int(controller.window_size), int(controller.min_activate_steps)
+        if not 1 <= self.window <= 32:
+            raise RuntimeError(f"evaluate(threshold_device=True): window_size = {self.window}; uav_threshold_rule takes windows of "
+                               f"1 .. 32 steps")
+        self.N = int(N)
+        self.hist = torch.zeros(N, self.window - 1, dtype=F32, device=device)
+        self.cnt = torch.zeros(N, dtype=torch.int32, device=device)
+        self.thr = torch.full((N,), float("nan"), dtype=torch.float64, device=device)
+        self._no_pred = {}
+
+    def has_update(self, t0, k):
+        """whether an env that enters with t0 steps behind it meets an update step within the next k"""
+        first = max(t0 + 1, self.window, self.min_steps)
+        return -(-first // self.EVERY) * self.EVERY <= t0 + k
+
+    def scan(self, series, active=None, t0=None, want_steps=False):
+        """series f32 [N, k] (any strides) -> (first_hit i32 [N], stop u8 [N, k] or None, thr f64 [N, k] or None).  t0: the steps
+        every active env has behind it, where the caller knows it: a call that can hold no update step skips the predictor."""
+        k = int(series.shape[1])
+        S = ops.threshold_slots(k, self.EVERY)
+        kw = dict(active=active, window=self.window, every=self.EVERY, min_steps=self.min_steps)
+        if t0 is None or self.has_update(t0, k):
+            x = ops.threshold_windows(series, self.hist, self.cnt, lo=self.lo, scale=self.scale, **kw)
+            pred = self.model(x.reshape(self.N * S, self.window, 1)).to(F32).reshape(self.N, S).contiguous()
+        else:           # no slot is read
+            if S not in self._no_pred:
+                self._no_pred[S] = torch.zeros(self.N, S, dtype=F32, device=series.device)
+            pred = self._no_pred[S]
+        return ops.threshold_rule(series, self.hist, self.cnt, pred, self.thr, factor=0.95, want_steps=want_steps, **kw)
+
+
 def _stepwise_policy_probs(kind, core, env):
     """policy_probs for the step-wise loop: the LSTM's (h, c) start at zero and are carried through LSTMActorCritic.step.
     nan[0] counts steps whose logits hold a NaN among envs whose episode has not ended (env.done of the previous step).
@@ -296,7 +337,7 @@ def _stepwise_policy_probs(kind, core, env):
 
 @torch.no_grad()
 def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21=20, noise=None, max_steps=None,
-             success_distance=SUCCESS_DISTANCE_THRESHOLD, fused=None, chunk=None, peak_stop_device=False):
+             success_distance=SUCCESS_DISTANCE_THRESHOLD, fused=None, chunk=None, peak_stop_device=False, threshold_device=False):
     """One greedy episode per environment of `env` (a uavppo VecMethaneEnv), all N together.
 
     policy_probs(obs [N, obs_dim]) -> probs or logits [N, 5] (argmax is taken), or a policy object: LSTMActorCritic,
@@ -313,8 +354,16 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     records (an episode then ends at min(first done record, first hit), no replay loop; a ThresholdController, if also given,
     keeps its replay), or one scan of steps = 1 per env step on the step-wise path.  Same decisions and metrics as the default,
     which evaluates the predictor through uav_lstm_fwd + uav_gemm_f32 (peak_pred agrees to the f32 kernels' rounding); a
-    predictor the kernel does not cover (peak_stop_refusal) raises RuntimeError."""
+    predictor the kernel does not cover (peak_stop_refusal) raises RuntimeError.
+    threshold_device=True: the PPOV2.0 rule runs on the device -- per fused chunk uav_threshold_windows, ONE batched call of the
+    controller's predictor over the chunk's windows, and uav_threshold_rule (first hit per env), or the rule kernel with steps = 1
+    per env step on the step-wise path (windows and predictor on update steps only).  With every rule given on the device there
+    is no replay loop: an episode ends at min(first done record, threshold hit, peak-stop hit).  Same decisions and metrics as
+    the default (the window mean is summed in np.mean's order, as the reference's, where the host replay uses torch's sum).  On
+    return controller.current_threshold holds the device's thresholds (f64 [N], NaN = None; on the fused path an env that ended
+    inside a chunk has the threshold of that chunk's last step)."""
     peak_stop_device = bool(peak_stop_device) and peak_stop is not None
+    threshold_device = bool(threshold_device) and controller is not None
     pc = _policy_core(policy_probs)
     if pc is None and fused:
         raise RuntimeError("evaluate(fused=True): a policy_probs function has no fused kernel; pass the policy object")
@@ -327,10 +376,10 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
             raise RuntimeError(f"evaluate(fused=True): {why}")
         if why is None:
             return _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
-                                   chunk, peak_stop_device)
+                                   chunk, peak_stop_device, threshold_device)
         probs, nan = _stepwise_policy_probs(kind, core, env)
         out = evaluate(probs, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
-                       peak_stop_device=peak_stop_device)
+                       peak_stop_device=peak_stop_device, threshold_device=threshold_device)
         if int(nan.item()) > 0:
             raise RuntimeError("NaN in probs")                                   # model.py:47-49
         return out
@@ -347,6 +396,7 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
         controller.reset()
     traj = torch.zeros(N, window_size_v21, dtype=torch.float64, device=dev) if peak_stop is not None else None
     dps = _DevicePeakStop(peak_stop, window_size_v21, N, dev) if peak_stop_device else None
+    dth = _DeviceThreshold(controller, N, dev) if threshold_device else None
     limit = max_steps or env.max_steps
     for t in range(1, limit + 1):
         act = torch.argmax(policy_probs(obs), dim=1).to(torch.int32)
@@ -356,7 +406,11 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
         pos_now, _, _, _ = env.peek()
         pos_end = torch.where(done_b[:, None], env.term_obs[:, :2].to(torch.float64) * 500.0, pos_now.to(torch.float64))
         stop_now = torch.zeros(N, dtype=torch.bool, device=dev)
-        if controller is not None:
+        if dth is not None:                  # one rule call of steps = 1; windows + predictor on update steps only
+            _, th_stop, _ = dth.scan(torch.where(done_b, env.term_obs[:, 2], obs[:, 2]).reshape(N, 1), active.to(torch.uint8), t - 1,
+                                     want_steps=True)
+            stop_now |= th_stop[:, 0] != 0
+        elif controller is not None:
             controller.push(cur)
             if t % 10 == 0:
                 controller.update_threshold(active)
@@ -386,6 +440,8 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
         pos_now, _, _, _ = env.peek()
         final_pos = torch.where(active[:, None], pos_now.to(torch.float64), final_pos)
         steps = torch.where(active, torch.full_like(steps, limit), steps)
+    if dth is not None:
+        controller.current_threshold = dth.thr
     deviation = torch.linalg.norm(final_pos - src, dim=1)
     out = {"deviations": deviation.cpu().numpy(), "steps": steps.cpu().numpy(),
            "success": (deviation <= success_distance).cpu().numpy(), "stopped_early": stopped.cpu().numpy()}
@@ -395,12 +451,14 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
 
 
 def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance, chunk,
-                    peak_stop_device=False):
+                    peak_stop_device=False, threshold_device=False):
     """evaluate() on uav_greedy_episodes: `chunk` steps per launch; the metrics (and the stop controllers) are computed from
     the records with the formulas of evaluate()'s step-wise loop, so the same actions give the same arrays bit for bit.  An
     env the kernel has ended stays frozen (no auto-reset); an env a controller stopped is passed as inactive to the next chunk.
     peak_stop_device: the PPOV2.1 rule of a whole chunk is one uav_peak_stop_scan over the records; without a ThresholdController
-    there is then no replay loop at all -- `ended = active & (done | hit)`, `stopped |= ended & hit` restated over the chunk."""
+    there is then no replay loop at all -- `ended = active & (done | hit)`, `stopped |= ended & hit` restated over the chunk.
+    threshold_device: the PPOV2.0 rule of a whole chunk is uav_threshold_windows, one batched predictor call and uav_threshold_rule.
+    `replay` is true only while some rule given is NOT on the device; the replay loop then takes the device rule's per-step flags."""
     N, dev = env.num_envs, env.device
     H = core.hidden if kind == "lstm" else 0
     env.reset()
@@ -420,9 +478,10 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
         controller.reset()
     traj = torch.zeros(N, window_size_v21, dtype=torch.float64, device=dev) if peak_stop is not None else None
     dps = _DevicePeakStop(peak_stop, window_size_v21, N, dev) if peak_stop_device else None
-    replay = controller is not None or (peak_stop is not None and dps is None)
+    dth = _DeviceThreshold(controller, N, dev) if threshold_device else None
+    replay = (controller is not None and dth is None) or (peak_stop is not None and dps is None)
     limit = max_steps or env.max_steps
-    chunk = int(chunk or (50 if replay or peak_stop is not None else 250))
+    chunk = int(chunk or (50 if controller is not None or peak_stop is not None else 250))
     rows = torch.arange(N, device=dev)
     last_pos = None
     t0 = 0
@@ -434,8 +493,12 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
         ops.greedy_episodes(env.state, N, env.cfg(), core.flat, H, k, cur_obs, h, c, kernel_active, recs, noise=nz,
                             nan_count=nan_count)
         done_c = (recs["flags"] & 1) != 0
-        if dps is not None:                      # `active` is kernel_active as the launch found it (the kernel clears it at `done`)
-            first_hit, peak_c, prob_c = dps.scan(recs["obs"][:, :, 2], active.to(torch.uint8))
+        if dps is not None or dth is not None:   # `active` is kernel_active as the launch found it (the kernel clears it at `done`)
+            was_active = active.to(torch.uint8)
+        if dps is not None:
+            first_hit, peak_c, prob_c = dps.scan(recs["obs"][:, :, 2], was_active)
+        if dth is not None:                      # every active env has t0 steps behind it
+            th_hit, th_stop, _ = dth.scan(recs["obs"][:, :, 2], was_active, t0, want_steps=replay)
         if replay:
             for i in range(k):                   # evaluate()'s loop body, step t = t0 + i + 1, on the records
                 t = t0 + i + 1
@@ -444,7 +507,9 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
                 pos_end = torch.where(done_b[:, None], recs["obs"][:, i, :2].to(torch.float64) * 500.0,
                                       recs["pos"][:, i].to(torch.float64))
                 stop_now = torch.zeros(N, dtype=torch.bool, device=dev)
-                if controller is not None:
+                if dth is not None:
+                    stop_now |= th_stop[:, i] != 0
+                elif controller is not None:
                     controller.push(cur)
                     if t % 10 == 0:
                         controller.update_threshold(active)
@@ -467,18 +532,21 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
                 final_pos = torch.where(ended[:, None], pos_end, final_pos)
                 active &= ~ended
             kernel_active &= active.to(torch.uint8)
-        elif dps is not None:                    # an episode ends at min(first done record, first hit); k = neither in this chunk
+        elif dps is not None or dth is not None:  # an episode ends at min(first done record, each rule's first hit); k = none in this chunk
             at_done = torch.where(done_c.any(1), done_c.to(torch.int32).argmax(1), k)
-            at_hit = torch.where(first_hit >= 0, first_hit.to(torch.int64), k)
+            at_peak = torch.where(first_hit >= 0, first_hit.to(torch.int64), k) if dps is not None else torch.full_like(at_done, k)
+            at_hit = at_peak if dth is None else torch.minimum(at_peak, torch.where(th_hit >= 0, th_hit.to(torch.int64), k))
             first = torch.minimum(at_done, at_hit)
             ended = active & (first < k)
             by_rule = ended & (at_hit <= at_done)
+            by_peak = ended & (at_peak <= first)  # the peak-stop rule fired on the episode's last step (alone or beside the others)
             first = first.clamp(max=k - 1)
             pos_end = torch.where((ended & (at_done <= at_hit))[:, None], recs["obs"][rows, first, :2].to(torch.float64) * 500.0,
                                   recs["pos"][rows, first].to(torch.float64))
             steps = torch.where(ended, first + (t0 + 1), steps)
             stopped |= by_rule
-            peak_pred = torch.where(by_rule, peak_c[rows, first].to(torch.float64), peak_pred)
+            if dps is not None:
+                peak_pred = torch.where(by_peak, peak_c[rows, first].to(torch.float64), peak_pred)
             final_pos = torch.where(ended[:, None], pos_end, final_pos)
             active &= ~ended
             kernel_active &= active.to(torch.uint8)
@@ -499,6 +567,8 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
     if bool(active.any()):
         final_pos = torch.where(active[:, None], last_pos.to(torch.float64), final_pos)
         steps = torch.where(active, torch.full_like(steps, limit), steps)
+    if dth is not None:
+        controller.current_threshold = dth.thr
     deviation = torch.linalg.norm(final_pos - src, dim=1)
     out = {"deviations": deviation.cpu().numpy(), "steps": steps.cpu().numpy(),
            "success": (deviation <= success_distance).cpu().numpy(), "stopped_early": stopped.cpu().numpy()}
@@ -520,9 +590,10 @@ def load_lstm_policy(path, device="cuda"):
     return pol
 
 
-def main(num_envs=1000, model_dir="model", device="cuda", policy="mlp"):
+def main(num_envs=1000, model_dir="model", device="cuda", policy="mlp", threshold_device=False):
     """The reference's main() (evaluate_with_lstm.py:39-134) with its 1000 episodes run as 1000 parallel environments.
-    policy="mlp": the reference's PPOActorCritic; "lstm": the vectorised trainer's LSTM actor-critic (same file name)."""
+    policy="mlp": the reference's PPOActorCritic; "lstm": the vectorised trainer's LSTM actor-critic (same file name).
+    threshold_device (--device-rule): the ThresholdController's rule on the device (evaluate(threshold_device=True))."""
     from model import PPOActorCritic
     from uavppo.vec_env import VecMethaneEnv
     if policy not in ("mlp", "lstm"):
@@ -544,9 +615,9 @@ def main(num_envs=1000, model_dir="model", device="cuda", policy="mlp"):
     env = VecMethaneEnv(num_envs, "v2.0", device, trend_k=trend_k)
     controller = ThresholdController(lstm_model, (scaler_params.min(), scaler_params.max()), num_envs, device=device)
     if policy == "lstm":
-        metrics = evaluate(ppo_model, env, controller)
-    else:
-        metrics = evaluate(lambda o: ppo_model.core.heads(o)[:, :5], env, controller)     # argmax of logits == argmax of probs
+        metrics = evaluate(ppo_model, env, controller, threshold_device=threshold_device)
+    else:                                                                                  # argmax of logits == argmax of probs
+        metrics = evaluate(lambda o: ppo_model.core.heads(o)[:, :5], env, controller, threshold_device=threshold_device)
     ok = metrics["success"]
     print("===== validation =====")
     print(f"mean deviation: {metrics['deviations'].mean():.2f} +- {metrics['deviations'].std():.2f} px")
@@ -561,4 +632,4 @@ def main(num_envs=1000, model_dir="model", device="cuda", policy="mlp"):
 
 if __name__ == "__main__":
     import sys
-    main(policy="lstm" if "--lstm" in sys.argv[1:] else "mlp")
+    main(policy="lstm" if "--lstm" in sys.argv[1:] else "mlp", threshold_device="--device-rule" in sys.argv[1:])

@@ -108,6 +108,8 @@ SIGNATURES = {
     "uav_stop_stability": (I32, [P, I32, C.POINTER(StopRule), P, P, I64, P, P, P, P, P, P]),
     "uav_peak_stop_param_count": (SZ, [I32]),
     "uav_peak_stop_scan": (I32, [P, P, I32, I32, P, I64, I64, I32, I32, P, P, P, F32, P, P, P, P]),
+    "uav_threshold_windows": (I32, [P, P, I64, I64, I32, I32, P, P, P, I32, I32, I32, F64, F64, F64, P, P]),
+    "uav_threshold_rule": (I32, [P, P, I64, I64, I32, I32, P, P, P, I32, I32, I32, F64, F64, P, P, P, P, P, P]),
     "uav_rccl_version": (I32, [C.POINTER(C.c_int)]),
     "uav_comm_unique_id": (I32, [P]),
     "uav_comm_init": (I32, [P, P, I32, I32]),

@@ -1035,3 +1035,58 @@ def peak_stop_scan(params, hidden, window, series, hist, hist_cnt, active=None, 
     if _t is not None:
         _t.record()
     return first_hit, peak, prob
+
+
+# ----------------------------------------------------------------------------- PPOV2.0 threshold stop rule (csrc/threshold.hip)
+def threshold_slots(steps, every=10):
+    """S = ceil(steps / every): the predictor rows per env of a call of `steps` steps."""
+    return (int(steps) + int(every) - 1) // int(every)
+
+
+def _threshold_series(series, hist, step_cnt, window):
+    if series.dim() != 2 or series.dtype != F32 or not series.is_cuda:
+        raise RuntimeError(f"series: expected a 2-D GPU float32 tensor (view), got {tuple(series.shape)} {series.dtype}")
+    N, W = int(series.shape[0]), int(window)
+    hist_p = _p(hist, F32, (N, max(W - 1, 0)), "hist")
+    if W == 1:          # an [N, 0] tensor has no storage, the C ABI refuses a NULL hist: any valid pointer serves, none of it is touched
+        hist_p = _p(step_cnt, I32, (N,), "step_cnt")
+    return N, int(series.shape[1]), W, hist_p
+
+
+def threshold_windows(series, hist, step_cnt, active=None, window=10, every=10, min_steps=20, lo=0.0, scale=1.0, conc_scale=100.0):
+    """The ConcentrationThresholdPredictor's inputs of a chunk (uav_threshold_windows).  series: f32 [N, steps] view of any strides
+    (recs["obs"][:, :, 2] as it is); hist f32 [N, window - 1] / step_cnt i32 [N]: the envs' last inputs and the steps seen before
+    this call (read only); active u8 [N] or None (all).  Returns x f32 [N, S, window], S = threshold_slots(steps, every): slot s of
+    env e holds the scaled window of its update step t = (step_cnt[e] // every + s + 1) * every where the call reaches it and
+    t >= max(window, min_steps), zeros otherwise."""
+    N, T, W, hist_p = _threshold_series(series, hist, step_cnt, window)
+    x = torch.empty(N, threshold_slots(T, every), W, dtype=F32, device=series.device)
+    _t = KERNEL_TIMER.bracket("threshold_windows")
+    check(lib().uav_threshold_windows(_h(series), C.c_void_p(series.data_ptr()), int(series.stride(0)), int(series.stride(1)), N, T,
+                                      _p(active, U8, (N,), "active"), hist_p, _p(step_cnt, I32, (N,), "step_cnt"), W, int(every),
+                                      int(min_steps), float(lo), float(scale), float(conc_scale), _p(x), _stream()),
+          "uav_threshold_windows")
+    if _t is not None:
+        _t.record()
+    return x
+
+
+def threshold_rule(series, hist, step_cnt, pred, thr, active=None, window=10, every=10, min_steps=20, conc_scale=100.0, factor=0.95,
+                   want_steps=True):
+    """The PPOV2.0 rule over every step of a chunk (uav_threshold_rule).  series, hist, step_cnt, active as threshold_windows (hist
+    and step_cnt are advanced here); pred f32 [N, S]: the predictor's outputs for threshold_windows' rows; thr f64 [N] in / out:
+    the threshold in force, NaN = none yet.  Returns (first_hit i32 [N]: first step of the call at which the rule fires, -1 if
+    none; stop u8 [N, steps]; thr_out f64 [N, steps] -- None, None with want_steps=False)."""
+    N, T, W, hist_p = _threshold_series(series, hist, step_cnt, window)
+    dev = series.device
+    stop = torch.empty(N, T, dtype=U8, device=dev) if want_steps else None
+    thr_out = torch.empty(N, T, dtype=F64, device=dev) if want_steps else None
+    first_hit = torch.empty(N, dtype=I32, device=dev)
+    _t = KERNEL_TIMER.bracket("threshold_rule")
+    check(lib().uav_threshold_rule(_h(series), C.c_void_p(series.data_ptr()), int(series.stride(0)), int(series.stride(1)), N, T,
+                                   _p(active, U8, (N,), "active"), hist_p, _p(step_cnt, I32, (N,), "step_cnt"), W, int(every),
+                                   int(min_steps), float(conc_scale), float(factor), _p(pred, F32, (N, threshold_slots(T, every)), "pred"),
+                                   _p(thr, F64, (N,), "thr"), _p(first_hit), _p(stop), _p(thr_out), _stream()), "uav_threshold_rule")
+    if _t is not None:
+        _t.record()
+    return first_hit, stop, thr_out

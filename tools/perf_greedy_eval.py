@@ -72,8 +72,7 @@ def _chunk_times(kind, N, chunk, dev, blocks, per_block, with_stop=True):
     h = torch.zeros(N, H, device=dev) if H else None
     c = torch.zeros(N, H, device=dev) if H else None
     active = torch.ones(N, dtype=torch.uint8, device=dev)
-    recs = {"act": torch.empty(N, chunk, dtype=torch.int32, device=dev), "obs": torch.empty(N, chunk, 6, device=dev),
-            "pos": torch.empty(N, chunk, 2, device=dev), "flags": torch.empty(N, chunk, dtype=torch.uint8, device=dev)}
+    recs = ops.greedy_recs(N, chunk, 6, dev)
     never = ops.make_stop_rule(pos_std_max=0.0) if with_stop else None
     win = torch.zeros(N, 10, 2, device=dev)
     cnt = torch.zeros(N, dtype=torch.int32, device=dev)

@@ -84,7 +84,8 @@ def kernel(a, dev, out, save):
     obs = (torch.rand(N, k, 6, generator=g) * 0.1).to(dev)          # the records' layout: column 2 is read in place
     hist0 = (torch.rand(N, WINDOW - 1, generator=g) * 0.1).to(dev)
     props = torch.cuda.get_device_properties(0)
-    simds, clock_hz = props.multi_processor_count * 4, props.clock_rate * 1e3
+    # clock_rate is in kHz; a torch build whose properties lack it: the MI355X's 2.4 GHz peak engine clock
+    simds, clock_hz = props.multi_processor_count * 4, getattr(props, "clock_rate", 2.4e6) * 1e3
     rows = {}
     for name, cnt0 in (("full_history", WINDOW - 1), ("first_chunk", 0)):
         hist, cnt = hist0.clone(), torch.full((N,), cnt0, dtype=torch.int32, device=dev)

@@ -6,7 +6,7 @@ episode each.  Same class and attribute names, the same CSV (evaluation_results.
 final_conc) and the same stop rule (:25-37): once 10 positions are recorded, stop when np.std of the last 10 agent
 positions, averaged over the two coordinates, is below 2.0 px AND the step's concentration is above the threshold.
 
-The rule runs on the device.  Where the fused greedy-episode kernels cover the policy (evaluate_with_lstm.fused_refusal:
+The rule runs on the device.  Where the fused greedy-episode kernels cover the policy (uavppo.greedy.fused_refusal:
 the reference's MLP or one LSTM layer of h = 64 / 128, fp16-split arithmetic, parameters in range) whole chunks of steps are
 one launch each of uav_greedy_episodes_stop -- the env lane pushes agent_pos into its window, evaluates the rule and freezes
 the env on a hit -- and the host only reduces the records: an env's episode ends at its first record with flags bit0 (done)
@@ -19,8 +19,8 @@ import numpy as np
 import torch
 
 from config import CONC_PEAK, CONC_REWARD_COEF
-from evaluate_with_lstm import _policy_core, _stepwise_policy_probs, fused_refusal
 from uavppo import ops
+from uavppo.greedy import GreedyRun, fused_refusal, policy_core, stepwise_policy_probs
 
 F32 = torch.float32
 CSV_COLUMNS = ("episode", "steps", "deviation", "success", "final_conc")
@@ -104,34 +104,21 @@ class ModelEvaluator:
         uav_greedy_episodes_stop.  want: optional dict that receives the concatenated records and rule_val (tests)."""
         env = self.env
         N, dev = env.num_envs, env.device
-        H = core.hidden if kind == "lstm" else 0
-        rule = self._rule()
-        h = torch.zeros(N, H, dtype=F32, device=dev) if H else None
-        c = torch.zeros(N, H, dtype=F32, device=dev) if H else None
-        kernel_active = torch.ones(N, dtype=torch.uint8, device=dev)
-        stop_win = torch.zeros(N, rule.window, 2, dtype=F32, device=dev)
-        stop_cnt = torch.zeros(N, dtype=torch.int32, device=dev)
-        nan_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        run = GreedyRun(kind, core, env, self._rule())
         active = torch.ones(N, dtype=torch.bool, device=dev)
         steps = torch.zeros(N, dtype=torch.int64, device=dev)
         stopped = torch.zeros(N, dtype=torch.bool, device=dev)
         pos = torch.zeros(N, 2, dtype=F32, device=dev)
         obs2 = torch.zeros(N, dtype=F32, device=dev)
         rows = torch.arange(N, device=dev)
-        kept = {"act": [], "obs": [], "pos": [], "flags": [], "rule_val": []} if want is not None else None
+        kept = []
         t0 = 0
         while t0 < limit:
             k = min(chunk, limit - t0)
-            recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, env.obs_dim, dtype=F32, device=dev),
-                    "pos": torch.empty(N, k, 2, dtype=F32, device=dev), "flags": torch.empty(N, k, dtype=torch.uint8, device=dev)}
             rv = torch.empty(N, k, dtype=F32, device=dev) if want is not None else None
-            nz = None if noise is None else noise[t0:t0 + k].transpose(0, 1).contiguous()
-            ops.greedy_episodes_stop(env.state, N, env.cfg(), core.flat, H, k, env.obs, h, c, kernel_active, recs, rule,
-                                     stop_win, stop_cnt, noise=nz, nan_count=nan_count, rule_val=rv)
-            if kept is not None:
-                for key in recs:
-                    kept[key].append(recs[key])
-                kept["rule_val"].append(rv)
+            recs = run.chunk(t0, k, noise, rule_val=rv)
+            if want is not None:
+                kept.append(dict(recs, rule_val=rv))
             end_c = (recs["flags"] & (DONE | STOPPED)) != 0            # an episode ends at its first such record
             ended = active & end_c.any(1)
             last = torch.where(ended, end_c.to(torch.int32).argmax(1), torch.full_like(rows, k - 1))
@@ -145,12 +132,11 @@ class ModelEvaluator:
             t0 += k
             if not bool(active.any()):
                 break
-        if int(nan_count.item()) > 0:
-            raise RuntimeError("NaN in probs")                                     # model.py:47-49
+        run.raise_on_nan()
         steps = torch.where(active, torch.full_like(steps, limit), steps)          # cut off by `max_steps`
         if want is not None:
-            want.update({key: torch.cat(v, 1) for key, v in kept.items()})
-            want.update(stop_win=stop_win, stop_cnt=stop_cnt, h=h, c=c, active=kernel_active)
+            want.update({key: torch.cat([r[key] for r in kept], 1) for key in kept[0]})
+            want.update(stop_win=run.stop_win, stop_cnt=run.stop_cnt, h=run.h, c=run.c, active=run.active)
         return steps, pos, obs2, stopped
 
     def _episodes_stepwise(self, kind, core, noise, limit, want=None):
@@ -160,7 +146,7 @@ class ModelEvaluator:
         env = self.env
         N, dev = env.num_envs, env.device
         rule = self._rule()
-        probs, nan = _stepwise_policy_probs(kind, core, env)
+        probs, nan = stepwise_policy_probs(kind, core, env)
         stop_win = torch.zeros(N, rule.window, 2, dtype=F32, device=dev)
         stop_cnt = torch.zeros(N, dtype=torch.int32, device=dev)
         active = torch.ones(N, dtype=torch.bool, device=dev)
@@ -198,7 +184,7 @@ class ModelEvaluator:
 
 
 def _policy_core_checked(policy):
-    pc = _policy_core(policy)
+    pc = policy_core(policy)
     if pc is None:
         raise TypeError(f"ModelEvaluator: expected a model path, LSTMActorCritic, MLPActorCritic or PPOActorCritic, "
                         f"got {type(policy).__name__}")

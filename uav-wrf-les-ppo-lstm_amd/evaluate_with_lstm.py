@@ -10,16 +10,11 @@ Python scalars become device tensors of length N.  No CPU fallback: everything g
 evaluate() also takes a policy object (the vectorised trainer's LSTMActorCritic / MLPActorCritic, or model.PPOActorCritic).
 Where uav_greedy_episodes covers it (single-layer LSTM h = 64 / 128 or the reference's MLP, 6 observation features, the
 fp16-split arithmetic, parameters inside that arithmetic's range) whole chunks of steps run in one launch each and the stop
-controllers are replayed over the chunk's records; everything else steps one launch sequence per time step.
-With peak_stop_device=True the PPOV2.1 rule is not replayed: uav_peak_stop_scan runs the predictor over every sliding window of
-a chunk's records in one scan and hands back the first hit per env.
-With threshold_device=True the PPOV2.0 rule is not replayed either: the predictor only runs every 10th step, from zero state, so a
-chunk's windows are cut out of the records by uav_threshold_windows, go through the ConcentrationThresholdPredictor as the rows of
-ONE batched call, and uav_threshold_rule applies the rule to every step and hands back the first hit per env.
+controllers are replayed over the chunk's records, or (peak_stop_device, threshold_device) run as device scans over them;
+everything else steps one launch sequence per time step.  What the scripts share is in uavppo/greedy.py.
 """
 from __future__ import annotations
 
-import contextlib
 import math
 import os
 
@@ -28,11 +23,9 @@ import torch
 
 from config import EVALUATE_SIZE, SUCCESS_DISTANCE_THRESHOLD
 from uavppo import ops
+from uavppo.greedy import GreedyRun, fused_refusal, policy_core, stepwise_policy_probs  # noqa: F401  (fused_refusal: tests, docs)
 
 F32 = torch.float32
-
-
-_MLP_SHAPE = (6, 256, 128, 5)            # in, h1, h2, n_act of the fused MLP kernels
 
 
 def _xavier(shape, gen):
@@ -195,54 +188,6 @@ class ThresholdController:
         return (step_count >= self.min_activate_steps) & has & ((current_conc >= thr) | (mean >= thr))
 
 
-def _policy_core(policy):
-    """(kind, policy) of a policy object: "lstm" for LSTMActorCritic, "mlp" for MLPActorCritic or model.PPOActorCritic (an
-    nn.Module, hence callable: the policy classes are recognised before anything is taken for a policy_probs function)."""
-    from uavppo.policy import LSTMActorCritic, MLPActorCritic
-    core = getattr(policy, "core", policy)
-    if isinstance(core, LSTMActorCritic):
-        return "lstm", core
-    if isinstance(core, MLPActorCritic):
-        return "mlp", core
-    if callable(policy):
-        return None
-    raise TypeError(f"evaluate: expected a callable, LSTMActorCritic, MLPActorCritic or PPOActorCritic, got {type(policy).__name__}")
-
-
-def _out_of_range(kind, core):
-    """max |param| (NaN not counted) against the trainer's fp16-split limit: (value, limit, out of range)."""
-    from uavppo.trainer import MLP_RANGE_LIMITS, RANGE_LIMITS
-    limit = RANGE_LIMITS[0] if kind == "lstm" else MLP_RANGE_LIMITS[0]
-    a = core.flat.detach().abs()
-    pmax = float(torch.where(torch.isnan(a), torch.zeros_like(a), a).max())
-    return pmax, limit, not pmax < limit
-
-
-def fused_refusal(policy, env):
-    """Why uav_greedy_episodes cannot run `policy` on `env` (None when it can)."""
-    kind, core = _policy_core(policy)
-    mode = ops.get_lstm_arith(env.device)
-    if mode != "fp16x3":
-        return f"the handle's arithmetic is {mode}; the fused greedy kernels exist in fp16x3 only"
-    trend = f" (the env has trend_k = {env.trend_k})" if env.trend_k else ""      # every refusal on a trend env names trend_k
-    if kind == "lstm":
-        if core.num_layers != 1 or core.hidden not in (64, 128) or core.n_act != 5:
-            return (f"LSTM {core.num_layers} layer(s), hidden {core.hidden}, obs_dim {core.obs_dim}, {core.n_act} actions; "
-                    f"the fused kernel covers one layer of hidden 64 / 128, obs_dim 6 + trend_k, 5 actions{trend}")
-        if core.obs_dim != 6 + env.trend_k:
-            return (f"the policy's obs_dim is {core.obs_dim}, the env's observations have {6 + env.trend_k} features "
-                    f"(6 + trend_k, trend_k = {env.trend_k})")
-    elif env.trend_k:
-        return f"trend_k = {env.trend_k}; the fused MLP greedy kernels take 6 observation features"
-    elif (core.in_dim, core.h1, core.h2, core.n_act) != _MLP_SHAPE:
-        return f"MLP {core.in_dim}-{core.h1}-{core.h2}-{core.n_act}; the fused kernel covers 6-256-128-5 only"
-    # NaN parameters are not out of range: they reach the kernel and come back as nan_count ("NaN in probs")
-    pmax, limit, out = _out_of_range(kind, core)
-    if out:
-        return f"max |param| = {pmax:g} is not below {limit:g}, the fp16-split range limit (uavppo/trainer.py)"
-    return None
-
-
 def peak_stop_refusal(peak_stop, window):
     """Why uav_peak_stop_scan cannot run `peak_stop` over windows of `window` steps (None when it can)."""
     l = peak_stop.lstm
@@ -308,31 +253,134 @@ class _DeviceThreshold:
         return ops.threshold_rule(series, self.hist, self.cnt, pred, self.thr, factor=0.95, want_steps=want_steps, **kw)
 
 
-def _stepwise_policy_probs(kind, core, env):
-    """policy_probs for the step-wise loop: the LSTM's (h, c) start at zero and are carried through LSTMActorCritic.step.
-    nan[0] counts steps whose logits hold a NaN among envs whose episode has not ended (env.done of the previous step).
-    Parameters beyond the fp16-split range on a handle in that mode: the policy's own calls run in bf16x6, as the trainer
-    switches (VecPPOTrainer._decide); the handle's mode is restored after each call, so the stop predictors keep theirs."""
-    N, A = env.num_envs, core.n_act
-    wide = ops.get_lstm_arith(env.device) == "fp16x3" and _out_of_range(kind, core)[2]
-    nan = torch.zeros(1, dtype=torch.int64, device=env.device)
-    live = torch.ones(N, dtype=torch.bool, device=env.device)
-    state = core.zero_state(N) if kind == "lstm" else None
-    work, calls = {}, [0]
+class _StopRules:
+    """The stop rules of one evaluate() call -- the PPOV2.0 ThresholdController and the PPOV2.1 PeakAndStopPredictor, each on the host
+    or on the device -- behind one loop body, step().  Resets the controller.  `replay` is true while some rule given is NOT on the
+    device: the fused path then walks a chunk's records through step(); otherwise first_hits() of the chunk's scan is all it needs."""
 
-    def probs(obs):
-        if calls[0]:
-            live.logical_and_(env.done <= 0.5)       # env.done of the previous step (stale before the first one)
-        calls[0] += 1
-        with ops.lstm_arith("bf16x6", env.device) if wide else contextlib.nullcontext():
-            if kind == "lstm":
-                logits = core.step(obs, state[0], state[1], work=work)[:, :A]
-            else:
-                logits = core.heads(obs.contiguous())[:, :A]
-        nan.add_((torch.isnan(logits).any(1) & live).sum())
-        return logits
+    def __init__(self, controller, peak_stop, window_size_v21, N, device, peak_stop_device, threshold_device):
+        self.controller, self.peak_stop, self.window, self.N, self.device = controller, peak_stop, window_size_v21, N, device
+        if controller is not None:
+            controller.reset()
+        self.peak_pred = torch.full((N,), float("nan"), dtype=torch.float64, device=device)
+        self.traj = torch.zeros(N, window_size_v21, dtype=torch.float64, device=device) if peak_stop is not None else None
+        self.dps = _DevicePeakStop(peak_stop, window_size_v21, N, device) if peak_stop_device and peak_stop is not None else None
+        self.dth = _DeviceThreshold(controller, N, device) if threshold_device and controller is not None else None
+        self.any = controller is not None or peak_stop is not None
+        self.replay = (controller is not None and self.dth is None) or (peak_stop is not None and self.dps is None)
+        self.peak_hit = self.thr_hit = self.peak_c = None
 
-    return probs, nan
+    def scan(self, series, active, t0, want_steps):
+        """The device rules over series f32 [N, k] (any strides), the concentrations of steps t0 + 1 .. t0 + k; their outputs are kept
+        for step() and first_hits().  active bool [N]: every active env has t0 steps behind it.  want_steps: step() will be called."""
+        if self.dps is None and self.dth is None:
+            return
+        active = active.to(torch.uint8)
+        if self.dps is not None:
+            self.peak_hit, self.peak_c, self.prob_c = self.dps.scan(series, active)
+        if self.dth is not None:
+            self.thr_hit, self.thr_stop, _ = self.dth.scan(series, active, t0, want_steps=want_steps)
+
+    def step(self, i, t, conc, active):
+        """The loop body (PPOV2.0/evaluate_with_lstm.py:84-92, PPOV2.1/evaluate_with_lstm.py:69-77) at step t, column i of the last
+        scan: conc f32 [N], the concentration record -> stop_now bool [N].  Host rules advance by this step."""
+        controller, traj = self.controller, self.traj
+        cur = conc.to(torch.float64) * 100.0                   # conc_field at the agent
+        stop_now = torch.zeros(self.N, dtype=torch.bool, device=self.device)
+        if self.dth is not None:
+            stop_now |= self.thr_stop[:, i] != 0
+        elif controller is not None:
+            controller.push(cur)
+            if t % 10 == 0:
+                controller.update_threshold(active)
+            stop_now |= controller.should_stop(cur, t)
+        peak = prob = None
+        if self.dps is not None:                               # NaN (no hit) until the env's window is full
+            peak, prob = self.peak_c[:, i], self.prob_c[:, i]
+        elif self.peak_stop is not None:
+            self.traj = traj = torch.roll(traj, -1, dims=1)
+            traj[:, -1] = cur
+            if t >= self.window:
+                peak, prob = self.peak_stop((traj / 100.0).to(F32))
+        if prob is not None:
+            hit = prob > 0.8
+            self.peak_pred = torch.where(hit & active, peak.to(torch.float64), self.peak_pred)   # recorded whenever the LSTM stopped it (:85-87)
+            stop_now |= hit
+        return stop_now
+
+    def first_hits(self, k):
+        """(at_peak, at_thr) of the last scan over k steps: per env the chunk step of each device rule's first hit as i64 [N], k where
+        it has none; the plain int k for a rule that is not there."""
+        return tuple(k if hit is None else torch.where(hit >= 0, hit.to(torch.int64), k) for hit in (self.peak_hit, self.thr_hit))
+
+    def finish(self, out):
+        if self.dth is not None:
+            self.controller.current_threshold = self.dth.thr
+        if self.peak_stop is not None:
+            out["peak_pred"] = self.peak_pred.cpu().numpy()
+        return out
+
+
+class _Episodes:
+    """Per env of an evaluate() call: whether its episode still runs, and the step, the position and the cause of its end.  Torch
+    tensor operations only."""
+
+    def __init__(self, N, device):
+        self.active = torch.ones(N, dtype=torch.bool, device=device)
+        self.steps = torch.zeros(N, dtype=torch.int64, device=device)
+        self.stopped = torch.zeros(N, dtype=torch.bool, device=device)
+        self.final_pos = torch.zeros(N, 2, dtype=torch.float64, device=device)
+        self.rows = torch.arange(N, device=device)
+        self.cols = self.rows[:0]
+
+    def end(self, ended, t, by_rule, pos_end):
+        """The episodes `ended` (bool [N], all of them active) end with step t (an int, or i64 [N]) at pos_end f64 [N, 2]; by_rule
+        bool [N] or None: a stop rule fired on that step (the reference sets the flag whenever the controller fires on the last step)."""
+        self.steps = torch.where(ended, t, self.steps)
+        if by_rule is not None:
+            self.stopped |= ended & by_rule
+        self.final_pos = torch.where(ended[:, None], pos_end, self.final_pos)
+        self.active ^= ended                      # `ended` lies within `active`: clears exactly those
+
+    def end_chunk(self, t0, k, done_c, obs, pos, at_peak, at_thr, peak_c=None, peak_pred=None):
+        """end() for the k steps t0 + 1 .. t0 + k at once: an episode ends at min(first done record, each rule's first hit).  done_c
+        bool [N, k], obs [N, k, D], pos [N, k, 2]: the chunk's records; at_peak, at_thr: _StopRules.first_hits(k); peak_c f32 [N, k] or
+        None: the peak-stop rule's peaks.  Returns peak_pred with the peak of every episode that rule ended."""
+        rows = self.rows
+        if self.cols.numel() != k:
+            self.cols = torch.arange(k, device=rows.device)
+        at_done = torch.where(done_c, self.cols, k).amin(1)                           # k = none in this chunk
+        hits = [a for a in (at_peak, at_thr) if torch.is_tensor(a)]
+        at_hit = torch.minimum(*hits) if len(hits) == 2 else hits[0] if hits else None
+        first = at_done if at_hit is None else torch.minimum(at_done, at_hit)
+        ended = self.active & (first < k)
+        if peak_c is not None:
+            by_peak = ended & (at_peak <= first)      # the peak-stop rule fired on the episode's last step (alone or beside the others)
+        first = first.clamp(max=k - 1)
+        pos_end = obs[rows, first, :2].to(torch.float64) * 500.0                      # the record is the terminal obs where done
+        if at_hit is not None:
+            pos_end = torch.where((ended & (at_done <= at_hit))[:, None], pos_end, pos[rows, first].to(torch.float64))
+        if peak_c is not None:
+            peak_pred = torch.where(by_peak, peak_c[rows, first].to(torch.float64), peak_pred)
+        self.end(ended, first + (t0 + 1), None if at_hit is None else at_hit <= at_done, pos_end)
+        return peak_pred
+
+    def metrics(self, src, limit, last_pos, success_distance):
+        """The reference's metrics dict against the sources src f64 [N, 2].  Episodes still active were cut off by `max_steps`:
+        they took `limit` steps and stand at last_pos [N, 2]."""
+        final_pos = torch.where(self.active[:, None], last_pos.to(torch.float64), self.final_pos)
+        steps = torch.where(self.active, limit, self.steps)
+        deviation = torch.linalg.norm(final_pos - src, dim=1)
+        return {"deviations": deviation.cpu().numpy(), "steps": steps.cpu().numpy(),
+                "success": (deviation <= success_distance).cpu().numpy(), "stopped_early": self.stopped.cpu().numpy()}
+
+
+def _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, threshold_device, max_steps):
+    """Resets the env, then the controller -> (source positions, _Episodes, _StopRules, step limit)"""
+    env.reset()
+    _, src, _, _ = env.peek()
+    rules = _StopRules(controller, peak_stop, window_size_v21, env.num_envs, env.device, peak_stop_device, threshold_device)
+    return src.clone(), _Episodes(env.num_envs, env.device), rules, max_steps or env.max_steps
 
 
 @torch.no_grad()
@@ -351,20 +399,15 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     chunk's records).  A NaN logit of a policy object raises RuntimeError("NaN in probs").  A policy_probs function takes
     neither fused=True nor chunk.
     peak_stop_device=True: the PPOV2.1 rule runs on uav_peak_stop_scan -- one scan over all sliding windows of a fused chunk's
-    records (an episode then ends at min(first done record, first hit), no replay loop; a ThresholdController, if also given,
-    keeps its replay), or one scan of steps = 1 per env step on the step-wise path.  Same decisions and metrics as the default,
-    which evaluates the predictor through uav_lstm_fwd + uav_gemm_f32 (peak_pred agrees to the f32 kernels' rounding); a
-    predictor the kernel does not cover (peak_stop_refusal) raises RuntimeError.
+    records, or one scan of steps = 1 per env step on the step-wise path.  Same decisions and metrics as the default, which
+    evaluates the predictor through uav_lstm_fwd + uav_gemm_f32 (peak_pred agrees to the f32 kernels' rounding); a predictor the
+    kernel does not cover (peak_stop_refusal) raises RuntimeError.
     threshold_device=True: the PPOV2.0 rule runs on the device -- per fused chunk uav_threshold_windows, ONE batched call of the
-    controller's predictor over the chunk's windows, and uav_threshold_rule (first hit per env), or the rule kernel with steps = 1
-    per env step on the step-wise path (windows and predictor on update steps only).  With every rule given on the device there
-    is no replay loop: an episode ends at min(first done record, threshold hit, peak-stop hit).  Same decisions and metrics as
-    the default (the window mean is summed in np.mean's order, as the reference's, where the host replay uses torch's sum).  On
-    return controller.current_threshold holds the device's thresholds (f64 [N], NaN = None; on the fused path an env that ended
-    inside a chunk has the threshold of that chunk's last step)."""
-    peak_stop_device = bool(peak_stop_device) and peak_stop is not None
-    threshold_device = bool(threshold_device) and controller is not None
-    pc = _policy_core(policy_probs)
+    controller's predictor over the chunk's windows, and uav_threshold_rule, or the rule kernel with steps = 1 per env step on the
+    step-wise path (windows and predictor on update steps only).  Same decisions and metrics as the default (the window mean is
+    summed in np.mean's order, as the reference's, where the host replay uses torch's sum).  On return controller.current_threshold
+    holds the device's thresholds (f64 [N], NaN = None; an env that ended inside a fused chunk has that chunk's last)."""
+    pc, nan = policy_core(policy_probs), None
     if pc is None and fused:
         raise RuntimeError("evaluate(fused=True): a policy_probs function has no fused kernel; pass the policy object")
     if pc is None and chunk is not None:
@@ -377,204 +420,61 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
         if why is None:
             return _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
                                    chunk, peak_stop_device, threshold_device)
-        probs, nan = _stepwise_policy_probs(kind, core, env)
-        out = evaluate(probs, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
-                       peak_stop_device=peak_stop_device, threshold_device=threshold_device)
-        if int(nan.item()) > 0:
-            raise RuntimeError("NaN in probs")                                   # model.py:47-49
-        return out
-    N, dev = env.num_envs, env.device
-    obs = env.reset()
-    _, src, _, _ = env.peek()
-    src = src.clone()
-    active = torch.ones(N, dtype=torch.bool, device=dev)
-    steps = torch.zeros(N, dtype=torch.int64, device=dev)
-    stopped = torch.zeros(N, dtype=torch.bool, device=dev)
-    final_pos = torch.zeros(N, 2, dtype=torch.float64, device=dev)
-    peak_pred = torch.full((N,), float("nan"), dtype=torch.float64, device=dev)
-    if controller is not None:
-        controller.reset()
-    traj = torch.zeros(N, window_size_v21, dtype=torch.float64, device=dev) if peak_stop is not None else None
-    dps = _DevicePeakStop(peak_stop, window_size_v21, N, dev) if peak_stop_device else None
-    dth = _DeviceThreshold(controller, N, dev) if threshold_device else None
-    limit = max_steps or env.max_steps
+        policy_probs, nan = stepwise_policy_probs(kind, core, env)
+    src, ep, rules, limit = _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, threshold_device, max_steps)
+    N, obs = env.num_envs, env.obs
     for t in range(1, limit + 1):
         act = torch.argmax(policy_probs(obs), dim=1).to(torch.int32)
         obs, _, done, _ = env.step(act, None if noise is None else noise[t - 1])
         done_b = done > 0.5
-        cur = torch.where(done_b, env.term_obs[:, 2], obs[:, 2]).to(torch.float64) * 100.0      # conc_field at the agent
+        conc = torch.where(done_b, env.term_obs[:, 2], obs[:, 2])
         pos_now, _, _, _ = env.peek()
         pos_end = torch.where(done_b[:, None], env.term_obs[:, :2].to(torch.float64) * 500.0, pos_now.to(torch.float64))
-        stop_now = torch.zeros(N, dtype=torch.bool, device=dev)
-        if dth is not None:                  # one rule call of steps = 1; windows + predictor on update steps only
-            _, th_stop, _ = dth.scan(torch.where(done_b, env.term_obs[:, 2], obs[:, 2]).reshape(N, 1), active.to(torch.uint8), t - 1,
-                                     want_steps=True)
-            stop_now |= th_stop[:, 0] != 0
-        elif controller is not None:
-            controller.push(cur)
-            if t % 10 == 0:
-                controller.update_threshold(active)
-            stop_now |= controller.should_stop(cur, t)
-        if dps is not None:                  # one scan of steps = 1: NaN (no hit) until the env's window is full
-            _, peak, prob = dps.scan(torch.where(done_b, env.term_obs[:, 2], obs[:, 2]).reshape(N, 1))
-            hit = prob[:, 0] > 0.8
-            peak_pred = torch.where(hit & active, peak[:, 0].to(torch.float64), peak_pred)
-            stop_now |= hit
-        elif peak_stop is not None:
-            traj = torch.roll(traj, -1, dims=1)
-            traj[:, -1] = cur
-            if t >= window_size_v21:
-                peak, prob = peak_stop((traj / 100.0).to(F32))
-                hit = prob > 0.8
-                peak_pred = torch.where(hit & active, peak.to(torch.float64), peak_pred)       # recorded whenever the LSTM stopped it (:85-87)
-                stop_now |= hit
-        ended = active & (done_b | stop_now)
-        steps = torch.where(ended, torch.full_like(steps, t), steps)
-        stopped |= ended & stop_now          # the reference sets the flag whenever the controller fires on the last step
-        final_pos = torch.where(ended[:, None], pos_end, final_pos)
-        active &= ~ended
-        if t % 16 == 0 and not bool(active.any()):
+        # the device rules, steps = 1.  Both get `active`; the peak-stop scan once ran over all envs, which changes nothing that is read:
+        # an inactive env never becomes active again, its hit is masked by `ended = active & ...`, peak_pred is gated by `hit & active`
+        rules.scan(conc.reshape(N, 1), ep.active, t - 1, True)
+        stop_now = rules.step(0, t, conc, ep.active)
+        ep.end(ep.active & (done_b | stop_now), t, stop_now, pos_end)
+        if t % 16 == 0 and not bool(ep.active.any()):
             break
-    # episodes cut off by `max_steps`
-    if bool(active.any()):
-        pos_now, _, _, _ = env.peek()
-        final_pos = torch.where(active[:, None], pos_now.to(torch.float64), final_pos)
-        steps = torch.where(active, torch.full_like(steps, limit), steps)
-    if dth is not None:
-        controller.current_threshold = dth.thr
-    deviation = torch.linalg.norm(final_pos - src, dim=1)
-    out = {"deviations": deviation.cpu().numpy(), "steps": steps.cpu().numpy(),
-           "success": (deviation <= success_distance).cpu().numpy(), "stopped_early": stopped.cpu().numpy()}
-    if peak_stop is not None:
-        out["peak_pred"] = peak_pred.cpu().numpy()
-    return out
+    if nan is not None and int(nan.item()) > 0:
+        raise RuntimeError("NaN in probs")                                       # model.py:47-49
+    return rules.finish(ep.metrics(src, limit, pos_now, success_distance))
 
 
 def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance, chunk,
                     peak_stop_device=False, threshold_device=False):
     """evaluate() on uav_greedy_episodes: `chunk` steps per launch; the metrics (and the stop controllers) are computed from
-    the records with the formulas of evaluate()'s step-wise loop, so the same actions give the same arrays bit for bit.  An
-    env the kernel has ended stays frozen (no auto-reset); an env a controller stopped is passed as inactive to the next chunk.
-    peak_stop_device: the PPOV2.1 rule of a whole chunk is one uav_peak_stop_scan over the records; without a ThresholdController
-    there is then no replay loop at all -- `ended = active & (done | hit)`, `stopped |= ended & hit` restated over the chunk.
-    threshold_device: the PPOV2.0 rule of a whole chunk is uav_threshold_windows, one batched predictor call and uav_threshold_rule.
-    `replay` is true only while some rule given is NOT on the device; the replay loop then takes the device rule's per-step flags."""
-    N, dev = env.num_envs, env.device
-    H = core.hidden if kind == "lstm" else 0
-    env.reset()
-    _, src, _, _ = env.peek()
-    src = src.clone()
-    cur_obs = env.obs
-    h = torch.zeros(N, H, dtype=F32, device=dev) if H else None
-    c = torch.zeros(N, H, dtype=F32, device=dev) if H else None
-    kernel_active = torch.ones(N, dtype=torch.uint8, device=dev)
-    nan_count = torch.zeros(1, dtype=torch.int32, device=dev)
-    active = torch.ones(N, dtype=torch.bool, device=dev)
-    steps = torch.zeros(N, dtype=torch.int64, device=dev)
-    stopped = torch.zeros(N, dtype=torch.bool, device=dev)
-    final_pos = torch.zeros(N, 2, dtype=torch.float64, device=dev)
-    peak_pred = torch.full((N,), float("nan"), dtype=torch.float64, device=dev)
-    if controller is not None:
-        controller.reset()
-    traj = torch.zeros(N, window_size_v21, dtype=torch.float64, device=dev) if peak_stop is not None else None
-    dps = _DevicePeakStop(peak_stop, window_size_v21, N, dev) if peak_stop_device else None
-    dth = _DeviceThreshold(controller, N, dev) if threshold_device else None
-    replay = (controller is not None and dth is None) or (peak_stop is not None and dps is None)
-    limit = max_steps or env.max_steps
-    chunk = int(chunk or (50 if controller is not None or peak_stop is not None else 250))
-    rows = torch.arange(N, device=dev)
-    last_pos = None
+    the records by the step-wise loop's own _StopRules.step / _Episodes.end, so the same actions give the same arrays bit for
+    bit.  An env the kernel has ended stays frozen (no auto-reset); an env a rule stopped goes into the next chunk inactive.
+    Only while some rule given is NOT on the device (rules.replay) are the records walked step by step, the device rules' per-step
+    flags among them; otherwise -- every rule on the device, or none given -- a chunk is one _Episodes.end_chunk."""
+    src, ep, rules, limit = _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, threshold_device, max_steps)
+    run = GreedyRun(kind, core, env)
+    chunk = int(chunk or (50 if rules.any else 250))
     t0 = 0
     while t0 < limit:
         k = min(chunk, limit - t0)
-        recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, env.obs_dim, dtype=F32, device=dev),
-                "pos": torch.empty(N, k, 2, dtype=F32, device=dev), "flags": torch.empty(N, k, dtype=torch.uint8, device=dev)}
-        nz = None if noise is None else noise[t0:t0 + k].transpose(0, 1).contiguous()
-        ops.greedy_episodes(env.state, N, env.cfg(), core.flat, H, k, cur_obs, h, c, kernel_active, recs, noise=nz,
-                            nan_count=nan_count)
+        recs = run.chunk(t0, k, noise)
         done_c = (recs["flags"] & 1) != 0
-        if dps is not None or dth is not None:   # `active` is kernel_active as the launch found it (the kernel clears it at `done`)
-            was_active = active.to(torch.uint8)
-        if dps is not None:
-            first_hit, peak_c, prob_c = dps.scan(recs["obs"][:, :, 2], was_active)
-        if dth is not None:                      # every active env has t0 steps behind it
-            th_hit, th_stop, _ = dth.scan(recs["obs"][:, :, 2], was_active, t0, want_steps=replay)
-        if replay:
-            for i in range(k):                   # evaluate()'s loop body, step t = t0 + i + 1, on the records
-                t = t0 + i + 1
+        conc = recs["obs"][:, :, 2]                  # the record is the terminal obs where done
+        rules.scan(conc, ep.active, t0, rules.replay)   # `active` is the kernel's as the launch found it (the kernel clears it at `done`)
+        if rules.replay:
+            for i in range(k):                       # evaluate()'s loop body, step t = t0 + i + 1, on the records
                 done_b = done_c[:, i]
-                cur = recs["obs"][:, i, 2].to(torch.float64) * 100.0          # the record is the terminal obs where done
-                pos_end = torch.where(done_b[:, None], recs["obs"][:, i, :2].to(torch.float64) * 500.0,
-                                      recs["pos"][:, i].to(torch.float64))
-                stop_now = torch.zeros(N, dtype=torch.bool, device=dev)
-                if dth is not None:
-                    stop_now |= th_stop[:, i] != 0
-                elif controller is not None:
-                    controller.push(cur)
-                    if t % 10 == 0:
-                        controller.update_threshold(active)
-                    stop_now |= controller.should_stop(cur, t)
-                if dps is not None:
-                    hit = prob_c[:, i] > 0.8
-                    peak_pred = torch.where(hit & active, peak_c[:, i].to(torch.float64), peak_pred)
-                    stop_now |= hit
-                elif peak_stop is not None:
-                    traj = torch.roll(traj, -1, dims=1)
-                    traj[:, -1] = cur
-                    if t >= window_size_v21:
-                        peak, prob = peak_stop((traj / 100.0).to(F32))
-                        hit = prob > 0.8
-                        peak_pred = torch.where(hit & active, peak.to(torch.float64), peak_pred)
-                        stop_now |= hit
-                ended = active & (done_b | stop_now)
-                steps = torch.where(ended, torch.full_like(steps, t), steps)
-                stopped |= ended & stop_now
-                final_pos = torch.where(ended[:, None], pos_end, final_pos)
-                active &= ~ended
-            kernel_active &= active.to(torch.uint8)
-        elif dps is not None or dth is not None:  # an episode ends at min(first done record, each rule's first hit); k = none in this chunk
-            at_done = torch.where(done_c.any(1), done_c.to(torch.int32).argmax(1), k)
-            at_peak = torch.where(first_hit >= 0, first_hit.to(torch.int64), k) if dps is not None else torch.full_like(at_done, k)
-            at_hit = at_peak if dth is None else torch.minimum(at_peak, torch.where(th_hit >= 0, th_hit.to(torch.int64), k))
-            first = torch.minimum(at_done, at_hit)
-            ended = active & (first < k)
-            by_rule = ended & (at_hit <= at_done)
-            by_peak = ended & (at_peak <= first)  # the peak-stop rule fired on the episode's last step (alone or beside the others)
-            first = first.clamp(max=k - 1)
-            pos_end = torch.where((ended & (at_done <= at_hit))[:, None], recs["obs"][rows, first, :2].to(torch.float64) * 500.0,
-                                  recs["pos"][rows, first].to(torch.float64))
-            steps = torch.where(ended, first + (t0 + 1), steps)
-            stopped |= by_rule
-            if dps is not None:
-                peak_pred = torch.where(by_peak, peak_c[rows, first].to(torch.float64), peak_pred)
-            final_pos = torch.where(ended[:, None], pos_end, final_pos)
-            active &= ~ended
-            kernel_active &= active.to(torch.uint8)
-        else:                                    # no controller: an episode ends exactly at its first done record
-            ended = active & done_c.any(1)
-            first = done_c.to(torch.int32).argmax(1)
-            pos_end = recs["obs"][rows, first, :2].to(torch.float64) * 500.0
-            steps = torch.where(ended, (first + (t0 + 1)).to(torch.int64), steps)
-            final_pos = torch.where(ended[:, None], pos_end, final_pos)
-            active &= ~ended
-        last_pos = recs["pos"][:, k - 1]
+                pos_end = torch.where(done_b[:, None], recs["obs"][:, i, :2].to(torch.float64) * 500.0, recs["pos"][:, i].to(torch.float64))
+                stop_now = rules.step(i, t0 + i + 1, conc[:, i], ep.active)
+                ep.end(ep.active & (done_b | stop_now), t0 + i + 1, stop_now, pos_end)
+        else:
+            rules.peak_pred = ep.end_chunk(t0, k, done_c, recs["obs"], recs["pos"], *rules.first_hits(k), rules.peak_c, rules.peak_pred)
+        if rules.any:
+            run.retire(ep.active)
+        last_pos = recs["pos"][:, k - 1]             # episodes cut off by `max_steps` are still active, so stepped through the last record
         t0 += k
-        if not bool(active.any()):
+        if not bool(ep.active.any()):
             break
-    if int(nan_count.item()) > 0:
-        raise RuntimeError("NaN in probs")                                       # model.py:47-49
-    # episodes cut off by `max_steps`: still active, so stepped through the last record
-    if bool(active.any()):
-        final_pos = torch.where(active[:, None], last_pos.to(torch.float64), final_pos)
-        steps = torch.where(active, torch.full_like(steps, limit), steps)
-    if dth is not None:
-        controller.current_threshold = dth.thr
-    deviation = torch.linalg.norm(final_pos - src, dim=1)
-    out = {"deviations": deviation.cpu().numpy(), "steps": steps.cpu().numpy(),
-           "success": (deviation <= success_distance).cpu().numpy(), "stopped_early": stopped.cpu().numpy()}
-    if peak_stop is not None:
-        out["peak_pred"] = peak_pred.cpu().numpy()
-    return out
+    run.raise_on_nan()
+    return rules.finish(ep.metrics(src, limit, last_pos, success_distance))
 
 
 def load_lstm_policy(path, device="cuda"):

@@ -9,8 +9,8 @@ import numpy as np
 import torch
 
 from config import ENV_VARIANT, SEED
-from evaluate_with_lstm import _policy_core, _stepwise_policy_probs, fused_refusal, load_lstm_policy
-from uavppo import ops
+from evaluate_with_lstm import load_lstm_policy
+from uavppo.greedy import GreedyRun, fused_refusal, policy_core, stepwise_policy_probs
 from uavppo.vec_env import VecMethaneEnv
 
 NOT_STEPPED = 4          # bit 2 of a record's flags (include/uavppo.h, uav_greedy_episodes): the env was not stepped, act = -1
@@ -50,36 +50,23 @@ def load_policy(path, device="cuda"):
 def greedy_records(policy, env, max_steps=None, chunk=250):
     """One greedy episode per environment of `env`: (reset observations [N, obs_dim], lists of per-chunk obs / act / flags
     records) as host arrays, in the record format of uav_greedy_episodes whichever path produced them."""
-    kind, core = _policy_core(policy)
+    kind, core = policy_core(policy)
     N, dev = env.num_envs, env.device
     limit = max_steps or env.max_steps
     env.reset()
     cur_obs0 = env.obs.cpu().numpy().copy()
     obs_c, act_c, flags_c = [], [], []
-    if fused_refusal(policy, env) is None:
-        H = core.hidden if kind == "lstm" else 0
-        h = torch.zeros(N, H, dtype=torch.float32, device=dev) if H else None
-        c = torch.zeros(N, H, dtype=torch.float32, device=dev) if H else None
-        active = torch.ones(N, dtype=torch.uint8, device=dev)
-        nan_count = torch.zeros(1, dtype=torch.int32, device=dev)
-        t0 = 0
-        while t0 < limit:
-            k = min(chunk, limit - t0)
-            recs = {"act": torch.empty(N, k, dtype=torch.int32, device=dev), "obs": torch.empty(N, k, env.obs_dim, dtype=torch.float32, device=dev),
-                    "pos": torch.empty(N, k, 2, dtype=torch.float32, device=dev), "flags": torch.empty(N, k, dtype=torch.uint8, device=dev)}
-            ops.greedy_episodes(env.state, N, env.cfg(), core.flat, H, k, env.obs, h, c, active, recs, nan_count=nan_count)
-            obs_c.append(recs["obs"].cpu().numpy()), act_c.append(recs["act"].cpu().numpy()), flags_c.append(recs["flags"].cpu().numpy())
-            t0 += k
-            if not bool(active.any()):
-                break
-        if int(nan_count.item()) > 0:
-            raise RuntimeError("NaN in probs")
-    else:
-        probs, nan = _stepwise_policy_probs(kind, core, env)
-        active = torch.ones(N, dtype=torch.bool, device=dev)
-        obs, t = env.obs, 0
-        while t < limit:
-            k = min(chunk, limit - t)
+    run = GreedyRun(kind, core, env) if fused_refusal(policy, env) is None else None
+    if run is None:
+        probs, nan = stepwise_policy_probs(kind, core, env)
+        active, obs = torch.ones(N, dtype=torch.bool, device=dev), env.obs
+    t0 = 0
+    while t0 < limit:
+        k = min(chunk, limit - t0)
+        if run is not None:
+            recs = run.chunk(t0, k)
+            ro, ra, rf, active = recs["obs"], recs["act"], recs["flags"], run.active
+        else:
             ro = torch.zeros(N, k, env.obs_dim, dtype=torch.float32, device=dev)
             ra = torch.full((N, k), -1, dtype=torch.int32, device=dev)
             rf = torch.full((N, k), NOT_STEPPED, dtype=torch.uint8, device=dev)
@@ -91,12 +78,14 @@ def greedy_records(policy, env, max_steps=None, chunk=250):
                 ra[:, i] = torch.where(active, act, ra[:, i])
                 rf[:, i] = torch.where(active, env.flags & 3, rf[:, i])
                 active = active & ~done_b
-            obs_c.append(ro.cpu().numpy()), act_c.append(ra.cpu().numpy()), flags_c.append(rf.cpu().numpy())
-            t += k
-            if not bool(active.any()):
-                break
-        if int(nan.item()) > 0:
-            raise RuntimeError("NaN in probs")
+        obs_c.append(ro.cpu().numpy()), act_c.append(ra.cpu().numpy()), flags_c.append(rf.cpu().numpy())
+        t0 += k
+        if not bool(active.any()):
+            break
+    if run is not None:
+        run.raise_on_nan()
+    elif int(nan.item()) > 0:
+        raise RuntimeError("NaN in probs")
     return cur_obs0, obs_c, act_c, flags_c
 
 
@@ -107,7 +96,7 @@ def generate_expert_data(policy="ppo_model.pth", num_episodes=100, variant=ENV_V
     `seed`; every (state, action) pair goes to `out` (None: not written).  Returns (states f32 [M, obs_dim], actions i64 [M])."""
     if isinstance(policy, (str, bytes)) or hasattr(policy, "__fspath__"):
         policy = load_policy(policy, device)
-    _, core = _policy_core(policy)
+    _, core = policy_core(policy)
     trend_k = getattr(core, "obs_dim", 6) - 6
     env = VecMethaneEnv(num_episodes, variant, core.device, seed=seed, trend_k=trend_k)
     states, actions = expert_pairs(*greedy_records(policy, env, max_steps))

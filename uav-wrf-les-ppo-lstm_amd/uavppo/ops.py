@@ -871,27 +871,44 @@ def rollout_mlp(env_state, n_env, cfg, params, horizon, it, cur_obs, bufs, last_
         _t.record()
 
 
-def greedy_episodes(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise=None, nan_count=None):
-    """`steps` steps of greedy evaluation episodes on the fused rollout kernels (uav_greedy_episodes): argmax action, no
-    auto-reset, ended / inactive envs frozen.  hidden = 0 (h, c None): the reference's MLP; 64 / 128: the single-layer LSTM.
-    cur_obs [N,D], h, c [N,H], active u8 [N] are in/out; recs: dict act i32 [N,steps], obs [N,steps,D], pos [N,steps,2],
-    flags u8 [N,steps] (bit0 done, bit1 reached, bit2 not stepped); noise f64 [N,steps,2] or None.  D = 6 + cfg.trend_k
-    (the LSTM kernels; the MLP kernels take trend_k = 0 only)."""
+def greedy_recs(n_env, steps, obs_dim, device):
+    """The record tensors of one greedy launch: act i32 [N,steps], obs [N,steps,obs_dim], pos [N,steps,2], flags u8 [N,steps]."""
+    N, k = n_env, steps
+    return {"act": torch.empty(N, k, dtype=I32, device=device), "obs": torch.empty(N, k, obs_dim, dtype=F32, device=device),
+            "pos": torch.empty(N, k, 2, dtype=F32, device=device), "flags": torch.empty(N, k, dtype=U8, device=device)}
+
+
+def _greedy(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise, nan_count, rule=None, stop_win=None,
+            stop_cnt=None, rule_val=None):
+    """uav_greedy_episodes, or with a `rule` uav_greedy_episodes_stop: the same arguments with the rule's four behind them."""
     N, T, D = n_env, steps, 6 + cfg.trend_k
     kind = 0 if hidden == 0 else 1
     if nan_count is None:
         nan_count = torch.zeros(1, dtype=I32, device=cur_obs.device)
+    symbol, tail = "uav_greedy_episodes", ()
+    if rule is not None:
+        W = int(rule.window)
+        symbol, tail = "uav_greedy_episodes_stop", (C.byref(rule), _p(stop_win, F32, (N, W, 2), "stop_win"),
+                                                    _p(stop_cnt, I32, (N,), "stop_cnt"), _p(rule_val, F32, (N, T), "rule_val"))
     _t = KERNEL_TIMER.bracket("greedy")
-    check(lib().uav_greedy_episodes(_h(cur_obs), _p(env_state, U8, name="env state"), N, C.byref(cfg), kind,
-                                    _p(params, F32, name="params"), int(hidden), T, _p(cur_obs, F32, (N, D), "cur_obs"),
-                                    _p(h, F32, (N, hidden), "h") if kind else None,
-                                    _p(c, F32, (N, hidden), "c") if kind else None,
-                                    _p(active, U8, (N,), "active"), _p(noise, F64, (N, T, 2), "noise"),
-                                    _p(recs["act"], I32, (N, T), "act"), _p(recs["obs"], F32, (N, T, D), "obs"),
-                                    _p(recs["pos"], F32, (N, T, 2), "pos"), _p(recs["flags"], U8, (N, T), "flags"),
-                                    _p(nan_count, I32, (1,), "nan_count"), _stream()), "uav_greedy_episodes")
+    check(getattr(lib(), symbol)(_h(cur_obs), _p(env_state, U8, name="env state"), N, C.byref(cfg), kind,
+                                 _p(params, F32, name="params"), int(hidden), T, _p(cur_obs, F32, (N, D), "cur_obs"),
+                                 _p(h, F32, (N, hidden), "h") if kind else None, _p(c, F32, (N, hidden), "c") if kind else None,
+                                 _p(active, U8, (N,), "active"), _p(noise, F64, (N, T, 2), "noise"),
+                                 _p(recs["act"], I32, (N, T), "act"), _p(recs["obs"], F32, (N, T, D), "obs"),
+                                 _p(recs["pos"], F32, (N, T, 2), "pos"), _p(recs["flags"], U8, (N, T), "flags"),
+                                 _p(nan_count, I32, (1,), "nan_count"), *tail, _stream()), symbol)
     if _t is not None:
         _t.record()
+
+
+def greedy_episodes(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise=None, nan_count=None):
+    """`steps` steps of greedy evaluation episodes on the fused rollout kernels (uav_greedy_episodes): argmax action, no
+    auto-reset, ended / inactive envs frozen.  hidden = 0 (h, c None): the reference's MLP; 64 / 128: the single-layer LSTM.
+    cur_obs [N,D], h, c [N,H], active u8 [N] are in/out; recs: dict act i32 [N,steps], obs [N,steps,D], pos [N,steps,2],
+    flags u8 [N,steps] (bit0 done, bit1 reached, bit2 not stepped; greedy_recs allocates it); noise f64 [N,steps,2] or None.
+    D = 6 + cfg.trend_k (the LSTM kernels; the MLP kernels take trend_k = 0 only)."""
+    _greedy(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise, nan_count)
 
 
 STOP_WIN_MAX = 16
@@ -912,23 +929,8 @@ def greedy_episodes_stop(env_state, n_env, cfg, params, hidden, steps, cur_obs, 
     stop_win f32 [N, window, 2] (the env's last positions, oldest first) and stop_cnt i32 [N] (valid rows) are in/out and
     carry the window across calls (zeros start an episode); rule_val: optional f32 [N, steps], pos_std of every stepped step
     with a full window, NaN otherwise."""
-    N, T, W, D = n_env, steps, int(rule.window), 6 + cfg.trend_k
-    kind = 0 if hidden == 0 else 1
-    if nan_count is None:
-        nan_count = torch.zeros(1, dtype=I32, device=cur_obs.device)
-    _t = KERNEL_TIMER.bracket("greedy")
-    check(lib().uav_greedy_episodes_stop(_h(cur_obs), _p(env_state, U8, name="env state"), N, C.byref(cfg), kind,
-                                         _p(params, F32, name="params"), int(hidden), T, _p(cur_obs, F32, (N, D), "cur_obs"),
-                                         _p(h, F32, (N, hidden), "h") if kind else None,
-                                         _p(c, F32, (N, hidden), "c") if kind else None,
-                                         _p(active, U8, (N,), "active"), _p(noise, F64, (N, T, 2), "noise"),
-                                         _p(recs["act"], I32, (N, T), "act"), _p(recs["obs"], F32, (N, T, D), "obs"),
-                                         _p(recs["pos"], F32, (N, T, 2), "pos"), _p(recs["flags"], U8, (N, T), "flags"),
-                                         _p(nan_count, I32, (1,), "nan_count"), C.byref(rule),
-                                         _p(stop_win, F32, (N, W, 2), "stop_win"), _p(stop_cnt, I32, (N,), "stop_cnt"),
-                                         _p(rule_val, F32, (N, T), "rule_val"), _stream()), "uav_greedy_episodes_stop")
-    if _t is not None:
-        _t.record()
+    _greedy(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise, nan_count, rule, stop_win, stop_cnt,
+            rule_val)
 
 
 def stop_stability(rule, pos, obs2, stop_win, stop_cnt, active=None, stop=None, value=None):
@@ -1007,6 +1009,17 @@ def peak_stop_param_count(hidden=32):
     return n
 
 
+def _series_hist(series, hist, cnt, window, cnt_name):
+    """(N, steps, window, hist pointer) of a rule call's `series` view and its [N, window - 1] history; `cnt` is the envs' i32 counter."""
+    if series.dim() != 2 or series.dtype != F32 or not series.is_cuda:
+        raise RuntimeError(f"series: expected a 2-D GPU float32 tensor (view), got {tuple(series.shape)} {series.dtype}")
+    N, W = int(series.shape[0]), int(window)
+    hist_p = _p(hist, F32, (N, max(W - 1, 0)), "hist")
+    if W == 1:          # an [N, 0] tensor has no storage, the C ABI refuses a NULL hist: any valid pointer serves, none of it is touched
+        hist_p = _p(cnt, I32, (N,), cnt_name)
+    return N, int(series.shape[1]), W, hist_p
+
+
 def peak_stop_scan(params, hidden, window, series, hist, hist_cnt, active=None, prob_min=0.8, want_values=True):
     """The PeakAndStopPredictor over every sliding window of a chunk (uav_peak_stop_scan).  params: the flat buffer of
     PeakAndStopPredictor.flat_params(); series: f32 [N, steps] view of any strides (recs["obs"][:, :, 2] as it is): env e's LSTM
@@ -1014,18 +1027,12 @@ def peak_stop_scan(params, hidden, window, series, hist, hist_cnt, active=None, 
     episode); active u8 [N] or None (all).  Returns (first_hit i32 [N]: first step whose window is full and has stop_prob >
     prob_min, -1 if none; peak, prob f32 [N, steps], NaN where the window is not full or the env inactive -- None with
     want_values=False)."""
-    if series.dim() != 2 or series.dtype != F32 or not series.is_cuda:
-        raise RuntimeError(f"series: expected a 2-D GPU float32 tensor (view), got {tuple(series.shape)} {series.dtype}")
-    N, T = int(series.shape[0]), int(series.shape[1])
-    W = int(window)
+    N, T, W, hist_p = _series_hist(series, hist, hist_cnt, window, "hist_cnt")
     P = peak_stop_param_count(hidden)
     dev = series.device
     peak = torch.empty(N, T, dtype=F32, device=dev) if want_values else None
     prob = torch.empty(N, T, dtype=F32, device=dev) if want_values else None
     first_hit = torch.empty(N, dtype=I32, device=dev)
-    hist_p = _p(hist, F32, (N, max(W - 1, 0)), "hist")
-    if W == 1:          # an [N, 0] tensor has no storage, the C ABI refuses a NULL hist: any valid pointer serves, none of it is touched
-        hist_p = _p(hist_cnt, I32, (N,), "hist_cnt")
     _t = KERNEL_TIMER.bracket("peak_stop_scan")
     check(lib().uav_peak_stop_scan(_h(series), _p(params, F32, (P,), "params"), int(hidden), W, C.c_void_p(series.data_ptr()),
                                    int(series.stride(0)), int(series.stride(1)), N, T, _p(active, U8, (N,), "active"),
@@ -1043,23 +1050,13 @@ def threshold_slots(steps, every=10):
     return (int(steps) + int(every) - 1) // int(every)
 
 
-def _threshold_series(series, hist, step_cnt, window):
-    if series.dim() != 2 or series.dtype != F32 or not series.is_cuda:
-        raise RuntimeError(f"series: expected a 2-D GPU float32 tensor (view), got {tuple(series.shape)} {series.dtype}")
-    N, W = int(series.shape[0]), int(window)
-    hist_p = _p(hist, F32, (N, max(W - 1, 0)), "hist")
-    if W == 1:          # an [N, 0] tensor has no storage, the C ABI refuses a NULL hist: any valid pointer serves, none of it is touched
-        hist_p = _p(step_cnt, I32, (N,), "step_cnt")
-    return N, int(series.shape[1]), W, hist_p
-
-
 def threshold_windows(series, hist, step_cnt, active=None, window=10, every=10, min_steps=20, lo=0.0, scale=1.0, conc_scale=100.0):
     """The ConcentrationThresholdPredictor's inputs of a chunk (uav_threshold_windows).  series: f32 [N, steps] view of any strides
     (recs["obs"][:, :, 2] as it is); hist f32 [N, window - 1] / step_cnt i32 [N]: the envs' last inputs and the steps seen before
     this call (read only); active u8 [N] or None (all).  Returns x f32 [N, S, window], S = threshold_slots(steps, every): slot s of
     env e holds the scaled window of its update step t = (step_cnt[e] // every + s + 1) * every where the call reaches it and
     t >= max(window, min_steps), zeros otherwise."""
-    N, T, W, hist_p = _threshold_series(series, hist, step_cnt, window)
+    N, T, W, hist_p = _series_hist(series, hist, step_cnt, window, "step_cnt")
     x = torch.empty(N, threshold_slots(T, every), W, dtype=F32, device=series.device)
     _t = KERNEL_TIMER.bracket("threshold_windows")
     check(lib().uav_threshold_windows(_h(series), C.c_void_p(series.data_ptr()), int(series.stride(0)), int(series.stride(1)), N, T,
@@ -1077,7 +1074,7 @@ def threshold_rule(series, hist, step_cnt, pred, thr, active=None, window=10, ev
     and step_cnt are advanced here); pred f32 [N, S]: the predictor's outputs for threshold_windows' rows; thr f64 [N] in / out:
     the threshold in force, NaN = none yet.  Returns (first_hit i32 [N]: first step of the call at which the rule fires, -1 if
     none; stop u8 [N, steps]; thr_out f64 [N, steps] -- None, None with want_steps=False)."""
-    N, T, W, hist_p = _threshold_series(series, hist, step_cnt, window)
+    N, T, W, hist_p = _series_hist(series, hist, step_cnt, window, "step_cnt")
     dev = series.device
     stop = torch.empty(N, T, dtype=U8, device=dev) if want_steps else None
     thr_out = torch.empty(N, T, dtype=F64, device=dev) if want_steps else None

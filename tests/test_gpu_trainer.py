@@ -977,3 +977,138 @@ def test_device_curriculum_equals_host_curriculum_in_the_loop():
     assert a.episodes_done > 600 and a.radius < 200.0
     # the lagged mirror the training script reads (never waits): at most one rollout behind
     assert 0 < a.episodes_lagged <= a.episodes_done
+
+
+# --------------------------------------------------------------------------------------------- rollout routes, info rows
+def test_info_rows_on_the_stepper_route_equal_the_per_call_route():
+    """log_info keeps an h = 256 stack off the fused tail: the stepper route and one uav_lstm_fwd per layer and step run the same
+    env kernel, so every buffer, the ten info columns and the carried state are BIT-identical over two rollouts in which episodes
+    end and restart (radius 200); rollout_route() names the route each trainer takes."""
+    from uavppo.trainer import VecPPOTrainer
+    mk = lambda **kw: VecPPOTrainer(72, 10, "lstm", hidden=256, layers=2, variant="v2.1", device=DEV, seed=5, trend_k=2, epochs=2, **kw)
+    a, b = mk(log_info=True), mk(log_info=True)
+    b.use_stepper = False
+    for tr in (a, b):
+        tr.radius = 200.0
+        tr.reset()
+    assert a.rollout_route() == "stepper" and b.rollout_route() == "per_call" and mk().rollout_route() == "tail"
+    for it in range(2):
+        a.collect(); b.collect()
+        for k in a.buf:
+            assert torch.equal(a.buf[k], b.buf[k]), (it, k)
+        assert torch.equal(a.info, b.info), it
+        assert torch.equal(a.h, b.h) and torch.equal(a.c, b.c), it
+        a.iteration += 1; b.iteration += 1
+    assert a.buf["done"].sum() > 0 and a.info.abs().sum() > 0
+
+
+def test_info_rows_of_the_stepwise_lstm_rollout_match_the_fused_kernel():
+    """The info columns (reward parts | obs[2] | agent x, y | source x, y) of _collect_stepwise_lstm against the fused rollout
+    kernel's on the same injected actions and noise, to the 1e-4 the MLP's two routes are held to
+    (test_fused_mlp_rollout_matches_oracle_simulation); episodes end inside the horizon, so the terminal-observation columns count."""
+    from uavppo.trainer import VecPPOTrainer
+    N, T, H = 21, 30, 64
+    bank = FieldBank.from_seed(2 * N, "v2.0", seed=41)
+    mk = lambda: VecPPOTrainer(N, T, "lstm", hidden=H, device=DEV, seed=8, bank=bank.interleaved(), bank_sources=bank.sources,
+                               gae_mode="standard", use_curriculum=False, log_info=True)
+    a, b = mk(), mk()
+    a.radius = b.radius = 200.0
+    a.reset(); b.reset()
+    rng = np.random.RandomState(1)
+    fa = torch.from_numpy(rng.randint(1, 5, (N, T)).astype(np.int32)).to(DEV)
+    nz = torch.from_numpy(rng.randn(N, T, 2)).to(DEV)
+    assert a.rollout_route() == "fused_lstm"
+    a.collect(forced_act=fa, noise=nz)
+    b.h0.copy_(b.h); b.c0.copy_(b.c)
+    b._collect_stepwise_lstm(fa, nz)
+    print("finished episodes:", int(a.buf["done"].sum().item()), " max |info difference|:", (a.info - b.info).abs().max().item())
+    assert torch.equal(a.buf["done"], b.buf["done"]) and a.buf["done"].sum() >= 2
+    assert torch.allclose(a.info, b.info, atol=1e-4)
+
+
+# --------------------------------------------------------------------------------------------- success pipeline, odd call orders
+def _curriculum_trainer(**kw):
+    from uavppo.trainer import VecPPOTrainer
+    tr = VecPPOTrainer(512, 64, "lstm", hidden=64, device=DEV, seed=5, epochs=1, **kw)
+    tr.radius = 200.0                # many episodes end in every rollout
+    tr.reset()
+    if not tr.device_curriculum:
+        tr.curriculum.current_radius = 200.0
+    return tr
+
+
+def _ended(*flags):
+    """(episodes, successes) the flags arrays hold: bit 0 = an episode ended, bit 1 = it reached the source; no rollout may
+    end more episodes than one success message carries."""
+    from uavppo.dist_utils import SUCC_CAP
+    for f in flags:
+        assert 0 < int((f & 1).ne(0).sum()) <= SUCC_CAP
+    return sum(int((f & 1).ne(0).sum()) for f in flags), sum(int((f & 2).ne(0).sum()) for f in flags)
+
+
+def test_two_rollouts_before_one_update_are_both_counted():
+    tr = _curriculum_trainer()
+    assert tr.device_curriculum
+    tr.collect()
+    f1 = tr.buf["flags"].clone()
+    tr.collect()
+    f2 = tr.buf["flags"].clone()
+    tr.update()
+    tr.update_curriculum()
+    assert (tr.episodes_done, tr.successes_done) == _ended(f1, f2)
+
+
+def test_update_curriculum_twice_counts_a_rollout_once():
+    for device in (True, False):
+        tr = _curriculum_trainer(device_curriculum=device)
+        tr.collect()
+        tr.update()
+        tr.update_curriculum()
+        tr.update_curriculum()
+        assert (tr.episodes_done, tr.successes_done) == _ended(tr.buf["flags"]), device
+
+
+def test_main_stream_success_exchange_equals_the_side_stream_one():
+    a, b = _curriculum_trainer(), _curriculum_trainer()
+    b.side_stream_curriculum = False
+    for it in range(3):
+        a.train_iteration(); b.train_iteration()
+        for k in a.buf:
+            assert torch.equal(a.buf[k], b.buf[k]), (it, k)
+    assert a.episodes_done == b.episodes_done > 0 and a.successes_done == b.successes_done
+    assert a.radius == b.radius and a.bonus == b.bonus and isinstance(a.bonus, np.float64) == isinstance(b.bonus, np.float64)
+
+
+def test_host_curriculum_counts_what_the_flags_hold():
+    tr = _curriculum_trainer(device_curriculum=False)
+    tr.collect()
+    tr.update()
+    tr.update_curriculum()
+    assert (tr.episodes_done, tr.successes_done) == _ended(tr.buf["flags"])
+    assert int(tr.last_success_bits.size) == tr.episodes_done and int(tr.last_success_bits.sum()) == tr.successes_done
+
+
+# --------------------------------------------------------------------------------------------- GAIL on the base loop's hooks
+def test_gail_train_iteration_is_the_base_loop_with_its_two_hooks():
+    """GAILTrainer.train_iteration() is VecPPOTrainer's: the discriminator steps run between update() and update_curriculum(), the
+    GAE reads the shaped reward, and buf["rew"] stays the environment's."""
+    from uavppo import ops
+    from uavppo.gail import GAILTrainer
+    rng = np.random.RandomState(71)
+    expert = (rng.rand(300, 6).astype(np.float32), rng.randint(0, 5, 300).astype(np.int64))
+    tr = GAILTrainer(64, 32, "lstm", hidden=64, device=DEV, seed=7, use_curriculum=False, expert=expert, env_coef=0.5, gail_coef=0.25,
+                     disc_steps=2)
+    tr.disc.flat.mul_(3.0)
+    tr.record = True
+    collect, seen = tr.collect, {}
+
+    def collect_and_copy():
+        collect()
+        seen["rew"] = tr.buf["rew"].clone()
+    tr.collect = collect_and_copy
+    tr.train_iteration()
+    assert tr.disc_opt_step == tr.disc_steps == 2 and len(tr.disc_log) == 2 and tr.iteration == 1
+    b, hp = tr.buf, tr.hp
+    want = ops.gae(tr.rew_shaped, b["val"], b["done"], hp["gamma"], hp["lam"], tr.gae_mode, last_val=tr.last_val)
+    assert want is not tr.adv and torch.equal(tr.adv, want) and not torch.equal(tr.rew_shaped, b["rew"])
+    assert torch.equal(b["rew"], seen["rew"])

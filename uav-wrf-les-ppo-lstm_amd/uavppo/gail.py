@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .dist_utils import allreduce_adv_stats, allreduce_grad, allreduce_sum
+from .dist_utils import allreduce_grad, allreduce_sum
 from .policy import _FlatPolicy
 from .trainer import VecPPOTrainer
 
@@ -142,13 +142,8 @@ class GAILTrainer(VecPPOTrainer):
                         out=self.rew_shaped.view(-1))
         return self.rew_shaped
 
-    def compute_advantages(self):
-        b, hp = self.buf, self.hp
-        self.shape_reward()
-        ops.gae(self.rew_shaped, b["val"], b["done"], hp["gamma"], hp["lam"], self.gae_mode, last_val=self.last_val, out=self.adv)
-        ops.adv_stats(self.adv, out=self.stats3)
-        allreduce_adv_stats(self.stats3)
-        ops.adv_normalise(self.adv, b["val"], self.stats3, self.adv_n, self.ret)
+    def _gae_reward(self):                  # compute_advantages(): the GAE reads the shaped reward
+        return self.shape_reward()
 
     def update_discriminator(self):
         obs, act = self._rows()
@@ -164,19 +159,8 @@ class GAILTrainer(VecPPOTrainer):
                           max_norm=0.0)
         return self.disc_sums
 
-    def train_iteration(self):
-        ev = self._iter_events.pop() if getattr(self, "_iter_events", None) else None
-        if ev is not None:
-            ev[0].record()
-        self.collect()
-        if ev is not None:
-            ev[1].record()
-        sums = self.update()
+    def _after_update(self):                # train_iteration(): policy first, discriminator afterwards, then the curriculum
         self.update_discriminator()
-        self.update_curriculum()
-        self.poll_param_range()
-        self.iteration += 1
-        return sums
 
     def disc_losses(self):
         """(expert loss, policy loss, accuracy) of the LAST discriminator step; raises on a NaN logit (or an action outside the

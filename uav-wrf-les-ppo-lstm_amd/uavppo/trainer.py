@@ -9,7 +9,6 @@ statistics (train_ppo2.0.py:35-39).
 """
 from __future__ import annotations
 
-
 import numpy as np
 import torch
 
@@ -48,6 +47,10 @@ def _side_stream(device):
     return _SIDE_STREAMS[key]
 
 
+# VecPPOTrainer._succ_stage, where the buffers' success flags are: not packed | packed (side stream) | gathered and handed on | counted
+_IDLE, _PACKED, _EXCHANGED, _COUNTED = range(4)
+
+
 class _DeviceCurriculumView:
     """What callers read off `trainer.curriculum` when the curriculum lives on the device (each access waits for the device)."""
 
@@ -64,7 +67,7 @@ class _DeviceCurriculumView:
 
     @property
     def success_history(self):
-        self._tr._sync_curriculum()
+        self._tr.sync_curriculum()
         return [None] * self._tr._hist_len          # the window's LENGTH is what callers look at; its bits stay on the device
 
 
@@ -154,11 +157,12 @@ class VecPPOTrainer:
         self._episodes_done = self._successes_done = 0   # finished episodes of the whole job (all ranks)
         self._hist_len = 0
         self.last_success_bits = None
+        self._curr_queue = []        # ring slots of the device curriculum's lagged host mirrors on their way, oldest first
         if self.device_curriculum:
             self._curr = ops.curriculum_state(self.device, self._radius, self._bonus)
             self._curr_host = torch.zeros(4, self._curr.numel(), dtype=torch.uint8).pin_memory()     # ring of lagged host mirrors
             self._curr_evs = [torch.cuda.Event() for _ in range(4)]
-            self._curr_queue, self._curr_next = [], 0
+            self._curr_next = 0
             self.last_mirror_slot = 0
             self._curr_done_ev = torch.cuda.Event()
             self._curr_pending = False
@@ -175,10 +179,13 @@ class VecPPOTrainer:
         self._pack_ev = torch.cuda.Event()
         self._roll_ev = torch.cuda.Event()
         self._gather_ev = torch.cuda.Event()
-        self._succ_pending = False
-        self._succ_exchanged = False
+        self._succ_stage = _IDLE               # where the flags of the current buffers are on their way to the curriculum
         self._succ_msg = None
         self.side_stream_curriculum = True     # False: pack + copy on the main stream inside update_curriculum (A/B, tools/ab_loop.py)
+        self._iter_events = []                 # (start, end) event pairs of time_rollouts() still to be recorded
+        self._env_lo = env_shard(self.rank, N)[0]
+        nb = N // self.num_minibatches
+        self._st = None                        # scratch of one step of the step-wise rollouts: _step_scratch()
         if policy == "lstm":
             L, H = layers, hidden
             # recurrent state (h | c) and its snapshot at the start of the current rollout (what BPTT starts from): each pair is
@@ -187,88 +194,78 @@ class VecPPOTrainer:
             self._state0 = torch.zeros(2, L, N, H, **f32)
             self.h, self.c = self._state[0], self._state[1]
             self.h0, self.c0 = self._state0[0], self._state0[1]
-            nb = N // self.num_minibatches
             self.work = {"dgates": ops.lstm_dgates(nb, T, H, self.device), "heads": torch.empty(nb, T, 6, **f32)}   # heads: logits | value, written by the sequence kernels
             for l in range(L):
                 self.work[f"stash{l}"] = torch.empty(nb, T, 6 * H, **f32)
                 self.work[f"y{l}"] = torch.empty(nb, T, H, **f32)
             # (a dy buffer for paths whose backward does not take dheads is allocated on first use: policy.backward)
-        else:
-            nb = N // self.num_minibatches
-            self.work = {"stash": None}      # layer-by-layer path only (770 floats per sample); allocated on first use
-            self._mlp_tmp = {"rew": torch.zeros(N, **f32), "done": torch.zeros(N, **f32),
-                             "flags": torch.zeros(N, dtype=torch.uint8, device=d), "stash": None}
-        if policy == "lstm":
             self.dhead_bias = self.policy.grad_views["head.bias"]       # the loss kernel's column sums ARE this gradient
-        self.dheads = torch.empty((N // self.num_minibatches) * T, 6, **f32)
+        else:
+            self.work = {"stash": None}      # layer-by-layer path only (770 floats per sample); allocated on first use
+            self._step_scratch()
+        self.dheads = torch.empty(nb * T, 6, **f32)
         self.reset()
 
     # ------------------------------------------------------------------------------------------
     def env_cfg(self):
         return ops.make_env_cfg(self.variant, self._radius, self._bonus, self.seed, self.bank, self.bank_sources,
-                                env_offset=env_shard(self.rank, self.N)[0], n_env_total=self.world * self.N,
+                                env_offset=self._env_lo, n_env_total=self.world * self.N,
                                 trend_k=self.trend_k, curriculum=self._curr)
 
-    # ------------------------------------------------------------------------------------------ T1 state
+    # ------------------------------------------------------------------------------------------ T1: successes -> curriculum
     # radius / bonus / episode counters.  Host curriculum: plain attributes.  Device curriculum: the truth is on the device; the
     # getters below WAIT for it (tests, logging at the end of a run); the training loop itself never calls them -- it reads the
     # lagged mirror (`radius_lagged`, `episodes_lagged`: the state as of the rollout before last, copied to pinned memory on
     # the side stream).
-    def _sync_curriculum(self):
+    def _read_curriculum(self, block, adopt=True):
+        """A HOST copy of the device curriculum block -> its scalars, taken as this trainer's own unless adopt=False.  An overflowed
+        message raises wherever the block is read: through the mirror one or two rollouts late, never at the end of a long run only."""
+        d = ops.curriculum_read(block.numpy())
+        if d["overflow"]:
+            raise RuntimeError(f"device curriculum: a rank ended more than {SUCC_CAP} episodes in one rollout (message capacity)")
+        if adopt:
+            self._radius = d["radius"]
+            self._bonus = np.float64(d["bonus"]) if d["bonus_is_f64"] else d["bonus"]
+            self._episodes_done, self._successes_done, self._hist_len = d["episodes"], d["successes"], d["hist_len"]
+        return d
+
+    def _read_mirror_slot(self, k):
+        self._curr_evs[k].synchronize()        # waits for that 64-byte copy only
+        return self._read_curriculum(self._curr_host[k], adopt=False)
+
+    def sync_curriculum(self):
+        """Device curriculum: wait for the device state and take it as the host scalars."""
         if not self.device_curriculum:
             return
-        if self._succ_pending and not self._succ_exchanged and not self._coll:
+        if self._succ_stage == _PACKED and not self._coll:
             self._exchange_successes()         # (with several ranks the exchange is a collective: only update() / collect() issue it)
         if self._curr_pending:
             self._curr_done_ev.synchronize()
-        d = ops.curriculum_read(self._curr.cpu().numpy())
-        if d["overflow"]:
-            raise RuntimeError(f"device curriculum: a rank ended more than {SUCC_CAP} episodes in one rollout (message capacity)")
-        self._radius = d["radius"]
-        self._bonus = np.float64(d["bonus"]) if d["bonus_is_f64"] else d["bonus"]
-        self._episodes_done, self._successes_done, self._hist_len = d["episodes"], d["successes"], d["hist_len"]
-
-    def sync_curriculum(self):
-        self._sync_curriculum()
+        self._read_curriculum(self._curr.cpu())
 
     def _poll_curriculum_mirror(self):
-        """Newest landed mirror of the device state (never waits)."""
+        """Newest landed mirror of the device state (never waits; the host curriculum queues none)."""
         latest = None
         while self._curr_queue and self._curr_evs[self._curr_queue[0]].query():
             latest = self._curr_queue.pop(0)
         if latest is not None:
-            d = ops.curriculum_read(self._curr_host[latest].numpy())
-            if d["overflow"]:          # surfaced one or two rollouts late, never at the end of a long run only
-                raise RuntimeError(f"device curriculum: a rank ended more than {SUCC_CAP} episodes in one rollout (message capacity)")
-            self._radius = d["radius"]
-            self._bonus = np.float64(d["bonus"]) if d["bonus_is_f64"] else d["bonus"]
-            self._episodes_done, self._successes_done, self._hist_len = d["episodes"], d["successes"], d["hist_len"]
+            self._read_curriculum(self._curr_host[latest])
 
     def rollout_radius(self, k=None):
         """The radius the LAST collected rollout ran with (device curriculum: from its lagged mirror, slot k = the value of
         `last_mirror_slot` taken right after that rollout's update_curriculum(); waits only for that 64-byte copy)."""
-        if not self.device_curriculum:
-            return self._rollout_radius
-        k = self.last_mirror_slot if k is None else k
-        self._curr_evs[k].synchronize()
-        return ops.curriculum_read(self._curr_host[k].numpy())["radius"]
+        return self._read_mirror_slot(self.last_mirror_slot if k is None else k)["radius"] if self.device_curriculum else self._rollout_radius
 
     def episodes_before_rollout(self, k):
         """Episodes the whole job had finished BEFORE the rollout whose mirror went to slot k (its `last_mirror_slot`): waits for
         that 64-byte copy only.  The mirror is taken on the device between two curriculum updates, from state every rank holds
         identically -- so this value, unlike the polled `episodes_lagged`, is the same on every rank at the same program point:
         what a multi-rank loop must base its stop decision on (a rank that stops alone leaves the others in the next all-reduce)."""
-        if not self.device_curriculum:
-            return self._episodes_done
-        self._curr_evs[k].synchronize()
-        d = ops.curriculum_read(self._curr_host[k].numpy())
-        if d["overflow"]:
-            raise RuntimeError(f"device curriculum: a rank ended more than {SUCC_CAP} episodes in one rollout (message capacity)")
-        return d["episodes"]
+        return self._read_mirror_slot(k)["episodes"] if self.device_curriculum else self._episodes_done
 
     @property
     def radius(self):
-        self._sync_curriculum()
+        self.sync_curriculum()
         return self._radius
 
     def _before_host_write(self):
@@ -285,7 +282,7 @@ class VecPPOTrainer:
 
     @property
     def bonus(self):
-        self._sync_curriculum()
+        self.sync_curriculum()
         return self._bonus
 
     @bonus.setter
@@ -298,25 +295,115 @@ class VecPPOTrainer:
 
     @property
     def radius_lagged(self):
-        if self.device_curriculum:
-            self._poll_curriculum_mirror()
+        self._poll_curriculum_mirror()
         return self._radius
 
     @property
     def episodes_lagged(self):
-        if self.device_curriculum:
-            self._poll_curriculum_mirror()
+        self._poll_curriculum_mirror()
         return self._episodes_done
 
     @property
     def episodes_done(self):
-        self._sync_curriculum()
+        self.sync_curriculum()
         return self._episodes_done
 
     @property
     def successes_done(self):
-        self._sync_curriculum()
+        self.sync_curriculum()
         return self._successes_done
+
+    # A rollout's flags (_succ_stage): packed right behind the rollout on the side stream; exchanged from collect() with one rank,
+    # with collectives on from update() behind the advantage-statistics all-reduce (or from update_curriculum() if still
+    # outstanding); counted by update_curriculum().  _IDLE: side_stream_curriculum = False, or buffers a caller filled by hand.
+    def _successes_before_rollout(self):
+        if self._succ_stage in (_PACKED, _EXCHANGED):    # a previous rollout's flags may still be read by the pack kernel on the side stream
+            torch.cuda.current_stream().wait_event(self._pack_ev)
+        if self.device_curriculum:
+            if self._succ_stage == _PACKED:        # collect() twice without an update(): finish the first one's exchange
+                self._exchange_successes()
+            if self._curr_pending:             # the env kernels read radius / bonus from the device state: a GPU-side wait, no host sync
+                torch.cuda.current_stream().wait_event(self._curr_done_ev)
+        self._succ_stage = _IDLE
+
+    def _pack_successes(self):
+        self._roll_ev.record()
+        with torch.cuda.stream(self._side):
+            self._side.wait_event(self._roll_ev)
+            self._succ_msg = pack_local_successes(self.buf["flags"])
+            self._pack_ev.record(self._side)       # the flags have been read: the next rollout may overwrite them
+        self._succ_stage = _PACKED
+
+    def _gather_successes(self, msg):
+        msgs = exchange_successes(msg)
+        if tuple(msgs.shape) != tuple(self._succ_host.shape):       # e.g. world_size > 1 without a process group
+            raise RuntimeError(f"success exchange returned {tuple(msgs.shape)}, expected {tuple(self._succ_host.shape)}: "
+                               "is torch.distributed initialised for world_size > 1?")
+        return msgs
+
+    def _exchange_successes(self):
+        """All-gather of the packed success bits + copy to pinned host memory, on the side stream.  With several ranks it is
+        issued from update(), BEHIND the advantage-statistics all-reduce in program order: RCCL runs a rank's collectives
+        in the order they were issued, and that all-reduce must not queue behind the pack kernel."""
+        on_main = abi_collectives() and self._coll
+        if on_main:
+            # ABI carrier: ONE communicator on raw streams.  RCCL runs a rank's collectives in the order its device reaches them, so
+            # the all-gather must not sit on another stream than the all-reduces (two ranks could then reach the two collectives in
+            # opposite orders and wait for each other): it goes on the MAIN stream, behind the pack kernel, and the side stream
+            # picks the gathered messages up again.  (torch.distributed serialises a group's collectives on its own stream.)
+            main = torch.cuda.current_stream()
+            main.wait_event(self._pack_ev)
+            msgs = self._gather_successes(self._succ_msg)
+            self._gather_ev.record(main)
+        with torch.cuda.stream(self._side):
+            if on_main:
+                self._side.wait_event(self._gather_ev)
+            else:
+                msgs = self._gather_successes(self._succ_msg)
+            if self.device_curriculum:
+                # lagged host mirror of the state as it was for THIS rollout, then the update itself: one thread walks the
+                # messages rank by rank, episode by episode (model.py:131-164)
+                k = self._curr_next
+                self._curr_next = (k + 1) % len(self._curr_evs)
+                if k in self._curr_queue:                       # the host is a whole ring ahead: drop the oldest mirror
+                    self._curr_queue.remove(k)
+                self._curr_host[k].copy_(self._curr, non_blocking=True)
+                self._curr_evs[k].record(self._side)
+                self._curr_queue.append(k)
+                self.last_mirror_slot = k
+                ops.curriculum_update(self._curr, msgs, SUCC_CAP)
+                self._curr_done_ev.record(self._side)
+                self._curr_pending = True
+            else:
+                self._succ_host.copy_(msgs, non_blocking=True)
+                self._succ_ev.record(self._side)
+        self._succ_stage = _EXCHANGED
+
+    def update_curriculum(self):
+        """Feed this iteration's finished episodes to the curriculum (host scalars).  The success bits are
+        compacted on the device; only they cross to the host / the other ranks, so every rank feeds the same
+        global (env, time)-ordered sequence to its replicated curriculum.  A rollout's episodes are counted once: a second
+        call before the next collect() does nothing."""
+        if self.curriculum is None or self._succ_stage == _COUNTED:
+            return
+        if self._succ_stage == _IDLE and self.device_curriculum:        # flags not produced by collect(): pack them now
+            self._pack_successes()
+        if self._succ_stage == _IDLE:          # host curriculum: pack and exchange them now, on the main stream
+            self._succ_host.copy_(self._gather_successes(pack_local_successes(self.buf["flags"])), non_blocking=True)
+            self._succ_ev.record()
+        elif self._succ_stage == _PACKED:      # collect() without an update() in between
+            self._exchange_successes()
+        self._succ_stage = _COUNTED
+        if self.device_curriculum:             # no host wait: the messages were (or are now) queued, the device does the rest
+            self._poll_curriculum_mirror()
+            return
+        self._succ_ev.synchronize()
+        bits = unpack_episode_successes(self._succ_host.numpy(), self.buf["flags"])
+        self._episodes_done += int(bits.size)            # over ALL ranks, in global (env, time) order
+        self._successes_done += int(bits.sum())
+        self.last_success_bits = bits
+        self.curriculum.update_many(bits)
+        self._radius, self._bonus = self.curriculum.current_radius, self.curriculum.explore_bonus
 
     # ------------------------------------------------------------------------------------------ range guard
     # The fp16-split kernels need |w| < 65504, |x| < 4096, |h0| < 64 (include/uavppo.h).  What can leave that range, and
@@ -359,6 +446,18 @@ class VecPPOTrainer:
         if latest is not None and self._guarded():
             self._decide([float(self._ranges_host[latest, 0]), 0.0, 0.0])
 
+    def _push_param_range(self):
+        """max |param| of the last Adam step -> pinned host memory, read at a later poll."""
+        if len(self._pmax_queue) == 4:     # the host is four updates ahead of the device: let the oldest copy land
+            self._ranges_evs[self._pmax_queue[0]].synchronize()
+            self.poll_param_range()
+        k = self._pmax_next
+        self._pmax_next = (k + 1) % 4
+        self._ranges_host[k].copy_(self.ranges, non_blocking=True)
+        self._ranges_evs[k].record()
+        self._pmax_queue.append(k)
+        self._buffers_own = False
+
     def check_ranges(self):
         """Kernel arithmetic for the update about to be queued (see above); sets it on the device's handle."""
         if not self._guarded():
@@ -385,17 +484,31 @@ class VecPPOTrainer:
             self.c.zero_()
 
     # ------------------------------------------------------------------------------------------ R1
+    def _stepwise_lstm_route(self):
+        """h = 256 on the fp16-split arithmetic, one minibatch: the stepper (uav_lstm_stepper_*) -- weights split once per
+        rollout, state kept in its piece planes, stash / y / heads written at [:, t] of the update's own arrays, so that
+        PPO epoch 0 adopts this forward pass -- with everything after the recurrent layers as one launch (uav_rollout_tail)
+        unless the per-step info rows are wanted.  Otherwise one uav_lstm_fwd call of T = 1 per layer and step."""
+        if not (self.use_stepper and self.policy.hidden == 256 and self.arith == "fp16x3" and self.num_minibatches == 1
+                and ops.lstm_bwd_caps(self.device, self.obs_dim, 256) != 0):      # 0: the handle is not on the fp16 step path
+            return "per_call"
+        return "tail" if self.use_fused_tail and self.info is None else "stepper"
+
+    def rollout_route(self):
+        """Which rollout the next collect() runs on the arithmetic in force: 'fused_lstm' | 'fused_mlp' (uav_rollout, one
+        persistent launch), or step-wise 'tail' | 'stepper' | 'per_call' (LSTM), 'per_call' (MLP)."""
+        if self.kind != "lstm":
+            return "fused_mlp" if self.fused_mlp else "per_call"
+        wide = self._guarded() and self.arith != "fp16x3"      # uav_rollout exists in the fp16-split form only
+        if self.policy.num_layers == 1 and self.policy.hidden in (64, 128) and not wide:
+            return "fused_lstm"
+        return self._stepwise_lstm_route()
+
     def collect(self, forced_act=None, noise=None):
         """Fill the (env, T, feat) buffers with one rollout of T steps per env."""
         self._rollout_forward_valid = False
         self._rollout_radius = self._radius    # (host curriculum: what this rollout runs with)
-        if self._succ_pending:                 # a previous rollout's flags may still be read by the pack kernel on the side stream
-            torch.cuda.current_stream().wait_event(self._pack_ev)
-        if self.device_curriculum:
-            if self._succ_pending and not self._succ_exchanged:     # collect() twice without an update(): finish the first one's exchange
-                self._exchange_successes()
-            if self._curr_pending:             # the env kernels read radius / bonus from the device state: a GPU-side wait, no host sync
-                torch.cuda.current_stream().wait_event(self._curr_done_ev)
+        self._successes_before_rollout()
         if self._guarded():
             self.poll_param_range()
             self._measure_params()
@@ -403,12 +516,10 @@ class VecPPOTrainer:
                 self.arith = self.force_arith
             ops.set_lstm_arith(self.arith, self.device)
             self._buffers_own = True
-        wide = self._guarded() and self.arith != "fp16x3"      # uav_rollout exists in the fp16-split form only
-        if self.kind == "lstm" and (self.policy.num_layers != 1 or self.policy.hidden not in (64, 128) or wide):
+        route = self.rollout_route()
+        if self.kind == "lstm":
             self._state0.copy_(self._state)
-            self._collect_stepwise_lstm(forced_act, noise)
-        elif self.kind == "lstm":
-            self._state0.copy_(self._state)
+        if route == "fused_lstm":
             reuse = self.reuse_rollout_forward and self.num_minibatches == 1
             ops.rollout_lstm(self.env_state, self.N, self.env_cfg(), self.policy.flat, self.policy.hidden, self.T,
                              self.iteration, self.cur_obs, self.h[0], self.c[0], self.buf, last_val=self.last_val,
@@ -416,141 +527,103 @@ class VecPPOTrainer:
                              stash=self.work["stash0"] if reuse else None, y=self.work["y0"] if reuse else None,
                              info=self.info, heads=self.work["heads"] if reuse else None)
             self._rollout_forward_valid = reuse
-        elif self.fused_mlp:
+        elif route == "fused_mlp":
             ops.rollout_mlp(self.env_state, self.N, self.env_cfg(), self.policy.flat, self.T, self.iteration, self.cur_obs,
                             self.buf, last_val=self.last_val, forced_act=forced_act, noise=noise, nan_count=self.nan_count,
                             info=self.info)
+        elif self.kind == "lstm":
+            self._collect_stepwise_lstm(forced_act, noise)
         else:
             self._collect_stepwise(forced_act, noise)
         if self.curriculum is not None and self.side_stream_curriculum:
-            self._roll_ev.record()
-            with torch.cuda.stream(self._side):
-                self._side.wait_event(self._roll_ev)
-                self._succ_msg = pack_local_successes(self.buf["flags"])
-                self._pack_ev.record(self._side)       # the flags have been read: the next rollout may overwrite them
-            self._succ_pending = True
-            self._succ_exchanged = False
+            self._pack_successes()
             if not self._coll:
                 self._exchange_successes()
 
-    def _exchange_successes(self):
-        """All-gather of the packed success bits + copy to pinned host memory, on the side stream.  With several ranks it is
-        issued from update(), BEHIND the advantage-statistics all-reduce in program order: RCCL runs a rank's collectives
-        in the order they were issued, and that all-reduce must not queue behind the pack kernel."""
-        msgs_main = None
-        if abi_collectives() and self._coll:
-            # ABI carrier: ONE communicator on raw streams.  RCCL runs a rank's collectives in the order its device reaches them, so
-            # the all-gather must not sit on another stream than the all-reduces (two ranks could then reach the two collectives in
-            # opposite orders and wait for each other): it goes on the MAIN stream, behind the pack kernel, and the side stream
-            # picks the gathered messages up again.  (torch.distributed serialises a group's collectives on its own stream.)
-            main = torch.cuda.current_stream()
-            main.wait_event(self._pack_ev)
-            msgs_main = exchange_successes(self._succ_msg)
-            self._gather_ev.record(main)
-        with torch.cuda.stream(self._side):
-            if msgs_main is not None:
-                self._side.wait_event(self._gather_ev)
-                msgs = msgs_main
-            else:
-                msgs = exchange_successes(self._succ_msg)
-            if tuple(msgs.shape) != tuple(self._succ_host.shape):       # e.g. world_size > 1 without a process group
-                raise RuntimeError(f"success exchange returned {tuple(msgs.shape)}, expected {tuple(self._succ_host.shape)}: "
-                                   "is torch.distributed initialised for world_size > 1?")
-            if self.device_curriculum:
-                # lagged host mirror of the state as it was for THIS rollout, then the update itself: one thread walks the
-                # messages rank by rank, episode by episode (model.py:131-164)
-                k = self._curr_next
-                self._curr_next = (k + 1) % len(self._curr_evs)
-                if k in self._curr_queue:                       # the host is a whole ring ahead: drop the oldest mirror
-                    self._curr_queue.remove(k)
-                self._curr_host[k].copy_(self._curr, non_blocking=True)
-                self._curr_evs[k].record(self._side)
-                self._curr_queue.append(k)
-                self.last_mirror_slot = k
-                ops.curriculum_update(self._curr, msgs, SUCC_CAP)
-                self._curr_done_ev.record(self._side)
-                self._curr_pending = True
-            else:
-                self._succ_host.copy_(msgs, non_blocking=True)
-                self._succ_ev.record(self._side)
-        self._succ_exchanged = True
+    def _step_scratch(self):
+        """Scratch of ONE step of the step-wise rollouts (every route but the two fused kernels), built once -- an LSTM's on its
+        first step-wise rollout: what the env step returns, the per-call routes' forward stashes, the action drawn and the restart
+        mask carried to the next step (LSTM), and -- with log_info -- the step's reward parts, terminal observation and source."""
+        if self._st is None:
+            N, d, log, f32 = self.N, self.device, self.info is not None, dict(dtype=torch.float32, device=self.device)
+            self._st = {"rew": torch.zeros(N, **f32), "done": torch.zeros(N, **f32), "flags": torch.zeros(N, dtype=torch.uint8, device=d),
+                        "work": {}, "stash": None, "info": torch.zeros(N, 5, **f32) if log else None,
+                        "term": torch.zeros(N, self.obs_dim, **f32) if log else None,
+                        "src": torch.zeros(N, 2, dtype=torch.float64, device=d) if log else None}
+            if self.kind == "lstm":
+                self._st.update(act=torch.zeros(N, dtype=torch.int32, device=d), keep=torch.ones(N, **f32))
+        return self._st
+
+    def _env_step(self, st, cfg, act, t, noise):
+        """Env step t of a step-wise rollout into the step scratch; with log_info, row t of the ten info columns."""
+        nz = None if noise is None else noise[:, t].contiguous()
+        if self.info is not None:
+            ops.env_peek(self.env_state, self.N, source=st["src"])           # source of the episode this step belongs to
+        ops.env_step(self.env_state, self.N, cfg, act, self.cur_obs, st["rew"], st["done"], st["flags"], noise=nz,
+                     info=st["info"], term_obs=st["term"])
+        if self.info is not None:
+            self.info[:, t, :5] = st["info"]
+            self.info[:, t, 5] = st["term"][:, 2]
+            self.info[:, t, 6:8] = st["term"][:, :2] * 500.0       # step-wise path: position from the observation
+            self.info[:, t, 8:10] = st["src"]
+
+    def _rollout_per_call(self, heads_of, forced_act, noise, keep=None):
+        """One policy forward + sample + env step launch group per time step (train_ppo2.0.py:157-198 with a batch of N states
+        instead of 1).  heads_of(): logits | value [N, 6] of the current observation; keep: the LSTM's restart mask [N]."""
+        b, st, cfg = self.buf, self._step_scratch(), self.env_cfg()
+        for t in range(self.T):
+            heads = heads_of()
+            fa = None if forced_act is None else forced_act[:, t].contiguous()
+            act, logp, _, _ = ops.policy_sample(heads[:, :5].contiguous(), seed=self.seed, counter=t, iteration=self.iteration,
+                                                index_offset=self._env_lo, forced_act=fa, nan_count=self.nan_count)
+            b["obs"][:, t] = self.cur_obs
+            b["act"][:, t] = act
+            b["val"][:, t] = heads[:, 5]
+            b["logp"][:, t] = logp
+            if keep is not None:
+                b["keep"][:, t] = keep
+            self._env_step(st, cfg, act, t, noise)
+            b["rew"][:, t] = st["rew"]
+            b["done"][:, t] = st["done"]
+            b["flags"][:, t] = st["flags"]
+            if keep is not None:
+                torch.sub(1.0, st["done"], out=keep)      # the recurrent state restarts where an episode ended
+
+    def _rollout_stepper(self, forced_act, noise):
+        b, st, w, cfg = self.buf, self._st, self.work, self.env_cfg()
+        for t in range(self.T):
+            b["obs"][:, t] = self.cur_obs
+            self.policy.step_at(b["obs"], t, w, w["heads"], keep=st["keep"])
+            fa = None if forced_act is None else forced_act[:, t].contiguous()
+            # sample from heads[:, t] in place; action / value / log-prob straight into column t
+            act = ops.policy_sample_at(w["heads"], t, st["act"], b["act"], b["val"], b["logp"], self.nan_count, seed=self.seed,
+                                       iteration=self.iteration, index_offset=self._env_lo, forced_act=fa)
+            self._env_step(st, cfg, act, t, noise)
+            # one launch: keep / rew / done / flags -> column t; keep <- 1 - done
+            ops.store_transition(t, st["keep"], st["rew"], st["done"], st["flags"], b["keep"], b["rew"], b["done"], b["flags"])
+
+    def _rollout_tail(self, forced_act, noise):
+        b, st, w, cfg, v = self.buf, self._st, self.work, self.env_cfg(), self.policy.views
+        b["obs"][:, 0] = self.cur_obs                  # later rows are written by the tail of the step before
+        for t in range(self.T):
+            top = self.policy.step_layers_at(b["obs"], t, w, keep=st["keep"])
+            ops.rollout_tail(self.env_state, cfg, top, t, v["head.weight"], v["head.bias"], w["heads"], st["act"],
+                             self.cur_obs, b["obs"], st["keep"], b["act"], b["val"], b["logp"], b["keep"], b["rew"], b["done"],
+                             b["flags"], self.nan_count, seed=self.seed, iteration=self.iteration, index_offset=self._env_lo,
+                             forced_act=None if forced_act is None else forced_act[:, t].contiguous(),
+                             noise=None if noise is None else noise[:, t].contiguous())
 
     def _collect_stepwise_lstm(self, forced_act=None, noise=None):
-        """Stacked / wide LSTM policies (BASELINE C5: h=256 x2): one cell step per layer + heads GEMM +
-        sample + env step per time step.  Same buffers and keep semantics as the fused rollout kernel."""
-        b = self.buf
-        if not hasattr(self, "_st"):
-            f32 = dict(dtype=torch.float32, device=self.device)
-            self._st = {"rew": torch.zeros(self.N, **f32), "done": torch.zeros(self.N, **f32),
-                        "flags": torch.zeros(self.N, dtype=torch.uint8, device=self.device),
-                        "act": torch.zeros(self.N, dtype=torch.int32, device=self.device),
-                        "keep": torch.ones(self.N, **f32), "work": {}}
-        st = self._st
-        cfg = self.env_cfg()
+        """Stacked / wide LSTM policies (BASELINE C5: h=256 x2) on the step-wise route this trainer's switches select.  Same
+        buffers and keep semantics as the fused rollout kernel.  (The caller snapshots _state0.)"""
+        st, route = self._step_scratch(), self._stepwise_lstm_route()
         st["keep"].fill_(1.0)
-        # h = 256 on the fp16-split arithmetic, one minibatch: the stepper (uav_lstm_stepper_*) -- weights split once per
-        # rollout, state kept in its piece planes, stash / y / heads written at [:, t] of the update's own arrays, so that
-        # PPO epoch 0 adopts this forward pass.  Otherwise one uav_lstm_fwd call of T = 1 per layer and step.
-        stepper = (self.use_stepper and self.policy.hidden == 256 and self.arith == "fp16x3" and self.num_minibatches == 1
-                   and ops.lstm_bwd_caps(self.device, self.obs_dim, 256) != 0)      # 0: the handle is not on the fp16 step path
-        # everything after the recurrent layers as one launch (uav_rollout_tail), unless the per-step info rows are wanted
-        tail = stepper and self.use_fused_tail and self.info is None
-        if stepper:
+        if route == "per_call":
+            self._rollout_per_call(lambda: self.policy.step(self.cur_obs, self.h, self.c, st["keep"], st["work"]), forced_act, noise,
+                                   keep=st["keep"])
+        else:
             self.policy.begin_steps(self.h, self.c)
-        for t in range(self.T):
-            if tail:
-                if t == 0:
-                    b["obs"][:, 0] = self.cur_obs                  # later rows are written by the tail of the step before
-                top = self.policy.step_layers_at(b["obs"], t, self.work, keep=st["keep"])
-                v = self.policy.views
-                ops.rollout_tail(self.env_state, cfg, top, t, v["head.weight"], v["head.bias"], self.work["heads"], st["act"],
-                                 self.cur_obs, b["obs"], st["keep"], b["act"], b["val"], b["logp"], b["keep"], b["rew"], b["done"],
-                                 b["flags"], self.nan_count, seed=self.seed, iteration=self.iteration,
-                                 index_offset=env_shard(self.rank, self.N)[0],
-                                 forced_act=None if forced_act is None else forced_act[:, t].contiguous(),
-                                 noise=None if noise is None else noise[:, t].contiguous())
-                continue
-            if stepper:
-                b["obs"][:, t] = self.cur_obs
-                heads = self.policy.step_at(b["obs"], t, self.work, self.work["heads"], keep=st["keep"])
-            else:
-                heads = self.policy.step(self.cur_obs, self.h, self.c, st["keep"], st["work"])
-            fa = None if forced_act is None else forced_act[:, t].contiguous()
-            if stepper:        # sample from heads[:, t] in place; action / value / log-prob straight into column t
-                act = ops.policy_sample_at(self.work["heads"], t, st["act"], b["act"], b["val"], b["logp"], self.nan_count,
-                                           seed=self.seed, iteration=self.iteration, index_offset=env_shard(self.rank, self.N)[0],
-                                           forced_act=fa)
-            else:
-                act, logp, _, _ = ops.policy_sample(heads[:, :5].contiguous(), seed=self.seed, counter=t,
-                                                    iteration=self.iteration, index_offset=env_shard(self.rank, self.N)[0],
-                                                    forced_act=fa, nan_count=self.nan_count)
-                b["obs"][:, t] = self.cur_obs
-                b["act"][:, t] = act
-                b["val"][:, t] = heads[:, 5]
-                b["logp"][:, t] = logp
-                b["keep"][:, t] = st["keep"]
-            nz = None if noise is None else noise[:, t].contiguous()
-            if self.info is not None and "info" not in st:
-                st["info"] = torch.zeros(self.N, 5, dtype=torch.float32, device=self.device)
-                st["term"] = torch.zeros(self.N, self.obs_dim, dtype=torch.float32, device=self.device)
-                st["src"] = torch.zeros(self.N, 2, dtype=torch.float64, device=self.device)
-            if self.info is not None:
-                ops.env_peek(self.env_state, self.N, source=st["src"])           # source of the episode this step belongs to
-            ops.env_step(self.env_state, self.N, cfg, act, self.cur_obs, st["rew"], st["done"], st["flags"], noise=nz,
-                         info=st.get("info"), term_obs=st.get("term"))
-            if self.info is not None:
-                self.info[:, t, :5] = st["info"]
-                self.info[:, t, 5] = st["term"][:, 2]
-                self.info[:, t, 6:8] = st["term"][:, :2] * 500.0       # step-wise path: position from the observation
-                self.info[:, t, 8:10] = st["src"]
-            if stepper:        # one launch: keep / rew / done / flags -> column t; keep <- 1 - done
-                ops.store_transition(t, st["keep"], st["rew"], st["done"], st["flags"], b["keep"], b["rew"], b["done"], b["flags"])
-            else:
-                b["rew"][:, t] = st["rew"]
-                b["done"][:, t] = st["done"]
-                b["flags"][:, t] = st["flags"]
-                torch.sub(1.0, st["done"], out=st["keep"])      # the recurrent state restarts where an episode ended
-        if stepper:
+            (self._rollout_tail if route == "tail" else self._rollout_stepper)(forced_act, noise)
             for l, sp in enumerate(self.policy.steppers(self.N, self.device)):
                 self.h[l].copy_(sp.hn)
                 self.c[l].copy_(sp.cn)
@@ -563,94 +636,75 @@ class VecPPOTrainer:
             self.last_val.copy_(self.policy.step(self.cur_obs, hh, cc, None, st["work"])[:, 5])
 
     def _collect_stepwise(self, forced_act=None, noise=None):
-        """MLP policy: one policy-forward + sample + env-step launch group per time step
-        (train_ppo2.0.py:157-198 with a batch of N states instead of 1)."""
-        b, tmp = self.buf, self._mlp_tmp
-        cfg = self.env_cfg()
-        for t in range(self.T):
-            heads = self.policy.heads(self.cur_obs, stash=tmp["stash"])
-            tmp["stash"] = self.policy._stash
-            logits = heads[:, :5].contiguous()
-            fa = None if forced_act is None else forced_act[:, t].contiguous()
-            act, logp, _, _ = ops.policy_sample(logits, seed=self.seed, counter=t, iteration=self.iteration,
-                                                index_offset=env_shard(self.rank, self.N)[0], forced_act=fa,
-                                                nan_count=self.nan_count)
-            b["obs"][:, t] = self.cur_obs
-            b["act"][:, t] = act
-            b["val"][:, t] = heads[:, 5]
-            b["logp"][:, t] = logp
-            nz = None if noise is None else noise[:, t].contiguous()
-            if self.info is not None and "info" not in tmp:
-                tmp["info"] = torch.zeros(self.N, 5, dtype=torch.float32, device=self.device)
-                tmp["term"] = torch.zeros(self.N, self.obs_dim, dtype=torch.float32, device=self.device)
-                tmp["src"] = torch.zeros(self.N, 2, dtype=torch.float64, device=self.device)
-            if self.info is not None:
-                ops.env_peek(self.env_state, self.N, source=tmp["src"])           # source of the episode this step belongs to
-            ops.env_step(self.env_state, self.N, cfg, act, self.cur_obs, tmp["rew"], tmp["done"], tmp["flags"], noise=nz,
-                         info=tmp.get("info"), term_obs=tmp.get("term"))
-            if self.info is not None:
-                self.info[:, t, :5] = tmp["info"]
-                self.info[:, t, 5] = tmp["term"][:, 2]
-                self.info[:, t, 6:8] = tmp["term"][:, :2] * 500.0
-                self.info[:, t, 8:10] = tmp["src"]
-            b["rew"][:, t] = tmp["rew"]
-            b["done"][:, t] = tmp["done"]
-            b["flags"][:, t] = tmp["flags"]
+        """MLP policy on the layer-by-layer kernels (uav_mlp_fwd), the forward stash kept across steps."""
+        st = self._step_scratch()
+
+        def heads_of():
+            heads = self.policy.heads(self.cur_obs, stash=st["stash"])
+            st["stash"] = self.policy._stash
+            return heads
+        self._rollout_per_call(heads_of, forced_act, noise)
         if self.last_val is not None:
-            self.last_val.copy_(self.policy.heads(self.cur_obs, stash=tmp["stash"])[:, 5])
+            self.last_val.copy_(heads_of()[:, 5])
 
     # ------------------------------------------------------------------------------------------ G1, G2
+    def _gae_reward(self):
+        """The reward array the GAE reads (GAILTrainer: the shaped reward)."""
+        return self.buf["rew"]
+
     def compute_advantages(self):
         b, hp = self.buf, self.hp
-        ops.gae(b["rew"], b["val"], b["done"], hp["gamma"], hp["lam"], self.gae_mode, last_val=self.last_val, out=self.adv)
+        ops.gae(self._gae_reward(), b["val"], b["done"], hp["gamma"], hp["lam"], self.gae_mode, last_val=self.last_val, out=self.adv)
         ops.adv_stats(self.adv, out=self.stats3)
         allreduce_adv_stats(self.stats3)          # (sum, sumsq, count): whole-buffer statistics over all ranks
         ops.adv_normalise(self.adv, b["val"], self.stats3, self.adv_n, self.ret)
 
     # ------------------------------------------------------------------------------------------ U1-U3
+    # minibatch slice -> flat gradient, one routine per policy kind (loss: the arguments of the loss kernel after the heads)
+    def _grad_lstm(self, sl, loss):
+        b, M = self.buf, self.num_minibatches
+        if self._rollout_forward_valid:
+            # first optimiser step after a fused rollout: parameters unchanged since the rollout, whose
+            # kernel already wrote this forward pass (stash, y) and its heads
+            L = self.policy.num_layers
+            self.policy.adopt_forward(b["obs"], b["keep"], self.h0, [self.work[f"stash{l}"] for l in range(L)],
+                                      [self.work[f"y{l}"] for l in range(L)])
+            heads = self.work["heads"]
+            self._rollout_forward_valid = False
+        else:
+            heads = self.policy.heads(b["obs"][sl], b["keep"][sl], self.h0[:, sl].contiguous() if M > 1 else self.h0,
+                                      self.c0[:, sl].contiguous() if M > 1 else self.c0, self.work)
+        ops.ppo_loss_heads(heads.view(self.dheads.shape[0], -1), *loss)
+        return self.policy.backward(self.dheads, self.work, self.dhead_bias)
+
+    def _grad_fused_mlp(self, sl, loss):
+        return ops.mlp_ppo_grad(self.policy.flat, self.buf["obs"][sl].reshape(-1, self.obs_dim), *loss[:8], self.loss_sums, self.policy.grad)
+
+    def _grad_layered_mlp(self, sl, loss):
+        n = self.dheads.shape[0]
+        if self.work["stash"] is None:
+            self.work["stash"] = torch.empty(n * (2 * 256 + 2 * 128 + 2), dtype=torch.float32, device=self.device)
+        heads = self.policy.heads(self.buf["obs"][sl].reshape(n, self.obs_dim), stash=self.work["stash"])
+        ops.ppo_loss_heads(heads, *loss)
+        return self.policy.backward(self.dheads)
+
     def update(self):
         """GAE + EPOCHS x num_minibatches optimiser steps (_update_model, train_ppo2.0.py:15-88)."""
         if self.check_ranges() != "fp16x3":
             self._rollout_forward_valid = False
         self.compute_advantages()
-        if self._succ_pending and not self._succ_exchanged:
+        if self._succ_stage == _PACKED:
             self._exchange_successes()
         b, hp = self.buf, self.hp
-        N, T, M = self.N, self.T, self.num_minibatches
-        nb = N // M
-        inv_n = 1.0 / float(nb * T * self.world)
+        nb = self.N // self.num_minibatches
+        inv_n = 1.0 / float(nb * self.T * self.world)
+        grad_of = self._grad_lstm if self.kind == "lstm" else self._grad_fused_mlp if self.fused_mlp else self._grad_layered_mlp
         for _ in range(hp["epochs"]):
-            for m in range(M):
+            for m in range(self.num_minibatches):
                 sl = slice(m * nb, (m + 1) * nb)
-                args = (b["act"][sl].reshape(-1), b["logp"][sl].reshape(-1), self.adv_n[sl].reshape(-1),
-                        self.ret[sl].reshape(-1), b["val"][sl].reshape(-1), inv_n, hp["clip"], hp["ent_beta"],
-                        self.loss_sums, self.dheads, self.dhead_bias)
-                if self.kind == "lstm":
-                    if self._rollout_forward_valid:
-                        # first optimiser step after a fused rollout: parameters unchanged since the rollout, whose
-                        # kernel already wrote this forward pass (stash, y) and its heads
-                        L = self.policy.num_layers
-                        self.policy.adopt_forward(b["obs"], b["keep"], self.h0, [self.work[f"stash{l}"] for l in range(L)],
-                                                  [self.work[f"y{l}"] for l in range(L)])
-                        heads = self.work["heads"]
-                        self._rollout_forward_valid = False
-                    else:
-                        heads = self.policy.heads(b["obs"][sl], b["keep"][sl],
-                                                  self.h0[:, sl].contiguous() if M > 1 else self.h0,
-                                                  self.c0[:, sl].contiguous() if M > 1 else self.c0, self.work)
-                    ops.ppo_loss_heads(heads.view(nb * T, -1), *args)
-                elif self.fused_mlp:
-                    grad = ops.mlp_ppo_grad(self.policy.flat, b["obs"][sl].reshape(nb * T, self.obs_dim), *args[:8],
-                                            self.loss_sums, self.policy.grad)
-                else:
-                    if self.work["stash"] is None:
-                        self.work["stash"] = torch.empty(nb * T * (2 * 256 + 2 * 128 + 2), dtype=torch.float32, device=self.device)
-                    heads = self.policy.heads(b["obs"][sl].reshape(nb * T, self.obs_dim), stash=self.work["stash"])
-                    ops.ppo_loss_heads(heads, *args)
-                if self.kind == "lstm":
-                    grad = self.policy.backward(self.dheads, self.work, self.dhead_bias)
-                elif not self.fused_mlp:
-                    grad = self.policy.backward(self.dheads)
+                grad = grad_of(sl, (b["act"][sl].reshape(-1), b["logp"][sl].reshape(-1), self.adv_n[sl].reshape(-1),
+                                    self.ret[sl].reshape(-1), b["val"][sl].reshape(-1), inv_n, hp["clip"], hp["ent_beta"],
+                                    self.loss_sums, self.dheads, self.dhead_bias))
                 allreduce_grad(grad)              # RCCL sum over ranks; inv_n already holds 1/global count
                 if self.record_grads:            # (gradient, parameters it was taken at)
                     self.grad_log.append((grad.clone(), self.policy.flat.clone()))
@@ -659,69 +713,27 @@ class VecPPOTrainer:
                               max_norm=hp["max_grad_norm"], gnorm_out=self.gnorm, pmax_out=self.ranges[0:1])
                 if self.record:
                     self.log.append((self.loss_sums.clone(), self.gnorm.clone()))
-        if self._guarded():                # max |param| of the last Adam step -> pinned host memory, read at a later poll
-            if len(self._pmax_queue) == 4:     # the host is four updates ahead of the device: let the oldest copy land
-                self._ranges_evs[self._pmax_queue[0]].synchronize()
-                self.poll_param_range()
-            k = self._pmax_next
-            self._pmax_next = (k + 1) % 4
-            self._ranges_host[k].copy_(self.ranges, non_blocking=True)
-            self._ranges_evs[k].record()
-            self._pmax_queue.append(k)
-            self._buffers_own = False
+        if self._guarded():
+            self._push_param_range()
         return self.loss_sums
-
-    # ------------------------------------------------------------------------------------------ T1
-    def update_curriculum(self):
-        """Feed this iteration's finished episodes to the curriculum (host scalars).  The success bits are
-        compacted on the device; only they cross to the host / the other ranks, so every rank feeds the same
-        global (env, time)-ordered sequence to its replicated curriculum."""
-        if self.curriculum is None:
-            return
-        if self.device_curriculum:             # no host wait: the messages were (or are now) queued, the device does the rest
-            if not self._succ_pending:         # flags not produced by collect(): pack them now
-                self._roll_ev.record()
-                with torch.cuda.stream(self._side):
-                    self._side.wait_event(self._roll_ev)
-                    self._succ_msg = pack_local_successes(self.buf["flags"])
-                    self._pack_ev.record(self._side)
-                self._succ_pending, self._succ_exchanged = True, False
-            if not self._succ_exchanged:
-                self._exchange_successes()
-            self._succ_pending = False
-            self._poll_curriculum_mirror()
-            return
-        if not self._succ_pending:             # flags not produced by collect(): pack and exchange them now
-            msgs = exchange_successes(pack_local_successes(self.buf["flags"]))
-            if tuple(msgs.shape) != tuple(self._succ_host.shape):
-                raise RuntimeError(f"success exchange returned {tuple(msgs.shape)}, expected {tuple(self._succ_host.shape)}: "
-                                   "is torch.distributed initialised for world_size > 1?")
-            self._succ_host.copy_(msgs, non_blocking=True)
-            self._succ_ev.record()
-        elif not self._succ_exchanged:         # collect() without an update() in between
-            self._exchange_successes()
-        self._succ_ev.synchronize()
-        self._succ_pending = False
-        bits = unpack_episode_successes(self._succ_host.numpy(), self.buf["flags"])
-        self._episodes_done += int(bits.size)            # over ALL ranks, in global (env, time) order
-        self._successes_done += int(bits.sum())
-        self.last_success_bits = bits
-        self.curriculum.update_many(bits)
-        self._radius, self._bonus = self.curriculum.current_radius, self.curriculum.explore_bonus
 
     def time_rollouts(self, event_pairs):
         """Measurement hook (bench.py): the next len(event_pairs) calls of train_iteration() record a (start, end) pair of
         torch.cuda.Event around their rollout on the current stream -- the loop that is timed stays train_iteration() itself."""
         self._iter_events = list(event_pairs)[::-1]
 
+    def _after_update(self):
+        """Between update() and update_curriculum() of an iteration (GAILTrainer: the discriminator steps)."""
+
     def train_iteration(self):
-        ev = self._iter_events.pop() if getattr(self, "_iter_events", None) else None
+        ev = self._iter_events.pop() if self._iter_events else None
         if ev is not None:
             ev[0].record()
         self.collect()
         if ev is not None:
             ev[1].record()
         sums = self.update()
+        self._after_update()
         self.update_curriculum()
         self.poll_param_range()
         self.iteration += 1

@@ -301,6 +301,16 @@ int uav_mlp_ppo_grad(uav_ctx* ctx, const float* params, const float* obs, const 
                      int n_act, float inv_n, float clip, float ent_beta, double* loss_sums, float* grad,
                      uav_stream stream);
 
+/* uav_mlp_ppo_grad for the MLP that takes the trend channels as inputs (uav_env_cfg::trend_k, what uav_rollout's policy_kind 2
+ * collects): obs [n][6 + trend_k], params and grad of uav_mlp_param_count(6 + trend_k, 256, 128, 5) floats in uav_mlp_fwd's
+ * layout for in_dim = 6 + trend_k; everything else, the arithmetic modes and their range limit included, as uav_mlp_ppo_grad.
+ * trend_k = 0 runs uav_mlp_ppo_grad's kernel and gives its bits; trend_k outside 0 .. 2 is refused.  The workspace must hold
+ * one gradient slab of that parameter count per workgroup.  The library cannot see how long `params` is: the caller checks.
+ * Added without a change of UAV_ABI_VERSION (a symbol only). */
+int uav_mlp_ppo_grad_trend(uav_ctx* ctx, const float* params, const float* obs, const int32_t* act, const float* logp_old,
+                           const float* adv, const float* ret, const float* val_old, int64_t n, int trend_k, float inv_n,
+                           float clip, float ent_beta, double* loss_sums, float* grad, uav_stream stream);
+
 /* ---- L1: nn.LSTM-semantics sequence kernels (gate order i,f,g,o; bias b_ih+b_hh;
  * PPOV2.0/model.py:206-212, PPOV2.1/model.py:263).  One layer per call.
  * x [N][T][I], keep [N][T] (1 = carry the recurrent state into step t, 0 = restart from zero;
@@ -451,10 +461,13 @@ int uav_env_materialise(uav_ctx* ctx, const void* state, int n_env, const uav_en
  * policy step + sample + env step + store, T steps in one launch; one workgroup owns a tile
  * of envs and keeps h/c in LDS/registers across the time loop.
  * policy_kind 0 = the reference's MLP 6-256-128 (params as uav_mlp_fwd; h, c, keep, stash, y_out unused / NULL; `hidden`
- * ignored), 1 = single-layer LSTM (params: w_ih w_hh b_ih b_hh Whead bhead).  Buffers (env,T,.) : obs [N][T][D], act i32, rew, val, logp, done f32
+ * ignored), 1 = single-layer LSTM (params: w_ih w_hh b_ih b_hh Whead bhead), 2 = the same MLP with 6 + cfg->trend_k inputs
+ * (params as uav_mlp_fwd with in_dim = 6 + trend_k; NULLs as kind 0; with trend_k = 0 it is kind 0's kernel and bits; the value
+ * was added without a change of UAV_ABI_VERSION).  Buffers (env,T,.) : obs [N][T][D], act i32, rew, val, logp, done f32
  * [N][T], flags u8 [N][T].  cur_obs [N][D] in/out (state to act on), h,c [N][H] in/out (LSTM).  D = 6 + cfg->trend_k observation
- * features: the LSTM policy takes trend_k 0, 1 or 2 with w_ih [4H][D] (so w_hh starts at 4H D); the MLP policy has 6 inputs and
- * refuses trend_k != 0.
+ * features: the LSTM policy takes trend_k 0, 1 or 2 with w_ih [4H][D] (so w_hh starts at 4H D); so does the MLP of kind 2 with
+ * W1 [256][D] (every later offset moves with D); the MLP of kind 0 has 6 inputs and refuses trend_k != 0.  The library cannot
+ * see how long `params` is: a caller of kind 2 checks it against uav_mlp_param_count(D, 256, 128, 5).
  * keep [N][T] out (LSTM: 0 where the state restarted), last_val [N] out or NULL (V of the state
  * after the last step, for UAV_GAE_STANDARD).  forced_act i32 [N][T] / noise f64 [N][T][2] are
  * NULL outside parity tests.  stash [N][T][6H] + y_out [N][T][H] (both or neither): the BPTT stash of
@@ -481,13 +494,14 @@ int uav_rollout(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg
  * active[n] = 0 are never stepped.  State (env blob, cur_obs, h, c, active) carries across calls: k calls of steps / k steps
  * give what one call of `steps` gives.
  * policy_kind 0 = the reference's MLP 6-256-128 (params as uav_mlp_fwd; h, c NULL, `hidden` ignored), 1 = single-layer LSTM
- * (params as uav_rollout, w_ih [4H][D]), hidden 64 or 128.  cur_obs f32 [N][D], h, c f32 [N][hidden], active u8 [N]: in/out;
- * D = 6 + cfg->trend_k, trend_k 0, 1 or 2 for the LSTM and 0 for the MLP.
+ * (params as uav_rollout, w_ih [4H][D]), hidden 64 or 128, 2 = the MLP with D inputs (params as uav_mlp_fwd with in_dim = D; h, c
+ * NULL; as uav_rollout's kind 2).  cur_obs f32 [N][D], h, c f32 [N][hidden], active u8 [N]: in/out;
+ * D = 6 + cfg->trend_k, trend_k 0, 1 or 2 for kinds 1 and 2 and 0 for kind 0.
  * Records: act i32 [N][steps], obs f32 [N][steps][D] (the observation the step returned -- the terminal one when done),
  * pos f32 [N][steps][2] (agent_pos after the move), flags u8 [N][steps] (bit0 done, bit1 reached, bit2 not stepped: then
  * act = -1, obs and pos 0).  nan_count (i32, device) += number of stepped env-steps with a NaN logit.
- * Refused (non-zero status, uav_last_error names the reason): a handle not in UAV_ARITH_FP16X3, trend_k != 0 with the MLP
- * policy (the fused MLP kernels take 6 features), hidden not 64 or 128, n_env * steps * D of 2^31 or more. */
+ * Refused (non-zero status, uav_last_error names the reason): a handle not in UAV_ARITH_FP16X3, trend_k != 0 with policy_kind 0
+ * (its MLP takes 6 features; kind 2 takes 6 + trend_k), hidden not 64 or 128, n_env * steps * D of 2^31 or more. */
 int uav_greedy_episodes(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg /*host*/, int policy_kind,
                         const float* params, int hidden, int steps, float* cur_obs, float* h, float* c, uint8_t* active,
                         const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags, int32_t* nan_count,

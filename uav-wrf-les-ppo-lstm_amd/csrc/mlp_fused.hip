@@ -14,6 +14,10 @@
 // of ONE sample and LayerNorm's per-sample reductions are a 4-lane shuffle + one LDS exchange between the 8 waves.
 // Both kernels run the same forward code in the same order: the rollout's log-probabilities are bit-identical to the
 // update's first forward pass.
+//
+// Input width: 6 (the reference's network), or 7 / 8 when the trend channels obs[6 + i] are inputs too (uav_rollout policy_kind 2,
+// uav_mlp_ppo_grad_trend).  Layer 1 is a K = 8 product at every width (two MFMA k-steps, X rows of 8 floats): only the W1 row
+// stride, the offsets behind W1, the observation copies and the place of db1 in the update depend on the width (MlpOff, INW).
 #include "env_core.h"
 #include "loss_core.h"
 #include "stop_rule_core.h"
@@ -51,11 +55,21 @@ constexpr int RS2 = H2 + 8;             // row stride (halves) of the dz2 piece 
 constexpr float LN_EPS_F = 1e-5f;
 constexpr float R_EPS = 1.1920928955078125e-07f;
 
-// flat parameter layout of csrc/mlp.hip: W1 b1 g1 be1 W2 b2 g2 be2 Wh bh
-constexpr int O_W1 = 0, O_B1 = O_W1 + H1 * IN, O_G1 = O_B1 + H1, O_BE1 = O_G1 + H1, O_W2 = O_BE1 + H1,
-              O_B2 = O_W2 + H2 * H1, O_G2 = O_B2 + H2, O_BE2 = O_G2 + H2, O_WH = O_BE2 + H2, O_BH = O_WH + NH * H2,
-              NPARAM = O_BH + NH;
-static_assert(NPARAM == 36230, "MLP parameter count (SURVEY 8a M1)");
+// flat parameter layout of csrc/mlp.hip for `in` input features: W1[256][in] b1 g1 be1 W2 b2 g2 be2 Wh bh.  in = 6 is the
+// reference's network; 7 and 8 carry the trend channels (obs[6 + i], uav_env_cfg::trend_k).  Every offset behind W1 moves
+// with `in`; W2 stays 16-byte aligned at all three widths (256 in + 768 floats).
+struct MlpOff {
+    int W1, B1, G1, BE1, W2, B2, G2, BE2, WH, BH, N;
+    __host__ __device__ constexpr explicit MlpOff(int in)
+        : W1(0), B1(H1 * in), G1(B1 + H1), BE1(G1 + H1), W2(BE1 + H1), B2(W2 + H2 * H1), G2(B2 + H2), BE2(G2 + H2),
+          WH(BE2 + H2), BH(WH + NH * H2), N(BH + NH) {}
+};
+static_assert(MlpOff(IN).N == 36230, "MLP parameter count (SURVEY 8a M1)");
+static_assert(MlpOff(7).W2 % 4 == 0 && MlpOff(8).W2 % 4 == 0, "W2 rows are read as float4");
+constexpr int IN_MAX = 8;               // the observation tile X and the W1 image are [.][8]
+// Input width of a kernel instantiation: INW = 6 is the reference's network with every offset a compile-time constant (the
+// kernels as they were); INW = 0 is ONE instantiation for 7 and 8 inputs with the width read at run time, as rollout.hip's
+// TREND form.
 
 // LDS regions common to both kernels (floats).  NC = column tiles (of 16 samples) a workgroup advances together: 1 in the
 // rollout (16 environments per workgroup keep all 256 CUs busy at 4096 environments), 2 in the update (every weight
@@ -65,7 +79,7 @@ template <int NC>
 struct Tiles {
     static constexpr int MS = MT * NC;
     float* prm;      // b1 g1 be1 [256 each] | b2 g2 be2 [128 each]
-    float* X;        // [MS][8]   observations of the tile, columns 6, 7 zero
+    float* X;        // [MS][8]   observations of the tile, columns from the input width on zero
     float* A1;       // [MS][AS1] a1 = relu(LN1(z1)); later dz1
     float* A2;       // [MS][AS2] a2 = relu(LN2(z2)); later dz2
     double* red;     // [2][8 waves][MS] per-wave partial sums of the LayerNorm reductions
@@ -476,7 +490,7 @@ constexpr size_t ROLL_LDS = (size_t)(Tiles<1>::FLOATS + 16 * WS2) * sizeof(float
 // argmax of the logits, no auto-reset, an ended or inactive env is never stepped.  GREEDY = false is the trainer's rollout.
 // STOP (with GREEDY): evaluate_model.py's stop rule after every env step, as in rollout_lstm_kernel (flags bit3; a hit ends the
 // episode as `done` does).  STOP = false compiles to the kernels as they were.
-template <bool H3, bool GREEDY = false, bool STOP = false>
+template <bool H3, bool GREEDY = false, bool STOP = false, int INW = IN>
 __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBlob blob, int N, int T, uint64_t iter,
                                                             const float* __restrict__ params, MlpRollBufs B) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -498,6 +512,8 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
     EnvParams P = P_arg;
     env_params_refresh(P);
     env_tables_to_lds(P, env_tab, threadIdx.x, 512);
+    const int in = INW ? INW : 6 + P.trend_k;                    // observation features = row stride of cur_obs, obs and W1
+    const MlpOff O(in);
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -509,27 +525,27 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
 
     // ---- parameters
     for (int i = threadIdx.x; i < H1; i += 512) {
-        L.prm[i] = params[O_B1 + i];
-        L.prm[H1 + i] = params[O_G1 + i];
-        L.prm[2 * H1 + i] = params[O_BE1 + i];
+        L.prm[i] = params[O.B1 + i];
+        L.prm[H1 + i] = params[O.G1 + i];
+        L.prm[2 * H1 + i] = params[O.BE1 + i];
     }
     for (int i = threadIdx.x; i < H2; i += 512) {
-        L.prm[3 * H1 + i] = params[O_B2 + i];
-        L.prm[3 * H1 + H2 + i] = params[O_G2 + i];
-        L.prm[3 * H1 + 2 * H2 + i] = params[O_BE2 + i];
+        L.prm[3 * H1 + i] = params[O.B2 + i];
+        L.prm[3 * H1 + H2 + i] = params[O.G2 + i];
+        L.prm[3 * H1 + 2 * H2 + i] = params[O.BE2 + i];
     }
     unsigned short* W2p = reinterpret_cast<unsigned short*>(W2i);   // H3: rows 0..15 as piece fragments [8 slabs][2][64 lanes][8]
     if (H3) {
         for (int i = threadIdx.x; i < 16 * H1; i += 512) {
             const int row = i >> 8, k = i & 255, sl = k >> 5, q8 = (k >> 3) & 3, e = k & 7;
             _Float16 p0, p1;
-            split2h(params[O_W2 + i], p0, p1);
+            split2h(params[O.W2 + i], p0, p1);
             unsigned short* d = W2p + ((sl * 2) * 64 + q8 * 16 + row) * 8 + e;
             d[0] = h_bits(p0);
             d[64 * 8] = h_bits(p1);
         }
     } else {
-        for (int i = threadIdx.x; i < 16 * H1; i += 512) W2i[(i >> 8) * WS2 + (i & 255)] = params[O_W2 + i];
+        for (int i = threadIdx.x; i < 16 * H1; i += 512) W2i[(i >> 8) * WS2 + (i & 255)] = params[O.W2 + i];
     }
     float w1a[2][2], wh[4];
 #pragma unroll
@@ -537,11 +553,11 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
             const int k = 4 * s + kq;
-            w1a[t][s] = k < IN ? params[O_W1 + (32 * w + 16 * t + j) * IN + k] : 0.f;
+            w1a[t][s] = k < in ? params[O.W1 + (32 * w + 16 * t + j) * in + k] : 0.f;
         }
 #pragma unroll
-    for (int s = 0; s < 4; ++s) wh[s] = j < NH ? params[O_WH + j * H2 + 16 * w + 4 * s + kq] : 0.f;
-    const float* bh = params + O_BH;
+    for (int s = 0; s < 4; ++s) wh[s] = j < NH ? params[O.WH + j * H2 + 16 * w + 4 * s + kq] : 0.f;
+    const float* bh = params + O.BH;
 
     bool on = true, ran = true;                                  // GREEDY, wave 0: env active now / at entry
     if (w == 0 && lane < MT) {
@@ -549,7 +565,7 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
         es_s[lane] = env_load(blob, n);
         for (int k = 0; k < NVIS; ++k) myvis[k] = blob.visited[(size_t)n * NVIS + k];
 #pragma unroll
-        for (int f = 0; f < 8; ++f) L.X[lane * 8 + f] = f < IN ? B.cur_obs[(size_t)n * IN + f] : 0.f;
+        for (int f = 0; f < 8; ++f) L.X[lane * 8 + f] = f < in ? B.cur_obs[(size_t)n * in + f] : 0.f;
         if constexpr (GREEDY) on = ran = my_env < N && B.active[n] != 0;
         if constexpr (STOP) sr = stop_ring_load(ring, B.stop_win + (size_t)n * B.rule.window * 2, B.stop_cnt[n], B.rule.window);
     }
@@ -564,7 +580,7 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
         if (H3) {
 #pragma unroll
             for (int sl = 0; sl < H1 / 32; ++sl) {
-                const float* src = params + O_W2 + (16 * w + j) * H1 + 32 * sl + 8 * kq;
+                const float* src = params + O.W2 + (16 * w + j) * H1 + 32 * sl + 8 * kq;
                 const f32x4 v0 = ld4(src), v1 = ld4(src + 4);
                 const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
 #pragma unroll
@@ -576,7 +592,7 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
             }
         } else {
 #pragma unroll
-            for (int s = 0; s < H1 / 16; ++s) wA[s] = ld4(params + O_W2 + (16 * w + j) * H1 + 16 * s + 4 * kq);
+            for (int s = 0; s < H1 / 16; ++s) wA[s] = ld4(params + O.W2 + (16 * w + j) * H1 + 16 * s + 4 * kq);
         }
         for (int t = 0; t < steps; ++t) {
             f32x4 xh1[1][2], xh2[1];
@@ -641,19 +657,19 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
                             }
                             if (env_lane) {
 #pragma unroll
-                                for (int f = 0; f < IN; ++f) B.obs[row * IN + f] = so.obs[f];
+                                for (int f = 0; f < IN_MAX; ++f) if (f < in) B.obs[row * in + f] = so.obs[f];
                                 B.act[row] = a_sel;
                                 B.flags[row] = (uint8_t)((so.done ? 1 : 0) | (so.reached ? 2 : 0) | (hit ? 8 : 0));
                                 B.pos[row * 2] = es.px;
                                 B.pos[row * 2 + 1] = es.py;
                             }
 #pragma unroll
-                            for (int f = 0; f < IN; ++f) L.X[lane * 8 + f] = so.obs[f];
+                            for (int f = 0; f < IN_MAX; ++f) if (f < in) L.X[lane * 8 + f] = so.obs[f];
                             es_s[lane] = es;
                             if (so.done || hit) on = false;
                         } else if (env_lane) {
 #pragma unroll
-                            for (int f = 0; f < IN; ++f) B.obs[row * IN + f] = 0.f;
+                            for (int f = 0; f < IN_MAX; ++f) if (f < in) B.obs[row * in + f] = 0.f;
                             B.act[row] = -1;
                             B.flags[row] = 4;
                             B.pos[row * 2] = 0.f;
@@ -707,7 +723,7 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
                         env_step_core(P, eg, es, myvis, a_sel, wind_x, wind_y, so);
                         if (env_lane) {
 #pragma unroll
-                            for (int f = 0; f < IN; ++f) B.obs[row * IN + f] = L.X[lane * 8 + f];
+                            for (int f = 0; f < IN_MAX; ++f) if (f < in) B.obs[row * in + f] = L.X[lane * 8 + f];
                             B.act[row] = a_sel;
                             B.rew[row] = (float)so.reward;
                             B.val[row] = V;
@@ -735,7 +751,7 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
                             env_obs(P, es, myvis, so.obs);
                         }
 #pragma unroll
-                        for (int f = 0; f < IN; ++f) L.X[lane * 8 + f] = so.obs[f];
+                        for (int f = 0; f < IN_MAX; ++f) if (f < in) L.X[lane * 8 + f] = so.obs[f];
                         es_s[lane] = es;
                     }
                 }
@@ -748,7 +764,7 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
         env_store(blob, my_env, es_s[lane]);
         for (int k = 0; k < NVIS; ++k) blob.visited[(size_t)my_env * NVIS + k] = myvis[k];
 #pragma unroll
-        for (int f = 0; f < IN; ++f) B.cur_obs[(size_t)my_env * IN + f] = L.X[lane * 8 + f];
+        for (int f = 0; f < IN_MAX; ++f) if (f < in) B.cur_obs[(size_t)my_env * in + f] = L.X[lane * 8 + f];
         if constexpr (STOP)
             B.stop_cnt[my_env] = stop_ring_store(ring, sr, B.stop_win + (size_t)my_env * B.rule.window * 2, B.rule.window);
     }
@@ -765,18 +781,24 @@ constexpr int LS_STRIDE = 10;             // doubles per loss lane: policy / val
 // + (H3) P2 [2 pieces][MS][RS2] dz2 as scaled fp16 planes, MX [8 waves][MS] per-sample maxima for their scale
 constexpr int UPD_FLOATS = Tiles<UNC>::FLOATS + 2 * H1 + 3 * H2 + UMS * 8 + 2 * UMS * LS_STRIDE + H1 * 8 + 8 * H2 + UMS * RS2 + NWAVE * UMS + UMS * RS2;
 constexpr size_t UPD_LDS = (size_t)UPD_FLOATS * sizeof(float);
-constexpr int SLAB = NPARAM;            // one gradient slab per workgroup, flat parameter layout
+// one gradient slab per workgroup, flat parameter layout: MlpOff(in).N floats
 
 // H3: the two K = 256 / K = 128 products (layer 2 forward, da1 = W2^T dz2) on the fp16 matrix pipe at f32 accuracy; `w2t`
 // is then the pre-split weights in MFMA fragment order (mlp_w2_pieces_kernel) instead of the f32 transpose.  dW2 (K = the
 // tile's 32 samples) stays on exact-f32 MFMA: its operands would need a second, transposed set of piece planes.
-template <bool H3>
+// INW = 0 (7 or 8 inputs, `in_rt`): db1 can no longer ride in a spare column of X -- at 8 inputs the 8-float row has none --
+// so X holds the observations only and the dW1 product's B operand takes its column j == 8 from the sample-valid predicate
+// instead of from LDS (the MFMA's B tile has 16 columns, only the LDS row is 8 wide).  The same k-ordered fmaf chain over
+// the tile's samples as the ones column of the 6-input form, so db1 rounds the same way at every width.
+template <bool H3, int INW = IN>
 __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     const float* __restrict__ params, const float* __restrict__ obs, const int32_t* __restrict__ act,
     const float* __restrict__ logp_old, const float* __restrict__ adv, const float* __restrict__ ret,
     const float* __restrict__ val_old, int64_t Bn, float inv_n, float clip, float beta, double* __restrict__ loss_partial,
-    float* __restrict__ slabs, const float* __restrict__ w2t) {
+    float* __restrict__ slabs, const float* __restrict__ w2t, int in_rt) {
     constexpr int NC = UNC, MS = UMS;
+    const int in = INW ? INW : in_rt;
+    const MlpOff O(in);
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const Tiles<NC> L(smem);
     float* ACC1 = smem + Tiles<NC>::FLOATS;
@@ -801,30 +823,30 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
 
     // ---- parameters: LayerNorm / bias vectors in LDS, the small weight fragments in registers
     for (int i = threadIdx.x; i < H1; i += 512) {
-        L.prm[i] = params[O_B1 + i];
-        L.prm[H1 + i] = params[O_G1 + i];
-        L.prm[2 * H1 + i] = params[O_BE1 + i];
+        L.prm[i] = params[O.B1 + i];
+        L.prm[H1 + i] = params[O.G1 + i];
+        L.prm[2 * H1 + i] = params[O.BE1 + i];
     }
     for (int i = threadIdx.x; i < H2; i += 512) {
-        L.prm[3 * H1 + i] = params[O_B2 + i];
-        L.prm[3 * H1 + H2 + i] = params[O_G2 + i];
-        L.prm[3 * H1 + 2 * H2 + i] = params[O_BE2 + i];
+        L.prm[3 * H1 + i] = params[O.B2 + i];
+        L.prm[3 * H1 + H2 + i] = params[O.G2 + i];
+        L.prm[3 * H1 + 2 * H2 + i] = params[O.BE2 + i];
     }
     for (int i = threadIdx.x; i < 2 * H1 + 3 * H2; i += 512) ACC1[i] = 0.f;
-    for (int i = threadIdx.x; i < H1 * 8; i += 512) W1L[i] = (i & 7) < IN ? params[O_W1 + (i >> 3) * IN + (i & 7)] : 0.f;
-    for (int i = threadIdx.x; i < 8 * H2; i += 512) WHL[i] = (i / H2) < NH ? params[O_WH + i] : 0.f;
+    for (int i = threadIdx.x; i < H1 * 8; i += 512) W1L[i] = (i & 7) < in ? params[O.W1 + (i >> 3) * in + (i & 7)] : 0.f;
+    for (int i = threadIdx.x; i < 8 * H2; i += 512) WHL[i] = (i / H2) < NH ? params[O.WH + i] : 0.f;
     // W2 is NOT held in registers: the 64 + 64 VGPRs of its two orientations beside the 64 of the dW2 accumulators spill
     // (measured: 85 VGPRs to scratch).  Both orientations are streamed from L2 instead -- 256 KB per 32 samples and CU,
     // dwordx4 per lane thanks to the permuted k order -- W2 row-major for the forward, its transpose (w2t, made once per
     // call) for da1 = W2^T dz2.
-    const float* wfw = params + O_W2 + (16 * w + j) * H1 + 4 * kq;           // forward:  W2[16 w + j][16 s + 4 kq ..]
+    const float* wfw = params + O.W2 + (16 * w + j) * H1 + 4 * kq;           // forward:  W2[16 w + j][16 s + 4 kq ..]
     const float* wbw0 = w2t + (32 * w + j) * H2 + 4 * kq;                    // backward: W2^T[32 w + 16 t + j][16 s + 4 kq ..]
     const float* wbw1 = wbw0 + 16 * H2;
     // H3: fragment-ordered pieces.  forward: [row tile w][8 slabs][2 pieces][64 lanes][8]; backward (after the 64 K halves of
     // the forward set): [row tile 2 w + t][4 slabs][2][64][8]
     const unsigned short* w2f = reinterpret_cast<const unsigned short*>(w2t) + (size_t)w * 8 * 2 * 512 + lane * 8;
     const unsigned short* w2b = reinterpret_cast<const unsigned short*>(w2t) + (size_t)H1 * H2 * 2 + (size_t)(2 * w) * 4 * 2 * 512 + lane * 8;
-    const float* bh = params + O_BH;
+    const float* bh = params + O.BH;
 
     f32x4 dW2[16], dW1[2], dWh;
 #pragma unroll
@@ -845,7 +867,8 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
             const int sj = threadIdx.x >> 3, f = threadIdx.x & 7;
             // column 6 = 1: W1 has no column 6 (the forward multiplies it by zero), and dW1 = dz1^T X then carries
             // db1 = dz1^T 1 in its seventh column for free
-            L.X[threadIdx.x] = (s0 + sj < Bn) ? (f < IN ? obs[(s0 + sj) * IN + f] : (f == IN ? 1.f : 0.f)) : 0.f;
+            if constexpr (INW == IN) L.X[threadIdx.x] = (s0 + sj < Bn) ? (f < IN ? obs[(s0 + sj) * IN + f] : (f == IN ? 1.f : 0.f)) : 0.f;
+            else L.X[threadIdx.x] = (s0 + sj < Bn && f < in) ? obs[(s0 + sj) * in + f] : 0.f;    // no ones column: see above
         }
         int a_s = 0;
         float lpo = 0.f, Ad = 0.f, Rt = 0.f, vo = 0.f;
@@ -1210,7 +1233,8 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
         // ---- dW1 += dz1^T x
 #pragma unroll
         for (int s = 0; s < MS / 4; ++s) {
-            const float b = j < 8 ? L.X[(4 * s + kq) * 8 + j] : 0.f;
+            float b = j < 8 ? L.X[(4 * s + kq) * 8 + j] : 0.f;
+            if constexpr (INW != IN) b = (j == IN_MAX && s0 + 4 * s + kq < Bn) ? 1.f : b;       // column 8 = sample valid: db1
 #pragma unroll
             for (int t = 0; t < 2; ++t) dW1[t] = mfma4(L.A1[(4 * s + kq) * AS1 + 32 * w + 16 * t + j], b, dW1[t]);
         }
@@ -1220,29 +1244,29 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     M_PROF_FLUSH();
 
     // ---- this workgroup's gradient slab (flat parameter layout) and loss partial
-    float* slab = slabs + (size_t)blockIdx.x * SLAB;
+    float* slab = slabs + (size_t)blockIdx.x * O.N;
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
         {
-            if (j < IN) slab[O_W1 + (32 * w + 16 * t + 4 * kq + r) * IN + j] = dW1[t][r];
-            else if (j == IN) slab[O_B1 + 32 * w + 16 * t + 4 * kq + r] = dW1[t][r];       // the ones column: db1
+            if (j < in) slab[O.W1 + (32 * w + 16 * t + 4 * kq + r) * in + j] = dW1[t][r];
+            else if (j == (INW == IN ? IN : IN_MAX)) slab[O.B1 + 32 * w + 16 * t + 4 * kq + r] = dW1[t][r];   // the ones column: db1
         }
 #pragma unroll
     for (int tj = 0; tj < 16; ++tj)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-            slab[O_W2 + (16 * w + 4 * kq + r) * H1 + 16 * tj + j] = H3 ? __builtin_amdgcn_ldexpf(dW2[tj][r], -e_run) : dW2[tj][r];
+            slab[O.W2 + (16 * w + 4 * kq + r) * H1 + 16 * tj + j] = H3 ? __builtin_amdgcn_ldexpf(dW2[tj][r], -e_run) : dW2[tj][r];
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-        if (4 * kq + r < NH) slab[O_WH + (4 * kq + r) * H2 + 16 * w + j] = dWh[r];
+        if (4 * kq + r < NH) slab[O.WH + (4 * kq + r) * H2 + 16 * w + j] = dWh[r];
     // LayerNorm / bias gradients from the per-unit accumulators
     __syncthreads();
-    for (int i = threadIdx.x; i < 2 * H1; i += 512) slab[(i < H1 ? O_G1 : O_BE1) + (i % H1)] = ACC1[i];
+    for (int i = threadIdx.x; i < 2 * H1; i += 512) slab[(i < H1 ? O.G1 : O.BE1) + (i % H1)] = ACC1[i];
     for (int i = threadIdx.x; i < 3 * H2; i += 512) {
         const int q = i / H2, u = i % H2;
-        slab[(q == 0 ? O_G2 : (q == 1 ? O_BE2 : O_B2)) + u] = ACC2[i];
+        slab[(q == 0 ? O.G2 : (q == 1 ? O.BE2 : O.B2)) + u] = ACC2[i];
     }
     if (w == 0) {
         // loss sums and the head-bias gradient: the loss lanes park their partial sums, lane 0 adds them in lane order
@@ -1254,22 +1278,22 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
                 double t = 0.0;
                 for (int sj = 0; sj < MS; ++sj) t += LS[sj * LS_STRIDE + k];
                 pp[k] = t;
-                if (k >= 4) slab[O_BH + k - 4] = (float)t;
+                if (k >= 4) slab[O.BH + k - 4] = (float)t;
             }
         }
     }
 }
 
 // w2t[u1][u2] = W2[u2][u1]  (128 KB; once per gradient call)
-__global__ __launch_bounds__(256) void mlp_w2_transpose_kernel(const float* __restrict__ params, float* __restrict__ w2t) {
+__global__ __launch_bounds__(256) void mlp_w2_transpose_kernel(const float* __restrict__ w2, float* __restrict__ w2t) {
     const int i = blockIdx.x * 256 + threadIdx.x;           // i = u1 * H2 + u2
-    if (i < H1 * H2) w2t[i] = params[O_W2 + (i % H2) * H1 + i / H2];
+    if (i < H1 * H2) w2t[i] = w2[(i % H2) * H1 + i / H2];
 }
 
 // H3: both orientations of W2 as fp16 piece fragments (once per gradient call): forward set [8 row tiles][8 slabs][2][64][8],
 // element (i, kq, e) of fragment (w, s) = W2[16 w + i][32 s + 8 kq + e]; backward set [16 row tiles][4 slabs][2][64][8],
 // element = W2[32 s + 8 kq + e][16 rt + i].
-__global__ __launch_bounds__(256) void mlp_w2_pieces_kernel(const float* __restrict__ params, unsigned short* __restrict__ out) {
+__global__ __launch_bounds__(256) void mlp_w2_pieces_kernel(const float* __restrict__ w2, unsigned short* __restrict__ out) {
     const int i = blockIdx.x * 256 + threadIdx.x;           // over 2 x H1 * H2 elements
     if (i >= 2 * H1 * H2) return;
     const bool bwd = i >= H1 * H2;
@@ -1279,11 +1303,11 @@ __global__ __launch_bounds__(256) void mlp_w2_pieces_kernel(const float* __restr
     size_t o;
     if (!bwd) {
         const int sl = (q >> 9) & 7, wt = q >> 12;
-        v = params[O_W2 + (16 * wt + row) * H1 + 32 * sl + 8 * kq + e];
+        v = w2[(16 * wt + row) * H1 + 32 * sl + 8 * kq + e];
         o = ((size_t)(wt * 8 + sl) * 2) * 512 + lane * 8 + e;
     } else {
         const int sl = (q >> 9) & 3, rt = q >> 11;
-        v = params[O_W2 + (32 * sl + 8 * kq + e) * H1 + 16 * rt + row];
+        v = w2[(32 * sl + 8 * kq + e) * H1 + 16 * rt + row];
         o = (size_t)H1 * H2 * 2 + ((size_t)(rt * 4 + sl) * 2) * 512 + lane * 8 + e;
     }
     _Float16 p0, p1;
@@ -1307,44 +1331,50 @@ __global__ __launch_bounds__(256) void mlp_slab_reduce_kernel(const float* __res
 
 }  // namespace
 
-// ---- entry used by uav_rollout (rollout.hip) for policy_kind 0
-int launch_rollout_mlp(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg, const float* params, int horizon,
-                       uint64_t iter, float* cur_obs, float* obs, int32_t* act, float* rew, float* val, float* logp,
-                       float* done, uint8_t* flags, float* last_val, const int32_t* forced_act, const double* noise,
-                       int32_t* nan_count, float* info, float* heads, hipStream_t st) {
-    EnvParams P;
-    int rc = env_params_from_cfg(ctx, cfg, n_env, P);
-    if (rc) return rc;
-    UAV_REQUIRE(P.trend_k == 0, "uav_rollout: the fused MLP rollout has 6 observation features (trend_k = 0)");
-    MlpRollBufs B{cur_obs, obs, act, rew, val, logp, done, flags, last_val, forced_act, noise, nan_count, info, heads};
-    EnvBlob blob = env_blob_view(env_state, n_env);
-    // the handle's arithmetic (uav_set_lstm_arith): FP16X3 = the 256 x 128 layer on the fp16 matrix pipe (max |param| < 2048);
-    // anything else = exact-f32 MFMA
-    if (ctx->lstm_arith == UAV_ARITH_FP16X3) {
-        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_mlp_kernel<true>), (int)ROLL_LDS));
-        hipLaunchKernelGGL(rollout_mlp_kernel<true>, dim3((n_env + MT - 1) / MT), dim3(512), ROLL_LDS, st, P, blob, n_env, horizon,
-                           iter, params, B);
+// one rollout_mlp_kernel launch in the width the env asks for: 6 inputs = the instantiation with compile-time offsets,
+// 7 / 8 = the run-time-width one
+template <bool H3, bool GREEDY, bool STOP>
+static int launch_rollout_mlp_form(const EnvParams& P, const EnvBlob& blob, int n_env, int steps, uint64_t iter, const float* params,
+                                   const MlpRollBufs& B, hipStream_t st) {
+    const dim3 grid((n_env + MT - 1) / MT);
+    if (P.trend_k == 0) {
+        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_mlp_kernel<H3, GREEDY, STOP>), (int)ROLL_LDS));
+        hipLaunchKernelGGL((rollout_mlp_kernel<H3, GREEDY, STOP>), grid, dim3(512), ROLL_LDS, st, P, blob, n_env, steps, iter, params, B);
     } else {
-        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_mlp_kernel<false>), (int)ROLL_LDS));
-        hipLaunchKernelGGL(rollout_mlp_kernel<false>, dim3((n_env + MT - 1) / MT), dim3(512), ROLL_LDS, st, P, blob, n_env, horizon,
-                           iter, params, B);
+        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_mlp_kernel<H3, GREEDY, STOP, 0>), (int)ROLL_LDS));
+        hipLaunchKernelGGL((rollout_mlp_kernel<H3, GREEDY, STOP, 0>), grid, dim3(512), ROLL_LDS, st, P, blob, n_env, steps, iter, params, B);
     }
     UAV_LAUNCH_CHECK();
     return 0;
 }
 
-// ---- entry used by uav_greedy_episodes (rollout.hip) for policy_kind 0: the fp16-split form only (the caller checked the mode)
+// ---- entry used by uav_rollout (rollout.hip) for policy_kind 0 (`trend` false: 6 inputs only) and 2 (6 + trend_k inputs)
+int launch_rollout_mlp(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg, const float* params, int horizon,
+                       uint64_t iter, float* cur_obs, float* obs, int32_t* act, float* rew, float* val, float* logp,
+                       float* done, uint8_t* flags, float* last_val, const int32_t* forced_act, const double* noise,
+                       int32_t* nan_count, float* info, float* heads, bool trend, hipStream_t st) {
+    EnvParams P;
+    int rc = env_params_from_cfg(ctx, cfg, n_env, P);
+    if (rc) return rc;
+    UAV_REQUIRE(trend || P.trend_k == 0, "uav_rollout: the fused MLP rollout has 6 observation features (trend_k = 0)");
+    UAV_REQUIRE(P.trend_k >= 0 && 6 + P.trend_k <= IN_MAX, "uav_rollout: trend_k=%d (0 .. 2)", P.trend_k);
+    MlpRollBufs B{cur_obs, obs, act, rew, val, logp, done, flags, last_val, forced_act, noise, nan_count, info, heads};
+    EnvBlob blob = env_blob_view(env_state, n_env);
+    // the handle's arithmetic (uav_set_lstm_arith): FP16X3 = the 256 x 128 layer on the fp16 matrix pipe (max |param| < 2048);
+    // anything else = exact-f32 MFMA
+    return ctx->lstm_arith == UAV_ARITH_FP16X3 ? launch_rollout_mlp_form<true, false, false>(P, blob, n_env, horizon, iter, params, B, st)
+                                               : launch_rollout_mlp_form<false, false, false>(P, blob, n_env, horizon, iter, params, B, st);
+}
+
+// ---- entry used by uav_greedy_episodes (rollout.hip) for policy_kind 0 and 2 (the caller checked kind against P.trend_k): the
+// fp16-split form only (the caller checked the mode)
 int launch_greedy_mlp(const EnvParams& P, void* env_state, int n_env, const float* params, int steps, float* cur_obs,
                       uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
                       int32_t* nan_count, hipStream_t st) {
+    UAV_REQUIRE(P.trend_k >= 0 && 6 + P.trend_k <= IN_MAX, "uav_greedy_episodes: trend_k=%d (0 .. 2)", P.trend_k);
     MlpRollBufs B{cur_obs, obs, act, nullptr, nullptr, nullptr, nullptr, flags, nullptr, nullptr, noise, nan_count, nullptr, nullptr,
                   active, pos};
-    EnvBlob blob = env_blob_view(env_state, n_env);
-    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_mlp_kernel<true, true>), (int)ROLL_LDS));
-    hipLaunchKernelGGL((rollout_mlp_kernel<true, true>), dim3((n_env + MT - 1) / MT), dim3(512), ROLL_LDS, st, P, blob, n_env, steps,
-                       0, params, B);
-    UAV_LAUNCH_CHECK();
-    return 0;
+    return launch_rollout_mlp_form<true, true, false>(P, env_blob_view(env_state, n_env), n_env, steps, 0, params, B, st);
 }
 
 // ---- the same with the stop rule (uav_greedy_episodes_stop; the caller checked the rule and its buffers)
@@ -1352,14 +1382,45 @@ int launch_greedy_mlp_stop(const EnvParams& P, void* env_state, int n_env, const
                            uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
                            int32_t* nan_count, const StopRule& rule, float* stop_win, int32_t* stop_cnt, float* rule_val,
                            hipStream_t st) {
+    UAV_REQUIRE(P.trend_k >= 0 && 6 + P.trend_k <= IN_MAX, "uav_greedy_episodes_stop: trend_k=%d (0 .. 2)", P.trend_k);
     MlpRollBufs B{cur_obs, obs, act, nullptr, nullptr, nullptr, nullptr, flags, nullptr, nullptr, noise, nan_count, nullptr, nullptr,
                   active, pos, stop_win, stop_cnt, rule_val, rule};
-    EnvBlob blob = env_blob_view(env_state, n_env);
-    UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&rollout_mlp_kernel<true, true, true>), (int)ROLL_LDS));
-    hipLaunchKernelGGL((rollout_mlp_kernel<true, true, true>), dim3((n_env + MT - 1) / MT), dim3(512), ROLL_LDS, st, P, blob, n_env,
-                       steps, 0, params, B);
+    return launch_rollout_mlp_form<true, true, true>(P, env_blob_view(env_state, n_env), n_env, steps, 0, params, B, st);
+}
+
+// uav_mlp_ppo_grad (in = 6) and uav_mlp_ppo_grad_trend (in = 6 + trend_k): the arguments are checked by the callers
+static int mlp_ppo_grad_impl(const char* who, uav_ctx* ctx, const float* params, const float* obs, const int32_t* act,
+                             const float* logp_old, const float* adv, const float* ret, const float* val_old, int64_t n, int in,
+                             float inv_n, float clip, float ent_beta, double* loss_sums, float* grad, hipStream_t st) {
+    const MlpOff O(in);
+    const int64_t ntile = (n + UMS - 1) / UMS;
+    int nb = ctx->num_cu;
+    if (nb > ntile) nb = (int)ntile;
+    const bool h3 = ctx->lstm_arith == UAV_ARITH_FP16X3;       // the handle's arithmetic (uav_set_lstm_arith); else exact-f32 MFMA
+    const size_t head = 65536, w2t_bytes = (size_t)H1 * H2 * sizeof(float) * 2;  // loss partials | W2^T or both piece sets | slabs
+    UAV_REQUIRE(ctx->ws_bytes >= head + w2t_bytes + (size_t)nb * O.N * sizeof(float), "%s: workspace too small", who);
+    double* partial = (double*)ctx->ws;
+    float* w2t = (float*)((char*)ctx->ws + head);
+    float* slabs = (float*)((char*)ctx->ws + head + w2t_bytes);
+#define LAUNCH_GRAD(H3_, INW_)                                                                                                   \
+    do {                                                                                                                         \
+        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&mlp_ppo_grad_kernel<H3_, INW_>), (int)UPD_LDS));                \
+        hipLaunchKernelGGL((mlp_ppo_grad_kernel<H3_, INW_>), dim3(nb), dim3(512), UPD_LDS, st, params, obs, act, logp_old, adv, ret, \
+                           val_old, n, inv_n, clip, ent_beta, partial, slabs, w2t, in);                                          \
+    } while (0)
+    if (h3) {
+        hipLaunchKernelGGL(mlp_w2_pieces_kernel, dim3(2 * H1 * H2 / 256), dim3(256), 0, st, params + O.W2, reinterpret_cast<unsigned short*>(w2t));
+        if (in == IN) LAUNCH_GRAD(true, IN);
+        else LAUNCH_GRAD(true, 0);
+    } else {
+        hipLaunchKernelGGL(mlp_w2_transpose_kernel, dim3(H1 * H2 / 256), dim3(256), 0, st, params + O.W2, w2t);
+        if (in == IN) LAUNCH_GRAD(false, IN);
+        else LAUNCH_GRAD(false, 0);
+    }
+#undef LAUNCH_GRAD
+    hipLaunchKernelGGL(mlp_slab_reduce_kernel, dim3((O.N + 255) / 256), dim3(256), 0, st, slabs, nb, O.N, grad);
     UAV_LAUNCH_CHECK();
-    return 0;
+    return launch_loss_final(partial, nb, NH, loss_sums, nullptr, st);
 }
 
 extern "C" int uav_mlp_ppo_grad(uav_ctx* ctx, const float* params, const float* obs, const int32_t* act,
@@ -1371,28 +1432,17 @@ extern "C" int uav_mlp_ppo_grad(uav_ctx* ctx, const float* params, const float* 
     UAV_REQUIRE(in_dim == IN && h1 == H1 && h2 == H2 && n_act == NA,
                 "uav_mlp_ppo_grad: the fused kernel is the reference's network (6-256-128, 5 actions); got %d-%d-%d, %d",
                 in_dim, h1, h2, n_act);
-    hipStream_t st = as_stream(stream);
-    const int64_t ntile = (n + UMS - 1) / UMS;
-    int nb = ctx->num_cu;
-    if (nb > ntile) nb = (int)ntile;
-    const bool h3 = ctx->lstm_arith == UAV_ARITH_FP16X3;       // the handle's arithmetic (uav_set_lstm_arith); else exact-f32 MFMA
-    const size_t head = 65536, w2t_bytes = (size_t)H1 * H2 * sizeof(float) * 2;  // loss partials | W2^T or both piece sets | slabs
-    UAV_REQUIRE(ctx->ws_bytes >= head + w2t_bytes + (size_t)nb * SLAB * sizeof(float), "uav_mlp_ppo_grad: workspace too small");
-    double* partial = (double*)ctx->ws;
-    float* w2t = (float*)((char*)ctx->ws + head);
-    float* slabs = (float*)((char*)ctx->ws + head + w2t_bytes);
-    if (h3) {
-        hipLaunchKernelGGL(mlp_w2_pieces_kernel, dim3(2 * H1 * H2 / 256), dim3(256), 0, st, params, reinterpret_cast<unsigned short*>(w2t));
-        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&mlp_ppo_grad_kernel<true>), (int)UPD_LDS));
-        hipLaunchKernelGGL(mlp_ppo_grad_kernel<true>, dim3(nb), dim3(512), UPD_LDS, st, params, obs, act, logp_old, adv, ret, val_old,
-                           n, inv_n, clip, ent_beta, partial, slabs, w2t);
-    } else {
-        hipLaunchKernelGGL(mlp_w2_transpose_kernel, dim3(H1 * H2 / 256), dim3(256), 0, st, params, w2t);
-        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&mlp_ppo_grad_kernel<false>), (int)UPD_LDS));
-        hipLaunchKernelGGL(mlp_ppo_grad_kernel<false>, dim3(nb), dim3(512), UPD_LDS, st, params, obs, act, logp_old, adv, ret, val_old,
-                           n, inv_n, clip, ent_beta, partial, slabs, w2t);
-    }
-    hipLaunchKernelGGL(mlp_slab_reduce_kernel, dim3((SLAB + 255) / 256), dim3(256), 0, st, slabs, nb, SLAB, grad);
-    UAV_LAUNCH_CHECK();
-    return launch_loss_final(partial, nb, NH, loss_sums, nullptr, st);
+    return mlp_ppo_grad_impl("uav_mlp_ppo_grad", ctx, params, obs, act, logp_old, adv, ret, val_old, n, IN, inv_n, clip, ent_beta,
+                             loss_sums, grad, as_stream(stream));
+}
+
+extern "C" int uav_mlp_ppo_grad_trend(uav_ctx* ctx, const float* params, const float* obs, const int32_t* act,
+                                      const float* logp_old, const float* adv, const float* ret, const float* val_old, int64_t n,
+                                      int trend_k, float inv_n, float clip, float ent_beta, double* loss_sums, float* grad,
+                                      uav_stream stream) {
+    UAV_REQUIRE(ctx && params && obs && act && logp_old && adv && ret && val_old && loss_sums && grad && n > 0,
+                "uav_mlp_ppo_grad_trend: bad argument");
+    UAV_REQUIRE(trend_k >= 0 && 6 + trend_k <= IN_MAX, "uav_mlp_ppo_grad_trend: trend_k=%d (0 .. 2)", trend_k);
+    return mlp_ppo_grad_impl("uav_mlp_ppo_grad_trend", ctx, params, obs, act, logp_old, adv, ret, val_old, n, IN + trend_k, inv_n, clip,
+                             ent_beta, loss_sums, grad, as_stream(stream));
 }

@@ -29,7 +29,7 @@ int env_params_from_cfg(const uav_ctx* ctx, const uav_env_cfg* cfg, int n_env, E
 int launch_rollout_mlp(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg, const float* params, int horizon,
                        uint64_t iter, float* cur_obs, float* obs, int32_t* act, float* rew, float* val, float* logp,
                        float* done, uint8_t* flags, float* last_val, const int32_t* forced_act, const double* noise,
-                       int32_t* nan_count, float* info, float* heads, hipStream_t st);
+                       int32_t* nan_count, float* info, float* heads, bool trend, hipStream_t st);
 int launch_greedy_mlp(const EnvParams& P, void* env_state, int n_env, const float* params, int steps, float* cur_obs,
                       uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
                       int32_t* nan_count, hipStream_t st);
@@ -802,11 +802,12 @@ extern "C" int uav_rollout(uav_ctx* ctx, void* env_state, int n_env, const uav_e
     UAV_REQUIRE(ctx && env_state && params && cur_obs && obs && act && rew && val && logp && done && flags && nan_count,
                 "uav_rollout: NULL argument");
     UAV_REQUIRE(n_env > 0 && horizon > 0, "uav_rollout: n_env=%d horizon=%d", n_env, horizon);
-    UAV_REQUIRE(policy_kind == 0 || policy_kind == 1, "uav_rollout: policy_kind %d (0 = MLP, 1 = LSTM)", policy_kind);
-    if (policy_kind == 0) {      // the reference's MLP policy: csrc/mlp_fused.hip
+    UAV_REQUIRE(policy_kind >= 0 && policy_kind <= 2, "uav_rollout: policy_kind %d (0 = MLP, 1 = LSTM, 2 = MLP with 6 + trend_k inputs)",
+                policy_kind);
+    if (policy_kind != 1) {      // the reference's MLP policy (2: with the trend channels as inputs): csrc/mlp_fused.hip
         UAV_REQUIRE(!stash && !y_out, "uav_rollout: stash / y_out belong to the LSTM policy");
         return launch_rollout_mlp(ctx, env_state, n_env, cfg, params, horizon, iter, cur_obs, obs, act, rew, val, logp, done,
-                                  flags, last_val, forced_act, noise, nan_count, info, heads, as_stream(stream));
+                                  flags, last_val, forced_act, noise, nan_count, info, heads, policy_kind == 2, as_stream(stream));
     }
     UAV_REQUIRE(h && c && keep, "uav_rollout: LSTM policy needs h, c, keep");
     EnvParams P;
@@ -834,7 +835,8 @@ static int greedy_episodes_impl(const char* who, uav_ctx* ctx, void* env_state, 
     UAV_REQUIRE(ctx && env_state && params && cur_obs && active && act && obs && pos && flags && nan_count,
                 "%s: NULL argument", who);
     UAV_REQUIRE(n_env > 0 && steps > 0, "%s: n_env=%d steps=%d", who, n_env, steps);
-    UAV_REQUIRE(policy_kind == 0 || policy_kind == 1, "%s: policy_kind %d (0 = MLP, 1 = LSTM)", who, policy_kind);
+    UAV_REQUIRE(policy_kind >= 0 && policy_kind <= 2, "%s: policy_kind %d (0 = MLP, 1 = LSTM, 2 = MLP with 6 + trend_k inputs)", who,
+                policy_kind);
     UAV_REQUIRE(ctx->lstm_arith == UAV_ARITH_FP16X3,
                 "%s: the fused greedy kernels exist in the fp16x3 arithmetic only (handle mode %d)", who, ctx->lstm_arith);
     StopRule R{};
@@ -847,10 +849,10 @@ static int greedy_episodes_impl(const char* who, uav_ctx* ctx, void* env_state, 
     EnvParams P;
     int rc = env_params_from_cfg(ctx, cfg, n_env, P);
     if (rc) return rc;
-    UAV_REQUIRE(policy_kind == 1 || P.trend_k == 0, "%s: trend_k=%d unsupported (the fused MLP kernels take 6 observation features)",
+    UAV_REQUIRE(policy_kind != 0 || P.trend_k == 0, "%s: trend_k=%d unsupported (the fused MLP kernels take 6 observation features)",
                 who, P.trend_k);
     UAV_REQUIRE((int64_t)n_env * steps * (6 + P.trend_k) < (1ll << 31), "%s: n_env * steps too large", who);
-    if (policy_kind == 0)
+    if (policy_kind != 1)
         return rule ? launch_greedy_mlp_stop(P, env_state, n_env, params, steps, cur_obs, active, noise, act, obs, pos, flags,
                                              nan_count, R, stop_win, stop_cnt, rule_val, st)
                     : launch_greedy_mlp(P, env_state, n_env, params, steps, cur_obs, active, noise, act, obs, pos, flags, nan_count, st);

@@ -58,8 +58,9 @@ class ModelEvaluator:
 
     def _load_model(self, path):
         from model import PPOActorCritic
-        model = PPOActorCritic(6, 5, device=self.device)
-        model.load_state_dict(torch.load(path, map_location="cpu"))
+        sd = torch.load(path, map_location="cpu")
+        model = PPOActorCritic(int(sd["feature.0.weight"].shape[1]), 5, device=self.device)      # 6, or 6 + trend_k
+        model.load_state_dict(sd)
         model.eval()
         return model
 

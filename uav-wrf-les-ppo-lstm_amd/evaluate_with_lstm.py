@@ -504,14 +504,15 @@ def main(num_envs=1000, model_dir="model", device="cuda", policy="mlp", threshol
         if policy == "lstm":
             ppo_model = load_lstm_policy(path, device)
         else:
-            ppo_model = PPOActorCritic(6, 5, device=device)
-            ppo_model.load_state_dict(torch.load(path, map_location="cpu"))
+            sd = torch.load(path, map_location="cpu")
+            ppo_model = PPOActorCritic(int(sd["feature.0.weight"].shape[1]), 5, device=device)     # 6, or 6 + TREND_K
+            ppo_model.load_state_dict(sd)
         lstm_model.load_state_dict(torch.load(os.path.join(model_dir, "lstm_threshold_predictor.pth"), map_location="cpu"))
         scaler_params = np.load(os.path.join(model_dir, "scaler_params.npy"))
     except FileNotFoundError as e:
         print(f"model files missing: {e}")
         return None
-    trend_k = ppo_model.obs_dim - 6 if policy == "lstm" else 0
+    trend_k = (ppo_model.obs_dim if policy == "lstm" else ppo_model.core.in_dim) - 6
     env = VecMethaneEnv(num_envs, "v2.0", device, trend_k=trend_k)
     controller = ThresholdController(lstm_model, (scaler_params.min(), scaler_params.max()), num_envs, device=device)
     if policy == "lstm":

@@ -36,12 +36,12 @@ def expert_pairs(cur_obs0, obs_rec, act_rec, flags_rec):
 
 def load_policy(path, device="cuda"):
     """A policy from a checkpoint train_ppo2.0.py writes: the LSTM actor-critic (keys lstm.*) or the reference's MLP
-    (keys feature.*, model.PPOActorCritic)."""
+    (keys feature.*, model.PPOActorCritic; 6 inputs, or 6 + TREND_K read off feature.0.weight)."""
     sd = torch.load(path, map_location="cpu")
     if any(k.startswith("lstm.") for k in sd):
         return load_lstm_policy(path, device)
     from model import PPOActorCritic
-    pol = PPOActorCritic(6, 5, device=device)
+    pol = PPOActorCritic(int(sd["feature.0.weight"].shape[1]), 5, device=device)
     pol.load_state_dict(sd)
     return pol
 
@@ -97,7 +97,7 @@ def generate_expert_data(policy="ppo_model.pth", num_episodes=100, variant=ENV_V
     if isinstance(policy, (str, bytes)) or hasattr(policy, "__fspath__"):
         policy = load_policy(policy, device)
     _, core = policy_core(policy)
-    trend_k = getattr(core, "obs_dim", 6) - 6
+    trend_k = (core.obs_dim if hasattr(core, "obs_dim") else core.in_dim) - 6      # LSTMActorCritic | MLPActorCritic
     env = VecMethaneEnv(num_episodes, variant, core.device, seed=seed, trend_k=trend_k)
     states, actions = expert_pairs(*greedy_records(policy, env, max_steps))
     if out:

@@ -88,6 +88,7 @@ SIGNATURES = {
     "uav_mlp_fwd": (I32, [P, P, P, I64, I32, I32, I32, I32, P, P, P]),
     "uav_mlp_bwd": (I32, [P, P, P, P, P, I64, I32, I32, I32, I32, P, P]),
     "uav_mlp_ppo_grad": (I32, [P, P, P, P, P, P, P, P, I64, I32, I32, I32, I32, F32, F32, F32, P, P, P]),
+    "uav_mlp_ppo_grad_trend": (I32, [P, P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, P, P]),
     "uav_lstm_fwd": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, P, P]),
     "uav_lstm_bwd": (I32, [P, P, P, P, P, P, P, I32, P, P, I32, I32, I32, P, P, P, P, I32, P, P]),
     "uav_lstm_bwd_caps": (I32, [P, I32, I32]),

@@ -9,7 +9,7 @@ import torch
 from . import ops
 
 F32 = torch.float32
-_MLP_SHAPE = (6, 256, 128, 5)            # in, h1, h2, n_act of the fused MLP kernels
+_MLP_SHAPE = (256, 128, 5)               # h1, h2, n_act of the fused MLP kernels; their input width is 6 + trend_k
 
 
 def policy_core(policy):
@@ -49,10 +49,12 @@ def fused_refusal(policy, env):
         if core.obs_dim != 6 + env.trend_k:
             return (f"the policy's obs_dim is {core.obs_dim}, the env's observations have {6 + env.trend_k} features "
                     f"(6 + trend_k, trend_k = {env.trend_k})")
-    elif env.trend_k:
-        return f"trend_k = {env.trend_k}; the fused MLP greedy kernels take 6 observation features"
-    elif (core.in_dim, core.h1, core.h2, core.n_act) != _MLP_SHAPE:
-        return f"MLP {core.in_dim}-{core.h1}-{core.h2}-{core.n_act}; the fused kernel covers 6-256-128-5 only"
+    elif (core.h1, core.h2, core.n_act) != _MLP_SHAPE or not 6 <= core.in_dim <= 8:
+        return (f"MLP {core.in_dim}-{core.h1}-{core.h2}-{core.n_act}; the fused kernel covers (6 + trend_k)-256-128-5 with "
+                f"trend_k 0, 1 or 2 only{trend}")
+    elif core.in_dim != 6 + env.trend_k:
+        return (f"the MLP has {core.in_dim} inputs, the env's observations have {6 + env.trend_k} features "
+                f"(6 + trend_k, trend_k = {env.trend_k})")
     # NaN parameters are not out of range: they reach the kernel and come back as nan_count ("NaN in probs")
     pmax, limit, out = _out_of_range(kind, core)
     if out:
@@ -96,6 +98,7 @@ class GreedyRun:
         N, dev = env.num_envs, env.device
         self.core, self.env, self.rule = core, env, rule
         self.H = core.hidden if kind == "lstm" else 0
+        self.trend = kind != "lstm" and env.trend_k != 0     # an MLP with 6 + trend_k inputs: policy_kind 2
         self.h = torch.zeros(N, self.H, dtype=F32, device=dev) if self.H else None
         self.c = torch.zeros(N, self.H, dtype=F32, device=dev) if self.H else None
         self.active = torch.ones(N, dtype=torch.uint8, device=dev)
@@ -111,10 +114,10 @@ class GreedyRun:
         nz = None if noise is None else noise[t0:t0 + k].transpose(0, 1).contiguous()
         args = (env.state, env.num_envs, env.cfg(), self.core.flat, self.H, k, env.obs, self.h, self.c, self.active, recs)
         if self.rule is None:
-            ops.greedy_episodes(*args, noise=nz, nan_count=self.nan_count)
+            ops.greedy_episodes(*args, noise=nz, nan_count=self.nan_count, trend=self.trend)
         else:
             ops.greedy_episodes_stop(*args, self.rule, self.stop_win, self.stop_cnt, noise=nz, nan_count=self.nan_count,
-                                     rule_val=rule_val)
+                                     rule_val=rule_val, trend=self.trend)
         return recs
 
     def retire(self, active):

@@ -491,6 +491,32 @@ def mlp_ppo_grad(params, obs, act, logp_old, adv, ret, val_old, inv_n, clip, ent
     return grad
 
 
+def mlp_ppo_grad_trend(params, obs, act, logp_old, adv, ret, val_old, inv_n, clip, ent_beta, loss_sums, grad, trend_k):
+    """mlp_ppo_grad for an MLP that takes the trend channels as inputs (uav_mlp_ppo_grad_trend): obs [n, 6 + trend_k],
+    params / grad of mlp_param_count(6 + trend_k) floats, trend_k 0, 1 or 2 (0 is mlp_ppo_grad's kernel and bits)."""
+    n, D = obs.shape[0], 6 + int(trend_k)
+    _mlp_trend_params("mlp_ppo_grad_trend", params, trend_k)
+    _t = KERNEL_TIMER.bracket("mlp_ppo_grad")
+    check(lib().uav_mlp_ppo_grad_trend(_h(obs), _p(params, F32, name="params"), _p(obs, F32, (n, D), "obs"),
+                                       _p(act, I32, (n,), "act"), _p(logp_old, F32, (n,), "logp_old"), _p(adv, F32, (n,), "adv"),
+                                       _p(ret, F32, (n,), "ret"), _p(val_old, F32, (n,), "val_old"), n, int(trend_k), float(inv_n),
+                                       float(clip), float(ent_beta), _p(loss_sums, F64, (4,), "loss_sums"),
+                                       _p(grad, F32, params.shape, "grad"), _stream()), "uav_mlp_ppo_grad_trend")
+    if _t is not None:
+        _t.record()
+    return grad
+
+
+def _mlp_trend_params(who, params, trend_k):
+    """The C ABI cannot see how long `params` is: a 6-input vector read as an 8-input network runs 512 floats past its end."""
+    if not 0 <= int(trend_k) <= 2:
+        raise RuntimeError(f"{who}: trend_k={trend_k} (the fused MLP kernels take 6 + trend_k inputs, trend_k 0, 1 or 2)")
+    want = mlp_param_count(6 + int(trend_k))
+    if params.numel() != want:
+        raise RuntimeError(f"{who}: params has {params.numel()} floats, an MLP with {6 + int(trend_k)} inputs "
+                           f"(trend_k = {int(trend_k)}) has {want}")
+
+
 # ----------------------------------------------------------------------------- E1-E5
 ENV_VARIANTS = {"v2.0": 0, "v2.1": 1, "v1.1": 2}
 ENV_MAX_STEPS = {"v2.0": 1000, "v2.1": 1000, "v1.1": 5000}
@@ -854,13 +880,17 @@ def rollout_lstm(env_state, n_env, cfg, params, hidden, horizon, it, cur_obs, h,
 
 
 def rollout_mlp(env_state, n_env, cfg, params, horizon, it, cur_obs, bufs, last_val=None, forced_act=None, noise=None,
-                nan_count=None, info=None, heads=None):
-    """Fused persistent rollout of the reference's MLP policy (csrc/mlp_fused.hip): uav_rollout with policy_kind 0."""
-    N, T = n_env, horizon
+                nan_count=None, info=None, heads=None, trend=False):
+    """Fused persistent rollout of the reference's MLP policy (csrc/mlp_fused.hip): uav_rollout with policy_kind 0.
+    trend=True: policy_kind 2, the MLP with D = 6 + cfg.trend_k inputs (cur_obs [N,D], obs [N,T,D], params of
+    mlp_param_count(D) floats); with cfg.trend_k = 0 that is kind 0's kernel and bits."""
+    N, T, D = n_env, horizon, 6 + (cfg.trend_k if trend else 0)
+    if trend:
+        _mlp_trend_params("rollout_mlp", params, cfg.trend_k)
     _t = KERNEL_TIMER.bracket("rollout")
-    check(lib().uav_rollout(_h(cur_obs), _p(env_state, U8, name="env state"), N, C.byref(cfg), 0,
-                            _p(params, F32, name="params"), 0, T, int(it), _p(cur_obs, F32, (N, 6), "cur_obs"), None, None,
-                            _p(bufs["obs"], F32, (N, T, 6), "obs"), _p(bufs["act"], I32, (N, T), "act"),
+    check(lib().uav_rollout(_h(cur_obs), _p(env_state, U8, name="env state"), N, C.byref(cfg), 2 if trend else 0,
+                            _p(params, F32, name="params"), 0, T, int(it), _p(cur_obs, F32, (N, D), "cur_obs"), None, None,
+                            _p(bufs["obs"], F32, (N, T, D), "obs"), _p(bufs["act"], I32, (N, T), "act"),
                             _p(bufs["rew"], F32, (N, T), "rew"), _p(bufs["val"], F32, (N, T), "val"),
                             _p(bufs["logp"], F32, (N, T), "logp"), _p(bufs["done"], F32, (N, T), "done"),
                             _p(bufs["flags"], U8, (N, T), "flags"), None, _p(last_val, F32, (N,), "last_val"),
@@ -879,10 +909,12 @@ def greedy_recs(n_env, steps, obs_dim, device):
 
 
 def _greedy(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise, nan_count, rule=None, stop_win=None,
-            stop_cnt=None, rule_val=None):
+            stop_cnt=None, rule_val=None, trend=False):
     """uav_greedy_episodes, or with a `rule` uav_greedy_episodes_stop: the same arguments with the rule's four behind them."""
     N, T, D = n_env, steps, 6 + cfg.trend_k
-    kind = 0 if hidden == 0 else 1
+    kind = (2 if trend else 0) if hidden == 0 else 1
+    if kind == 2:
+        _mlp_trend_params("greedy_episodes", params, cfg.trend_k)
     if nan_count is None:
         nan_count = torch.zeros(1, dtype=I32, device=cur_obs.device)
     symbol, tail = "uav_greedy_episodes", ()
@@ -902,13 +934,15 @@ def _greedy(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active,
         _t.record()
 
 
-def greedy_episodes(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise=None, nan_count=None):
+def greedy_episodes(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise=None, nan_count=None,
+                    trend=False):
     """`steps` steps of greedy evaluation episodes on the fused rollout kernels (uav_greedy_episodes): argmax action, no
     auto-reset, ended / inactive envs frozen.  hidden = 0 (h, c None): the reference's MLP; 64 / 128: the single-layer LSTM.
     cur_obs [N,D], h, c [N,H], active u8 [N] are in/out; recs: dict act i32 [N,steps], obs [N,steps,D], pos [N,steps,2],
     flags u8 [N,steps] (bit0 done, bit1 reached, bit2 not stepped; greedy_recs allocates it); noise f64 [N,steps,2] or None.
-    D = 6 + cfg.trend_k (the LSTM kernels; the MLP kernels take trend_k = 0 only)."""
-    _greedy(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise, nan_count)
+    D = 6 + cfg.trend_k.  The LSTM takes trend_k 0, 1 or 2; the MLP (hidden = 0) takes trend_k = 0, or with trend=True
+    (policy_kind 2) an MLP of D inputs at trend_k 0, 1 or 2, params of mlp_param_count(D) floats."""
+    _greedy(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise, nan_count, trend=trend)
 
 
 STOP_WIN_MAX = 16
@@ -923,14 +957,14 @@ def make_stop_rule(window=10, pos_std_max=2.0, conc_coef=2.0, conc_peak=100.0, c
 
 
 def greedy_episodes_stop(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, rule, stop_win, stop_cnt,
-                         noise=None, nan_count=None, rule_val=None):
+                         noise=None, nan_count=None, rule_val=None, trend=False):
     """greedy_episodes with evaluate_model.py's stop rule applied on the device after every step (uav_greedy_episodes_stop):
     a hit ends the env's episode as `done` does and sets flags bit3 in the step's record.  rule: make_stop_rule(...);
     stop_win f32 [N, window, 2] (the env's last positions, oldest first) and stop_cnt i32 [N] (valid rows) are in/out and
     carry the window across calls (zeros start an episode); rule_val: optional f32 [N, steps], pos_std of every stepped step
-    with a full window, NaN otherwise."""
+    with a full window, NaN otherwise.  trend: as greedy_episodes."""
     _greedy(env_state, n_env, cfg, params, hidden, steps, cur_obs, h, c, active, recs, noise, nan_count, rule, stop_win, stop_cnt,
-            rule_val)
+            rule_val, trend=trend)
 
 
 def stop_stability(rule, pos, obs2, stop_win, stop_cnt, active=None, stop=None, value=None):

@@ -117,9 +117,10 @@ class VecPPOTrainer:
         self.exp_avg_sq = torch.zeros(P, **f32)
         self.opt_step = 0
         self.iteration = 0
-        # the reference's MLP (6-256-128, 5 actions) has fused persistent kernels (csrc/mlp_fused.hip); other sizes, trend
-        # channels and fused_mlp=False take the layer-by-layer path (uav_mlp_fwd / uav_ppo_loss / uav_mlp_bwd + step-wise rollout)
-        self.fused_mlp = policy == "mlp" and D == 6
+        # the reference's MLP (256-128, 5 actions; 6 inputs, or 7 / 8 with the trend channels) has fused persistent kernels
+        # (csrc/mlp_fused.hip); other sizes and fused_mlp=False take the layer-by-layer path (uav_mlp_fwd / uav_ppo_loss /
+        # uav_mlp_bwd + step-wise rollout)
+        self.fused_mlp = policy == "mlp" and 6 <= D <= 8
         self.reuse_rollout_forward = True    # epoch 0 adopts the rollout kernel's stash (same parameters)
         self.use_stepper = True              # h = 256 step-wise rollouts through uav_lstm_stepper_* (A/B switch)
         self.use_fused_tail = True           # ... and heads + sample + env step + store of a step as ONE launch (A/B switch)
@@ -530,7 +531,7 @@ class VecPPOTrainer:
         elif route == "fused_mlp":
             ops.rollout_mlp(self.env_state, self.N, self.env_cfg(), self.policy.flat, self.T, self.iteration, self.cur_obs,
                             self.buf, last_val=self.last_val, forced_act=forced_act, noise=noise, nan_count=self.nan_count,
-                            info=self.info)
+                            info=self.info, trend=self.trend_k != 0)
         elif self.kind == "lstm":
             self._collect_stepwise_lstm(forced_act, noise)
         else:
@@ -678,7 +679,10 @@ class VecPPOTrainer:
         return self.policy.backward(self.dheads, self.work, self.dhead_bias)
 
     def _grad_fused_mlp(self, sl, loss):
-        return ops.mlp_ppo_grad(self.policy.flat, self.buf["obs"][sl].reshape(-1, self.obs_dim), *loss[:8], self.loss_sums, self.policy.grad)
+        obs = self.buf["obs"][sl].reshape(-1, self.obs_dim)
+        if self.trend_k:
+            return ops.mlp_ppo_grad_trend(self.policy.flat, obs, *loss[:8], self.loss_sums, self.policy.grad, self.trend_k)
+        return ops.mlp_ppo_grad(self.policy.flat, obs, *loss[:8], self.loss_sums, self.policy.grad)
 
     def _grad_layered_mlp(self, sl, loss):
         n = self.dheads.shape[0]

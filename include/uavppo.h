@@ -632,6 +632,26 @@ int uav_rollout_tail(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg
                      float* logp_buf, float* keep_buf, float* rew_buf, float* done_buf, uint8_t* flags_buf, int32_t* nan_count,
                      uav_stream stream);
 
+/* The tail of step t of a step-wise GREEDY evaluation as ONE launch (evaluate_with_lstm.py:67-101 after the recurrent layers),
+ * for the policies uav_greedy_episodes does not cover (stacked layers, h = 256, parameters beyond the fp16-split range): for
+ * every env with active[n] != 0, the logits y_t W_head^T + b_head of rows 0 .. n_act-1 of w_head (the sums of uav_gemm_f32's
+ * few-column kernel bit for bit; y = the [n] rows of `hidden` floats y_stride apart), a = the first index of the largest logit
+ * (torch.argmax), one env step WITHOUT auto-reset (cfg as uav_env_step; noise_t f64 [n][2] or NULL: the counter RNG), the stop
+ * rule of uav_greedy_episodes_stop when `rule` is given (NULL: none; stop_win, stop_cnt, rule_val as there, the window updated
+ * in place), and column t of the records of uav_greedy_episodes: act i32 [n][steps], obs f32 [n][steps][D], pos f32 [n][steps][2],
+ * flags u8 [n][steps] (bit0 done, bit1 reached, bit3 stopped by the rule), rule_val f32 [n][steps] or NULL.  The observation goes
+ * to cur_obs [n][D] as well, and active[n] is cleared on done or a hit; the blob stays as that step left it.  An env that comes
+ * in with active[n] = 0 gets the record act = -1, flags = 4 (bit2: not stepped), obs and pos 0, rule_val NaN, and nothing else
+ * of it is read or written.  nan_count += the stepped envs with a NaN logit.  No other column of the records is touched: `steps`
+ * calls with t = 0 .. steps-1 around the layers' step kernels fill what one uav_greedy_episodes(_stop) call fills.
+ * Refused with a reason: a NULL argument, t outside 0 .. steps-1, hidden not a multiple of 4 in 4 .. 256 or rows of y / w_head
+ * not 16-byte aligned, n_act outside 2 .. 6, a rule window outside 1 .. 16, n_env * steps * D of 2^31 or more.  Added without
+ * a change of UAV_ABI_VERSION (a symbol only). */
+int uav_greedy_tail(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg /*host*/, const float* y, int64_t y_stride,
+                    int hidden, const float* w_head, const float* b_head, int n_act, int steps, int t, const double* noise_t,
+                    float* cur_obs, uint8_t* active, int32_t* act, float* obs, float* pos, uint8_t* flags, int32_t* nan_count,
+                    const uav_stop_rule* rule /*host*/, float* stop_win, int32_t* stop_cnt, float* rule_val, uav_stream stream);
+
 /* ---- K9: the iteration's exchanges over RCCL / xGMI (SURVEY 8b `uav_allreduce`, 8e).  One process per GPU, one communicator per
  * handle; RCCL is bound at run time (dlopen librccl.so.1 -- inside a PyTorch process the copy torch already loaded; $UAV_RCCL_LIB
  * overrides), so the library itself has no link-time dependency on it.  A host that is not PyTorch uses these instead of

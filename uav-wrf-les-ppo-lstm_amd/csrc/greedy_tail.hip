@@ -1,0 +1,149 @@
+// greedy_tail.hip -- the tail of ONE step of a step-wise greedy evaluation (evaluate_with_lstm.py's loop for the policies the
+// fused greedy kernels of rollout.hip do not cover: stacked layers, h = 256, parameters beyond the fp16-split range) as one
+// launch behind the per-layer LSTM step kernels: policy heads of the top layer's y, argmax, environment step WITHOUT reset,
+// the optional stop rule, the step's record, the next observation and the env's `active` flag.  A step of such a policy is
+// then L + 2 launches on the steppers (3 L + 1 on the uav_lstm_fwd layers) instead of the few dozen of the torch loop.
+//
+// The greedy twin of rollout_tail_kernel (rollout.hip), with the GREEDY branch of rollout_lstm_kernel as its body: a wave
+// takes four envs, the heads as rows_dot_kernel forms them (rows_dot_core.h: the same sums, so the logits are bit for bit
+// uav_gemm_f32's few-columns form), then lanes 0..3 each carry one env through env_step_kernel's body (env_core.h) and
+// stop_rule_step (stop_rule_core.h; the window in place in stop_win / stop_cnt, as stop_stability_kernel holds it).
+// An env with active[i] = 0 only gets its "not stepped" record; its blob, cur_obs row and window are not touched.
+// Built with the default -ffp-contract=off: it holds env and stop-rule arithmetic.
+#include "env_core.h"
+#include "rows_dot_core.h"
+#include "stop_rule_core.h"
+
+int env_params_from_cfg(const uav_ctx* ctx, const uav_env_cfg* cfg, int n_env, EnvParams& P);
+
+struct GreedyTailBufs {
+    float* cur_obs;             // [N][od] in/out
+    uint8_t* active;            // [N] in/out
+    const double* noise;        // optional [N][2]: this step's standard normals
+    int32_t* act; float* obs; float* pos; uint8_t* flags;      // records [N][steps](, od | 2), written at column t
+    int32_t* nan_count;
+    float* stop_win; int32_t* stop_cnt; float* rule_val;        // with a rule: window [N][window][2] + fill [N] in/out, optional [N][steps]
+};
+
+template <int A>
+__global__ __launch_bounds__(256) void greedy_tail_kernel(EnvParams P, EnvBlob b, int n, const float* __restrict__ y, int64_t ldy,
+                                                          int K, const float* __restrict__ w_head, const float* __restrict__ b_head,
+                                                          int steps, int t, GreedyTailBufs B, bool has_rule, StopRule R) {
+    const int lane = threadIdx.x & 63;
+    const int64_t m0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;
+    if (m0 >= n) return;
+    env_params_refresh(P);
+    RowsDot<8, 1> rd;
+    rd.load_w(w_head, K, A, K, lane);
+    float red[4];
+    rd.rows4(y, ldy, m0, n, K, lane, red);
+    float z[A];
+#pragma unroll
+    for (int o = 0; o < A; ++o) {
+        float v = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float tot = RowsDot<8, 1>::total(red[r], o);
+            if (lane == r) v = tot;
+        }
+        z[o] = v + b_head[o];
+    }
+    const int64_t i64 = m0 + lane;
+    if (lane >= 4 || i64 >= n) return;
+    const int i = (int)i64;
+    const int od = 6 + P.trend_k;
+    const size_t col = (size_t)i * steps + t;
+    if (B.active[i] == 0) {                         // not stepped: act -1, flags bit2, obs and pos 0
+        B.act[col] = -1;
+        B.flags[col] = 4;
+        for (int k = 0; k < od; ++k) B.obs[col * od + k] = 0.f;
+        B.pos[col * 2] = 0.f;
+        B.pos[col * 2 + 1] = 0.f;
+        if (has_rule && B.rule_val) B.rule_val[col] = __builtin_nanf("");
+        return;
+    }
+    // ---- argmax of the logits (torch.argmax: the first of equal maxima)
+    int a_sel = 0;
+    float m = z[0];
+    bool bad = (z[0] != z[0]);
+#pragma unroll
+    for (int a = 1; a < A; ++a) {
+        bad |= (z[a] != z[a]);
+        if (z[a] > m) { m = z[a]; a_sel = a; }
+    }
+    if (bad) atomicAdd(B.nan_count, 1);
+    // ---- env_step_kernel's body without the reset: an ended env stays as its last step left it
+    EnvState s = env_load(b, i);
+    unsigned short* vis = b.visited + (size_t)i * NVIS;
+    const int eg = P.env_offset + i;
+    double z0, z1;
+    if (B.noise) { z0 = B.noise[2 * (size_t)i]; z1 = B.noise[2 * (size_t)i + 1]; }
+    else env_step_noise(P, eg, s, z0, z1);
+    const int a_env = a_sel > 4 ? 4 : a_sel;        // uav_env_step's clamp (n_act = 6 only)
+    StepOut o;
+    double tx, ty;
+    env_step_wind(s, z0, z1, tx, ty);
+    env_step_core(P, eg, s, vis, a_env, tx, ty, o);
+    env_store(b, i, s);
+    // ---- the stop rule on this step's agent_pos and obs[2]
+    bool hit = false;
+    if (has_rule) {
+        float ring[2 * STOP_WIN_MAX];
+        float* win = B.stop_win + (size_t)i * R.window * 2;
+        StopRing sr = stop_ring_load(ring, win, B.stop_cnt[i], R.window);
+        float rv;
+        hit = stop_rule_step(R, ring, sr, s.px, s.py, o.obs[2], B.rule_val != nullptr, rv);
+        B.stop_cnt[i] = stop_ring_store(ring, sr, win, R.window);
+        if (B.rule_val) B.rule_val[col] = rv;
+    }
+    // ---- the record, and what the next step starts from
+    B.act[col] = a_sel;
+    B.flags[col] = (uint8_t)((o.done ? 1 : 0) | (o.reached ? 2 : 0) | (hit ? 8 : 0));
+    for (int k = 0; k < od; ++k) {
+        B.obs[col * od + k] = o.obs[k];
+        B.cur_obs[(size_t)i * od + k] = o.obs[k];
+    }
+    B.pos[col * 2] = s.px;
+    B.pos[col * 2 + 1] = s.py;
+    if (o.done || hit) B.active[i] = 0;
+}
+
+extern "C" int uav_greedy_tail(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg, const float* y, int64_t y_stride,
+                               int hidden, const float* w_head, const float* b_head, int n_act, int steps, int t,
+                               const double* noise_t, float* cur_obs, uint8_t* active, int32_t* act, float* obs, float* pos,
+                               uint8_t* flags, int32_t* nan_count, const uav_stop_rule* rule, float* stop_win, int32_t* stop_cnt,
+                               float* rule_val, uav_stream stream) {
+    UAV_REQUIRE(ctx && env_state && y && w_head && b_head && cur_obs && active && act && obs && pos && flags && nan_count,
+                "uav_greedy_tail: NULL argument");
+    UAV_REQUIRE(n_env > 0 && steps > 0 && t >= 0 && t < steps, "uav_greedy_tail: n_env=%d steps=%d t=%d", n_env, steps, t);
+    UAV_REQUIRE(hidden >= 4 && hidden <= 256 && hidden % 4 == 0 && y_stride % 4 == 0 && y_stride >= hidden &&
+                (reinterpret_cast<uintptr_t>(y) & 15) == 0 && (reinterpret_cast<uintptr_t>(w_head) & 15) == 0,
+                "uav_greedy_tail: hidden %d (a multiple of 4 up to 256), y rows 16-byte aligned", hidden);
+    StopRule R{};
+    if (rule) {
+        UAV_REQUIRE(rule->window >= 1 && rule->window <= STOP_WIN_MAX, "uav_greedy_tail: rule window=%d (1 .. %d)", rule->window,
+                    STOP_WIN_MAX);
+        UAV_REQUIRE(stop_win && stop_cnt, "uav_greedy_tail: NULL stop_win / stop_cnt (the rule's window buffers)");
+        R = StopRule{rule->window, rule->pos_std_max, rule->conc_coef, rule->conc_peak, rule->conc_min};
+    }
+    EnvParams P;
+    int rc = env_params_from_cfg(ctx, cfg, n_env, P);
+    if (rc) return rc;
+    UAV_REQUIRE((int64_t)n_env * steps * (6 + P.trend_k) < (1ll << 31), "uav_greedy_tail: n_env * steps too large");
+    const GreedyTailBufs B{cur_obs, active, noise_t, act, obs, pos, flags, nan_count, stop_win, stop_cnt, rule ? rule_val : nullptr};
+    const dim3 grid((unsigned)((n_env + 15) / 16));
+#define LAUNCH_T(A_)                                                                                                             \
+    hipLaunchKernelGGL(greedy_tail_kernel<A_>, grid, dim3(256), 0, as_stream(stream), P, env_blob_view(env_state, n_env), n_env, \
+                       y, y_stride, hidden, w_head, b_head, steps, t, B, rule != nullptr, R)
+    switch (n_act) {
+        case 2: LAUNCH_T(2); break;
+        case 3: LAUNCH_T(3); break;
+        case 4: LAUNCH_T(4); break;
+        case 5: LAUNCH_T(5); break;
+        case 6: LAUNCH_T(6); break;
+        default: UAV_REQUIRE(false, "uav_greedy_tail: n_act=%d unsupported (2..6)", n_act);
+    }
+#undef LAUNCH_T
+    UAV_LAUNCH_CHECK();
+    return 0;
+}

@@ -10,8 +10,10 @@ The rule runs on the device.  Where the fused greedy-episode kernels cover the p
 the reference's MLP or one LSTM layer of h = 64 / 128, fp16-split arithmetic, parameters in range) whole chunks of steps are
 one launch each of uav_greedy_episodes_stop -- the env lane pushes agent_pos into its window, evaluates the rule and freezes
 the env on a hit -- and the host only reduces the records: an env's episode ends at its first record with flags bit0 (done)
-or bit3 (stopped by the rule).  Every other policy steps one launch sequence per time step, with the rule applied by
-uav_stop_stability (the same device function).  No CPU fallback: everything goes through uavppo.ops.
+or bit3 (stopped by the rule).  Every other LSTM policy (stacked layers, h = 256, parameters out of range: uavppo.greedy.tail_refusal)
+runs the same chunks on the tail route: per env step the layers' step kernels and one uav_greedy_tail launch, which applies the rule
+as the fused kernels do.  What is left steps one launch sequence per time step, with the rule applied by uav_stop_stability (the same
+device function).  No CPU fallback: everything goes through uavppo.ops.
 """
 from __future__ import annotations
 
@@ -20,7 +22,7 @@ import torch
 
 from config import CONC_PEAK, CONC_REWARD_COEF
 from uavppo import ops
-from uavppo.greedy import GreedyRun, fused_refusal, policy_core, stepwise_policy_probs
+from uavppo.greedy import GreedyRun, fused_refusal, policy_core, policy_route, stepwise_policy_probs  # noqa: F401  (fused_refusal: tests)
 
 F32 = torch.float32
 CSV_COLUMNS = ("episode", "steps", "deviation", "success", "final_conc")
@@ -40,7 +42,9 @@ def write_results_csv(path, steps, deviations, success, final_conc):
 class ModelEvaluator:
     """model_path_or_policy: a reference-keyed .pth of PPOActorCritic(6, 5) (as the reference), or a policy object
     (LSTMActorCritic, MLPActorCritic, model.PPOActorCritic).  env: a VecMethaneEnv of `eval_episodes` environments (default:
-    v1.1, procedural fields, radius 50 -- the reference builds a fresh MethaneEnv, no curriculum)."""
+    v1.1, procedural fields, radius 50 -- the reference builds a fresh MethaneEnv, no curriculum).  run_evaluation() takes the
+    fused greedy kernels where they cover the policy, the tail route (the LSTM layers' step kernels + uav_greedy_tail per env step)
+    for every other LSTMActorCritic, and the step-wise loop for what is left; its fused= / tail= keywords force a route."""
 
     def __init__(self, model_path_or_policy, eval_episodes=1000, device="cuda", env=None):
         from uavppo.vec_env import VecMethaneEnv
@@ -68,26 +72,28 @@ class ModelEvaluator:
         return ops.make_stop_rule(self.position_window, self.stability_threshold, CONC_REWARD_COEF, CONC_PEAK, self.conc_threshold)
 
     @torch.no_grad()
-    def run_evaluation(self, noise=None, max_steps=2000, fused=None, chunk=None, csv_path="evaluation_results.csv"):
+    def run_evaluation(self, noise=None, max_steps=2000, fused=None, chunk=None, csv_path="evaluation_results.csv", tail=None):
         """One greedy episode per environment, all together, each until done, the stop rule, or `max_steps` (:52).
         noise: optional f64 [max_steps, N, 2] standard normals (parity tests).  fused: None = the fused kernels where
-        fused_refusal allows, else step-wise; True = fused or a RuntimeError naming why not; False = step-wise.  chunk: steps
-        per fused launch (default 250).  csv_path: where the reference's CSV goes (None: not written).
+        fused_refusal allows, else step-wise; True = fused or a RuntimeError naming why not; False = step-wise.  tail: None = the
+        tail route where the fused kernels refuse the policy and tail_refusal allows; True = the tail route or a RuntimeError naming
+        why not; False = never (fused=False alone still means step-wise).  The tail route gives the step-wise loop's rows: where
+        `done` ends an episode its position is read off the terminal observation, as there.  chunk: steps per fused launch or per
+        host visit of the tail route (default 250).  csv_path: where the reference's CSV goes (None: not written).
         Returns numpy arrays of length N: steps, deviations (f64), success (deviation < current_radius), final_conc (f32,
         (CONC_REWARD_COEF * obs[2]) * CONC_PEAK of the last step) and stopped_early (the rule fired on the last step).
         A NaN logit raises RuntimeError("NaN in probs")."""
         kind, core = _policy_core_checked(self.model)
         env = self.env
-        why = fused_refusal(self.model, env) if fused is not False else "fused=False"
-        if fused and why is not None:
-            raise RuntimeError(f"run_evaluation(fused=True): {why}")
-        if why is not None and chunk is not None:
+        route = policy_route(self.model, env, fused, tail, "run_evaluation")
+        if route == "stepwise" and chunk is not None:
             raise ValueError("run_evaluation(chunk=...): chunks belong to the fused path")
         env.reset()
         _, src, _, _ = env.peek()
         src = src.cpu().numpy()
-        if why is None:
-            steps, pos, obs2, stopped = self._episodes_fused(kind, core, noise, int(max_steps), int(chunk or 250))
+        if route != "stepwise":
+            steps, pos, obs2, stopped = self._episodes_fused(kind, core, noise, int(max_steps), int(chunk or 250),
+                                                             tail=route == "tail")
         else:
             steps, pos, obs2, stopped = self._episodes_stepwise(kind, core, noise, int(max_steps))
         pos, obs2 = pos.cpu().numpy().astype(np.float32), obs2.cpu().numpy().astype(np.float32)
@@ -100,12 +106,15 @@ class ModelEvaluator:
             write_results_csv(csv_path, out["steps"], out["deviations"], out["success"], out["final_conc"])
         return out
 
-    def _episodes_fused(self, kind, core, noise, limit, chunk, want=None):
+    def _episodes_fused(self, kind, core, noise, limit, chunk, want=None, tail=False):
         """Per env: steps, final agent_pos (f32), obs[2] of the last step, stopped-by-the-rule -- reduced from the records of
-        uav_greedy_episodes_stop.  want: optional dict that receives the concatenated records and rule_val (tests)."""
+        uav_greedy_episodes_stop, or with tail=True of GreedyRun's tail backend; the position of a step that ended its episode
+        by `done` is then obs[:2] * 500 of the terminal observation rounded to f32, as _episodes_stepwise takes it (within an
+        ulp of agent_pos), so both give the same rows.  want: optional dict that receives the concatenated records and rule_val
+        (tests)."""
         env = self.env
         N, dev = env.num_envs, env.device
-        run = GreedyRun(kind, core, env, self._rule())
+        run = GreedyRun(kind, core, env, self._rule(), tail=tail)
         active = torch.ones(N, dtype=torch.bool, device=dev)
         steps = torch.zeros(N, dtype=torch.int64, device=dev)
         stopped = torch.zeros(N, dtype=torch.bool, device=dev)
@@ -127,7 +136,11 @@ class ModelEvaluator:
             stopped |= ended & ((recs["flags"][rows, last] & STOPPED) != 0)
             # envs still running took every step of the chunk: their last record is the cap's, should this be the last chunk
             take = active
-            pos = torch.where(take[:, None], recs["pos"][rows, last], pos)
+            p_last = recs["pos"][rows, last]
+            if tail:
+                p_last = torch.where(((recs["flags"][rows, last] & DONE) != 0)[:, None],
+                                     (recs["obs"][rows, last, :2].to(torch.float64) * 500.0).to(F32), p_last)
+            pos = torch.where(take[:, None], p_last, pos)
             obs2 = torch.where(take, recs["obs"][rows, last, 2], obs2)
             active = active & ~ended
             t0 += k

@@ -10,8 +10,11 @@ Python scalars become device tensors of length N.  No CPU fallback: everything g
 evaluate() also takes a policy object (the vectorised trainer's LSTMActorCritic / MLPActorCritic, or model.PPOActorCritic).
 Where uav_greedy_episodes covers it (single-layer LSTM h = 64 / 128 or the reference's MLP, 6 observation features, the
 fp16-split arithmetic, parameters inside that arithmetic's range) whole chunks of steps run in one launch each and the stop
-controllers are replayed over the chunk's records, or (peak_stop_device, threshold_device) run as device scans over them;
-everything else steps one launch sequence per time step.  What the scripts share is in uavppo/greedy.py.
+controllers are replayed over the chunk's records, or (peak_stop_device, threshold_device) run as device scans over them.
+Every other LSTM policy (stacked layers, h = 256, parameters beyond the fp16-split range, the other arithmetic modes) runs the
+same chunk driver on the tail route: per env step the layers' step kernels and ONE uav_greedy_tail launch (heads, argmax, env
+step, record), no host visit inside a chunk.  What is left (other MLPs, policy_probs functions) steps one launch sequence per
+time step.  What the scripts share is in uavppo/greedy.py.
 """
 from __future__ import annotations
 
@@ -23,7 +26,8 @@ import torch
 
 from config import EVALUATE_SIZE, SUCCESS_DISTANCE_THRESHOLD
 from uavppo import ops
-from uavppo.greedy import GreedyRun, fused_refusal, policy_core, stepwise_policy_probs  # noqa: F401  (fused_refusal: tests, docs)
+from uavppo.greedy import (GreedyRun, fused_refusal, policy_core, policy_route, stepwise_policy_probs,  # noqa: F401
+                           tail_refusal)                                    # (fused_refusal, tail_refusal: tests, docs)
 
 F32 = torch.float32
 
@@ -385,7 +389,8 @@ def _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, thresh
 
 @torch.no_grad()
 def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21=20, noise=None, max_steps=None,
-             success_distance=SUCCESS_DISTANCE_THRESHOLD, fused=None, chunk=None, peak_stop_device=False, threshold_device=False):
+             success_distance=SUCCESS_DISTANCE_THRESHOLD, fused=None, chunk=None, peak_stop_device=False, threshold_device=False,
+             tail=None):
     """One greedy episode per environment of `env` (a uavppo VecMethaneEnv), all N together.
 
     policy_probs(obs [N, obs_dim]) -> probs or logits [N, 5] (argmax is taken), or a policy object: LSTMActorCritic,
@@ -395,9 +400,13 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     stopped_early [, peak_pred]) as numpy arrays of length N.
     fused (policy objects): None = uav_greedy_episodes where it covers the policy (fused_refusal), else step-wise (parameters
     beyond the fp16-split range then run in bf16x6); True = the fused kernel or a RuntimeError naming why not; False =
-    step-wise.  chunk: steps per fused launch (default: 250, or 50 with a stop controller, whose rules are replayed over each
-    chunk's records).  A NaN logit of a policy object raises RuntimeError("NaN in probs").  A policy_probs function takes
-    neither fused=True nor chunk.
+    step-wise.  tail (policy objects): None = where the fused kernel refuses the policy and the tail route covers it
+    (tail_refusal: any LSTMActorCritic of 5 actions, hidden a multiple of 4 up to 256), the tail route -- the LSTM layers' step
+    kernels and one uav_greedy_tail per env step under the fused path's chunk driver, the same metric arrays as the step-wise
+    loop bit for bit; True = the tail route or a RuntimeError naming why not; False = never.  fused=False alone still means
+    step-wise, fused=True the fused kernel or an error.  chunk: steps per fused launch, or per host visit of the tail route
+    (default: 250, or 50 with a stop controller, whose rules are replayed over each chunk's records).  A NaN logit of a policy
+    object raises RuntimeError("NaN in probs").  A policy_probs function takes none of fused=True, tail=True and chunk.
     peak_stop_device=True: the PPOV2.1 rule runs on uav_peak_stop_scan -- one scan over all sliding windows of a fused chunk's
     records, or one scan of steps = 1 per env step on the step-wise path.  Same decisions and metrics as the default, which
     evaluates the predictor through uav_lstm_fwd + uav_gemm_f32 (peak_pred agrees to the f32 kernels' rounding); a predictor the
@@ -410,16 +419,16 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     pc, nan = policy_core(policy_probs), None
     if pc is None and fused:
         raise RuntimeError("evaluate(fused=True): a policy_probs function has no fused kernel; pass the policy object")
+    if pc is None and tail:
+        raise RuntimeError("evaluate(tail=True): a policy_probs function has no tail route; pass the policy object")
     if pc is None and chunk is not None:
         raise ValueError("evaluate(chunk=...): chunks belong to the fused path of a policy object")
     if pc is not None:
         kind, core = pc
-        why = fused_refusal(policy_probs, env) if fused is not False else "fused=False"
-        if fused and why is not None:
-            raise RuntimeError(f"evaluate(fused=True): {why}")
-        if why is None:
+        route = policy_route(policy_probs, env, fused, tail, "evaluate")
+        if route != "stepwise":
             return _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
-                                   chunk, peak_stop_device, threshold_device)
+                                   chunk, peak_stop_device, threshold_device, tail=route == "tail")
         policy_probs, nan = stepwise_policy_probs(kind, core, env)
     src, ep, rules, limit = _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, threshold_device, max_steps)
     N, obs = env.num_envs, env.obs
@@ -443,14 +452,14 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
 
 
 def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance, chunk,
-                    peak_stop_device=False, threshold_device=False):
-    """evaluate() on uav_greedy_episodes: `chunk` steps per launch; the metrics (and the stop controllers) are computed from
+                    peak_stop_device=False, threshold_device=False, tail=False):
+    """evaluate() on uav_greedy_episodes: `chunk` steps per launch (tail: on GreedyRun's tail backend, `chunk` steps per host visit); the metrics (and the stop controllers) are computed from
     the records by the step-wise loop's own _StopRules.step / _Episodes.end, so the same actions give the same arrays bit for
     bit.  An env the kernel has ended stays frozen (no auto-reset); an env a rule stopped goes into the next chunk inactive.
     Only while some rule given is NOT on the device (rules.replay) are the records walked step by step, the device rules' per-step
     flags among them; otherwise -- every rule on the device, or none given -- a chunk is one _Episodes.end_chunk."""
     src, ep, rules, limit = _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, threshold_device, max_steps)
-    run = GreedyRun(kind, core, env)
+    run = GreedyRun(kind, core, env, tail=tail)
     chunk = int(chunk or (50 if rules.any else 250))
     t0 = 0
     while t0 < limit:

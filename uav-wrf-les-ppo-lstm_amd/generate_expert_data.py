@@ -3,14 +3,15 @@
 # Counterpart of the reference's PPOV1.1/generate_expert_data.py: num_episodes greedy (argmax) episodes of a trained policy,
 # every (state acted on, action) pair saved as expert_data.npz with the keys `states`, `actions` (:35-58).  The episodes run as
 # that many PARALLEL environments through the evaluation path of evaluate_with_lstm.py: the fused greedy-episode kernels
-# (uav_greedy_episodes) where they cover the policy (fused_refusal), the step-wise loop otherwise; both leave the same records
+# (uav_greedy_episodes) where they cover the policy (fused_refusal), the tail route (the LSTM layers' step kernels + uav_greedy_tail
+# per env step) for every other LSTM policy (tail_refusal), the step-wise loop for what is left; all leave the same records
 # (action, returned observation, flags per step), which expert_pairs() cuts into pairs on the host.
 import numpy as np
 import torch
 
 from config import ENV_VARIANT, SEED
 from evaluate_with_lstm import load_lstm_policy
-from uavppo.greedy import GreedyRun, fused_refusal, policy_core, stepwise_policy_probs
+from uavppo.greedy import GreedyRun, fused_refusal, policy_core, policy_route, stepwise_policy_probs  # noqa: F401  (fused_refusal: tests)
 from uavppo.vec_env import VecMethaneEnv
 
 NOT_STEPPED = 4          # bit 2 of a record's flags (include/uavppo.h, uav_greedy_episodes): the env was not stepped, act = -1
@@ -47,16 +48,18 @@ def load_policy(path, device="cuda"):
 
 
 @torch.no_grad()
-def greedy_records(policy, env, max_steps=None, chunk=250):
+def greedy_records(policy, env, max_steps=None, chunk=250, fused=None, tail=None):
     """One greedy episode per environment of `env`: (reset observations [N, obs_dim], lists of per-chunk obs / act / flags
-    records) as host arrays, in the record format of uav_greedy_episodes whichever path produced them."""
+    records) as host arrays, in the record format of uav_greedy_episodes whichever path produced them.  fused / tail: as
+    evaluate_with_lstm.evaluate (None: the fused kernels, else the tail route, else the step-wise loop)."""
     kind, core = policy_core(policy)
     N, dev = env.num_envs, env.device
     limit = max_steps or env.max_steps
     env.reset()
     cur_obs0 = env.obs.cpu().numpy().copy()
     obs_c, act_c, flags_c = [], [], []
-    run = GreedyRun(kind, core, env) if fused_refusal(policy, env) is None else None
+    route = policy_route(policy, env, fused, tail, "greedy_records")
+    run = GreedyRun(kind, core, env, tail=route == "tail") if route != "stepwise" else None
     if run is None:
         probs, nan = stepwise_policy_probs(kind, core, env)
         active, obs = torch.ones(N, dtype=torch.bool, device=dev), env.obs
@@ -90,16 +93,19 @@ def greedy_records(policy, env, max_steps=None, chunk=250):
 
 
 def generate_expert_data(policy="ppo_model.pth", num_episodes=100, variant=ENV_VARIANT, seed=SEED, max_steps=None,
-                         out="expert_data.npz", device="cuda"):
+                         out="expert_data.npz", device="cuda", fused=None, tail=None):
     """num_episodes greedy episodes of `policy` (an LSTMActorCritic, MLPActorCritic or model.PPOActorCritic, or the path of a
     checkpoint train_ppo2.0.py wrote; the reference loads 'ppo_model.pth') as num_episodes parallel environments seeded with
-    `seed`; every (state, action) pair goes to `out` (None: not written).  Returns (states f32 [M, obs_dim], actions i64 [M])."""
+    `seed`; every (state, action) pair goes to `out` (None: not written).  Returns (states f32 [M, obs_dim], actions i64 [M]).
+    The episodes run on the fused greedy kernels where they cover the policy, on the tail route (uav_greedy_tail behind the LSTM
+    layers' step kernels) for every other LSTM policy, step-wise otherwise: the same pairs on each; fused / tail as
+    evaluate_with_lstm.evaluate force a route."""
     if isinstance(policy, (str, bytes)) or hasattr(policy, "__fspath__"):
         policy = load_policy(policy, device)
     _, core = policy_core(policy)
     trend_k = (core.obs_dim if hasattr(core, "obs_dim") else core.in_dim) - 6      # LSTMActorCritic | MLPActorCritic
     env = VecMethaneEnv(num_episodes, variant, core.device, seed=seed, trend_k=trend_k)
-    states, actions = expert_pairs(*greedy_records(policy, env, max_steps))
+    states, actions = expert_pairs(*greedy_records(policy, env, max_steps, fused=fused, tail=tail))
     if out:
         np.savez(out, states=states, actions=actions)
         print(f"expert data: {num_episodes} episodes, {len(actions)} pairs -> {out}")

@@ -967,6 +967,36 @@ def greedy_episodes_stop(env_state, n_env, cfg, params, hidden, steps, cur_obs, 
             rule_val, trend=trend)
 
 
+def greedy_tail(env_state, cfg, y, w_head, b_head, t, cur_obs, active, recs, nan_count, noise=None, rule=None, stop_win=None,
+                stop_cnt=None, rule_val=None):
+    """uav_greedy_tail: everything of greedy evaluation step t after the recurrent layers in one launch -- the logits of y (the top
+    layer's output, [N, H] or [N, 1, H]; rows may be strided), argmax, the environment step without auto-reset, the stop rule
+    when `rule` (make_stop_rule) is given, and column t of recs (greedy_recs: act / obs / pos / flags [N, steps, ..]) and of
+    rule_val [N, steps].  w_head [A + 1, H] / b_head [A + 1] are the policy's head rows (the critic row is not read).  cur_obs
+    [N, D], active u8 [N], stop_win / stop_cnt are in/out; noise f64 [N, 2] or None.  Inactive envs get the "not stepped" record
+    and are otherwise left alone.  Identical results to gemm_rows + argmax + env_step (+ stop_stability) on envs that run."""
+    N, H = y.shape[0], y.shape[-1]
+    D = 6 + cfg.trend_k
+    T = recs["act"].shape[1]
+    if not y.is_cuda or y.dtype != F32 or y.numel() != N * H or y.stride(-1) != 1:
+        raise RuntimeError(f"y: expected a GPU float32 [N, H] or [N, 1, H] tensor with contiguous rows, got {tuple(y.shape)} {y.dtype}")
+    A1 = w_head.shape[0]
+    tail = (None, None, None, None)
+    if rule is not None:
+        W = int(rule.window)
+        tail = (C.byref(rule), _p(stop_win, F32, (N, W, 2), "stop_win"), _p(stop_cnt, I32, (N,), "stop_cnt"),
+                _p(rule_val, F32, (N, T), "rule_val"))
+    elif rule_val is not None:
+        raise RuntimeError("rule_val belongs to a rule")
+    check(lib().uav_greedy_tail(_h(y), _p(env_state, U8, name="env state"), N, C.byref(cfg), C.c_void_p(y.data_ptr()),
+                                int(y.stride(0)) if N > 1 else H, H, _p(w_head, F32, (A1, H), "w_head"),
+                                _p(b_head, F32, (A1,), "b_head"), A1 - 1, T, int(t), _p(noise, F64, (N, 2), "noise"),
+                                _p(cur_obs, F32, (N, D), "cur_obs"), _p(active, U8, (N,), "active"),
+                                _p(recs["act"], I32, (N, T), "act"), _p(recs["obs"], F32, (N, T, D), "obs"),
+                                _p(recs["pos"], F32, (N, T, 2), "pos"), _p(recs["flags"], U8, (N, T), "flags"),
+                                _p(nan_count, I32, (1,), "nan_count"), *tail, _stream()), "uav_greedy_tail")
+
+
 def stop_stability(rule, pos, obs2, stop_win, stop_cnt, active=None, stop=None, value=None):
     """One step of the stop rule for envs stepped by other means (uav_stop_stability): pos f32 [N, 2] (agent_pos after the
     move), obs2 f32 [N] or a column view such as obs[:, 2] (any element stride), active u8 [N] or None (all).  Updates

@@ -274,10 +274,11 @@ class LSTMActorCritic(_FlatPolicy):
             x = work[f"y{l}"]
         return x
 
-    def step(self, obs, h, c, keep=None, work=None):
+    def step(self, obs, h, c, keep=None, work=None, want_heads=True):
         """One time step for N envs (step-wise rollout of configurations the fused rollout kernel does
         not cover: stacked layers, h = 256).  obs [N, I]; h, c [L, N, H] updated in place; keep [N] or None.
-        Returns heads [N, A+1]."""
+        Returns heads [N, A+1]; with want_heads=False the top layer's output [N, 1, H] instead (a caller that applies the
+        heads itself: uav_greedy_tail)."""
         N = obs.shape[0]
         x = obs.view(N, 1, -1)
         k = None if keep is None else keep.view(N, 1)
@@ -292,6 +293,8 @@ class LSTMActorCritic(_FlatPolicy):
             h[l].copy_(hn)
             c[l].copy_(cn)
             x = y
+        if not want_heads:
+            return x
         return ops.gemm(x.view(N, self.hidden), v["head.weight"], trans_b=True, bias=v["head.bias"])
 
     def backward(self, dheads, work=None, dhead_bias=None):

@@ -35,6 +35,7 @@ typedef void* uav_stream;         /* hipStream_t */
 /* GAE modes (train_ppo2.0.py:18-32 vs PPOV1.0/ppo0.0.py:337-350) */
 #define UAV_GAE_REFERENCE_EXACT 0  /* mask from done[t+1], last step bootstraps from itself */
 #define UAV_GAE_STANDARD        1  /* mask from done[t], bootstrap from last_val            */
+#define UAV_GAE_INLINE_V10      2  /* PPOV1.1/train_ppo1.0.py:75-84: mask from done[t+1]; the last step takes its own done and last_val = V(next_state) */
 
 /* environment variants */
 #define UAV_ENV_V20 0   /* sigma = 500/16, clip 499      PPOV2.0/environment.py:54,105 */
@@ -83,7 +84,9 @@ int uav_absmax(uav_ctx* ctx, const float* x, int64_t n, float* out, uav_stream s
 
 /* ---- G1: GAE scan.  Replaces train_ppo2.0.py:18-32 (one wavefront per env row, affine
  * suffix scan over T with wave shuffles).  rew,val,done,adv: f32 [n_env][horizon].
- * last_val: f32 [n_env] (STANDARD mode) or NULL. */
+ * last_val: f32 [n_env] (STANDARD mode; required in INLINE_V10 mode) or NULL.
+ * INLINE_V10: delta = r + (gamma * next_value) * mask - v in the reference's order, next_value = val[t+1] (last step:
+ * last_val[env]), mask = 1 - done[t+1] (last step: 1 - done[T-1]).  Added without a change of UAV_ABI_VERSION (an enum value only). */
 int uav_gae(uav_ctx* ctx, const float* rew, const float* val, const float* done,
             const float* last_val, int n_env, int horizon, float gamma, float lam, int mode,
             float* adv, uav_stream stream);
@@ -95,6 +98,11 @@ int uav_gae(uav_ctx* ctx, const float* rew, const float* val, const float* done,
 int uav_adv_stats(uav_ctx* ctx, const float* adv, int64_t n, double* stats3, uav_stream stream);
 int uav_adv_normalise(uav_ctx* ctx, const float* adv, const float* val, int64_t n,
                       const double* stats3, float* adv_out, float* ret_out, uav_stream stream);
+/* The inline update's form (PPOV1.1/train_ppo1.0.py:86-89), same stats3 contract: ret_out = adv + val from the RAW
+ * advantage, adv_out = (adv - mean) / (std + 1e-8f) with the unbiased std (the mean subtracted in f64) and NO guard: count == 1 gives NaN as torch's
+ * .std() of one element does, and a constant buffer is divided by 1e-8.  Added without a change of UAV_ABI_VERSION (a symbol only). */
+int uav_adv_normalise_inline(uav_ctx* ctx, const float* adv, const float* val, int64_t n,
+                             const double* stats3, float* adv_out, float* ret_out, uav_stream stream);
 
 /* ---- T1 input (the curriculum of model.py:131-164 consumes one success flag per finished episode): the success bits of
  * the episodes that ended in a rollout, compacted in (env, time) order without a host round trip.  flags u8 [n] as written
@@ -310,6 +318,18 @@ int uav_mlp_ppo_grad(uav_ctx* ctx, const float* params, const float* obs, const 
 int uav_mlp_ppo_grad_trend(uav_ctx* ctx, const float* params, const float* obs, const int32_t* act, const float* logp_old,
                            const float* adv, const float* ret, const float* val_old, int64_t n, int trend_k, float inv_n,
                            float clip, float ent_beta, double* loss_sums, float* grad, uav_stream stream);
+
+/* uav_mlp_ppo_grad_trend over a minibatch of ROWS of the sample buffers (shuffled minibatches, train_ppo1.0.py:93-103): the six
+ * arrays hold n_total samples (obs [n_total][6 + trend_k], ...), rows i32 [n_rows] indexes them, and sample s of the launch is
+ * buffer row rows[s] -- for the observation row and for each of the five per-sample scalars.  Tiles, reduction order, slabs and
+ * loss partials are the contiguous entries': on the same samples in the same order the gradient and loss_sums are bit-identical
+ * to uav_mlp_ppo_grad(_trend) on gathered contiguous copies.  inv_n = 1 / (global sample count of this optimiser step).  An index
+ * outside [0, n_total) is clamped into it (a bad caller gets a wrong gradient, not a device fault); n_total < 2^31.  Both
+ * arithmetic modes, trend_k 0 .. 2.  Added without a change of UAV_ABI_VERSION (a symbol only). */
+int uav_mlp_ppo_grad_rows(uav_ctx* ctx, const float* params, const float* obs, const int32_t* act, const float* logp_old,
+                          const float* adv, const float* ret, const float* val_old, int64_t n_total, const int32_t* rows,
+                          int64_t n_rows, int trend_k, float inv_n, float clip, float ent_beta, double* loss_sums, float* grad,
+                          uav_stream stream);
 
 /* ---- L1: nn.LSTM-semantics sequence kernels (gate order i,f,g,o; bias b_ih+b_hh;
  * PPOV2.0/model.py:206-212, PPOV2.1/model.py:263).  One layer per call.

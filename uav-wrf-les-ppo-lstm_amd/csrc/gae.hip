@@ -8,6 +8,8 @@
 
 // A[t] = b_t + a_t * A[t+1] is an affine map; the suffix composition over a 64-step chunk is a
 // Hillis-Steele scan on (a, b) pairs with wave shuffles:  (a1,b1) o (a2,b2) = (a1*a2, b1 + a1*b2).
+// INLINE (UAV_GAE_INLINE_V10, PPOV1.1/train_ppo1.0.py:75-84) is a template switch, so the two older modes compile as before.
+template <bool INLINE = false>
 __global__ __launch_bounds__(256) void gae_scan_kernel(const float* __restrict__ rew,
                                                        const float* __restrict__ val,
                                                        const float* __restrict__ done,
@@ -36,7 +38,13 @@ __global__ __launch_bounds__(256) void gae_scan_kernel(const float* __restrict__
         if (in) {
             float nnt, nv;
             const bool last = (t == T - 1);
-            if (mode == UAV_GAE_REFERENCE_EXACT) {
+            if constexpr (INLINE) {
+                // train_ppo1.0.py:76-82: mask from done[t+1] and V[t+1]; the last step takes its own done and V(next_state),
+                // and delta = r + (gamma * next_value) * mask - v in that order
+                nnt = 1.0f - (last ? d : d1);
+                nv = (gamma * (last ? last_val[env] : v1)) * nnt;
+                b = (r + nv) - v;
+            } else if (mode == UAV_GAE_REFERENCE_EXACT) {
                 // train_ppo2.0.py:23-28: mask from done[t+1]; the last step uses its own done/value
                 nnt = 1.0f - (last ? d : d1);
                 nv = (last ? v : v1) * nnt;
@@ -44,7 +52,7 @@ __global__ __launch_bounds__(256) void gae_scan_kernel(const float* __restrict__
                 nnt = 1.0f - d;
                 nv = (last ? (last_val ? last_val[env] : 0.f) : v1) * nnt;
             }
-            b = (r + gamma * nv) - v;     // delta, train_ppo2.0.py:30
+            if constexpr (!INLINE) b = (r + gamma * nv) - v;     // delta, train_ppo2.0.py:30
             a = gl * nnt;                 // gamma*lambda*next_non_terminal, :31
         }
 #pragma unroll
@@ -119,6 +127,28 @@ __global__ __launch_bounds__(256) void adv_normalise_kernel(const float* __restr
         const float a = (adv[i] - mean) / den;
         adv_out[i] = a;
         ret_out[i] = a + val[i];                      // :40 returns from the NORMALISED advantage
+    }
+}
+
+// PPOV1.1/train_ppo1.0.py:86-89: returns from the RAW advantage, then (A - mean) / (std + 1e-8) with the unbiased std and no
+// guard -- one sample (cnt == 1) gives 0/0 = NaN as torch does, a constant buffer divides by 1e-8.  The mean is subtracted in
+// f64 from the widened sample (a mean rounded to f32 would move every element by up to 2^-24 |mean| / std, whatever its own
+// size); the kernel is HBM-bound, the conversion is free.
+__global__ __launch_bounds__(256) void adv_normalise_inline_kernel(const float* __restrict__ adv,
+                                                                   const float* __restrict__ val, int64_t n,
+                                                                   const double* __restrict__ stats3,
+                                                                   float* __restrict__ adv_out,
+                                                                   float* __restrict__ ret_out) {
+#pragma clang fp contract(off)
+    const double cnt = stats3[2];
+    const double mean_d = stats3[0] / cnt;
+    const double var = (stats3[1] - cnt * mean_d * mean_d) / (cnt - 1.0);
+    const float sd = (float)sqrt(var > 0.0 ? var : (var == var ? 0.0 : var));
+    const float den = sd + 1e-8f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float a = adv[i];
+        ret_out[i] = a + val[i];
+        adv_out[i] = (float)((double)a - mean_d) / den;
     }
 }
 
@@ -318,12 +348,17 @@ int uav_gae(uav_ctx* ctx, const float* rew, const float* val, const float* done,
             float* adv, uav_stream stream) {
     UAV_REQUIRE(ctx && rew && val && done && adv, "uav_gae: NULL argument");
     UAV_REQUIRE(n_env > 0 && horizon > 0, "uav_gae: n_env=%d horizon=%d", n_env, horizon);
-    UAV_REQUIRE(mode == UAV_GAE_REFERENCE_EXACT || mode == UAV_GAE_STANDARD, "uav_gae: mode %d", mode);
+    UAV_REQUIRE(mode == UAV_GAE_REFERENCE_EXACT || mode == UAV_GAE_STANDARD || mode == UAV_GAE_INLINE_V10, "uav_gae: mode %d", mode);
+    UAV_REQUIRE(mode != UAV_GAE_INLINE_V10 || last_val, "uav_gae: mode UAV_GAE_INLINE_V10 needs last_val (V(next_state))");
     const float gl = (float)((double)gamma * (double)lam);
     // the reference multiplies the python floats first (GAMMA * LAMBDA, f64) then rounds to f32
     const int blocks = (n_env + 3) / 4;
-    hipLaunchKernelGGL(gae_scan_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), rew, val, done,
-                       last_val, n_env, horizon, gamma, gl, mode, adv);
+    if (mode == UAV_GAE_INLINE_V10)
+        hipLaunchKernelGGL(gae_scan_kernel<true>, dim3(blocks), dim3(256), 0, as_stream(stream), rew, val, done,
+                           last_val, n_env, horizon, gamma, gl, mode, adv);
+    else
+        hipLaunchKernelGGL(gae_scan_kernel<false>, dim3(blocks), dim3(256), 0, as_stream(stream), rew, val, done,
+                           last_val, n_env, horizon, gamma, gl, mode, adv);
     UAV_LAUNCH_CHECK();
     return 0;
 }
@@ -349,7 +384,16 @@ int uav_adv_normalise(uav_ctx* ctx, const float* adv, const float* val, int64_t 
     UAV_LAUNCH_CHECK();
     return 0;
 }
-
+int uav_adv_normalise_inline(uav_ctx* ctx, const float* adv, const float* val, int64_t n,
+                             const double* stats3, float* adv_out, float* ret_out, uav_stream stream) {
+    UAV_REQUIRE(ctx && adv && val && stats3 && adv_out && ret_out && n > 0, "uav_adv_normalise_inline: bad argument");
+    int nb = (int)((n + 1023) / 1024);
+    if (nb > 2048) nb = 2048;
+    hipLaunchKernelGGL(adv_normalise_inline_kernel, dim3(nb), dim3(256), 0, as_stream(stream), adv, val, n, stats3,
+                       adv_out, ret_out);
+    UAV_LAUNCH_CHECK();
+    return 0;
+}
 
 int uav_episode_rows(uav_ctx* ctx, const float* rew, const float* info, const uint8_t* flags, int n_env, int T, int env_offset,
                      double* carry, double* rows, int cap, int32_t* count, uav_stream stream) {

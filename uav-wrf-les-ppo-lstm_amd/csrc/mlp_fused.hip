@@ -790,12 +790,15 @@ constexpr size_t UPD_LDS = (size_t)UPD_FLOATS * sizeof(float);
 // so X holds the observations only and the dW1 product's B operand takes its column j == 8 from the sample-valid predicate
 // instead of from LDS (the MFMA's B tile has 16 columns, only the LDS row is 8 wide).  The same k-ordered fmaf chain over
 // the tile's samples as the ones column of the 6-input form, so db1 rounds the same way at every width.
-template <bool H3, int INW = IN>
+// ROWS (uav_mlp_ppo_grad_rows): sample s of the launch is row rows[s] of the Bt-row buffers -- the observation row and the five
+// per-sample scalars are gathered, everything behind the staging is the contiguous form's.  The index of the NEXT tile is
+// fetched with this tile's loads, so a tile's gathers never wait for their index; an index outside [0, Bt) is clamped.
+template <bool H3, int INW = IN, bool ROWS = false>
 __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     const float* __restrict__ params, const float* __restrict__ obs, const int32_t* __restrict__ act,
     const float* __restrict__ logp_old, const float* __restrict__ adv, const float* __restrict__ ret,
     const float* __restrict__ val_old, int64_t Bn, float inv_n, float clip, float beta, double* __restrict__ loss_partial,
-    float* __restrict__ slabs, const float* __restrict__ w2t, int in_rt) {
+    float* __restrict__ slabs, const float* __restrict__ w2t, int in_rt, const int32_t* __restrict__ rows, int64_t Bt) {
     constexpr int NC = UNC, MS = UMS;
     const int in = INW ? INW : in_rt;
     const MlpOff O(in);
@@ -860,6 +863,17 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     int e_run = 100;
     const int64_t ntile = (Bn + MS - 1) / MS;
     M_PROF_DECL;
+    // ROWS: the buffer row of launch sample s (0 past the end: never used), and the rows of this thread's X element / loss sample
+    auto row_of = [&](int64_t s) {
+        int r = s < Bn ? rows[s] : 0;
+        r = r < 0 ? 0 : r;
+        return (int64_t)r < Bt ? r : (int)(Bt - 1);
+    };
+    int rx_next = 0, rl_next = 0;
+    if constexpr (ROWS) {
+        if (threadIdx.x < MS * 8) rx_next = row_of((int64_t)blockIdx.x * MS + (threadIdx.x >> 3));
+        if (w == 0 && lane < MS) rl_next = row_of((int64_t)blockIdx.x * MS + lane);
+    }
     for (int64_t tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
         const int64_t s0 = tile * MS;
         // ---- stage the tile's observations; the loss lanes fetch their per-sample scalars early
@@ -867,14 +881,18 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
             const int sj = threadIdx.x >> 3, f = threadIdx.x & 7;
             // column 6 = 1: W1 has no column 6 (the forward multiplies it by zero), and dW1 = dz1^T X then carries
             // db1 = dz1^T 1 in its seventh column for free
-            if constexpr (INW == IN) L.X[threadIdx.x] = (s0 + sj < Bn) ? (f < IN ? obs[(s0 + sj) * IN + f] : (f == IN ? 1.f : 0.f)) : 0.f;
-            else L.X[threadIdx.x] = (s0 + sj < Bn && f < in) ? obs[(s0 + sj) * in + f] : 0.f;    // no ones column: see above
+            const int64_t rx = ROWS ? (int64_t)rx_next : s0 + sj;
+            if constexpr (INW == IN) L.X[threadIdx.x] = (s0 + sj < Bn) ? (f < IN ? obs[rx * IN + f] : (f == IN ? 1.f : 0.f)) : 0.f;
+            else L.X[threadIdx.x] = (s0 + sj < Bn && f < in) ? obs[rx * in + f] : 0.f;    // no ones column: see above
+            if constexpr (ROWS) rx_next = row_of(s0 + (int64_t)gridDim.x * MS + sj);
         }
         int a_s = 0;
         float lpo = 0.f, Ad = 0.f, Rt = 0.f, vo = 0.f;
         const bool loss_lane = (w == 0) && lane < MS && s0 + lane < Bn;
         if (loss_lane) {
-            a_s = act[s0 + lane]; lpo = logp_old[s0 + lane]; Ad = adv[s0 + lane]; Rt = ret[s0 + lane]; vo = val_old[s0 + lane];
+            const int64_t rl = ROWS ? (int64_t)rl_next : s0 + lane;
+            a_s = act[rl]; lpo = logp_old[rl]; Ad = adv[rl]; Rt = ret[rl]; vo = val_old[rl];
+            if constexpr (ROWS) rl_next = row_of(s0 + (int64_t)gridDim.x * MS + lane);
         }
         lds_barrier();
         M_PROF_MARK(0);
@@ -1388,10 +1406,12 @@ int launch_greedy_mlp_stop(const EnvParams& P, void* env_state, int n_env, const
     return launch_rollout_mlp_form<true, true, true>(P, env_blob_view(env_state, n_env), n_env, steps, 0, params, B, st);
 }
 
-// uav_mlp_ppo_grad (in = 6) and uav_mlp_ppo_grad_trend (in = 6 + trend_k): the arguments are checked by the callers
+// uav_mlp_ppo_grad (in = 6), uav_mlp_ppo_grad_trend (in = 6 + trend_k) and uav_mlp_ppo_grad_rows (rows != nullptr: the n
+// samples are rows[0 .. n) of n_total-row buffers): the arguments are checked by the callers
 static int mlp_ppo_grad_impl(const char* who, uav_ctx* ctx, const float* params, const float* obs, const int32_t* act,
                              const float* logp_old, const float* adv, const float* ret, const float* val_old, int64_t n, int in,
-                             float inv_n, float clip, float ent_beta, double* loss_sums, float* grad, hipStream_t st) {
+                             float inv_n, float clip, float ent_beta, double* loss_sums, float* grad, hipStream_t st,
+                             const int32_t* rows = nullptr, int64_t n_total = 0) {
     const MlpOff O(in);
     const int64_t ntile = (n + UMS - 1) / UMS;
     int nb = ctx->num_cu;
@@ -1402,11 +1422,16 @@ static int mlp_ppo_grad_impl(const char* who, uav_ctx* ctx, const float* params,
     double* partial = (double*)ctx->ws;
     float* w2t = (float*)((char*)ctx->ws + head);
     float* slabs = (float*)((char*)ctx->ws + head + w2t_bytes);
+#define LAUNCH_GRAD_(H3_, INW_, ROWS_)                                                                                           \
+    do {                                                                                                                         \
+        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&mlp_ppo_grad_kernel<H3_, INW_, ROWS_>), (int)UPD_LDS));         \
+        hipLaunchKernelGGL((mlp_ppo_grad_kernel<H3_, INW_, ROWS_>), dim3(nb), dim3(512), UPD_LDS, st, params, obs, act, logp_old, adv, \
+                           ret, val_old, n, inv_n, clip, ent_beta, partial, slabs, w2t, in, rows, n_total);                      \
+    } while (0)
 #define LAUNCH_GRAD(H3_, INW_)                                                                                                   \
     do {                                                                                                                         \
-        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&mlp_ppo_grad_kernel<H3_, INW_>), (int)UPD_LDS));                \
-        hipLaunchKernelGGL((mlp_ppo_grad_kernel<H3_, INW_>), dim3(nb), dim3(512), UPD_LDS, st, params, obs, act, logp_old, adv, ret, \
-                           val_old, n, inv_n, clip, ent_beta, partial, slabs, w2t, in);                                          \
+        if (rows) LAUNCH_GRAD_(H3_, INW_, true);                                                                                 \
+        else LAUNCH_GRAD_(H3_, INW_, false);                                                                                     \
     } while (0)
     if (h3) {
         hipLaunchKernelGGL(mlp_w2_pieces_kernel, dim3(2 * H1 * H2 / 256), dim3(256), 0, st, params + O.W2, reinterpret_cast<unsigned short*>(w2t));
@@ -1418,6 +1443,7 @@ static int mlp_ppo_grad_impl(const char* who, uav_ctx* ctx, const float* params,
         else LAUNCH_GRAD(false, 0);
     }
 #undef LAUNCH_GRAD
+#undef LAUNCH_GRAD_
     hipLaunchKernelGGL(mlp_slab_reduce_kernel, dim3((O.N + 255) / 256), dim3(256), 0, st, slabs, nb, O.N, grad);
     UAV_LAUNCH_CHECK();
     return launch_loss_final(partial, nb, NH, loss_sums, nullptr, st);
@@ -1445,4 +1471,17 @@ extern "C" int uav_mlp_ppo_grad_trend(uav_ctx* ctx, const float* params, const f
     UAV_REQUIRE(trend_k >= 0 && 6 + trend_k <= IN_MAX, "uav_mlp_ppo_grad_trend: trend_k=%d (0 .. 2)", trend_k);
     return mlp_ppo_grad_impl("uav_mlp_ppo_grad_trend", ctx, params, obs, act, logp_old, adv, ret, val_old, n, IN + trend_k, inv_n, clip,
                              ent_beta, loss_sums, grad, as_stream(stream));
+}
+
+extern "C" int uav_mlp_ppo_grad_rows(uav_ctx* ctx, const float* params, const float* obs, const int32_t* act,
+                                     const float* logp_old, const float* adv, const float* ret, const float* val_old,
+                                     int64_t n_total, const int32_t* rows, int64_t n_rows, int trend_k, float inv_n, float clip,
+                                     float ent_beta, double* loss_sums, float* grad, uav_stream stream) {
+    UAV_REQUIRE(ctx && params && obs && act && logp_old && adv && ret && val_old && rows && loss_sums && grad && n_rows > 0,
+                "uav_mlp_ppo_grad_rows: bad argument");
+    UAV_REQUIRE(n_total > 0 && n_total <= 0x7fffffffLL, "uav_mlp_ppo_grad_rows: n_total=%lld (1 .. 2^31 - 1: the indices are i32)",
+                (long long)n_total);
+    UAV_REQUIRE(trend_k >= 0 && 6 + trend_k <= IN_MAX, "uav_mlp_ppo_grad_rows: trend_k=%d (0 .. 2)", trend_k);
+    return mlp_ppo_grad_impl("uav_mlp_ppo_grad_rows", ctx, params, obs, act, logp_old, adv, ret, val_old, n_rows, IN + trend_k, inv_n,
+                             clip, ent_beta, loss_sums, grad, as_stream(stream), rows, n_total);
 }

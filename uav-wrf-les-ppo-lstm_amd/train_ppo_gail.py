@@ -4,8 +4,9 @@
 # rollout's (state, action) pairs from an expert set (generate_expert_data.py), one discriminator step per policy update
 # (:150-175).  Here the loop is uavppo.gail.GAILTrainer over NUM_ENVS vectorised environments, and the discriminator's output
 # is USED: the rollout's reward is env_coef * r + gail_coef * softplus(z) (the reference computes the discriminator and feeds
-# it to nothing).  Not carried over: the V1.0-style inline PPO update of :71-148 (the policy side is the project's
-# _update_model path), the TensorBoard histograms, PPOV1.1/evaluate_model.py.
+# it to nothing).  The policy side is the project's _update_model path by default; --update-form inline_v10 --minibatch-rows B
+# (MLP policy) runs the reference's own inline update of :71-148 -- bootstrapped GAE, returns from the raw advantage, shuffled
+# row minibatches (uavppo/trainer.py).  Not carried over: the TensorBoard histograms.
 import os
 
 import numpy as np
@@ -19,7 +20,8 @@ from uavppo.gail import GAILTrainer
 
 def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert_path="expert_data.npz", policy=POLICY,
                    hidden=HIDDEN, gail_coef=1.0, env_coef=1.0, disc_lr=LEARNING_RATE, disc_steps=1, seed=SEED, device="cuda",
-                   model_path="ppo_gail_model.pth", disc_path="discriminator.pth", max_iterations=None):
+                   model_path="ppo_gail_model.pth", disc_path="discriminator.pth", max_iterations=None, update_form="update_model",
+                   minibatch_rows=None):
     """Run GAILTrainer until num_episodes episodes have finished (the reference trains 2000, train_ppo_gail.py:49) or
     max_iterations rollouts were collected; print the reference's progress line every 10 iterations (:201-203, its
     `episode` read as the iteration); save the policy as ppo_gail_model.pth (:208) and the discriminator as
@@ -28,7 +30,7 @@ def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert
     tr = GAILTrainer(num_envs, horizon, policy, hidden=hidden, layers=NUM_LAYERS, variant=ENV_VARIANT, seed=seed, device=device,
                      gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, gamma=GAMMA, lam=LAMBDA, clip=CLIP_EPSILON,
                      ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, expert=(states, actions), gail_coef=gail_coef,
-                     env_coef=env_coef, disc_lr=disc_lr, disc_steps=disc_steps)
+                     env_coef=env_coef, disc_lr=disc_lr, disc_steps=disc_steps, update_form=update_form, minibatch_rows=minibatch_rows)
     it, mean_rewards = 0, []
     while tr.episodes_lagged < num_episodes and (max_iterations is None or it < max_iterations):
         tr.train_iteration()
@@ -63,11 +65,14 @@ def _main(argv):
     ap.add_argument("--gail-coef", type=float, default=1.0)
     ap.add_argument("--env-coef", type=float, default=1.0)
     ap.add_argument("--max-iterations", type=int, default=None)
+    ap.add_argument("--update-form", default="update_model", choices=("update_model", "inline_v10"))
+    ap.add_argument("--minibatch-rows", type=int, default=None, help="shuffled row minibatches of this size (MLP policy)")
     ap.add_argument("--model-path", default="ppo_gail_model.pth")
     ap.add_argument("--disc-path", default="discriminator.pth")
     a = ap.parse_args(argv)
     train_ppo_gail(a.episodes, a.num_envs, a.horizon, a.expert, a.policy, a.hidden, a.gail_coef, a.env_coef,
-                   max_iterations=a.max_iterations, model_path=a.model_path, disc_path=a.disc_path)
+                   max_iterations=a.max_iterations, model_path=a.model_path, disc_path=a.disc_path, update_form=a.update_form,
+                   minibatch_rows=a.minibatch_rows)
 
 
 if __name__ == "__main__":

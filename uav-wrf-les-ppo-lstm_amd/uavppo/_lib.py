@@ -56,6 +56,7 @@ SIGNATURES = {
     "uav_gae": (I32, [P, P, P, P, P, I32, I32, F32, F32, I32, P, P]),
     "uav_adv_stats": (I32, [P, P, I64, P, P]),
     "uav_adv_normalise": (I32, [P, P, P, I64, P, P, P, P]),
+    "uav_adv_normalise_inline": (I32, [P, P, P, I64, P, P, P, P]),
     "uav_pack_success_bits": (I32, [P, P, I64, I32, P, P]),
     "uav_episode_rows": (I32, [P, P, P, P, I32, I32, I32, P, P, I32, P, P]),
     "uav_curriculum_state_bytes": (SZ, []),
@@ -89,6 +90,7 @@ SIGNATURES = {
     "uav_mlp_bwd": (I32, [P, P, P, P, P, I64, I32, I32, I32, I32, P, P]),
     "uav_mlp_ppo_grad": (I32, [P, P, P, P, P, P, P, P, I64, I32, I32, I32, I32, F32, F32, F32, P, P, P]),
     "uav_mlp_ppo_grad_trend": (I32, [P, P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, P, P]),
+    "uav_mlp_ppo_grad_rows": (I32, [P, P, P, P, P, P, P, P, I64, P, I64, I32, F32, F32, F32, P, P, P]),
     "uav_lstm_fwd": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, P, P]),
     "uav_lstm_bwd": (I32, [P, P, P, P, P, P, P, I32, P, P, I32, I32, I32, P, P, P, P, I32, P, P]),
     "uav_lstm_bwd_caps": (I32, [P, I32, I32]),

@@ -7,9 +7,11 @@ reference trains its discriminator and then uses it nowhere, so its policy never
 rollout's reward is shaped as env_coef * r + gail_coef * softplus(z) = env_coef * r - gail_coef * log(1 - D) before GAE
 (uav_disc_reward).  gail_coef = 0, env_coef = 1 is VecPPOTrainer bit for bit.
 
-Out of scope: the V1.0-style inline PPO update of the reference's GAIL script (value-clipped loss, bootstrap at
-BATCH_SIZE boundaries, shuffled minibatches, train_ppo_gail.py:71-148) -- the policy side is the project's _update_model path;
-the TensorBoard histograms; PPOV1.1/evaluate_model.py; a multi-rank GPU test (the all-reduce is issued, and exercised under the
+The policy side of the reference's GAIL script (train_ppo_gail.py:71-148: bootstrap at BATCH_SIZE boundaries, returns from
+the raw advantage, shuffled row minibatches) is VecPPOTrainer's update_form="inline_v10" + minibatch_rows=B, which GAILTrainer
+inherits (MLP policy); the default stays the project's _update_model path.
+
+Out of scope: the TensorBoard histograms; PPOV1.1/evaluate_model.py; a multi-rank GPU test (the all-reduce is issued, and exercised under the
 one-rank forced-collectives switch only).
 """
 from __future__ import annotations

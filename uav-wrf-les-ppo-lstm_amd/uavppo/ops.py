@@ -10,7 +10,7 @@ import torch
 from . import _lib
 from ._lib import EnvCfg, check, lib
 
-GAE_MODES = {"reference_exact": 0, "standard": 1}
+GAE_MODES = {"reference_exact": 0, "standard": 1, "inline_v10": 2}
 WS_BYTES = 256 << 20
 
 
@@ -128,6 +128,19 @@ def adv_normalise(adv, val, stats3, adv_out=None, ret_out=None):
     check(lib().uav_adv_normalise(_h(adv), _p(adv, F32, name="adv"), _p(val, F32, name="val"), adv.numel(),
                                   _p(stats3, F64, (3,), "stats3"), _p(adv_out, F32, adv.shape, "adv_out"),
                                   _p(ret_out, F32, adv.shape, "ret_out"), _stream()), "uav_adv_normalise")
+    return adv_out, ret_out
+
+
+def adv_normalise_inline(adv, val, stats3, adv_out=None, ret_out=None):
+    """The inline update's normalisation (PPOV1.1/train_ppo1.0.py:86-89): ret_out = adv + val from the RAW advantage,
+    adv_out = (adv - mean) / (std + 1e-8), unbiased std, no guard -- one sample gives NaN, as torch's .std() does."""
+    adv_out = torch.empty_like(adv) if adv_out is None else adv_out
+    ret_out = torch.empty_like(adv) if ret_out is None else ret_out
+    if val.shape != adv.shape:
+        raise RuntimeError("adv_normalise_inline: val/adv shape mismatch")
+    check(lib().uav_adv_normalise_inline(_h(adv), _p(adv, F32, name="adv"), _p(val, F32, name="val"), adv.numel(),
+                                         _p(stats3, F64, (3,), "stats3"), _p(adv_out, F32, adv.shape, "adv_out"),
+                                         _p(ret_out, F32, adv.shape, "ret_out"), _stream()), "uav_adv_normalise_inline")
     return adv_out, ret_out
 
 
@@ -502,6 +515,28 @@ def mlp_ppo_grad_trend(params, obs, act, logp_old, adv, ret, val_old, inv_n, cli
                                        _p(ret, F32, (n,), "ret"), _p(val_old, F32, (n,), "val_old"), n, int(trend_k), float(inv_n),
                                        float(clip), float(ent_beta), _p(loss_sums, F64, (4,), "loss_sums"),
                                        _p(grad, F32, params.shape, "grad"), _stream()), "uav_mlp_ppo_grad_trend")
+    if _t is not None:
+        _t.record()
+    return grad
+
+
+def mlp_ppo_grad_rows(params, obs, act, logp_old, adv, ret, val_old, rows, inv_n, clip, ent_beta, loss_sums, grad, trend_k=0):
+    """mlp_ppo_grad_trend over a minibatch of rows (uav_mlp_ppo_grad_rows): the six arrays hold n_total samples, rows i32
+    [n_rows] indexes them, sample s of the launch is buffer row rows[s].  Bit-identical to the contiguous entries on gathered
+    copies of the same rows in the same order; an index outside [0, n_total) is clamped by the kernel."""
+    n_total, D = obs.shape[0], 6 + int(trend_k)
+    _mlp_trend_params("mlp_ppo_grad_rows", params, trend_k)
+    if rows.dim() != 1 or rows.numel() == 0:
+        raise RuntimeError(f"mlp_ppo_grad_rows: rows must be a non-empty 1-d index tensor, got shape {tuple(rows.shape)}")
+    if n_total >= 2 ** 31:
+        raise RuntimeError(f"mlp_ppo_grad_rows: {n_total} buffer rows do not fit the i32 indices")
+    _t = KERNEL_TIMER.bracket("mlp_ppo_grad")
+    check(lib().uav_mlp_ppo_grad_rows(_h(obs), _p(params, F32, name="params"), _p(obs, F32, (n_total, D), "obs"),
+                                      _p(act, I32, (n_total,), "act"), _p(logp_old, F32, (n_total,), "logp_old"),
+                                      _p(adv, F32, (n_total,), "adv"), _p(ret, F32, (n_total,), "ret"),
+                                      _p(val_old, F32, (n_total,), "val_old"), n_total, _p(rows, I32, name="rows"), rows.numel(),
+                                      int(trend_k), float(inv_n), float(clip), float(ent_beta), _p(loss_sums, F64, (4,), "loss_sums"),
+                                      _p(grad, F32, params.shape, "grad"), _stream()), "uav_mlp_ppo_grad_rows")
     if _t is not None:
         _t.record()
     return grad

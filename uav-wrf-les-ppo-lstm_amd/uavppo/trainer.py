@@ -74,7 +74,8 @@ class _DeviceCurriculumView:
 class VecPPOTrainer:
     def __init__(self, num_envs, horizon, policy="lstm", hidden=128, layers=1, variant="v2.0", device="cuda",
                  seed=1234, gae_mode="reference_exact", num_minibatches=1, bank=None, bank_sources=None,
-                 rank=0, world_size=1, use_curriculum=True, trend_k=0, log_info=False, device_curriculum=None, **hp):
+                 rank=0, world_size=1, use_curriculum=True, trend_k=0, log_info=False, device_curriculum=None,
+                 update_form="update_model", minibatch_rows=None, **hp):
         self.hp = dict(DEFAULTS)
         self.hp.update(hp)
         self.N, self.T = int(num_envs), int(horizon)
@@ -82,8 +83,28 @@ class VecPPOTrainer:
         self._coll = self.world > 1 or collectives_on()          # the three exchanges of an iteration are issued
         self.device = torch.device(device)
         self.variant, self.seed = variant, int(seed)
-        self.gae_mode = gae_mode
+        # update_form "inline_v10": the inline update of PPOV1.1/train_ppo1.0.py:63-141 (also the policy side of
+        # train_ppo_gail.py:71-148) instead of _update_model's arithmetic -- GAE with a real bootstrap V(next_state) on the last
+        # step, returns from the raw advantage, (A - mean) / (std + 1e-8) without a guard.  It sets the GAE mode itself (a gae_mode other than the default beside it is refused).
+        if update_form not in ("update_model", "inline_v10"):
+            raise ValueError(f"update_form {update_form!r}: 'update_model' or 'inline_v10'")
+        if update_form == "inline_v10" and gae_mode not in ("reference_exact", "inline_v10"):
+            raise ValueError(f"update_form='inline_v10' runs its own GAE (uav_gae mode inline_v10); gae_mode={gae_mode!r} would be ignored")
+        self.update_form = update_form
+        self.gae_mode = "inline_v10" if update_form == "inline_v10" else gae_mode
         self.num_minibatches = int(num_minibatches)
+        # minibatch_rows = B: every epoch one permutation of this rank's N * T sample rows, cut into chunks of B (the last one
+        # shorter, as Tensor.split), each chunk one optimiser step (train_ppo1.0.py:92-136) through uav_mlp_ppo_grad_rows
+        self.minibatch_rows = None if minibatch_rows is None else int(minibatch_rows)
+        if self.minibatch_rows is not None:
+            if self.num_minibatches != 1:
+                raise ValueError("num_minibatches and minibatch_rows are two ways to cut the buffer: give one of them")
+            if self.minibatch_rows < 1:
+                raise ValueError(f"minibatch_rows={minibatch_rows}: a positive row count")
+            if policy != "mlp" or not 6 <= 6 + int(trend_k) <= 8:
+                raise ValueError("minibatch_rows needs the MLP policy on the fused path (6-256-128 with trend_k 0..2): only "
+                                 "uav_mlp_ppo_grad_rows reads its samples through a row index; an LSTM's samples are whole "
+                                 "env sequences")
         if self.N % self.num_minibatches:
             raise ValueError("num_envs must be divisible by num_minibatches (minibatches are whole env sequences)")
         self.kind = policy
@@ -106,7 +127,7 @@ class VecPPOTrainer:
         self.adv = torch.zeros(N, T, **f32)
         self.adv_n = torch.zeros(N, T, **f32)
         self.ret = torch.zeros(N, T, **f32)
-        self.last_val = torch.zeros(N, **f32) if gae_mode == "standard" else None
+        self.last_val = torch.zeros(N, **f32) if self.gae_mode in ("standard", "inline_v10") else None
         self.stats3 = torch.zeros(3, dtype=torch.float64, device=d)
         self.loss_sums = torch.zeros(4, dtype=torch.float64, device=d)
         self.gnorm = torch.zeros(1, **f32)
@@ -129,6 +150,9 @@ class VecPPOTrainer:
         self.record_grads = False    # tests: ... and the (all-reduced, unclipped) flat gradient of every optimiser step + its parameters
         self.log = []
         self.grad_log = []
+        self.forced_perms = None     # tests: list of index tensors [N * T], consumed in order instead of the drawn permutations
+        self._perm_gen = None        # device generator of the row permutations, seeded by (seed, rank) on first use
+        self._last_n = (self.N // self.num_minibatches) * self.T      # local samples of the last optimiser step (losses())
         # range guard of the fp16-split kernels: device maxima [|param|, |obs|, |h0|], mirrored to pinned host memory
         self.ranges = torch.zeros(3, **f32)
         self._ranges_host = torch.zeros(4, 3, dtype=torch.float32).pin_memory()      # ring: the host may run iterations ahead
@@ -658,7 +682,8 @@ class VecPPOTrainer:
         ops.gae(self._gae_reward(), b["val"], b["done"], hp["gamma"], hp["lam"], self.gae_mode, last_val=self.last_val, out=self.adv)
         ops.adv_stats(self.adv, out=self.stats3)
         allreduce_adv_stats(self.stats3)          # (sum, sumsq, count): whole-buffer statistics over all ranks
-        ops.adv_normalise(self.adv, b["val"], self.stats3, self.adv_n, self.ret)
+        normalise = ops.adv_normalise_inline if self.update_form == "inline_v10" else ops.adv_normalise
+        normalise(self.adv, b["val"], self.stats3, self.adv_n, self.ret)
 
     # ------------------------------------------------------------------------------------------ U1-U3
     # minibatch slice -> flat gradient, one routine per policy kind (loss: the arguments of the loss kernel after the heads)
@@ -692,8 +717,44 @@ class VecPPOTrainer:
         ops.ppo_loss_heads(heads, *loss)
         return self.policy.backward(self.dheads)
 
+    def _next_perm(self):
+        """One permutation of this rank's N * T sample rows (row = env * T + t) as i32 on the device."""
+        L = self.N * self.T
+        if self.forced_perms is not None:
+            perm = torch.as_tensor(self.forced_perms.pop(0)).to(self.device).reshape(-1)
+            if perm.numel() != L:
+                raise ValueError(f"forced_perms: a permutation of {perm.numel()} rows for a buffer of {L}")
+        else:
+            if self._perm_gen is None:
+                self._perm_gen = torch.Generator(device=self.device).manual_seed(self.seed * 1000003 + self.rank)
+            perm = torch.randperm(L, generator=self._perm_gen, device=self.device)
+        return perm.to(torch.int32)
+
+    def _optimiser_step(self, grad):
+        hp = self.hp
+        allreduce_grad(grad)              # RCCL sum over ranks; inv_n already holds 1/global count
+        if self.record_grads:            # (gradient, parameters it was taken at)
+            self.grad_log.append((grad.clone(), self.policy.flat.clone()))
+        self.opt_step += 1
+        ops.clip_adam(self.policy.flat, grad, self.exp_avg, self.exp_avg_sq, self.opt_step, hp["lr"],
+                      max_norm=hp["max_grad_norm"], gnorm_out=self.gnorm, pmax_out=self.ranges[0:1])
+        if self.record:
+            self.log.append((self.loss_sums.clone(), self.gnorm.clone()))
+
+    def _epoch_rows(self):
+        """One epoch in shuffled row minibatches: every rank cuts its own permutation into the same number of chunks, so the
+        gradient all-reduces pair up; inv_n = 1 / (len(chunk) * world)."""
+        b, hp = self.buf, self.hp
+        flat = [b["obs"].view(-1, self.obs_dim)] + [x.view(-1) for x in (b["act"], b["logp"], self.adv_n, self.ret, b["val"])]
+        for rows in self._next_perm().split(self.minibatch_rows):
+            self._last_n = rows.numel()
+            grad = ops.mlp_ppo_grad_rows(self.policy.flat, *flat, rows.contiguous(), 1.0 / float(rows.numel() * self.world),
+                                         hp["clip"], hp["ent_beta"], self.loss_sums, self.policy.grad, self.trend_k)
+            self._optimiser_step(grad)
+
     def update(self):
-        """GAE + EPOCHS x num_minibatches optimiser steps (_update_model, train_ppo2.0.py:15-88)."""
+        """GAE + EPOCHS x num_minibatches optimiser steps (_update_model, train_ppo2.0.py:15-88), or with minibatch_rows
+        EPOCHS x ceil(N T / minibatch_rows) steps over shuffled rows."""
         if self.check_ranges() != "fp16x3":
             self._rollout_forward_valid = False
         self.compute_advantages()
@@ -704,19 +765,15 @@ class VecPPOTrainer:
         inv_n = 1.0 / float(nb * self.T * self.world)
         grad_of = self._grad_lstm if self.kind == "lstm" else self._grad_fused_mlp if self.fused_mlp else self._grad_layered_mlp
         for _ in range(hp["epochs"]):
+            if self.minibatch_rows is not None:
+                self._epoch_rows()
+                continue
             for m in range(self.num_minibatches):
                 sl = slice(m * nb, (m + 1) * nb)
                 grad = grad_of(sl, (b["act"][sl].reshape(-1), b["logp"][sl].reshape(-1), self.adv_n[sl].reshape(-1),
                                     self.ret[sl].reshape(-1), b["val"][sl].reshape(-1), inv_n, hp["clip"], hp["ent_beta"],
                                     self.loss_sums, self.dheads, self.dhead_bias))
-                allreduce_grad(grad)              # RCCL sum over ranks; inv_n already holds 1/global count
-                if self.record_grads:            # (gradient, parameters it was taken at)
-                    self.grad_log.append((grad.clone(), self.policy.flat.clone()))
-                self.opt_step += 1
-                ops.clip_adam(self.policy.flat, grad, self.exp_avg, self.exp_avg_sq, self.opt_step, hp["lr"],
-                              max_norm=hp["max_grad_norm"], gnorm_out=self.gnorm, pmax_out=self.ranges[0:1])
-                if self.record:
-                    self.log.append((self.loss_sums.clone(), self.gnorm.clone()))
+                self._optimiser_step(grad)
         if self._guarded():
             self._push_param_range()
         return self.loss_sums
@@ -754,5 +811,5 @@ class VecPPOTrainer:
         s = t.cpu().numpy()
         if s[3] > 0 or s[4] > 0:
             raise RuntimeError("NaN in probs")
-        n = (self.N // self.num_minibatches) * self.T * self.world
+        n = self._last_n * self.world           # (row minibatches: the last chunk's size, the same on every rank)
         return s[0] / n, s[1] / n, s[2] / n

@@ -1,0 +1,67 @@
+"""Static comparison of the gfx950 kernels of two source trees, no GPU needed: registers, scratch, LDS, instruction count and
+lane-spill traffic (v_readlane + v_writelane) of every kernel, before and after a change.
+
+    python tools/kernel_static_table.py OLD_CSRC NEW_CSRC rollout mlp_fused greedy_tail env loss > profiles/NAME.md
+
+Each file is compiled to device assembly with the Makefile's flags (FAST_TU files with -ffp-contract=fast).  A kernel is
+"same" when its instruction stream is identical after block labels are renumbered.  A record for a refactor, not a gate.
+"""
+import hashlib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
+FAST_TU = ("lstm", "wgrad")
+
+
+def kernels(csrc, tu):
+    """{demangled kernel name: dict(vgpr, sgpr, scratch, lds, insts, lanes, sha)} of csrc/tu.hip"""
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, tu + ".s")
+        extra = ["-ffp-contract=fast"] if tu in FAST_TU else []
+        subprocess.run([HIPCC, *FLAGS, *extra, "--cuda-device-only", "-S", os.path.join(csrc, tu + ".hip"), "-o", out], check=True)
+        txt = open(out).read()
+    res = {}
+    meta = {m.group(1): m.group(2) for m in re.finditer(r"\.amdhsa_kernel (\S+)\n(.*?)\.end_amdhsa_kernel", txt, re.S)}
+    for name, block in meta.items():
+        body = re.search(r"^%s:[^\n]*\n(.*?)^\s+\.amdhsa_kernel " % re.escape(name), txt, re.S | re.M).group(1)
+        ins = []
+        for line in body.splitlines():
+            line = line.split(";")[0].strip()
+            if not line or line.startswith(".") and not line.startswith(".LBB"):
+                continue
+            ins.append(re.sub(r"\.LBB\d+_", ".LBB_", line))
+        code = [i for i in ins if not i.endswith(":")]
+        info = txt[txt.index("\t.size\t%s," % name):][:3000]                  # the "; Kernel info:" comment block behind the function
+        stat = lambda key, src: int(re.search(r"%s[:, ]+(\d+)" % key, src).group(1))                 # noqa: E731
+        nice = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
+        nice = re.sub(r"^void |\(.*$", "", nice.replace("(anonymous namespace)::", ""))
+        res[nice] = dict(vgpr=stat(r"; NumVgprs", info), sgpr=stat(r"; TotalNumSgprs", info), scratch=stat(r"; ScratchSize", info),
+                         lds=stat(r"\.amdhsa_group_segment_fixed_size", block),
+                         insts=len(code), lanes=sum(i.startswith(("v_readlane", "v_writelane")) for i in code),
+                         sha=hashlib.sha256("\n".join(ins).encode()).hexdigest())
+    return res
+
+
+def main():
+    old, new, tus = sys.argv[1], sys.argv[2], sys.argv[3:]
+    print("| file | kernel | VGPR | SGPR | scratch B | static LDS B | instructions | v_readlane + v_writelane | stream |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    cell = lambda a, b: str(a) if a == b else f"{a} -> {b}"                                         # noqa: E731
+    for tu in tus:
+        a, b = kernels(old, tu), kernels(new, tu)
+        for k in sorted(set(a) | set(b)):
+            if k not in a or k not in b:
+                print(f"| {tu}.hip | `{k}` | | | | | | | {'only old' if k in a else 'only new'} |")
+                continue
+            x, y = a[k], b[k]
+            print(f"| {tu}.hip | `{k}` | " + " | ".join(cell(x[f], y[f]) for f in ("vgpr", "sgpr", "scratch", "lds", "insts", "lanes")) +
+                  f" | {'same' if x['sha'] == y['sha'] else 'differs'} |")
+
+
+if __name__ == "__main__":
+    main()

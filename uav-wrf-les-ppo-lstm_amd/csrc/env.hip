@@ -1,6 +1,5 @@
 // env.hip -- E1-E5 as stand-alone kernels: reset, one vectorised step with auto-reset, peek.
-// One thread per environment; arithmetic in env_core.h.  (The fused rollout kernel in
-// rollout.hip runs the same core inside its time loop.)
+// One thread per environment; arithmetic in env_core.h, which every other kernel that steps an env calls too.
 #include <math.h>
 #include <vector>
 #include "env_core.h"
@@ -97,27 +96,18 @@ __global__ __launch_bounds__(256) void env_step_kernel(EnvParams P, EnvBlob b, i
     EnvState s = env_load(b, i);
     unsigned short* vis = b.visited + (size_t)i * NVIS;
     const int eg = P.env_offset + i;
-    double z0, z1;
-    if (noise) { z0 = noise[2 * (size_t)i]; z1 = noise[2 * (size_t)i + 1]; }
-    else env_step_noise(P, eg, s, z0, z1);
     int a = act[i];
     a = a < 0 ? 0 : (a > 4 ? 4 : a);
     StepOut o;
-    double tx, ty;
-    env_step_wind(s, z0, z1, tx, ty);
-    env_step_core(P, eg, s, vis, a, tx, ty, o);
+    env_step(P, eg, s, vis, a, noise, (size_t)i, o);
     const int od = 6 + P.trend_k;
     if (term_obs) for (int k = 0; k < od; ++k) term_obs[(size_t)i * od + k] = o.obs[k];
     if (info) for (int k = 0; k < 5; ++k) info[(size_t)i * 5 + k] = (float)o.info[k];
     rew[i] = (float)o.reward;
     if (rew64) rew64[i] = o.reward;
     done[i] = o.done ? 1.f : 0.f;
-    flags[i] = (uint8_t)((o.done ? 1 : 0) | (o.reached ? 2 : 0));
-    if (o.done) {                                   // the reset of train_ppo2.0.py:139
-        s.episode += 1;
-        env_begin_episode(P, eg, s, vis);
-        env_obs(P, s, vis, o.obs);
-    }
+    flags[i] = (uint8_t)step_flags(o);
+    env_auto_reset(P, eg, s, vis, o);
     env_store(b, i, s);
     for (int k = 0; k < od; ++k) obs_out[(size_t)i * od + k] = o.obs[k];
 }

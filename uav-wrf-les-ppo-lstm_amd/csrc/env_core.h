@@ -1,5 +1,6 @@
-// env_core.h -- device-side arithmetic of ONE plume environment (E2-E5), shared by the
-// stand-alone step kernel (env.hip) and the fused persistent rollout kernel (rollout.hip).
+// env_core.h -- device-side arithmetic of ONE plume environment (E2-E5) and the composed step built from it (at the end of
+// this file), shared by every kernel that steps an env: env.hip, both fused rollouts (rollout.hip, mlp_fused.hip) and the
+// step-wise routes' tails (rollout.hip, greedy_tail.hip).
 //
 // Reference: PPOV2.0/environment.py:41-49 (reset), :51-62 (field), :64-80 (obs), :82-169 (step);
 // PPOV2.1/environment.py:56 (sigma=15); PPOV1.1/environment.py:105 (clip 500-1e-6).
@@ -333,4 +334,73 @@ __device__ __forceinline__ void env_step_core(const EnvParams& P, int env_global
 __device__ __forceinline__ void env_step_noise(const EnvParams& P, int env_global, const EnvState& s, double& z0, double& z1) {
     const Philox4 r = philox4x32_10(P.seed, (uint32_t)s.steps, (uint32_t)env_global, (uint32_t)s.episode, RNG_STEP);
     normal2(r, P.ftab, z0, z1);
+}
+
+// ---- one step, composed.  Every kernel that steps an env (env_step_kernel, the two step-wise tails, both fused rollouts) goes
+// through the pieces below, so the routes agree bit for bit because they run the same lines, not copies of them.
+
+// This step's two standard normals: row `row` of the caller's optional noise array ([rows][2]), else the counter RNG.
+__device__ __forceinline__ void env_step_normals(const EnvParams& P, int env_global, const EnvState& s,
+                                                 const double* __restrict__ noise, size_t row, double& z0, double& z1) {
+    if (noise) { z0 = noise[2 * row]; z1 = noise[2 * row + 1]; }
+    else env_step_noise(P, env_global, s, z0, z1);
+}
+
+// The action-independent half of a step: normals -> wind displacement.  rollout_lstm_kernel calls this before its heads are
+// known and env_step_core later; everyone else calls env_step().
+__device__ __forceinline__ void env_step_draw_wind(const EnvParams& P, int env_global, const EnvState& s,
+                                                   const double* __restrict__ noise, size_t row, double& tx, double& ty) {
+    double z0, z1;
+    env_step_normals(P, env_global, s, noise, row, z0, z1);
+    env_step_wind(s, z0, z1, tx, ty);
+}
+
+// normals -> wind -> E4.  `action` is already in 0 .. 4.
+__device__ __forceinline__ void env_step(const EnvParams& P, int env_global, EnvState& s, unsigned short* vis, int action,
+                                         const double* __restrict__ noise, size_t row, StepOut& out) {
+    double tx, ty;
+    env_step_draw_wind(P, env_global, s, noise, row, tx, ty);
+    env_step_core(P, env_global, s, vis, action, tx, ty, out);
+}
+
+// The reset of train_ppo2.0.py:139: a finished episode is followed at once by the next one, whose first observation replaces
+// the terminal one in out.obs.
+__device__ __forceinline__ void env_auto_reset(const EnvParams& P, int env_global, EnvState& s, unsigned short* vis, StepOut& out) {
+    if (out.done) {
+        s.episode += 1;
+        env_begin_episode(P, env_global, s, vis);
+        env_obs(P, s, vis, out.obs);
+    }
+}
+
+// The step's flags byte: bit0 done, bit1 reached, bit3 the stop rule fired (bit2 = "not stepped", greedy_rec_idle).
+__device__ __forceinline__ int step_flags(const StepOut& out, bool hit = false) {
+    return (out.done ? 1 : 0) | (out.reached ? 2 : 0) | (hit ? 8 : 0);
+}
+
+// ---- the record of one greedy evaluation step in global memory: act / flags [N][steps], obs [N][steps][od], pos [N][steps][2]
+// and, with a stop rule, rule_val [N][steps] (else NULL).  `row` = env * steps + t.  (rollout_lstm_kernel parks the same record
+// in LDS for its store wave and keeps its own stores.)
+struct GreedyRec {
+    int32_t* act; float* obs; float* pos; uint8_t* flags; float* rule_val;
+};
+// a stepped env: the action, the observation the step returned, agent_pos after the move, the flags
+__device__ __forceinline__ void greedy_rec_stepped(const GreedyRec& R, size_t row, int od, int action, const StepOut& out,
+                                                   const EnvState& s, bool hit) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) if (k < od) R.obs[row * od + k] = out.obs[k];
+    R.act[row] = action;
+    R.flags[row] = (uint8_t)step_flags(out, hit);
+    R.pos[row * 2] = s.px;
+    R.pos[row * 2 + 1] = s.py;
+}
+// an env that is not stepped (ended, or inactive on entry): act -1, flags bit2, obs and pos 0, rule_val NaN
+__device__ __forceinline__ void greedy_rec_idle(const GreedyRec& R, size_t row, int od) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) if (k < od) R.obs[row * od + k] = 0.f;
+    R.act[row] = -1;
+    R.flags[row] = 4;
+    R.pos[row * 2] = 0.f;
+    R.pos[row * 2 + 1] = 0.f;
+    if (R.rule_val) R.rule_val[row] = __builtin_nanf("");
 }

@@ -4,13 +4,13 @@
 // the optional stop rule, the step's record, the next observation and the env's `active` flag.  A step of such a policy is
 // then L + 2 launches on the steppers (3 L + 1 on the uav_lstm_fwd layers) instead of the few dozen of the torch loop.
 //
-// The greedy twin of rollout_tail_kernel (rollout.hip), with the GREEDY branch of rollout_lstm_kernel as its body: a wave
-// takes four envs, the heads as rows_dot_kernel forms them (rows_dot_core.h: the same sums, so the logits are bit for bit
-// uav_gemm_f32's few-columns form), then lanes 0..3 each carry one env through env_step_kernel's body (env_core.h) and
-// stop_rule_step (stop_rule_core.h; the window in place in stop_win / stop_cnt, as stop_stability_kernel holds it).
+// A wave takes four envs: the heads by rows4_heads (rows_dot_core.h: rows_dot_kernel's sums, so the logits are bit for bit
+// uav_gemm_f32's few-columns form), then lanes 0..3 each carry one env through argmax_first (loss_core.h), env_step (env_core.h)
+// and stop_rule_step (stop_rule_core.h; the window in place in stop_win / stop_cnt, as stop_stability_kernel holds it).
 // An env with active[i] = 0 only gets its "not stepped" record; its blob, cur_obs row and window are not touched.
 // Built with the default -ffp-contract=off: it holds env and stop-rule arithmetic.
 #include "env_core.h"
+#include "loss_core.h"
 #include "rows_dot_core.h"
 #include "stop_rule_core.h"
 
@@ -33,57 +33,27 @@ __global__ __launch_bounds__(256) void greedy_tail_kernel(EnvParams P, EnvBlob b
     const int64_t m0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;
     if (m0 >= n) return;
     env_params_refresh(P);
-    RowsDot<8, 1> rd;
-    rd.load_w(w_head, K, A, K, lane);
-    float red[4];
-    rd.rows4(y, ldy, m0, n, K, lane, red);
     float z[A];
-#pragma unroll
-    for (int o = 0; o < A; ++o) {
-        float v = 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float tot = RowsDot<8, 1>::total(red[r], o);
-            if (lane == r) v = tot;
-        }
-        z[o] = v + b_head[o];
-    }
+    rows4_heads<A>(w_head, b_head, y, ldy, m0, n, K, lane, z);
     const int64_t i64 = m0 + lane;
     if (lane >= 4 || i64 >= n) return;
     const int i = (int)i64;
     const int od = 6 + P.trend_k;
     const size_t col = (size_t)i * steps + t;
-    if (B.active[i] == 0) {                         // not stepped: act -1, flags bit2, obs and pos 0
-        B.act[col] = -1;
-        B.flags[col] = 4;
-        for (int k = 0; k < od; ++k) B.obs[col * od + k] = 0.f;
-        B.pos[col * 2] = 0.f;
-        B.pos[col * 2 + 1] = 0.f;
-        if (has_rule && B.rule_val) B.rule_val[col] = __builtin_nanf("");
+    const GreedyRec rec{B.act, B.obs, B.pos, B.flags, B.rule_val};
+    if (B.active[i] == 0) {
+        greedy_rec_idle(rec, col, od);
         return;
     }
-    // ---- argmax of the logits (torch.argmax: the first of equal maxima)
-    int a_sel = 0;
-    float m = z[0];
-    bool bad = (z[0] != z[0]);
-#pragma unroll
-    for (int a = 1; a < A; ++a) {
-        bad |= (z[a] != z[a]);
-        if (z[a] > m) { m = z[a]; a_sel = a; }
-    }
+    bool bad;
+    const int a_sel = argmax_first<A>(z, bad);
     if (bad) atomicAdd(B.nan_count, 1);
-    // ---- env_step_kernel's body without the reset: an ended env stays as its last step left it
+    // ---- the env step without the reset: an ended env stays as its last step left it
     EnvState s = env_load(b, i);
     unsigned short* vis = b.visited + (size_t)i * NVIS;
-    const int eg = P.env_offset + i;
-    double z0, z1;
-    if (B.noise) { z0 = B.noise[2 * (size_t)i]; z1 = B.noise[2 * (size_t)i + 1]; }
-    else env_step_noise(P, eg, s, z0, z1);
     const int a_env = a_sel > 4 ? 4 : a_sel;        // uav_env_step's clamp (n_act = 6 only)
     StepOut o;
-    double tx, ty;
-    env_step_wind(s, z0, z1, tx, ty);
-    env_step_core(P, eg, s, vis, a_env, tx, ty, o);
+    env_step(P, P.env_offset + i, s, vis, a_env, B.noise, (size_t)i, o);
     env_store(b, i, s);
     // ---- the stop rule on this step's agent_pos and obs[2]
     bool hit = false;
@@ -97,14 +67,8 @@ __global__ __launch_bounds__(256) void greedy_tail_kernel(EnvParams P, EnvBlob b
         if (B.rule_val) B.rule_val[col] = rv;
     }
     // ---- the record, and what the next step starts from
-    B.act[col] = a_sel;
-    B.flags[col] = (uint8_t)((o.done ? 1 : 0) | (o.reached ? 2 : 0) | (hit ? 8 : 0));
-    for (int k = 0; k < od; ++k) {
-        B.obs[col * od + k] = o.obs[k];
-        B.cur_obs[(size_t)i * od + k] = o.obs[k];
-    }
-    B.pos[col * 2] = s.px;
-    B.pos[col * 2 + 1] = s.py;
+    greedy_rec_stepped(rec, col, od, a_sel, o, s, hit);
+    for (int k = 0; k < od; ++k) B.cur_obs[(size_t)i * od + k] = o.obs[k];
     if (o.done || hit) B.active[i] = 0;
 }
 

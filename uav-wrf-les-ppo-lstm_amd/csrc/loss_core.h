@@ -62,6 +62,65 @@ __device__ __forceinline__ int sample_categorical(const float* z, float* p, cons
     return a;
 }
 
+// ---- the fused rollouts' flavour (rollout_lstm_kernel, rollout_mlp_kernel).  Two flavours exist on purpose: the draw above
+// uses libm's expf / logf and keys the counter RNG by (counter, env), because uav_policy_sample and the step-wise tail must
+// agree with the loss kernels' softmax bit for bit; the fused kernels sit on the chain that paces a rollout and use the
+// hardware __expf / __logf, with the word keyed (step, env, iteration) by the kernel.  Their log-probs differ in the last bits,
+// and each route's update recomputes them with softmax_row either way.
+
+// argmax of logits (torch.argmax: the first of equal maxima); bad = a NaN logit
+template <int A>
+__device__ __forceinline__ int argmax_first(const float (&z)[A], bool& bad) {
+    int a_sel = 0;
+    float m = z[0];
+    bad = (z[0] != z[0]);
+#pragma unroll
+    for (int a = 1; a < A; ++a) {
+        bad |= (z[a] != z[a]);
+        if (z[a] > m) { m = z[a]; a_sel = a; }
+    }
+    return a_sel;
+}
+
+// softmax + Categorical(probs) sample / log_prob (train_ppo2.0.py:161-163,189).  forced: NULL, or the action is forced[row];
+// u_word(): the step's 32-bit Philox word, called only when the action is drawn (a kernel that formed it earlier returns it).
+// Returns the action in 0 .. A-1; lp = log of its normalised probability clamped to [eps, 1 - eps]; bad = a NaN probability.
+template <int A, class U>
+__device__ __forceinline__ int rollout_draw(const float (&z)[A], const int32_t* __restrict__ forced, size_t row, U&& u_word,
+                                            float& lp, bool& bad) {
+    float p[A];
+    float m = z[0];
+#pragma unroll
+    for (int a = 1; a < A; ++a) m = fmaxf(m, z[a]);
+    float ssum = 0.f;
+#pragma unroll
+    for (int a = 0; a < A; ++a) { p[a] = __expf(z[a] - m); ssum += p[a]; }
+    float psum = 0.f;
+    bad = false;
+#pragma unroll
+    for (int a = 0; a < A; ++a) { p[a] = p[a] / ssum; psum += p[a]; bad |= (p[a] != p[a]); }
+    int a_sel;
+    if (forced) {
+        a_sel = forced[row];
+    } else {
+        const float target = u01_f32(u_word()) * psum;
+        float cdf = 0.f;
+        a_sel = A - 1;
+        bool found = false;
+#pragma unroll
+        for (int a = 0; a < A; ++a) {                 // inverse CDF: first a with target < cdf
+            cdf += p[a];
+            if (!found && target < cdf) { a_sel = a; found = true; }
+        }
+    }
+    a_sel = a_sel < 0 ? 0 : (a_sel > A - 1 ? A - 1 : a_sel);
+    float psel = 0.f;
+#pragma unroll
+    for (int a = 0; a < A; ++a) if (a == a_sel) psel = p[a];
+    lp = __logf(fminf(fmaxf(psel / psum, F32_EPS), 1.0f - F32_EPS));
+    return a_sel;
+}
+
 constexpr int LOSS_BLOCKS = 1024;
 constexpr int LOSS_PSTRIDE = 16;   // doubles per block partial: 4 loss sums + up to 9 head-bias sums
 

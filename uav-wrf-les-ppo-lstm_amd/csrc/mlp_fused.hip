@@ -53,7 +53,6 @@ constexpr int WS2 = 260;                // row stride of the rollout's LDS image
 constexpr int RS1 = H1 + 8;             // row stride (halves) of the a1 piece planes: conflict-free ds_read_b128
 constexpr int RS2 = H2 + 8;             // row stride (halves) of the dz2 piece planes
 constexpr float LN_EPS_F = 1e-5f;
-constexpr float R_EPS = 1.1920928955078125e-07f;
 
 // flat parameter layout of csrc/mlp.hip for `in` input features: W1[256][in] b1 g1 be1 W2 b2 g2 be2 Wh bh.  in = 6 is the
 // reference's network; 7 and 8 carry the trend channels (obs[6 + i], uav_env_cfg::trend_k).  Every offset behind W1 moves
@@ -486,10 +485,10 @@ constexpr size_t ROLL_LDS = (size_t)(Tiles<1>::FLOATS + 16 * WS2) * sizeof(float
 
 // H3: the 256 x 128 layer on the fp16 matrix pipe (layer2_h3) -- the update kernel of the same arithmetic runs the same
 // code, so the rollout's log-probabilities stay bit-identical to the update's first forward pass.
-// GREEDY: greedy evaluation episodes (uav_greedy_episodes; see rollout_lstm_kernel in rollout.hip for the record format):
-// argmax of the logits, no auto-reset, an ended or inactive env is never stepped.  GREEDY = false is the trainer's rollout.
-// STOP (with GREEDY): evaluate_model.py's stop rule after every env step, as in rollout_lstm_kernel (flags bit3; a hit ends the
-// episode as `done` does).  STOP = false compiles to the kernels as they were.
+// GREEDY: greedy evaluation episodes (uav_greedy_episodes; the record is env_core.h's GreedyRec): argmax of the logits, no
+// auto-reset, an ended or inactive env is never stepped.  GREEDY = false is the trainer's rollout.
+// STOP (with GREEDY): evaluate_model.py's stop rule after every env step (flags bit3; a hit ends the episode as `done` does).
+// STOP = false compiles to the kernels as they were.
 template <bool H3, bool GREEDY = false, bool STOP = false, int INW = IN>
 __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBlob blob, int N, int T, uint64_t iter,
                                                             const float* __restrict__ params, MlpRollBufs B) {
@@ -622,105 +621,50 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
                 __builtin_amdgcn_s_waitcnt(0xc07f);              // lgkmcnt(0): HD written (single wave)
                 __builtin_amdgcn_wave_barrier();
                 if (lane < MT) {
-                    float z[NA], p[NA];
+                    float z[NA];
 #pragma unroll
                     for (int a = 0; a < NA; ++a) z[a] = L.HD[lane * 8 + a];
                     const float V = L.HD[lane * 8 + NA];
                     if (value_only) {
                         if (env_lane) B.last_val[my_env] = V;
                     } else if constexpr (GREEDY) {
-                        // argmax of the logits (torch.argmax: the first of equal maxima), then the environment step without reset
-                        int a_sel = 0;
-                        float m = z[0];
-                        bool bad = (z[0] != z[0]);
-#pragma unroll
-                        for (int a = 1; a < NA; ++a) {
-                            bad |= (z[a] != z[a]);
-                            if (z[a] > m) { m = z[a]; a_sel = a; }
-                        }
+                        // argmax of the logits, then the environment step without reset
+                        bool bad;
+                        const int a_sel = argmax_first<NA>(z, bad);
                         if (bad && env_lane && on) atomicAdd(B.nan_count, 1);
                         const size_t row = (size_t)min(my_env, N - 1) * T + t;
+                        const GreedyRec rec{B.act, B.obs, B.pos, B.flags, STOP ? B.rule_val : nullptr};
                         if (on) {
-                            const int eg = P.env_offset + my_env;
                             EnvState es = es_s[lane];
-                            double z0, z1, wind_x, wind_y;
-                            if (B.noise) { z0 = B.noise[2 * row]; z1 = B.noise[2 * row + 1]; }
-                            else env_step_noise(P, eg, es, z0, z1);
-                            env_step_wind(es, z0, z1, wind_x, wind_y);
                             StepOut so;
-                            env_step_core(P, eg, es, myvis, a_sel, wind_x, wind_y, so);
+                            env_step(P, P.env_offset + my_env, es, myvis, a_sel, B.noise, row, so);
                             bool hit = false;                    // STOP: the rule fires on this step
                             if constexpr (STOP) {
                                 float rv;
                                 hit = stop_rule_step(B.rule, ring, sr, es.px, es.py, so.obs[2], B.rule_val != nullptr, rv);
                                 if (B.rule_val && env_lane) B.rule_val[row] = rv;
                             }
-                            if (env_lane) {
-#pragma unroll
-                                for (int f = 0; f < IN_MAX; ++f) if (f < in) B.obs[row * in + f] = so.obs[f];
-                                B.act[row] = a_sel;
-                                B.flags[row] = (uint8_t)((so.done ? 1 : 0) | (so.reached ? 2 : 0) | (hit ? 8 : 0));
-                                B.pos[row * 2] = es.px;
-                                B.pos[row * 2 + 1] = es.py;
-                            }
+                            if (env_lane) greedy_rec_stepped(rec, row, in, a_sel, so, es, hit);
 #pragma unroll
                             for (int f = 0; f < IN_MAX; ++f) if (f < in) L.X[lane * 8 + f] = so.obs[f];
                             es_s[lane] = es;
                             if (so.done || hit) on = false;
                         } else if (env_lane) {
-#pragma unroll
-                            for (int f = 0; f < IN_MAX; ++f) if (f < in) B.obs[row * in + f] = 0.f;
-                            B.act[row] = -1;
-                            B.flags[row] = 4;
-                            B.pos[row * 2] = 0.f;
-                            B.pos[row * 2 + 1] = 0.f;
-                            if constexpr (STOP)
-                                if (B.rule_val) B.rule_val[row] = __builtin_nanf("");
+                            greedy_rec_idle(rec, row, in);
                         }
                         (void)V;
                     } else {
-                        // softmax + Categorical(probs) sample / log_prob (train_ppo2.0.py:161-163,189), as rollout.hip
-                        float m = z[0];
-#pragma unroll
-                        for (int a = 1; a < NA; ++a) m = fmaxf(m, z[a]);
-                        float ssum = 0.f;
-#pragma unroll
-                        for (int a = 0; a < NA; ++a) { p[a] = __expf(z[a] - m); ssum += p[a]; }
-                        float psum = 0.f;
-                        bool bad = false;
-#pragma unroll
-                        for (int a = 0; a < NA; ++a) { p[a] = p[a] / ssum; psum += p[a]; bad |= (p[a] != p[a]); }
-                        if (bad && env_lane) atomicAdd(B.nan_count, 1);
                         const int eg = P.env_offset + my_env;
                         const size_t row = (size_t)min(my_env, N - 1) * T + t;
-                        int a_sel;
-                        if (B.forced_act) {
-                            a_sel = B.forced_act[row];
-                        } else {
-                            const uint32_t u_act = philox4x32_10(P.seed, (uint32_t)t, (uint32_t)eg, (uint32_t)iter, RNG_ACTION).x;
-                            const float target = u01_f32(u_act) * psum;
-                            float cdf = 0.f;
-                            a_sel = NA - 1;
-                            bool found = false;
-#pragma unroll
-                            for (int a = 0; a < NA; ++a) {       // inverse CDF: first a with target < cdf
-                                cdf += p[a];
-                                if (!found && target < cdf) { a_sel = a; found = true; }
-                            }
-                        }
-                        a_sel = a_sel < 0 ? 0 : (a_sel > NA - 1 ? NA - 1 : a_sel);
-                        float psel = 0.f;
-#pragma unroll
-                        for (int a = 0; a < NA; ++a) if (a == a_sel) psel = p[a];
-                        const float lp = __logf(fminf(fmaxf(psel / psum, R_EPS), 1.0f - R_EPS));
+                        float lp;
+                        bool bad;
+                        const int a_sel = rollout_draw<NA>(z, B.forced_act, row, [&]() {
+                            return philox4x32_10(P.seed, (uint32_t)t, (uint32_t)eg, (uint32_t)iter, RNG_ACTION).x; }, lp, bad);
+                        if (bad && env_lane) atomicAdd(B.nan_count, 1);
                         // environment step (f64, env_core.h) + auto reset
                         EnvState es = es_s[lane];
-                        double z0, z1, wind_x, wind_y;
-                        if (B.noise) { z0 = B.noise[2 * row]; z1 = B.noise[2 * row + 1]; }
-                        else env_step_noise(P, eg, es, z0, z1);
-                        env_step_wind(es, z0, z1, wind_x, wind_y);
                         StepOut so;
-                        env_step_core(P, eg, es, myvis, a_sel, wind_x, wind_y, so);
+                        env_step(P, eg, es, myvis, a_sel, B.noise, row, so);
                         if (env_lane) {
 #pragma unroll
                             for (int f = 0; f < IN_MAX; ++f) if (f < in) B.obs[row * in + f] = L.X[lane * 8 + f];
@@ -729,7 +673,7 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
                             B.val[row] = V;
                             B.logp[row] = lp;
                             B.done[row] = so.done ? 1.f : 0.f;
-                            B.flags[row] = (uint8_t)((so.done ? 1 : 0) | (so.reached ? 2 : 0));
+                            B.flags[row] = (uint8_t)step_flags(so);
                             if (B.heads) {
 #pragma unroll
                                 for (int a = 0; a < NA; ++a) B.heads[row * NH + a] = z[a];
@@ -745,11 +689,7 @@ __global__ __launch_bounds__(512) void rollout_mlp_kernel(EnvParams P_arg, EnvBl
                                 B.info[row * 10 + 9] = (float)es.sy;
                             }
                         }
-                        if (so.done) {
-                            es.episode += 1;
-                            env_begin_episode(P, eg, es, myvis);
-                            env_obs(P, es, myvis, so.obs);
-                        }
+                        env_auto_reset(P, eg, es, myvis, so);
 #pragma unroll
                         for (int f = 0; f < IN_MAX; ++f) if (f < in) L.X[lane * 8 + f] = so.obs[f];
                         es_s[lane] = es;

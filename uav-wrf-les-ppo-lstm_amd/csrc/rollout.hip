@@ -54,7 +54,6 @@ extern "C" int uav_roll_prof_read(unsigned long long* out) {
 #define R_PROF_MARK(i)
 #define R_PROF_FLUSH()
 #endif
-constexpr float R_F32_EPS = 1.1920928955078125e-07f;
 
 #define r_sigmoid fast_sigmoid
 #define r_tanh fast_tanh
@@ -467,13 +466,10 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
             uint32_t u_act = 0;
             double wind_x = 0.0, wind_y = 0.0;
             if (lane < RMT && !value_only) {
-                double z0, z1;
                 const int eg = P.env_offset + my_env;
                 const size_t row = (size_t)min(my_env, N - 1) * T + t;
                 if (!GREEDY && !B.forced_act) u_act = philox4x32_10(P.seed, (uint32_t)t, (uint32_t)eg, (uint32_t)iter, RNG_ACTION).x;
-                if (B.noise) { z0 = B.noise[2 * row]; z1 = B.noise[2 * row + 1]; }
-                else env_step_noise(P, eg, es_s[lane], z0, z1);
-                env_step_wind(es_s[lane], z0, z1, wind_x, wind_y);
+                env_step_draw_wind(P, eg, es_s[lane], B.noise, row, wind_x, wind_y);
             }
             R_PROF_MARK(6);
             lds_barrier();                       // barrier 1: h_t visible
@@ -503,14 +499,16 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
             __builtin_amdgcn_wave_barrier();
             R_PROF_MARK(2);
             if (lane < RMT) {
-                float z[NA], p[NA];
+                float z[NA];
 #pragma unroll
                 for (int a = 0; a < NA; ++a) z[a] = hd[lane * 16 + a] + bh[a];
                 const float V = hd[lane * 16 + NA] + bh[NA];
                 if (value_only) {
                     if (env_lane) B.last_val[my_env] = V;
                 } else if constexpr (GREEDY) {
-                    // argmax of the logits (torch.argmax: the first of equal maxima), then the environment step without reset
+                    // argmax of the logits (torch.argmax: the first of equal maxima), then the environment step without reset.
+                    // argmax_first (loss_core.h) written out: through the helper the h = 64 TREND form of this branch gains a
+                    // VGPR and 47 SGPR-spill lane moves (profiles/step_core_static_table.md)
                     const bool on = kbuf[lane] != 0.f;
                     int a_sel = 0;
                     float m = z[0];
@@ -534,7 +532,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                             if (B.rule_val && env_lane) B.rule_val[(size_t)my_env * T + t] = rv;
                         }
                         tr[0] = __int_as_float(a_sel);
-                        tr[5] = __int_as_float((so.done ? 1 : 0) | (so.reached ? 2 : 0) | (hit ? 8 : 0));
+                        tr[5] = __int_as_float(step_flags(so, hit));
                         if constexpr (TREND) {
 #pragma unroll
                             for (int f = 0; f < 8; ++f) {
@@ -562,40 +560,12 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                     }
                     (void)V;
                 } else {
-                    // softmax + Categorical(probs) sample / log_prob (train_ppo2.0.py:161-163,189)
-                    float m = z[0];
-#pragma unroll
-                    for (int a = 1; a < NA; ++a) m = fmaxf(m, z[a]);
-                    float ssum = 0.f;
-#pragma unroll
-                    for (int a = 0; a < NA; ++a) { p[a] = __expf(z[a] - m); ssum += p[a]; }
-                    float psum = 0.f;
-                    bool bad = false;
-#pragma unroll
-                    for (int a = 0; a < NA; ++a) { p[a] = p[a] / ssum; psum += p[a]; bad |= (p[a] != p[a]); }
-                    if (bad && env_lane) atomicAdd(B.nan_count, 1);
                     const int eg = P.env_offset + my_env;
-                    int a_sel;
                     const size_t row = (size_t)min(my_env, N - 1) * T + t;
-                    if (B.forced_act) {
-                        a_sel = B.forced_act[row];
-                    } else {
-                        const float target = u01_f32(u_act) * psum;
-                        float cdf = 0.f;
-                        a_sel = NA - 1;
-                        bool found = false;
-#pragma unroll
-                        for (int a = 0; a < NA; ++a) {             // inverse CDF: first a with target < cdf
-                            cdf += p[a];
-                            if (!found && target < cdf) { a_sel = a; found = true; }
-                        }
-                    }
-                    a_sel = a_sel < 0 ? 0 : (a_sel > NA - 1 ? NA - 1 : a_sel);
-                    float psel = 0.f;
-#pragma unroll
-                    for (int a = 0; a < NA; ++a) if (a == a_sel) psel = p[a];
-                    const float qa = psel / psum;
-                    const float lp = __logf(fminf(fmaxf(qa, R_F32_EPS), 1.0f - R_F32_EPS));
+                    float lp;
+                    bool bad;
+                    const int a_sel = rollout_draw<NA>(z, B.forced_act, row, [&]() { return u_act; }, lp, bad);
+                    if (bad && env_lane) atomicAdd(B.nan_count, 1);
                     R_PROF_MARK(3);
                     // environment step (f64, env_core.h) + auto reset
                     EnvState es = es_s[lane];
@@ -609,7 +579,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                     tr[2] = V;
                     tr[3] = lp;
                     tr[4] = so.done ? 1.f : 0.f;
-                    tr[5] = __int_as_float((so.done ? 1 : 0) | (so.reached ? 2 : 0));
+                    tr[5] = __int_as_float(step_flags(so));
                     tr[6] = kbuf[lane];
                     if (B.heads) {
 #pragma unroll
@@ -631,11 +601,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                     for (int f = 0; f < OW; ++f) trs[RMT * 8 + lane * 8 + f] = ob_old[f];
                     trs[SRC + lane * 8] = (float)es.sx;                   // source of the episode this step belongs to
                     trs[SRC + lane * 8 + 1] = (float)es.sy;
-                    if (so.done) {
-                        es.episode += 1;
-                        env_begin_episode(P, eg, es, myvis);
-                        env_obs(P, es, myvis, so.obs);
-                    }
+                    env_auto_reset(P, eg, es, myvis, so);
 #pragma unroll
                     for (int f = 0; f < OW; ++f) xbuf[lane * 8 + f] = f < I ? so.obs[f] : 0.f;
                     es_s[lane] = es;
@@ -679,9 +645,9 @@ static int launch_rollout(const EnvParams& P, EnvBlob blob, int N, int T, uint64
 // as one launch: policy heads of the top layer's y_t, action sample, environment step, PPOBuffer.store, next observation into
 // the sequence array -- five launches (rows-dot GEMM 14.3 us, uav_policy_sample_at 4.3, uav_env_step 8.6, uav_store_transition
 // 2.9, a copy 3.4 at 4096 envs, each mostly launch and memory latency) that all sit on the step's dependency chain.
-// A wave takes four envs: the heads as rows_dot_kernel forms them (rows_dot_core.h: the same sums, so heads[:, t] is bit for
-// bit uav_gemm_f32's), then lanes 0..3 each carry one env through uav_policy_sample_at's draw (loss_core.h) and
-// env_step_kernel's body (env_core.h).  4096 envs = 1024 waves = one per SIMD.
+// A wave takes four envs: the heads by rows4_heads (rows_dot_core.h: rows_dot_kernel's sums, so heads[:, t] is bit for bit
+// uav_gemm_f32's), then lanes 0..3 each carry one env through uav_policy_sample_at's draw (sample_categorical, loss_core.h)
+// and env_step + env_auto_reset (env_core.h).  4096 envs = 1024 waves = one per SIMD.
 template <int A>
 __global__ __launch_bounds__(256) void rollout_tail_kernel(
     EnvParams P, EnvBlob b, int n, const float* __restrict__ y, int64_t ldy, int K, const float* __restrict__ w_head,
@@ -694,21 +660,8 @@ __global__ __launch_bounds__(256) void rollout_tail_kernel(
     const int64_t m0 = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;
     if (m0 >= n) return;
     env_params_refresh(P);
-    RowsDot<8, 1> rd;
-    rd.load_w(w_head, K, A + 1, K, lane);
-    float red[4];
-    rd.rows4(y, ldy, m0, n, K, lane, red);
     float z[A + 1];
-#pragma unroll
-    for (int o = 0; o <= A; ++o) {
-        float v = 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float tot = RowsDot<8, 1>::total(red[r], o);
-            if (lane == r) v = tot;
-        }
-        z[o] = v + b_head[o];
-    }
+    rows4_heads<A + 1>(w_head, b_head, y, ldy, m0, n, K, lane, z);
     const int64_t i64 = m0 + lane;
     if (lane >= 4 || i64 >= n) return;
     const int i = (int)i64;
@@ -724,26 +677,17 @@ __global__ __launch_bounds__(256) void rollout_tail_kernel(
     act_buf[col] = a;
     logp_buf[col] = logf(fminf(fmaxf(qa, F32_EPS), 1.0f - F32_EPS));
     val_buf[col] = z[A];
-    // ---- uav_env_step (env_step_kernel's body)
+    // ---- uav_env_step
     EnvState s = env_load(b, i);
     unsigned short* vis = b.visited + (size_t)i * NVIS;
     const int eg = P.env_offset + i;
-    double z0, z1;
-    if (noise) { z0 = noise[2 * (size_t)i]; z1 = noise[2 * (size_t)i + 1]; }
-    else env_step_noise(P, eg, s, z0, z1);
     a = a < 0 ? 0 : (a > 4 ? 4 : a);
     StepOut o;
-    double tx, ty;
-    env_step_wind(s, z0, z1, tx, ty);
-    env_step_core(P, eg, s, vis, a, tx, ty, o);
+    env_step(P, eg, s, vis, a, noise, (size_t)i, o);
     const float d = o.done ? 1.f : 0.f;
-    const uint8_t fl = (uint8_t)((o.done ? 1 : 0) | (o.reached ? 2 : 0));
+    const uint8_t fl = (uint8_t)step_flags(o);
     const float rw = (float)o.reward;
-    if (o.done) {                                   // the reset of train_ppo2.0.py:139
-        s.episode += 1;
-        env_begin_episode(P, eg, s, vis);
-        env_obs(P, s, vis, o.obs);
-    }
+    env_auto_reset(P, eg, s, vis, o);
     env_store(b, i, s);
     // ---- uav_store_transition, and the observation step t + 1 starts from
     keep_buf[col] = keep[i];

@@ -1,6 +1,6 @@
 // rows_dot_core.h -- a few output columns of a short inner product, one WAVE per row (rows_dot_kernel of gemm.hip and the
-// step-wise rollout's tail kernel of rollout.hip share this arithmetic, so the policy heads a rollout step samples from are
-// bit for bit the ones uav_gemm_f32 writes).
+// step-wise routes' tail kernels -- rollout.hip, greedy_tail.hip, through rows4_heads below -- share this arithmetic, so the
+// policy heads a step samples from are bit for bit the ones uav_gemm_f32 writes).
 #pragma once
 #include "common.h"
 
@@ -70,3 +70,25 @@ struct RowsDot {
         return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, red), ((o & 4) ? 32 : 0) + ((o & 2) ? 16 : 0) + ((o & 1) ? 8 : 0)));
     }
 };
+
+// The policy heads of a step-wise route's tail kernel: a wave takes rows m0 .. m0 + 3 of y (K <= 256), and lane r < 4 gets
+// z[o] = y[m0 + r] . W[o] + bias[o] for the NOUT <= 8 head rows -- the sums of rows_dot_kernel in its order, so the logits
+// are bit for bit uav_gemm_f32's few-columns form.  Lanes 4 .. 63 get the bias alone.
+template <int NOUT>
+__device__ __forceinline__ void rows4_heads(const float* __restrict__ W, const float* __restrict__ bias, const float* __restrict__ y,
+                                            int64_t ldy, int64_t m0, int64_t n, int K, int lane, float (&z)[NOUT]) {
+    RowsDot<8, 1> rd;
+    rd.load_w(W, K, NOUT, K, lane);
+    float red[4];
+    rd.rows4(y, ldy, m0, n, K, lane, red);
+#pragma unroll
+    for (int o = 0; o < NOUT; ++o) {
+        float v = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float tot = RowsDot<8, 1>::total(red[r], o);
+            if (lane == r) v = tot;
+        }
+        z[o] = v + bias[o];
+    }
+}

@@ -331,6 +331,34 @@ int uav_mlp_ppo_grad_rows(uav_ctx* ctx, const float* params, const float* obs, c
                           int64_t n_rows, int trend_k, float inv_n, float clip, float ent_beta, double* loss_sums, float* grad,
                           uav_stream stream);
 
+/* ---- shuffled env-sequence minibatches: pack the selected envs of several arrays in ONE launch (csrc/gather.hip).
+ * One array of a uav_gather_rows_multi call: `planes` planes of rows of row_bytes bytes each; plane p of the source starts at
+ * src + p * src_plane_stride_bytes and holds n_rows rows, plane p of the destination starts at dst + p * dst_plane_stride_bytes
+ * and receives n_sel rows.  planes = 1 for the [N][T]... sample arrays (the strides are then ignored), planes = L for the
+ * recurrent start state h0 / c0 [L][N][H]. */
+typedef struct uav_gather_spec {
+    const void* src;
+    void* dst;
+    int64_t row_bytes;
+    int32_t planes;
+    int32_t pad_;
+    int64_t src_plane_stride_bytes;
+    int64_t dst_plane_stride_bytes;
+} uav_gather_spec;
+#define UAV_GATHER_MAX_SPECS 12
+
+/* dst[p][j][:] = src[p][idx[j]][:] for every spec, plane p and j < n_sel: idx i32 [n_sel] (device), specs a HOST array of
+ * n_specs <= UAV_GATHER_MAX_SPECS entries that the call copies into the kernel's arguments by value.  A pure copy -- the bytes
+ * torch.index_select gives -- of all arrays in one launch: what makes a shuffled minibatch of whole env sequences contiguous, so
+ * that the sequence kernels run on it unchanged.  An array whose row_bytes, two base addresses and (planes > 1) two plane strides
+ * are multiples of 16 moves 16 bytes per lane, the lanes of a wave on consecutive chunks of a row; any other array moves 4 bytes
+ * per lane.  row_bytes must be a positive multiple of 4; with planes > 1 a plane stride must cover its plane's rows; every
+ * array's planes * n_sel * row_bytes / 4 stays below 2^31; n_rows < 2^31.  Source and destination must not overlap.  An index
+ * outside [0, n_rows) is clamped into it (a bad caller gets wrong data, not a device fault).  Rows j >= n_sel of a destination
+ * are not written.  Added without a change of UAV_ABI_VERSION (a symbol only). */
+int uav_gather_rows_multi(uav_ctx* ctx, const int32_t* idx, int64_t n_sel, int64_t n_rows, const uav_gather_spec* specs,
+                          int n_specs, uav_stream stream);
+
 /* ---- L1: nn.LSTM-semantics sequence kernels (gate order i,f,g,o; bias b_ih+b_hh;
  * PPOV2.0/model.py:206-212, PPOV2.1/model.py:263).  One layer per call.
  * x [N][T][I], keep [N][T] (1 = carry the recurrent state into step t, 0 = restart from zero;

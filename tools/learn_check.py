@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Does the fused path learn?  A few hundred PPO iterations at a C3-like shape (or, with a 4th argument "c5", the stacked
 h = 256 x 2 + trend policy of BASELINE C5 at 1024 envs x 128 steps: stepper rollout, piece-plane inputs, fused dx, split
-GEMMs); prints reward / success trend."""
+GEMMs); prints reward / success trend.  The switch --shuffle-envs anywhere on the command line draws a fresh permutation of
+the envs per epoch for the minibatches (VecPPOTrainer(shuffle_envs=True))."""
 import os
 import sys
 import time
@@ -16,17 +17,19 @@ from uavppo.trainer import VecPPOTrainer  # noqa: E402
 
 def main():
     N, T = 4096, 128
+    shuffle = "--shuffle-envs" in sys.argv
+    sys.argv = [a for a in sys.argv if a != "--shuffle-envs"]
     iters = int(sys.argv[1]) if len(sys.argv) > 1 else 300
     lr = float(sys.argv[2]) if len(sys.argv) > 2 else 3e-4
     mb = int(sys.argv[3]) if len(sys.argv) > 3 else 8
     if len(sys.argv) > 4 and sys.argv[4] in ("c5", "c5full"):
         N, T = (1024, 128) if sys.argv[4] == "c5" else (4096, 256)       # c5full: BASELINE C5's exact per-GPU shape
         tr = VecPPOTrainer(N, T, "lstm", hidden=256, layers=2, trend_k=2, variant="v2.1", device="cuda:0", seed=1, lr=lr,
-                           num_minibatches=mb, use_curriculum=True)
+                           num_minibatches=mb, use_curriculum=True, shuffle_envs=shuffle)
     elif len(sys.argv) > 4 and sys.argv[4] == "mlp":      # the reference's own policy through the fused MLP kernels
-        tr = VecPPOTrainer(N, T, "mlp", device="cuda:0", seed=1, lr=lr, num_minibatches=mb, use_curriculum=True)
+        tr = VecPPOTrainer(N, T, "mlp", device="cuda:0", seed=1, lr=lr, num_minibatches=mb, use_curriculum=True, shuffle_envs=shuffle)
     else:
-        tr = VecPPOTrainer(N, T, "lstm", hidden=128, device="cuda:0", seed=1, lr=lr, num_minibatches=mb, use_curriculum=True)
+        tr = VecPPOTrainer(N, T, "lstm", hidden=128, device="cuda:0", seed=1, lr=lr, num_minibatches=mb, use_curriculum=True, shuffle_envs=shuffle)
     t0 = time.perf_counter()
     for it in range(iters):
         tr.train_iteration()

@@ -43,6 +43,15 @@ class LstmBwdLayer(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("keep", "stash", "w_hh", "w_ih", "dgates", "dx", "dhn", "dcn", "dh0", "dc0")]
 
 
+class GatherSpec(C.Structure):
+    """struct uav_gather_spec (include/uavppo.h)."""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("planes", C.c_int32), ("pad_", C.c_int32),
+                ("src_plane_stride_bytes", C.c_int64), ("dst_plane_stride_bytes", C.c_int64)]
+
+
+GATHER_MAX_SPECS = 12      # UAV_GATHER_MAX_SPECS
+
+
 # name -> (restype, argtypes); mirrors include/uavppo.h one to one
 SIGNATURES = {
     "uav_abi_version": (I32, []),
@@ -91,6 +100,7 @@ SIGNATURES = {
     "uav_mlp_ppo_grad": (I32, [P, P, P, P, P, P, P, P, I64, I32, I32, I32, I32, F32, F32, F32, P, P, P]),
     "uav_mlp_ppo_grad_trend": (I32, [P, P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, P, P]),
     "uav_mlp_ppo_grad_rows": (I32, [P, P, P, P, P, P, P, P, I64, P, I64, I32, F32, F32, F32, P, P, P]),
+    "uav_gather_rows_multi": (I32, [P, P, I64, I64, C.POINTER(GatherSpec), I32, P]),
     "uav_lstm_fwd": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, P, P]),
     "uav_lstm_bwd": (I32, [P, P, P, P, P, P, P, I32, P, P, I32, I32, I32, P, P, P, P, I32, P, P]),
     "uav_lstm_bwd_caps": (I32, [P, I32, I32]),

@@ -504,6 +504,57 @@ def mlp_ppo_grad(params, obs, act, logp_old, adv, ret, val_old, inv_n, clip, ent
     return grad
 
 
+class GatherPlan:
+    """The checked arguments of gather_rows_multi for one fixed set of (src, dst) arrays: built once, launched many times
+    (the trainer's packed minibatch buffers never move).  Keeps the tensors alive."""
+
+    def __init__(self, pairs):
+        pairs = [tuple(p) for p in pairs]
+        if not 1 <= len(pairs) <= _lib.GATHER_MAX_SPECS:
+            raise RuntimeError(f"gather_rows_multi: {len(pairs)} arrays (1 .. {_lib.GATHER_MAX_SPECS})")
+        self.specs = (_lib.GatherSpec * len(pairs))()
+        self.tensors = pairs
+        self.n_rows = self.max_sel = None
+        for k, pair in enumerate(pairs):
+            src, dst = pair[:2]
+            rd = int(pair[2]) if len(pair) > 2 else 0          # the dimension the rows are selected on: 0, or 1 behind a plane dimension
+            name = f"pairs[{k}]"
+            _p(src, name=name + " src")
+            _p(dst, src.dtype, name=name + " dst")
+            if rd not in (0, 1) or src.dim() <= rd or dst.dim() != src.dim():
+                raise RuntimeError(f"{name}: row dimension {rd} of shapes {tuple(src.shape)} -> {tuple(dst.shape)}")
+            if src.shape[:rd] != dst.shape[:rd] or src.shape[rd + 1:] != dst.shape[rd + 1:]:
+                raise RuntimeError(f"{name}: shapes {tuple(src.shape)} -> {tuple(dst.shape)} differ outside the row dimension")
+            row_bytes = src[(0,) * (rd + 1)].numel() * src.element_size()
+            if row_bytes == 0 or row_bytes % 4:
+                raise RuntimeError(f"{name}: rows of {row_bytes} bytes (a positive multiple of 4)")
+            if self.n_rows not in (None, src.shape[rd]):
+                raise RuntimeError(f"{name}: {src.shape[rd]} source rows, the arrays before it have {self.n_rows}")
+            self.n_rows = int(src.shape[rd])
+            self.max_sel = int(dst.shape[rd]) if self.max_sel is None else min(self.max_sel, int(dst.shape[rd]))
+            planes = int(src.shape[0]) if rd else 1
+            self.specs[k] = _lib.GatherSpec(src.data_ptr(), dst.data_ptr(), row_bytes, planes, 0, self.n_rows * row_bytes,
+                                            int(dst.shape[rd]) * row_bytes)
+        self.handle = _h(pairs[0][0])
+
+
+def gather_rows_multi(idx, pairs):
+    """uav_gather_rows_multi: dst[j] = src[idx[j]] for every (src, dst) of `pairs` in ONE launch -- the bytes of
+    torch.index_select(src, 0, idx) in dst[:len(idx)].  idx i32 [n_sel]; a pair is (src [n_rows, ...], dst [>= n_sel, ...]) or,
+    for arrays with a leading plane dimension such as h0 [L, N, H], (src, dst, 1): dst[p, j] = src[p, idx[j]].  Rows of dst
+    past n_sel are left alone.  4-byte-multiple rows, same dtype per pair, at most 12 pairs.  `pairs` may be a GatherPlan built
+    from them before.  An index outside [0, n_rows) is clamped by the kernel."""
+    plan = pairs if isinstance(pairs, GatherPlan) else GatherPlan(pairs)
+    if idx.dim() != 1 or not 1 <= idx.numel() <= plan.max_sel:
+        raise RuntimeError(f"gather_rows_multi: idx of shape {tuple(idx.shape)} for destinations of {plan.max_sel} rows")
+    _t = KERNEL_TIMER.bracket("gather_rows")
+    check(lib().uav_gather_rows_multi(plan.handle, _p(idx, I32, name="idx"), idx.numel(), plan.n_rows, plan.specs, len(plan.specs),
+                                      _stream()), "uav_gather_rows_multi")
+    if _t is not None:
+        _t.record()
+    return plan
+
+
 def mlp_ppo_grad_trend(params, obs, act, logp_old, adv, ret, val_old, inv_n, clip, ent_beta, loss_sums, grad, trend_k):
     """mlp_ppo_grad for an MLP that takes the trend channels as inputs (uav_mlp_ppo_grad_trend): obs [n, 6 + trend_k],
     params / grad of mlp_param_count(6 + trend_k) floats, trend_k 0, 1 or 2 (0 is mlp_ppo_grad's kernel and bits)."""

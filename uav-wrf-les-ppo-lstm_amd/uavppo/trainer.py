@@ -75,7 +75,7 @@ class VecPPOTrainer:
     def __init__(self, num_envs, horizon, policy="lstm", hidden=128, layers=1, variant="v2.0", device="cuda",
                  seed=1234, gae_mode="reference_exact", num_minibatches=1, bank=None, bank_sources=None,
                  rank=0, world_size=1, use_curriculum=True, trend_k=0, log_info=False, device_curriculum=None,
-                 update_form="update_model", minibatch_rows=None, **hp):
+                 update_form="update_model", minibatch_rows=None, shuffle_envs=False, **hp):
         self.hp = dict(DEFAULTS)
         self.hp.update(hp)
         self.N, self.T = int(num_envs), int(horizon)
@@ -104,7 +104,17 @@ class VecPPOTrainer:
             if policy != "mlp" or not 6 <= 6 + int(trend_k) <= 8:
                 raise ValueError("minibatch_rows needs the MLP policy on the fused path (6-256-128 with trend_k 0..2): only "
                                  "uav_mlp_ppo_grad_rows reads its samples through a row index; an LSTM's samples are whole "
-                                 "env sequences")
+                                 "env sequences (shuffle_envs=True shuffles those)")
+        # shuffle_envs: every epoch one permutation of this rank's N envs, cut into num_minibatches chunks of N / M whole env
+        # sequences; a chunk is packed into contiguous buffers by ONE launch (uav_gather_rows_multi) and the update's kernels run
+        # on the packed minibatch unchanged
+        self.shuffle_envs = bool(shuffle_envs)
+        if self.shuffle_envs:
+            if self.minibatch_rows is not None:
+                raise ValueError("shuffle_envs and minibatch_rows are two ways to shuffle the buffer (whole env sequences / single "
+                                 "sample rows): give one of them")
+            if self.num_minibatches == 1:
+                raise ValueError("shuffle_envs with num_minibatches=1: one minibatch of all envs leaves nothing to shuffle")
         if self.N % self.num_minibatches:
             raise ValueError("num_envs must be divisible by num_minibatches (minibatches are whole env sequences)")
         self.kind = policy
@@ -150,8 +160,9 @@ class VecPPOTrainer:
         self.record_grads = False    # tests: ... and the (all-reduced, unclipped) flat gradient of every optimiser step + its parameters
         self.log = []
         self.grad_log = []
-        self.forced_perms = None     # tests: list of index tensors [N * T], consumed in order instead of the drawn permutations
-        self._perm_gen = None        # device generator of the row permutations, seeded by (seed, rank) on first use
+        self.forced_perms = None     # tests: list of index tensors [N * T] (shuffle_envs: [N]), consumed in order instead of the drawn permutations
+        self.perm_log = []           # tests (record, shuffle_envs): the env permutation of every epoch
+        self._perm_gen = None        # device generator of the row / env permutations, seeded by (seed, rank) on first use
         self._last_n = (self.N // self.num_minibatches) * self.T      # local samples of the last optimiser step (losses())
         # range guard of the fp16-split kernels: device maxima [|param|, |obs|, |h0|], mirrored to pinned host memory
         self.ranges = torch.zeros(3, **f32)
@@ -229,6 +240,21 @@ class VecPPOTrainer:
             self.work = {"stash": None}      # layer-by-layer path only (770 floats per sample); allocated on first use
             self._step_scratch()
         self.dheads = torch.empty(nb * T, 6, **f32)
+        self._pack = self._pack_plan = None
+        if self.shuffle_envs:
+            # the packed minibatch: nb whole env sequences of the seven sample arrays (the MLP: six, it has no restart mask) and
+            # the LSTM's start state, allocated once; the plan holds the checked (source, destination) table of the launch
+            b, pk = self.buf, {}
+            src = {"obs": b["obs"], "act": b["act"], "logp": b["logp"], "adv_n": self.adv_n, "ret": self.ret, "val": b["val"]}
+            if policy == "lstm":
+                src["keep"] = b["keep"]
+            for k, v in src.items():
+                pk[k] = torch.empty((nb,) + tuple(v.shape[1:]), dtype=v.dtype, device=d)
+            pairs = [(src[k], pk[k]) for k in src]
+            if policy == "lstm":
+                pk["h0"], pk["c0"] = torch.empty(layers, nb, hidden, **f32), torch.empty(layers, nb, hidden, **f32)
+                pairs += [(self.h0, pk["h0"], 1), (self.c0, pk["c0"], 1)]
+            self._pack, self._pack_plan = pk, ops.GatherPlan(pairs)
         self.reset()
 
     # ------------------------------------------------------------------------------------------
@@ -687,7 +713,7 @@ class VecPPOTrainer:
 
     # ------------------------------------------------------------------------------------------ U1-U3
     # minibatch slice -> flat gradient, one routine per policy kind (loss: the arguments of the loss kernel after the heads)
-    def _grad_lstm(self, sl, loss):
+    def _grad_lstm(self, sl, loss, pk=None):
         b, M = self.buf, self.num_minibatches
         if self._rollout_forward_valid:
             # first optimiser step after a fused rollout: parameters unchanged since the rollout, whose
@@ -697,29 +723,32 @@ class VecPPOTrainer:
                                       [self.work[f"y{l}"] for l in range(L)])
             heads = self.work["heads"]
             self._rollout_forward_valid = False
+        elif pk is not None:             # a packed minibatch of shuffled envs: its own start state beside it
+            heads = self.policy.heads(pk["obs"], pk["keep"], pk["h0"], pk["c0"], self.work)
         else:
             heads = self.policy.heads(b["obs"][sl], b["keep"][sl], self.h0[:, sl].contiguous() if M > 1 else self.h0,
                                       self.c0[:, sl].contiguous() if M > 1 else self.c0, self.work)
         ops.ppo_loss_heads(heads.view(self.dheads.shape[0], -1), *loss)
         return self.policy.backward(self.dheads, self.work, self.dhead_bias)
 
-    def _grad_fused_mlp(self, sl, loss):
-        obs = self.buf["obs"][sl].reshape(-1, self.obs_dim)
+    def _grad_fused_mlp(self, sl, loss, pk=None):
+        obs = (self.buf["obs"][sl] if pk is None else pk["obs"]).reshape(-1, self.obs_dim)
         if self.trend_k:
             return ops.mlp_ppo_grad_trend(self.policy.flat, obs, *loss[:8], self.loss_sums, self.policy.grad, self.trend_k)
         return ops.mlp_ppo_grad(self.policy.flat, obs, *loss[:8], self.loss_sums, self.policy.grad)
 
-    def _grad_layered_mlp(self, sl, loss):
+    def _grad_layered_mlp(self, sl, loss, pk=None):
         n = self.dheads.shape[0]
         if self.work["stash"] is None:
             self.work["stash"] = torch.empty(n * (2 * 256 + 2 * 128 + 2), dtype=torch.float32, device=self.device)
-        heads = self.policy.heads(self.buf["obs"][sl].reshape(n, self.obs_dim), stash=self.work["stash"])
+        heads = self.policy.heads((self.buf["obs"][sl] if pk is None else pk["obs"]).reshape(n, self.obs_dim), stash=self.work["stash"])
         ops.ppo_loss_heads(heads, *loss)
         return self.policy.backward(self.dheads)
 
     def _next_perm(self):
-        """One permutation of this rank's N * T sample rows (row = env * T + t) as i32 on the device."""
-        L = self.N * self.T
+        """One permutation of this rank's N * T sample rows (row = env * T + t) -- with shuffle_envs of its N envs -- as i32 on
+        the device."""
+        L = self.N if self.shuffle_envs else self.N * self.T
         if self.forced_perms is not None:
             perm = torch.as_tensor(self.forced_perms.pop(0)).to(self.device).reshape(-1)
             if perm.numel() != L:
@@ -752,9 +781,24 @@ class VecPPOTrainer:
                                          hp["clip"], hp["ent_beta"], self.loss_sums, self.policy.grad, self.trend_k)
             self._optimiser_step(grad)
 
+    def _epoch_envs(self, grad_of, inv_n):
+        """One epoch in shuffled minibatches of whole env sequences: every rank cuts its own permutation of its N envs into the
+        same num_minibatches chunks of N / M, so the gradient all-reduces pair up; a chunk is packed by one launch and then
+        takes the unshuffled minibatch's route through grad_of and the optimiser step."""
+        hp, pk, nb = self.hp, self._pack, self.N // self.num_minibatches
+        perm = self._next_perm()
+        if self.record:
+            self.perm_log.append(perm)
+        loss = (pk["act"].view(-1), pk["logp"].view(-1), pk["adv_n"].view(-1), pk["ret"].view(-1), pk["val"].view(-1), inv_n,
+                hp["clip"], hp["ent_beta"], self.loss_sums, self.dheads, self.dhead_bias)
+        for m in range(self.num_minibatches):
+            ops.gather_rows_multi(perm[m * nb:(m + 1) * nb], self._pack_plan)
+            self._optimiser_step(grad_of(None, loss, pk))
+
     def update(self):
-        """GAE + EPOCHS x num_minibatches optimiser steps (_update_model, train_ppo2.0.py:15-88), or with minibatch_rows
-        EPOCHS x ceil(N T / minibatch_rows) steps over shuffled rows."""
+        """GAE + EPOCHS x num_minibatches optimiser steps (_update_model, train_ppo2.0.py:15-88) -- with shuffle_envs over a
+        fresh permutation of the envs per epoch -- or with minibatch_rows EPOCHS x ceil(N T / minibatch_rows) steps over
+        shuffled rows."""
         if self.check_ranges() != "fp16x3":
             self._rollout_forward_valid = False
         self.compute_advantages()
@@ -767,6 +811,9 @@ class VecPPOTrainer:
         for _ in range(hp["epochs"]):
             if self.minibatch_rows is not None:
                 self._epoch_rows()
+                continue
+            if self.shuffle_envs:
+                self._epoch_envs(grad_of, inv_n)
                 continue
             for m in range(self.num_minibatches):
                 sl = slice(m * nb, (m + 1) * nb)

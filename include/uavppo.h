@@ -443,6 +443,18 @@ int uav_lstm_wgrad(uav_ctx* ctx, const float* x, const float* keep, const float*
                    const float* stash, const float* dgates, const float* w_ih, const float* dheads,
                    int n_heads, int N, int T, int I, int H, float* dw_ih, float* dw_hh, float* db, float* db_hh,
                    float* dw_head, float* dx, uav_stream stream);
+/* Start states of truncated BPTT, one layer per call: the recurrent state entering every chunk of `chunk` consecutive steps,
+ * read out of ONE forward pass.  y [N][T][H] and stash [N][T][6H] as uav_lstm_fwd / the stepper / uav_rollout wrote them, keep
+ * [N][T] or NULL (all ones), h0, c0 [N][H] that pass started from.  C = T / chunk; h_out, c_out [N * C][H]: row n * C + k is
+ * the state carried into step t0 = k * chunk, already multiplied by keep[n][t0] -- h0[n], c0[n] for k = 0, else y[n][t0 - 1]
+ * and the stash's c_prev slot stash[n][t0][4H:5H].  The [N][T] sample arrays viewed as [N * C][chunk] with these start states
+ * are then ordinary sequences for uav_lstm_fwd / _bwd / _wgrad (a start state that is already masked makes keep[:, 0] = 0 of
+ * such a view harmless in all of them).  One launch over N * C * H elements, 16-byte loads and stores when H % 4 == 0 and
+ * every array is 16-byte aligned, 4-byte ones otherwise; plain stores, no workspace.  Refused with a reason: chunk < 1, T not
+ * a multiple of chunk, H < 1, N * T * 6H of 2^31 or more, a NULL array other than keep.
+ * Added without a change of UAV_ABI_VERSION (a symbol only). */
+int uav_lstm_chunk_states(uav_ctx* ctx, const float* y, const float* stash, const float* keep, const float* h0, const float* c0,
+                          int N, int T, int H, int chunk, float* h_out, float* c_out, uav_stream stream);
 
 /* ---- E1-E5: vectorised plume environment (environment.py:19-169).  State lives in one
  * caller-owned device blob of uav_env_state_bytes(n_env) bytes. */

@@ -56,6 +56,7 @@ HIDDEN = 128             # LSTM hidden size (64 / 128)
 NUM_LAYERS = 1
 NUM_MINIBATCHES = 1      # the reference uses ONE minibatch of the whole buffer per epoch (train_ppo2.0.py:44-45)
 SHUFFLE_ENVS = False     # True (with NUM_MINIBATCHES > 1): every epoch cuts a fresh permutation of the envs into the minibatches
+BPTT_LEN = None          # LSTM: truncated BPTT over chunks of this many steps (divides HORIZON); None = whole env sequences
 GAE_MODE = "reference_exact"   # or "standard" (PPOV1.0/ppo0.0.py:337-350)
 SEED = 1234
 TREND_K = 0              # extra observation channels obs[2](t) - obs[2](t-1-i), i < TREND_K (BASELINE C5: 2)

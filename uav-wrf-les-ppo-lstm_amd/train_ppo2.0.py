@@ -11,7 +11,7 @@ import numpy as np
 import pandas as pd
 import torch
 
-from config import (BATCH_SIZE, CLIP_EPSILON, DIST_BACKEND, ENTROPY_BETA, ENV_VARIANT, EPISODES, EPOCHS, FIELD_BANK, GAE_MODE, GAMMA,
+from config import (BATCH_SIZE, BPTT_LEN, CLIP_EPSILON, DIST_BACKEND, ENTROPY_BETA, ENV_VARIANT, EPISODES, EPOCHS, FIELD_BANK, GAE_MODE, GAMMA,
                     GRID_SIZE, HIDDEN, HORIZON, ITERATIONS, LAMBDA, LEARNING_RATE, LOCAL_RANK, MAX_STEPS, NUM_ENVS, NUM_LAYERS,
                     NUM_MINIBATCHES, POLICY, RANK, SEED, SHUFFLE_ENVS, TREND_K, WORLD_SIZE)  # noqa: F401
 from environment import MethaneEnv
@@ -177,7 +177,7 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
     rank, world, dev = _init_distributed()
     bank, bank_src = field_bank.load(FIELD_BANK, ENV_VARIANT, dev)
     tr = VecPPOTrainer(NUM_ENVS, HORIZON, POLICY, hidden=HIDDEN, layers=NUM_LAYERS, variant=ENV_VARIANT, seed=SEED, device=dev,
-                       gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, log_info=True, gamma=GAMMA, lam=LAMBDA,
+                       gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, bptt_len=BPTT_LEN, log_info=True, gamma=GAMMA, lam=LAMBDA,
                        clip=CLIP_EPSILON, ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, rank=rank, world_size=world,
                        bank=bank, bank_sources=bank_src, trend_k=TREND_K)
     rows_per_iter = []                  # this rank's rows, iteration by iteration (merged in rank order at the end)

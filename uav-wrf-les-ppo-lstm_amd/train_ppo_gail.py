@@ -12,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from config import (CLIP_EPSILON, ENTROPY_BETA, ENV_VARIANT, EPOCHS, GAE_MODE, GAMMA, HIDDEN, HORIZON, LAMBDA, LEARNING_RATE, NUM_ENVS,
+from config import (BPTT_LEN, CLIP_EPSILON, ENTROPY_BETA, ENV_VARIANT, EPOCHS, GAE_MODE, GAMMA, HIDDEN, HORIZON, LAMBDA, LEARNING_RATE, NUM_ENVS,
                     NUM_LAYERS, NUM_MINIBATCHES, POLICY, SEED, SHUFFLE_ENVS)
 from model import Discriminator, compute_discriminator_loss, get_expert_data  # noqa: F401  (train_ppo_gail.py:24-27)
 from uavppo.gail import GAILTrainer
@@ -28,7 +28,7 @@ def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert
     discriminator.pth.  Returns the trainer."""
     states, actions = get_expert_data(expert_path)
     tr = GAILTrainer(num_envs, horizon, policy, hidden=hidden, layers=NUM_LAYERS, variant=ENV_VARIANT, seed=seed, device=device,
-                     gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, gamma=GAMMA, lam=LAMBDA, clip=CLIP_EPSILON,
+                     gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, bptt_len=BPTT_LEN, gamma=GAMMA, lam=LAMBDA, clip=CLIP_EPSILON,
                      ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, expert=(states, actions), gail_coef=gail_coef,
                      env_coef=env_coef, disc_lr=disc_lr, disc_steps=disc_steps, update_form=update_form, minibatch_rows=minibatch_rows)
     it, mean_rewards = 0, []

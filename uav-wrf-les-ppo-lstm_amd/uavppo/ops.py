@@ -684,6 +684,22 @@ def lstm_fwd(x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, stash=None, want_stash=Tru
     return y, hn, cn, stash
 
 
+def lstm_chunk_states(y, stash, keep, h0, c0, chunk, h_out=None, c_out=None):
+    """uav_lstm_chunk_states: the state entering every chunk of `chunk` steps of one layer's forward pass, already masked.
+    y [N, T, H], stash [N, T, 6H], keep [N, T] or None, h0, c0 [N, H] -> h_out, c_out [N * (T // chunk), H] (row n * C + k:
+    chunk k of env n).  The outputs may be views into larger arrays (contiguous, any 4-byte alignment)."""
+    N, T, H = y.shape
+    chunk = int(chunk)
+    rows = N * (T // chunk) if chunk >= 1 else 0
+    h_out = torch.empty(rows, H, dtype=F32, device=y.device) if h_out is None else h_out
+    c_out = torch.empty(rows, H, dtype=F32, device=y.device) if c_out is None else c_out
+    check(lib().uav_lstm_chunk_states(_h(y), _p(y, F32, (N, T, H), "y"), _p(stash, F32, (N, T, 6 * H), "stash"),
+                                      _p(keep, F32, (N, T), "keep"), _p(h0, F32, (N, H), "h0"), _p(c0, F32, (N, H), "c0"),
+                                      N, T, H, chunk, _p(h_out, F32, (rows, H), "h_out"), _p(c_out, F32, (rows, H), "c_out"),
+                                      _stream()), "uav_lstm_chunk_states")
+    return h_out, c_out
+
+
 class LstmStepper:
     """uav_lstm_fwd one time step per call for one layer (H = 256, fp16-split arithmetic): weights split once by begin(),
     recurrent state kept on the device in `state`; step(t) reads x[:, t] and fills y[:, t] / stash[:, t] of the [N, T]

@@ -29,6 +29,30 @@ RANGE_LIMITS = (0.5 * 65504.0, 0.5 * 4096.0, 0.5 * 64.0)
 MLP_RANGE_LIMITS = (0.5 * 2048.0, float("inf"), float("inf"))
 
 
+def chunk_plan(num_envs, horizon, num_minibatches, bptt_len, policy="lstm", minibatch_rows=None):
+    """Truncated BPTT's cut of a rank's buffer: the [N][T] samples seen as N * C sequences of bptt_len consecutive steps
+    (C = T / bptt_len chunk rows per env, row n * C + k = steps [k * bptt_len, (k + 1) * bptt_len) of env n), minibatch m the
+    chunk rows [m R, (m + 1) R).  Returns (C, R); raises ValueError, with the reason, for what cannot be cut that way.  Pure
+    host arithmetic: VecPPOTrainer calls it before it touches a device."""
+    N, T, M, Lc = int(num_envs), int(horizon), int(num_minibatches), int(bptt_len)
+    if minibatch_rows is not None:
+        raise ValueError("bptt_len and minibatch_rows are two ways to cut the buffer (sequences of bptt_len steps / single sample "
+                         "rows of the MLP): give one of them")
+    if policy != "lstm":
+        raise ValueError(f"bptt_len needs the LSTM policy: the {policy!r} policy carries no recurrent state through time to truncate")
+    if Lc < 1:
+        raise ValueError(f"bptt_len={bptt_len}: at least 1 step")
+    if Lc > T:
+        raise ValueError(f"bptt_len={Lc} is longer than the horizon of {T} steps")
+    if T % Lc:
+        raise ValueError(f"bptt_len={Lc} does not divide the horizon of {T} steps (chunks are whole)")
+    C = T // Lc
+    if (N * C) % M:
+        raise ValueError(f"num_envs * horizon / bptt_len = {N * C} chunk rows are not divisible by num_minibatches={M} "
+                         "(minibatches are whole chunk rows)")
+    return C, N * C // M
+
+
 _SIDE_STREAMS = {}
 
 
@@ -75,7 +99,7 @@ class VecPPOTrainer:
     def __init__(self, num_envs, horizon, policy="lstm", hidden=128, layers=1, variant="v2.0", device="cuda",
                  seed=1234, gae_mode="reference_exact", num_minibatches=1, bank=None, bank_sources=None,
                  rank=0, world_size=1, use_curriculum=True, trend_k=0, log_info=False, device_curriculum=None,
-                 update_form="update_model", minibatch_rows=None, shuffle_envs=False, **hp):
+                 update_form="update_model", minibatch_rows=None, shuffle_envs=False, bptt_len=None, **hp):
         self.hp = dict(DEFAULTS)
         self.hp.update(hp)
         self.N, self.T = int(num_envs), int(horizon)
@@ -115,7 +139,14 @@ class VecPPOTrainer:
                                  "sample rows): give one of them")
             if self.num_minibatches == 1:
                 raise ValueError("shuffle_envs with num_minibatches=1: one minibatch of all envs leaves nothing to shuffle")
-        if self.N % self.num_minibatches:
+        # bptt_len = Lc (truncated BPTT, LSTM only): the update runs on the N * C sequences of Lc consecutive steps the buffer
+        # holds (C = T / Lc), each started from the recurrent state the rollout's parameters give at its first step
+        # (_chunk_start_states, once per iteration) -- gradients do not cross a chunk boundary.  The sample arrays are
+        # contiguous, so the chunk view [N * C][Lc] is a reshape; the sequence kernels run on it unchanged.  None, or Lc = T
+        # (one chunk per env), is full BPTT: the path without the keyword.
+        self.bptt_len = None if bptt_len is None else int(bptt_len)
+        self._C = 1 if bptt_len is None else chunk_plan(self.N, self.T, self.num_minibatches, bptt_len, policy, self.minibatch_rows)[0]
+        if self._C == 1 and self.N % self.num_minibatches:
             raise ValueError("num_envs must be divisible by num_minibatches (minibatches are whole env sequences)")
         self.kind = policy
         self.trend_k = int(trend_k)
@@ -160,10 +191,12 @@ class VecPPOTrainer:
         self.record_grads = False    # tests: ... and the (all-reduced, unclipped) flat gradient of every optimiser step + its parameters
         self.log = []
         self.grad_log = []
-        self.forced_perms = None     # tests: list of index tensors [N * T] (shuffle_envs: [N]), consumed in order instead of the drawn permutations
+        self.forced_perms = None     # tests: list of index tensors [N * T] (shuffle_envs: [N], with bptt_len [N * C]), consumed in order instead of the drawn permutations
         self.perm_log = []           # tests (record, shuffle_envs): the env permutation of every epoch
         self._perm_gen = None        # device generator of the row / env permutations, seeded by (seed, rank) on first use
-        self._last_n = (self.N // self.num_minibatches) * self.T      # local samples of the last optimiser step (losses())
+        self._S, self._Ls = self.N * self._C, self.T // self._C       # the update's sequences: S rows of Ls steps (N, T without bptt_len)
+        self._nb = self._S // self.num_minibatches                    # ... per minibatch
+        self._last_n = self._nb * self._Ls                            # local samples of the last optimiser step (losses())
         # range guard of the fp16-split kernels: device maxima [|param|, |obs|, |h0|], mirrored to pinned host memory
         self.ranges = torch.zeros(3, **f32)
         self._ranges_host = torch.zeros(4, 3, dtype=torch.float32).pin_memory()      # ring: the host may run iterations ahead
@@ -220,7 +253,7 @@ class VecPPOTrainer:
         self.side_stream_curriculum = True     # False: pack + copy on the main stream inside update_curriculum (A/B, tools/ab_loop.py)
         self._iter_events = []                 # (start, end) event pairs of time_rollouts() still to be recorded
         self._env_lo = env_shard(self.rank, N)[0]
-        nb = N // self.num_minibatches
+        nb, S, Ls = self._nb, self._S, self._Ls
         self._st = None                        # scratch of one step of the step-wise rollouts: _step_scratch()
         if policy == "lstm":
             L, H = layers, hidden
@@ -230,30 +263,43 @@ class VecPPOTrainer:
             self._state0 = torch.zeros(2, L, N, H, **f32)
             self.h, self.c = self._state[0], self._state[1]
             self.h0, self.c0 = self._state0[0], self._state0[1]
-            self.work = {"dgates": ops.lstm_dgates(nb, T, H, self.device), "heads": torch.empty(nb, T, 6, **f32)}   # heads: logits | value, written by the sequence kernels
+            self.work = {"dgates": ops.lstm_dgates(nb, Ls, H, self.device), "heads": torch.empty(nb, Ls, 6, **f32)}   # heads: logits | value, written by the sequence kernels
             for l in range(L):
-                self.work[f"stash{l}"] = torch.empty(nb, T, 6 * H, **f32)
-                self.work[f"y{l}"] = torch.empty(nb, T, H, **f32)
+                self.work[f"stash{l}"] = torch.empty(nb, Ls, 6 * H, **f32)
+                self.work[f"y{l}"] = torch.empty(nb, Ls, H, **f32)
             # (a dy buffer for paths whose backward does not take dheads is allocated on first use: policy.backward)
             self.dhead_bias = self.policy.grad_views["head.bias"]       # the loss kernel's column sums ARE this gradient
         else:
             self.work = {"stash": None}      # layer-by-layer path only (770 floats per sample); allocated on first use
             self._step_scratch()
-        self.dheads = torch.empty(nb * T, 6, **f32)
+        self.dheads = torch.empty(nb * Ls, 6, **f32)
+        # what the update reads its sequences from: the sample arrays and the start state themselves, or -- truncated BPTT --
+        # their [N * C][Lc] views and the chunks' start states h0c, c0c [L][N * C][H]
+        self._u = {"obs": self.buf["obs"], "act": self.buf["act"], "logp": self.buf["logp"], "val": self.buf["val"],
+                   "keep": self.buf["keep"], "adv_n": self.adv_n, "ret": self.ret}
+        self._rwork = self.work                # the [N][T] arrays a rollout writes its forward pass to (epoch 0 adopts it)
+        if policy == "lstm":
+            self._u["h0"], self._u["c0"] = self.h0, self.c0
+        if self._C > 1:
+            self._u = {k: v.view((S, Ls) + tuple(v.shape[2:])) for k, v in self._u.items() if k not in ("h0", "c0")}
+            self.h0c, self.c0c = torch.zeros(layers, S, hidden, **f32), torch.zeros(layers, S, hidden, **f32)
+            self._u["h0"], self._u["c0"] = self.h0c, self.c0c
+            if self.num_minibatches == 1:      # one minibatch: the work arrays hold all N * T samples, chunk rows in buffer order
+                self._rwork = {k: v.view(N, T, -1) for k, v in self.work.items() if k != "dgates"}
         self._pack = self._pack_plan = None
         if self.shuffle_envs:
             # the packed minibatch: nb whole env sequences of the seven sample arrays (the MLP: six, it has no restart mask) and
             # the LSTM's start state, allocated once; the plan holds the checked (source, destination) table of the launch
-            b, pk = self.buf, {}
-            src = {"obs": b["obs"], "act": b["act"], "logp": b["logp"], "adv_n": self.adv_n, "ret": self.ret, "val": b["val"]}
+            u, pk = self._u, {}
+            src = {k: u[k] for k in ("obs", "act", "logp", "adv_n", "ret", "val")}
             if policy == "lstm":
-                src["keep"] = b["keep"]
+                src["keep"] = u["keep"]
             for k, v in src.items():
                 pk[k] = torch.empty((nb,) + tuple(v.shape[1:]), dtype=v.dtype, device=d)
             pairs = [(src[k], pk[k]) for k in src]
             if policy == "lstm":
                 pk["h0"], pk["c0"] = torch.empty(layers, nb, hidden, **f32), torch.empty(layers, nb, hidden, **f32)
-                pairs += [(self.h0, pk["h0"], 1), (self.c0, pk["c0"], 1)]
+                pairs += [(u["h0"], pk["h0"], 1), (u["c0"], pk["c0"], 1)]
             self._pack, self._pack_plan = pk, ops.GatherPlan(pairs)
         self.reset()
 
@@ -575,8 +621,8 @@ class VecPPOTrainer:
             ops.rollout_lstm(self.env_state, self.N, self.env_cfg(), self.policy.flat, self.policy.hidden, self.T,
                              self.iteration, self.cur_obs, self.h[0], self.c[0], self.buf, last_val=self.last_val,
                              forced_act=forced_act, noise=noise, nan_count=self.nan_count,
-                             stash=self.work["stash0"] if reuse else None, y=self.work["y0"] if reuse else None,
-                             info=self.info, heads=self.work["heads"] if reuse else None)
+                             stash=self._rwork["stash0"] if reuse else None, y=self._rwork["y0"] if reuse else None,
+                             info=self.info, heads=self._rwork["heads"] if reuse else None)
             self._rollout_forward_valid = reuse
         elif route == "fused_mlp":
             ops.rollout_mlp(self.env_state, self.N, self.env_cfg(), self.policy.flat, self.T, self.iteration, self.cur_obs,
@@ -641,7 +687,7 @@ class VecPPOTrainer:
                 torch.sub(1.0, st["done"], out=keep)      # the recurrent state restarts where an episode ended
 
     def _rollout_stepper(self, forced_act, noise):
-        b, st, w, cfg = self.buf, self._st, self.work, self.env_cfg()
+        b, st, w, cfg = self.buf, self._st, self._rwork, self.env_cfg()
         for t in range(self.T):
             b["obs"][:, t] = self.cur_obs
             self.policy.step_at(b["obs"], t, w, w["heads"], keep=st["keep"])
@@ -654,7 +700,7 @@ class VecPPOTrainer:
             ops.store_transition(t, st["keep"], st["rew"], st["done"], st["flags"], b["keep"], b["rew"], b["done"], b["flags"])
 
     def _rollout_tail(self, forced_act, noise):
-        b, st, w, cfg, v = self.buf, self._st, self.work, self.env_cfg(), self.policy.views
+        b, st, w, cfg, v = self.buf, self._st, self._rwork, self.env_cfg(), self.policy.views
         b["obs"][:, 0] = self.cur_obs                  # later rows are written by the tail of the step before
         for t in range(self.T):
             top = self.policy.step_layers_at(b["obs"], t, w, keep=st["keep"])
@@ -714,20 +760,20 @@ class VecPPOTrainer:
     # ------------------------------------------------------------------------------------------ U1-U3
     # minibatch slice -> flat gradient, one routine per policy kind (loss: the arguments of the loss kernel after the heads)
     def _grad_lstm(self, sl, loss, pk=None):
-        b, M = self.buf, self.num_minibatches
+        u, M = self._u, self.num_minibatches
         if self._rollout_forward_valid:
             # first optimiser step after a fused rollout: parameters unchanged since the rollout, whose
-            # kernel already wrote this forward pass (stash, y) and its heads
+            # kernel already wrote this forward pass (stash, y) and its heads (truncated BPTT: seen through the chunk view)
             L = self.policy.num_layers
-            self.policy.adopt_forward(b["obs"], b["keep"], self.h0, [self.work[f"stash{l}"] for l in range(L)],
+            self.policy.adopt_forward(u["obs"], u["keep"], u["h0"], [self.work[f"stash{l}"] for l in range(L)],
                                       [self.work[f"y{l}"] for l in range(L)])
             heads = self.work["heads"]
             self._rollout_forward_valid = False
         elif pk is not None:             # a packed minibatch of shuffled envs: its own start state beside it
             heads = self.policy.heads(pk["obs"], pk["keep"], pk["h0"], pk["c0"], self.work)
         else:
-            heads = self.policy.heads(b["obs"][sl], b["keep"][sl], self.h0[:, sl].contiguous() if M > 1 else self.h0,
-                                      self.c0[:, sl].contiguous() if M > 1 else self.c0, self.work)
+            heads = self.policy.heads(u["obs"][sl], u["keep"][sl], u["h0"][:, sl].contiguous() if M > 1 else u["h0"],
+                                      u["c0"][:, sl].contiguous() if M > 1 else u["c0"], self.work)
         ops.ppo_loss_heads(heads.view(self.dheads.shape[0], -1), *loss)
         return self.policy.backward(self.dheads, self.work, self.dhead_bias)
 
@@ -746,9 +792,9 @@ class VecPPOTrainer:
         return self.policy.backward(self.dheads)
 
     def _next_perm(self):
-        """One permutation of this rank's N * T sample rows (row = env * T + t) -- with shuffle_envs of its N envs -- as i32 on
-        the device."""
-        L = self.N if self.shuffle_envs else self.N * self.T
+        """One permutation of this rank's N * T sample rows (row = env * T + t) -- with shuffle_envs of its N envs, or with
+        bptt_len beside it of its N * C chunk rows -- as i32 on the device."""
+        L = self._S if self.shuffle_envs else self.N * self.T
         if self.forced_perms is not None:
             perm = torch.as_tensor(self.forced_perms.pop(0)).to(self.device).reshape(-1)
             if perm.numel() != L:
@@ -785,7 +831,7 @@ class VecPPOTrainer:
         """One epoch in shuffled minibatches of whole env sequences: every rank cuts its own permutation of its N envs into the
         same num_minibatches chunks of N / M, so the gradient all-reduces pair up; a chunk is packed by one launch and then
         takes the unshuffled minibatch's route through grad_of and the optimiser step."""
-        hp, pk, nb = self.hp, self._pack, self.N // self.num_minibatches
+        hp, pk, nb = self.hp, self._pack, self._nb
         perm = self._next_perm()
         if self.record:
             self.perm_log.append(perm)
@@ -794,6 +840,34 @@ class VecPPOTrainer:
         for m in range(self.num_minibatches):
             ops.gather_rows_multi(perm[m * nb:(m + 1) * nb], self._pack_plan)
             self._optimiser_step(grad_of(None, loss, pk))
+
+    def _chunk_start_states(self):
+        """Truncated BPTT: h0c, c0c [L][N * C][H], the state every chunk row starts from, with the parameters as they are before
+        the iteration's first optimiser step -- the rollout's -- and fixed for all its epochs.  Taken from the rollout's own
+        forward pass where epoch 0 is about to adopt it; otherwise from ONE forward pass over the buffers, run in env slices
+        that fit the update's work arrays, which the first optimiser step overwrites."""
+        b, L, Lc, C = self.buf, self.policy.num_layers, self._Ls, self._C
+        if self._rollout_forward_valid:
+            w = self._rwork
+            for l in range(L):
+                ops.lstm_chunk_states(w[f"y{l}"], w[f"stash{l}"], b["keep"], self.h0[l], self.c0[l], Lc, self.h0c[l], self.c0c[l])
+            return
+        ns = max(1, (self._nb * Lc) // self.T)             # whole env sequences the work arrays of one minibatch hold
+        for e0 in range(0, self.N, ns):
+            e1 = min(e0 + ns, self.N)
+            n, whole = e1 - e0, e0 == 0 and e1 == self.N
+            w = {}
+            if n * self.T <= self._nb * Lc:
+                for l in range(L):
+                    for k in (f"stash{l}", f"y{l}"):
+                        a = self.work[k]
+                        w[k] = a.view(-1)[:n * self.T * a.shape[2]].view(n, self.T, a.shape[2])
+            h0, c0 = (self.h0, self.c0) if whole else (self.h0[:, e0:e1].contiguous(), self.c0[:, e0:e1].contiguous())
+            keep = b["keep"][e0:e1]
+            self.policy.heads(b["obs"][e0:e1], keep, h0, c0, w, want_heads=False)
+            for l, (_, stash, y, _) in enumerate(self.policy._saved[0]):
+                ops.lstm_chunk_states(y, stash, keep, h0[l], c0[l], Lc, self.h0c[l, e0 * C:e1 * C], self.c0c[l, e0 * C:e1 * C])
+            self.policy._saved = None
 
     def update(self):
         """GAE + EPOCHS x num_minibatches optimiser steps (_update_model, train_ppo2.0.py:15-88) -- with shuffle_envs over a
@@ -804,9 +878,11 @@ class VecPPOTrainer:
         self.compute_advantages()
         if self._succ_stage == _PACKED:
             self._exchange_successes()
-        b, hp = self.buf, self.hp
-        nb = self.N // self.num_minibatches
-        inv_n = 1.0 / float(nb * self.T * self.world)
+        u, hp = self._u, self.hp
+        nb = self._nb
+        inv_n = 1.0 / float(nb * self._Ls * self.world)
+        if self._C > 1:
+            self._chunk_start_states()
         grad_of = self._grad_lstm if self.kind == "lstm" else self._grad_fused_mlp if self.fused_mlp else self._grad_layered_mlp
         for _ in range(hp["epochs"]):
             if self.minibatch_rows is not None:
@@ -817,8 +893,8 @@ class VecPPOTrainer:
                 continue
             for m in range(self.num_minibatches):
                 sl = slice(m * nb, (m + 1) * nb)
-                grad = grad_of(sl, (b["act"][sl].reshape(-1), b["logp"][sl].reshape(-1), self.adv_n[sl].reshape(-1),
-                                    self.ret[sl].reshape(-1), b["val"][sl].reshape(-1), inv_n, hp["clip"], hp["ent_beta"],
+                grad = grad_of(sl, (u["act"][sl].reshape(-1), u["logp"][sl].reshape(-1), u["adv_n"][sl].reshape(-1),
+                                    u["ret"][sl].reshape(-1), u["val"][sl].reshape(-1), inv_n, hp["clip"], hp["ent_beta"],
                                     self.loss_sums, self.dheads, self.dhead_bias))
                 self._optimiser_step(grad)
         if self._guarded():

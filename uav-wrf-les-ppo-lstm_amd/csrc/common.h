@@ -99,6 +99,19 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// A global load at  uniform pointer + 32-bit byte offset + constant,  the scalar-base form
+//   global_load v, v_off, s[base:base+1] offset:imm
+// -- against a v_lshl_add_u64, and the integer VALU work in front of it, per load when a 64-bit address is built per lane.
+// For the compiler to pick that form in a loop, `ubase` must be loop-invariant (a kernel argument) and `off_bytes` must
+// change inside the loop: give it as  lane part (formed once) + uniform part of this iteration  -- one v_add_u32 with a
+// scalar operand per distinct uniform part, everything in front of it scalar arithmetic.  (Of a loop-invariant offset the
+// zero-extension is hoisted out of the loop as a VGPR pair, and the 64-bit adds are back.)  Keep imm_bytes inside the
+// immediate field (gfx950: -4096 .. 4095).
+template <class V>
+__device__ __forceinline__ V ld_ubase(const void* ubase, unsigned off_bytes, int imm_bytes = 0) {
+    return *reinterpret_cast<const V*>(static_cast<const char*>(ubase) + off_bytes + imm_bytes);
+}
+
 // LSTM gate activations: v_exp_f32 + v_rcp_f32 (1 ulp each).  A plain `1.0f / x` compiles to the
 // ~10-instruction IEEE division sequence; with 20 activations per lane per step that sequence,
 // not the MFMAs, paced the persistent kernels (tools/mfma_probe.hip).

@@ -375,12 +375,18 @@ __device__ __forceinline__ void lstm_wgrad_split(
     }
 
     // ---- A operand: raw dG values of this lane, [tile mi][row 8 kq + e]; tile 2p+m <-> gate rows 64w + 32p + 2i + m
+    // Addressing of every load stream below (ld_ubase, common.h): byte offsets from the kernel's pointers.  The slab's first
+    // row, clamped (the tail issues harmless reloads), and everything else that depends on the slab is workgroup- or
+    // wave-uniform and stays scalar; what depends on the lane is fixed for the whole kernel and formed here, once.
+    // The launch checks N*T*4H < 2^30, so every byte offset fits 32 bits.
+    auto slab_row = [&](int slab) { return r_begin + (slab < nslab ? slab : nslab - 1) * KS6; };
+    const unsigned a_lane = ((unsigned)(8 * kq) * (4 * H) + 2 * j) * 4;      // dG: rows 8 kq + e, gate columns .. + 2 j
     float raw[4][8];
+    constexpr int AR = 8192 / (16 * H) < 8 ? 8192 / (16 * H) : 8;            // dG rows that one base reaches with its immediate
     auto load_a_one = [&](int slab, int pair, int e) {
-        slab = slab < nslab ? slab : nslab - 1;                       // clamped: the tail issues harmless reloads
-        // 32-bit element offsets from the (scalar) base pointer: the launch checks N*T*4H < 2^30
-        const unsigned off = (unsigned)(r_begin + slab * KS6 + 8 * kq) * (4 * H) + 64 * w + 32 * pair + 2 * j;
-        const float2 t2 = *reinterpret_cast<const float2*>(dgates + (off + (unsigned)e * (4 * H)));
+        const int eb = e / AR * AR + AR / 2;                                 // the base sits in the middle of its rows
+        const unsigned ub = ((unsigned)(slab_row(slab) + eb) * (4 * H) + 64 * w + 32 * pair) * 4;
+        const float2 t2 = ld_ubase<float2>(dgates, a_lane + ub, (e - eb) * (4 * H) * 4);
         raw[2 * pair][e] = t2.x;
         raw[2 * pair + 1][e] = t2.y;
     };
@@ -393,31 +399,40 @@ __device__ __forceinline__ void lstm_wgrad_split(
     float v[NV], hz = 0.f, xv[XV], dv[DV];
     float kv = 1.f;                                                  // keep[q0 + (lane & 7)]: read back by v_readlane
     int i_start = -1;                                                // row of this thread's group with t == 0
+    // The set of loads per slab is the same whatever the slab holds: a load under a branch (no sequence start in the
+    // group, no keep, a padding column) makes the compiler lose count of the loads in flight and wait for all of them.  Such
+    // lanes load a word that exists and commit_b puts the constant in its place.
+    const unsigned c_lane = (unsigned)c * 4, k_lane = (unsigned)(lane & 7) * 4;
+    unsigned x_lane[XV], d_lane[DV];
+#pragma unroll
+    for (int k = 0; k < XV; ++k) {
+        const int idx = tid + k * NT, q = idx >> 4, f = idx & 15;
+        x_lane[k] = (unsigned)(q * I + (f < I ? f : 0)) * 4;
+    }
+#pragma unroll
+    for (int k = 0; k < DV; ++k) {
+        const int idx = tid + k * NT, q = idx >> 3, a = idx & 7;
+        d_lane[k] = (a < NH && q < KS6) ? (unsigned)(q * NH + a) * 4 : 0u;
+    }
+    const float* const keep_or_y = keep ? keep : y;                   // (N*T floats either way)
     auto load_b_y = [&](int slab, int i) {
-        slab = slab < nslab ? slab : nslab - 1;
-        const int rr = r_begin + slab * KS6 + 8 * rg - 1 + i;
-        v[i] = y[(unsigned)(rr < 0 ? 0 : rr) * H + c];
+        const int q0 = slab_row(slab) + 8 * rg;                       // first row of this thread's group (uniform)
+        if (i == 0) v[0] = ld_ubase<float>(y, c_lane + (unsigned)(q0 > 0 ? q0 - 1 : 0) * (H * 4));
+        else v[i] = ld_ubase<float>(y, c_lane + (unsigned)q0 * (H * 4), (i - 1) * H * 4);
     };
     auto load_b_rest = [&](int slab) {
-        slab = slab < nslab ? slab : nslab - 1;
-        const int q0 = r_begin + slab * KS6 + 8 * rg;                 // first row of this thread's group (uniform)
-        const int tq = q0 % T;                                        // T >= 8: at most one sequence start in 8 rows
+        const int r0 = slab_row(slab), q0 = r0 + 8 * rg;
+        const int nq = q0 / T, tq = q0 - nq * T;                      // T >= 8: at most one sequence start in 8 rows
         i_start = (tq == 0) ? 0 : (tq + 7 >= T ? T - tq : -1);
-        if (i_start >= 0) hz = h0[(unsigned)((q0 + i_start) / T) * H + c];
+        hz = ld_ubase<float>(h0, c_lane + (unsigned)(tq == 0 ? nq : min(nq + 1, N - 1)) * (H * 4));     // row (q0 + i_start) / T
         // a vector load, NOT a scalar one: s_load returns through lgkmcnt, so every LDS fragment wait behind it
         // would also wait out its HBM latency
-        kv = keep ? keep[q0 + (lane & 7)] : 1.f;
+        kv = ld_ubase<float>(keep_or_y, k_lane + (unsigned)q0 * 4);
 #pragma unroll
-        for (int k = 0; k < XV; ++k) {
-            const int idx = tid + k * NT, q = idx >> 4, f = idx & 15;
-            const unsigned r = (unsigned)(r_begin + slab * KS6 + q);
-            xv[k] = (f < I) ? x[r * I + f] : (f == 6 ? 1.f : 0.f);
-        }
+        for (int k = 0; k < XV; ++k) xv[k] = ld_ubase<float>(x, x_lane[k] + (unsigned)(r0 * I) * 4);
+        if (HEADS) {
 #pragma unroll
-        for (int k = 0; k < DV; ++k) {
-            const int idx = tid + k * NT, q = idx >> 3, a = idx & 7;
-            const unsigned r = (unsigned)(r_begin + slab * KS6 + (q < KS6 ? q : 0));
-            dv[k] = (HEADS && a < NH && q < KS6) ? dheads[r * NH + a] : 0.f;
+            for (int k = 0; k < DV; ++k) dv[k] = ld_ubase<float>(dheads, d_lane[k] + (unsigned)(r0 * NH) * 4);
         }
     };
     auto load_b = [&](int slab) {
@@ -432,7 +447,8 @@ __device__ __forceinline__ void lstm_wgrad_split(
         float hp[8], yy[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const float kpi = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, kv), i));
+            const float kld = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, kv), i));
+            const float kpi = keep ? kld : 1.f;
             hp[i] = ((i == i_start) ? hz : v[i]) * (kpi * P::BSCALE);
             yy[i] = HEADS ? v[i + 1 < NV ? i + 1 : 0] : 0.f;
         }
@@ -450,7 +466,7 @@ __device__ __forceinline__ void lstm_wgrad_split(
         for (int k = 0; k < XV; ++k) {
             const int idx = tid + k * NT, q = idx >> 4, f = idx & 15;
             typename P::piece xq[NP];
-            P::split(xv[k] * P::XSCALE, xq);
+            P::split(((f < I) ? xv[k] : (f == 6 ? 1.f : 0.f)) * P::XSCALE, xq);       // column 6 = ones -> db
             unsigned short* d = bp + (H + f) * KP + q;
 #pragma unroll
             for (int p = 0; p < NP; ++p) d[p * BPL] = P::bits(xq[p]);
@@ -461,7 +477,7 @@ __device__ __forceinline__ void lstm_wgrad_split(
                 const int idx = tid + k * NT, q = idx >> 3, a = idx & 7;
                 if (q < KS6) {
                     __bf16 pa, pb, pc;
-                    split3(dv[k], pa, pb, pc);
+                    split3(a < NH ? dv[k] : 0.f, pa, pb, pc);
                     unsigned short* d = dp + a * KP + q;
                     d[0] = bf_bits(pa);
                     d[DPL] = bf_bits(pb);
@@ -531,6 +547,9 @@ __device__ __forceinline__ void lstm_wgrad_split(
         WX_PROF_MARK(0);
         mfma_pair(buf, 0, sl);
         WX_PROF_DEP(acc[0][NT_ - 1]); WX_PROF_DEP(acc[1][NT_ - 1]); WX_PROF_MARK(2);
+        // commit_b is the first reader of the B-side loads, the youngest in flight at the top of the slab: nothing of it may be
+        // scheduled up into pair 0's block, or its wait for them (all loads, at that point) lands there as well
+        __builtin_amdgcn_sched_barrier(0);
         commit_b(buf ^ 1);                                // planes of slab sl + 1 (a clamped copy on the last slab)
         if constexpr (!P::LOADS_BETWEEN_TILES) load_b(sl + 2);
         WX_PROF_MARK(5);
@@ -545,18 +564,21 @@ __device__ __forceinline__ void lstm_wgrad_split(
     }
     WX_PROF_FLUSH();
     float* slab = slabs + (size_t)blockIdx.x * WG<H>::SLAB;
+    // the lane's coordinates once more, from the hardware: so none of them stays in a register through the loop for this
+    const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int jo = ln & 15, ko = ln >> 4;
 #pragma unroll
     for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float usc = pol.row_unscale(mi, r, kq);
+            const float usc = pol.row_unscale(mi, r, ko);
 #pragma unroll
             for (int ni = 0; ni < NT_; ++ni)
-                slab[(size_t)(64 * w + 32 * (mi >> 1) + 2 * (4 * kq + r) + (mi & 1)) * G::NC + 16 * ni + j] =
+                slab[(size_t)(64 * w + 32 * (mi >> 1) + 2 * (4 * ko + r) + (mi & 1)) * G::NC + 16 * ni + jo] =
                     acc[mi][ni][r] * (ni == NT_ - 1 ? usc * (P::BSCALE / P::XSCALE) : usc);
         }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) slab[(size_t)4 * H * G::NC + (size_t)(4 * kq + r) * H + 16 * w + j] = acch[r];
+    for (int r = 0; r < 4; ++r) slab[(size_t)4 * H * G::NC + (size_t)(4 * ko + r) * H + 16 * w + jo] = acch[r];
 }
 
 // the entry points, one per arithmetic: profiles and bench.py find the kernels by these names in a kernel trace

@@ -134,6 +134,36 @@ int uav_ppo_loss_from_y(uav_ctx* ctx, const float* y, const float* w_head, const
                         float ent_beta, double* loss_sums, float* dheads, float* dhead_bias,
                         uav_stream stream);
 
+/* Update diagnostics of the loss-bearing entry points: how far a call's samples have moved from the rollout policy.
+ * While a buffer is attached to the handle, uav_ppo_loss (both layouts), uav_ppo_loss_from_y, uav_mlp_ppo_grad,
+ * uav_mlp_ppo_grad_trend and uav_mlp_ppo_grad_rows launch the diagnostic instantiation of their loss kernel and OVERWRITE
+ * diag (device f64 [UAV_PPO_DIAG_N]) with that call's sums over its n samples, on the call's stream:
+ *   [UAV_PPO_DIAG_KL_K1]    sum of logp_old - logp                            (k1 estimator of the KL to the rollout policy)
+ *   [UAV_PPO_DIAG_KL_K3]    sum of expm1(lr) - lr, lr = logp - logp_old       (k3 estimator: every term >= 0)
+ *   [UAV_PPO_DIAG_CLIPPED]  count of ratio < 1 - clip or ratio > 1 + clip
+ *   [UAV_PPO_DIAG_VCLIPPED] count of |V - val_old| > clip
+ *   [UAV_PPO_DIAG_VERR2]    sum of (ret - V)^2
+ *   [UAV_PPO_DIAG_RET]      sum of ret
+ *   [UAV_PPO_DIAG_RET2]     sum of ret^2
+ *   [UAV_PPO_DIAG_COUNT]    n
+ * logp, lr, ratio and V are the f32 values the loss itself uses; the arithmetic on them, expm1 included, is f64.  The sums
+ * are reduced in a fixed order (block partials, one final pass) and repeat bit for bit.  Every other output of the call is
+ * bit-identical to the call without a buffer attached.  Samples with NaN probabilities are not special-cased: loss_sums[3]
+ * counts them as before and the sums they enter become NaN; a ratio that overflows f32 (lr > 88.7) adds more than 3.4e38 to
+ * the k3 sum, lr = +inf (logp_old = -inf) makes it infinite.  NULL detaches (the state of a new handle): the calls then run
+ * the kernels without the diagnostics and never touch a former buffer.  The pointer is kept, not the memory: detach before
+ * the buffer is freed.  Added without a change of UAV_ABI_VERSION (a symbol only). */
+#define UAV_PPO_DIAG_N 8
+#define UAV_PPO_DIAG_KL_K1 0
+#define UAV_PPO_DIAG_KL_K3 1
+#define UAV_PPO_DIAG_CLIPPED 2
+#define UAV_PPO_DIAG_VCLIPPED 3
+#define UAV_PPO_DIAG_VERR2 4
+#define UAV_PPO_DIAG_RET 5
+#define UAV_PPO_DIAG_RET2 6
+#define UAV_PPO_DIAG_COUNT 7
+int uav_set_ppo_diag(uav_ctx* ctx, double* diag);
+
 /* ---- K3 (sampling part): softmax + Categorical sample + log_prob + NaN check
  * (train_ppo2.0.py:161-163,189; torch Categorical(probs) semantics).  u: uniforms in [0,1)
  * [n] or NULL to use the counter RNG: row i draws from Philox(seed; counter & 0xffffffff, index_offset + i,

@@ -57,6 +57,8 @@ NUM_LAYERS = 1
 NUM_MINIBATCHES = 1      # the reference uses ONE minibatch of the whole buffer per epoch (train_ppo2.0.py:44-45)
 SHUFFLE_ENVS = False     # True (with NUM_MINIBATCHES > 1): every epoch cuts a fresh permutation of the envs into the minibatches
 BPTT_LEN = None          # LSTM: truncated BPTT over chunks of this many steps (divides HORIZON); None = whole env sequences
+PPO_DIAGNOSTICS = False  # True: per-epoch approx. KL / clip fractions / explained variance of every update (update_diagnostics.csv)
+TARGET_KL = None         # a positive number: stop an update's epochs once the epoch's approx. KL (k3) exceeds it; implies PPO_DIAGNOSTICS
 GAE_MODE = "reference_exact"   # or "standard" (PPOV1.0/ppo0.0.py:337-350)
 SEED = 1234
 TREND_K = 0              # extra observation channels obs[2](t) - obs[2](t-1-i), i < TREND_K (BASELINE C5: 2)

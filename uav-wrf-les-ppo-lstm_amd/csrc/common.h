@@ -43,6 +43,7 @@ struct uav_ctx {
     // the same for the last few h = 256 stashes uav_lstm_fwd / the stepper wrote (1 = h_prev slot written, 0 = left out by the
     // fp16-split path): uav_lstm_wgrad refuses to read a slot the forward pass did not write (mode changed in between)
     uav_form_table hslot_form;
+    double* ppo_diag;  // device f64[UAV_PPO_DIAG_N] the loss-bearing entry points overwrite with their diagnostic sums, or NULL (uav_set_ppo_diag)
 };
 static inline void uav_dg_record(uav_ctx* ctx, const void* p, int packed) { ctx->dg_form.record(p, packed); }
 static inline int uav_dg_form(const uav_ctx* ctx, const void* p) { return ctx->dg_form.find(p); }    // -1 = not recorded (filled by the caller)

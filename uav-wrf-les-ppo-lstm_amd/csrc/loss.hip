@@ -25,13 +25,27 @@ __device__ __forceinline__ void loss_block_epilogue(const LossAcc& a, const floa
     }
 }
 
-template <int A>
+// DIAG: the block's diagnostic sums, by the same fixed tree, to row blockIdx.x of the diagnostics' own partials
+__device__ __forceinline__ void diag_block_epilogue(const DiagAcc& d, double* partial) {
+    __shared__ double sm[4];
+    double t[UAV_PPO_DIAG_N];
+#pragma unroll
+    for (int k = 0; k < UAV_PPO_DIAG_N; ++k) t[k] = block256_sum(d.s[k], sm);
+    if (threadIdx.x == 0) {
+        double* dp = diag_partials(partial) + (size_t)UAV_PPO_DIAG_N * blockIdx.x;
+#pragma unroll
+        for (int k = 0; k < UAV_PPO_DIAG_N; ++k) dp[k] = t[k];
+    }
+}
+
+template <int A, bool DIAG = false>
 __global__ __launch_bounds__(256) void ppo_loss_kernel(
     const float* __restrict__ logits, const float* __restrict__ value, const int32_t* __restrict__ act,
     const float* __restrict__ logp_old, const float* __restrict__ adv, const float* __restrict__ ret,
     const float* __restrict__ val_old, int64_t n, float inv_n, float clip, float beta,
     double* __restrict__ partial, float* __restrict__ dlogits, float* __restrict__ dvalue, int ldl, int ldv) {
     LossAcc acc{0.0, 0.0, 0.0, 0.0};
+    DiagAcc dg{};
     float s_db[A + 1];                       // column sums of (dlogits | dvalue) = gradient of the head biases
 #pragma unroll
     for (int k = 0; k <= A; ++k) s_db[k] = 0.f;
@@ -39,8 +53,8 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(
         float z[A], dz[A];
 #pragma unroll
         for (int k = 0; k < A; ++k) z[k] = logits[i * ldl + k];
-        const float dV = ppo_sample<A>(z, value[i * ldv], act[i], logp_old[i], adv[i], ret[i], val_old[i], inv_n, clip,
-                                       beta, acc, dz);
+        const float dV = ppo_sample<A, DIAG>(z, value[i * ldv], act[i], logp_old[i], adv[i], ret[i], val_old[i], inv_n, clip,
+                                             beta, acc, dz, &dg);
         dvalue[i * ldv] = dV;
         s_db[A] += dV;
 #pragma unroll
@@ -50,6 +64,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(
         }
     }
     loss_block_epilogue<A>(acc, s_db, partial);
+    if constexpr (DIAG) diag_block_epilogue(dg, partial);
 }
 
 // ---- heads fused into the loss: heads = y W_head^T + b_head by MFMA straight from the LSTM output ----
@@ -60,7 +75,7 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(
 // 16x16 result tiles are transposed through LDS so that lane l owns sample l, then the same per-sample
 // loss math runs.  `heads` is never written to HBM and the separate heads GEMM disappears.
 typedef float f32x4_l __attribute__((ext_vector_type(4)));
-template <int A, int H>
+template <int A, int H, bool DIAG = false>
 __global__ __launch_bounds__(256) void ppo_loss_from_y_kernel(
     const float* __restrict__ y, const float* __restrict__ w_head, const float* __restrict__ b_head,
     const int32_t* __restrict__ act, const float* __restrict__ logp_old, const float* __restrict__ adv,
@@ -77,6 +92,7 @@ __global__ __launch_bounds__(256) void ppo_loss_from_y_kernel(
     }
     __syncthreads();
     LossAcc acc{0.0, 0.0, 0.0, 0.0};
+    DiagAcc dg{};
     float s_db[A + 1];
 #pragma unroll
     for (int k = 0; k <= A; ++k) s_db[k] = 0.f;
@@ -129,7 +145,7 @@ __global__ __launch_bounds__(256) void ppo_loss_from_y_kernel(
 #pragma unroll
             for (int k = 0; k < A; ++k) z[k] = hd[w][lane * 9 + k] + bh[k];
             const float V = hd[w][lane * 9 + A] + bh[A];
-            const float dV = ppo_sample<A>(z, V, act[i], logp_old[i], adv[i], ret[i], val_old[i], inv_n, clip, beta, acc, dz);
+            const float dV = ppo_sample<A, DIAG>(z, V, act[i], logp_old[i], adv[i], ret[i], val_old[i], inv_n, clip, beta, acc, dz, &dg);
             s_db[A] += dV;
 #pragma unroll
             for (int k = 0; k < A; ++k) {
@@ -141,6 +157,7 @@ __global__ __launch_bounds__(256) void ppo_loss_from_y_kernel(
         __builtin_amdgcn_wave_barrier();
     }
     loss_block_epilogue<A>(acc, s_db, partial);
+    if constexpr (DIAG) diag_block_epilogue(dg, partial);
 }
 
 // one pass over the block partials: thread (column c = tid % 16, row group g = tid / 16) sums rows g, g+64, ... of
@@ -168,6 +185,24 @@ __global__ __launch_bounds__(1024) void loss_final_kernel(const double* __restri
         else if (dbias) dbias[threadIdx.x - 4] = (float)r;
     }
 }
+
+// the diagnostics' partials [nb][UAV_PPO_DIAG_N] -> diag[UAV_PPO_DIAG_N]: thread (column c = tid % 8, row group g = tid / 8) sums rows
+// g, g + 64, ... of column c in order, then the 64 group sums of a column are added in a fixed order
+__global__ __launch_bounds__(512) void diag_final_kernel(const double* __restrict__ dpartial, int nb, double* __restrict__ diag) {
+    __shared__ double sm[64][UAV_PPO_DIAG_N + 1];
+    const int c = threadIdx.x & (UAV_PPO_DIAG_N - 1), g = threadIdx.x / UAV_PPO_DIAG_N;
+    double s = 0.0;
+    for (int i = g; i < nb; i += 64) s += dpartial[(size_t)UAV_PPO_DIAG_N * i + c];
+    sm[g][c] = s;
+    __syncthreads();
+    if (threadIdx.x < UAV_PPO_DIAG_N) {
+        double r = 0.0;
+#pragma unroll
+        for (int k = 0; k < 64; ++k) r += sm[k][threadIdx.x];
+        diag[threadIdx.x] = r;
+    }
+}
+static_assert(UAV_PPO_DIAG_N == 8, "diag_final_kernel: 512 threads = 64 row groups x 8 columns");
 
 // ---- sampling ------------------------------------------------------------------------------------
 template <int A>
@@ -226,6 +261,13 @@ int launch_loss_final(double* partial, int nb, int n_heads, double* loss_sums, f
     return 0;
 }
 
+// the same for the diagnostics' partials a DIAG kernel of `nb` blocks left behind its loss partials (loss_core.h: diag_partials)
+int launch_diag_final(double* partial, int nb, double* diag, hipStream_t st) {
+    hipLaunchKernelGGL(diag_final_kernel, dim3(1), dim3(512), 0, st, partial + (size_t)LOSS_PSTRIDE * nb, nb, diag);
+    UAV_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" {
 
 int uav_ppo_loss(uav_ctx* ctx, const float* logits, const float* value, const int32_t* act,
@@ -242,9 +284,16 @@ int uav_ppo_loss(uav_ctx* ctx, const float* logits, const float* value, const in
     int nb = (int)((n + 255) / 256);
     if (nb > LOSS_BLOCKS) nb = LOSS_BLOCKS;
     double* partial = (double*)ctx->ws;
-#define LAUNCH_LOSS(A_)                                                                                  \
-    hipLaunchKernelGGL(ppo_loss_kernel<A_>, dim3(nb), dim3(256), 0, as_stream(stream), logits, value,   \
+    double* const diag = ctx->ppo_diag;      // uav_set_ppo_diag: attached = the DIAG instantiation + its final pass
+    UAV_REQUIRE(!diag || ctx->ws_bytes >= (size_t)nb * (LOSS_PSTRIDE + UAV_PPO_DIAG_N) * sizeof(double), "uav_ppo_loss: workspace too small");
+#define LAUNCH_LOSS_(A_, D_)                                                                                \
+    hipLaunchKernelGGL((ppo_loss_kernel<A_, D_>), dim3(nb), dim3(256), 0, as_stream(stream), logits, value, \
                        act, logp_old, adv, ret, val_old, n, inv_n, clip, ent_beta, partial, dlogits, dvalue, ldl, ldv)
+#define LAUNCH_LOSS(A_)                     \
+    do {                                    \
+        if (diag) LAUNCH_LOSS_(A_, true);   \
+        else LAUNCH_LOSS_(A_, false);       \
+    } while (0)
     switch (n_act) {
         case 2: LAUNCH_LOSS(2); break;
         case 3: LAUNCH_LOSS(3); break;
@@ -255,10 +304,11 @@ int uav_ppo_loss(uav_ctx* ctx, const float* logits, const float* value, const in
         default: UAV_REQUIRE(false, "uav_ppo_loss: n_act=%d unsupported", n_act);
     }
 #undef LAUNCH_LOSS
+#undef LAUNCH_LOSS_
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, as_stream(stream), partial, nb, n_act + 1, loss_sums,
                        dhead_bias);
     UAV_LAUNCH_CHECK();
-    return 0;
+    return diag ? launch_diag_final(partial, nb, diag, as_stream(stream)) : 0;
 }
 
 int uav_ppo_loss_from_y(uav_ctx* ctx, const float* y, const float* w_head, const float* b_head, const int32_t* act,
@@ -271,9 +321,16 @@ int uav_ppo_loss_from_y(uav_ctx* ctx, const float* y, const float* w_head, const
     int nb = (int)((n + 255) / 256);
     if (nb > LOSS_BLOCKS) nb = LOSS_BLOCKS;
     double* partial = (double*)ctx->ws;
-#define LAUNCH_LY(H_)                                                                                             \
-    hipLaunchKernelGGL((ppo_loss_from_y_kernel<5, H_>), dim3(nb), dim3(256), 0, as_stream(stream), y, w_head, b_head, \
+    double* const diag = ctx->ppo_diag;
+    UAV_REQUIRE(!diag || ctx->ws_bytes >= (size_t)nb * (LOSS_PSTRIDE + UAV_PPO_DIAG_N) * sizeof(double), "uav_ppo_loss_from_y: workspace too small");
+#define LAUNCH_LY_(H_, D_)                                                                                                \
+    hipLaunchKernelGGL((ppo_loss_from_y_kernel<5, H_, D_>), dim3(nb), dim3(256), 0, as_stream(stream), y, w_head, b_head, \
                        act, logp_old, adv, ret, val_old, n, inv_n, clip, ent_beta, partial, dheads)
+#define LAUNCH_LY(H_)                     \
+    do {                                  \
+        if (diag) LAUNCH_LY_(H_, true);   \
+        else LAUNCH_LY_(H_, false);       \
+    } while (0)
     switch (hidden) {
         case 64: LAUNCH_LY(64); break;
         case 128: LAUNCH_LY(128); break;
@@ -281,10 +338,11 @@ int uav_ppo_loss_from_y(uav_ctx* ctx, const float* y, const float* w_head, const
         default: UAV_REQUIRE(false, "uav_ppo_loss_from_y: hidden=%d unsupported (64/128/256)", hidden);
     }
 #undef LAUNCH_LY
+#undef LAUNCH_LY_
     hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, as_stream(stream), partial, nb, n_act + 1, loss_sums,
                        dhead_bias);
     UAV_LAUNCH_CHECK();
-    return 0;
+    return diag ? launch_diag_final(partial, nb, diag, as_stream(stream)) : 0;
 }
 
 int uav_policy_sample(uav_ctx* ctx, const float* logits, int64_t n, int n_act, const float* u,

@@ -126,10 +126,51 @@ constexpr int LOSS_PSTRIDE = 16;   // doubles per block partial: 4 loss sums + u
 
 struct LossAcc { double pl, vl, en, nan; };
 
-// one sample: loss terms into `acc`, d(total)/d(logits) into dz[A], d(total)/dV returned
-template <int A>
+// Update diagnostics (uav_set_ppo_diag): UAV_PPO_DIAG_N f64 sums over a call's samples, by-products of the loss arithmetic.
+// They exist in the DIAG = true instantiations only; DIAG = false is the loss code without them.
+//   [UAV_PPO_DIAG_KL_K1]    logp_old - logp                      the k1 estimator of KL(old || new)
+//   [UAV_PPO_DIAG_KL_K3]    expm1(lr) - lr, lr = logp - logp_old the k3 estimator (non-negative)
+//   [UAV_PPO_DIAG_CLIPPED]  count of ratio < 1 - clip or ratio > 1 + clip
+//   [UAV_PPO_DIAG_VCLIPPED] count of |V - v_old| > clip
+//   [UAV_PPO_DIAG_VERR2]    (R - V)^2
+//   [UAV_PPO_DIAG_RET]      R
+//   [UAV_PPO_DIAG_RET2]     R^2
+//   [UAV_PPO_DIAG_COUNT]    the sample count
+// logp, ratio, V and lr are the f32 values the loss itself uses; the arithmetic on them is f64 (in f32 (ratio - 1) - lr cancels
+// to nothing at the small lr that matters), expm1 included.  Samples with NaN probabilities are not special-cased: loss_sums[3]
+// counts them as before and they make the sums they enter NaN; a ratio that overflows (lr > 88.7 in f32) puts more than 3.4e38
+// into the k3 sum, and lr = +inf (logp_old = -inf) makes it infinite.
+struct DiagAcc { double s[UAV_PPO_DIAG_N]; };
+
+// expm1(x) - x in f64 for the k3 estimator, in a dozen registers: libm's expm1 inlined into mlp_ppo_grad_kernel (a kernel at
+// its 256-VGPR limit) tripled that kernel's spills.  |x| <= 1/4: the series x^2 / 2! + x^3 / 3! + ... + x^14 / 14! by Horner
+// -- no cancellation against x, truncation x^15 / 15! < 3e-18 of the leading term, every term of one sign or alternating and
+// decreasing, so the result is >= 0.  Larger |x| (< 1024): y = x 2^-k with |y| <= 1/4, expm1(y) by the same series, then k
+// times expm1(2 t) = E (E + 2) -- about one ulp per doubling, k <= 12 -- and x is subtracted; overflow past x = 709.8 gives
+// +inf by itself.  |x| >= 1024, infinite or NaN: the limits (+inf, -1 - x, NaN).
+__device__ __forceinline__ double diag_expm1_series(double y, bool minus_y) {      // expm1(y) (- y), |y| <= 1/4
+    double p = 1.0 / 14.0;
+#pragma unroll
+    for (int n = 13; n >= 3; --n) p = __builtin_fma(p, y, 1.0) * (1.0 / n);       // ... (1 + y / (n + 1) (...)) / n
+    p = __builtin_fma(p, y, 1.0) * 0.5 * y * y;                                     // y^2 / 2 + y^3 / 6 + ...
+    return minus_y ? p : p + y;
+}
+__device__ __forceinline__ double diag_k3(double x) {
+    const double ax = __builtin_fabs(x);
+    if (ax <= 0.25) return diag_expm1_series(x, true);
+    if (!(ax < 1024.0)) return x > 0.0 ? __builtin_inf() : (x < 0.0 ? -1.0 - x : x);
+    const int k = (int)((__builtin_bit_cast(unsigned long long, ax) >> 52) & 0x7ff) - 1023 + 3;      // |x| < 2^(k - 2), so |y| < 1/4; k in 1 .. 12
+    double E = diag_expm1_series(ldexp(x, -k), false);
+    for (int i = 0; i < k; ++i) E = E * (E + 2.0);
+    return E - x;
+}
+// block partials of the diagnostics: [gridDim.x][UAV_PPO_DIAG_N] doubles right behind the gridDim.x loss partials
+__device__ __forceinline__ double* diag_partials(double* loss_partial) { return loss_partial + (size_t)LOSS_PSTRIDE * gridDim.x; }
+
+// one sample: loss terms into `acc`, d(total)/d(logits) into dz[A], d(total)/dV returned; DIAG: the diagnostic terms into *dg
+template <int A, bool DIAG = false>
 __device__ __forceinline__ float ppo_sample(const float* z, float V, int a, float lpo, float Ad, float R, float vo,
-                                            float inv_n, float clip, float beta, LossAcc& acc, float* dz) {
+                                            float inv_n, float clip, float beta, LossAcc& acc, float* dz, DiagAcc* dg = nullptr) {
     float p[A];
     softmax_row<A>(z, p);
     float psum = 0.f;
@@ -189,6 +230,17 @@ __device__ __forceinline__ float ppo_sample(const float* z, float V, int a, floa
         const float dpol = g_logp * ((k == a ? 1.0f : 0.0f) - q[k]);
         const float dent = -beta * inv_n * p[k] * (hk[k] - ph);
         dz[k] = dpol + dent;
+    }
+    if constexpr (DIAG) {
+        const double lr = (double)(logp - lpo), Rd = (double)R, er = Rd - (double)V;      // lr: the f32 argument of the ratio's expf
+        dg->s[UAV_PPO_DIAG_KL_K1] -= lr;
+        dg->s[UAV_PPO_DIAG_KL_K3] += diag_k3(lr);          // f64: the f32 ratio's own rounding (6e-8) would swamp lr^2 / 2
+        dg->s[UAV_PPO_DIAG_CLIPPED] += (ratio < lo || ratio > hi) ? 1.0 : 0.0;
+        dg->s[UAV_PPO_DIAG_VCLIPPED] += (fabsf(dv) > clip) ? 1.0 : 0.0;
+        dg->s[UAV_PPO_DIAG_VERR2] += er * er;
+        dg->s[UAV_PPO_DIAG_RET] += Rd;
+        dg->s[UAV_PPO_DIAG_RET2] += Rd * Rd;
+        dg->s[UAV_PPO_DIAG_COUNT] += 1.0;
     }
     return 0.5f * inv_n * gV;
 }

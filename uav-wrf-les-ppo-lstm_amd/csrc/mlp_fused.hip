@@ -26,6 +26,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 int env_params_from_cfg(const uav_ctx* ctx, const uav_env_cfg* cfg, int n_env, EnvParams& P);
 int launch_loss_final(double* partial, int nb, int n_heads, double* loss_sums, float* dhead_bias, hipStream_t st);
+int launch_diag_final(double* partial, int nb, double* diag, hipStream_t st);
 
 #ifdef UAV_X6_PROFILE
 // phase timing (instrumented build only, tools/build_prof.sh): cycles per phase summed over the tiles of workgroup 0,
@@ -721,6 +722,9 @@ constexpr int LS_STRIDE = 10;             // doubles per loss lane: policy / val
 // + (H3) P2 [2 pieces][MS][RS2] dz2 as scaled fp16 planes, MX [8 waves][MS] per-sample maxima for their scale
 constexpr int UPD_FLOATS = Tiles<UNC>::FLOATS + 2 * H1 + 3 * H2 + UMS * 8 + 2 * UMS * LS_STRIDE + H1 * 8 + 8 * H2 + UMS * RS2 + NWAVE * UMS + UMS * RS2;
 constexpr size_t UPD_LDS = (size_t)UPD_FLOATS * sizeof(float);
+// DIAG (uav_set_ppo_diag): + DLS [MS][UAV_PPO_DIAG_N] doubles, the loss lanes' running diagnostic sums, behind everything else
+constexpr size_t UPD_LDS_DIAG = UPD_LDS + (size_t)UMS * UAV_PPO_DIAG_N * sizeof(double);
+static_assert(UPD_LDS % sizeof(double) == 0 && UPD_LDS_DIAG <= 160 * 1024, "mlp_ppo_grad_kernel: LDS over 160 KB per workgroup");
 // one gradient slab per workgroup, flat parameter layout: MlpOff(in).N floats
 
 // H3: the two K = 256 / K = 128 products (layer 2 forward, da1 = W2^T dz2) on the fp16 matrix pipe at f32 accuracy; `w2t`
@@ -733,7 +737,9 @@ constexpr size_t UPD_LDS = (size_t)UPD_FLOATS * sizeof(float);
 // ROWS (uav_mlp_ppo_grad_rows): sample s of the launch is row rows[s] of the Bt-row buffers -- the observation row and the five
 // per-sample scalars are gathered, everything behind the staging is the contiguous form's.  The index of the NEXT tile is
 // fetched with this tile's loads, so a tile's gathers never wait for their index; an index outside [0, Bt) is clamped.
-template <bool H3, int INW = IN, bool ROWS = false>
+// DIAG: the loss lanes also keep the update diagnostics (loss_core.h: DiagAcc), in LDS like their loss sums, and lane 0 leaves
+// the workgroup's eight sums behind the loss partials.  DIAG = false compiles to the kernels as they were.
+template <bool H3, int INW = IN, bool ROWS = false, bool DIAG = false>
 __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     const float* __restrict__ params, const float* __restrict__ obs, const int32_t* __restrict__ act,
     const float* __restrict__ logp_old, const float* __restrict__ adv, const float* __restrict__ ret,
@@ -759,6 +765,7 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     // dz2 once more for dW2 = dz2^T a1 (K = the tile's samples, so the scale must not depend on the sample): plane 0 =
     // fp16(x), plane 1 = fp16(x - plane 0) with x = dz2 * 2^e_run, e_run the WAVE's running power of two (below)
     unsigned short* P2w = reinterpret_cast<unsigned short*>(MX + NWAVE * MS);
+    double* DLS = reinterpret_cast<double*>(smem + UPD_FLOATS);     // DIAG only
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -796,6 +803,8 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     for (int i = 0; i < 16; ++i) dW2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     dW1[0] = dW1[1] = dWh = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int i = threadIdx.x; i < MS * LS_STRIDE; i += 512) LS[i] = 0.0;
+    if constexpr (DIAG)
+        for (int i = threadIdx.x; i < MS * UAV_PPO_DIAG_N; i += 512) DLS[i] = 0.0;
 
     // H3: the dW2 accumulators of this wave hold dW2 * 2^e_run: dz2 rows of this wave's 16 units enter the fp16 product
     // scaled by a power of two that puts the largest magnitude seen SO FAR in [2^13, 2^14); when a tile brings a larger one
@@ -882,7 +891,10 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
                     for (int a = 0; a < NA; ++a) z[a] = L.HD[lane * 8 + a];
                     double* ls = LS + lane * LS_STRIDE;
                     LossAcc lacc{ls[0], ls[1], ls[2], ls[3]};
-                    dV = ppo_sample<NA>(z, L.HD[lane * 8 + NA], a_s, lpo, Ad, Rt, vo, inv_n, clip, beta, lacc, dz);
+                    if constexpr (DIAG) {
+                        DiagAcc* dg = reinterpret_cast<DiagAcc*>(DLS + lane * UAV_PPO_DIAG_N);
+                        dV = ppo_sample<NA, true>(z, L.HD[lane * 8 + NA], a_s, lpo, Ad, Rt, vo, inv_n, clip, beta, lacc, dz, dg);
+                    } else dV = ppo_sample<NA>(z, L.HD[lane * 8 + NA], a_s, lpo, Ad, Rt, vo, inv_n, clip, beta, lacc, dz);
                     ls[0] = lacc.pl; ls[1] = lacc.vl; ls[2] = lacc.en; ls[3] = lacc.nan;
                     // head-bias gradient sums: f32 running sums as before (kept as f32 VALUES in the f64 slots)
 #pragma unroll
@@ -1238,6 +1250,14 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
                 pp[k] = t;
                 if (k >= 4) slab[O.BH + k - 4] = (float)t;
             }
+            if constexpr (DIAG) {
+                double* dp = diag_partials(loss_partial) + (size_t)UAV_PPO_DIAG_N * blockIdx.x;
+                for (int k = 0; k < UAV_PPO_DIAG_N; ++k) {
+                    double t = 0.0;
+                    for (int sj = 0; sj < MS; ++sj) t += DLS[sj * UAV_PPO_DIAG_N + k];
+                    dp[k] = t;
+                }
+            }
         }
     }
 }
@@ -1362,11 +1382,18 @@ static int mlp_ppo_grad_impl(const char* who, uav_ctx* ctx, const float* params,
     double* partial = (double*)ctx->ws;
     float* w2t = (float*)((char*)ctx->ws + head);
     float* slabs = (float*)((char*)ctx->ws + head + w2t_bytes);
+    double* const diag = ctx->ppo_diag;      // uav_set_ppo_diag: attached = the DIAG instantiation + its final pass
+    UAV_REQUIRE(!diag || (size_t)nb * (LOSS_PSTRIDE + UAV_PPO_DIAG_N) * sizeof(double) <= head, "%s: %d workgroups' loss partials over the workspace head", who, nb);
+#define LAUNCH_GRAD__(H3_, INW_, ROWS_, D_, LDS_)                                                                                \
+    do {                                                                                                                         \
+        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&mlp_ppo_grad_kernel<H3_, INW_, ROWS_, D_>), (int)(LDS_)));      \
+        hipLaunchKernelGGL((mlp_ppo_grad_kernel<H3_, INW_, ROWS_, D_>), dim3(nb), dim3(512), LDS_, st, params, obs, act, logp_old, adv, \
+                           ret, val_old, n, inv_n, clip, ent_beta, partial, slabs, w2t, in, rows, n_total);                      \
+    } while (0)
 #define LAUNCH_GRAD_(H3_, INW_, ROWS_)                                                                                           \
     do {                                                                                                                         \
-        UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&mlp_ppo_grad_kernel<H3_, INW_, ROWS_>), (int)UPD_LDS));         \
-        hipLaunchKernelGGL((mlp_ppo_grad_kernel<H3_, INW_, ROWS_>), dim3(nb), dim3(512), UPD_LDS, st, params, obs, act, logp_old, adv, \
-                           ret, val_old, n, inv_n, clip, ent_beta, partial, slabs, w2t, in, rows, n_total);                      \
+        if (diag) LAUNCH_GRAD__(H3_, INW_, ROWS_, true, UPD_LDS_DIAG);                                                           \
+        else LAUNCH_GRAD__(H3_, INW_, ROWS_, false, UPD_LDS);                                                                    \
     } while (0)
 #define LAUNCH_GRAD(H3_, INW_)                                                                                                   \
     do {                                                                                                                         \
@@ -1384,9 +1411,11 @@ static int mlp_ppo_grad_impl(const char* who, uav_ctx* ctx, const float* params,
     }
 #undef LAUNCH_GRAD
 #undef LAUNCH_GRAD_
+#undef LAUNCH_GRAD__
     hipLaunchKernelGGL(mlp_slab_reduce_kernel, dim3((O.N + 255) / 256), dim3(256), 0, st, slabs, nb, O.N, grad);
     UAV_LAUNCH_CHECK();
-    return launch_loss_final(partial, nb, NH, loss_sums, nullptr, st);
+    const int rc = launch_loss_final(partial, nb, NH, loss_sums, nullptr, st);
+    return (rc || !diag) ? rc : launch_diag_final(partial, nb, diag, st);
 }
 
 extern "C" int uav_mlp_ppo_grad(uav_ctx* ctx, const float* params, const float* obs, const int32_t* act,

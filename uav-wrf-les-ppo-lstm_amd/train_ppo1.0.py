@@ -21,7 +21,8 @@ import os
 import numpy as np
 import torch
 
-from config import BATCH_SIZE, CLIP_EPSILON, ENTROPY_BETA, EPOCHS, GAMMA, LAMBDA, LEARNING_RATE, SEED, WINDOW_SIZE
+from config import (BATCH_SIZE, CLIP_EPSILON, ENTROPY_BETA, EPOCHS, GAMMA, LAMBDA, LEARNING_RATE, PPO_DIAGNOSTICS, SEED, TARGET_KL,
+                    WINDOW_SIZE)
 from environment import MethaneEnv
 from model import PPOActorCritic, PPOBuffer, PPOTrainer
 from uavppo import ops
@@ -33,11 +34,15 @@ _spec.loader.exec_module(_t20)
 ClipAdam = _t20.ClipAdam
 
 
-def _update_inline(buffer, next_value, model, optimizer, perms=None):
+def _update_inline(buffer, next_value, model, optimizer, perms=None, diag_out=None):
     """train_ppo1.0.py:64-141 on the GPU: GAE bootstrapped from next_value = V(next_state), returns from the raw advantage,
     unguarded normalisation, then EPOCHS x (one permutation of the L rows, cut into chunks of BATCH_SIZE, one optimiser step per
     chunk).  perms (parity tests): index tensors [L], one per epoch, consumed in order instead of torch.randperm(L).  Returns the
-    loss sums (policy, value, entropy, NaN count) and chunk length of every optimiser step."""
+    loss sums (policy, value, entropy, NaN count) and chunk length of every optimiser step.
+    diag_out (a list; train_ppo passes one when config.PPO_DIAGNOSTICS or config.TARGET_KL is set): the loss kernel's update
+    diagnostics are summed per epoch (uav_set_ppo_diag, attached for the epochs only), config.TARGET_KL drops the remaining
+    epochs once an epoch's approximate KL exceeds it (uavppo.trainer.kl_stop: one host read per epoch), and the dict of
+    uavppo.trainer.diagnostics_from_sums is appended to the list."""
     states, actions, rewards, values, log_probs, dones = buffer.get()
     core = model.core
     dev = core.device
@@ -52,20 +57,39 @@ def _update_inline(buffer, next_value, model, optimizer, perms=None):
     x, act, lp = d(states), d(actions.to(torch.int32)), d(log_probs)
     loss_sums = torch.zeros(4, dtype=torch.float64, device=dev)
     steps = []
-    for _ in range(EPOCHS):                                                                    # :92-94
-        perm = torch.as_tensor(perms.pop(0)) if perms is not None else torch.randperm(L)
-        if perm.numel() != L:
-            raise ValueError(f"_update_inline: a permutation of {perm.numel()} rows for a buffer of {L}")
-        for rows in perm.to(dev, torch.int32).split(BATCH_SIZE):
-            grad = ops.mlp_ppo_grad_rows(core.flat, x, act, lp, adv_n.reshape(-1), ret.reshape(-1), val.reshape(-1),
-                                         rows.contiguous(), 1.0 / rows.numel(), CLIP_EPSILON, ENTROPY_BETA, loss_sums, core.grad)
-            if isinstance(optimizer, ClipAdam):                                                # :133-136
-                optimizer.step_flat(core.flat, grad)
-            else:                                                                              # a torch optimiser on model.parameters()
-                model.publish_grads()
-                torch.nn.utils.clip_grad_norm_(model.parameters(), 0.5)
-                optimizer.step()
-            steps.append((loss_sums.clone(), rows.numel()))
+    diag = diag_ep = target = None
+    if diag_out is not None:
+        from uavppo.trainer import check_target_kl, diagnostics_from_sums, kl_stop
+        target = check_target_kl(TARGET_KL)
+        diag = torch.zeros(ops.PPO_DIAG_N, dtype=torch.float64, device=dev)
+        diag_ep = torch.zeros(EPOCHS, ops.PPO_DIAG_N, dtype=torch.float64, device=dev)
+        ops.set_ppo_diag(diag)
+    epochs_run = 0
+    try:
+        for e in range(EPOCHS):                                                                # :92-94
+            perm = torch.as_tensor(perms.pop(0)) if perms is not None else torch.randperm(L)
+            if perm.numel() != L:
+                raise ValueError(f"_update_inline: a permutation of {perm.numel()} rows for a buffer of {L}")
+            for rows in perm.to(dev, torch.int32).split(BATCH_SIZE):
+                grad = ops.mlp_ppo_grad_rows(core.flat, x, act, lp, adv_n.reshape(-1), ret.reshape(-1), val.reshape(-1),
+                                             rows.contiguous(), 1.0 / rows.numel(), CLIP_EPSILON, ENTROPY_BETA, loss_sums, core.grad)
+                if diag is not None:
+                    diag_ep[e] += diag
+                if isinstance(optimizer, ClipAdam):                                            # :133-136
+                    optimizer.step_flat(core.flat, grad)
+                else:                                                                          # a torch optimiser on model.parameters()
+                    model.publish_grads()
+                    torch.nn.utils.clip_grad_norm_(model.parameters(), 0.5)
+                    optimizer.step()
+                steps.append((loss_sums.clone(), rows.numel()))
+            epochs_run = e + 1
+            if target is not None and kl_stop(diag_ep[e].cpu().numpy(), target):
+                break
+    finally:
+        if diag is not None:
+            ops.set_ppo_diag(None)
+    if diag_out is not None:
+        diag_out.append(diagnostics_from_sums(diag_ep.cpu().numpy(), epochs_run=epochs_run))
     if any(s[3].item() > 0 for s, _ in steps):
         raise RuntimeError("NaN in probs")
     return steps
@@ -81,6 +105,11 @@ def train_ppo(episodes=2000, model_path="ppo_successful_models.pth", env=None, m
     buffer = PPOBuffer()
     trainer = PPOTrainer(env, model, optimizer)
     gen = torch.Generator(device=model.core.device).manual_seed(SEED)
+    # config.PPO_DIAGNOSTICS (or TARGET_KL): update_diagnostics.csv beside the saved models, one row per update
+    diag_log, diag_out, diag_text = None, None, ""
+    if PPO_DIAGNOSTICS or TARGET_KL is not None:
+        from uavppo.update_log import UpdateDiagnosticsLog, path_beside, progress_text
+        diag_log, diag_out = UpdateDiagnosticsLog(path_beside(model_path)), []
     success_count, episode_rewards, success_history, successful_models, t = 0, [], [], [], 0
     for episode in range(episodes):
         env.current_radius = trainer.current_radius                      # train_ppo1.0.py:45
@@ -105,9 +134,14 @@ def train_ppo(episodes=2000, model_path="ppo_successful_models.pth", env=None, m
             if len(buffer.states) >= BATCH_SIZE:                         # :63-141
                 with torch.no_grad():
                     next_value = model(torch.from_numpy(np.asarray(next_state, np.float32))[None])[1]
-                _update_inline(buffer, next_value.reshape(-1), model, optimizer)
+                _update_inline(buffer, next_value.reshape(-1), model, optimizer, diag_out=diag_out)
                 buffer.clear()
+                if diag_log is not None:
+                    diag_log.add(len(diag_log.rows) + 1, diag_out[-1])
+                    diag_text = " | " + progress_text(diag_out.pop())
             if max_steps_total is not None and t >= max_steps_total and not done:
+                if diag_log is not None:
+                    diag_log.close()
                 return model, successful_models, trainer
         success = bool(env.trajectory[-1]["reached"])                   # :144-152
         trainer.update(success)
@@ -120,7 +154,9 @@ def train_ppo(episodes=2000, model_path="ppo_successful_models.pth", env=None, m
         episode_rewards.append(total_reward)
         if episode % 10 == 0:                                            # :165-168
             print(f"Episode {episode} | Mean Reward: {np.mean(episode_rewards[-10:]):.2f} | "
-                  f"Success Rate: {np.mean(success_history):.2%}")
+                  f"Success Rate: {np.mean(success_history):.2%}" + diag_text)
+    if diag_log is not None:
+        diag_log.close()
     torch.save(successful_models, model_path)                            # :173
     print(f"training finished: {len(successful_models)} successful models saved to {model_path}")
     return model, successful_models, trainer

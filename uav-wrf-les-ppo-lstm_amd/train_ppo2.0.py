@@ -13,7 +13,7 @@ import torch
 
 from config import (BATCH_SIZE, BPTT_LEN, CLIP_EPSILON, DIST_BACKEND, ENTROPY_BETA, ENV_VARIANT, EPISODES, EPOCHS, FIELD_BANK, GAE_MODE, GAMMA,
                     GRID_SIZE, HIDDEN, HORIZON, ITERATIONS, LAMBDA, LEARNING_RATE, LOCAL_RANK, MAX_STEPS, NUM_ENVS, NUM_LAYERS,
-                    NUM_MINIBATCHES, POLICY, RANK, SEED, SHUFFLE_ENVS, TREND_K, WORLD_SIZE)  # noqa: F401
+                    NUM_MINIBATCHES, POLICY, PPO_DIAGNOSTICS, RANK, SEED, SHUFFLE_ENVS, TARGET_KL, TREND_K, WORLD_SIZE)  # noqa: F401
 from environment import MethaneEnv
 from model import PPOActorCritic, PPOBuffer, PPOTrainer
 from uavppo import ops
@@ -179,7 +179,13 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
     tr = VecPPOTrainer(NUM_ENVS, HORIZON, POLICY, hidden=HIDDEN, layers=NUM_LAYERS, variant=ENV_VARIANT, seed=SEED, device=dev,
                        gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, bptt_len=BPTT_LEN, log_info=True, gamma=GAMMA, lam=LAMBDA,
                        clip=CLIP_EPSILON, ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, rank=rank, world_size=world,
-                       bank=bank, bank_sources=bank_src, trend_k=TREND_K)
+                       bank=bank, bank_sources=bank_src, trend_k=TREND_K, diagnostics=PPO_DIAGNOSTICS, target_kl=TARGET_KL)
+    # config.PPO_DIAGNOSTICS (or TARGET_KL): update_diagnostics.csv beside the episode CSV, one row per iteration (rank 0; the values
+    # are over all ranks' samples).  Reading them waits for the update: one host wait per iteration that a run without them does not have.
+    diag_log = None
+    if PPO_DIAGNOSTICS or TARGET_KL is not None:
+        from uavppo.update_log import UpdateDiagnosticsLog, path_beside, progress_text
+        diag_log = UpdateDiagnosticsLog(path_beside(csv_path) if rank == 0 else None)
     rows_per_iter = []                  # this rank's rows, iteration by iteration (merged in rank order at the end)
     traj = None
     # The CSV rows are reduced on the device (uav_episode_rows: f64 running sums per env row, one 12-double row per ended episode)
@@ -261,16 +267,22 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
             slots.append(tr.last_mirror_slot)
             del slots[:-3]
         it += 1
+        diag = tr.diagnostics() if diag_log is not None else None
+        if diag is not None:
+            diag_log.add(it, diag)
         if log_every and it % log_every == 0:
             pl, vl, ent = tr.losses()              # (also where NaN probabilities raise, on every rank together)
             if rank == 0:
-                print(f"It {it} | episodes {tr.episodes_lagged} | radius {tr.radius_lagged:.1f} | policy {pl:.4f} value {vl:.4f} entropy {ent:.4f}")
+                print(f"It {it} | episodes {tr.episodes_lagged} | radius {tr.radius_lagged:.1f} | policy {pl:.4f} value {vl:.4f} entropy {ent:.4f}"
+                      + (f" | {progress_text(diag)}" if diag is not None else ""))
     if pending is not None:
         log_rollout(pending)
     tr.losses()
     tr.sync_curriculum()             # (raises if a rank ever ended more episodes in one rollout than its success message holds)
     if traj is not None:
         traj.writer.close()
+    if diag_log is not None:
+        diag_log.close()
     if world > 1:                        # rank order == global env order (contiguous shards)
         gathered = [None] * world
         dist.all_gather_object(gathered, rows_per_iter)

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from config import (BPTT_LEN, CLIP_EPSILON, ENTROPY_BETA, ENV_VARIANT, EPOCHS, GAE_MODE, GAMMA, HIDDEN, HORIZON, LAMBDA, LEARNING_RATE, NUM_ENVS,
-                    NUM_LAYERS, NUM_MINIBATCHES, POLICY, SEED, SHUFFLE_ENVS)
+                    NUM_LAYERS, NUM_MINIBATCHES, POLICY, PPO_DIAGNOSTICS, SEED, SHUFFLE_ENVS, TARGET_KL)
 from model import Discriminator, compute_discriminator_loss, get_expert_data  # noqa: F401  (train_ppo_gail.py:24-27)
 from uavppo.gail import GAILTrainer
 
@@ -30,10 +30,19 @@ def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert
     tr = GAILTrainer(num_envs, horizon, policy, hidden=hidden, layers=NUM_LAYERS, variant=ENV_VARIANT, seed=seed, device=device,
                      gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, bptt_len=BPTT_LEN, gamma=GAMMA, lam=LAMBDA, clip=CLIP_EPSILON,
                      ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, expert=(states, actions), gail_coef=gail_coef,
-                     env_coef=env_coef, disc_lr=disc_lr, disc_steps=disc_steps, update_form=update_form, minibatch_rows=minibatch_rows)
+                     env_coef=env_coef, disc_lr=disc_lr, disc_steps=disc_steps, update_form=update_form, minibatch_rows=minibatch_rows,
+                     diagnostics=PPO_DIAGNOSTICS, target_kl=TARGET_KL)
+    # config.PPO_DIAGNOSTICS (or TARGET_KL): update_diagnostics.csv beside the saved policy, one row per iteration (one host wait each)
+    diag_log = diag = None
+    if PPO_DIAGNOSTICS or TARGET_KL is not None:
+        from uavppo.update_log import UpdateDiagnosticsLog, path_beside, progress_text
+        diag_log = UpdateDiagnosticsLog(path_beside(model_path or "ppo_gail_model.pth"))
     it, mean_rewards = 0, []
     while tr.episodes_lagged < num_episodes and (max_iterations is None or it < max_iterations):
         tr.train_iteration()
+        if diag_log is not None:
+            diag = tr.diagnostics()
+            diag_log.add(it + 1, diag)
         if it % 10 == 0:
             ended = tr.buf["done"].sum().clamp(min=1.0)
             mean_rewards.append(float(tr.buf["rew"].sum() / ended))          # reward collected per episode ended in this rollout
@@ -41,8 +50,11 @@ def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert
             el, pl, acc = tr.disc_losses()
             rate = tr.successes_done / max(tr.episodes_done, 1)
             print(f"Episode {it} | Mean Reward: {mean_rewards[-1]:.2f} | Success Rate: {rate:.2%}")
-            print(f"  episodes {tr.episodes_done} | radius {tr.radius:.1f} | D expert {el:.4f} policy {pl:.4f} accuracy {acc:.3f}")
+            print(f"  episodes {tr.episodes_done} | radius {tr.radius:.1f} | D expert {el:.4f} policy {pl:.4f} accuracy {acc:.3f}"
+                  + (f" | {progress_text(diag)}" if diag is not None else ""))
         it += 1
+    if diag_log is not None:
+        diag_log.close()
     tr.losses()
     tr.disc_losses()
     for path, sd in ((model_path, tr.policy.state_dict()), (disc_path, tr.disc.state_dict())):

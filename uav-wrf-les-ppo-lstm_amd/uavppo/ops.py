@@ -306,6 +306,20 @@ def ppo_loss_from_y(y, w_head, b_head, act, logp_old, adv, ret, val_old, inv_n, 
     return loss_sums, dheads
 
 
+PPO_DIAG_N = 8             # UAV_PPO_DIAG_N
+# the eight sums, include/uavppo.h UAV_PPO_DIAG_*
+PPO_DIAG_NAMES = ("kl_k1", "kl_k3", "clipped", "value_clipped", "verr2", "ret", "ret2", "count")
+
+
+def set_ppo_diag(diag, device=None):
+    """Attach a device f64 [PPO_DIAG_N] buffer to the device's handle (uav_set_ppo_diag): until set_ppo_diag(None) detaches it,
+    every loss-bearing call on that device -- ppo_loss, ppo_loss_heads, ppo_loss_from_y, mlp_ppo_grad, mlp_ppo_grad_trend,
+    mlp_ppo_grad_rows -- overwrites it with the call's eight diagnostic sums.  The handle keeps the POINTER: detach before the
+    tensor is freed."""
+    handle = Context.get(device).handle if diag is None else _h(diag)      # `device` says whose handle to detach from
+    check(lib().uav_set_ppo_diag(handle, _p(diag, F64, (PPO_DIAG_N,), "diag")), "uav_set_ppo_diag")
+
+
 # ----------------------------------------------------------------------------- U3
 ARITH = {"fp16x3": 0, "bf16x6": 1, "f32_mfma": 2}
 

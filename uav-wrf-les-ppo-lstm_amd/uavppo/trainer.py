@@ -53,6 +53,61 @@ def chunk_plan(num_envs, horizon, num_minibatches, bptt_len, policy="lstm", mini
     return C, N * C // M
 
 
+def check_target_kl(target_kl):
+    """target_kl as a float, or None (no early stop); anything but a positive finite number is refused."""
+    if target_kl is None:
+        return None
+    if isinstance(target_kl, bool) or not isinstance(target_kl, (int, float, np.integer, np.floating)):
+        raise ValueError(f"target_kl={target_kl!r}: a positive finite number, or None")
+    v = float(target_kl)
+    if not (v > 0.0 and v < float("inf")):
+        raise ValueError(f"target_kl={target_kl!r}: a positive finite number, or None")
+    return v
+
+
+def kl_stop(sums8, target_kl):
+    """The early-stop rule after an epoch, from that epoch's eight (all-reduced) diagnostic sums (ops.PPO_DIAG_NAMES): stop when
+    the epoch's mean k3 estimate  sums[1] / sums[7]  is greater than target_kl.  A plain comparison -- no 1.5 x factor as some
+    other trainers apply, and a NaN estimate (NaN probabilities, which losses() reports) never stops."""
+    return target_kl is not None and bool(float(sums8[1]) / float(sums8[7]) > target_kl)
+
+
+def diagnostics_from_sums(sums, epochs_run=None, target_kl=None):
+    """[epochs][8] per-epoch diagnostic sums (ops.PPO_DIAG_NAMES; an epoch's row = the sum over its optimiser steps, over all
+    ranks) -> the dict VecPPOTrainer.diagnostics() returns: per-epoch lists over the epochs that ran of
+      approx_kl            S1 / n   the k3 estimator, mean of expm1(lr) - lr   (what target_kl is compared with)
+      approx_kl_k1         S0 / n   mean of logp_old - logp
+      clip_fraction        S2 / n   samples whose ratio left [1 - clip, 1 + clip]
+      value_clip_fraction  S3 / n   samples whose value moved more than clip from the rollout's
+      explained_variance   1 - S4 / (S6 - S5^2 / n) = 1 - sum (R - V)^2 / sum (R - mean R)^2; NaN when the returns are constant
+    and epochs_run, stopped_early.  epochs_run = None: the epochs are walked in order and the walk ends behind the first one that
+    kl_stop() stops at -- the decision update() takes -- or at the first row without samples."""
+    s = np.asarray(sums, dtype=np.float64).reshape(-1, 8)
+    if epochs_run is None:
+        epochs_run = 0
+        for row in s:
+            if not row[7] > 0:
+                break
+            epochs_run += 1
+            if kl_stop(row, target_kl):
+                break
+    epochs_run = int(epochs_run)
+    out = {k: [] for k in ("approx_kl", "approx_kl_k1", "clip_fraction", "value_clip_fraction", "explained_variance")}
+    for S in s[:epochs_run]:
+        n = S[7]
+        out["approx_kl"].append(float(S[1] / n))
+        out["approx_kl_k1"].append(float(S[0] / n))
+        out["clip_fraction"].append(float(S[2] / n))
+        out["value_clip_fraction"].append(float(S[3] / n))
+        var_n = S[6] - S[5] * S[5] / n                       # n * variance of the returns
+        # constant returns: S6 and S5^2 / n then agree up to the rounding of the f64 sums (about 1e-16 sqrt(n) relative), so a
+        # difference below 1e-12 of the second moment is rounding, not variance
+        out["explained_variance"].append(float(1.0 - S[4] / var_n) if var_n > 1e-12 * S[6] else float("nan"))
+    out["epochs_run"] = epochs_run
+    out["stopped_early"] = epochs_run < s.shape[0]
+    return out
+
+
 _SIDE_STREAMS = {}
 
 
@@ -99,9 +154,16 @@ class VecPPOTrainer:
     def __init__(self, num_envs, horizon, policy="lstm", hidden=128, layers=1, variant="v2.0", device="cuda",
                  seed=1234, gae_mode="reference_exact", num_minibatches=1, bank=None, bank_sources=None,
                  rank=0, world_size=1, use_curriculum=True, trend_k=0, log_info=False, device_curriculum=None,
-                 update_form="update_model", minibatch_rows=None, shuffle_envs=False, bptt_len=None, **hp):
+                 update_form="update_model", minibatch_rows=None, shuffle_envs=False, bptt_len=None, diagnostics=False,
+                 target_kl=None, **hp):
         self.hp = dict(DEFAULTS)
         self.hp.update(hp)
+        # diagnostics: every optimiser step's loss kernel also leaves eight sums (include/uavppo.h, uav_set_ppo_diag) that
+        # update() adds up per epoch -- diagnostics() turns them into approx. KL, clip fractions and explained variance.
+        # target_kl: after each epoch those sums are all-reduced and read (the update's one host wait per epoch) and the
+        # remaining epochs are dropped once kl_stop() says so.  Both off: update() issues exactly the launches it did without them.
+        self.target_kl = check_target_kl(target_kl)
+        self._diag_on = bool(diagnostics) or self.target_kl is not None
         self.N, self.T = int(num_envs), int(horizon)
         self.rank, self.world = int(rank), int(world_size)
         self._coll = self.world > 1 or collectives_on()          # the three exchanges of an iteration are issued
@@ -179,6 +241,11 @@ class VecPPOTrainer:
         self.exp_avg_sq = torch.zeros(P, **f32)
         self.opt_step = 0
         self.iteration = 0
+        # diagnostics: the buffer the loss kernels overwrite per call | its per-epoch sums of the last update() | the row in use
+        self._diag_sums = torch.zeros(ops.PPO_DIAG_N, dtype=torch.float64, device=d) if self._diag_on else None
+        self._diag_epochs = torch.zeros(int(self.hp["epochs"]), ops.PPO_DIAG_N, dtype=torch.float64, device=d) if self._diag_on else None
+        self._diag_row = None
+        self._diag_epochs_run = 0
         # the reference's MLP (256-128, 5 actions; 6 inputs, or 7 / 8 with the trend channels) has fused persistent kernels
         # (csrc/mlp_fused.hip); other sizes and fused_mlp=False take the layer-by-layer path (uav_mlp_fwd / uav_ppo_loss /
         # uav_mlp_bwd + step-wise rollout)
@@ -807,6 +874,8 @@ class VecPPOTrainer:
 
     def _optimiser_step(self, grad):
         hp = self.hp
+        if self._diag_row is not None:   # diagnostics: this step's eight sums (its loss kernel just wrote them) into the epoch's row
+            self._diag_row.add_(self._diag_sums)
         allreduce_grad(grad)              # RCCL sum over ranks; inv_n already holds 1/global count
         if self.record_grads:            # (gradient, parameters it was taken at)
             self.grad_log.append((grad.clone(), self.policy.flat.clone()))
@@ -872,7 +941,7 @@ class VecPPOTrainer:
     def update(self):
         """GAE + EPOCHS x num_minibatches optimiser steps (_update_model, train_ppo2.0.py:15-88) -- with shuffle_envs over a
         fresh permutation of the envs per epoch -- or with minibatch_rows EPOCHS x ceil(N T / minibatch_rows) steps over
-        shuffled rows."""
+        shuffled rows.  With diagnostics / target_kl the epochs run under _epochs_with_diagnostics, which may end them early."""
         if self.check_ranges() != "fp16x3":
             self._rollout_forward_valid = False
         self.compute_advantages()
@@ -884,22 +953,63 @@ class VecPPOTrainer:
         if self._C > 1:
             self._chunk_start_states()
         grad_of = self._grad_lstm if self.kind == "lstm" else self._grad_fused_mlp if self.fused_mlp else self._grad_layered_mlp
-        for _ in range(hp["epochs"]):
+
+        def epoch():
             if self.minibatch_rows is not None:
-                self._epoch_rows()
-                continue
+                return self._epoch_rows()
             if self.shuffle_envs:
-                self._epoch_envs(grad_of, inv_n)
-                continue
+                return self._epoch_envs(grad_of, inv_n)
             for m in range(self.num_minibatches):
                 sl = slice(m * nb, (m + 1) * nb)
                 grad = grad_of(sl, (u["act"][sl].reshape(-1), u["logp"][sl].reshape(-1), u["adv_n"][sl].reshape(-1),
                                     u["ret"][sl].reshape(-1), u["val"][sl].reshape(-1), inv_n, hp["clip"], hp["ent_beta"],
                                     self.loss_sums, self.dheads, self.dhead_bias))
                 self._optimiser_step(grad)
+
+        if not self._diag_on:
+            for _ in range(hp["epochs"]):
+                epoch()
+        else:
+            self._epochs_with_diagnostics(epoch, int(hp["epochs"]))
         if self._guarded():
             self._push_param_range()
         return self.loss_sums
+
+    def _epochs_with_diagnostics(self, epoch, epochs):
+        """update()'s epochs with the diagnostics buffer attached to the device's handle -- for their duration only: whatever else
+        uses the handle (the discriminator steps, a caller's own loss calls) never sees it.  Row e of _diag_epochs collects
+        epoch e's sums.  With target_kl the row is all-reduced and read after the epoch and kl_stop() decides whether the next
+        one runs: the decision is a function of the all-reduced row alone, which every rank holds identically, so the ranks
+        leave the loop together (a rank that stopped alone would leave the others waiting in the next gradient all-reduce).
+        Without target_kl the whole array is all-reduced once, behind the last epoch, and nothing is read."""
+        if self._diag_epochs.shape[0] != epochs:
+            self._diag_epochs = torch.zeros(epochs, ops.PPO_DIAG_N, dtype=torch.float64, device=self.device)
+        self._diag_epochs.zero_()
+        self._diag_epochs_run = 0
+        ops.set_ppo_diag(self._diag_sums, self.device)
+        try:
+            for e in range(epochs):
+                self._diag_row = self._diag_epochs[e]
+                epoch()
+                self._diag_epochs_run = e + 1
+                if self.target_kl is not None:
+                    if self._coll:
+                        allreduce_sum(self._diag_row)
+                    if kl_stop(self._diag_row.cpu().numpy(), self.target_kl):
+                        break
+        finally:
+            self._diag_row = None
+            ops.set_ppo_diag(None, self.device)
+        if self.target_kl is None and self._coll:
+            allreduce_sum(self._diag_epochs)
+
+    def diagnostics(self):
+        """The last update()'s per-epoch diagnostics (diagnostics_from_sums: approx_kl, approx_kl_k1, clip_fraction,
+        value_clip_fraction, explained_variance as lists over the epochs that ran; epochs_run; stopped_early), over all ranks'
+        samples.  One host read; no collective (update() issued it)."""
+        if not self._diag_on:
+            raise RuntimeError("diagnostics(): build the trainer with diagnostics=True (or a target_kl)")
+        return diagnostics_from_sums(self._diag_epochs.cpu().numpy(), epochs_run=self._diag_epochs_run)
 
     def time_rollouts(self, event_pairs):
         """Measurement hook (bench.py): the next len(event_pairs) calls of train_iteration() record a (start, end) pair of

@@ -231,7 +231,7 @@ def test_early_stop_is_the_update_of_fewer_epochs(cut):
     dn = never.diagnostics()
     assert dn["epochs_run"] == 5 and dn["stopped_early"] is False and dn["approx_kl"] == kl
     # the parameter-range push at the end of update() happened in the stopped run too
-    assert len(b._pmax_queue) == len(plain._pmax_queue) == 1
+    assert len(b.guard.ring) == len(plain.guard.ring) == 1
 
 
 # ---------------------------------------------------------------------------------------------- 6: two ranks

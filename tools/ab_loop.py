@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A/B of the iteration loop on one device, interleaved rounds (cdna_hip_programming.md rule 24):
-  guard   range guard off / on (uavppo/trainer.py: Adam publishes max |param|, polled at the next rollout)
+  guard   range guard off / on (uavppo/range_guard.py: Adam publishes max |param|, polled at the next rollout)
   side    curriculum success bits packed + copied on the main stream at the iteration's host sync / on a side stream right
           behind the rollout (the sync then never drains the main stream)
 usage: ab_loop.py [guard|side]"""
@@ -21,17 +21,14 @@ WHAT = sys.argv[1] if len(sys.argv) > 1 else "side"
 def run(mode, k=10):
     if WHAT == "side":
         tr.side_stream_curriculum = (mode == "new")
-    elif mode == "old":
-        tr._guarded = lambda: False
+    else:
+        tr.guard.enabled = (mode == "new")
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(k):
         tr.train_iteration()
     torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / k * 1e3
-    if WHAT == "guard" and mode == "old":
-        del tr._guarded
-    return dt
+    return (time.perf_counter() - t0) / k * 1e3
 
 
 for m in ("old", "new"):

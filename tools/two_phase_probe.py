@@ -45,10 +45,10 @@ def rank_main(variant):
         tr = VecPPOTrainer(n_env, 128, "lstm", hidden=128, device=dev, seed=1234, rank=rank, world_size=world,
                            use_curriculum=(variant != "nocurr"))
         if tag[0] == "B" and variant == "samestream":
-            tr._side = keep["side"]
+            tr.link.side = keep["side"]
         if tag[0] == "B" and variant == "mainstream":
             tr.side_stream_curriculum = False
-        keep["side"] = tr._side
+        keep["side"] = tr.link.side
         for _ in range(warm):
             tr.train_iteration()
         if timers:

@@ -71,7 +71,7 @@ class DeviceEpisodeLog:
 
     def __init__(self, trainer, slots=2):
         import torch
-        from .trainer import _side_stream
+        from .curriculum_link import _side_stream
         if trainer.info is None:
             raise ValueError("DeviceEpisodeLog needs a trainer built with log_info=True")
         self.tr = trainer
@@ -149,14 +149,14 @@ class DeviceEpisodeLog:
 
 class RolloutMirror:
     """The per-iteration host copies the reference-shaped training log needs (info [N,T,10], flags, rew: 21 + 0.5 + 2 MB at
-    C3) without stalling the GPU: issued on the process's ONE side stream (uavppo/trainer.py: _side_stream) right behind the
+    C3) without stalling the GPU: issued on the process's ONE side stream (uavppo/curriculum_link.py: _side_stream) right behind the
     rollout into a ring of pinned host slots, so they cross PCIe while the update's kernels run; the host reads slot k
     after waiting for ITS event only, and the next rollout is fenced behind the copy (which finished milliseconds
     earlier).  Replaces three blocking `.cpu().numpy()` calls per iteration."""
 
     def __init__(self, trainer, slots=2):
         import torch
-        from .trainer import _side_stream
+        from .curriculum_link import _side_stream
         self.tr = trainer
         self.side = _side_stream(trainer.device)
         self.names = [("info", trainer.info), ("flags", trainer.buf["flags"]), ("rew", trainer.buf["rew"])]

@@ -29,7 +29,7 @@ def policy_core(policy):
 
 def _out_of_range(kind, core):
     """max |param| (NaN not counted) against the trainer's fp16-split limit: (value, limit, out of range)."""
-    from .trainer import MLP_RANGE_LIMITS, RANGE_LIMITS
+    from .range_guard import MLP_RANGE_LIMITS, RANGE_LIMITS
     limit = RANGE_LIMITS[0] if kind == "lstm" else MLP_RANGE_LIMITS[0]
     a = core.flat.detach().abs()
     pmax = float(torch.where(torch.isnan(a), torch.zeros_like(a), a).max())
@@ -110,7 +110,7 @@ def stepwise_policy_probs(kind, core, env):
     """policy_probs for the step-wise loop: the LSTM's (h, c) start at zero and are carried through LSTMActorCritic.step.
     nan[0] counts steps whose logits hold a NaN among envs whose episode has not ended (env.done of the previous step).
     Parameters beyond the fp16-split range on a handle in that mode: the policy's own calls run in bf16x6, as the trainer
-    switches (VecPPOTrainer._decide); the handle's mode is restored after each call, so the stop predictors keep theirs."""
+    switches (RangeGuard._decide, uavppo/range_guard.py); the handle's mode is restored after each call, so the stop predictors keep theirs."""
     N, A = env.num_envs, core.n_act
     wide = ops.get_lstm_arith(env.device) == "fp16x3" and _out_of_range(kind, core)[2]
     nan = torch.zeros(1, dtype=torch.int64, device=env.device)

@@ -13,20 +13,13 @@ import numpy as np
 import torch
 
 from . import ops
-from .dist_utils import (SUCC_CAP, abi_collectives, allreduce_adv_stats, allreduce_grad, allreduce_sum, collectives_on, env_shard, exchange_successes, pack_local_successes,
-                         unpack_episode_successes)
-from .curriculum import Curriculum
+from .curriculum_link import CurriculumLink
+from .dist_utils import allreduce_adv_stats, allreduce_grad, allreduce_sum, collectives_on, env_shard
 from .policy import LSTMActorCritic, MLPActorCritic
+from .range_guard import RangeGuard
 
 # reference hyper-parameters, PPOV2.0/config.py:12-18 and train_ppo2.0.py:87,114
 DEFAULTS = dict(gamma=0.99, lam=0.95, clip=0.2, ent_beta=0.01, lr=3e-5, epochs=5, max_grad_norm=0.5)
-# operand ranges of the default (fp16-split) LSTM kernels, include/uavppo.h: |w| < 65504, |x| < 4096, |h0| < 64.  The
-# trainer switches to the bf16-split kernels at HALF of each limit; parameters move by at most lr per optimiser step, so a
-# weight maximum read one iteration late still has that margin.
-RANGE_LIMITS = (0.5 * 65504.0, 0.5 * 4096.0, 0.5 * 64.0)
-# the fused MLP kernels run their 256 x 128 products on the same fp16 split: its operand a1 = relu(LayerNorm) is bounded by
-# sqrt(255) |g1| + |be1|, so max |param| < 2048 keeps it inside fp16's range (include/uavppo.h, uav_mlp_ppo_grad); half of it:
-MLP_RANGE_LIMITS = (0.5 * 2048.0, float("inf"), float("inf"))
 
 
 def chunk_plan(num_envs, horizon, num_minibatches, bptt_len, policy="lstm", minibatch_rows=None):
@@ -51,6 +44,52 @@ def chunk_plan(num_envs, horizon, num_minibatches, bptt_len, policy="lstm", mini
         raise ValueError(f"num_envs * horizon / bptt_len = {N * C} chunk rows are not divisible by num_minibatches={M} "
                          "(minibatches are whole chunk rows)")
     return C, N * C // M
+
+
+def check_options(num_envs, horizon, policy, trend_k, update_form, gae_mode, num_minibatches, minibatch_rows, shuffle_envs, bptt_len):
+    """VecPPOTrainer's keywords that cut or shuffle the buffer, refused where they contradict each other.  Returns
+    (gae_mode, minibatch_rows, C): the GAE mode in force, the row count as an int or None, the chunk rows per env (chunk_plan;
+    1 = full BPTT).  Pure host arithmetic, like chunk_plan: VecPPOTrainer calls it before it allocates anything."""
+    N, M = int(num_envs), int(num_minibatches)
+    # update_form "inline_v10": the inline update of PPOV1.1/train_ppo1.0.py:63-141 (also the policy side of
+    # train_ppo_gail.py:71-148) instead of _update_model's arithmetic -- GAE with a real bootstrap V(next_state) on the last
+    # step, returns from the raw advantage, (A - mean) / (std + 1e-8) without a guard.  It sets the GAE mode itself (a gae_mode other than the default beside it is refused).
+    if update_form not in ("update_model", "inline_v10"):
+        raise ValueError(f"update_form {update_form!r}: 'update_model' or 'inline_v10'")
+    if update_form == "inline_v10" and gae_mode not in ("reference_exact", "inline_v10"):
+        raise ValueError(f"update_form='inline_v10' runs its own GAE (uav_gae mode inline_v10); gae_mode={gae_mode!r} would be ignored")
+    # minibatch_rows = B: every epoch one permutation of this rank's N * T sample rows, cut into chunks of B (the last one
+    # shorter, as Tensor.split), each chunk one optimiser step (train_ppo1.0.py:92-136) through uav_mlp_ppo_grad_rows
+    rows = None if minibatch_rows is None else int(minibatch_rows)
+    if rows is not None:
+        if M != 1:
+            raise ValueError("num_minibatches and minibatch_rows are two ways to cut the buffer: give one of them")
+        if rows < 1:
+            raise ValueError(f"minibatch_rows={minibatch_rows}: a positive row count")
+        if policy != "mlp" or not 6 <= 6 + int(trend_k) <= 8:
+            raise ValueError("minibatch_rows needs the MLP policy on the fused path (6-256-128 with trend_k 0..2): only "
+                             "uav_mlp_ppo_grad_rows reads its samples through a row index; an LSTM's samples are whole "
+                             "env sequences (shuffle_envs=True shuffles those)")
+    # shuffle_envs: every epoch one permutation of this rank's N envs, cut into num_minibatches chunks of N / M whole env
+    # sequences; a chunk is packed into contiguous buffers by ONE launch (uav_gather_rows_multi) and the update's kernels run
+    # on the packed minibatch unchanged
+    if shuffle_envs:
+        if rows is not None:
+            raise ValueError("shuffle_envs and minibatch_rows are two ways to shuffle the buffer (whole env sequences / single "
+                             "sample rows): give one of them")
+        if M == 1:
+            raise ValueError("shuffle_envs with num_minibatches=1: one minibatch of all envs leaves nothing to shuffle")
+    # bptt_len = Lc (truncated BPTT, LSTM only): the update runs on the N * C sequences of Lc consecutive steps the buffer
+    # holds (C = T / Lc), each started from the recurrent state the rollout's parameters give at its first step
+    # (_chunk_start_states, once per iteration) -- gradients do not cross a chunk boundary.  The sample arrays are
+    # contiguous, so the chunk view [N * C][Lc] is a reshape; the sequence kernels run on it unchanged.  None, or Lc = T
+    # (one chunk per env), is full BPTT: the path without the keyword.
+    C = 1 if bptt_len is None else chunk_plan(N, horizon, M, bptt_len, policy, rows)[0]
+    if C == 1 and N % M:
+        raise ValueError("num_envs must be divisible by num_minibatches (minibatches are whole env sequences)")
+    if policy not in ("lstm", "mlp"):
+        raise ValueError(policy)
+    return "inline_v10" if update_form == "inline_v10" else gae_mode, rows, C
 
 
 def check_target_kl(target_kl):
@@ -108,46 +147,11 @@ def diagnostics_from_sums(sums, epochs_run=None, target_kl=None):
     return out
 
 
-_SIDE_STREAMS = {}
-
-
-def _side_stream(device):
-    """ONE side stream per device and process, shared by every trainer built in it.  A trainer used to draw its own
-    stream from torch's pool; a SECOND trainer in a process (bench.py's old weak -> strong sequence) then ran its success
-    exchange on a second pool stream, and with two rank processes sharing one GPU over gloo every iteration of that second
-    trainer stalled for 50-900 ms in update() (tools/two_phase_probe.py: `base` 58-245 ms per C3 iteration against 9.6 ms
-    in fresh processes; `samestream` -- the second trainer reusing the first one's stream -- 10.7 ms; `nocurr` and
-    `mainstream`, which never touch a side stream, 9.0 / 9.8 ms; dropping the first trainer, gc, empty_cache, kernel
-    timers and the torch thread count made no difference).  Streams are a per-process resource: keep exactly one."""
-    device = torch.device(device)
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
-    return _SIDE_STREAMS[key]
-
-
-# VecPPOTrainer._succ_stage, where the buffers' success flags are: not packed | packed (side stream) | gathered and handed on | counted
-_IDLE, _PACKED, _EXCHANGED, _COUNTED = range(4)
-
-
-class _DeviceCurriculumView:
-    """What callers read off `trainer.curriculum` when the curriculum lives on the device (each access waits for the device)."""
-
-    def __init__(self, tr):
-        self._tr = tr
-
-    @property
-    def current_radius(self):
-        return self._tr.radius
-
-    @property
-    def explore_bonus(self):
-        return self._tr.bonus
-
-    @property
-    def success_history(self):
-        self._tr.sync_curriculum()
-        return [None] * self._tr._hist_len          # the window's LENGTH is what callers look at; its bits stay on the device
+def _delegate(owner, name, setter=False):
+    """A trainer attribute that lives on one of its collaborators (self.<owner>.<name>)."""
+    def fset(self, v):
+        setattr(getattr(self, owner), name, v)
+    return property(lambda self: getattr(getattr(self, owner), name), fset if setter else None)
 
 
 class VecPPOTrainer:
@@ -163,63 +167,55 @@ class VecPPOTrainer:
         # target_kl: after each epoch those sums are all-reduced and read (the update's one host wait per epoch) and the
         # remaining epochs are dropped once kl_stop() says so.  Both off: update() issues exactly the launches it did without them.
         self.target_kl = check_target_kl(target_kl)
+        self.gae_mode, self.minibatch_rows, self._C = check_options(num_envs, horizon, policy, trend_k, update_form, gae_mode,
+                                                                    num_minibatches, minibatch_rows, shuffle_envs, bptt_len)
         self._diag_on = bool(diagnostics) or self.target_kl is not None
         self.N, self.T = int(num_envs), int(horizon)
         self.rank, self.world = int(rank), int(world_size)
         self._coll = self.world > 1 or collectives_on()          # the three exchanges of an iteration are issued
         self.device = torch.device(device)
         self.variant, self.seed = variant, int(seed)
-        # update_form "inline_v10": the inline update of PPOV1.1/train_ppo1.0.py:63-141 (also the policy side of
-        # train_ppo_gail.py:71-148) instead of _update_model's arithmetic -- GAE with a real bootstrap V(next_state) on the last
-        # step, returns from the raw advantage, (A - mean) / (std + 1e-8) without a guard.  It sets the GAE mode itself (a gae_mode other than the default beside it is refused).
-        if update_form not in ("update_model", "inline_v10"):
-            raise ValueError(f"update_form {update_form!r}: 'update_model' or 'inline_v10'")
-        if update_form == "inline_v10" and gae_mode not in ("reference_exact", "inline_v10"):
-            raise ValueError(f"update_form='inline_v10' runs its own GAE (uav_gae mode inline_v10); gae_mode={gae_mode!r} would be ignored")
-        self.update_form = update_form
-        self.gae_mode = "inline_v10" if update_form == "inline_v10" else gae_mode
-        self.num_minibatches = int(num_minibatches)
-        # minibatch_rows = B: every epoch one permutation of this rank's N * T sample rows, cut into chunks of B (the last one
-        # shorter, as Tensor.split), each chunk one optimiser step (train_ppo1.0.py:92-136) through uav_mlp_ppo_grad_rows
-        self.minibatch_rows = None if minibatch_rows is None else int(minibatch_rows)
-        if self.minibatch_rows is not None:
-            if self.num_minibatches != 1:
-                raise ValueError("num_minibatches and minibatch_rows are two ways to cut the buffer: give one of them")
-            if self.minibatch_rows < 1:
-                raise ValueError(f"minibatch_rows={minibatch_rows}: a positive row count")
-            if policy != "mlp" or not 6 <= 6 + int(trend_k) <= 8:
-                raise ValueError("minibatch_rows needs the MLP policy on the fused path (6-256-128 with trend_k 0..2): only "
-                                 "uav_mlp_ppo_grad_rows reads its samples through a row index; an LSTM's samples are whole "
-                                 "env sequences (shuffle_envs=True shuffles those)")
-        # shuffle_envs: every epoch one permutation of this rank's N envs, cut into num_minibatches chunks of N / M whole env
-        # sequences; a chunk is packed into contiguous buffers by ONE launch (uav_gather_rows_multi) and the update's kernels run
-        # on the packed minibatch unchanged
-        self.shuffle_envs = bool(shuffle_envs)
-        if self.shuffle_envs:
-            if self.minibatch_rows is not None:
-                raise ValueError("shuffle_envs and minibatch_rows are two ways to shuffle the buffer (whole env sequences / single "
-                                 "sample rows): give one of them")
-            if self.num_minibatches == 1:
-                raise ValueError("shuffle_envs with num_minibatches=1: one minibatch of all envs leaves nothing to shuffle")
-        # bptt_len = Lc (truncated BPTT, LSTM only): the update runs on the N * C sequences of Lc consecutive steps the buffer
-        # holds (C = T / Lc), each started from the recurrent state the rollout's parameters give at its first step
-        # (_chunk_start_states, once per iteration) -- gradients do not cross a chunk boundary.  The sample arrays are
-        # contiguous, so the chunk view [N * C][Lc] is a reshape; the sequence kernels run on it unchanged.  None, or Lc = T
-        # (one chunk per env), is full BPTT: the path without the keyword.
+        self.update_form, self.num_minibatches, self.shuffle_envs = update_form, int(num_minibatches), bool(shuffle_envs)
         self.bptt_len = None if bptt_len is None else int(bptt_len)
-        self._C = 1 if bptt_len is None else chunk_plan(self.N, self.T, self.num_minibatches, bptt_len, policy, self.minibatch_rows)[0]
-        if self._C == 1 and self.N % self.num_minibatches:
-            raise ValueError("num_envs must be divisible by num_minibatches (minibatches are whole env sequences)")
-        self.kind = policy
-        self.trend_k = int(trend_k)
+        self.kind, self.trend_k = policy, int(trend_k)
         self.obs_dim = D = 6 + self.trend_k      # 6 reference features + trend channels (BASELINE C5)
+        self._S, self._Ls = self.N * self._C, self.T // self._C       # the update's sequences: S rows of Ls steps (N, T without bptt_len)
+        self._nb = self._S // self.num_minibatches                    # ... per minibatch
+        self._last_n = self._nb * self._Ls                            # local samples of the last optimiser step (losses())
+        self._env_lo = env_shard(self.rank, self.N)[0]                # environments of this rank: global indices [rank*N, (rank+1)*N)
+        # the reference's MLP (256-128, 5 actions; 6 inputs, or 7 / 8 with the trend channels) has fused persistent kernels
+        # (csrc/mlp_fused.hip); other sizes and fused_mlp=False take the layer-by-layer path (uav_mlp_fwd / uav_ppo_loss /
+        # uav_mlp_bwd + step-wise rollout)
+        self._fused_mlp = policy == "mlp" and 6 <= D <= 8
+        self.reuse_rollout_forward = True    # epoch 0 adopts the rollout kernel's stash (same parameters)
+        self.use_stepper = True              # h = 256 step-wise rollouts through uav_lstm_stepper_* (A/B switch)
+        self.use_fused_tail = True           # ... and heads + sample + env step + store of a step as ONE launch (A/B switch)
+        self._rollout_forward_valid = False
+        self.record = False          # tests: keep (loss_sums, grad norm) of every optimiser step
+        self.record_grads = False    # tests: ... and the (all-reduced, unclipped) flat gradient of every optimiser step + its parameters
+        self.log = []
+        self.grad_log = []
+        self.forced_perms = None     # tests: list of index tensors [N * T] (shuffle_envs: [N], with bptt_len [N * C]), consumed in order instead of the drawn permutations
+        self.perm_log = []           # tests (record, shuffle_envs): the env permutation of every epoch
+        self._perm_gen = None        # device generator of the row / env permutations, seeded by (seed, rank) on first use
+        self._iter_events = []       # (start, end) event pairs of time_rollouts() still to be recorded
+        self._st = None              # scratch of one step of the step-wise rollouts: _step_scratch()
+        self.opt_step = 0
+        self.iteration = 0
         if policy == "lstm":
             self.policy = LSTMActorCritic(D, hidden, layers, 5, self.device, seed=self.seed)
-        elif policy == "mlp":
-            self.policy = MLPActorCritic(D, 5, device=self.device, seed=self.seed)
         else:
-            raise ValueError(policy)
-        N, T, d = self.N, self.T, self.device
+            self.policy = MLPActorCritic(D, 5, device=self.device, seed=self.seed)
+        # the allocation steps, in the order the tensors have always been allocated in
+        self._alloc_samples(log_info)
+        self._alloc_collaborators(bank, bank_sources, use_curriculum, device_curriculum)
+        self._alloc_policy_work(hidden, layers)
+        self._alloc_update_views(hidden, layers)
+        self.reset()
+
+    def _alloc_samples(self, log_info):
+        """The [N][T] sample buffers a rollout fills, what GAE makes of them, and the optimiser's state."""
+        N, T, D, d = self.N, self.T, self.obs_dim, self.device
         f32 = dict(dtype=torch.float32, device=d)
         self.buf = {"obs": torch.zeros(N, T, D, **f32), "act": torch.zeros(N, T, dtype=torch.int32, device=d),
                     "rew": torch.zeros(N, T, **f32), "val": torch.zeros(N, T, **f32), "logp": torch.zeros(N, T, **f32),
@@ -239,90 +235,27 @@ class VecPPOTrainer:
         P = self.policy.num_params()
         self.exp_avg = torch.zeros(P, **f32)
         self.exp_avg_sq = torch.zeros(P, **f32)
-        self.opt_step = 0
-        self.iteration = 0
         # diagnostics: the buffer the loss kernels overwrite per call | its per-epoch sums of the last update() | the row in use
         self._diag_sums = torch.zeros(ops.PPO_DIAG_N, dtype=torch.float64, device=d) if self._diag_on else None
         self._diag_epochs = torch.zeros(int(self.hp["epochs"]), ops.PPO_DIAG_N, dtype=torch.float64, device=d) if self._diag_on else None
         self._diag_row = None
         self._diag_epochs_run = 0
-        # the reference's MLP (256-128, 5 actions; 6 inputs, or 7 / 8 with the trend channels) has fused persistent kernels
-        # (csrc/mlp_fused.hip); other sizes and fused_mlp=False take the layer-by-layer path (uav_mlp_fwd / uav_ppo_loss /
-        # uav_mlp_bwd + step-wise rollout)
-        self.fused_mlp = policy == "mlp" and 6 <= D <= 8
-        self.reuse_rollout_forward = True    # epoch 0 adopts the rollout kernel's stash (same parameters)
-        self.use_stepper = True              # h = 256 step-wise rollouts through uav_lstm_stepper_* (A/B switch)
-        self.use_fused_tail = True           # ... and heads + sample + env step + store of a step as ONE launch (A/B switch)
-        self._rollout_forward_valid = False
-        self.record = False          # tests: keep (loss_sums, grad norm) of every optimiser step
-        self.record_grads = False    # tests: ... and the (all-reduced, unclipped) flat gradient of every optimiser step + its parameters
-        self.log = []
-        self.grad_log = []
-        self.forced_perms = None     # tests: list of index tensors [N * T] (shuffle_envs: [N], with bptt_len [N * C]), consumed in order instead of the drawn permutations
-        self.perm_log = []           # tests (record, shuffle_envs): the env permutation of every epoch
-        self._perm_gen = None        # device generator of the row / env permutations, seeded by (seed, rank) on first use
-        self._S, self._Ls = self.N * self._C, self.T // self._C       # the update's sequences: S rows of Ls steps (N, T without bptt_len)
-        self._nb = self._S // self.num_minibatches                    # ... per minibatch
-        self._last_n = self._nb * self._Ls                            # local samples of the last optimiser step (losses())
-        # range guard of the fp16-split kernels: device maxima [|param|, |obs|, |h0|], mirrored to pinned host memory
-        self.ranges = torch.zeros(3, **f32)
-        self._ranges_host = torch.zeros(4, 3, dtype=torch.float32).pin_memory()      # ring: the host may run iterations ahead
-        self._ranges_evs = [torch.cuda.Event() for _ in range(4)]
-        self._pmax_queue = []        # ring slots whose copy of the Adam kernel's max |param| is on its way, oldest first
-        self._pmax_next = 0
-        self._buffers_own = False    # True between a collect() and the update() that consumes its buffers
-        self.arith = "fp16x3"
-        self.range_events = 0        # iterations that ran on the wide-range (bf16-split) kernels
-        # force_arith: "fp16x3" | "bf16x6" | "f32_mfma" pins the LSTM kernels' arithmetic (A/B runs, reference gradients);
-        # None = the range guard decides.  A handle that uav_create started in another mode (UAV_LSTM_F32_MFMA=1 /
-        # UAV_LSTM_BF16X6=1 in the environment: a whole-process A/B) keeps it.
-        init_mode = ops.Context.get(self.device).initial_arith
-        self.force_arith = None if init_mode == "fp16x3" else init_mode
-        self._flat_version = -1
-        # environments of this rank: global indices [rank*N, (rank+1)*N)
+
+    def _alloc_collaborators(self, bank, bank_sources, use_curriculum, device_curriculum):
+        """The range guard, this rank's environments, and the curriculum link."""
+        N, d = self.N, self.device
+        self.guard = RangeGuard(self.policy, self.kind, d, enabled=self.kind == "lstm" or self._fused_mlp)
         self.env_state = torch.zeros(ops.env_state_bytes(N), dtype=torch.uint8, device=d)
-        self.cur_obs = torch.zeros(N, D, **f32)
+        self.cur_obs = torch.zeros(N, self.obs_dim, dtype=torch.float32, device=d)
         self.bank = None if bank is None else torch.as_tensor(bank, dtype=torch.float64).to(d).contiguous()
         self.bank_sources = None if bank_sources is None else torch.as_tensor(bank_sources, dtype=torch.float64).to(d).contiguous()
-        # T1.  device_curriculum (the default with a curriculum): the 120-episode window, radius and bonus live in a device block
-        # (uav_curriculum_*), updated by a one-thread kernel on the side stream from the gathered success messages and read by
-        # the env kernels at launch -- the loop has no host synchronisation left.  False: the host-side Curriculum class (the
-        # reference's arithmetic in Python; what the N = 1 PPOTrainer of model.py uses), one wait per iteration.
-        self.device_curriculum = bool(use_curriculum) if device_curriculum is None else bool(device_curriculum and use_curriculum)
-        self._radius, self._bonus = 50.0, 0.6
-        self._episodes_done = self._successes_done = 0   # finished episodes of the whole job (all ranks)
-        self._hist_len = 0
-        self.last_success_bits = None
-        self._curr_queue = []        # ring slots of the device curriculum's lagged host mirrors on their way, oldest first
-        if self.device_curriculum:
-            self._curr = ops.curriculum_state(self.device, self._radius, self._bonus)
-            self._curr_host = torch.zeros(4, self._curr.numel(), dtype=torch.uint8).pin_memory()     # ring of lagged host mirrors
-            self._curr_evs = [torch.cuda.Event() for _ in range(4)]
-            self._curr_next = 0
-            self.last_mirror_slot = 0
-            self._curr_done_ev = torch.cuda.Event()
-            self._curr_pending = False
-            self.curriculum = _DeviceCurriculumView(self)
-        else:
-            self._curr = None
-            self.curriculum = Curriculum() if use_curriculum else None
-        # the curriculum's success bits leave on a side stream right behind the rollout and land in pinned host memory
-        # while the update runs: the iteration's one host sync (update_curriculum) then waits for a copy that finished
-        # milliseconds ago instead of draining the main stream
-        self._side = _side_stream(self.device) if use_curriculum else None
-        self._succ_host = (torch.zeros(self.world, 4 + SUCC_CAP + 1, dtype=torch.uint8).pin_memory() if use_curriculum else None)
-        self._succ_ev = torch.cuda.Event()
-        self._pack_ev = torch.cuda.Event()
-        self._roll_ev = torch.cuda.Event()
-        self._gather_ev = torch.cuda.Event()
-        self._succ_stage = _IDLE               # where the flags of the current buffers are on their way to the curriculum
-        self._succ_msg = None
-        self.side_stream_curriculum = True     # False: pack + copy on the main stream inside update_curriculum (A/B, tools/ab_loop.py)
-        self._iter_events = []                 # (start, end) event pairs of time_rollouts() still to be recorded
-        self._env_lo = env_shard(self.rank, N)[0]
-        nb, S, Ls = self._nb, self._S, self._Ls
-        self._st = None                        # scratch of one step of the step-wise rollouts: _step_scratch()
-        if policy == "lstm":
+        self.link = CurriculumLink(d, self.world, self._coll, use_curriculum, device_curriculum)
+
+    def _alloc_policy_work(self, hidden, layers):
+        """The recurrent state and the work arrays the update's kernels write their forward pass to."""
+        N, nb, Ls = self.N, self._nb, self._Ls
+        f32 = dict(dtype=torch.float32, device=self.device)
+        if self.kind == "lstm":
             L, H = layers, hidden
             # recurrent state (h | c) and its snapshot at the start of the current rollout (what BPTT starts from): each pair is
             # ONE allocation, so the snapshot before a rollout is one copy launch instead of two
@@ -340,12 +273,17 @@ class VecPPOTrainer:
             self.work = {"stash": None}      # layer-by-layer path only (770 floats per sample); allocated on first use
             self._step_scratch()
         self.dheads = torch.empty(nb * Ls, 6, **f32)
-        # what the update reads its sequences from: the sample arrays and the start state themselves, or -- truncated BPTT --
-        # their [N * C][Lc] views and the chunks' start states h0c, c0c [L][N * C][H]
+
+    def _alloc_update_views(self, hidden, layers):
+        """What the update reads its sequences from: the sample arrays and the start state themselves, or -- truncated BPTT --
+        their [N * C][Lc] views and the chunks' start states h0c, c0c [L][N * C][H]; with shuffle_envs, the packed minibatch."""
+        N, T, d, nb, S, Ls = self.N, self.T, self.device, self._nb, self._S, self._Ls
+        f32 = dict(dtype=torch.float32, device=d)
+        lstm = self.kind == "lstm"
         self._u = {"obs": self.buf["obs"], "act": self.buf["act"], "logp": self.buf["logp"], "val": self.buf["val"],
                    "keep": self.buf["keep"], "adv_n": self.adv_n, "ret": self.ret}
         self._rwork = self.work                # the [N][T] arrays a rollout writes its forward pass to (epoch 0 adopts it)
-        if policy == "lstm":
+        if lstm:
             self._u["h0"], self._u["c0"] = self.h0, self.c0
         if self._C > 1:
             self._u = {k: v.view((S, Ls) + tuple(v.shape[2:])) for k, v in self._u.items() if k not in ("h0", "c0")}
@@ -359,287 +297,69 @@ class VecPPOTrainer:
             # the LSTM's start state, allocated once; the plan holds the checked (source, destination) table of the launch
             u, pk = self._u, {}
             src = {k: u[k] for k in ("obs", "act", "logp", "adv_n", "ret", "val")}
-            if policy == "lstm":
+            if lstm:
                 src["keep"] = u["keep"]
             for k, v in src.items():
                 pk[k] = torch.empty((nb,) + tuple(v.shape[1:]), dtype=v.dtype, device=d)
             pairs = [(src[k], pk[k]) for k in src]
-            if policy == "lstm":
+            if lstm:
                 pk["h0"], pk["c0"] = torch.empty(layers, nb, hidden, **f32), torch.empty(layers, nb, hidden, **f32)
                 pairs += [(u["h0"], pk["h0"], 1), (u["c0"], pk["c0"], 1)]
             self._pack, self._pack_plan = pk, ops.GatherPlan(pairs)
-        self.reset()
 
     # ------------------------------------------------------------------------------------------
     def env_cfg(self):
-        return ops.make_env_cfg(self.variant, self._radius, self._bonus, self.seed, self.bank, self.bank_sources,
+        k = self.link
+        return ops.make_env_cfg(self.variant, k.host_radius, k.host_bonus, self.seed, self.bank, self.bank_sources,
                                 env_offset=self._env_lo, n_env_total=self.world * self.N,
-                                trend_k=self.trend_k, curriculum=self._curr)
+                                trend_k=self.trend_k, curriculum=k.block)
 
-    # ------------------------------------------------------------------------------------------ T1: successes -> curriculum
-    # radius / bonus / episode counters.  Host curriculum: plain attributes.  Device curriculum: the truth is on the device; the
-    # getters below WAIT for it (tests, logging at the end of a run); the training loop itself never calls them -- it reads the
-    # lagged mirror (`radius_lagged`, `episodes_lagged`: the state as of the rollout before last, copied to pinned memory on
-    # the side stream).
-    def _read_curriculum(self, block, adopt=True):
-        """A HOST copy of the device curriculum block -> its scalars, taken as this trainer's own unless adopt=False.  An overflowed
-        message raises wherever the block is read: through the mirror one or two rollouts late, never at the end of a long run only."""
-        d = ops.curriculum_read(block.numpy())
-        if d["overflow"]:
-            raise RuntimeError(f"device curriculum: a rank ended more than {SUCC_CAP} episodes in one rollout (message capacity)")
-        if adopt:
-            self._radius = d["radius"]
-            self._bonus = np.float64(d["bonus"]) if d["bonus_is_f64"] else d["bonus"]
-            self._episodes_done, self._successes_done, self._hist_len = d["episodes"], d["successes"], d["hist_len"]
-        return d
-
-    def _read_mirror_slot(self, k):
-        self._curr_evs[k].synchronize()        # waits for that 64-byte copy only
-        return self._read_curriculum(self._curr_host[k], adopt=False)
-
-    def sync_curriculum(self):
-        """Device curriculum: wait for the device state and take it as the host scalars."""
-        if not self.device_curriculum:
-            return
-        if self._succ_stage == _PACKED and not self._coll:
-            self._exchange_successes()         # (with several ranks the exchange is a collective: only update() / collect() issue it)
-        if self._curr_pending:
-            self._curr_done_ev.synchronize()
-        self._read_curriculum(self._curr.cpu())
-
-    def _poll_curriculum_mirror(self):
-        """Newest landed mirror of the device state (never waits; the host curriculum queues none)."""
-        latest = None
-        while self._curr_queue and self._curr_evs[self._curr_queue[0]].query():
-            latest = self._curr_queue.pop(0)
-        if latest is not None:
-            self._read_curriculum(self._curr_host[latest])
+    # ------------------------------------------------------------------------------------------ the two collaborators' surface
+    # T1, successes -> curriculum: self.link (uavppo/curriculum_link.py).  The getters of radius / bonus / episodes_done /
+    # successes_done WAIT for a device curriculum; the training loop reads the lagged ones.
+    curriculum = _delegate("link", "curriculum")
+    device_curriculum = _delegate("link", "device_curriculum")
+    last_mirror_slot = _delegate("link", "last_mirror_slot")
+    last_success_bits = _delegate("link", "last_success_bits")
+    side_stream_curriculum = _delegate("link", "use_side_stream", setter=True)
+    radius = _delegate("link", "radius", setter=True)
+    bonus = _delegate("link", "bonus", setter=True)
+    radius_lagged = _delegate("link", "radius_lagged")
+    episodes_lagged = _delegate("link", "episodes_lagged")
+    episodes_done = _delegate("link", "episodes_done")
+    successes_done = _delegate("link", "successes_done")
 
     def rollout_radius(self, k=None):
-        """The radius the LAST collected rollout ran with (device curriculum: from its lagged mirror, slot k = the value of
-        `last_mirror_slot` taken right after that rollout's update_curriculum(); waits only for that 64-byte copy)."""
-        return self._read_mirror_slot(self.last_mirror_slot if k is None else k)["radius"] if self.device_curriculum else self._rollout_radius
+        return self.link.rollout_radius(k)
 
     def episodes_before_rollout(self, k):
-        """Episodes the whole job had finished BEFORE the rollout whose mirror went to slot k (its `last_mirror_slot`): waits for
-        that 64-byte copy only.  The mirror is taken on the device between two curriculum updates, from state every rank holds
-        identically -- so this value, unlike the polled `episodes_lagged`, is the same on every rank at the same program point:
-        what a multi-rank loop must base its stop decision on (a rank that stops alone leaves the others in the next all-reduce)."""
-        return self._read_mirror_slot(k)["episodes"] if self.device_curriculum else self._episodes_done
+        return self.link.episodes_before_rollout(k)
 
-    @property
-    def radius(self):
-        self.sync_curriculum()
-        return self._radius
-
-    def _before_host_write(self):
-        """A host-side write into the device block must land behind the side stream's pending update of it."""
-        if self._curr_pending:
-            torch.cuda.current_stream().wait_event(self._curr_done_ev)
-
-    @radius.setter
-    def radius(self, v):
-        self._radius = float(v)
-        if self.device_curriculum:
-            self._before_host_write()
-            self._curr[:32].view(torch.float64)[0] = self._radius
-
-    @property
-    def bonus(self):
-        self.sync_curriculum()
-        return self._bonus
-
-    @bonus.setter
-    def bonus(self, v):
-        self._bonus = v
-        if self.device_curriculum:
-            self._before_host_write()
-            self._curr[:32].view(torch.float64)[1] = float(v)
-            self._curr[:32].view(torch.float64)[2] = 1.0 if isinstance(v, np.float64) else 0.0
-
-    @property
-    def radius_lagged(self):
-        self._poll_curriculum_mirror()
-        return self._radius
-
-    @property
-    def episodes_lagged(self):
-        self._poll_curriculum_mirror()
-        return self._episodes_done
-
-    @property
-    def episodes_done(self):
-        self.sync_curriculum()
-        return self._episodes_done
-
-    @property
-    def successes_done(self):
-        self.sync_curriculum()
-        return self._successes_done
-
-    # A rollout's flags (_succ_stage): packed right behind the rollout on the side stream; exchanged from collect() with one rank,
-    # with collectives on from update() behind the advantage-statistics all-reduce (or from update_curriculum() if still
-    # outstanding); counted by update_curriculum().  _IDLE: side_stream_curriculum = False, or buffers a caller filled by hand.
-    def _successes_before_rollout(self):
-        if self._succ_stage in (_PACKED, _EXCHANGED):    # a previous rollout's flags may still be read by the pack kernel on the side stream
-            torch.cuda.current_stream().wait_event(self._pack_ev)
-        if self.device_curriculum:
-            if self._succ_stage == _PACKED:        # collect() twice without an update(): finish the first one's exchange
-                self._exchange_successes()
-            if self._curr_pending:             # the env kernels read radius / bonus from the device state: a GPU-side wait, no host sync
-                torch.cuda.current_stream().wait_event(self._curr_done_ev)
-        self._succ_stage = _IDLE
-
-    def _pack_successes(self):
-        self._roll_ev.record()
-        with torch.cuda.stream(self._side):
-            self._side.wait_event(self._roll_ev)
-            self._succ_msg = pack_local_successes(self.buf["flags"])
-            self._pack_ev.record(self._side)       # the flags have been read: the next rollout may overwrite them
-        self._succ_stage = _PACKED
-
-    def _gather_successes(self, msg):
-        msgs = exchange_successes(msg)
-        if tuple(msgs.shape) != tuple(self._succ_host.shape):       # e.g. world_size > 1 without a process group
-            raise RuntimeError(f"success exchange returned {tuple(msgs.shape)}, expected {tuple(self._succ_host.shape)}: "
-                               "is torch.distributed initialised for world_size > 1?")
-        return msgs
-
-    def _exchange_successes(self):
-        """All-gather of the packed success bits + copy to pinned host memory, on the side stream.  With several ranks it is
-        issued from update(), BEHIND the advantage-statistics all-reduce in program order: RCCL runs a rank's collectives
-        in the order they were issued, and that all-reduce must not queue behind the pack kernel."""
-        on_main = abi_collectives() and self._coll
-        if on_main:
-            # ABI carrier: ONE communicator on raw streams.  RCCL runs a rank's collectives in the order its device reaches them, so
-            # the all-gather must not sit on another stream than the all-reduces (two ranks could then reach the two collectives in
-            # opposite orders and wait for each other): it goes on the MAIN stream, behind the pack kernel, and the side stream
-            # picks the gathered messages up again.  (torch.distributed serialises a group's collectives on its own stream.)
-            main = torch.cuda.current_stream()
-            main.wait_event(self._pack_ev)
-            msgs = self._gather_successes(self._succ_msg)
-            self._gather_ev.record(main)
-        with torch.cuda.stream(self._side):
-            if on_main:
-                self._side.wait_event(self._gather_ev)
-            else:
-                msgs = self._gather_successes(self._succ_msg)
-            if self.device_curriculum:
-                # lagged host mirror of the state as it was for THIS rollout, then the update itself: one thread walks the
-                # messages rank by rank, episode by episode (model.py:131-164)
-                k = self._curr_next
-                self._curr_next = (k + 1) % len(self._curr_evs)
-                if k in self._curr_queue:                       # the host is a whole ring ahead: drop the oldest mirror
-                    self._curr_queue.remove(k)
-                self._curr_host[k].copy_(self._curr, non_blocking=True)
-                self._curr_evs[k].record(self._side)
-                self._curr_queue.append(k)
-                self.last_mirror_slot = k
-                ops.curriculum_update(self._curr, msgs, SUCC_CAP)
-                self._curr_done_ev.record(self._side)
-                self._curr_pending = True
-            else:
-                self._succ_host.copy_(msgs, non_blocking=True)
-                self._succ_ev.record(self._side)
-        self._succ_stage = _EXCHANGED
+    def sync_curriculum(self):
+        return self.link.sync()
 
     def update_curriculum(self):
-        """Feed this iteration's finished episodes to the curriculum (host scalars).  The success bits are
-        compacted on the device; only they cross to the host / the other ranks, so every rank feeds the same
-        global (env, time)-ordered sequence to its replicated curriculum.  A rollout's episodes are counted once: a second
-        call before the next collect() does nothing."""
-        if self.curriculum is None or self._succ_stage == _COUNTED:
-            return
-        if self._succ_stage == _IDLE and self.device_curriculum:        # flags not produced by collect(): pack them now
-            self._pack_successes()
-        if self._succ_stage == _IDLE:          # host curriculum: pack and exchange them now, on the main stream
-            self._succ_host.copy_(self._gather_successes(pack_local_successes(self.buf["flags"])), non_blocking=True)
-            self._succ_ev.record()
-        elif self._succ_stage == _PACKED:      # collect() without an update() in between
-            self._exchange_successes()
-        self._succ_stage = _COUNTED
-        if self.device_curriculum:             # no host wait: the messages were (or are now) queued, the device does the rest
-            self._poll_curriculum_mirror()
-            return
-        self._succ_ev.synchronize()
-        bits = unpack_episode_successes(self._succ_host.numpy(), self.buf["flags"])
-        self._episodes_done += int(bits.size)            # over ALL ranks, in global (env, time) order
-        self._successes_done += int(bits.sum())
-        self.last_success_bits = bits
-        self.curriculum.update_many(bits)
-        self._radius, self._bonus = self.curriculum.current_radius, self.curriculum.explore_bonus
+        return self.link.count(self.buf["flags"])
 
-    # ------------------------------------------------------------------------------------------ range guard
-    # The fp16-split kernels need |w| < 65504, |x| < 4096, |h0| < 64 (include/uavppo.h).  What can leave that range, and
-    # where it is caught without stalling the loop:
-    #   parameters   move by <= lr per optimiser step.  The Adam kernel publishes max |param| after every step
-    #                (uav_clip_adam's pmax_out); its copy to pinned host memory is polled, never waited for, at the start of
-    #                a later rollout (the host runs one to two iterations ahead of the device), against HALF the limit.  Parameters written by
-    #                anything else (initialisation, load_state_dict: torch bumps flat._version) are measured before the
-    #                next rollout runs on them -- a sync, on such an iteration only.
-    #   observations / recurrent state of the trainer's OWN rollouts are bounded by construction (positions, field values
-    #                and counters scaled to O(1); |h| < 1), so they are not measured in the loop.  Buffers filled by a
-    #                caller (update() without a preceding collect()) ARE measured, synchronously, before the update.
-    def _guarded(self):
-        """Every LSTM policy: the h = 64 / 128 sequence kernels AND the h = 256 step kernels are fp16-split by default.
-        (At h = 256 the wide-range modes run the generic exact-f32 step path -- slow, but never silently out of range.)
-        The fused MLP kernels likewise (their wide-range mode is the exact-f32 MFMA form of the same kernels)."""
-        return self.kind == "lstm" or self.fused_mlp
-
-    def _decide(self, maxima):
-        ok = all(v == v and v < lim for v, lim in zip(maxima, RANGE_LIMITS if self.kind == "lstm" else MLP_RANGE_LIMITS))
-        self.arith = "fp16x3" if ok else "bf16x6"
-        self.range_events += (not ok)
-        if self.force_arith is not None:
-            self.arith = self.force_arith
-        return ok
-
-    def _measure_params(self):
-        """Synchronous probe of the parameters when something other than the Adam kernel wrote them."""
-        if self.policy.flat._version != self._flat_version:
-            self._pmax_queue.clear()            # maxima published before the foreign write say nothing about it
-            ops.absmax(self.policy.flat, out=self.ranges[0:1])
-            self._flat_version = self.policy.flat._version
-            self._decide([float(self.ranges[0].item()), 0.0, 0.0])
+    # range guard: self.guard (uavppo/range_guard.py)
+    arith = _delegate("guard", "arith")
+    range_events = _delegate("guard", "range_events")
+    force_arith = _delegate("guard", "force_arith", setter=True)
 
     def poll_param_range(self):
-        """Read the newest of the Adam kernel's max |param| copies that has landed (never waits)."""
-        latest = None
-        while self._pmax_queue and self._ranges_evs[self._pmax_queue[0]].query():
-            latest = self._pmax_queue.pop(0)
-        if latest is not None and self._guarded():
-            self._decide([float(self._ranges_host[latest, 0]), 0.0, 0.0])
-
-    def _push_param_range(self):
-        """max |param| of the last Adam step -> pinned host memory, read at a later poll."""
-        if len(self._pmax_queue) == 4:     # the host is four updates ahead of the device: let the oldest copy land
-            self._ranges_evs[self._pmax_queue[0]].synchronize()
-            self.poll_param_range()
-        k = self._pmax_next
-        self._pmax_next = (k + 1) % 4
-        self._ranges_host[k].copy_(self.ranges, non_blocking=True)
-        self._ranges_evs[k].record()
-        self._pmax_queue.append(k)
-        self._buffers_own = False
+        return self.guard.poll()
 
     def check_ranges(self):
-        """Kernel arithmetic for the update about to be queued (see above); sets it on the device's handle."""
-        if not self._guarded():
-            return self.arith
-        if self.force_arith is not None:
-            self.arith = self.force_arith
-        if not self._buffers_own:               # foreign buffers: measure everything now
-            self._pmax_queue.clear()
-            ops.absmax(self.policy.flat, out=self.ranges[0:1])
-            if self.kind == "lstm":
-                ops.absmax(self.buf["obs"], out=self.ranges[1:2])
-                ops.absmax(self.h0, out=self.ranges[2:3])
-            self._flat_version = self.policy.flat._version
-            self._decide(self.ranges.tolist())
-        else:
-            self._measure_params()
-        ops.set_lstm_arith(self.arith, self.device)
-        return self.arith
+        return self.guard.before_update(self.buf["obs"], self.h0 if self.kind == "lstm" else None)
+
+    @property
+    def fused_mlp(self):
+        return self._fused_mlp
+
+    @fused_mlp.setter
+    def fused_mlp(self, on):             # (A/B, tests: False sends a fused-size MLP down the layer-by-layer path, which has no guard)
+        self._fused_mlp = bool(on)
+        self.guard.enabled = self.kind == "lstm" or self._fused_mlp
 
     def reset(self):
         ops.env_reset(self.env_state, self.N, self.env_cfg(), self.cur_obs)
@@ -663,7 +383,7 @@ class VecPPOTrainer:
         persistent launch), or step-wise 'tail' | 'stepper' | 'per_call' (LSTM), 'per_call' (MLP)."""
         if self.kind != "lstm":
             return "fused_mlp" if self.fused_mlp else "per_call"
-        wide = self._guarded() and self.arith != "fp16x3"      # uav_rollout exists in the fp16-split form only
+        wide = self.guard.enabled and self.arith != "fp16x3"     # uav_rollout exists in the fp16-split form only
         if self.policy.num_layers == 1 and self.policy.hidden in (64, 128) and not wide:
             return "fused_lstm"
         return self._stepwise_lstm_route()
@@ -671,15 +391,8 @@ class VecPPOTrainer:
     def collect(self, forced_act=None, noise=None):
         """Fill the (env, T, feat) buffers with one rollout of T steps per env."""
         self._rollout_forward_valid = False
-        self._rollout_radius = self._radius    # (host curriculum: what this rollout runs with)
-        self._successes_before_rollout()
-        if self._guarded():
-            self.poll_param_range()
-            self._measure_params()
-            if self.force_arith is not None:
-                self.arith = self.force_arith
-            ops.set_lstm_arith(self.arith, self.device)
-            self._buffers_own = True
+        self.link.before_rollout()
+        self.guard.before_rollout()
         route = self.rollout_route()
         if self.kind == "lstm":
             self._state0.copy_(self._state)
@@ -699,10 +412,7 @@ class VecPPOTrainer:
             self._collect_stepwise_lstm(forced_act, noise)
         else:
             self._collect_stepwise(forced_act, noise)
-        if self.curriculum is not None and self.side_stream_curriculum:
-            self._pack_successes()
-            if not self._coll:
-                self._exchange_successes()
+        self.link.after_rollout(self.buf["flags"])
 
     def _step_scratch(self):
         """Scratch of ONE step of the step-wise rollouts (every route but the two fused kernels), built once -- an LSTM's on its
@@ -881,7 +591,7 @@ class VecPPOTrainer:
             self.grad_log.append((grad.clone(), self.policy.flat.clone()))
         self.opt_step += 1
         ops.clip_adam(self.policy.flat, grad, self.exp_avg, self.exp_avg_sq, self.opt_step, hp["lr"],
-                      max_norm=hp["max_grad_norm"], gnorm_out=self.gnorm, pmax_out=self.ranges[0:1])
+                      max_norm=hp["max_grad_norm"], gnorm_out=self.gnorm, pmax_out=self.guard.ranges[0:1])
         if self.record:
             self.log.append((self.loss_sums.clone(), self.gnorm.clone()))
 
@@ -945,8 +655,7 @@ class VecPPOTrainer:
         if self.check_ranges() != "fp16x3":
             self._rollout_forward_valid = False
         self.compute_advantages()
-        if self._succ_stage == _PACKED:
-            self._exchange_successes()
+        self.link.in_update()             # (the success exchange, behind the advantage-statistics all-reduce)
         u, hp = self._u, self.hp
         nb = self._nb
         inv_n = 1.0 / float(nb * self._Ls * self.world)
@@ -971,8 +680,7 @@ class VecPPOTrainer:
                 epoch()
         else:
             self._epochs_with_diagnostics(epoch, int(hp["epochs"]))
-        if self._guarded():
-            self._push_param_range()
+        self.guard.after_update()
         return self.loss_sums
 
     def _epochs_with_diagnostics(self, epoch, epochs):

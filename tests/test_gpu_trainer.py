@@ -716,7 +716,7 @@ def _redraw_kink_samples(pol, rng, obs, act, lp, vo, ret, clip=0.2, relu_margin=
 
 @pytest.mark.parametrize("n", [1, 7, 16, 100, 256, 5000, 70001])
 def test_fused_mlp_gradient_matches_oracle_and_layered_path(n):
-    """uav_mlp_ppo_grad (forward + loss + backward on chip, csrc/mlp_fused.hip) vs torch-CPU autograd through the oracle's
+    """uav_mlp_ppo_grad (forward + loss + backward on chip, csrc/mlp_update.hip) vs torch-CPU autograd through the oracle's
     restatement of model.py:42-53 + train_ppo2.0.py:55-83, and vs the layer-by-layer HIP path; ragged last tiles included."""
     from uavppo import ops
     from uavppo.policy import MLPActorCritic

@@ -7,7 +7,7 @@
 // base address.  It has nothing to do with DPP or with MFMA hazards: the rotation was applied to element 0 four times
 // (ISA of the cluster kernel with the builtin applied directly: ONE v_mov_b32_dpp per four uses; through a by-value
 // helper -- float t = v[r]; bit_cast(t) -- four).  Rule for this code base: never bit_cast a subscripted ext-vector
-// directly; go through a by-value temporary or a helper taking the scalar (csrc/mlp_fused.hip: row16_sum(float) does).
+// directly; go through a by-value temporary or a helper taking the scalar (csrc/mlp_tile_core.h: row16_sum(float) does).
 //
 //   hipcc -O3 --offload-arch=gfx950 -emit-llvm -S --cuda-device-only tools/bitcast_vector_elt_probe.hip -o - | grep extractelement
 //     direct:  ONE  `extractelement <4 x i32> %v, i64 0`     (wrong)

@@ -44,7 +44,7 @@ __device__ __forceinline__ void split2u(float a, _Float16& p0, _Float16& p1) {  
 }
 __device__ __forceinline__ unsigned short hb(_Float16 v) { return __builtin_bit_cast(unsigned short, v); }
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-__device__ __forceinline__ f16x8 tr_frag(const unsigned short* plane, int rs, int lane) {     // csrc/mlp_fused.hip: tr_frag
+__device__ __forceinline__ f16x8 tr_frag(const unsigned short* plane, int rs, int lane) {     // csrc/mlp_tile_core.h: tr_frag
     typedef short v4s __attribute__((__vector_size__(4 * sizeof(short))));
     typedef __attribute__((address_space(3))) v4s lds_v4s;
     const int li = lane & 15, kq = lane >> 4;

@@ -3,9 +3,14 @@ lane-spill traffic (v_readlane + v_writelane) of every kernel, before and after 
 
     python tools/kernel_static_table.py OLD_CSRC NEW_CSRC rollout mlp_fused greedy_tail env loss > profiles/NAME.md
 
-Each file is compiled to device assembly with the Makefile's flags (FAST_TU files with -ffp-contract=fast).  A kernel is
-"same" when its instruction stream is identical after block labels are renumbered.  A record for a refactor, not a gate.
+Each file is compiled to device assembly with the Makefile's flags (FAST_TU files with -ffp-contract=fast).  The kernels of all
+named files are collected per tree -- a file that a tree does not have is skipped -- and matched by kernel name, so a kernel
+that moved between files is followed (`... OLD_CSRC NEW_CSRC mlp_fused mlp_rollout mlp_update`).  The stream column says
+"same" when the instruction stream is identical after block labels are renumbered, "same opcodes" when the instruction count
+and the multiset of opcodes are equal but the stream is reordered or uses other registers, else "differs".  A record for a
+refactor, not a gate.
 """
+import collections
 import hashlib
 import os
 import re
@@ -19,7 +24,7 @@ FAST_TU = ("lstm", "wgrad")
 
 
 def kernels(csrc, tu):
-    """{demangled kernel name: dict(vgpr, sgpr, scratch, lds, insts, lanes, sha)} of csrc/tu.hip"""
+    """{demangled kernel name: dict(tu, vgpr, sgpr, scratch, lds, insts, lanes, sha, ops)} of csrc/tu.hip"""
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, tu + ".s")
         extra = ["-ffp-contract=fast"] if tu in FAST_TU else []
@@ -40,10 +45,19 @@ def kernels(csrc, tu):
         stat = lambda key, src: int(re.search(r"%s[:, ]+(\d+)" % key, src).group(1))                 # noqa: E731
         nice = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
         nice = re.sub(r"^void |\(.*$", "", nice.replace("(anonymous namespace)::", ""))
-        res[nice] = dict(vgpr=stat(r"; NumVgprs", info), sgpr=stat(r"; TotalNumSgprs", info), scratch=stat(r"; ScratchSize", info),
+        res[nice] = dict(tu=tu + ".hip", ops=collections.Counter(i.split()[0] for i in code), vgpr=stat(r"; NumVgprs", info), sgpr=stat(r"; TotalNumSgprs", info), scratch=stat(r"; ScratchSize", info),
                          lds=stat(r"\.amdhsa_group_segment_fixed_size", block),
                          insts=len(code), lanes=sum(i.startswith(("v_readlane", "v_writelane")) for i in code),
                          sha=hashlib.sha256("\n".join(ins).encode()).hexdigest())
+    return res
+
+
+def tree(csrc, tus):
+    """the kernels of every file of `tus` that the tree has, by kernel name"""
+    res = {}
+    for tu in tus:
+        if os.path.exists(os.path.join(csrc, tu + ".hip")):
+            res.update(kernels(csrc, tu))
     return res
 
 
@@ -52,15 +66,15 @@ def main():
     print("| file | kernel | VGPR | SGPR | scratch B | static LDS B | instructions | v_readlane + v_writelane | stream |")
     print("|---|---|---|---|---|---|---|---|---|")
     cell = lambda a, b: str(a) if a == b else f"{a} -> {b}"                                         # noqa: E731
-    for tu in tus:
-        a, b = kernels(old, tu), kernels(new, tu)
-        for k in sorted(set(a) | set(b)):
-            if k not in a or k not in b:
-                print(f"| {tu}.hip | `{k}` | | | | | | | {'only old' if k in a else 'only new'} |")
-                continue
-            x, y = a[k], b[k]
-            print(f"| {tu}.hip | `{k}` | " + " | ".join(cell(x[f], y[f]) for f in ("vgpr", "sgpr", "scratch", "lds", "insts", "lanes")) +
-                  f" | {'same' if x['sha'] == y['sha'] else 'differs'} |")
+    a, b = tree(old, tus), tree(new, tus)
+    for k in sorted(set(a) | set(b), key=lambda k: ((a.get(k) or b[k])["tu"], k)):
+        if k not in a or k not in b:
+            print(f"| {(a.get(k) or b[k])['tu']} | `{k}` | | | | | | | {'only old' if k in a else 'only new'} |")
+            continue
+        x, y = a[k], b[k]
+        stream = "same" if x["sha"] == y["sha"] else ("same opcodes" if x["ops"] == y["ops"] else "differs")
+        print(f"| {cell(x['tu'], y['tu'])} | `{k}` | " + " | ".join(cell(x[f], y[f]) for f in ("vgpr", "sgpr", "scratch", "lds", "insts", "lanes")) +
+              f" | {stream} |")
 
 
 if __name__ == "__main__":

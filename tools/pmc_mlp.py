@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Small driver for PMC collection with the reference's own MLP policy at BASELINE C3's per-GPU shape (4096 envs x 128 steps, fused
-kernels of csrc/mlp_fused.hip): ONE iteration, 2 epochs (counters are per launch)."""
+kernels of csrc/mlp_rollout.hip and csrc/mlp_update.hip): ONE iteration, 2 epochs (counters are per launch)."""
 import os
 import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

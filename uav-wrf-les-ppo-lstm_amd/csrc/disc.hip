@@ -5,7 +5,7 @@
 // PPOV1.1/train_ppo_gail.py:157-175 (two BCELoss means, backward; the optimiser step is uav_clip_adam's).
 //
 // Shape of the work.  A row is sa = [state | one_hot(action) | 1 | 0...] padded to K = 16, so the bias b1 rides as a column of
-// W1 and the whole first layer of 16 rows is 8 unit tiles x 4 v_mfma_f32_16x16x4_f32 (exact f32, the idiom of mlp_fused.hip's
+// W1 and the whole first layer of 16 rows is 8 unit tiles x 4 v_mfma_f32_16x16x4_f32 (exact f32, the idiom of mlp_tile_core.h's
 // small layers).  One wave owns 16 rows at a time:
 //   forward   pre[row][unit] = sa W1p^T: A = sa (lane (j, kq) holds sa[row j][col 4 ks + kq]), B = W1p (held in 32 registers
 //             for the whole kernel); the result leaves lane (j, kq) with pre[row 4 kq + r][unit 16 ut + j], r < 4, ut < 8.

@@ -1,5 +1,5 @@
 // env_core.h -- device-side arithmetic of ONE plume environment (E2-E5) and the composed step built from it (at the end of
-// this file), shared by every kernel that steps an env: env.hip, both fused rollouts (rollout.hip, mlp_fused.hip) and the
+// this file), shared by every kernel that steps an env: env.hip, both fused rollouts (rollout.hip, mlp_rollout.hip) and the
 // step-wise routes' tails (rollout.hip, greedy_tail.hip).
 //
 // Reference: PPOV2.0/environment.py:41-49 (reset), :51-62 (field), :64-80 (obs), :82-169 (step);

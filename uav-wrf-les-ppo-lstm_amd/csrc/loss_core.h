@@ -1,5 +1,5 @@
 // loss_core.h -- the per-sample arithmetic of the clipped-PPO loss (train_ppo2.0.py:55-83), shared by the elementwise
-// loss kernels (loss.hip) and the fused MLP update (mlp_fused.hip), so every path rounds alike.
+// loss kernels (loss.hip) and the fused MLP update (mlp_update.hip), so every path rounds alike.
 #pragma once
 #include "common.h"
 #include "philox.h"

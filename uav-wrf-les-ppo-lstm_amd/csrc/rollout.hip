@@ -748,7 +748,7 @@ extern "C" int uav_rollout(uav_ctx* ctx, void* env_state, int n_env, const uav_e
     UAV_REQUIRE(n_env > 0 && horizon > 0, "uav_rollout: n_env=%d horizon=%d", n_env, horizon);
     UAV_REQUIRE(policy_kind >= 0 && policy_kind <= 2, "uav_rollout: policy_kind %d (0 = MLP, 1 = LSTM, 2 = MLP with 6 + trend_k inputs)",
                 policy_kind);
-    if (policy_kind != 1) {      // the reference's MLP policy (2: with the trend channels as inputs): csrc/mlp_fused.hip
+    if (policy_kind != 1) {      // the reference's MLP policy (2: with the trend channels as inputs): csrc/mlp_rollout.hip
         UAV_REQUIRE(!stash && !y_out, "uav_rollout: stash / y_out belong to the LSTM policy");
         return launch_rollout_mlp(ctx, env_state, n_env, cfg, params, horizon, iter, cur_obs, obs, act, rew, val, logp, done,
                                   flags, last_val, forced_act, noise, nan_count, info, heads, policy_kind == 2, as_stream(stream));

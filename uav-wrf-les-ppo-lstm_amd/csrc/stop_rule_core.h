@@ -10,7 +10,7 @@
 // np.std over a [window][2] f32 array reduces along the outer axis, i.e. sequentially in time order, all in f32:
 //     mean_k = (sum_i p_ik) / window;  var_k = (sum_i (p_ik - mean_k)^2) / window;  std_k = sqrt(var_k);  (std_0 + std_1) / 2
 // stop_pos_std() below is that chain, operation for operation.  It is bit-exact only without FMA contraction: every
-// translation unit that includes this header is built with -ffp-contract=off (csrc/Makefile; rollout, mlp_fused, env).
+// translation unit that includes this header is built with -ffp-contract=off (csrc/Makefile; rollout, mlp_rollout, env).
 // f32 division and sqrt are the correctly rounded ones (hipcc's default), as numpy's are.
 //
 // Window buffers of the entry points (include/uavppo.h: uav_greedy_episodes_stop, uav_stop_stability):

@@ -56,7 +56,7 @@ def _update_model(buffer, model, optimizer):
     x, act, lp = d(states), d(actions.to(torch.int32)), d(log_probs)
     loss_sums = None
     core = model.core
-    fused = (core.in_dim, core.h1, core.h2, core.n_act) == (6, 256, 128, 5)    # the reference's sizes: csrc/mlp_fused.hip
+    fused = (core.in_dim, core.h1, core.h2, core.n_act) == (6, 256, 128, 5)    # the reference's sizes: csrc/mlp_update.hip
     for _ in range(EPOCHS):                                                    # :43 (one minibatch of the whole buffer)
         if fused:        # forward + loss + backward of :55-86 in one on-chip pass
             loss_sums = torch.zeros(4, dtype=torch.float64, device=dev) if loss_sums is None else loss_sums

@@ -503,7 +503,7 @@ def mlp_bwd(params, x, stash, dheads, in_dim=6, h1=256, h2=128, n_act=5, grad=No
 
 def mlp_ppo_grad(params, obs, act, logp_old, adv, ret, val_old, inv_n, clip, ent_beta, loss_sums, grad, in_dim=6, h1=256,
                  h2=128, n_act=5):
-    """Fused forward + clipped-PPO loss + backward of the reference's MLP policy (csrc/mlp_fused.hip): obs [n, 6] and the
+    """Fused forward + clipped-PPO loss + backward of the reference's MLP policy (csrc/mlp_update.hip): obs [n, 6] and the
     per-sample scalars in, flat gradient (layout of `params`) and loss_sums f64[4] out; nothing else touches HBM."""
     n = obs.shape[0]
     _t = KERNEL_TIMER.bracket("mlp_ppo_grad")
@@ -997,7 +997,7 @@ def rollout_lstm(env_state, n_env, cfg, params, hidden, horizon, it, cur_obs, h,
 
 def rollout_mlp(env_state, n_env, cfg, params, horizon, it, cur_obs, bufs, last_val=None, forced_act=None, noise=None,
                 nan_count=None, info=None, heads=None, trend=False):
-    """Fused persistent rollout of the reference's MLP policy (csrc/mlp_fused.hip): uav_rollout with policy_kind 0.
+    """Fused persistent rollout of the reference's MLP policy (csrc/mlp_rollout.hip): uav_rollout with policy_kind 0.
     trend=True: policy_kind 2, the MLP with D = 6 + cfg.trend_k inputs (cur_obs [N,D], obs [N,T,D], params of
     mlp_param_count(D) floats); with cfg.trend_k = 0 that is kind 0's kernel and bits."""
     N, T, D = n_env, horizon, 6 + (cfg.trend_k if trend else 0)

@@ -184,7 +184,7 @@ class VecPPOTrainer:
         self._last_n = self._nb * self._Ls                            # local samples of the last optimiser step (losses())
         self._env_lo = env_shard(self.rank, self.N)[0]                # environments of this rank: global indices [rank*N, (rank+1)*N)
         # the reference's MLP (256-128, 5 actions; 6 inputs, or 7 / 8 with the trend channels) has fused persistent kernels
-        # (csrc/mlp_fused.hip); other sizes and fused_mlp=False take the layer-by-layer path (uav_mlp_fwd / uav_ppo_loss /
+        # (csrc/mlp_rollout.hip, csrc/mlp_update.hip); other sizes and fused_mlp=False take the layer-by-layer path (uav_mlp_fwd / uav_ppo_loss /
         # uav_mlp_bwd + step-wise rollout)
         self._fused_mlp = policy == "mlp" and 6 <= D <= 8
         self.reuse_rollout_forward = True    # epoch 0 adopts the rollout kernel's stash (same parameters)

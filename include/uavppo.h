@@ -164,6 +164,22 @@ int uav_ppo_loss_from_y(uav_ctx* ctx, const float* y, const float* w_head, const
 #define UAV_PPO_DIAG_COUNT 7
 int uav_set_ppo_diag(uav_ctx* ctx, double* diag);
 
+/* ---- behaviour cloning: the supervised loss on expert actions, forward + backward in one pass, on the packed heads
+ * [n][n_act+1] (logits | value) that the policies' heads() return.  The log-probability is the one uav_ppo_loss forms on the
+ * same logits, bit for bit: softmax, q = p / sum p, q[a] clamped to [eps, 1 - eps], libm's logf.  Per sample with 0 <= a < n_act:
+ *   nll = -log q[a];  d/dlogp = -inv_n where the clamp is open, 0 where it binds;  entropy H = -sum p log(p + 1e-8) and its
+ *   gradient as uav_ppo_loss;  with vtarget (f32 [n]) vl = 0.5 (V - R)^2 and dV = value_coef * inv_n * (V - R), with
+ *   vtarget == NULL vl = 0 and dV = 0;  total = mean nll + value_coef * mean vl - ent_beta * mean H over 1 / inv_n samples.
+ * A sample with a < 0 or a >= n_act is MASKED (a padded step of a ragged episode): its row of dheads is 0 and it enters no sum.
+ * bc_sums (f64 [UAV_BC_SUMS_N], device): {sum nll, sum 0.5 (V - R)^2 (not multiplied by value_coef), sum entropy, count of
+ * samples with a NaN probability, count of argmax(logits) == a (first of equal maxima), count of unmasked samples}, reduced in a
+ * fixed order (block partials, one final pass): they repeat bit for bit.  dheads [n][n_act+1] = d(total)/d(heads); dhead_bias
+ * (f32 [n_act+1], or NULL): its column sums.  n_act = 5 only; n = 0 is refused.  A buffer attached with uav_set_ppo_diag is
+ * neither read nor written.  Added without a change of UAV_ABI_VERSION (a symbol only). */
+#define UAV_BC_SUMS_N 6
+int uav_bc_loss(uav_ctx* ctx, const float* heads, const int32_t* act, const float* vtarget, int64_t n, int n_act, float inv_n,
+                float value_coef, float ent_beta, double* bc_sums, float* dheads, float* dhead_bias, uav_stream stream);
+
 /* ---- K3 (sampling part): softmax + Categorical sample + log_prob + NaN check
  * (train_ppo2.0.py:161-163,189; torch Categorical(probs) semantics).  u: uniforms in [0,1)
  * [n] or NULL to use the counter RNG: row i draws from Philox(seed; counter & 0xffffffff, index_offset + i,
@@ -360,6 +376,19 @@ int uav_mlp_ppo_grad_rows(uav_ctx* ctx, const float* params, const float* obs, c
                           const float* adv, const float* ret, const float* val_old, int64_t n_total, const int32_t* rows,
                           int64_t n_rows, int trend_k, float inv_n, float clip, float ent_beta, double* loss_sums, float* grad,
                           uav_stream stream);
+
+/* The behaviour-cloning gradient (the loss of uav_bc_loss) through the same network in one pass: uav_mlp_ppo_grad_rows' kernel
+ * with the cloning loss on its loss lanes, which read act and, if given, vtarget instead of the five PPO scalars.  obs
+ * [n_total][6 + trend_k], act i32 [n_total], vtarget f32 [n_total] or NULL.  rows == NULL: the contiguous form, n_rows is
+ * ignored and the n_total samples are taken in order; rows i32 [n_rows]: sample s of the launch is buffer row rows[s], indices
+ * clamped into [0, n_total) as there, and gradient and sums are bit-identical to the contiguous form on gathered copies.
+ * bc_sums f64 [UAV_BC_SUMS_N] as uav_bc_loss; masked samples (a < 0 or a >= 5) add nothing to the gradient or the sums, but
+ * their observations still pass through the network and must be finite.  grad, arithmetic modes and their range limit as
+ * uav_mlp_ppo_grad; trend_k 0 .. 2.  There is no diagnostic form: a buffer attached with uav_set_ppo_diag is neither read nor
+ * written.  Added without a change of UAV_ABI_VERSION (a symbol only). */
+int uav_mlp_bc_grad(uav_ctx* ctx, const float* params, const float* obs, const int32_t* act, const float* vtarget,
+                    int64_t n_total, const int32_t* rows, int64_t n_rows, int trend_k, float inv_n, float value_coef,
+                    float ent_beta, double* bc_sums, float* grad, uav_stream stream);
 
 /* ---- shuffled env-sequence minibatches: pack the selected envs of several arrays in ONE launch (csrc/gather.hip).
  * One array of a uav_gather_rows_multi call: `planes` planes of rows of row_bytes bytes each; plane p of the source starts at

@@ -5,7 +5,9 @@ lane-spill traffic (v_readlane + v_writelane) of every kernel, before and after 
 
 Each file is compiled to device assembly with the Makefile's flags (FAST_TU files with -ffp-contract=fast).  The kernels of all
 named files are collected per tree -- a file that a tree does not have is skipped -- and matched by kernel name, so a kernel
-that moved between files is followed (`... OLD_CSRC NEW_CSRC mlp_fused mlp_rollout mlp_update`).  The stream column says
+that moved between files is followed (`... OLD_CSRC NEW_CSRC mlp_fused mlp_rollout mlp_update`).  A template kernel whose
+argument list gained a trailing `false` (a new defaulted bool) is matched with its old name; a kernel only one tree has is listed
+with its own figures.  The stream column says
 "same" when the instruction stream is identical after block labels are renumbered, "same opcodes" when the instruction count
 and the multiset of opcodes are equal but the stream is reordered or uses other registers, else "differs".  A record for a
 refactor, not a gate.
@@ -67,9 +69,14 @@ def main():
     print("|---|---|---|---|---|---|---|---|---|")
     cell = lambda a, b: str(a) if a == b else f"{a} -> {b}"                                         # noqa: E731
     a, b = tree(old, tus), tree(new, tus)
+    # a template that gained a defaulted trailing bool: old `name<args>` is new `name<args, false>`, listed under the new name
+    for k in [k for k in a if k not in b and k.endswith(">") and k[:-1] + ", false>" in b]:
+        a[k[:-1] + ", false>"] = a.pop(k)
     for k in sorted(set(a) | set(b), key=lambda k: ((a.get(k) or b[k])["tu"], k)):
         if k not in a or k not in b:
-            print(f"| {(a.get(k) or b[k])['tu']} | `{k}` | | | | | | | {'only old' if k in a else 'only new'} |")
+            x = a.get(k) or b[k]
+            print(f"| {x['tu']} | `{k}` | " + " | ".join(str(x[f]) for f in ("vgpr", "sgpr", "scratch", "lds", "insts", "lanes")) +
+                  f" | {'only old' if k in a else 'only new'} |")
             continue
         x, y = a[k], b[k]
         stream = "same" if x["sha"] == y["sha"] else ("same opcodes" if x["ops"] == y["ops"] else "differs")

@@ -61,6 +61,10 @@ PPO_DIAGNOSTICS = False  # True: per-epoch approx. KL / clip fractions / explain
 TARGET_KL = None         # a positive number: stop an update's epochs once the epoch's approx. KL (k3) exceeds it; implies PPO_DIAGNOSTICS
 GAE_MODE = "reference_exact"   # or "standard" (PPOV1.0/ppo0.0.py:337-350)
 SEED = 1234
+BC_EPOCHS = 10           # behaviour cloning (train_bc.py): passes over the expert set ...
+BC_BATCH = 4096          # ... in chunks of this many pairs (MLP) or whole episodes (LSTM), one optimiser step each
+BC_LR = 3e-4             # its Adam step size
+BC_VALUE_COEF = 0.0      # weight of the value regression, used only when value targets are given
 TREND_K = 0              # extra observation channels obs[2](t) - obs[2](t-1-i), i < TREND_K (BASELINE C5: 2)
 FIELD_BANK = None        # None = procedural fields | path to .npz / netCDF (conc, tke, source) | "synth:F" (BASELINE C4: "synth:64")
 ITERATIONS = 200         # vectorised trainer: rollout + update iterations ...

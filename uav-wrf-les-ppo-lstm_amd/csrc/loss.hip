@@ -67,6 +67,47 @@ __global__ __launch_bounds__(256) void ppo_loss_kernel(
     if constexpr (DIAG) diag_block_epilogue(dg, partial);
 }
 
+// ---- behaviour cloning on packed heads [n][A+1] (uav_bc_loss): bc_sample per row; block partials = UAV_BC_SUMS_N loss sums
+// + the A + 1 head-bias sums, reduced by the same fixed tree as the PPO kernels'
+template <int A>
+__global__ __launch_bounds__(256) void bc_loss_kernel(const float* __restrict__ heads, const int32_t* __restrict__ act,
+                                                      const float* __restrict__ vtarget, int64_t n, float inv_n, float vcoef,
+                                                      float beta, double* __restrict__ partial, float* __restrict__ dheads) {
+    static_assert(UAV_BC_SUMS_N + A + 1 <= LOSS_PSTRIDE, "bc_loss_kernel: block partial over LOSS_PSTRIDE doubles");
+    constexpr int NH = A + 1;
+    BcAcc acc{0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    float s_db[NH];
+#pragma unroll
+    for (int k = 0; k < NH; ++k) s_db[k] = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float z[A], dz[A];
+#pragma unroll
+        for (int k = 0; k < A; ++k) z[k] = heads[i * NH + k];
+        const float dV = bc_sample<A>(z, heads[i * NH + A], act[i], vtarget != nullptr, vtarget ? vtarget[i] : 0.f, inv_n, vcoef,
+                                      beta, acc, dz);
+        dheads[i * NH + A] = dV;
+        s_db[A] += dV;
+#pragma unroll
+        for (int k = 0; k < A; ++k) {
+            dheads[i * NH + k] = dz[k];
+            s_db[k] += dz[k];
+        }
+    }
+    __shared__ double sm[4];
+    const double t[UAV_BC_SUMS_N] = {block256_sum(acc.nll, sm), block256_sum(acc.vl, sm), block256_sum(acc.en, sm),
+                                     block256_sum(acc.nan, sm), block256_sum(acc.agree, sm), block256_sum(acc.cnt, sm)};
+    double dbs[NH];
+#pragma unroll
+    for (int k = 0; k < NH; ++k) dbs[k] = block256_sum((double)s_db[k], sm);
+    if (threadIdx.x == 0) {
+        double* pp = partial + (size_t)LOSS_PSTRIDE * blockIdx.x;
+#pragma unroll
+        for (int k = 0; k < UAV_BC_SUMS_N; ++k) pp[k] = t[k];
+#pragma unroll
+        for (int k = 0; k < NH; ++k) pp[UAV_BC_SUMS_N + k] = dbs[k];
+    }
+}
+
 // ---- heads fused into the loss: heads = y W_head^T + b_head by MFMA straight from the LSTM output ----
 // One wave = 64 samples (4 m-tiles of 16).  Each 16-row tile of y is loaded with fully coalesced
 // float4 reads into a padded per-wave LDS tile (fragment-shaped loads straight from global touch 64
@@ -161,7 +202,9 @@ __global__ __launch_bounds__(256) void ppo_loss_from_y_kernel(
 }
 
 // one pass over the block partials: thread (column c = tid % 16, row group g = tid / 16) sums rows g, g+64, ... of
-// column c (coalesced 128-B rows, independent loads), then the 64 group sums of a column are added in a fixed order
+// column c (coalesced 128-B rows, independent loads), then the 64 group sums of a column are added in a fixed order.
+// NS: the loss sums in front of the head-bias sums (4: the PPO kernels; UAV_BC_SUMS_N: the cloning kernels)
+template <int NS = 4>
 __global__ __launch_bounds__(1024) void loss_final_kernel(const double* __restrict__ partial, int nb, int n_heads,
                                                           double* __restrict__ out4, float* __restrict__ dbias) {
     __shared__ double sm[64][17];
@@ -177,12 +220,12 @@ __global__ __launch_bounds__(1024) void loss_final_kernel(const double* __restri
     for (; i < nb; i += 64) s0 += partial[(size_t)LOSS_PSTRIDE * i + c];
     sm[g][c] = (s0 + s1) + (s2 + s3);
     __syncthreads();
-    if (threadIdx.x < 4 + n_heads) {
+    if (threadIdx.x < NS + n_heads) {
         double r = 0.0;
 #pragma unroll
         for (int k = 0; k < 64; ++k) r += sm[k][threadIdx.x];
-        if (threadIdx.x < 4) out4[threadIdx.x] = r;
-        else if (dbias) dbias[threadIdx.x - 4] = (float)r;
+        if (threadIdx.x < NS) out4[threadIdx.x] = r;
+        else if (dbias) dbias[threadIdx.x - NS] = (float)r;
     }
 }
 
@@ -256,7 +299,14 @@ __global__ __launch_bounds__(256) void store_transition_kernel(int n, int T, int
 
 // block partials [nb][LOSS_PSTRIDE] -> loss_sums[4] (+ head-bias gradient), for the fused kernels of other files
 int launch_loss_final(double* partial, int nb, int n_heads, double* loss_sums, float* dhead_bias, hipStream_t st) {
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, st, partial, nb, n_heads, loss_sums, dhead_bias);
+    hipLaunchKernelGGL(loss_final_kernel<4>, dim3(1), dim3(1024), 0, st, partial, nb, n_heads, loss_sums, dhead_bias);
+    UAV_LAUNCH_CHECK();
+    return 0;
+}
+
+// block partials [nb][LOSS_PSTRIDE] of a cloning kernel -> bc_sums[UAV_BC_SUMS_N] (+ head-bias gradient)
+int launch_bc_final(double* partial, int nb, int n_heads, double* bc_sums, float* dhead_bias, hipStream_t st) {
+    hipLaunchKernelGGL(loss_final_kernel<UAV_BC_SUMS_N>, dim3(1), dim3(1024), 0, st, partial, nb, n_heads, bc_sums, dhead_bias);
     UAV_LAUNCH_CHECK();
     return 0;
 }
@@ -305,7 +355,7 @@ int uav_ppo_loss(uav_ctx* ctx, const float* logits, const float* value, const in
     }
 #undef LAUNCH_LOSS
 #undef LAUNCH_LOSS_
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, as_stream(stream), partial, nb, n_act + 1, loss_sums,
+    hipLaunchKernelGGL(loss_final_kernel<4>, dim3(1), dim3(1024), 0, as_stream(stream), partial, nb, n_act + 1, loss_sums,
                        dhead_bias);
     UAV_LAUNCH_CHECK();
     return diag ? launch_diag_final(partial, nb, diag, as_stream(stream)) : 0;
@@ -339,10 +389,24 @@ int uav_ppo_loss_from_y(uav_ctx* ctx, const float* y, const float* w_head, const
     }
 #undef LAUNCH_LY
 #undef LAUNCH_LY_
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(1024), 0, as_stream(stream), partial, nb, n_act + 1, loss_sums,
+    hipLaunchKernelGGL(loss_final_kernel<4>, dim3(1), dim3(1024), 0, as_stream(stream), partial, nb, n_act + 1, loss_sums,
                        dhead_bias);
     UAV_LAUNCH_CHECK();
     return diag ? launch_diag_final(partial, nb, diag, as_stream(stream)) : 0;
+}
+
+int uav_bc_loss(uav_ctx* ctx, const float* heads, const int32_t* act, const float* vtarget, int64_t n, int n_act, float inv_n,
+                float value_coef, float ent_beta, double* bc_sums, float* dheads, float* dhead_bias, uav_stream stream) {
+    UAV_REQUIRE(ctx && heads && act && bc_sums && dheads, "uav_bc_loss: NULL argument");
+    UAV_REQUIRE(n > 0 && n_act == 5, "uav_bc_loss: n=%lld n_act=%d (5 actions supported)", (long long)n, n_act);
+    int nb = (int)((n + 255) / 256);
+    if (nb > LOSS_BLOCKS) nb = LOSS_BLOCKS;
+    double* partial = (double*)ctx->ws;
+    UAV_REQUIRE(ctx->ws_bytes >= (size_t)nb * LOSS_PSTRIDE * sizeof(double), "uav_bc_loss: workspace too small");
+    hipLaunchKernelGGL(bc_loss_kernel<5>, dim3(nb), dim3(256), 0, as_stream(stream), heads, act, vtarget, n, inv_n, value_coef,
+                       ent_beta, partial, dheads);
+    UAV_LAUNCH_CHECK();
+    return launch_bc_final(partial, nb, n_act + 1, bc_sums, dhead_bias, as_stream(stream));
 }
 
 int uav_policy_sample(uav_ctx* ctx, const float* logits, int64_t n, int n_act, const float* u,

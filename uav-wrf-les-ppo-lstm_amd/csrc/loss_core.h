@@ -245,3 +245,67 @@ __device__ __forceinline__ float ppo_sample(const float* z, float V, int a, floa
     return 0.5f * inv_n * gV;
 }
 
+// ---- behaviour cloning (uav_bc_loss, uav_mlp_bc_grad): the supervised loss on the expert's action.  Softmax, normalisation,
+// clamp and logf are ppo_sample's, so the log-probability formed here is bit for bit the one ppo_sample forms on the same logits.
+struct BcAcc { double nll, vl, en, nan, agree, cnt; };
+
+// one sample: loss terms into `acc`, d(total)/d(logits) into dz[A], d(total)/dV returned.  a outside 0 .. A-1 is a MASKED sample
+// (a padded step of a ragged episode): dz = 0, dV = 0 and no sum, the NaN count included, sees it.  has_vt: R is a value target
+// (vl = 0.5 (V - R)^2, dV = vcoef inv_n (V - R)); without one vl = 0 and dV = 0.
+template <int A>
+__device__ __forceinline__ float bc_sample(const float (&z)[A], float V, int a, bool has_vt, float R, float inv_n, float vcoef,
+                                           float beta, BcAcc& acc, float* dz) {
+    if (a < 0 || a >= A) {
+#pragma unroll
+        for (int k = 0; k < A; ++k) dz[k] = 0.f;
+        return 0.f;
+    }
+    float p[A];
+    softmax_row<A>(z, p);
+    float psum = 0.f;
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < A; ++k) {
+        psum += p[k];
+        bad |= (p[k] != p[k]);
+    }
+    if (bad) acc.nan += 1.0;
+    float q[A];
+    float qa = 0.f;
+#pragma unroll
+    for (int k = 0; k < A; ++k) {
+        q[k] = p[k] / psum;
+        if (k == a) qa = q[k];
+    }
+    const bool clamp_open = (qa >= F32_EPS) && (qa <= 1.0f - F32_EPS);
+    const float qc = fminf(fmaxf(qa, F32_EPS), 1.0f - F32_EPS);
+    acc.nll += (double)(-logf(qc));
+    const float g_logp = clamp_open ? -inv_n : 0.f;       // dL/dlogp
+    bool zbad;
+    if (argmax_first<A>(z, zbad) == a) acc.agree += 1.0;
+    acc.cnt += 1.0;
+
+    float dV = 0.f;
+    if (has_vt) {
+        const float e = V - R;
+        acc.vl += (double)(0.5f * e * e);
+        dV = vcoef * inv_n * e;
+    }
+    // entropy: ppo_sample's
+    float Hs = 0.f, hk[A], ph = 0.f;
+#pragma unroll
+    for (int k = 0; k < A; ++k) {
+        const float lg = logf(p[k] + 1e-8f);
+        Hs -= p[k] * lg;
+        hk[k] = -lg - p[k] / (p[k] + 1e-8f);
+        ph += p[k] * hk[k];
+    }
+    acc.en += (double)Hs;
+#pragma unroll
+    for (int k = 0; k < A; ++k) {
+        const float dpol = g_logp * ((k == a ? 1.0f : 0.0f) - q[k]);
+        const float dent = -beta * inv_n * p[k] * (hk[k] - ph);
+        dz[k] = dpol + dent;
+    }
+    return dV;
+}

@@ -13,6 +13,7 @@
 
 int launch_loss_final(double* partial, int nb, int n_heads, double* loss_sums, float* dhead_bias, hipStream_t st);
 int launch_diag_final(double* partial, int nb, double* diag, hipStream_t st);
+int launch_bc_final(double* partial, int nb, int n_heads, double* bc_sums, float* dhead_bias, hipStream_t st);
 
 #ifdef UAV_X6_PROFILE
 // phase timing (instrumented build only, tools/build_prof.sh): cycles per phase summed over the tiles of workgroup 0,
@@ -46,6 +47,9 @@ constexpr int UPD_FLOATS = Tiles<UNC>::FLOATS + 2 * H1 + 3 * H2 + UMS * 8 + 2 * 
 constexpr size_t UPD_LDS = (size_t)UPD_FLOATS * sizeof(float);
 // DIAG (uav_set_ppo_diag): + DLS [MS][UAV_PPO_DIAG_N] doubles, the loss lanes' running diagnostic sums, behind everything else
 constexpr size_t UPD_LDS_DIAG = UPD_LDS + (size_t)UMS * UAV_PPO_DIAG_N * sizeof(double);
+// BC (uav_mlp_bc_grad): + BLS [MS][2] doubles, the loss lanes' agreement and sample counts, in the same place (there is no BC + DIAG form)
+constexpr size_t UPD_LDS_BC = UPD_LDS + (size_t)UMS * 2 * sizeof(double);
+static_assert(UAV_BC_SUMS_N == 6 && UAV_BC_SUMS_N + NH <= LOSS_PSTRIDE, "mlp_ppo_grad_kernel<BC>: 4 sums in LS + 2 in BLS + the head-bias sums per partial");
 static_assert(UPD_LDS % sizeof(double) == 0 && UPD_LDS_DIAG <= 160 * 1024, "mlp_ppo_grad_kernel: LDS over 160 KB per workgroup");
 // one gradient slab per workgroup, flat parameter layout: MlpOff(in).N floats
 
@@ -61,7 +65,11 @@ static_assert(UPD_LDS % sizeof(double) == 0 && UPD_LDS_DIAG <= 160 * 1024, "mlp_
 // fetched with this tile's loads, so a tile's gathers never wait for their index; an index outside [0, Bt) is clamped.
 // DIAG: the loss lanes also keep the update diagnostics (loss_core.h: DiagAcc), in LDS like their loss sums, and lane 0 leaves
 // the workgroup's eight sums behind the loss partials.  DIAG = false compiles to the kernels as they were.
-template <bool H3, int INW = IN, bool ROWS = false, bool DIAG = false>
+// BC (uav_mlp_bc_grad): the behaviour-cloning loss on the loss lanes (loss_core.h: bc_sample) -- they load act and, when `ret`
+// is not NULL, the value target from it; logp_old, adv and val_old are never read and `clip` carries value_coef.  The workgroup's
+// partial is UAV_BC_SUMS_N sums + the head-bias sums.  Everything but the loss lanes is the PPO forms' code; BC = false compiles to
+// the kernels as they were, and there is no BC + DIAG form.
+template <bool H3, int INW = IN, bool ROWS = false, bool DIAG = false, bool BC = false>
 __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     const float* __restrict__ params, const float* __restrict__ obs, const int32_t* __restrict__ act,
     const float* __restrict__ logp_old, const float* __restrict__ adv, const float* __restrict__ ret,
@@ -88,6 +96,8 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     // fp16(x), plane 1 = fp16(x - plane 0) with x = dz2 * 2^e_run, e_run the WAVE's running power of two (below)
     unsigned short* P2w = reinterpret_cast<unsigned short*>(MX + NWAVE * MS);
     double* DLS = reinterpret_cast<double*>(smem + UPD_FLOATS);     // DIAG only
+    double* BLS = DLS;                                              // BC only
+    static_assert(!(BC && DIAG), "mlp_ppo_grad_kernel: no diagnostics for the cloning loss");
 
     const int lane = threadIdx.x & 63;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -118,6 +128,8 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     for (int i = threadIdx.x; i < MS * LS_STRIDE; i += 512) LS[i] = 0.0;
     if constexpr (DIAG)
         for (int i = threadIdx.x; i < MS * UAV_PPO_DIAG_N; i += 512) DLS[i] = 0.0;
+    if constexpr (BC)
+        for (int i = threadIdx.x; i < MS * 2; i += 512) BLS[i] = 0.0;
 
     // H3: the dW2 accumulators of this wave hold dW2 * 2^e_run: dz2 rows of this wave's 16 units enter the fp16 product
     // scaled by a power of two that puts the largest magnitude seen SO FAR in [2^13, 2^14); when a tile brings a larger one
@@ -153,7 +165,12 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
         const bool loss_lane = (w == 0) && lane < MS && s0 + lane < Bn;
         if (loss_lane) {
             const int64_t rl = ROWS ? (int64_t)rl_next : s0 + lane;
-            a_s = act[rl]; lpo = logp_old[rl]; Ad = adv[rl]; Rt = ret[rl]; vo = val_old[rl];
+            if constexpr (BC) {
+                a_s = act[rl];
+                if (ret) Rt = ret[rl];
+            } else {
+                a_s = act[rl]; lpo = logp_old[rl]; Ad = adv[rl]; Rt = ret[rl]; vo = val_old[rl];
+            }
             if constexpr (ROWS) rl_next = row_of(s0 + (int64_t)gridDim.x * MS + lane);
         }
         lds_barrier();
@@ -204,7 +221,13 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
                     for (int a = 0; a < NA; ++a) z[a] = L.HD[lane * 8 + a];
                     double* ls = LS + lane * LS_STRIDE;
                     LossAcc lacc{ls[0], ls[1], ls[2], ls[3]};
-                    if constexpr (DIAG) {
+                    if constexpr (BC) {
+                        double* bl = BLS + lane * 2;
+                        BcAcc bacc{ls[0], ls[1], ls[2], ls[3], bl[0], bl[1]};
+                        dV = bc_sample<NA>(z, L.HD[lane * 8 + NA], a_s, ret != nullptr, Rt, inv_n, clip, beta, bacc, dz);
+                        lacc = LossAcc{bacc.nll, bacc.vl, bacc.en, bacc.nan};
+                        bl[0] = bacc.agree; bl[1] = bacc.cnt;
+                    } else if constexpr (DIAG) {
                         DiagAcc* dg = reinterpret_cast<DiagAcc*>(DLS + lane * UAV_PPO_DIAG_N);
                         dV = ppo_sample<NA, true>(z, L.HD[lane * 8 + NA], a_s, lpo, Ad, Rt, vo, inv_n, clip, beta, lacc, dz, dg);
                     } else dV = ppo_sample<NA>(z, L.HD[lane * 8 + NA], a_s, lpo, Ad, Rt, vo, inv_n, clip, beta, lacc, dz);
@@ -536,8 +559,15 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
             for (int k = 0; k < 4 + NH; ++k) {
                 double t = 0.0;
                 for (int sj = 0; sj < MS; ++sj) t += LS[sj * LS_STRIDE + k];
-                pp[k] = t;
+                pp[(BC && k >= 4) ? k + 2 : k] = t;              // BC: the head-bias sums behind the six loss sums
                 if (k >= 4) slab[O.BH + k - 4] = (float)t;
+            }
+            if constexpr (BC) {
+                for (int k = 0; k < 2; ++k) {
+                    double t = 0.0;
+                    for (int sj = 0; sj < MS; ++sj) t += BLS[sj * 2 + k];
+                    pp[4 + k] = t;
+                }
             }
             if constexpr (DIAG) {
                 double* dp = diag_partials(loss_partial) + (size_t)UAV_PPO_DIAG_N * blockIdx.x;
@@ -613,7 +643,7 @@ static int with_bools(F&& f, bool on, Rest... rest) {
 static int mlp_ppo_grad_impl(const char* who, uav_ctx* ctx, const float* params, const float* obs, const int32_t* act,
                              const float* logp_old, const float* adv, const float* ret, const float* val_old, int64_t n, int in,
                              float inv_n, float clip, float ent_beta, double* loss_sums, float* grad, hipStream_t st,
-                             const int32_t* rows = nullptr, int64_t n_total = 0) {
+                             const int32_t* rows = nullptr, int64_t n_total = 0, bool bc = false) {
     const MlpOff O(in);
     const int64_t ntile = (n + UMS - 1) / UMS;
     int nb = ctx->num_cu;
@@ -624,21 +654,25 @@ static int mlp_ppo_grad_impl(const char* who, uav_ctx* ctx, const float* params,
     double* partial = (double*)ctx->ws;
     float* w2t = (float*)((char*)ctx->ws + head);
     float* slabs = (float*)((char*)ctx->ws + head + w2t_bytes);
-    double* const diag = ctx->ppo_diag;      // uav_set_ppo_diag: attached = the DIAG instantiation + its final pass
+    // uav_set_ppo_diag: attached = the DIAG instantiation + its final pass.  bc (uav_mlp_bc_grad: `ret` = vtarget or NULL, `clip` =
+    // value_coef, logp_old / adv / val_old unused, loss_sums = bc_sums[UAV_BC_SUMS_N]) has no such form and leaves the buffer alone
+    double* const diag = bc ? nullptr : ctx->ppo_diag;
     UAV_REQUIRE(!diag || (size_t)nb * (LOSS_PSTRIDE + UAV_PPO_DIAG_N) * sizeof(double) <= head, "%s: %d workgroups' loss partials over the workspace head", who, nb);
     if (h3) hipLaunchKernelGGL(mlp_w2_pieces_kernel, dim3(2 * H1 * H2 / 256), dim3(256), 0, st, params + O.W2, reinterpret_cast<unsigned short*>(w2t));
     else hipLaunchKernelGGL(mlp_w2_transpose_kernel, dim3(H1 * H2 / 256), dim3(256), 0, st, params + O.W2, w2t);
-    const int rc_grad = with_bools([&](auto h3_, auto six, auto rows_, auto diag_) {
-        constexpr auto kern = &mlp_ppo_grad_kernel<h3_(), six() ? IN : 0, rows_(), diag_()>;
-        const size_t lds = diag_() ? UPD_LDS_DIAG : UPD_LDS;
+    const int rc_grad = with_bools([&](auto h3_, auto six, auto rows_, auto diag_, auto bc_) {
+        constexpr bool dg = diag_() && !bc_();
+        constexpr auto kern = &mlp_ppo_grad_kernel<h3_(), six() ? IN : 0, rows_(), dg, bc_()>;
+        const size_t lds = dg ? UPD_LDS_DIAG : (bc_() ? UPD_LDS_BC : UPD_LDS);
         UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
         hipLaunchKernelGGL(kern, dim3(nb), dim3(512), lds, st, params, obs, act, logp_old, adv, ret, val_old, n, inv_n, clip, ent_beta,
                            partial, slabs, w2t, in, rows, n_total);
         return 0;
-    }, h3, in == IN, rows != nullptr, diag != nullptr);
+    }, h3, in == IN, rows != nullptr, diag != nullptr, bc);
     if (rc_grad) return rc_grad;
     hipLaunchKernelGGL(mlp_slab_reduce_kernel, dim3((O.N + 255) / 256), dim3(256), 0, st, slabs, nb, O.N, grad);
     UAV_LAUNCH_CHECK();
+    if (bc) return launch_bc_final(partial, nb, NH, loss_sums, nullptr, st);
     const int rc = launch_loss_final(partial, nb, NH, loss_sums, nullptr, st);
     return (rc || !diag) ? rc : launch_diag_final(partial, nb, diag, st);
 }
@@ -678,4 +712,16 @@ extern "C" int uav_mlp_ppo_grad_rows(uav_ctx* ctx, const float* params, const fl
     UAV_REQUIRE(trend_k >= 0 && 6 + trend_k <= IN_MAX, "uav_mlp_ppo_grad_rows: trend_k=%d (0 .. 2)", trend_k);
     return mlp_ppo_grad_impl("uav_mlp_ppo_grad_rows", ctx, params, obs, act, logp_old, adv, ret, val_old, n_rows, IN + trend_k, inv_n,
                              clip, ent_beta, loss_sums, grad, as_stream(stream), rows, n_total);
+}
+
+extern "C" int uav_mlp_bc_grad(uav_ctx* ctx, const float* params, const float* obs, const int32_t* act, const float* vtarget,
+                               int64_t n_total, const int32_t* rows, int64_t n_rows, int trend_k, float inv_n, float value_coef,
+                               float ent_beta, double* bc_sums, float* grad, uav_stream stream) {
+    UAV_REQUIRE(ctx && params && obs && act && bc_sums && grad, "uav_mlp_bc_grad: NULL argument");
+    UAV_REQUIRE(n_total > 0 && n_total <= 0x7fffffffLL && (!rows || n_rows > 0),
+                "uav_mlp_bc_grad: n_total=%lld n_rows=%lld (n_total 1 .. 2^31 - 1: the indices are i32; n_rows > 0 with rows)",
+                (long long)n_total, (long long)n_rows);
+    UAV_REQUIRE(trend_k >= 0 && 6 + trend_k <= IN_MAX, "uav_mlp_bc_grad: trend_k=%d (0 .. 2)", trend_k);
+    return mlp_ppo_grad_impl("uav_mlp_bc_grad", ctx, params, obs, act, nullptr, nullptr, vtarget, nullptr, rows ? n_rows : n_total,
+                             IN + trend_k, inv_n, value_coef, ent_beta, bc_sums, grad, as_stream(stream), rows, n_total, true);
 }

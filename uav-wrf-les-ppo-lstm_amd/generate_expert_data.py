@@ -35,6 +35,14 @@ def expert_pairs(cur_obs0, obs_rec, act_rec, flags_rec):
     return np.ascontiguousarray(acted_on[stepped], dtype=np.float32), act_rec[stepped].astype(np.int64)
 
 
+def expert_lengths(flags_rec):
+    """Steps per episode, i64 [E], from the flags records expert_pairs takes (an array [N, S] or the list of the launches' chunks):
+    the slots of env e that are not flagged "not stepped".  expert_pairs concatenates episodes in env order and steps in time
+    order, so these lengths cut its flat arrays back into episodes (uavppo.bc.load_expert_sequences)."""
+    flags_rec = np.concatenate([np.asarray(c) for c in flags_rec], axis=1) if isinstance(flags_rec, (list, tuple)) else np.asarray(flags_rec)
+    return ((flags_rec & NOT_STEPPED) == 0).sum(axis=1).astype(np.int64)
+
+
 def load_policy(path, device="cuda"):
     """A policy from a checkpoint train_ppo2.0.py writes: the LSTM actor-critic (keys lstm.*) or the reference's MLP
     (keys feature.*, model.PPOActorCritic; 6 inputs, or 6 + TREND_K read off feature.0.weight)."""
@@ -93,21 +101,24 @@ def greedy_records(policy, env, max_steps=None, chunk=250, fused=None, tail=None
 
 
 def generate_expert_data(policy="ppo_model.pth", num_episodes=100, variant=ENV_VARIANT, seed=SEED, max_steps=None,
-                         out="expert_data.npz", device="cuda", fused=None, tail=None):
+                         out="expert_data.npz", device="cuda", fused=None, tail=None, lengths=False):
     """num_episodes greedy episodes of `policy` (an LSTMActorCritic, MLPActorCritic or model.PPOActorCritic, or the path of a
     checkpoint train_ppo2.0.py wrote; the reference loads 'ppo_model.pth') as num_episodes parallel environments seeded with
     `seed`; every (state, action) pair goes to `out` (None: not written).  Returns (states f32 [M, obs_dim], actions i64 [M]).
     The episodes run on the fused greedy kernels where they cover the policy, on the tail route (uav_greedy_tail behind the LSTM
     layers' step kernels) for every other LSTM policy, step-wise otherwise: the same pairs on each; fused / tail as
-    evaluate_with_lstm.evaluate force a route."""
+    evaluate_with_lstm.evaluate force a route.  lengths=True also saves the key `lengths` (expert_lengths: i64 [num_episodes],
+    what behaviour cloning of an LSTM policy cuts the pairs into episodes with); the default writes the reference's two keys."""
     if isinstance(policy, (str, bytes)) or hasattr(policy, "__fspath__"):
         policy = load_policy(policy, device)
     _, core = policy_core(policy)
     trend_k = (core.obs_dim if hasattr(core, "obs_dim") else core.in_dim) - 6      # LSTMActorCritic | MLPActorCritic
     env = VecMethaneEnv(num_episodes, variant, core.device, seed=seed, trend_k=trend_k)
-    states, actions = expert_pairs(*greedy_records(policy, env, max_steps, fused=fused, tail=tail))
+    recs = greedy_records(policy, env, max_steps, fused=fused, tail=tail)
+    states, actions = expert_pairs(*recs)
     if out:
-        np.savez(out, states=states, actions=actions)
+        extra = {"lengths": expert_lengths(recs[3])} if lengths else {}
+        np.savez(out, states=states, actions=actions, **extra)
         print(f"expert data: {num_episodes} episodes, {len(actions)} pairs -> {out}")
     return states, actions
 

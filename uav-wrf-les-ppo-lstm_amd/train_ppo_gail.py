@@ -21,17 +21,20 @@ from uavppo.gail import GAILTrainer
 def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert_path="expert_data.npz", policy=POLICY,
                    hidden=HIDDEN, gail_coef=1.0, env_coef=1.0, disc_lr=LEARNING_RATE, disc_steps=1, seed=SEED, device="cuda",
                    model_path="ppo_gail_model.pth", disc_path="discriminator.pth", max_iterations=None, update_form="update_model",
-                   minibatch_rows=None):
+                   minibatch_rows=None, init_model=None):
     """Run GAILTrainer until num_episodes episodes have finished (the reference trains 2000, train_ppo_gail.py:49) or
     max_iterations rollouts were collected; print the reference's progress line every 10 iterations (:201-203, its
     `episode` read as the iteration); save the policy as ppo_gail_model.pth (:208) and the discriminator as
-    discriminator.pth.  Returns the trainer."""
+    discriminator.pth.  init_model: the path of a policy checkpoint (train_bc.py's, train_ppo2.0.py's) loaded into the
+    trainer's policy before the first rollout; None starts from the seeded initialisation.  Returns the trainer."""
     states, actions = get_expert_data(expert_path)
     tr = GAILTrainer(num_envs, horizon, policy, hidden=hidden, layers=NUM_LAYERS, variant=ENV_VARIANT, seed=seed, device=device,
                      gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, bptt_len=BPTT_LEN, gamma=GAMMA, lam=LAMBDA, clip=CLIP_EPSILON,
                      ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, expert=(states, actions), gail_coef=gail_coef,
                      env_coef=env_coef, disc_lr=disc_lr, disc_steps=disc_steps, update_form=update_form, minibatch_rows=minibatch_rows,
                      diagnostics=PPO_DIAGNOSTICS, target_kl=TARGET_KL)
+    if init_model is not None:
+        tr.policy.load_state_dict(torch.load(init_model, map_location="cpu"))
     # config.PPO_DIAGNOSTICS (or TARGET_KL): update_diagnostics.csv beside the saved policy, one row per iteration (one host wait each)
     diag_log = diag = None
     if PPO_DIAGNOSTICS or TARGET_KL is not None:

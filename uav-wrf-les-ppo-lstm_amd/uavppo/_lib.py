@@ -74,6 +74,7 @@ SIGNATURES = {
     "uav_ppo_loss": (I32, [P, P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, P, P, P, P]),
     "uav_ppo_loss_from_y": (I32, [P, P, P, P, P, P, P, P, P, I64, I32, I32, F32, F32, F32, P, P, P, P]),
     "uav_set_ppo_diag": (I32, [P, P]),
+    "uav_bc_loss": (I32, [P, P, P, P, I64, I32, F32, F32, F32, P, P, P, P]),
     "uav_policy_sample": (I32, [P, P, I64, I32, P, U64, U64, I64, P, P, P, P, P, P]),
     "uav_policy_sample_at": (I32, [P, P, I64, I64, I32, U64, U64, I64, P, P, I32, I32, P, P, P, P, P]),
     "uav_store_transition": (I32, [P, I32, I32, I32, P, P, P, P, P, P, P, P, P]),
@@ -101,6 +102,7 @@ SIGNATURES = {
     "uav_mlp_ppo_grad": (I32, [P, P, P, P, P, P, P, P, I64, I32, I32, I32, I32, F32, F32, F32, P, P, P]),
     "uav_mlp_ppo_grad_trend": (I32, [P, P, P, P, P, P, P, P, I64, I32, F32, F32, F32, P, P, P]),
     "uav_mlp_ppo_grad_rows": (I32, [P, P, P, P, P, P, P, P, I64, P, I64, I32, F32, F32, F32, P, P, P]),
+    "uav_mlp_bc_grad": (I32, [P, P, P, P, P, I64, P, I64, I32, F32, F32, F32, P, P, P]),
     "uav_gather_rows_multi": (I32, [P, P, I64, I64, C.POINTER(GatherSpec), I32, P]),
     "uav_lstm_fwd": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, P, P, I32, P, P]),
     "uav_lstm_bwd": (I32, [P, P, P, P, P, P, P, I32, P, P, I32, I32, I32, P, P, P, P, I32, P, P]),

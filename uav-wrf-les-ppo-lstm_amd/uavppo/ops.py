@@ -306,6 +306,22 @@ def ppo_loss_from_y(y, w_head, b_head, act, logp_old, adv, ret, val_old, inv_n, 
     return loss_sums, dheads
 
 
+BC_SUMS_N = 6              # UAV_BC_SUMS_N
+# the six sums, include/uavppo.h uav_bc_loss
+BC_SUMS_NAMES = ("nll", "value_loss", "entropy", "nan", "agree", "count")
+
+
+def bc_loss_heads(heads, act, vtarget, inv_n, value_coef, ent_beta, bc_sums, dheads, dhead_bias=None):
+    """Behaviour-cloning loss on packed heads (uav_bc_loss): heads [n, 6] (logits | value) and the expert's actions i32 [n] in,
+    dheads [n, 6] and bc_sums f64 [BC_SUMS_N] out.  act outside 0 .. 4 masks a sample (zero row of dheads, in no sum);
+    vtarget f32 [n] or None (no value regression)."""
+    n, A1 = heads.shape
+    check(lib().uav_bc_loss(_h(heads), _p(heads, F32, (n, A1), "heads"), _p(act, I32, (n,), "act"), _p(vtarget, F32, (n,), "vtarget"),
+                            n, A1 - 1, float(inv_n), float(value_coef), float(ent_beta), _p(bc_sums, F64, (BC_SUMS_N,), "bc_sums"),
+                            _p(dheads, F32, (n, A1), "dheads"), _p(dhead_bias, F32, (A1,), "dhead_bias"), _stream()), "uav_bc_loss")
+    return bc_sums, dheads
+
+
 PPO_DIAG_N = 8             # UAV_PPO_DIAG_N
 # the eight sums, include/uavppo.h UAV_PPO_DIAG_*
 PPO_DIAG_NAMES = ("kl_k1", "kl_k3", "clipped", "value_clipped", "verr2", "ret", "ret2", "count")
@@ -602,6 +618,28 @@ def mlp_ppo_grad_rows(params, obs, act, logp_old, adv, ret, val_old, rows, inv_n
                                       _p(val_old, F32, (n_total,), "val_old"), n_total, _p(rows, I32, name="rows"), rows.numel(),
                                       int(trend_k), float(inv_n), float(clip), float(ent_beta), _p(loss_sums, F64, (4,), "loss_sums"),
                                       _p(grad, F32, params.shape, "grad"), _stream()), "uav_mlp_ppo_grad_rows")
+    if _t is not None:
+        _t.record()
+    return grad
+
+
+def mlp_bc_grad(params, obs, act, vtarget, inv_n, value_coef, ent_beta, bc_sums, grad, trend_k=0, rows=None):
+    """Fused forward + behaviour-cloning loss + backward of the 6+k-256-128 MLP (uav_mlp_bc_grad): obs [n_total, 6 + trend_k], act
+    i32 [n_total], vtarget f32 [n_total] or None; rows None: all samples in order, rows i32 [n_rows]: sample s of the launch is
+    buffer row rows[s] (clamped into the buffer by the kernel), bit-identical to the contiguous form on gathered copies.  Flat
+    gradient and bc_sums f64 [BC_SUMS_N] out."""
+    n_total, D = obs.shape[0], 6 + int(trend_k)
+    _mlp_trend_params("mlp_bc_grad", params, trend_k)
+    if rows is not None and (rows.dim() != 1 or rows.numel() == 0):
+        raise RuntimeError(f"mlp_bc_grad: rows must be a non-empty 1-d index tensor, got shape {tuple(rows.shape)}")
+    if n_total >= 2 ** 31:
+        raise RuntimeError(f"mlp_bc_grad: {n_total} buffer rows do not fit the i32 indices")
+    _t = KERNEL_TIMER.bracket("mlp_bc_grad")
+    check(lib().uav_mlp_bc_grad(_h(obs), _p(params, F32, name="params"), _p(obs, F32, (n_total, D), "obs"),
+                                _p(act, I32, (n_total,), "act"), _p(vtarget, F32, (n_total,), "vtarget"), n_total,
+                                _p(rows, I32, name="rows"), 0 if rows is None else rows.numel(), int(trend_k), float(inv_n),
+                                float(value_coef), float(ent_beta), _p(bc_sums, F64, (BC_SUMS_N,), "bc_sums"),
+                                _p(grad, F32, params.shape, "grad"), _stream()), "uav_mlp_bc_grad")
     if _t is not None:
         _t.record()
     return grad

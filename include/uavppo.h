@@ -104,6 +104,27 @@ int uav_adv_normalise(uav_ctx* ctx, const float* adv, const float* val, int64_t 
 int uav_adv_normalise_inline(uav_ctx* ctx, const float* adv, const float* val, int64_t n,
                              const double* stats3, float* adv_out, float* ret_out, uav_stream stream);
 
+/* ---- N1-N3: running return-based reward normalisation (csrc/reward_norm.hip; no counterpart in the reference).  Between
+ * the rollout and uav_gae, with no host read:  uav_return_stats -> ranks all-reduce stats3 -> uav_return_norm_merge ->
+ * uav_reward_scale.
+ * uav_return_stats: rew, done f32 [n_env][horizon]; the discounted return trace in f64,
+ *   G[e][t] = rew[e][t] + gamma * k[e][t-1] * G[e][t-1],  k = (done != 0) ? 0 : 1,  the term in front of t = 0 being gamma * carry[e];
+ * carry (f64 [n_env], device, read and written) leaves as k[e][T-1] * G[e][T-1], so the next rollout continues the episodes
+ * this one left open.  stats3 (f64 [3], device) = {sum G, sum G^2, n_env * horizon}, summed in a fixed order (the same bits
+ * on every run); trace_out: f64 [n_env][horizon] or NULL.  One wavefront per env row, any horizon; gamma in [0, 1].
+ * uav_return_norm_merge: state f64 [UAV_RETNORM_STATE_N] = {mean, M2, count, skipped} (device; all zeros to start) takes the
+ * batch in by Chan's update: nb = stats3[2], mb = s / nb, M2b = max(q - s s / nb, 0), d = mb - mean, tot = count + nb,
+ * mean += d nb / tot, M2 += M2b + d d count nb / tot, count = tot.  A batch whose s or q is not finite (or whose nb is not
+ * positive) leaves mean, M2 and count as they were and adds 1 to `skipped`.  Then scale[0] (f32, device) =
+ * (float)(1 / sqrt(M2 / count + eps)) in f64, or 1 while count == 0 or M2 / count is not greater than 0.  eps > 0.
+ * uav_reward_scale: out[i] = rew[i] * scale[0] in f32, clamped to [-clip, clip] when clip > 0 (clip <= 0: no clamp); a NaN
+ * stays a NaN; out may be rew.  Added without a change of UAV_ABI_VERSION (symbols only). */
+#define UAV_RETNORM_STATE_N 4
+int uav_return_stats(uav_ctx* ctx, const float* rew, const float* done, double* carry, int n_env, int horizon,
+                     double gamma, double* stats3, double* trace_out, uav_stream stream);
+int uav_return_norm_merge(uav_ctx* ctx, double* state, const double* stats3, double eps, float* scale, uav_stream stream);
+int uav_reward_scale(uav_ctx* ctx, const float* rew, int64_t n, const float* scale, float clip, float* out, uav_stream stream);
+
 /* ---- T1 input (the curriculum of model.py:131-164 consumes one success flag per finished episode): the success bits of
  * the episodes that ended in a rollout, compacted in (env, time) order without a host round trip.  flags u8 [n] as written
  * by uav_rollout / uav_env_step (bit0 done, bit1 reached) -> msg u8 [4 + cap + 1]: count (4 bytes, little endian) | bit1 of

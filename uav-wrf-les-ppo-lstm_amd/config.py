@@ -59,6 +59,8 @@ SHUFFLE_ENVS = False     # True (with NUM_MINIBATCHES > 1): every epoch cuts a f
 BPTT_LEN = None          # LSTM: truncated BPTT over chunks of this many steps (divides HORIZON); None = whole env sequences
 PPO_DIAGNOSTICS = False  # True: per-epoch approx. KL / clip fractions / explained variance of every update (update_diagnostics.csv)
 TARGET_KL = None         # a positive number: stop an update's epochs once the epoch's approx. KL (k3) exceeds it; implies PPO_DIAGNOSTICS
+NORMALISE_REWARDS = False  # True: the GAE reads the reward scaled by the running std of the discounted return (reward_norm_state.npz)
+REWARD_CLIP = 10.0       # ... and clamped to +-REWARD_CLIP afterwards (None: no clamp)
 GAE_MODE = "reference_exact"   # or "standard" (PPOV1.0/ppo0.0.py:337-350)
 SEED = 1234
 BC_EPOCHS = 10           # behaviour cloning (train_bc.py): passes over the expert set ...

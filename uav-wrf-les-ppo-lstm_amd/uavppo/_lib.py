@@ -66,6 +66,9 @@ SIGNATURES = {
     "uav_adv_stats": (I32, [P, P, I64, P, P]),
     "uav_adv_normalise": (I32, [P, P, P, I64, P, P, P, P]),
     "uav_adv_normalise_inline": (I32, [P, P, P, I64, P, P, P, P]),
+    "uav_return_stats": (I32, [P, P, P, P, I32, I32, C.c_double, P, P, P]),
+    "uav_return_norm_merge": (I32, [P, P, P, C.c_double, P, P]),
+    "uav_reward_scale": (I32, [P, P, I64, P, F32, P, P]),
     "uav_pack_success_bits": (I32, [P, P, I64, I32, P, P]),
     "uav_episode_rows": (I32, [P, P, P, P, I32, I32, I32, P, P, I32, P, P]),
     "uav_curriculum_state_bytes": (SZ, []),

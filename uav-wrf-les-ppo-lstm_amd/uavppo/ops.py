@@ -144,6 +144,37 @@ def adv_normalise_inline(adv, val, stats3, adv_out=None, ret_out=None):
     return adv_out, ret_out
 
 
+RETNORM_STATE_N = 4       # UAV_RETNORM_STATE_N: mean, M2, count, skipped
+
+
+def return_stats(rew, done, carry, gamma, stats3=None, trace_out=None):
+    """N1: the discounted return trace of rew / done f32 [n, T] in f64, continued from and into carry f64 [n] (in place);
+    returns stats3 = {sum G, sum G^2, n T} (f64, device).  trace_out: f64 [n, T] to receive the traces, or None."""
+    n, T = rew.shape
+    stats3 = torch.empty(3, dtype=F64, device=rew.device) if stats3 is None else stats3
+    check(lib().uav_return_stats(_h(rew), _p(rew, F32, (n, T), "rew"), _p(done, F32, (n, T), "done"), _p(carry, F64, (n,), "carry"),
+                                 n, T, float(gamma), _p(stats3, F64, (3,), "stats3"), _p(trace_out, F64, (n, T), "trace_out"),
+                                 _stream()), "uav_return_stats")
+    return stats3
+
+
+def return_norm_merge(state, stats3, eps=1e-8, scale=None):
+    """N2: Chan's update of state f64 [4] = {mean, M2, count, skipped} (in place) by the batch sums stats3; returns
+    scale f32 [1] = 1 / sqrt(M2 / count + eps) (1 without samples or variance).  No host sync."""
+    scale = torch.empty(1, dtype=F32, device=state.device) if scale is None else scale
+    check(lib().uav_return_norm_merge(_h(state), _p(state, F64, (RETNORM_STATE_N,), "state"), _p(stats3, F64, (3,), "stats3"),
+                                      float(eps), _p(scale, F32, (1,), "scale"), _stream()), "uav_return_norm_merge")
+    return scale
+
+
+def reward_scale(rew, scale, clip=0.0, out=None):
+    """N3: out = clamp(rew * scale[0], -clip, clip) in f32 (clip <= 0: no clamp); out may be rew."""
+    out = torch.empty_like(rew) if out is None else out
+    check(lib().uav_reward_scale(_h(rew), _p(rew, F32, name="rew"), rew.numel(), _p(scale, F32, (1,), "scale"), float(clip),
+                                 _p(out, F32, rew.shape, "out"), _stream()), "uav_reward_scale")
+    return out
+
+
 def pack_success_bits(flags, cap, out=None):
     """flags u8 [..] -> u8 [4 + cap + 1] message (count LE | success bits of the ended episodes in order | spare)."""
     f = flags.reshape(-1)

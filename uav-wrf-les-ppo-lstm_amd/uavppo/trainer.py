@@ -17,6 +17,7 @@ from .curriculum_link import CurriculumLink
 from .dist_utils import allreduce_adv_stats, allreduce_grad, allreduce_sum, collectives_on, env_shard
 from .policy import LSTMActorCritic, MLPActorCritic
 from .range_guard import RangeGuard
+from .reward_norm import RewardNormaliser, check_reward_norm
 
 # reference hyper-parameters, PPOV2.0/config.py:12-18 and train_ppo2.0.py:87,114
 DEFAULTS = dict(gamma=0.99, lam=0.95, clip=0.2, ent_beta=0.01, lr=3e-5, epochs=5, max_grad_norm=0.5)
@@ -159,9 +160,14 @@ class VecPPOTrainer:
                  seed=1234, gae_mode="reference_exact", num_minibatches=1, bank=None, bank_sources=None,
                  rank=0, world_size=1, use_curriculum=True, trend_k=0, log_info=False, device_curriculum=None,
                  update_form="update_model", minibatch_rows=None, shuffle_envs=False, bptt_len=None, diagnostics=False,
-                 target_kl=None, **hp):
+                 target_kl=None, normalise_rewards=False, reward_clip=10.0, reward_norm_gamma=None, **hp):
         self.hp = dict(DEFAULTS)
         self.hp.update(hp)
+        # normalise_rewards: the GAE reads the reward scaled by a running estimate of the discounted return's standard deviation
+        # and clamped to +-reward_clip (None: no clamp), self.reward_norm (uavppo/reward_norm.py); reward_norm_gamma: the discount of
+        # that return, None = hp["gamma"].  buf["rew"] is never written.  Off: update() issues exactly the launches it did without it.
+        self.normalise_rewards = bool(normalise_rewards)
+        self.reward_clip, self.reward_norm_gamma = check_reward_norm(reward_clip, reward_norm_gamma, self.hp["gamma"])
         # diagnostics: every optimiser step's loss kernel also leaves eight sums (include/uavppo.h, uav_set_ppo_diag) that
         # update() adds up per epoch -- diagnostics() turns them into approx. KL, clip fractions and explained variance.
         # target_kl: after each epoch those sums are all-reduced and read (the update's one host wait per epoch) and the
@@ -250,6 +256,8 @@ class VecPPOTrainer:
         self.bank = None if bank is None else torch.as_tensor(bank, dtype=torch.float64).to(d).contiguous()
         self.bank_sources = None if bank_sources is None else torch.as_tensor(bank_sources, dtype=torch.float64).to(d).contiguous()
         self.link = CurriculumLink(d, self.world, self._coll, use_curriculum, device_curriculum)
+        self.reward_norm = (RewardNormaliser(N, self.T, self.reward_norm_gamma, self.reward_clip or None, device=d)
+                            if self.normalise_rewards else None)
 
     def _alloc_policy_work(self, hidden, layers):
         """The recurrent state and the work arrays the update's kernels write their forward pass to."""
@@ -366,6 +374,8 @@ class VecPPOTrainer:
         if self.kind == "lstm":
             self.h.zero_()
             self.c.zero_()
+        if self.reward_norm is not None:
+            self.reward_norm.reset()
 
     # ------------------------------------------------------------------------------------------ R1
     def _stepwise_lstm_route(self):
@@ -528,7 +538,11 @@ class VecPPOTrainer:
 
     def compute_advantages(self):
         b, hp = self.buf, self.hp
-        ops.gae(self._gae_reward(), b["val"], b["done"], hp["gamma"], hp["lam"], self.gae_mode, last_val=self.last_val, out=self.adv)
+        rew = self._gae_reward()
+        if self.reward_norm is not None:          # N1-N3: the scaled copy rew_n; the array it reads stays as it is.  Every call
+            # takes the buffers into the running estimate as one more rollout (update() makes the call: once per rollout)
+            rew = self.reward_norm(rew, b["done"])
+        ops.gae(rew, b["val"], b["done"], hp["gamma"], hp["lam"], self.gae_mode, last_val=self.last_val, out=self.adv)
         ops.adv_stats(self.adv, out=self.stats3)
         allreduce_adv_stats(self.stats3)          # (sum, sumsq, count): whole-buffer statistics over all ranks
         normalise = ops.adv_normalise_inline if self.update_form == "inline_v10" else ops.adv_normalise

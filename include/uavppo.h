@@ -474,6 +474,36 @@ int uav_lstm_bwd(uav_ctx* ctx, const float* keep, const float* stash, const floa
  * argument), and its contents as f32 rows out [N][T][4H] (a copy where the buffer already is f32 rows). */
 size_t uav_lstm_dgates_bytes(uav_ctx* ctx, int N, int T, int H);
 int uav_lstm_dgates_f32(uav_ctx* ctx, const float* dgates, int N, int T, int H, float* out, uav_stream stream);
+/* TILE FORM of the H = 64 / 128 gate gradients, asked for per buffer and per uav_lstm_bwd call -- never a mode of the handle, so
+ * every caller that does not ask keeps f32 rows [N][T][4H].  In tile form the same f32 values and the same 4H-float rows are kept,
+ * but element (env n, step t, column c) lies at
+ *     (((n / 16) * T + t) * 16 + n % 16) * 4H + c
+ * so the 16 rows that one BPTT workgroup writes in a step are one contiguous block (ceil(N / 16) tiles; the rows of a ragged last
+ * tile past N are never written or read).  Results are bit-identical to the rows form: uav_lstm_wgrad walks K in the same order.
+ *   uav_lstm_dgates_tile_bytes  bytes of a tile-form buffer for uav_lstm_bwd (dheads, <= 7 heads) + uav_lstm_wgrad (input width I),
+ *                               or 0 when this shape is refused (uav_last_error says why: H other than 64 / 128, I > 6, T not a
+ *                               multiple of 32, UAV_ARITH_F32_MFMA, 2^30 values or more, N * T not in whole 32-row slabs per
+ *                               workgroup) -- the caller then keeps f32 rows.
+ *   uav_lstm_dgates_tile        arms `dgates` (at least that many bytes): the NEXT uav_lstm_bwd on this pointer, which must be for
+ *                               this N, T, H, without dx, writes tile form; nonzero when the shape is refused.  The handle then
+ *                               records the buffer as tile form: uav_lstm_wgrad reads it as such (and refuses it for another shape,
+ *                               with dx, under UAV_ARITH_F32_MFMA, or while it is only armed), uav_lstm_dgates_f32 returns its
+ *                               rows.  One arming serves one uav_lstm_bwd: a later uav_lstm_bwd on the pointer that was not armed
+ *                               again writes f32 rows and drops the record.  A handle keeps at most eight such records at a time
+ *                               (the ninth buffer is refused until one is forgotten; a record is never evicted).
+ *   uav_lstm_dgates_form       UAV_DG_* of what the handle has recorded for the pointer (UAV_DG_ROWS when nothing is), -1 on a
+ *                               bad argument.
+ *   uav_lstm_dgates_forget      drops the pointer's tile record (armed or written): call it before the memory is freed or filled
+ *                               by hand, so that the address, reused, is read as f32 rows again.
+ * Added without a change of UAV_ABI_VERSION (symbols only). */
+#define UAV_DG_ROWS 0           /* f32 [N][T][4H] */
+#define UAV_DG_PIECES 1         /* H = 256 on the fp16-split arithmetic: the BPTT's fp16 piece chunks */
+#define UAV_DG_TILE_ARMED 2     /* armed by uav_lstm_dgates_tile, not yet written */
+#define UAV_DG_TILE 3           /* written in tile form */
+size_t uav_lstm_dgates_tile_bytes(uav_ctx* ctx, int N, int T, int I, int H);
+int uav_lstm_dgates_tile(uav_ctx* ctx, float* dgates, int N, int T, int I, int H);
+int uav_lstm_dgates_form(uav_ctx* ctx, const float* dgates);
+int uav_lstm_dgates_forget(uav_ctx* ctx, const float* dgates);
 /* What uav_lstm_bwd can do for this layer shape under the handle's arithmetic (a bit mask):
  *   UAV_BWD_FUSES_DX      dx [N][T][I] = dG W_ih (the gradient of the layer's input, for the layer below) is formed by
  *                         uav_lstm_bwd itself -- its per-step recurrent product multiplies the same dG fragments (H = 256 = I

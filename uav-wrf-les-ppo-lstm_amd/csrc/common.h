@@ -23,6 +23,41 @@ struct uav_form_table {
         return -1;
     }
 };
+// ---- "tile form" of the h = 64 / 128 gate gradients: the same f32 values and the same 4H-float rows as [N][T][4H], but the
+// 16 rows that one BPTT workgroup (16 envs) writes in a step are adjacent -- one contiguous 16 x 4H block per (tile, step)
+// instead of 16 pieces that lie T rows apart:  row(n, t) = ((n / 16) * T + t) * 16 + n % 16,  ceil(N / 16) tiles.
+struct DgTile {
+    static constexpr int MT = 16;                   // envs per tile = envs per BPTT workgroup
+    __host__ __device__ static size_t row(int n, int t, int T) { return ((size_t)(n / MT) * T + t) * MT + n % MT; }
+    __host__ __device__ static size_t rows(int N, int T) { return (size_t)((N + MT - 1) / MT) * MT * T; }
+    __host__ __device__ static size_t bytes(int N, int T, int H) { return rows(N, T) * 4 * H * sizeof(float); }
+};
+// Tile form is asked for PER BUFFER and per uav_lstm_bwd call (uav_lstm_dgates_tile), never per handle: the handle is shared
+// by everything that runs on the device.  state: 1 = armed (the next uav_lstm_bwd on this pointer writes tile form),
+// 2 = written in tile form for (N, T, H).  Any other uav_lstm_bwd on the pointer, and uav_lstm_dgates_forget, drop the entry.
+struct uav_dg_tile_table {
+    struct entry { const void* p; int N, T, H, state; } e[8];
+    entry* find(const void* p) {
+        for (auto& x : e)
+            if (x.p == p && x.state) return &x;
+        return nullptr;
+    }
+    const entry* find(const void* p) const { return const_cast<uav_dg_tile_table*>(this)->find(p); }
+    // false = all 8 entries are in use by other buffers (an entry is never evicted: a buffer written in tile form and then
+    // forgotten by the table would be read as f32 rows)
+    bool arm(const void* p, int N, int T, int H) {
+        entry* x = find(p);
+        for (auto& y : e)
+            if (!x && !y.state) x = &y;
+        if (!x) return false;
+        *x = {p, N, T, H, 1};
+        return true;
+    }
+    void forget(const void* p) {
+        if (entry* x = find(p)) *x = {nullptr, 0, 0, 0, 0};
+    }
+};
+
 struct uav_ctx {
     int device;
     int num_cu;
@@ -40,6 +75,8 @@ struct uav_ctx {
     // form of the last few gate-gradient buffers uav_lstm_bwd / _bwd_stack wrote (1 = fp16 piece chunks, 0 = f32 rows): uav_lstm_wgrad
     // refuses a buffer whose recorded form is not the one the handle's CURRENT mode would read (mode changed in between)
     uav_form_table dg_form;
+    // h = 64 / 128 gate-gradient buffers armed for / written in tile form (DgTile above): uav_lstm_dgates_tile, uav_lstm_bwd
+    uav_dg_tile_table dg_tile;
     // the same for the last few h = 256 stashes uav_lstm_fwd / the stepper wrote (1 = h_prev slot written, 0 = left out by the
     // fp16-split path): uav_lstm_wgrad refuses to read a slot the forward pass did not write (mode changed in between)
     uav_form_table hslot_form;

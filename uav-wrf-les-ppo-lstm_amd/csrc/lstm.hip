@@ -66,7 +66,9 @@ int lstm_h3_bwd_stack(uav_ctx* ctx, int nl, const uav_lstm_bwd_layer* layers, co
                       const float* w_head, int n_heads, int N, int T, hipStream_t st);
 int lstm_wgrad_fused(uav_ctx* ctx, const float* dgates, const float* y, const float* keep, const float* h0,
                      const float* x, int I, const float* dheads, int NH, int N, int T, int H,
-                     float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, hipStream_t st);
+                     float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, bool tile, hipStream_t st);
+const char* lstm_wgrad_tile_refusal(const uav_ctx* ctx, int N, int T, int I, int H);
+int lstm_dg_tile_to_rows(const float* dgates, int N, int T, int H, float* out, hipStream_t st);
 
 constexpr int MT = 16;      // env rows per workgroup (MFMA M)
 constexpr int TC = 32;      // time steps staged per chunk
@@ -732,7 +734,7 @@ struct BwdSplitGeom {
                                   NW * WPARK * sizeof(unsigned short);
 };
 
-template <class P, int H>
+template <class P, int H, bool TILE = false>
 __device__ __forceinline__ void lstm_bwd_split(
     const float* __restrict__ keep, const float* __restrict__ stash, const float* __restrict__ w_hh,
     const float* __restrict__ dheads, const float* __restrict__ w_head, int NH, const float* __restrict__ dhn,
@@ -787,7 +789,10 @@ __device__ __forceinline__ void lstm_bwd_split(
         dh_rec[0] = a4.x; dh_rec[1] = a4.y; dh_rec[2] = a4.z; dh_rec[3] = a4.w;
         dc_next[0] = c4.x; dc_next[1] = c4.y; dc_next[2] = c4.z; dc_next[3] = c4.w;
     }
-    const size_t srow = (size_t)n * T;
+    // gate-gradient row of (env j, step t): n T + t as f32 rows [N][T][4H], or -- tile form (common.h: DgTile) -- the 16 rows
+    // of this workgroup's step adjacent, (tile T + t) 16 + j.  Only live lanes store, so the padded rows of a ragged last tile stay unwritten.
+    const size_t dg_row0 = TILE ? (size_t)blockIdx.x * T * MT + j : (size_t)n * T;
+    constexpr int DG_STEP = TILE ? MT : 1;
 
     // ---- LDS-DMA (inline asm; ordering: comment above BwdSplitGeom): stash gather [q][env lane/4][units 4 (lane%4) ..]
     typedef __attribute__((address_space(3))) float lds_f;
@@ -908,7 +913,7 @@ __device__ __forceinline__ void lstm_bwd_split(
         // above rely on that): ahead of the products, or behind them where they drain under the partial-sum reduce
         // instead of queueing in front of the products of the slowest wave, which everybody then waits for at b1
         auto store_dg = [&](int q) {
-            if (live) *reinterpret_cast<float4*>(dgates + (srow + t) * (4 * H) + q * H + uo) = float4{dg[q][0], dg[q][1], dg[q][2], dg[q][3]};
+            if (live) *reinterpret_cast<float4*>(dgates + (dg_row0 + (size_t)t * DG_STEP) * (4 * H) + q * H + uo) = float4{dg[q][0], dg[q][1], dg[q][2], dg[q][3]};
         };
         // this wave's 64 gate gradients as B fragments: slab sb = gates 2sb, 2sb+1; element e = (gate 2sb + e/4, unit e%4)
         vec bp[2][NP];
@@ -977,6 +982,23 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel(
     float* __restrict__ dc0) {
     lstm_bwd_split<SplitBf16x6, H>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0);
 }
+// the same two kernels writing dgates in tile form (common.h: DgTile); a kernel trace still finds them by the names above as prefixes
+template <int H>
+__global__ __launch_bounds__(H * 4) void lstm_bwd_h3k_kernel_tile(
+    const float* __restrict__ keep, const float* __restrict__ stash, const float* __restrict__ w_hh,
+    const float* __restrict__ dheads, const float* __restrict__ w_head, int NH, const float* __restrict__ dhn,
+    const float* __restrict__ dcn, int N, int T, float* __restrict__ dgates, float* __restrict__ dh0,
+    float* __restrict__ dc0) {
+    lstm_bwd_split<SplitF16x3, H, true>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0);
+}
+template <int H>
+__global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel_tile(
+    const float* __restrict__ keep, const float* __restrict__ stash, const float* __restrict__ w_hh,
+    const float* __restrict__ dheads, const float* __restrict__ w_head, int NH, const float* __restrict__ dhn,
+    const float* __restrict__ dcn, int N, int T, float* __restrict__ dgates, float* __restrict__ dh0,
+    float* __restrict__ dc0) {
+    lstm_bwd_split<SplitBf16x6, H, true>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0);
+}
 
 // the entry points of arithmetic P
 template <class P, int H, bool FUSE_X>
@@ -984,10 +1006,10 @@ static constexpr auto fwd_split_kernel() {
     if constexpr (std::is_same<P, SplitF16x3>::value) return &lstm_fwd_h3_kernel<H, FUSE_X>;
     else return &lstm_fwd_x6_kernel<H, FUSE_X>;
 }
-template <class P, int H>
+template <class P, int H, bool TILE>
 static constexpr auto bwd_split_kernel() {
-    if constexpr (std::is_same<P, SplitF16x3>::value) return &lstm_bwd_h3k_kernel<H>;
-    else return &lstm_bwd_x6k_kernel<H>;
+    if constexpr (std::is_same<P, SplitF16x3>::value) return TILE ? &lstm_bwd_h3k_kernel_tile<H> : &lstm_bwd_h3k_kernel<H>;
+    else return TILE ? &lstm_bwd_x6k_kernel_tile<H> : &lstm_bwd_x6k_kernel<H>;
 }
 
 // f(P{}) with the split policy of the handle's mode
@@ -999,10 +1021,10 @@ static int with_split(F&& f) {
 template <class P, int H>
 static int launch_bwd_split(const float* keep, const float* stash, const float* w_hh, const float* dheads,
                             const float* w_head, int NH, const float* dhn, const float* dcn, int N, int T, float* dgates,
-                            float* dh0, float* dc0, hipStream_t st) {
+                            bool tile, float* dh0, float* dc0, hipStream_t st) {
     const dim3 grid((N + MT - 1) / MT), block(H * 4);
     const size_t lx = BwdSplitGeom<P, H>::LDS;
-    constexpr auto kern = bwd_split_kernel<P, H>();
+    const auto kern = tile ? bwd_split_kernel<P, H, true>() : bwd_split_kernel<P, H, false>();
     UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(kern), (int)lx));
     hipLaunchKernelGGL(kern, grid, block, lx, st, keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0);
     UAV_LAUNCH_CHECK();
@@ -1061,6 +1083,27 @@ static int launch_bwd(const float* keep, const float* stash, const float* w_hh, 
     return 0;
 }
 
+static_assert(MT == DgTile::MT, "a tile of the gate-gradient tile form is one BPTT workgroup's envs");
+
+// out[n][t][4H] = the row of (n, t) in a tile-form gate-gradient buffer (common.h: DgTile); one float4 per thread
+__global__ __launch_bounds__(256) void dg_tile_to_rows_kernel(const float4* __restrict__ dgates, int N, int T, int H4,
+                                                              float4* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)N * T * H4) return;
+    const int64_t r = i / H4;
+    const int c = (int)(i - r * H4), n = (int)(r / T), t = (int)(r - (int64_t)n * T);
+    out[i] = dgates[DgTile::row(n, t, T) * H4 + c];
+}
+int lstm_dg_tile_to_rows(const float* dgates, int N, int T, int H, float* out, hipStream_t st) {
+    const int64_t nv = (int64_t)N * T * H;                   // float4s: 4H / 4 per row
+    UAV_REQUIRE(((reinterpret_cast<uintptr_t>(dgates) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && (nv + 255) / 256 < (1ll << 31),
+                "uav_lstm_dgates_f32: tile form needs 16-byte aligned buffers and fewer than 2^39 values");
+    hipLaunchKernelGGL(dg_tile_to_rows_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st,
+                       reinterpret_cast<const float4*>(dgates), N, T, H, reinterpret_cast<float4*>(out));
+    UAV_LAUNCH_CHECK();
+    return 0;
+}
+
 // b[i] = a0[i] + a1[i]
 __global__ void add2_kernel(const float* a0, const float* a1, float* b, int n) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1069,15 +1112,20 @@ __global__ void add2_kernel(const float* a0, const float* a1, float* b, int n) {
 
 static int lstm_bwd_seq(const float* keep, const float* stash, const float* w_hh, const float* dy,
                         const float* dheads, const float* w_head, int NH, const float* dhn, const float* dcn, int N,
-                        int T, int H, float* dgates, float* dh0, float* dc0, hipStream_t st) {
+                        int T, int H, float* dgates, bool tile, float* dh0, float* dc0, hipStream_t st) {
     if (dheads && NH <= 7 && !uav_want_f32_mfma()) {   // the PPO path: split MFMA, K split over waves
         return with_split([&](auto p) {
             using P = decltype(p);
-            return H == 64 ? launch_bwd_split<P, 64>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0, st)
-                           : launch_bwd_split<P, 128>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0, st);
+            return H == 64 ? launch_bwd_split<P, 64>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, tile, dh0, dc0, st)
+                           : launch_bwd_split<P, 128>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, tile, dh0, dc0, st);
         });
     }
-    // exact-f32 MFMA (UAV_ARITH_F32_MFMA), plain dy (stacked layers), more than 7 heads
+    // exact-f32 MFMA (UAV_ARITH_F32_MFMA), plain dy (stacked layers), more than 7 heads: f32 rows only
+    if (tile) {
+        uav_set_error("uav_lstm_bwd: this dgates buffer is armed for tile form (uav_lstm_dgates_tile), which only the split kernels "
+                      "driven by dheads (at most 7 heads) write; uav_lstm_dgates_forget returns it to f32 rows");
+        return 2;
+    }
     switch (H) {
         case 64: return launch_bwd<64>(keep, stash, w_hh, dy, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0, st);
         case 128: return launch_bwd<128>(keep, stash, w_hh, dy, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0, st);
@@ -1147,9 +1195,48 @@ size_t uav_lstm_dgates_bytes(uav_ctx* ctx, int N, int T, int H) {
 int uav_lstm_dgates_f32(uav_ctx* ctx, const float* dgates, int N, int T, int H, float* out, uav_stream stream) {
     UAV_REQUIRE(ctx && dgates && out && N > 0 && T > 0 && H > 0, "uav_lstm_dgates_f32: bad argument");
     uav_enter(ctx);
+    if (const auto* te = ctx->dg_tile.find(dgates)) {                        // h = 64 / 128 tile form (common.h: DgTile)
+        UAV_REQUIRE(te->state == 2, "uav_lstm_dgates_f32: this dgates buffer is armed for tile form (uav_lstm_dgates_tile) but no "
+                    "uav_lstm_bwd has written it since");
+        UAV_REQUIRE(te->N == N && te->T == T && te->H == H, "uav_lstm_dgates_f32: this dgates buffer was written in tile form for "
+                    "N=%d T=%d H=%d, not N=%d T=%d H=%d", te->N, te->T, te->H, N, T, H);
+        return lstm_dg_tile_to_rows(dgates, N, T, H, out, as_stream(stream));
+    }
     const int form = H == DgPack::H ? uav_dg_form(ctx, dgates) : 0;          // as recorded by the call that wrote it, else by the mode
     if (form > 0 || (form < 0 && H == DgPack::H && lstm_h3_dg_packed(H))) return lstm_pc_unpack(dgates, N, T, out, as_stream(stream));
     UAV_CHECK_HIP(hipMemcpyAsync(out, dgates, (size_t)N * T * 4 * H * sizeof(float), hipMemcpyDeviceToDevice, as_stream(stream)));
+    return 0;
+}
+
+size_t uav_lstm_dgates_tile_bytes(uav_ctx* ctx, int N, int T, int I, int H) {
+    if (!ctx || N <= 0 || T <= 0 || I <= 0 || H <= 0) return 0;
+    uav_enter(ctx);
+    if (const char* why = lstm_wgrad_tile_refusal(ctx, N, T, I, H)) {
+        uav_set_error("uav_lstm_dgates_tile_bytes(N=%d, T=%d, I=%d, H=%d): %s", N, T, I, H, why);
+        return 0;
+    }
+    return DgTile::bytes(N, T, H);
+}
+
+int uav_lstm_dgates_tile(uav_ctx* ctx, float* dgates, int N, int T, int I, int H) {
+    UAV_REQUIRE(ctx && dgates && N > 0 && T > 0 && I > 0 && H > 0, "uav_lstm_dgates_tile: bad argument");
+    uav_enter(ctx);
+    const char* why = lstm_wgrad_tile_refusal(ctx, N, T, I, H);
+    UAV_REQUIRE(!why, "uav_lstm_dgates_tile(N=%d, T=%d, I=%d, H=%d): %s", N, T, I, H, why);
+    UAV_REQUIRE(ctx->dg_tile.arm(dgates, N, T, H), "uav_lstm_dgates_tile: eight other buffers of this handle are armed for or written in "
+                "tile form; uav_lstm_dgates_forget one of them first");
+    return 0;
+}
+
+int uav_lstm_dgates_form(uav_ctx* ctx, const float* dgates) {
+    if (!ctx || !dgates) return -1;
+    if (const auto* te = ctx->dg_tile.find(dgates)) return te->state == 2 ? UAV_DG_TILE : UAV_DG_TILE_ARMED;
+    return uav_dg_form(ctx, dgates) > 0 ? UAV_DG_PIECES : UAV_DG_ROWS;
+}
+
+int uav_lstm_dgates_forget(uav_ctx* ctx, const float* dgates) {
+    UAV_REQUIRE(ctx && dgates, "uav_lstm_dgates_forget: bad argument");
+    ctx->dg_tile.forget(dgates);
     return 0;
 }
 
@@ -1161,6 +1248,7 @@ int uav_lstm_bwd_stack(uav_ctx* ctx, int n_layers, const uav_lstm_bwd_layer* lay
     UAV_REQUIRE(!dheads || (w_head && n_heads > 0 && n_heads <= 8), "uav_lstm_bwd_stack: dheads needs w_head and 1..8 heads");
     UAV_REQUIRE(N > 0 && T > 0, "uav_lstm_bwd_stack: N=%d T=%d", N, T);
     UAV_REQUIRE(H == 256 && lstm_h3_stack_ok(H), "uav_lstm_bwd_stack: H = 256 on the fp16-split arithmetic only (uav_lstm_bwd_caps)");
+    for (int l = 0; l < n_layers && l < 4; ++l) ctx->dg_tile.forget(layers[l].dgates);       // h = 256 never writes tile form
     return lstm_h3_bwd_stack(ctx, n_layers, layers, dy, dheads, w_head, n_heads, N, T, as_stream(stream));
 }
 
@@ -1173,13 +1261,29 @@ int uav_lstm_bwd(uav_ctx* ctx, const float* keep, const float* stash, const floa
     UAV_REQUIRE((dy != nullptr) != (dheads != nullptr), "uav_lstm_bwd: give exactly one of dy / dheads");
     UAV_REQUIRE(!dheads || (w_head && n_heads > 0 && n_heads <= 8), "uav_lstm_bwd: dheads needs w_head and 1..8 heads");
     UAV_REQUIRE(N > 0 && T > 0, "uav_lstm_bwd: N=%d T=%d", N, T);
+    // Tile form (common.h: DgTile) is written only into a buffer armed for exactly this shape by uav_lstm_dgates_tile, and the
+    // record then says so until the next uav_lstm_bwd on the buffer; every other call writes f32 rows and drops the record.
+    auto* te = ctx->dg_tile.find(dgates);
+    const bool tile = te && te->state == 1;
+    if (te && !tile) {
+        ctx->dg_tile.forget(dgates);
+        te = nullptr;
+    }
+    if (tile)
+        UAV_REQUIRE(te->N == N && te->T == T && te->H == H && !dx, "uav_lstm_bwd: this dgates buffer is armed for tile form at N=%d T=%d "
+                    "H=%d without dx (uav_lstm_dgates_tile), not for this call", te->N, te->T, te->H);
     if (H != 64 && H != 128) {
         return lstm_generic_bwd(ctx, keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, H, dgates, dh0, dc0, w_ih, I, dx,
                                 as_stream(stream));
     }
     UAV_REQUIRE(!dx, "uav_lstm_bwd: dx is not formed by the H = 64 / 128 sequence kernels (uav_lstm_wgrad does it)");
-    return lstm_bwd_seq(keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, H, dgates, dh0, dc0,
-                        as_stream(stream));
+    const int rc = lstm_bwd_seq(keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, H, dgates, tile, dh0, dc0,
+                                as_stream(stream));
+    if (tile) {
+        if (rc) ctx->dg_tile.forget(dgates);
+        else te->state = 2;
+    }
+    return rc;
 }
 
 int uav_lstm_wgrad(uav_ctx* ctx, const float* x, const float* keep, const float* h0, const float* y,
@@ -1193,9 +1297,21 @@ int uav_lstm_wgrad(uav_ctx* ctx, const float* x, const float* keep, const float*
     hipStream_t st = as_stream(stream);
     const int64_t NT = (int64_t)N * T;
     int rc;
+    // a buffer in tile form (common.h: DgTile) is read by the split weight-gradient kernels alone, at the shape it was written for
+    bool tile = false;
+    if (const auto* te = ctx->dg_tile.find(dgates)) {
+        UAV_REQUIRE(te->state == 2, "uav_lstm_wgrad: this dgates buffer is armed for tile form (uav_lstm_dgates_tile) but no uav_lstm_bwd "
+                    "has written it since: what it holds are not tile blocks");
+        UAV_REQUIRE(te->N == N && te->T == T && te->H == H && !dx, "uav_lstm_wgrad: this dgates buffer was written in tile form for N=%d "
+                    "T=%d H=%d, which this call (N=%d T=%d H=%d%s) would read as f32 rows", te->N, te->T, te->H, N, T, H, dx ? ", dx" : "");
+        const char* why = lstm_wgrad_tile_refusal(ctx, N, T, I, H);
+        UAV_REQUIRE(!why, "uav_lstm_wgrad: this dgates buffer was written in tile form, which this call cannot read: %s (the arithmetic "
+                    "mode must not change between uav_lstm_bwd and uav_lstm_wgrad)", why);
+        tile = true;
+    }
     if (I <= 6 && (H == 64 || H == 128)) {
         if ((rc = lstm_wgrad_fused(ctx, dgates, y, keep, h0, x, I, dheads, n_heads, N, T, H, dw_ih, dw_hh, db, db_hh,
-                                   dw_head, st))) return rc;
+                                   dw_head, tile, st))) return rc;
     } else {
         // generic path: column sums use the tail of the workspace, the split-K slabs everything in front of it
         UAV_REQUIRE(stash, "uav_lstm_wgrad: stash is required when I > 6");

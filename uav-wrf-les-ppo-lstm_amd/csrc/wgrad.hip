@@ -339,7 +339,7 @@ extern "C" int uav_wx6_prof_read(unsigned long long* out) {
 #define WX_PROF_FLUSH()
 #endif
 
-template <int H, bool HEADS, class P>
+template <int H, bool HEADS, class P, bool TILE = false>
 __device__ __forceinline__ void lstm_wgrad_split(
     const float* __restrict__ dgates, const float* __restrict__ y, const float* __restrict__ keep,
     const float* __restrict__ h0, const float* __restrict__ x, int I, const float* __restrict__ dheads, int NH,
@@ -380,10 +380,23 @@ __device__ __forceinline__ void lstm_wgrad_split(
     // wave-uniform and stays scalar; what depends on the lane is fixed for the whole kernel and formed here, once.
     // The launch checks N*T*4H < 2^30, so every byte offset fits 32 bits.
     auto slab_row = [&](int slab) { return r_begin + (slab < nslab ? slab : nslab - 1) * KS6; };
-    const unsigned a_lane = ((unsigned)(8 * kq) * (4 * H) + 2 * j) * 4;      // dG: rows 8 kq + e, gate columns .. + 2 j
+    // TILE: dgates is in tile form (common.h: DgTile).  K is walked exactly as over f32 rows -- env n's steps, then env n + 1's --
+    // only where a row lies differs: T is a multiple of the slab, so a slab's 32 rows are steps t0 .. t0 + 31 of ONE env, and
+    // consecutive steps lie DgTile::MT rows apart.  That stride is past the immediate field, so each row has a uniform part of
+    // its own; the lane part stays fixed.  The launch checks that the padded buffer's byte offsets fit 32 bits.
+    constexpr int ASTEP = TILE ? DgTile::MT : 1;                             // dG rows between consecutive k
+    const unsigned a_lane = ((unsigned)(8 * kq) * (ASTEP * 4 * H) + 2 * j) * 4;   // dG: rows 8 kq + e, gate columns .. + 2 j
     float raw[4][8];
     constexpr int AR = 8192 / (16 * H) < 8 ? 8192 / (16 * H) : 8;            // dG rows that one base reaches with its immediate
     auto load_a_one = [&](int slab, int pair, int e) {
+        if constexpr (TILE) {
+            const unsigned r0 = (unsigned)slab_row(slab), n = r0 / (unsigned)T, t0 = r0 - n * (unsigned)T;
+            const unsigned row = ((n / DgTile::MT) * (unsigned)T + t0 + e) * DgTile::MT + n % DgTile::MT;
+            const float2 t2 = ld_ubase<float2>(dgates, a_lane + (row * (4 * H) + 64 * w + 32 * pair) * 4);
+            raw[2 * pair][e] = t2.x;
+            raw[2 * pair + 1][e] = t2.y;
+            return;
+        }
         const int eb = e / AR * AR + AR / 2;                                 // the base sits in the middle of its rows
         const unsigned ub = ((unsigned)(slab_row(slab) + eb) * (4 * H) + 64 * w + 32 * pair) * 4;
         const float2 t2 = ld_ubase<float2>(dgates, a_lane + ub, (e - eb) * (4 * H) * 4);
@@ -597,6 +610,22 @@ __global__ __launch_bounds__(H * 4) void lstm_wgrad_h3_kernel(
     lstm_wgrad_split<H, HEADS, WgF16x3>(dgates, y, keep, h0, x, I, dheads, NH, N, T, rows_per_block, slabs);
 }
 
+// the same two kernels reading dgates in tile form (common.h: DgTile); a kernel trace still finds them by the names above as prefixes
+template <int H, bool HEADS>
+__global__ __launch_bounds__(H * 4) void lstm_wgrad_x6_kernel_tile(
+    const float* __restrict__ dgates, const float* __restrict__ y, const float* __restrict__ keep,
+    const float* __restrict__ h0, const float* __restrict__ x, int I, const float* __restrict__ dheads, int NH,
+    int N, int T, int rows_per_block, float* __restrict__ slabs) {
+    lstm_wgrad_split<H, HEADS, WgBf16x6, true>(dgates, y, keep, h0, x, I, dheads, NH, N, T, rows_per_block, slabs);
+}
+template <int H, bool HEADS>
+__global__ __launch_bounds__(H * 4) void lstm_wgrad_h3_kernel_tile(
+    const float* __restrict__ dgates, const float* __restrict__ y, const float* __restrict__ keep,
+    const float* __restrict__ h0, const float* __restrict__ x, int I, const float* __restrict__ dheads, int NH,
+    int N, int T, int rows_per_block, float* __restrict__ slabs) {
+    lstm_wgrad_split<H, HEADS, WgF16x3, true>(dgates, y, keep, h0, x, I, dheads, NH, N, T, rows_per_block, slabs);
+}
+
 // sum the slabs in block order and scatter into dW_hh / dW_ih / db / dW_head
 template <int H>
 __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slabs, int nb, int I, int NH,
@@ -628,72 +657,97 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
     }
 }
 
-template <class P, int H, bool HEADS>
+template <class P, int H, bool HEADS, bool TILE>
 static constexpr auto wgrad_split_kernel() {
-    if constexpr (std::is_same<P, WgF16x3>::value) return &lstm_wgrad_h3_kernel<H, HEADS>;
-    else return &lstm_wgrad_x6_kernel<H, HEADS>;
+    if constexpr (std::is_same<P, WgF16x3>::value) return TILE ? &lstm_wgrad_h3_kernel_tile<H, HEADS> : &lstm_wgrad_h3_kernel<H, HEADS>;
+    else return TILE ? &lstm_wgrad_x6_kernel_tile<H, HEADS> : &lstm_wgrad_x6_kernel<H, HEADS>;
 }
 
 // the split kernel of arithmetic P, with the head tile if there are heads, on nb workgroups of rpb rows
 template <class P, int H>
-static int launch_wgrad_split(const float* dgates, const float* y, const float* keep, const float* h0, const float* x, int I,
+static int launch_wgrad_split(const float* dgates, bool tile, const float* y, const float* keep, const float* h0, const float* x, int I,
                               const float* dheads, int NH, int N, int T, int nb, int rpb, float* slabs, hipStream_t st) {
-    const auto kern = dheads ? wgrad_split_kernel<P, H, true>() : wgrad_split_kernel<P, H, false>();
+    const auto kern = tile ? (dheads ? wgrad_split_kernel<P, H, true, true>() : wgrad_split_kernel<P, H, false, true>())
+                           : (dheads ? wgrad_split_kernel<P, H, true, false>() : wgrad_split_kernel<P, H, false, false>());
     const size_t lds = WGS<H, P>::LDS;
     UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(kern), (int)lds));
     hipLaunchKernelGGL(kern, dim3(nb), dim3(H * 4), lds, st, dgates, y, keep, h0, x, I, dheads, NH, N, T, rpb, slabs);
     return 0;
 }
 
+// How the N * T rows are cut into workgroups: nb x rpb rows for the exact-f32 kernel, nbx x rpx for the split kernels -- full
+// 32-row slabs everywhere, T >= 8 (at most one sequence start per 8 rows) -- and whether the split kernels take the shape.
 template <int H>
-static int launch_wgrad(uav_ctx* ctx, const float* dgates, const float* y, const float* keep, const float* h0,
+struct WgradPlan {
+    int nb = 0, nbx = 0;
+    int64_t rpb = 0, rpx = 0;
+    bool split_ok = false;
+    WgradPlan(const uav_ctx* ctx, int N, int T, int I, bool heads, int NH) {
+        using G = WG<H>;
+        const int64_t NTr = (int64_t)N * T;
+        nb = ctx->num_cu;
+        const int64_t max_nb = (int64_t)(ctx->ws_bytes / (G::SLAB * sizeof(float)));
+        if (nb > max_nb) nb = (int)max_nb;
+        if (nb < 1) return;
+        rpb = (NTr + nb - 1) / nb;
+        rpb = (rpb + KC - 1) / KC * KC;
+        nb = (int)((NTr + rpb - 1) / rpb);
+        rpx = (NTr + nb - 1) / nb;
+        rpx = (rpx + KS6 - 1) / KS6 * KS6;
+        nbx = (int)((NTr + rpx - 1) / rpx);
+        split_ok = (NTr % rpx == 0) && T >= 8 && I <= 6 && (!heads || NH <= 8) && NTr * 4 * H < (1ll << 30) && !uav_want_f32_mfma();
+    }
+};
+
+template <int H>
+static int launch_wgrad(uav_ctx* ctx, const float* dgates, bool tile, const float* y, const float* keep, const float* h0,
                         const float* x, int I, const float* dheads, int NH, int N, int T,
                         float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, hipStream_t st) {
     using G = WG<H>;
-    const int64_t NTr = (int64_t)N * T;
-    int nb = ctx->num_cu;
-    const int64_t max_nb = (int64_t)(ctx->ws_bytes / (G::SLAB * sizeof(float)));
-    if (nb > max_nb) nb = (int)max_nb;
-    UAV_REQUIRE(nb >= 1, "uav_lstm_wgrad: workspace too small for one slab");
-    int64_t rpb = (NTr + nb - 1) / nb;
-    rpb = (rpb + KC - 1) / KC * KC;
-    nb = (int)((NTr + rpb - 1) / rpb);
+    const WgradPlan<H> pl(ctx, N, T, I, dheads != nullptr, NH);
+    UAV_REQUIRE(pl.nb >= 1, "uav_lstm_wgrad: workspace too small for one slab");
     float* slabs = (float*)ctx->ws;
-    // split variants: full 32-row slabs everywhere, T >= 8 (at most one sequence start per 8 rows)
-    {
-        int64_t rpx = (NTr + nb - 1) / nb;
-        rpx = (rpx + KS6 - 1) / KS6 * KS6;
-        const int nbx = (int)((NTr + rpx - 1) / rpx);
-        const bool split_ok = (NTr % rpx == 0) && T >= 8 && I <= 6 && (!dheads || NH <= 8) && NTr * 4 * H < (1ll << 30) &&
-                              !uav_want_f32_mfma();
-        if (split_ok) {
-            const int rc = uav_want_bf16x6()
-                               ? launch_wgrad_split<WgBf16x6, H>(dgates, y, keep, h0, x, I, dheads, NH, N, T, nbx, (int)rpx, slabs, st)
-                               : launch_wgrad_split<WgF16x3, H>(dgates, y, keep, h0, x, I, dheads, NH, N, T, nbx, (int)rpx, slabs, st);
-            if (rc) return rc;
-            hipLaunchKernelGGL((wgrad_reduce_kernel<H>), dim3((unsigned)((G::SLAB + 255) / 256)), dim3(256), 0, st, slabs,
-                               nbx, I, NH, dw_ih, dw_hh, db, db_hh, dw_head);
-            UAV_LAUNCH_CHECK();
-            return 0;
-        }
+    if (pl.split_ok) {
+        const int rc = uav_want_bf16x6()
+                           ? launch_wgrad_split<WgBf16x6, H>(dgates, tile, y, keep, h0, x, I, dheads, NH, N, T, pl.nbx, (int)pl.rpx, slabs, st)
+                           : launch_wgrad_split<WgF16x3, H>(dgates, tile, y, keep, h0, x, I, dheads, NH, N, T, pl.nbx, (int)pl.rpx, slabs, st);
+        if (rc) return rc;
+        hipLaunchKernelGGL((wgrad_reduce_kernel<H>), dim3((unsigned)((G::SLAB + 255) / 256)), dim3(256), 0, st, slabs,
+                           pl.nbx, I, NH, dw_ih, dw_hh, db, db_hh, dw_head);
+        UAV_LAUNCH_CHECK();
+        return 0;
     }
-    // exact-f32 MFMA (UAV_ARITH_F32_MFMA), ragged shapes the split kernels do not take
+    // exact-f32 MFMA (UAV_ARITH_F32_MFMA), ragged shapes the split kernels do not take: f32 rows only
+    UAV_REQUIRE(!tile, "uav_lstm_wgrad: a dgates buffer in tile form is read by the split kernels only, which do not take this call");
     UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&lstm_wgrad_kernel<H>), (int)G::LDS));
-    hipLaunchKernelGGL((lstm_wgrad_kernel<H>), dim3(nb), dim3(H * 4), G::LDS, st, dgates, y, keep, h0, x, I, dheads, NH, N,
-                       T, rpb, slabs);
-    hipLaunchKernelGGL((wgrad_reduce_kernel<H>), dim3((unsigned)((G::SLAB + 255) / 256)), dim3(256), 0, st, slabs, nb, I,
+    hipLaunchKernelGGL((lstm_wgrad_kernel<H>), dim3(pl.nb), dim3(H * 4), G::LDS, st, dgates, y, keep, h0, x, I, dheads, NH, N,
+                       T, pl.rpb, slabs);
+    hipLaunchKernelGGL((wgrad_reduce_kernel<H>), dim3((unsigned)((G::SLAB + 255) / 256)), dim3(256), 0, st, slabs, pl.nb, I,
                        NH, dw_ih, dw_hh, db, db_hh, dw_head);
     UAV_LAUNCH_CHECK();
     return 0;
 }
 
+// Why a gate-gradient buffer of this shape cannot be in tile form (common.h: DgTile), or NULL when it can: the split kernels must
+// take the shape with or without heads, T must be a multiple of their 32-row slab (a workgroup's rows start on a multiple of 32,
+// so then no slab straddles two envs), and the byte offsets into the buffer, padded to whole tiles, must fit the kernels' 32 bits.
+const char* lstm_wgrad_tile_refusal(const uav_ctx* ctx, int N, int T, int I, int H) {
+    if (H != 64 && H != 128) return "tile form exists for H = 64 / 128 only";
+    if (I > 6) return "tile form needs an input of at most 6 features (the fused weight-gradient pass)";
+    if (T % KS6 != 0) return "tile form needs T to be a multiple of 32, the weight-gradient kernels' K slab";
+    if (uav_want_f32_mfma()) return "the exact-f32 kernels (UAV_ARITH_F32_MFMA) read and write f32 rows only";
+    if ((int64_t)DgTile::rows(N, T) * 4 * H >= (1ll << 30)) return "tile form needs fewer than 2^30 values in the buffer, padded to whole 16-env tiles";
+    const bool ok = H == 64 ? WgradPlan<64>(ctx, N, T, I, true, 8).split_ok : WgradPlan<128>(ctx, N, T, I, true, 8).split_ok;
+    return ok ? nullptr : "the split weight-gradient kernels do not take this shape (N * T rows in whole 32-row slabs per workgroup)";
+}
+
 // fast path entry used by uav_lstm_wgrad (lstm.hip) when I <= 6 and H in {64,128}
 int lstm_wgrad_fused(uav_ctx* ctx, const float* dgates, const float* y, const float* keep, const float* h0,
                      const float* x, int I, const float* dheads, int NH, int N, int T, int H,
-                     float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, hipStream_t st) {
+                     float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, bool tile, hipStream_t st) {
     switch (H) {
-        case 64: return launch_wgrad<64>(ctx, dgates, y, keep, h0, x, I, dheads, NH, N, T, dw_ih, dw_hh, db, db_hh, dw_head, st);
-        case 128: return launch_wgrad<128>(ctx, dgates, y, keep, h0, x, I, dheads, NH, N, T, dw_ih, dw_hh, db, db_hh, dw_head, st);
+        case 64: return launch_wgrad<64>(ctx, dgates, tile, y, keep, h0, x, I, dheads, NH, N, T, dw_ih, dw_hh, db, db_hh, dw_head, st);
+        case 128: return launch_wgrad<128>(ctx, dgates, tile, y, keep, h0, x, I, dheads, NH, N, T, dw_ih, dw_hh, db, db_hh, dw_head, st);
     }
     uav_set_error("lstm_wgrad_fused: H=%d unsupported", H);
     return 2;

@@ -112,6 +112,10 @@ SIGNATURES = {
     "uav_lstm_bwd_caps": (I32, [P, I32, I32]),
     "uav_lstm_dgates_bytes": (SZ, [P, I32, I32, I32]),
     "uav_lstm_dgates_f32": (I32, [P, P, I32, I32, I32, P, P]),
+    "uav_lstm_dgates_tile_bytes": (SZ, [P, I32, I32, I32, I32]),
+    "uav_lstm_dgates_tile": (I32, [P, P, I32, I32, I32, I32]),
+    "uav_lstm_dgates_form": (I32, [P, P]),
+    "uav_lstm_dgates_forget": (I32, [P, P]),
     "uav_lstm_bwd_stack": (I32, [P, I32, P, P, P, P, I32, I32, I32, I32, P]),
     "uav_lstm_wgrad": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, P, P, P, P, P, P, P]),
     "uav_lstm_chunk_states": (I32, [P, P, P, P, P, P, I32, I32, I32, I32, P, P, P]),

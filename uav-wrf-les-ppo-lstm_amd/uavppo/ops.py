@@ -873,6 +873,41 @@ def lstm_dgates_f32(dgates, N, T, H):
     return out
 
 
+DG_ROWS, DG_PIECES, DG_TILE_ARMED, DG_TILE = 0, 1, 2, 3      # uav_lstm_dgates_form (include/uavppo.h: UAV_DG_*)
+
+
+def lstm_dgates_tile_bytes(N, T, I, H, device):
+    """uav_lstm_dgates_tile_bytes: size of an h = 64 / 128 gate-gradient buffer in TILE form (the 16 rows a BPTT workgroup writes in
+    a step adjacent; include/uavppo.h), or 0 when the library refuses the form for this shape and the caller keeps f32 rows."""
+    return int(lib().uav_lstm_dgates_tile_bytes(Context.get(torch.device(device)).handle, int(N), int(T), int(I), int(H)))
+
+
+def lstm_dgates_tile(N, T, I, H, device):
+    """A gate-gradient buffer large enough for tile form (an opaque flat f32 tensor; pass it to lstm_bwd with dgates_tile), or None
+    when the form is refused for this shape."""
+    nbytes = lstm_dgates_tile_bytes(N, T, I, H, device)
+    return torch.empty(nbytes // 4, dtype=F32, device=device) if nbytes else None
+
+
+def lstm_dgates_form(dgates):
+    """uav_lstm_dgates_form: DG_ROWS / DG_PIECES / DG_TILE_ARMED / DG_TILE as the device handle has recorded it for this buffer."""
+    return int(lib().uav_lstm_dgates_form(_h(dgates), _p(dgates, F32, None, "dgates")))
+
+
+def lstm_dgates_forget(dgates):
+    """uav_lstm_dgates_forget: drop the handle's tile-form record of this buffer (before it is freed or filled by hand)."""
+    check(lib().uav_lstm_dgates_forget(_h(dgates), _p(dgates, F32, None, "dgates")), "uav_lstm_dgates_forget")
+
+
+def _arm_tile(dgates, N, T, I, H):
+    need = lstm_dgates_tile_bytes(N, T, I, H, dgates.device)
+    if not need:
+        raise RuntimeError(lib().uav_last_error().decode())
+    if dgates.numel() * 4 < need:
+        raise RuntimeError(f"dgates: {dgates.numel() * 4} bytes, uav_lstm_dgates_tile_bytes({N}, {T}, {I}, {H}) = {need} (allocate with ops.lstm_dgates_tile)")
+    check(lib().uav_lstm_dgates_tile(_h(dgates), _p(dgates, F32, None, "dgates"), N, T, I, H), "uav_lstm_dgates_tile")
+
+
 def lstm_wgrad(x, keep, h0, y, stash, dgates, w_ih, dheads=None):
     """The weight-gradient pass alone, from given gate gradients: dW_ih, dW_hh, db (and dW_head = dheads^T y)."""
     N, T, I = x.shape
@@ -924,11 +959,14 @@ def lstm_bwd_stack(layers, keep, dy=None, dheads=None, w_head=None):
 
 def lstm_bwd(x, keep, stash, w_ih, w_hh, y, h0, dy=None, dheads=None, w_head=None, dhn=None, dcn=None, need_dx=False,
              dgates=None, dw_ih=None, dw_hh=None, db=None, dw_head=None, want_dstate=True, wgrad_dheads=None, bwd_done=False,
-             db_hh=None):
+             db_hh=None, dgates_tile=False):
     """BPTT sequence kernel + fused weight-gradient pass of one layer.  y, h0: the layer's forward
     output and initial hidden state (h_prev of the weight gradient is y shifted by one step).
     db_hh: a second [4H] tensor that receives the bias gradient too (nn.LSTM's bias_hh; saves the caller a copy launch).
-    bwd_done: dgates (and the dx a layer above needs) were already produced by lstm_bwd_stack: only the weight gradients."""
+    bwd_done: dgates (and the dx a layer above needs) were already produced by lstm_bwd_stack: only the weight gradients.
+    dgates_tile: the caller's `dgates` (ops.lstm_dgates_tile) is written and read in tile form, for this call alone -- same results
+    to the bit; raises where the library refuses the form.  True leaves the buffer recorded as tile form (lstm_dgates_f32 returns its
+    rows), "transient" drops the record once the weight gradients are formed (a work buffer nobody reads afterwards)."""
     N, T, I = x.shape
     H = w_hh.shape[1]
     dev = x.device
@@ -947,15 +985,24 @@ def lstm_bwd(x, keep, stash, w_ih, w_hh, y, h0, dy=None, dheads=None, w_head=Non
         dw_head = torch.empty(nhw, H, dtype=F32, device=dev)
     # the h = 256 step path forms dx = dG W_ih inside its per-step recurrent product (same dG fragments) when I == H
     dx_in_bwd = bool(need_dx and lstm_bwd_caps(x.device, I, H) & 1) or bwd_done
+    if dgates_tile:
+        if bwd_done or need_dx:
+            raise RuntimeError("lstm_bwd: dgates_tile is for one uav_lstm_bwd + uav_lstm_wgrad pair without dx")
+        _arm_tile(dgates, N, T, I, H)
     _t = None if bwd_done else KERNEL_TIMER.bracket("lstm_bwd")
     if not bwd_done:
-        check(lib().uav_lstm_bwd(_h(x), _p(keep, F32, (N, T), "keep"), _p(stash, F32, (N, T, 6 * H), "stash"),
-                                 _p(w_hh, F32, (4 * H, H), "w_hh"), _p(dy, F32, (N, T, H), "dy"),
-                                 _p(dheads, F32, (N, T, nh), "dheads"), _p(w_head, F32, (nh, H), "w_head"), nh,
-                                 _p(dhn, F32, (N, H), "dhn"), _p(dcn, F32, (N, H), "dcn"), N, T, H,
-                                 _pdg(dgates, N, T, H), _p(dh0), _p(dc0),
-                                 _p(w_ih, F32, (4 * H, I), "w_ih") if dx_in_bwd else None, I, _p(dx) if dx_in_bwd else None,
-                                 _stream()), "uav_lstm_bwd")
+        try:
+            check(lib().uav_lstm_bwd(_h(x), _p(keep, F32, (N, T), "keep"), _p(stash, F32, (N, T, 6 * H), "stash"),
+                                     _p(w_hh, F32, (4 * H, H), "w_hh"), _p(dy, F32, (N, T, H), "dy"),
+                                     _p(dheads, F32, (N, T, nh), "dheads"), _p(w_head, F32, (nh, H), "w_head"), nh,
+                                     _p(dhn, F32, (N, H), "dhn"), _p(dcn, F32, (N, H), "dcn"), N, T, H,
+                                     _pdg(dgates, N, T, H), _p(dh0), _p(dc0),
+                                     _p(w_ih, F32, (4 * H, I), "w_ih") if dx_in_bwd else None, I, _p(dx) if dx_in_bwd else None,
+                                     _stream()), "uav_lstm_bwd")
+        except Exception:
+            if dgates_tile:
+                lstm_dgates_forget(dgates)      # a refused call leaves the buffer as it was: f32 rows to whoever uses it next
+            raise
     if _t is not None:
         _t.record()
     _t = KERNEL_TIMER.bracket("lstm_wgrad")
@@ -969,6 +1016,8 @@ def lstm_bwd(x, keep, stash, w_ih, w_hh, y, h0, dy=None, dheads=None, w_head=Non
           "uav_lstm_wgrad")
     if _t is not None:
         _t.record()
+    if dgates_tile == "transient":
+        lstm_dgates_forget(dgates)
     return {"dx": dx, "dw_ih": dw_ih, "dw_hh": dw_hh, "db": db, "dh0": dh0, "dc0": dc0, "dgates": dgates,
             "dw_head": dw_head}
 

@@ -345,6 +345,12 @@ class LSTMActorCritic(_FlatPolicy):
             if work.get("dy") is None or work["dy"].shape[0] != N * T:
                 work["dy"] = torch.empty(N * T, H, dtype=torch.float32, device=dheads.device)
             dy = ops.gemm(dheads, v["head.weight"], out=work["dy"]).view(N, T, H)
+        # the owner of `work` asked for its gate gradients in tile form (VecPPOTrainer._request_dgates_tile): per call, and only
+        # while the buffer it allocated for that holds this call's shape -- any other call keeps f32 rows
+        tile = False
+        if getattr(self, "dgates_tile", False) and L == 1 and fused_heads and work.get("dgates") is not None:
+            need = ops.lstm_dgates_tile_bytes(N, T, self.obs_dim, H, dheads.device)
+            tile = "transient" if 0 < need <= work["dgates"].numel() * 4 else False
         for l in reversed(range(self.num_layers)):
             x, stash, y, h0 = saved[l]
             top = (l == self.num_layers - 1)
@@ -356,7 +362,8 @@ class LSTMActorCritic(_FlatPolicy):
                              wgrad_dheads=dheads.view(N, T, -1) if top else None,
                              need_dx=(l > 0), dgates=work.get("dgates"), dw_ih=g[f"lstm.weight_ih_l{l}"],
                              dw_hh=g[f"lstm.weight_hh_l{l}"], db=g[f"lstm.bias_ih_l{l}"],
-                             dw_head=g["head.weight"] if top else None, want_dstate=False, db_hh=g[f"lstm.bias_hh_l{l}"])
+                             dw_head=g["head.weight"] if top else None, want_dstate=False, db_hh=g[f"lstm.bias_hh_l{l}"],
+                             dgates_tile=tile)
             dy = r["dx"]
         self._saved = None
         return self.grad

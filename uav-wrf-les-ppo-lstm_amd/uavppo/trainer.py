@@ -9,6 +9,8 @@ statistics (train_ppo2.0.py:35-39).
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -160,8 +162,9 @@ class VecPPOTrainer:
                  seed=1234, gae_mode="reference_exact", num_minibatches=1, bank=None, bank_sources=None,
                  rank=0, world_size=1, use_curriculum=True, trend_k=0, log_info=False, device_curriculum=None,
                  update_form="update_model", minibatch_rows=None, shuffle_envs=False, bptt_len=None, diagnostics=False,
-                 target_kl=None, normalise_rewards=False, reward_clip=10.0, reward_norm_gamma=None, **hp):
+                 target_kl=None, normalise_rewards=False, reward_clip=10.0, reward_norm_gamma=None, dgates_tile=None, **hp):
         self.hp = dict(DEFAULTS)
+        self.dgates_tile = dgates_tile       # gate gradients of the update in tile form: None = the rule of _request_dgates_tile, True / False = A/B
         self.hp.update(hp)
         # normalise_rewards: the GAE reads the reward scaled by a running estimate of the discounted return's standard deviation
         # and clamped to +-reward_clip (None: no clamp), self.reward_norm (uavppo/reward_norm.py); reward_norm_gamma: the discount of
@@ -272,6 +275,7 @@ class VecPPOTrainer:
             self.h, self.c = self._state[0], self._state[1]
             self.h0, self.c0 = self._state0[0], self._state0[1]
             self.work = {"dgates": ops.lstm_dgates(nb, Ls, H, self.device), "heads": torch.empty(nb, Ls, 6, **f32)}   # heads: logits | value, written by the sequence kernels
+            self._request_dgates_tile(L, H)
             for l in range(L):
                 self.work[f"stash{l}"] = torch.empty(nb, Ls, 6 * H, **f32)
                 self.work[f"y{l}"] = torch.empty(nb, Ls, H, **f32)
@@ -281,6 +285,34 @@ class VecPPOTrainer:
             self.work = {"stash": None}      # layer-by-layer path only (770 floats per sample); allocated on first use
             self._step_scratch()
         self.dheads = torch.empty(nb * Ls, 6, **f32)
+
+    def _request_dgates_tile(self, layers, hidden):
+        """Whether this trainer's own work["dgates"] is written and read in TILE form (include/uavppo.h, uav_lstm_dgates_tile: the
+        16 rows a BPTT workgroup writes per step adjacent instead of Ls rows apart; same values, same gradients to the bit).  The
+        request is made per uav_lstm_bwd call for this one buffer (ops.lstm_bwd, dgates_tile="transient"), never as a mode of the
+        device handle, which everything on the device shares.  Asked for when the form exists for the shape -- one layer,
+        h = 64 / 128, at most 6 inputs, sequences of a multiple of 32 steps; the library has the last word
+        (ops.lstm_dgates_tile_bytes) -- and when it pays: the form helps the BPTT where HBM binds it, which takes a
+        16-env tile on every CU.  Rule: tiles = ceil(nb / 16) >= the device's CU count.  Evidence
+        (profiles/dgates_tile_perf.json; one MI355X, 256 CUs, parent and this tree alternating): C3, 256 tiles: the BPTT 0.548-0.555
+        -> 0.527-0.529 ms per launch, the weight-gradient pass unchanged, the iteration 6.72-6.82 -> 6.58-6.68 ms; C4, 64 tiles:
+        4.348-4.351 ms on rows, 4.373-4.383 with the form forced (slower); C2, 16 tiles: 1.482-1.485 against 1.480-1.483 (nothing).
+        Tile counts between 64 and 256 are not measured and keep rows.  dgates_tile=True / False, or UAVPPO_DGATES_TILE=1 / 0 in the
+        environment of a caller that cannot pass it, override the rule for A/B runs (the shape conditions still hold)."""
+        self.policy.dgates_tile = False
+        want = self.dgates_tile
+        if os.environ.get("UAVPPO_DGATES_TILE") in ("0", "1"):         # A/B runs of unchanged callers (bench.py)
+            want = os.environ["UAVPPO_DGATES_TILE"] == "1"
+        if want is False or layers != 1 or hidden not in (64, 128) or self.obs_dim > 6 or self._Ls % 32:
+            return
+        if want is None and (self._nb + 15) // 16 < torch.cuda.get_device_properties(self.device).multi_processor_count:
+            return
+        nbytes = ops.lstm_dgates_tile_bytes(self._nb, self._Ls, self.obs_dim, hidden, self.device)
+        if not nbytes:
+            return
+        if self.work["dgates"].numel() * 4 < nbytes:                   # nb is no multiple of 16: the last tile is padded
+            self.work["dgates"] = torch.empty(nbytes // 4, dtype=torch.float32, device=self.device)
+        self.policy.dgates_tile = True
 
     def _alloc_update_views(self, hidden, layers):
         """What the update reads its sequences from: the sample arrays and the start state themselves, or -- truncated BPTT --

@@ -1,4 +1,4 @@
-"""Tile form of the h = 64 / 128 gate gradients (include/uavppo.h, uav_lstm_dgates_tile; csrc/common.h DgTile): the BPTT writes the
+"""Tile form of the h = 64 / 128 gate gradients (include/uavppo.h, uav_lstm_dgates_tile; csrc/lstm_forms.h DgTile): the BPTT writes the
 16 rows of a workgroup's step as one contiguous block, the weight-gradient pass reads them there.  Nothing but the place of a row
 changes, so everything is held to BIT equality with the f32-rows form of the same call: the gate gradients themselves (through
 uav_lstm_dgates_f32), dh0 / dc0, every weight gradient, and a trainer's parameters, Adam moments and loss sums after three iterations.
@@ -176,6 +176,33 @@ def test_a_handle_keeps_eight_records_and_evicts_none():
         for b in bufs:
             ops.lstm_dgates_forget(b)
     assert all(ops.lstm_dgates_form(b) == ops.DG_ROWS for b in bufs)
+
+
+def test_a_buffer_has_one_record_through_pieces_tile_and_forget():
+    """One buffer, three writers in a row: an h = 256 BPTT (fp16 piece chunks), an armed h = 64 BPTT (tile blocks), then forget.
+    The handle keeps ONE record per buffer (csrc/lstm_forms.h), so what it reports is always the last of them -- after the forget
+    f32 rows, not the pieces of two calls ago."""
+    from uavppo import ops
+    N, T, H = 16, 32, 64
+    N2, T2, H2 = 5, 1, 256                      # the smallest piece-form shape of tests/test_gpu_lstm_h256.py
+    buf = ops.lstm_dgates_tile(N, T, 6, H, DEV)
+    assert buf is not None and buf.numel() * 4 >= ops.lstm_dgates_bytes(N2, T2, H2, DEV)
+    try:
+        p = _inputs(H2, N2, T2, False)
+        with ops.lstm_arith("fp16x3"):
+            y, _, _, stash = ops.lstm_fwd(p["x"], p["keep"], p["h0"], p["c0"], p["w_ih"], p["w_hh"], p["b_ih"], p["b_hh"])
+            ops.lstm_bwd(p["x"], p["keep"], stash, p["w_ih"], p["w_hh"], y, p["h0"], dheads=p["dheads"], w_head=p["w_head"],
+                         dhn=p["dhn"], dcn=p["dcn"], dgates=buf)
+        assert ops.lstm_dgates_form(buf) == ops.DG_PIECES
+        rows = _backward(H, N, T, False, "fp16x3", False)
+        tile = _backward(H, N, T, False, "fp16x3", True, dgates=buf)
+        assert ops.lstm_dgates_form(buf) == ops.DG_TILE
+        for k in ("dw_hh", "dw_ih", "db", "dw_head"):
+            assert torch.isfinite(rows[k]).all() and torch.equal(tile[k], rows[k]), k
+        ops.lstm_dgates_forget(buf)
+        assert ops.lstm_dgates_form(buf) == ops.DG_ROWS
+    finally:
+        ops.lstm_dgates_forget(buf)
 
 
 def _train(tile, N=64, T=32, H=64, iters=3, **kw):

@@ -556,7 +556,7 @@ def test_lstm_bwd_stack_three_layers_equals_per_layer_calls(ops):
 @pytest.mark.parametrize("N,T,I", [(80, 19, 8), (33, 9, 256), (64, 12, 256), (5, 6, 6), (130, 7, 3), (16, 1, 8), (70, 2, 256), (256, 33, 256)])
 def test_h256_gate_gradients_stored_once_equal_the_f32_rows_form(ops, N, T, I):
     """h = 256 on the fp16-split arithmetic keeps the gate gradients ONCE, as the fp16 piece chunks the BPTT's recurrent product
-    consumes (+ one power-of-two scale per env and step; common.h DgPack, uav_lstm_dgates_bytes), and the weight-gradient pass
+    consumes (+ one power-of-two scale per env and step; lstm_forms.h DgPack, uav_lstm_dgates_bytes), and the weight-gradient pass
     reads that form directly (csrc/wgrad_pc.hip: LDS-DMA + transposed fragment reads, the scales riding on h_prev / x).  Against the
     round-4 form kept behind UAV_DEBUG_DG_F32 (f32 rows written as well, weight gradients through gemm_h3_tn8_kernel):
     the recurrent results are the same bits (same pieces, same kernel), the unpacked gate gradients equal the f32 rows to the

@@ -27,11 +27,11 @@ def ops():
 
 
 # ---- the dispatch rules of the h = 64 / 128 layer, restated (a case's kernels follow from its shape, heads and mode):
-#   forward   csrc/lstm.hip:1100-1101  I <= 8: the input product fused into the sequence kernel; I > 8: a GEMM into the
-#             stash first.  :1033 the split kernels (heads fused) unless f32_mfma, then the exact kernel + one heads GEMM.
-#   backward  csrc/lstm.hip:1073  dheads with at most 7 heads and not f32_mfma: the split kernel (lstm_bwd_split);
+#   forward   csrc/lstm_api.hip (uav_lstm_fwd)  I <= 8: the input product fused into the sequence kernel; I > 8: a GEMM into the
+#             stash first.  lstm.hip launch_fwd: the split kernels (heads fused) unless f32_mfma, then the exact kernel + one heads GEMM.
+#   backward  csrc/lstm.hip lstm_bwd_seq  dheads with at most 7 heads and not f32_mfma: the split kernel (lstm_bwd_split);
 #             else (8 heads, plain dy, f32_mfma) the exact kernel (lstm_bwd_kernel).
-#   wgrad     csrc/lstm.hip:1196  I <= 6: launch_wgrad (csrc/wgrad.hip:627-665), else column sums + products (:1254-1271).
+#   wgrad     csrc/lstm_api.hip (uav_lstm_wgrad)  I <= 6: launch_wgrad (csrc/wgrad.hip), else column sums + products (LstmWgrad::rows).
 #             wgrad.hip:632-645: nb = min(num_cu, workspace / slab); rows per block rounded up to 16, nb refitted; rpx = the
 #             rows per block rounded up to 32; the split kernel iff N T % rpx == 0, T >= 8, I <= 6, at most 8 heads,
 #             N T 4H < 2^30 and not f32_mfma (rpx / 32 slabs per workgroup), else the exact kernel lstm_wgrad_kernel.

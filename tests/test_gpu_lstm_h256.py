@@ -1,5 +1,5 @@
 """The h = 256 LSTM backward (fp16-split step kernels, gate gradients stored once as fp16 pieces with one power-of-two scale per
-(env, step): common.h DgPack, csrc/wgrad_pc.hip) against an f64 LSTM -- across the dispatch branches of the weight-gradient
+(env, step): lstm_forms.h DgPack, csrc/wgrad_pc.hip) against an f64 LSTM -- across the dispatch branches of the weight-gradient
 pass, over 40 decades of gradient magnitude, with (env, step) rows whose gate gradients are exactly zero or NaN, and with a
 stash whose h_prev slot the forward pass left unwritten.  -m gpu."""
 import pytest

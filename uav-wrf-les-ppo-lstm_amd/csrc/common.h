@@ -6,57 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/uavppo.h"
-
-// pointer -> small int for the last 8 buffers recorded (an entry is overwritten when its pointer is recorded again)
-struct uav_form_table {
-    struct { const void* p; int v; } e[8];
-    int next;
-    void record(const void* p, int v) {
-        for (auto& x : e)
-            if (x.p == p) { x.v = v; return; }
-        e[next] = {p, v};
-        next = (next + 1) % 8;
-    }
-    int find(const void* p) const {               // -1 = not recorded
-        for (auto& x : e)
-            if (x.p == p) return x.v;
-        return -1;
-    }
-};
-// ---- "tile form" of the h = 64 / 128 gate gradients: the same f32 values and the same 4H-float rows as [N][T][4H], but the
-// 16 rows that one BPTT workgroup (16 envs) writes in a step are adjacent -- one contiguous 16 x 4H block per (tile, step)
-// instead of 16 pieces that lie T rows apart:  row(n, t) = ((n / 16) * T + t) * 16 + n % 16,  ceil(N / 16) tiles.
-struct DgTile {
-    static constexpr int MT = 16;                   // envs per tile = envs per BPTT workgroup
-    __host__ __device__ static size_t row(int n, int t, int T) { return ((size_t)(n / MT) * T + t) * MT + n % MT; }
-    __host__ __device__ static size_t rows(int N, int T) { return (size_t)((N + MT - 1) / MT) * MT * T; }
-    __host__ __device__ static size_t bytes(int N, int T, int H) { return rows(N, T) * 4 * H * sizeof(float); }
-};
-// Tile form is asked for PER BUFFER and per uav_lstm_bwd call (uav_lstm_dgates_tile), never per handle: the handle is shared
-// by everything that runs on the device.  state: 1 = armed (the next uav_lstm_bwd on this pointer writes tile form),
-// 2 = written in tile form for (N, T, H).  Any other uav_lstm_bwd on the pointer, and uav_lstm_dgates_forget, drop the entry.
-struct uav_dg_tile_table {
-    struct entry { const void* p; int N, T, H, state; } e[8];
-    entry* find(const void* p) {
-        for (auto& x : e)
-            if (x.p == p && x.state) return &x;
-        return nullptr;
-    }
-    const entry* find(const void* p) const { return const_cast<uav_dg_tile_table*>(this)->find(p); }
-    // false = all 8 entries are in use by other buffers (an entry is never evicted: a buffer written in tile form and then
-    // forgotten by the table would be read as f32 rows)
-    bool arm(const void* p, int N, int T, int H) {
-        entry* x = find(p);
-        for (auto& y : e)
-            if (!x && !y.state) x = &y;
-        if (!x) return false;
-        *x = {p, N, T, H, 1};
-        return true;
-    }
-    void forget(const void* p) {
-        if (entry* x = find(p)) *x = {nullptr, 0, 0, 0, 0};
-    }
-};
+#include "lstm_forms.h"      // DgTile, DgPack, uav_lstm_forms
 
 struct uav_ctx {
     int device;
@@ -72,19 +22,9 @@ struct uav_ctx {
     hipEvent_t side_ev[8];    // fork / join + a small ring of per-step hand-off events per side stream
     void* comm;               // ncclComm_t of this process's rank (comm.hip: uav_comm_init), or NULL
     int comm_rank, comm_world;
-    // form of the last few gate-gradient buffers uav_lstm_bwd / _bwd_stack wrote (1 = fp16 piece chunks, 0 = f32 rows): uav_lstm_wgrad
-    // refuses a buffer whose recorded form is not the one the handle's CURRENT mode would read (mode changed in between)
-    uav_form_table dg_form;
-    // h = 64 / 128 gate-gradient buffers armed for / written in tile form (DgTile above): uav_lstm_dgates_tile, uav_lstm_bwd
-    uav_dg_tile_table dg_tile;
-    // the same for the last few h = 256 stashes uav_lstm_fwd / the stepper wrote (1 = h_prev slot written, 0 = left out by the
-    // fp16-split path): uav_lstm_wgrad refuses to read a slot the forward pass did not write (mode changed in between)
-    uav_form_table hslot_form;
+    uav_lstm_forms forms;     // what the dgates / stash buffers of the LSTM update hold (lstm_forms.h; decided in lstm_api.hip)
     double* ppo_diag;  // device f64[UAV_PPO_DIAG_N] the loss-bearing entry points overwrite with their diagnostic sums, or NULL (uav_set_ppo_diag)
 };
-static inline void uav_dg_record(uav_ctx* ctx, const void* p, int packed) { ctx->dg_form.record(p, packed); }
-static inline int uav_dg_form(const uav_ctx* ctx, const void* p) { return ctx->dg_form.find(p); }    // -1 = not recorded (filled by the caller)
-
 // arithmetic / debug switches of the call in flight on this thread (set from the handle by the LSTM entry points; the
 // launch helpers below them have no ctx argument).  No getenv on any call path: the UAV_LSTM_BF16X6 / UAV_LSTM_F32_MFMA
 // environment variables are read ONCE, by uav_create, as the handle's initial mode.
@@ -299,35 +239,6 @@ struct SplitBf16x6 {         // UAV_ARITH_BF16X6: three bf16 pieces, six product
         a1 = mma(w(0), b[0], a1);
     }
     __device__ __forceinline__ static f32x4 tile_sum(f32x4 a0, f32x4 a1) { return a0 + a1; }
-};
-
-// ---- gate gradients of the h = 256 fp16-split step path, stored ONCE (round 5): the `dgates` buffer that travels from
-// uav_lstm_bwd / _bwd_stack to uav_lstm_wgrad holds what the BPTT's recurrent product consumes -- the two fp16 pieces of
-// every row, scaled per (env, step) by the power of two that puts the row's largest magnitude in [2^13, 2^14), in MFMA
-// fragment order (lstm_generic.hip: frag_index) -- and the weight-gradient pass reads THAT (wgrad_pc.hip) instead of a second,
-// f32 copy (8 of the 17 KB the gate-gradient kernel moved per env-step; -10 % of a C5 iteration by ablation,
-// profiles/r05_c5_no_f32_dgates_ablation.log).  Layout, time-major so that a step's block and the GEMM's K walk are linear:
-//   halves  pieces[t][rt][s][piece][512]      rt < RT = NP / 16 (16-env row tiles, NP = N rounded up to 64; rows >= N zero),
-//                                             s < NS = 4H / 32 (32 gate rows), 512 = (kq * 16 + env) * 8 + i, row 32 s + 8 kq + i
-//   floats  isc[t][NP]                        2^-e of (env, step): dG = (p0 + 2^-11 p1) * isc; 0 for rows >= N and for
-//                                             rows whose gate gradients are all zero (max isc is the weight-gradient block scale)
-//   floats  iscm[t][NP]                       isc * keep[env][step]: the scale under which dW_hh = dG^T h_prev takes h_prev[n][t] = y[n][t-1]
-//                                             * keep[n][t] straight from the layer's output y (h0 at t = 0) -- the forward pass then
-//                                             need not write an h_prev slot into the stash at all
-// The same byte count as f32 [N][T][4H] plus 8 bytes per (env, step): uav_lstm_dgates_bytes.
-struct DgPack {
-    static constexpr int H = 256, NS = 4 * H / 32;
-    int N, T, NP, RT;
-    __host__ __device__ DgPack(int n, int t) : N(n), T(t), NP((n + 63) / 64 * 64), RT(NP / 16) {}
-    __host__ __device__ size_t step_halves() const { return (size_t)RT * NS * 1024; }
-    __host__ __device__ size_t piece_bytes() const { return (size_t)T * step_halves() * 2; }
-    __host__ __device__ size_t bytes() const { return piece_bytes() + 2 * (size_t)T * NP * sizeof(float); }
-    __host__ __device__ unsigned short* pieces(void* base, int t) const { return (unsigned short*)base + (size_t)t * step_halves(); }
-    __host__ __device__ const unsigned short* pieces(const void* base, int t) const { return (const unsigned short*)base + (size_t)t * step_halves(); }
-    __host__ __device__ float* isc(void* base, int t) const { return (float*)((char*)base + piece_bytes()) + (size_t)t * NP; }
-    __host__ __device__ const float* isc(const void* base, int t) const { return (const float*)((const char*)base + piece_bytes()) + (size_t)t * NP; }
-    __host__ __device__ float* iscm(void* base, int t) const { return isc(base, T) + (size_t)t * NP; }
-    __host__ __device__ const float* iscm(const void* base, int t) const { return isc(base, T) + (size_t)t * NP; }
 };
 
 // ---- wave / block reductions (deterministic: fixed tree, no atomics) -------------------------

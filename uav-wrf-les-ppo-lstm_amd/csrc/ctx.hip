@@ -3,12 +3,11 @@
 #include <mutex>
 #include <set>
 #include <utility>
-#include "common.h"
+#include "internal.h"
 
 static thread_local char g_err[512] = "";
 thread_local int g_uav_arith = 0;
 thread_local unsigned g_uav_debug = 0;
-int env_init_tables(uav_ctx* ctx);
 
 void uav_set_error(const char* fmt, ...) {
     va_list ap;

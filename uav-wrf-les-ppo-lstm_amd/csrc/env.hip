@@ -2,7 +2,7 @@
 // One thread per environment; arithmetic in env_core.h, which every other kernel that steps an env calls too.
 #include <math.h>
 #include <vector>
-#include "env_core.h"
+#include "internal_env.h"
 
 // called once from uav_create: the table is the host libm's pow, i.e. the reference's own values
 int env_init_tables(uav_ctx* ctx) {

@@ -7,7 +7,7 @@
 // through LDS k-major so fragment reads are conflict-free ds_read_b32.  Generic strides make
 // NN / NT / TN one kernel; split-K (grid.z) writes slabs to the context workspace and a second
 // kernel reduces them in a fixed order (deterministic, no float atomics).
-#include "common.h"
+#include "internal.h"
 #include "rows_dot_core.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));

@@ -26,7 +26,7 @@
 // XCD-aware order: workgroups are dispatched round-robin over the 8 XCDs (own L2 each), so the tiles that share operand
 // slabs -- all tiles of one K range under split-K, the column tiles of one row block otherwise -- are placed on
 // consecutive slots of ONE XCD: the operands then cross HBM once per group instead of once per tile.
-#include "common.h"
+#include "internal.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));

@@ -9,12 +9,9 @@
 // and stop_rule_step (stop_rule_core.h; the window in place in stop_win / stop_cnt, as stop_stability_kernel holds it).
 // An env with active[i] = 0 only gets its "not stepped" record; its blob, cur_obs row and window are not touched.
 // Built with the default -ffp-contract=off: it holds env and stop-rule arithmetic.
-#include "env_core.h"
+#include "internal_env.h"
 #include "loss_core.h"
 #include "rows_dot_core.h"
-#include "stop_rule_core.h"
-
-int env_params_from_cfg(const uav_ctx* ctx, const uav_env_cfg* cfg, int n_env, EnvParams& P);
 
 struct GreedyTailBufs {
     float* cur_obs;             // [N][od] in/out

@@ -4,7 +4,7 @@
 // Categorical(probs) behaviour restated here (renormalise, clamp to [eps, 1-eps], log) is
 // torch.distributions' -- see oracle/ppo_oracle.py:categorical_logp.
 // HBM-bound elementwise kernels: loss reads 4*(A+6) B and writes 4*(A+1) B per sample.
-#include "common.h"
+#include "internal.h"
 #include "philox.h"
 
 #include "loss_core.h"

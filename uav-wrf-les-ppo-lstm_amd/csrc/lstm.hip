@@ -30,45 +30,7 @@
 //     time-batched GEMM into the stash first.
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
-
-int gemm_f32(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k,
-             const float* B, int64_t sb_k, int64_t sb_n, float* C, int64_t ldc, const float* bias,
-             int accumulate, hipStream_t st);
-int colsum(uav_ctx* ctx, const float* X, int64_t B, int C, float* out, float* scratch, hipStream_t st);
-int colsum_absmax(uav_ctx* ctx, const float* X, int64_t B, int C, float* out, float* scratch, unsigned* absmax_bits,
-                  hipStream_t st);
-int colsum_xw(uav_ctx* ctx, const float* X, int64_t B, int C, const float* x, int I, float* colsum_out, float* xw_out,
-              float* scratch, unsigned* absmax_bits, hipStream_t st, int xw_transposed = 0);
-bool gemm_h3_ok(int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k, const float* B, int64_t sb_k,
-                int64_t sb_n);
-int gemm_h3(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k, const float* B,
-            int64_t sb_k, int64_t sb_n, float* C, int64_t ldc, const float* bias, int accumulate, const unsigned* a_absmax,
-            hipStream_t st);
-int lstm_generic_fwd(uav_ctx* ctx, const float* keep, const float* h0, const float* c0, const float* w_hh, int N, int T,
-                     int H, float* y, float* hn, float* cn, float* stash, hipStream_t st);
-int lstm_h3_fwd(uav_ctx* ctx, const float* x, int I, const float* w_ih, const float* b_ih, const float* b_hh,
-                const float* keep, const float* h0, const float* c0, const float* w_hh, int N, int T, float* y, float* hn,
-                float* cn, float* stash, hipStream_t st);
-bool lstm_h3_step_path(int H);
-int lstm_generic_bwd(uav_ctx* ctx, const float* keep, const float* stash, const float* w_hh, const float* dy,
-                     const float* dheads, const float* w_head, int n_heads,
-                     const float* dhn, const float* dcn, int N, int T, int H, float* dgates, float* dh0, float* dc0,
-                     const float* w_ih, int I, float* dx, hipStream_t st);
-int lstm_generic_bwd_caps(int I, int H);
-bool lstm_h3_stack_ok(int H);
-bool lstm_h3_dg_packed(int H);
-int lstm_pc_unpack(const void* dgates, int N, int T, float* out, hipStream_t st);
-int lstm_pc_hprev_rows(const float* y, const float* keep, const float* h0, int N, int T, float* out, hipStream_t st);
-int lstm_pc_wgrad(uav_ctx* ctx, const float* x, const float* y, const float* h0, const void* dgates, int N, int T, int I, float* dw_ih,
-                  float* dw_hh, float* db, float* db_hh, hipStream_t st);
-int lstm_h3_bwd_stack(uav_ctx* ctx, int nl, const uav_lstm_bwd_layer* layers, const float* dy, const float* dheads,
-                      const float* w_head, int n_heads, int N, int T, hipStream_t st);
-int lstm_wgrad_fused(uav_ctx* ctx, const float* dgates, const float* y, const float* keep, const float* h0,
-                     const float* x, int I, const float* dheads, int NH, int N, int T, int H,
-                     float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, bool tile, hipStream_t st);
-const char* lstm_wgrad_tile_refusal(const uav_ctx* ctx, int N, int T, int I, int H);
-int lstm_dg_tile_to_rows(const float* dgates, int N, int T, int H, float* out, hipStream_t st);
+#include "internal.h"
 
 constexpr int MT = 16;      // env rows per workgroup (MFMA M)
 constexpr int TC = 32;      // time steps staged per chunk
@@ -789,7 +751,7 @@ __device__ __forceinline__ void lstm_bwd_split(
         dh_rec[0] = a4.x; dh_rec[1] = a4.y; dh_rec[2] = a4.z; dh_rec[3] = a4.w;
         dc_next[0] = c4.x; dc_next[1] = c4.y; dc_next[2] = c4.z; dc_next[3] = c4.w;
     }
-    // gate-gradient row of (env j, step t): n T + t as f32 rows [N][T][4H], or -- tile form (common.h: DgTile) -- the 16 rows
+    // gate-gradient row of (env j, step t): n T + t as f32 rows [N][T][4H], or -- tile form (lstm_forms.h: DgTile) -- the 16 rows
     // of this workgroup's step adjacent, (tile T + t) 16 + j.  Only live lanes store, so the padded rows of a ragged last tile stay unwritten.
     const size_t dg_row0 = TILE ? (size_t)blockIdx.x * T * MT + j : (size_t)n * T;
     constexpr int DG_STEP = TILE ? MT : 1;
@@ -982,7 +944,7 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_x6k_kernel(
     float* __restrict__ dc0) {
     lstm_bwd_split<SplitBf16x6, H>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, dh0, dc0);
 }
-// the same two kernels writing dgates in tile form (common.h: DgTile); a kernel trace still finds them by the names above as prefixes
+// the same two kernels writing dgates in tile form (lstm_forms.h: DgTile); a kernel trace still finds them by the names above as prefixes
 template <int H>
 __global__ __launch_bounds__(H * 4) void lstm_bwd_h3k_kernel_tile(
     const float* __restrict__ keep, const float* __restrict__ stash, const float* __restrict__ w_hh,
@@ -1085,34 +1047,17 @@ static int launch_bwd(const float* keep, const float* stash, const float* w_hh, 
 
 static_assert(MT == DgTile::MT, "a tile of the gate-gradient tile form is one BPTT workgroup's envs");
 
-// out[n][t][4H] = the row of (n, t) in a tile-form gate-gradient buffer (common.h: DgTile); one float4 per thread
-__global__ __launch_bounds__(256) void dg_tile_to_rows_kernel(const float4* __restrict__ dgates, int N, int T, int H4,
-                                                              float4* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (int64_t)N * T * H4) return;
-    const int64_t r = i / H4;
-    const int c = (int)(i - r * H4), n = (int)(r / T), t = (int)(r - (int64_t)n * T);
-    out[i] = dgates[DgTile::row(n, t, T) * H4 + c];
-}
-int lstm_dg_tile_to_rows(const float* dgates, int N, int T, int H, float* out, hipStream_t st) {
-    const int64_t nv = (int64_t)N * T * H;                   // float4s: 4H / 4 per row
-    UAV_REQUIRE(((reinterpret_cast<uintptr_t>(dgates) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && (nv + 255) / 256 < (1ll << 31),
-                "uav_lstm_dgates_f32: tile form needs 16-byte aligned buffers and fewer than 2^39 values");
-    hipLaunchKernelGGL(dg_tile_to_rows_kernel, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st,
-                       reinterpret_cast<const float4*>(dgates), N, T, H, reinterpret_cast<float4*>(out));
-    UAV_LAUNCH_CHECK();
-    return 0;
+// ---- what this file gives the entry points (lstm_api.hip, through internal.h)
+int lstm_fwd_seq(bool fuse, const float* x, const float* keep, const float* h0, const float* c0, const float* w_ih, const float* w_hh,
+                 const float* b_ih, const float* b_hh, int N, int T, int I, int H, float* y, float* hn, float* cn, float* stash,
+                 const float* w_head, const float* b_head, int NHD, float* heads, bool* heads_done, hipStream_t st) {
+    return H == 64 ? launch_fwd<64>(fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, NHD, heads, heads_done, st)
+                   : launch_fwd<128>(fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, NHD, heads, heads_done, st);
 }
 
-// b[i] = a0[i] + a1[i]
-__global__ void add2_kernel(const float* a0, const float* a1, float* b, int n) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) b[i] = a0[i] + a1[i];
-}
-
-static int lstm_bwd_seq(const float* keep, const float* stash, const float* w_hh, const float* dy,
-                        const float* dheads, const float* w_head, int NH, const float* dhn, const float* dcn, int N,
-                        int T, int H, float* dgates, bool tile, float* dh0, float* dc0, hipStream_t st) {
+int lstm_bwd_seq(const float* keep, const float* stash, const float* w_hh, const float* dy, const float* dheads,
+                 const float* w_head, int NH, const float* dhn, const float* dcn, int N, int T, int H, float* dgates, bool tile,
+                 float* dh0, float* dc0, hipStream_t st) {
     if (dheads && NH <= 7 && !uav_want_f32_mfma()) {   // the PPO path: split MFMA, K split over waves
         return with_split([&](auto p) {
             using P = decltype(p);
@@ -1133,262 +1078,3 @@ static int lstm_bwd_seq(const float* keep, const float* stash, const float* w_hh
     uav_set_error("uav_lstm_bwd: H=%d unsupported (64, 128)", H);
     return 2;
 }
-
-extern "C" {
-
-int uav_lstm_fwd(uav_ctx* ctx, const float* x, const float* keep, const float* h0, const float* c0, const float* w_ih,
-                 const float* w_hh, const float* b_ih, const float* b_hh, int N, int T, int I, int H, float* y,
-                 float* hn, float* cn, float* stash, const float* w_head, const float* b_head, int n_heads, float* heads,
-                 uav_stream stream) {
-    UAV_REQUIRE(ctx && x && h0 && c0 && w_ih && w_hh && b_ih && b_hh && y && hn && cn, "uav_lstm_fwd: NULL argument");
-    uav_enter(ctx);
-    UAV_REQUIRE(N > 0 && T > 0 && I > 0, "uav_lstm_fwd: N=%d T=%d I=%d", N, T, I);
-    UAV_REQUIRE(!heads || (w_head && b_head && n_heads > 0 && n_heads <= 8), "uav_lstm_fwd: heads needs w_head, b_head, 1..8 heads");
-    hipStream_t st = as_stream(stream);
-    const bool persistent = (H == 64 || H == 128);
-    const bool fuse = I <= 8 && persistent;
-    const bool step256 = lstm_h3_step_path(H);      // h = 256: one fused launch per step, input projection inside
-    if (step256) UAV_REQUIRE(stash, "uav_lstm_fwd: stash is required when H is not 64/128");
-    if (!fuse && !step256) {
-        // time-batched input projection into the gates slot of the stash: pre = x W_ih^T + (b_ih + b_hh)
-        UAV_REQUIRE(stash, "uav_lstm_fwd: stash is required when I > 8 or H is not 64/128");
-        float* bsum = (float*)ctx->ws;   // 4H floats at the head of the workspace... kept clear of GEMM slabs below
-        uav_ctx sub = *ctx;
-        sub.ws = (char*)ctx->ws + 65536;
-        sub.ws_bytes = ctx->ws_bytes - 65536;
-        hipLaunchKernelGGL(add2_kernel, dim3((4 * H + 255) / 256), dim3(256), 0, st, b_ih, b_hh, bsum, 4 * H);
-        int rc = gemm_f32(&sub, (int64_t)N * T, 4 * H, I, x, I, 1, w_ih, 1, I, stash, 6 * H, bsum, 0, st);
-        if (rc) return rc;
-    }
-    bool heads_done = false;
-    int rc;
-    switch (H) {
-        case 64: rc = launch_fwd<64>(fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, n_heads, heads, &heads_done, st); break;
-        case 128: rc = launch_fwd<128>(fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, n_heads, heads, &heads_done, st); break;
-        default:  // any other hidden size: one launch per time step (lstm_generic.hip)
-            rc = step256 ? lstm_h3_fwd(ctx, x, I, w_ih, b_ih, b_hh, keep, h0, c0, w_hh, N, T, y, hn, cn, stash, st)
-                         : lstm_generic_fwd(ctx, keep, h0, c0, w_hh, N, T, H, y, hn, cn, stash, st);
-    }
-    if (rc) return rc;
-    // h = 256: whether this stash's h_prev slot was written (the fp16-split step path with packed gate gradients leaves it out)
-    if (H == DgPack::H) ctx->hslot_form.record(stash, step256 && lstm_h3_dg_packed(H) ? 0 : 1);
-    // kernels without the fused head product: heads = y W_head^T + b_head as one GEMM over the rows of y
-    if (heads && !heads_done)
-        return gemm_f32(ctx, (int64_t)N * T, n_heads, H, y, H, 1, w_head, 1, H, heads, n_heads, b_head, 0, st);
-    return 0;
-}
-
-int uav_lstm_bwd_caps(uav_ctx* ctx, int I, int H) {
-    if (!ctx) return 0;
-    if (H == 64 || H == 128) return UAV_BWD_TAKES_DHEADS;            // the persistent sequence kernels
-    uav_enter(ctx);
-    return lstm_generic_bwd_caps(I, H);
-}
-
-size_t uav_lstm_dgates_bytes(uav_ctx* ctx, int N, int T, int H) {
-    if (!ctx || N <= 0 || T <= 0 || H <= 0) return 0;
-    uav_enter(ctx);
-    if (H == DgPack::H && lstm_h3_dg_packed(H)) return DgPack(N, T).bytes();
-    return (size_t)N * T * 4 * H * sizeof(float);
-}
-
-int uav_lstm_dgates_f32(uav_ctx* ctx, const float* dgates, int N, int T, int H, float* out, uav_stream stream) {
-    UAV_REQUIRE(ctx && dgates && out && N > 0 && T > 0 && H > 0, "uav_lstm_dgates_f32: bad argument");
-    uav_enter(ctx);
-    if (const auto* te = ctx->dg_tile.find(dgates)) {                        // h = 64 / 128 tile form (common.h: DgTile)
-        UAV_REQUIRE(te->state == 2, "uav_lstm_dgates_f32: this dgates buffer is armed for tile form (uav_lstm_dgates_tile) but no "
-                    "uav_lstm_bwd has written it since");
-        UAV_REQUIRE(te->N == N && te->T == T && te->H == H, "uav_lstm_dgates_f32: this dgates buffer was written in tile form for "
-                    "N=%d T=%d H=%d, not N=%d T=%d H=%d", te->N, te->T, te->H, N, T, H);
-        return lstm_dg_tile_to_rows(dgates, N, T, H, out, as_stream(stream));
-    }
-    const int form = H == DgPack::H ? uav_dg_form(ctx, dgates) : 0;          // as recorded by the call that wrote it, else by the mode
-    if (form > 0 || (form < 0 && H == DgPack::H && lstm_h3_dg_packed(H))) return lstm_pc_unpack(dgates, N, T, out, as_stream(stream));
-    UAV_CHECK_HIP(hipMemcpyAsync(out, dgates, (size_t)N * T * 4 * H * sizeof(float), hipMemcpyDeviceToDevice, as_stream(stream)));
-    return 0;
-}
-
-size_t uav_lstm_dgates_tile_bytes(uav_ctx* ctx, int N, int T, int I, int H) {
-    if (!ctx || N <= 0 || T <= 0 || I <= 0 || H <= 0) return 0;
-    uav_enter(ctx);
-    if (const char* why = lstm_wgrad_tile_refusal(ctx, N, T, I, H)) {
-        uav_set_error("uav_lstm_dgates_tile_bytes(N=%d, T=%d, I=%d, H=%d): %s", N, T, I, H, why);
-        return 0;
-    }
-    return DgTile::bytes(N, T, H);
-}
-
-int uav_lstm_dgates_tile(uav_ctx* ctx, float* dgates, int N, int T, int I, int H) {
-    UAV_REQUIRE(ctx && dgates && N > 0 && T > 0 && I > 0 && H > 0, "uav_lstm_dgates_tile: bad argument");
-    uav_enter(ctx);
-    const char* why = lstm_wgrad_tile_refusal(ctx, N, T, I, H);
-    UAV_REQUIRE(!why, "uav_lstm_dgates_tile(N=%d, T=%d, I=%d, H=%d): %s", N, T, I, H, why);
-    UAV_REQUIRE(ctx->dg_tile.arm(dgates, N, T, H), "uav_lstm_dgates_tile: eight other buffers of this handle are armed for or written in "
-                "tile form; uav_lstm_dgates_forget one of them first");
-    return 0;
-}
-
-int uav_lstm_dgates_form(uav_ctx* ctx, const float* dgates) {
-    if (!ctx || !dgates) return -1;
-    if (const auto* te = ctx->dg_tile.find(dgates)) return te->state == 2 ? UAV_DG_TILE : UAV_DG_TILE_ARMED;
-    return uav_dg_form(ctx, dgates) > 0 ? UAV_DG_PIECES : UAV_DG_ROWS;
-}
-
-int uav_lstm_dgates_forget(uav_ctx* ctx, const float* dgates) {
-    UAV_REQUIRE(ctx && dgates, "uav_lstm_dgates_forget: bad argument");
-    ctx->dg_tile.forget(dgates);
-    return 0;
-}
-
-int uav_lstm_bwd_stack(uav_ctx* ctx, int n_layers, const uav_lstm_bwd_layer* layers, const float* dy, const float* dheads,
-                       const float* w_head, int n_heads, int N, int T, int H, uav_stream stream) {
-    UAV_REQUIRE(ctx && layers, "uav_lstm_bwd_stack: NULL argument");
-    uav_enter(ctx);
-    UAV_REQUIRE((dy != nullptr) != (dheads != nullptr), "uav_lstm_bwd_stack: give exactly one of dy / dheads");
-    UAV_REQUIRE(!dheads || (w_head && n_heads > 0 && n_heads <= 8), "uav_lstm_bwd_stack: dheads needs w_head and 1..8 heads");
-    UAV_REQUIRE(N > 0 && T > 0, "uav_lstm_bwd_stack: N=%d T=%d", N, T);
-    UAV_REQUIRE(H == 256 && lstm_h3_stack_ok(H), "uav_lstm_bwd_stack: H = 256 on the fp16-split arithmetic only (uav_lstm_bwd_caps)");
-    for (int l = 0; l < n_layers && l < 4; ++l) ctx->dg_tile.forget(layers[l].dgates);       // h = 256 never writes tile form
-    return lstm_h3_bwd_stack(ctx, n_layers, layers, dy, dheads, w_head, n_heads, N, T, as_stream(stream));
-}
-
-int uav_lstm_bwd(uav_ctx* ctx, const float* keep, const float* stash, const float* w_hh, const float* dy,
-                 const float* dheads, const float* w_head, int n_heads, const float* dhn, const float* dcn, int N,
-                 int T, int H, float* dgates, float* dh0, float* dc0, const float* w_ih, int I, float* dx,
-                 uav_stream stream) {
-    UAV_REQUIRE(ctx && stash && w_hh && dgates, "uav_lstm_bwd: NULL argument");
-    uav_enter(ctx);
-    UAV_REQUIRE((dy != nullptr) != (dheads != nullptr), "uav_lstm_bwd: give exactly one of dy / dheads");
-    UAV_REQUIRE(!dheads || (w_head && n_heads > 0 && n_heads <= 8), "uav_lstm_bwd: dheads needs w_head and 1..8 heads");
-    UAV_REQUIRE(N > 0 && T > 0, "uav_lstm_bwd: N=%d T=%d", N, T);
-    // Tile form (common.h: DgTile) is written only into a buffer armed for exactly this shape by uav_lstm_dgates_tile, and the
-    // record then says so until the next uav_lstm_bwd on the buffer; every other call writes f32 rows and drops the record.
-    auto* te = ctx->dg_tile.find(dgates);
-    const bool tile = te && te->state == 1;
-    if (te && !tile) {
-        ctx->dg_tile.forget(dgates);
-        te = nullptr;
-    }
-    if (tile)
-        UAV_REQUIRE(te->N == N && te->T == T && te->H == H && !dx, "uav_lstm_bwd: this dgates buffer is armed for tile form at N=%d T=%d "
-                    "H=%d without dx (uav_lstm_dgates_tile), not for this call", te->N, te->T, te->H);
-    if (H != 64 && H != 128) {
-        return lstm_generic_bwd(ctx, keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, H, dgates, dh0, dc0, w_ih, I, dx,
-                                as_stream(stream));
-    }
-    UAV_REQUIRE(!dx, "uav_lstm_bwd: dx is not formed by the H = 64 / 128 sequence kernels (uav_lstm_wgrad does it)");
-    const int rc = lstm_bwd_seq(keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, H, dgates, tile, dh0, dc0,
-                                as_stream(stream));
-    if (tile) {
-        if (rc) ctx->dg_tile.forget(dgates);
-        else te->state = 2;
-    }
-    return rc;
-}
-
-int uav_lstm_wgrad(uav_ctx* ctx, const float* x, const float* keep, const float* h0, const float* y,
-                   const float* stash, const float* dgates, const float* w_ih, const float* dheads, int n_heads, int N,
-                   int T, int I, int H, float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, float* dx,
-                   uav_stream stream) {
-    UAV_REQUIRE(ctx && x && h0 && y && dgates && w_ih && dw_ih && dw_hh && db, "uav_lstm_wgrad: NULL argument");
-    uav_enter(ctx);
-    UAV_REQUIRE(N > 0 && T > 0 && I > 0 && H > 0, "uav_lstm_wgrad: N=%d T=%d I=%d H=%d", N, T, I, H);
-    UAV_REQUIRE(!dheads || (dw_head && n_heads > 0 && n_heads <= 8), "uav_lstm_wgrad: dheads needs dw_head, 1..8 heads");
-    hipStream_t st = as_stream(stream);
-    const int64_t NT = (int64_t)N * T;
-    int rc;
-    // a buffer in tile form (common.h: DgTile) is read by the split weight-gradient kernels alone, at the shape it was written for
-    bool tile = false;
-    if (const auto* te = ctx->dg_tile.find(dgates)) {
-        UAV_REQUIRE(te->state == 2, "uav_lstm_wgrad: this dgates buffer is armed for tile form (uav_lstm_dgates_tile) but no uav_lstm_bwd "
-                    "has written it since: what it holds are not tile blocks");
-        UAV_REQUIRE(te->N == N && te->T == T && te->H == H && !dx, "uav_lstm_wgrad: this dgates buffer was written in tile form for N=%d "
-                    "T=%d H=%d, which this call (N=%d T=%d H=%d%s) would read as f32 rows", te->N, te->T, te->H, N, T, H, dx ? ", dx" : "");
-        const char* why = lstm_wgrad_tile_refusal(ctx, N, T, I, H);
-        UAV_REQUIRE(!why, "uav_lstm_wgrad: this dgates buffer was written in tile form, which this call cannot read: %s (the arithmetic "
-                    "mode must not change between uav_lstm_bwd and uav_lstm_wgrad)", why);
-        tile = true;
-    }
-    if (I <= 6 && (H == 64 || H == 128)) {
-        if ((rc = lstm_wgrad_fused(ctx, dgates, y, keep, h0, x, I, dheads, n_heads, N, T, H, dw_ih, dw_hh, db, db_hh,
-                                   dw_head, tile, st))) return rc;
-    } else {
-        // generic path: column sums use the tail of the workspace, the split-K slabs everything in front of it
-        UAV_REQUIRE(stash, "uav_lstm_wgrad: stash is required when I > 6");
-        const size_t red_floats = (size_t)1024 * 9 * 4 * H + 64;      // colsum (+ dG^T x) partials + the word for max |dG|
-        UAV_REQUIRE(ctx->ws_bytes >= red_floats * sizeof(float) * 2, "uav_lstm_wgrad: workspace too small");
-        float* red = (float*)((char*)ctx->ws + ctx->ws_bytes) - red_floats;
-        uav_ctx sub = *ctx;
-        sub.ws_bytes = ctx->ws_bytes - red_floats * sizeof(float);
-        // h = 256 on the fp16-split step path: `dgates` is the BPTT's piece chunks (common.h: DgPack), read as they are by
-        // wgrad_pc.hip -- db, dw_hh and dw_ih for a narrow (I <= 8) or hidden-wide (I = 256) input.  Any other request (another
-        // width, dx) first unpacks to f32 rows in the workspace and takes the products below.
-        bool done = false;
-        const float* hprev = stash + 5 * H;                 // rows of h_prev: the stash's slot, stride 6H
-        int64_t ld_hprev = 6 * H;
-        {
-            const int form = uav_dg_form(ctx, dgates), want = lstm_h3_dg_packed(H) ? 1 : 0;
-            UAV_REQUIRE(form < 0 || H != DgPack::H || form == want, "uav_lstm_wgrad: this dgates buffer was written as %s but the handle's "
-                        "arithmetic mode / debug flags now read %s (they must not change between uav_lstm_bwd and uav_lstm_wgrad)",
-                        form ? "fp16 piece chunks" : "f32 rows", want ? "fp16 piece chunks" : "f32 rows");
-            // the f32-rows form below reads h_prev from the stash's slot: refuse a stash whose forward pass left it out
-            UAV_REQUIRE(H != DgPack::H || want || ctx->hslot_form.find(stash) != 0, "uav_lstm_wgrad: this stash was written by "
-                        "uav_lstm_fwd / the stepper on the fp16-split arithmetic, which leaves out its h_prev slot, but the handle's "
-                        "arithmetic mode / debug flags now read that slot (they must not change between the forward pass and "
-                        "uav_lstm_wgrad)");
-        }
-        if (lstm_h3_dg_packed(H)) {
-            if ((I <= 8 || I == H) && !dx) {
-                if ((rc = lstm_pc_wgrad(ctx, x, y, h0, dgates, N, T, I, dw_ih, dw_hh, db, db_hh, st))) return rc;
-                done = true;
-            } else {
-                const size_t f32_bytes = (size_t)NT * 5 * H * sizeof(float);       // gate gradients 4H + h_prev H (this mode's forward
-                UAV_REQUIRE(sub.ws_bytes >= f32_bytes + (64u << 20), "uav_lstm_wgrad (h=256, I=%d%s): needs %zu bytes of workspace for "
-                            "the gate gradients and h_prev as f32 rows", I, dx ? ", dx" : "", f32_bytes + (64u << 20));   // writes no slot)
-                float* rows = (float*)((char*)sub.ws + sub.ws_bytes - f32_bytes);
-                sub.ws_bytes -= f32_bytes;
-                if ((rc = lstm_pc_unpack(dgates, N, T, rows, st))) return rc;
-                float* hp = rows + (size_t)NT * 4 * H;
-                if ((rc = lstm_pc_hprev_rows(y, keep, h0, N, T, hp, st))) return rc;
-                dgates = rows;
-                hprev = hp;
-                ld_hprev = H;
-            }
-        }
-        // The large products go to the 16-bit matrix pipe as three fp16 piece products (gemm_h3.hip) unless exact f32 or
-        // the bf16 split was asked for: dG is block-scaled by one power of two from its absolute maximum, which the bias
-        // gradient's column-sum pass (it reads all of dG anyway) delivers; h_prev, x and W_ih are inside fp16's range
-        // under the same preconditions as the sequence kernels' (include/uavppo.h, uav_set_lstm_arith).
-        const bool h3 = !uav_want_f32_mfma() && !uav_want_bf16x6() && (reinterpret_cast<uintptr_t>(dgates) & 15) == 0;
-        unsigned* amax = h3 ? reinterpret_cast<unsigned*>(red + (size_t)1024 * 9 * 4 * H) : nullptr;
-        auto product = [&](int64_t M, int64_t Nn, int64_t K, const float* A, int64_t sa_m, int64_t sa_k, const float* B,
-                           int64_t sb_k, int64_t sb_n, float* C, int64_t ldc) {
-            if (h3 && gemm_h3_ok(M, Nn, K, A, sa_m, sa_k, B, sb_k, sb_n))
-                return gemm_h3(&sub, M, Nn, K, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, nullptr, 0, amax, st);
-            return gemm_f32(&sub, M, Nn, K, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, nullptr, 0, st);
-        };
-        if (!done) {
-            // a narrow input (layer 1: obs + trend, I <= 8): dW_ih = dG^T x rides on the bias gradient's pass over dG
-            const bool narrow = I <= 8 && (reinterpret_cast<uintptr_t>(dgates) & 15) == 0;
-            if (narrow) rc = colsum_xw(&sub, dgates, NT, 4 * H, x, I, db, dw_ih, red, amax, st);
-            else rc = colsum_absmax(&sub, dgates, NT, 4 * H, db, red, amax, st);
-            if (rc) return rc;
-            if (db_hh) UAV_CHECK_HIP(hipMemcpyAsync(db_hh, db, (size_t)4 * H * sizeof(float), hipMemcpyDeviceToDevice, st));
-            if ((rc = product(4 * H, H, NT, dgates, 1, 4 * H, hprev, ld_hprev, 1, dw_hh, H))) return rc;
-            if (!narrow && (rc = product(4 * H, I, NT, dgates, 1, 4 * H, x, I, 1, dw_ih, I))) return rc;
-        }
-        if (dheads) {        // dW_head = dheads^T y [n_heads][H]: a stream over y with the few dheads columns riding along
-            if (H % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)
-                rc = colsum_xw(&sub, y, NT, H, dheads, n_heads, nullptr, dw_head, red, nullptr, st, 1);
-            else
-                rc = gemm_f32(&sub, n_heads, H, NT, dheads, 1, n_heads, y, H, 1, dw_head, H, nullptr, 0, st);
-            if (rc) return rc;
-        }
-        if (dx) return product(NT, I, 4 * H, dgates, 4 * H, 1, w_ih, I, 1, dx, I);
-        return 0;
-    }
-    if (dx) return gemm_f32(ctx, NT, I, 4 * H, dgates, 4 * H, 1, w_ih, I, 1, dx, I, nullptr, 0, st);
-    return 0;
-}
-
-}  // extern "C"

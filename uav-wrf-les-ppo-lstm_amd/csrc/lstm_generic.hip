@@ -7,12 +7,12 @@
 //                         workgroup a 64 units x 64 envs tile, operands straight from L2 into registers, no LDS, no barrier;
 //                         step_bwd_h3_kernel  = dh_{t-1} = dG_t W_hh the same way, dG block-scaled per env by a power of
 //                         two (cell_bwd_h3_kernel); since round 5 those pieces are KEPT for all steps and are what uav_lstm_wgrad
-//                         consumes (common.h: DgPack, wgrad_pc.hip) -- no f32 dG rows, no h_prev slot in the stash.
+//                         consumes (lstm_forms.h: DgPack, wgrad_pc.hip) -- no f32 dG rows, no h_prev slot in the stash.
 //                         The launch boundary IS the cross-CU exchange of h_t (1.5-2 us): cheaper than any in-kernel
 //                         flag hand-off of 16 KB per CU and step (MI355X_MICROARCH.md price list: 4+ us).
 //   any other H:          gemm.hip's exact-f32 GEMM + a pointwise kernel per step (UAV_LSTM_F32_MFMA=1 forces this path).
 // Same stash layout and semantics as lstm.hip (gates i,f,g,o | c_prev | h_prev per (n,t)).
-#include "common.h"
+#include "internal.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -23,10 +23,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define STEP_ABL 0      // ablation builds of the step kernels only (tools/ab_step_fwd.sh): step_fwd_h3_kernel 1 no MFMAs, 2 no recurrent loads,
 #endif                  // 3 no epilogue, 4 each wave loads ONE of the four B column tiles (what sharing B through LDS would leave on the L1
                         // path); 5 step_bwd_h3_kernel: each wave loads one of its two A and one of its two B tiles (the same question)
-
-int gemm_f32(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k,
-             const float* B, int64_t sb_k, int64_t sb_n, float* C, int64_t ldc, const float* bias,
-             int accumulate, hipStream_t st);
 
 // state <- init * keep[:,0]
 __global__ void gen_init_state(const float* __restrict__ h0, const float* __restrict__ c0, const float* __restrict__ keep,
@@ -489,7 +485,7 @@ __global__ void add2v_kernel(const float* a0, const float* a1, float* b, int n) 
 // Gate gradients of step t (gen_cell_bwd's arithmetic).  One WAVE per env (H = 256: lane l owns units 4 l .. 4 l + 3):
 // the row as two fp16 planes in MFMA fragment order, scaled by the power of two that puts the row's largest magnitude in
 // [2^13, 2^14) (gradients span dozens of binades; scaled back exactly by step_bwd_h3_kernel) -- for the recurrent product AND,
-// kept for all steps (common.h: DgPack), for the weight-gradient pass.  dgates != NULL (UAV_DEBUG_DG_F32, the round-4 form kept
+// kept for all steps (lstm_forms.h: DgPack), for the weight-gradient pass.  dgates != NULL (UAV_DEBUG_DG_F32, the round-4 form kept
 // as an A/B switch): the pieces are one step's scratch and the weight-gradient pass gets f32 rows [n][t][4H] as well.
 // A workgroup = the 16 envs of one fragment row tile (16 waves): every wave parks its row's pieces in LDS and the workgroup
 // then writes the tile's 64 KB of piece chunks as ONE linear block -- lanes writing their own 8 bytes straight to the
@@ -766,7 +762,7 @@ static bool h3_step_ok(int H) {
     return H == 256 && !uav_want_f32_mfma() && !uav_want_bf16x6() && !uav_debug(UAV_DEBUG_STEP_F32);
 }
 
-// the gate gradients stay in the packed form only (common.h: DgPack) unless the A/B switch asks for the round-4 f32 rows too
+// the gate gradients stay in the packed form only (lstm_forms.h: DgPack) unless the A/B switch asks for the round-4 f32 rows too
 static bool h3_dg_packed(int H) { return h3_step_ok(H) && !uav_debug(UAV_DEBUG_DG_F32); }
 bool lstm_h3_dg_packed(int H) { return h3_dg_packed(H); }
 
@@ -890,42 +886,45 @@ int uav_lstm_stepper_begin(uav_ctx* ctx, void* state, const float* w_ih, const f
     return 0;
 }
 
-// the stepper writes a stash one step at a time: its h_prev slot counts as written only if every step since step 0 wrote it
-static void stepper_hslot_record(uav_ctx* ctx, const float* stash, int t, int hslot) {
-    ctx->hslot_form.record(stash, t > 0 && ctx->hslot_form.find(stash) == 0 ? 0 : hslot);
+// the arguments of one stepper step, checked in the name of the entry point `who`
+static int stepper_args(const char* who, const uav_stepper_call& c, int N, int T, int H, StepFwdArgs& A, int& IPS) {
+    UAV_REQUIRE(c.state && c.x && c.y && c.stash && c.hn && c.cn, "%s: NULL argument", who);
+    UAV_REQUIRE(uav_lstm_stepper_bytes(N, c.I, H) != 0 && T > 0 && c.t >= 0 && c.t < T, "%s: bad shape (N=%d T=%d t=%d I=%d H=%d)", who, N, T, c.t, c.I, H);
+    UAV_REQUIRE(h3_step_ok(H), "%s: only the fp16-split arithmetic steps (uav_set_lstm_arith)", who);
+    const StepperLayout L = stepper_layout(N, c.I);
+    char* b = (char*)c.state;
+    unsigned short* hp0 = (unsigned short*)(b + L.hp0);
+    unsigned short* hp1 = (unsigned short*)(b + L.hp1);
+    // `below`: the stepper state of the layer below (same N, its H = this I = 256), already stepped to t: its piece
+    // planes of h_t (parity (t + 1) & 1, not yet masked) ARE this layer's input in fragment order
+    const unsigned short* xp = nullptr;
+    if (c.below) {
+        UAV_REQUIRE(c.I == 256, "%s: `below` needs I = 256 (the layer below's hidden size), got %d", who, c.I);
+        const StepperLayout LB = stepper_layout(N, 8);        // hp0 / hp1 offsets do not depend on the input width
+        xp = (const unsigned short*)((const char*)c.below + (((c.t + 1) & 1) ? LB.hp1 : LB.hp0));
+    }
+    A = StepFwdArgs{(const unsigned short*)(b + L.wxp), (const unsigned short*)(b + L.wp), (const float*)(b + L.bsum), c.x, c.I, xp, 1,
+                    (c.t & 1) ? hp1 : hp0, (c.t & 1) ? hp0 : hp1, (float*)(b + L.hs), (float*)(b + L.cs), c.stash, c.keep_t, (int64_t)1,
+                    (int64_t)0, N, T, c.t, c.y, c.hn, c.cn, h3_dg_packed(H) ? 0 : 1};
+    IPS = L.IP / 32;
+    return 0;
 }
 
 int uav_lstm_stepper_step(uav_ctx* ctx, void* state, const float* x, const void* below, const float* keep_t, int N, int T, int t,
                           int I, int H, float* y, float* stash, float* hn, float* cn, uav_stream stream) {
-    UAV_REQUIRE(ctx && state && x && y && stash && hn && cn, "uav_lstm_stepper_step: NULL argument");
-    UAV_REQUIRE(uav_lstm_stepper_bytes(N, I, H) != 0 && T > 0 && t >= 0 && t < T, "uav_lstm_stepper_step: bad shape (N=%d T=%d t=%d I=%d H=%d)", N, T, t, I, H);
+    UAV_REQUIRE(ctx, "uav_lstm_stepper_step: NULL argument");
     uav_enter(ctx);
-    UAV_REQUIRE(h3_step_ok(H), "uav_lstm_stepper_step: only the fp16-split arithmetic steps (uav_set_lstm_arith)");
-    const StepperLayout L = stepper_layout(N, I);
-    char* b = (char*)state;
-    hipStream_t st = as_stream(stream);
-    const unsigned short* wxp = (const unsigned short*)(b + L.wxp);
-    const unsigned short* wp = (const unsigned short*)(b + L.wp);
-    const float* bsum = (const float*)(b + L.bsum);
-    unsigned short* hp0 = (unsigned short*)(b + L.hp0);
-    unsigned short* hp1 = (unsigned short*)(b + L.hp1);
-    float* hs = (float*)(b + L.hs);
-    float* cs = (float*)(b + L.cs);
+    const uav_stepper_call c{state, x, below, keep_t, t, I, y, stash, hn, cn};
+    StepFwdArgs A;
+    int IPS, rc;
+    if ((rc = stepper_args("uav_lstm_stepper_step", c, N, T, H, A, IPS))) return rc;
+    ctx->forms.stash_step(stash, t, A.hslot);
     const dim3 grid((N + 63) / 64, 256 / 64);
-    const int hslot = h3_dg_packed(H) ? 0 : 1;
-    stepper_hslot_record(ctx, stash, t, hslot);
-    // `below`: the stepper state of the layer below (same N, its H = this I = 256), already stepped to t: its piece
-    // planes of h_t (parity (t + 1) & 1, not yet masked) ARE this layer's input in fragment order
-    const unsigned short* xp = nullptr;
-    if (below) {
-        UAV_REQUIRE(I == 256, "uav_lstm_stepper_step: `below` needs I = 256 (the layer below's hidden size), got %d", I);
-        const StepperLayout LB = stepper_layout(N, 8);        // hp0 / hp1 offsets do not depend on the input width
-        xp = (const unsigned short*)((const char*)below + (((t + 1) & 1) ? LB.hp1 : LB.hp0));
-    }
-#define LAUNCH_STEP(IPS_)                                                                                                     \
-    hipLaunchKernelGGL((step_fwd_h3_kernel<256, IPS_>), grid, dim3(256), 0, st, wxp, wp, bsum, x, I, xp, 1, (t & 1) ? hp1 : hp0, \
-                       (t & 1) ? hp0 : hp1, hs, cs, stash, keep_t, (int64_t)1, (int64_t)0, N, T, t, y, hn, cn, hslot)
-    switch (L.IP / 32) {
+    hipStream_t st = as_stream(stream);
+#define LAUNCH_STEP(IPS_)                                                                                                      \
+    hipLaunchKernelGGL((step_fwd_h3_kernel<256, IPS_>), grid, dim3(256), 0, st, A.wxp, A.wp, A.bsum, A.x, A.I, A.xp, A.last_pieces, \
+                       A.hp_in, A.hp_out, A.hs, A.cs, A.stash, A.keep, A.keep_sn, A.keep_off, A.N, A.T, A.t, A.y, A.hn, A.cn, A.hslot)
+    switch (IPS) {
         case 1: LAUNCH_STEP(1); break;
         case 2: LAUNCH_STEP(2); break;
         case 4: LAUNCH_STEP(4); break;
@@ -936,27 +935,6 @@ int uav_lstm_stepper_step(uav_ctx* ctx, void* state, const float* x, const void*
     return 0;
 }
 
-// the arguments of one stepper step, as uav_lstm_stepper_step forms them
-static int stepper_args(const uav_stepper_call& c, int N, int T, int H, StepFwdArgs& A, int& IPS) {
-    UAV_REQUIRE(c.state && c.x && c.y && c.stash && c.hn && c.cn, "uav_lstm_stepper_step_pair: NULL argument");
-    UAV_REQUIRE(uav_lstm_stepper_bytes(N, c.I, H) != 0 && T > 0 && c.t >= 0 && c.t < T, "uav_lstm_stepper_step_pair: bad shape (N=%d T=%d t=%d I=%d H=%d)", N, T, c.t, c.I, H);
-    const StepperLayout L = stepper_layout(N, c.I);
-    char* b = (char*)c.state;
-    unsigned short* hp0 = (unsigned short*)(b + L.hp0);
-    unsigned short* hp1 = (unsigned short*)(b + L.hp1);
-    const unsigned short* xp = nullptr;
-    if (c.below) {
-        UAV_REQUIRE(c.I == 256, "uav_lstm_stepper_step_pair: `below` needs I = 256, got %d", c.I);
-        const StepperLayout LB = stepper_layout(N, 8);
-        xp = (const unsigned short*)((const char*)c.below + (((c.t + 1) & 1) ? LB.hp1 : LB.hp0));
-    }
-    A = StepFwdArgs{(const unsigned short*)(b + L.wxp), (const unsigned short*)(b + L.wp), (const float*)(b + L.bsum), c.x, c.I, xp, 1,
-                    (c.t & 1) ? hp1 : hp0, (c.t & 1) ? hp0 : hp1, (float*)(b + L.hs), (float*)(b + L.cs), c.stash, c.keep_t, (int64_t)1,
-                    (int64_t)0, N, T, c.t, c.y, c.hn, c.cn, h3_dg_packed(H) ? 0 : 1};
-    IPS = L.IP / 32;
-    return 0;
-}
-
 int uav_lstm_stepper_step_pair(uav_ctx* ctx, const uav_stepper_call* a, const uav_stepper_call* b, int N, int T, int H,
                                uav_stream stream) {
     UAV_REQUIRE(ctx && a && b, "uav_lstm_stepper_step_pair: NULL argument");
@@ -964,9 +942,10 @@ int uav_lstm_stepper_step_pair(uav_ctx* ctx, const uav_stepper_call* a, const ua
     UAV_REQUIRE(h3_step_ok(H), "uav_lstm_stepper_step_pair: only the fp16-split arithmetic steps (uav_set_lstm_arith)");
     StepFwdArgs A, B;
     int ia, ib, rc;
-    if ((rc = stepper_args(*a, N, T, H, A, ia)) || (rc = stepper_args(*b, N, T, H, B, ib))) return rc;
-    stepper_hslot_record(ctx, a->stash, a->t, A.hslot);
-    stepper_hslot_record(ctx, b->stash, b->t, B.hslot);
+    if ((rc = stepper_args("uav_lstm_stepper_step_pair", *a, N, T, H, A, ia)) || (rc = stepper_args("uav_lstm_stepper_step_pair", *b, N, T, H, B, ib)))
+        return rc;
+    ctx->forms.stash_step(a->stash, a->t, A.hslot);
+    ctx->forms.stash_step(b->stash, b->t, B.hslot);
     hipStream_t st = as_stream(stream);
     if (ia == 1 && ib == 8) {                 // (layer 1 of a narrow input, layer 2 on the layer below's planes): the one instantiated pair
         hipLaunchKernelGGL((step_fwd_h3_pair_kernel<256, 1, 8>), dim3((N + 63) / 64, 256 / 64, 2), dim3(256), 0, st, A, B);
@@ -1053,7 +1032,6 @@ static int lstm_h3_bwd(uav_ctx* ctx, const float* keep, const float* stash, cons
     int rc;
     if ((rc = h3_bwd_attr())) return rc;
     H3Bwd L{keep, stash, dy, dheads, w_head, n_heads, N, T, dgates, dx, h3_dg_packed(H3Bwd::H)};
-    uav_dg_record(ctx, dgates, L.packed);
     if ((rc = L.prepare((char*)ctx->ws + ctx->ws_bytes - need, w_hh, w_ih, dhn, dcn, st))) return rc;
     for (int t = T - 1; t >= 0; --t) L.step(t, st);
     L.finish(dh0, dc0, st);
@@ -1100,7 +1078,6 @@ int lstm_h3_bwd_stack(uav_ctx* ctx, int nl, const uav_lstm_bwd_layer* layers, co
         const uav_lstm_bwd_layer& a = layers[l];
         L[l] = H3Bwd{a.keep, a.stash, l == 0 ? dy : layers[l - 1].dx, l == 0 ? dheads : nullptr, l == 0 ? w_head : nullptr,
                      l == 0 ? n_heads : 0, N, T, a.dgates, a.dx, h3_dg_packed(H3Bwd::H)};
-        uav_dg_record(ctx, a.dgates, L[l].packed);
         if ((rc = L[l].prepare((char*)ctx->ws + ctx->ws_bytes - (size_t)(l + 1) * need, a.w_hh, a.w_ih, a.dhn, a.dcn, str[l]))) {
             (void)join();
             return rc;
@@ -1165,7 +1142,6 @@ int lstm_generic_bwd(uav_ctx* ctx, const float* keep, const float* stash, const 
     if (h3_step_ok(H)) return lstm_h3_bwd(ctx, keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, dgates, dh0, dc0, w_ih, dx, st);
     const int64_t NH = (int64_t)N * H;
     UAV_REQUIRE((size_t)(2 * NH) * sizeof(float) + (64u << 20) <= ctx->ws_bytes, "lstm (generic): workspace too small");
-    uav_dg_record(ctx, dgates, 0);
     float* dh = (float*)((char*)ctx->ws + ctx->ws_bytes) - 2 * NH;
     float* dc = dh + NH;
     uav_ctx sub = *ctx;

@@ -7,11 +7,7 @@
 // column reductions.  Flat parameter layout (heads contiguous so actor|critic is ONE GEMM):
 //   W1[h1][in] b1[h1] g1[h1] be1[h1] W2[h2][h1] b2[h2] g2[h2] be2[h2] Wh[A+1][h2] bh[A+1]
 // Stash (consumed by the backward): xhat1[B][h1] a1[B][h1] xhat2[B][h2] a2[B][h2] rstd1[B] rstd2[B].
-#include "common.h"
-
-int gemm_f32(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k,
-             const float* B, int64_t sb_k, int64_t sb_n, float* C, int64_t ldc, const float* bias,
-             int accumulate, hipStream_t st);
+#include "internal.h"
 
 constexpr float LN_EPS = 1e-5f;
 
@@ -271,7 +267,7 @@ __global__ __launch_bounds__(256) void colsum_xw_reduce_kernel(const float* __re
 // colsum of X [B][C] (colsum_out may be NULL) + X^T x for x [B][I] (or x^T X with xw_transposed), I <= 8, C % 4 == 0,
 // X 16-byte aligned; scratch >= 1024 * 9 * C floats
 int colsum_xw(uav_ctx* ctx, const float* X, int64_t B, int C, const float* x, int I, float* colsum_out, float* xw_out,
-              float* scratch, unsigned* absmax_bits, hipStream_t st, int xw_transposed = 0) {
+              float* scratch, unsigned* absmax_bits, hipStream_t st, int xw_transposed) {
     UAV_REQUIRE(I >= 1 && I <= 8 && C % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0, "colsum_xw: I <= 8, cols %% 4 == 0, aligned X");
     int nb = (int)((B + 255) / 256);
     if (nb > 1024) nb = 1024;
@@ -285,8 +281,6 @@ int colsum_xw(uav_ctx* ctx, const float* X, int64_t B, int C, const float* x, in
     return 0;
 }
 
-int colsum_absmax(uav_ctx* ctx, const float* X, int64_t B, int C, float* out, float* scratch, unsigned* absmax_bits,
-                  hipStream_t st);
 int colsum(uav_ctx* ctx, const float* X, int64_t B, int C, float* out, float* scratch, hipStream_t st) {
     return colsum_absmax(ctx, X, B, C, out, scratch, nullptr, st);
 }

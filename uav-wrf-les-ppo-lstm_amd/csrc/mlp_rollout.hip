@@ -3,12 +3,9 @@
 // step -> store for 16 environments per workgroup and keeps every activation on chip.  Its GREEDY forms are the evaluation
 // episodes (argmax, no auto-reset), with or without the stop rule.  The forward is mlp_tile_core.h's, shared with the update
 // kernel (mlp_update.hip): the log-probabilities stored here are bit-identical to that kernel's first forward pass.
-#include "env_core.h"
+#include "internal_env.h"
 #include "loss_core.h"
 #include "mlp_tile_core.h"
-#include "stop_rule_core.h"
-
-int env_params_from_cfg(const uav_ctx* ctx, const uav_env_cfg* cfg, int n_env, EnvParams& P);
 
 namespace {
 

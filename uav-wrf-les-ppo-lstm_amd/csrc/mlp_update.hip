@@ -8,12 +8,9 @@
 // the 16 forms (profiles/mlp_split_static_table.md).
 #include <type_traits>
 
+#include "internal.h"
 #include "loss_core.h"
 #include "mlp_tile_core.h"
-
-int launch_loss_final(double* partial, int nb, int n_heads, double* loss_sums, float* dhead_bias, hipStream_t st);
-int launch_diag_final(double* partial, int nb, double* diag, hipStream_t st);
-int launch_bc_final(double* partial, int nb, int n_heads, double* bc_sums, float* dhead_bias, hipStream_t st);
 
 #ifdef UAV_X6_PROFILE
 // phase timing (instrumented build only, tools/build_prof.sh): cycles per phase summed over the tiles of workgroup 0,

@@ -18,25 +18,11 @@
 //  in every wave: 1.9 ms vs 1.2 ms.  The env role stays on wave 0.)
 // Procedural fields make the whole rollout HBM-write-only apart from the policy parameters:
 // 44 B per env-step (obs 24, act 4, rew 4, val 4, logp 4, done 4) + 5 B (keep, flags).
-#include "env_core.h"
+#include "internal_env.h"
 #include "loss_core.h"
 #include "rows_dot_core.h"
-#include "stop_rule_core.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-int env_params_from_cfg(const uav_ctx* ctx, const uav_env_cfg* cfg, int n_env, EnvParams& P);
-int launch_rollout_mlp(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg* cfg, const float* params, int horizon,
-                       uint64_t iter, float* cur_obs, float* obs, int32_t* act, float* rew, float* val, float* logp,
-                       float* done, uint8_t* flags, float* last_val, const int32_t* forced_act, const double* noise,
-                       int32_t* nan_count, float* info, float* heads, bool trend, hipStream_t st);
-int launch_greedy_mlp(const EnvParams& P, void* env_state, int n_env, const float* params, int steps, float* cur_obs,
-                      uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
-                      int32_t* nan_count, hipStream_t st);
-int launch_greedy_mlp_stop(const EnvParams& P, void* env_state, int n_env, const float* params, int steps, float* cur_obs,
-                           uint8_t* active, const double* noise, int32_t* act, float* obs, float* pos, uint8_t* flags,
-                           int32_t* nan_count, const StopRule& rule, float* stop_win, int32_t* stop_cnt, float* rule_val,
-                           hipStream_t st);
 
 constexpr int RMT = 16;
 

@@ -15,7 +15,7 @@
 // in a fixed order (deterministic, no float atomics).
 #include <stdlib.h>
 #include <type_traits>
-#include "common.h"
+#include "internal.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -380,7 +380,7 @@ __device__ __forceinline__ void lstm_wgrad_split(
     // wave-uniform and stays scalar; what depends on the lane is fixed for the whole kernel and formed here, once.
     // The launch checks N*T*4H < 2^30, so every byte offset fits 32 bits.
     auto slab_row = [&](int slab) { return r_begin + (slab < nslab ? slab : nslab - 1) * KS6; };
-    // TILE: dgates is in tile form (common.h: DgTile).  K is walked exactly as over f32 rows -- env n's steps, then env n + 1's --
+    // TILE: dgates is in tile form (lstm_forms.h: DgTile).  K is walked exactly as over f32 rows -- env n's steps, then env n + 1's --
     // only where a row lies differs: T is a multiple of the slab, so a slab's 32 rows are steps t0 .. t0 + 31 of ONE env, and
     // consecutive steps lie DgTile::MT rows apart.  That stride is past the immediate field, so each row has a uniform part of
     // its own; the lane part stays fixed.  The launch checks that the padded buffer's byte offsets fit 32 bits.
@@ -610,7 +610,7 @@ __global__ __launch_bounds__(H * 4) void lstm_wgrad_h3_kernel(
     lstm_wgrad_split<H, HEADS, WgF16x3>(dgates, y, keep, h0, x, I, dheads, NH, N, T, rows_per_block, slabs);
 }
 
-// the same two kernels reading dgates in tile form (common.h: DgTile); a kernel trace still finds them by the names above as prefixes
+// the same two kernels reading dgates in tile form (lstm_forms.h: DgTile); a kernel trace still finds them by the names above as prefixes
 template <int H, bool HEADS>
 __global__ __launch_bounds__(H * 4) void lstm_wgrad_x6_kernel_tile(
     const float* __restrict__ dgates, const float* __restrict__ y, const float* __restrict__ keep,
@@ -728,7 +728,7 @@ static int launch_wgrad(uav_ctx* ctx, const float* dgates, bool tile, const floa
     return 0;
 }
 
-// Why a gate-gradient buffer of this shape cannot be in tile form (common.h: DgTile), or NULL when it can: the split kernels must
+// Why a gate-gradient buffer of this shape cannot be in tile form (lstm_forms.h: DgTile), or NULL when it can: the split kernels must
 // take the shape with or without heads, T must be a multiple of their 32-row slab (a workgroup's rows start on a multiple of 32,
 // so then no slab straddles two envs), and the byte offsets into the buffer, padded to whole tiles, must fit the kernels' 32 bits.
 const char* lstm_wgrad_tile_refusal(const uav_ctx* ctx, int N, int T, int I, int H) {
@@ -741,7 +741,7 @@ const char* lstm_wgrad_tile_refusal(const uav_ctx* ctx, int N, int T, int I, int
     return ok ? nullptr : "the split weight-gradient kernels do not take this shape (N * T rows in whole 32-row slabs per workgroup)";
 }
 
-// fast path entry used by uav_lstm_wgrad (lstm.hip) when I <= 6 and H in {64,128}
+// fast path entry used by uav_lstm_wgrad (lstm_api.hip) when I <= 6 and H in {64,128}
 int lstm_wgrad_fused(uav_ctx* ctx, const float* dgates, const float* y, const float* keep, const float* h0,
                      const float* x, int I, const float* dheads, int NH, int N, int T, int H,
                      float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, bool tile, hipStream_t st) {

@@ -22,7 +22,7 @@
 //                       * B: f32 rows -> registers (two slabs ahead) -> split -> LDS piece planes, as gemm_h3_tn8_kernel.
 //                       Split-K over contiguous slab ranges, all tiles of a range on one XCD; deterministic slab reduce.
 // Results differ from the round-4 path (f32 rows through gemm_h3_tn8_kernel) only in where the power-of-two scale is applied.
-#include "common.h"
+#include "internal.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 

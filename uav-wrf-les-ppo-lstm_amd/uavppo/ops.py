@@ -3,7 +3,9 @@ into libuavppo.so on torch's current HIP stream.  PyTorch only supplies device m
 streams here; every number is produced by the hand-written HIP kernels."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import types
 
 import torch
 
@@ -908,6 +910,24 @@ def _arm_tile(dgates, N, T, I, H):
     check(lib().uav_lstm_dgates_tile(_h(dgates), _p(dgates, F32, None, "dgates"), N, T, I, H), "uav_lstm_dgates_tile")
 
 
+@contextlib.contextmanager
+def _tile_request(dgates, mode, N, T, I, H):
+    """lstm_bwd's dgates_tile in one place: arm the buffer; if uav_lstm_bwd refuses (`written` still unset), forget it -- a refused
+    call leaves the buffer as it was, f32 rows to whoever uses it next; and once the weight gradients are formed, forget a
+    "transient" request (a work buffer nobody reads afterwards).  mode False: nothing at all."""
+    request = types.SimpleNamespace(written=False)
+    if mode:
+        _arm_tile(dgates, N, T, I, H)
+    try:
+        yield request
+    except Exception:
+        if mode and not request.written:
+            lstm_dgates_forget(dgates)
+        raise
+    if mode == "transient":
+        lstm_dgates_forget(dgates)
+
+
 def lstm_wgrad(x, keep, h0, y, stash, dgates, w_ih, dheads=None):
     """The weight-gradient pass alone, from given gate gradients: dW_ih, dW_hh, db (and dW_head = dheads^T y)."""
     N, T, I = x.shape
@@ -985,13 +1005,11 @@ def lstm_bwd(x, keep, stash, w_ih, w_hh, y, h0, dy=None, dheads=None, w_head=Non
         dw_head = torch.empty(nhw, H, dtype=F32, device=dev)
     # the h = 256 step path forms dx = dG W_ih inside its per-step recurrent product (same dG fragments) when I == H
     dx_in_bwd = bool(need_dx and lstm_bwd_caps(x.device, I, H) & 1) or bwd_done
-    if dgates_tile:
-        if bwd_done or need_dx:
-            raise RuntimeError("lstm_bwd: dgates_tile is for one uav_lstm_bwd + uav_lstm_wgrad pair without dx")
-        _arm_tile(dgates, N, T, I, H)
-    _t = None if bwd_done else KERNEL_TIMER.bracket("lstm_bwd")
-    if not bwd_done:
-        try:
+    if dgates_tile and (bwd_done or need_dx):
+        raise RuntimeError("lstm_bwd: dgates_tile is for one uav_lstm_bwd + uav_lstm_wgrad pair without dx")
+    with _tile_request(dgates, dgates_tile, N, T, I, H) as request:
+        _t = None if bwd_done else KERNEL_TIMER.bracket("lstm_bwd")
+        if not bwd_done:
             check(lib().uav_lstm_bwd(_h(x), _p(keep, F32, (N, T), "keep"), _p(stash, F32, (N, T, 6 * H), "stash"),
                                      _p(w_hh, F32, (4 * H, H), "w_hh"), _p(dy, F32, (N, T, H), "dy"),
                                      _p(dheads, F32, (N, T, nh), "dheads"), _p(w_head, F32, (nh, H), "w_head"), nh,
@@ -999,25 +1017,20 @@ def lstm_bwd(x, keep, stash, w_ih, w_hh, y, h0, dy=None, dheads=None, w_head=Non
                                      _pdg(dgates, N, T, H), _p(dh0), _p(dc0),
                                      _p(w_ih, F32, (4 * H, I), "w_ih") if dx_in_bwd else None, I, _p(dx) if dx_in_bwd else None,
                                      _stream()), "uav_lstm_bwd")
-        except Exception:
-            if dgates_tile:
-                lstm_dgates_forget(dgates)      # a refused call leaves the buffer as it was: f32 rows to whoever uses it next
-            raise
-    if _t is not None:
-        _t.record()
-    _t = KERNEL_TIMER.bracket("lstm_wgrad")
-    check(lib().uav_lstm_wgrad(_h(x), _p(x, F32, (N, T, I), "x"), _p(keep, F32, (N, T), "keep"), _p(h0, F32, (N, H), "h0"),
-                               _p(y, F32, (N, T, H), "y"), _p(stash, F32, (N, T, 6 * H), "stash"),
-                               _pdg(dgates, N, T, H), _p(w_ih, F32, (4 * H, I), "w_ih"),
-                               _p(wgrad_dheads, F32, (N, T, nhw), "dheads"), nhw, N, T, I, H,
-                               _p(dw_ih, F32, (4 * H, I), "dw_ih"), _p(dw_hh, F32, (4 * H, H), "dw_hh"),
-                               _p(db, F32, (4 * H,), "db"), _p(db_hh, F32, (4 * H,), "db_hh"), _p(dw_head, F32, (nhw, H), "dw_head"),
-                               None if dx_in_bwd else _p(dx), _stream()),
-          "uav_lstm_wgrad")
-    if _t is not None:
-        _t.record()
-    if dgates_tile == "transient":
-        lstm_dgates_forget(dgates)
+        request.written = True
+        if _t is not None:
+            _t.record()
+        _t = KERNEL_TIMER.bracket("lstm_wgrad")
+        check(lib().uav_lstm_wgrad(_h(x), _p(x, F32, (N, T, I), "x"), _p(keep, F32, (N, T), "keep"), _p(h0, F32, (N, H), "h0"),
+                                   _p(y, F32, (N, T, H), "y"), _p(stash, F32, (N, T, 6 * H), "stash"),
+                                   _pdg(dgates, N, T, H), _p(w_ih, F32, (4 * H, I), "w_ih"),
+                                   _p(wgrad_dheads, F32, (N, T, nhw), "dheads"), nhw, N, T, I, H,
+                                   _p(dw_ih, F32, (4 * H, I), "dw_ih"), _p(dw_hh, F32, (4 * H, H), "dw_hh"),
+                                   _p(db, F32, (4 * H,), "db"), _p(db_hh, F32, (4 * H,), "db_hh"), _p(dw_head, F32, (nhw, H), "dw_head"),
+                                   None if dx_in_bwd else _p(dx), _stream()),
+              "uav_lstm_wgrad")
+        if _t is not None:
+            _t.record()
     return {"dx": dx, "dw_ih": dw_ih, "dw_hh": dw_hh, "db": db, "dh0": dh0, "dc0": dc0, "dgates": dgates,
             "dw_head": dw_head}
 

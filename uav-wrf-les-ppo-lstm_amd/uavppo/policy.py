@@ -129,6 +129,7 @@ class LSTMActorCritic(_FlatPolicy):
         self.views["head.weight"][A:].copy_(_orthogonal((1, H), 1.0, gen))
         self.views["head.bias"].zero_()
         self._saved = None
+        self.dgates_tile = False     # set by the owner of backward()'s `work` buffers (VecPPOTrainer._request_dgates_tile)
 
     def _named(self, src):
         A = self.n_act
@@ -348,7 +349,7 @@ class LSTMActorCritic(_FlatPolicy):
         # the owner of `work` asked for its gate gradients in tile form (VecPPOTrainer._request_dgates_tile): per call, and only
         # while the buffer it allocated for that holds this call's shape -- any other call keeps f32 rows
         tile = False
-        if getattr(self, "dgates_tile", False) and L == 1 and fused_heads and work.get("dgates") is not None:
+        if self.dgates_tile and L == 1 and fused_heads and work.get("dgates") is not None:
             need = ops.lstm_dgates_tile_bytes(N, T, self.obs_dim, H, dheads.device)
             tile = "transient" if 0 < need <= work["dgates"].numel() * 4 else False
         for l in reversed(range(self.num_layers)):

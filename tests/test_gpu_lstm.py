@@ -399,11 +399,10 @@ def test_lstm_stepper_equals_sequence_forward(ops, N, T, I):
     assert torch.equal(y[:, 0], y2_ref[:, 0]) and _stash_equal(stash[:, 0], st2_ref[:, 0])
 
 
-def test_stepper_step_pair_equals_the_two_steps(ops):
-    """uav_lstm_stepper_step_pair: layer 1's step t + 1 and layer 2's step t (reading layer 1's piece planes of step t) as ONE launch --
-    the update's forward pass over a stored sequence (uavppo/policy.py) -- gives the bits of the layer-by-layer stepper loop: y, the
-    BPTT stash, final states, for a ragged env count and with restart masks."""
-    H, N, T, I = 256, 100, 7, 8
+def _pair_equals_the_two_steps(ops, N, T, I):
+    """a two-layer h = 256 stack through the steppers, layer 2 on layer 1's piece planes: with uav_lstm_stepper_step_pair against layer by
+    layer -- every output of both layers bit for bit"""
+    H = 256
     g = torch.Generator().manual_seed(5)
     mk = lambda *shape, s=0.1: (torch.randn(*shape, generator=g) * s).to(DEV)
     x = mk(N, T, I, s=1.0)
@@ -433,6 +432,20 @@ def test_stepper_step_pair_equals_the_two_steps(ops):
     for l in range(2):
         assert torch.equal(a[0][l], b[0][l]) and _stash_equal(a[1][l], b[1][l]), l
         assert torch.equal(a[2][l], b[2][l]) and torch.equal(a[3][l], b[3][l]), l
+
+
+def test_stepper_step_pair_equals_the_two_steps(ops):
+    """uav_lstm_stepper_step_pair: layer 1's step t + 1 and layer 2's step t (reading layer 1's piece planes of step t) as ONE launch --
+    the update's forward pass over a stored sequence (uavppo/policy.py) -- gives the bits of the layer-by-layer stepper loop: y, the
+    BPTT stash, final states, for a ragged env count and with restart masks."""
+    _pair_equals_the_two_steps(ops, N=100, T=7, I=8)
+
+
+def test_stepper_step_pair_of_other_widths_equals_the_two_steps(ops):
+    """Only the (1, 8) pair of input slab counts is instantiated as one kernel.  A first layer of I = 40 (two slabs) takes the pair
+    call's other branch: the two checked steps launched one after the other -- same bits as the layer-by-layer loop, for a ragged
+    64-env tile (N = 37) and with restarts."""
+    _pair_equals_the_two_steps(ops, N=37, T=3, I=40)
 
 
 @pytest.mark.parametrize("mode", ["bf16x6", "f32_mfma"])

@@ -7,7 +7,7 @@
 //   k = 0    h0[n] keep[n][0]                  c0[n] keep[n][0]
 //   k > 0    y[n][t0 - 1] keep[n][t0]          stash[n][t0][4H:5H] keep[n][t0]      (the stash's c_prev slot)
 // The slot holds the cell state entering step t in every forward form that fills a stash -- the h = 64 / 128 sequence kernels
-// (lstm.hip: c_reg, masked by the step before), lstm_generic.hip's cell kernel (cs, masked), the h = 256 stepper (written
+// (lstm.hip: c_reg, masked by the step before), lstm_generic.hip's cell kernel (cs, masked), lstm_h3.hip's h = 256 step kernel (written
 // unmasked by step t - 1 and rewritten masked by step t where the env restarts) and uav_rollout's stash with and without the
 // trend channels (c_reg, zeroed by keep_fixup) -- and y holds the unmasked h_t in all of them; with keep in {0, 1} the
 // product here is the same number whether or not the slot was masked before.

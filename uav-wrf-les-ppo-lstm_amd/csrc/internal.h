@@ -26,20 +26,30 @@ int lstm_fwd_seq(bool fuse, const float* x, const float* keep, const float* h0, 
 int lstm_bwd_seq(const float* keep, const float* stash, const float* w_hh, const float* dy, const float* dheads, const float* w_head,
                  int NH, const float* dhn, const float* dcn, int N, int T, int H, float* dgates, bool tile, float* dh0, float* dc0,
                  hipStream_t st);
-// lstm_generic.hip: one launch per time step (h = 256 on the fp16 split; any other hidden size in exact f32)
-bool lstm_h3_step_path(int H);
-bool lstm_h3_stack_ok(int H);
-bool lstm_h3_dg_packed(int H);
-int lstm_generic_bwd_caps(int I, int H);
+// lstm_generic.hip: one GEMM + one pointwise launch per time step in exact f32, any hidden size
 int lstm_generic_fwd(uav_ctx* ctx, const float* keep, const float* h0, const float* c0, const float* w_hh, int N, int T, int H, float* y,
                      float* hn, float* cn, float* stash, hipStream_t st);
+int lstm_generic_bwd(uav_ctx* ctx, const float* keep, const float* stash, const float* w_hh, const float* dy, const float* dhn,
+                     const float* dcn, int N, int T, int H, float* dgates, float* dh0, float* dc0, hipStream_t st);
+void lstm_fill(float* x, const float* src, int64_t n, hipStream_t st);
+// lstm_h3.hip: h = 256 on the fp16 split, one fused launch per time step.  Under the mode uav_enter set: does the step path run
+// for this H, are its gate gradients kept packed (lstm_forms.h: DgPack), the UAV_BWD_* bits of its BPTT
+bool lstm_h3_step_path(int H);
+bool lstm_h3_dg_packed(int H);
+int lstm_h3_bwd_caps(int I, int H);
 int lstm_h3_fwd(uav_ctx* ctx, const float* x, int I, const float* w_ih, const float* b_ih, const float* b_hh, const float* keep,
                 const float* h0, const float* c0, const float* w_hh, int N, int T, float* y, float* hn, float* cn, float* stash, hipStream_t st);
-int lstm_generic_bwd(uav_ctx* ctx, const float* keep, const float* stash, const float* w_hh, const float* dy, const float* dheads,
-                     const float* w_head, int n_heads, const float* dhn, const float* dcn, int N, int T, int H, float* dgates, float* dh0,
-                     float* dc0, const float* w_ih, int I, float* dx, hipStream_t st);
+int lstm_h3_bwd(uav_ctx* ctx, const float* keep, const float* stash, const float* w_hh, const float* dy, const float* dheads,
+                const float* w_head, int n_heads, const float* dhn, const float* dcn, int N, int T, float* dgates, float* dh0,
+                float* dc0, const float* w_ih, float* dx, hipStream_t st);
 int lstm_h3_bwd_stack(uav_ctx* ctx, int nl, const uav_lstm_bwd_layer* layers, const float* dy, const float* dheads, const float* w_head,
                       int n_heads, int N, int T, hipStream_t st);
+// the stepper behind uav_lstm_stepper_* (H = 256, 0 < I <= 256, arguments and mode checked by the entry points)
+size_t lstm_h3_stepper_bytes(int N, int I);
+int lstm_h3_stepper_begin(void* state, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* h0,
+                          const float* c0, int N, int I, hipStream_t st);
+int lstm_h3_stepper_step(const uav_stepper_call& c, int N, int T, hipStream_t st);
+int lstm_h3_stepper_step_pair(const uav_stepper_call& a, const uav_stepper_call& b, int N, int T, hipStream_t st);
 // wgrad.hip, wgrad_pc.hip: the weight-gradient passes
 int lstm_wgrad_fused(uav_ctx* ctx, const float* dgates, const float* y, const float* keep, const float* h0, const float* x, int I,
                      const float* dheads, int NH, int N, int T, int H, float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head,

@@ -1,6 +1,6 @@
 // lstm_api.hip -- the C ABI of every LSTM path: argument checks, the choice of kernel family by hidden size and arithmetic mode
-// (lstm.hip: persistent h = 64 / 128; lstm_generic.hip: one launch per step; wgrad.hip / wgrad_pc.hip / gemm*.hip: weight
-// gradients), and what a `dgates` / `stash` buffer holds between two calls.  The forms are DECIDED in lstm_forms.h; this file asks
+// (lstm.hip: persistent h = 64 / 128; lstm_h3.hip: h = 256 on the fp16 split, one launch per step; lstm_generic.hip: exact f32, any
+// size; wgrad.hip / wgrad_pc.hip / gemm*.hip: weight gradients), and what a `dgates` / `stash` buffer holds between two calls.  The forms are DECIDED in lstm_forms.h; this file asks
 // with the handle's mode as plain values and touches no record.
 #include "internal.h"
 
@@ -115,6 +115,28 @@ struct LstmWgrad {
     }
 };
 
+// uav_lstm_bwd off the persistent kernels, one launch per time step: the fp16-split step path where it runs, else exact f32
+static int lstm_bwd_steps(uav_ctx* ctx, const float* keep, const float* stash, const float* w_hh, const float* dy, const float* dheads,
+                          const float* w_head, int n_heads, const float* dhn, const float* dcn, int N, int T, int H, float* dgates,
+                          float* dh0, float* dc0, const float* w_ih, int I, float* dx, hipStream_t st) {
+    const bool h3 = lstm_h3_step_path(H);
+    UAV_REQUIRE(dy || h3, "uav_lstm_bwd: this hidden size / arithmetic takes dy (form dheads . w_head with uav_gemm_f32); "
+                "see uav_lstm_bwd_caps");
+    UAV_REQUIRE(!dx || (w_ih && (lstm_h3_bwd_caps(I, H) & UAV_BWD_FUSES_DX)), "uav_lstm_bwd: dx is formed here only when uav_lstm_bwd_caps(ctx, I, H) "
+                "says so (H = 256 = I on the fp16-split arithmetic); otherwise ask uav_lstm_wgrad for it");
+    if (h3) return lstm_h3_bwd(ctx, keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, dgates, dh0, dc0, w_ih, dx, st);
+    return lstm_generic_bwd(ctx, keep, stash, w_hh, dy, dhn, dcn, N, T, H, dgates, dh0, dc0, st);
+}
+
+// the checks of one stepper step, in the name of the entry point `who`
+static int stepper_check(const char* who, const uav_stepper_call& c, int N, int T, int H) {
+    UAV_REQUIRE(c.state && c.x && c.y && c.stash && c.hn && c.cn, "%s: NULL argument", who);
+    UAV_REQUIRE(uav_lstm_stepper_bytes(N, c.I, H) != 0 && T > 0 && c.t >= 0 && c.t < T, "%s: bad shape (N=%d T=%d t=%d I=%d H=%d)", who, N, T, c.t, c.I, H);
+    UAV_REQUIRE(lstm_h3_step_path(H), "%s: only the fp16-split arithmetic steps (uav_set_lstm_arith)", who);
+    UAV_REQUIRE(!c.below || c.I == 256, "%s: `below` needs I = 256 (the layer below's hidden size), got %d", who, c.I);
+    return 0;
+}
+
 extern "C" {
 
 int uav_lstm_fwd(uav_ctx* ctx, const float* x, const float* keep, const float* h0, const float* c0, const float* w_ih,
@@ -145,7 +167,7 @@ int uav_lstm_fwd(uav_ctx* ctx, const float* x, const float* keep, const float* h
     int rc;
     if (persistent)
         rc = lstm_fwd_seq(fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, H, y, hn, cn, stash, w_head, b_head, n_heads, heads, &heads_done, st);
-    else  // any other hidden size: one launch per time step (lstm_generic.hip)
+    else  // any other hidden size: one launch per time step (lstm_h3.hip, lstm_generic.hip)
         rc = step256 ? lstm_h3_fwd(ctx, x, I, w_ih, b_ih, b_hh, keep, h0, c0, w_hh, N, T, y, hn, cn, stash, st)
                      : lstm_generic_fwd(ctx, keep, h0, c0, w_hh, N, T, H, y, hn, cn, stash, st);
     if (rc) return rc;
@@ -161,7 +183,7 @@ int uav_lstm_bwd_caps(uav_ctx* ctx, int I, int H) {
     if (!ctx) return 0;
     if (H == 64 || H == 128) return UAV_BWD_TAKES_DHEADS;            // the persistent sequence kernels
     uav_enter(ctx);
-    return lstm_generic_bwd_caps(I, H);
+    return lstm_h3_bwd_caps(I, H);                                   // the exact-f32 step path: none
 }
 
 size_t uav_lstm_dgates_bytes(uav_ctx* ctx, int N, int T, int H) {
@@ -218,7 +240,7 @@ int uav_lstm_bwd_stack(uav_ctx* ctx, int n_layers, const uav_lstm_bwd_layer* lay
     UAV_REQUIRE((dy != nullptr) != (dheads != nullptr), "uav_lstm_bwd_stack: give exactly one of dy / dheads");
     UAV_REQUIRE(!dheads || (w_head && n_heads > 0 && n_heads <= 8), "uav_lstm_bwd_stack: dheads needs w_head and 1..8 heads");
     UAV_REQUIRE(N > 0 && T > 0, "uav_lstm_bwd_stack: N=%d T=%d", N, T);
-    UAV_REQUIRE(H == 256 && lstm_h3_stack_ok(H), "uav_lstm_bwd_stack: H = 256 on the fp16-split arithmetic only (uav_lstm_bwd_caps)");
+    UAV_REQUIRE(H == 256 && lstm_h3_step_path(H), "uav_lstm_bwd_stack: H = 256 on the fp16-split arithmetic only (uav_lstm_bwd_caps)");
     const int nl = n_layers < 4 ? n_layers : 4;
     for (int l = 0; l < nl; ++l) ctx->forms.forget(layers[l].dgates);       // h = 256 never writes tile form
     const int rc = lstm_h3_bwd_stack(ctx, n_layers, layers, dy, dheads, w_head, n_heads, N, T, as_stream(stream));
@@ -242,8 +264,8 @@ int uav_lstm_bwd(uav_ctx* ctx, const float* keep, const float* stash, const floa
     int rc, wrote;
     if (H != 64 && H != 128) {
         wrote = lstm_h3_dg_packed(H) ? UAV_DG_PIECES : UAV_DG_ROWS;
-        rc = lstm_generic_bwd(ctx, keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, H, dgates, dh0, dc0, w_ih, I, dx,
-                              as_stream(stream));
+        rc = lstm_bwd_steps(ctx, keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, H, dgates, dh0, dc0, w_ih, I, dx,
+                            as_stream(stream));
     } else {
         UAV_REQUIRE(!dx, "uav_lstm_bwd: dx is not formed by the H = 64 / 128 sequence kernels (uav_lstm_wgrad does it)");
         wrote = form == UAV_DG_TILE ? UAV_DG_TILE : -1;             // their f32 rows are not recorded
@@ -279,6 +301,46 @@ int uav_lstm_wgrad(uav_ctx* ctx, const float* x, const float* keep, const float*
     // 3. dx = dG W_ih over the rows the path left
     if (dx) return g.product(g.NT(), I, 4 * H, g.dgates, 4 * H, 1, w_ih, I, 1, dx, I);
     return 0;
+}
+
+// ---- uav_lstm_fwd one time step per call (lstm_h3.hip): the checks and the stash record here, layout and launches there
+size_t uav_lstm_stepper_bytes(int N, int I, int H) {
+    if (H != 256 || N <= 0 || I <= 0 || I > 256) return 0;
+    return lstm_h3_stepper_bytes(N, I);
+}
+
+int uav_lstm_stepper_begin(uav_ctx* ctx, void* state, const float* w_ih, const float* w_hh, const float* b_ih,
+                           const float* b_hh, const float* h0, const float* c0, int N, int I, int H, uav_stream stream) {
+    UAV_REQUIRE(ctx && state && w_ih && w_hh && b_ih && b_hh && h0 && c0, "uav_lstm_stepper_begin: NULL argument");
+    UAV_REQUIRE(uav_lstm_stepper_bytes(N, I, H) != 0, "uav_lstm_stepper_begin: H = %d, I = %d not supported (H = 256, I <= 256)", H, I);
+    uav_enter(ctx);
+    UAV_REQUIRE(lstm_h3_step_path(H), "uav_lstm_stepper_begin: only the fp16-split arithmetic steps (uav_set_lstm_arith)");
+    return lstm_h3_stepper_begin(state, w_ih, w_hh, b_ih, b_hh, h0, c0, N, I, as_stream(stream));
+}
+
+int uav_lstm_stepper_step(uav_ctx* ctx, void* state, const float* x, const void* below, const float* keep_t, int N, int T, int t,
+                          int I, int H, float* y, float* stash, float* hn, float* cn, uav_stream stream) {
+    UAV_REQUIRE(ctx, "uav_lstm_stepper_step: NULL argument");
+    uav_enter(ctx);
+    const uav_stepper_call c{state, x, below, keep_t, t, I, y, stash, hn, cn};
+    int rc;
+    if ((rc = stepper_check("uav_lstm_stepper_step", c, N, T, H))) return rc;
+    ctx->forms.stash_step(stash, t, lstm_h3_dg_packed(H) ? 0 : 1);
+    return lstm_h3_stepper_step(c, N, T, as_stream(stream));
+}
+
+int uav_lstm_stepper_step_pair(uav_ctx* ctx, const uav_stepper_call* a, const uav_stepper_call* b, int N, int T, int H,
+                               uav_stream stream) {
+    UAV_REQUIRE(ctx && a && b, "uav_lstm_stepper_step_pair: NULL argument");
+    uav_enter(ctx);
+    UAV_REQUIRE(lstm_h3_step_path(H), "uav_lstm_stepper_step_pair: only the fp16-split arithmetic steps (uav_set_lstm_arith)");
+    int rc;
+    if ((rc = stepper_check("uav_lstm_stepper_step_pair", *a, N, T, H)) || (rc = stepper_check("uav_lstm_stepper_step_pair", *b, N, T, H)))
+        return rc;
+    const int hslot = lstm_h3_dg_packed(H) ? 0 : 1;
+    ctx->forms.stash_step(a->stash, a->t, hslot);
+    ctx->forms.stash_step(b->stash, b->t, hslot);
+    return lstm_h3_stepper_step_pair(*a, *b, N, T, as_stream(stream));
 }
 
 }  // extern "C"

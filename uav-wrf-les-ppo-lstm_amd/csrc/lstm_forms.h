@@ -1,7 +1,7 @@
 // lstm_forms.h -- the storage forms of the LSTM update's gate-gradient (`dgates`) and `stash` buffers: their layouts, the one
 // record a device handle keeps per buffer, and every decision taken from that record.  Host-only and free of HIP (plain C++17:
 // tests/host/lstm_forms_check.cpp); the kernels see the two layout structs through common.h.  The entry points (lstm_api.hip,
-// the stepper in lstm_generic.hip) hand in the handle's mode as plain values and never touch an entry themselves.
+// the stepper's among them) hand in the handle's mode as plain values and never touch an entry themselves.
 #pragma once
 #include <stddef.h>
 #include "../../include/uavppo.h"
@@ -25,7 +25,7 @@ struct DgTile {
 // ---- gate gradients of the h = 256 fp16-split step path, stored ONCE (round 5): the `dgates` buffer that travels from
 // uav_lstm_bwd / _bwd_stack to uav_lstm_wgrad holds what the BPTT's recurrent product consumes -- the two fp16 pieces of
 // every row, scaled per (env, step) by the power of two that puts the row's largest magnitude in [2^13, 2^14), in MFMA
-// fragment order (lstm_generic.hip: frag_index) -- and the weight-gradient pass reads THAT (wgrad_pc.hip) instead of a second,
+// fragment order (lstm_h3.hip: frag_index) -- and the weight-gradient pass reads THAT (wgrad_pc.hip) instead of a second,
 // f32 copy (8 of the 17 KB the gate-gradient kernel moved per env-step; -10 % of a C5 iteration by ablation,
 // profiles/r05_c5_no_f32_dgates_ablation.log).  Layout, time-major so that a step's block and the GEMM's K walk are linear:
 //   halves  pieces[t][rt][s][piece][512]      rt < RT = NP / 16 (16-env row tiles, NP = N rounded up to 64; rows >= N zero),

@@ -125,6 +125,38 @@ int uav_return_stats(uav_ctx* ctx, const float* rew, const float* done, double* 
 int uav_return_norm_merge(uav_ctx* ctx, double* state, const double* stats3, double eps, float* scale, uav_stream stream);
 int uav_reward_scale(uav_ctx* ctx, const float* rew, int64_t n, const float* scale, float clip, float* out, uav_stream stream);
 
+/* ---- O1-O5: running per-channel observation normalisation, FOLDED into the policy's first affine layer (csrc/obs_norm.hip; no
+ * counterpart in the reference).  x^ = (x - mu) / sigma per channel and the first layer w x^ + b make the affine map
+ * w_eff x + b_eff of the RAW observation, so no kernel that reads an observation changes.  D = 6 .. 8 channels everywhere.
+ * uav_obs_stats: obs f32, `rows` rows of D channels, row r at obs + r * row_stride (floats; row_stride >= D) -> stats f64
+ *   [1 + 2 D] = {rows, sum_j x, sum_j x^2}, accumulated in f64 in ONE order for every shape (256 x 256 slots, slot k the rows
+ *   k, k + 65536, ... in turn; then a fixed tree: uavppo/obs_norm.py batch_stats states it), the same bits on every call.  obs is
+ *   not written.  One launch behind a 4-byte memset; uses the handle's workspace.
+ * uav_obs_norm_merge: state f64 [UAV_OBSNORM_STATE_N(D)] = {count, skipped, mean_j, M2_j} (device; all zeros to start) takes
+ *   the batch in by Chan's update per channel, in uav_return_norm_merge's order of operations (nb = stats[0]).  A batch with a
+ *   sum that is not finite, or with nb <= 0, leaves count, mean and M2 as they were and adds 1 to `skipped`.  Then, per channel,
+ *   mu[j] = (float)mean_j and inv_sigma[j] = (float)(1 / sqrt(M2_j / count + eps)) (f32 [D], device); while count == 0, and for
+ *   every channel whose bit of `mask` (bit j = channel j) is clear, mu[j] = 0 and inv_sigma[j] = 1.  eps > 0.
+ * uav_obs_fold: w f32 [rows][D], b f32 [rows] (the master first layer) -> w_eff[r][j] = w[r][j] * inv_sigma[j] in f32,
+ *   b_eff[r] = (float)(b[r] - sum_j w_eff[r][j] * mu[j]), the sum in f64 with j ascending.  pmax_inout (f32, device, or NULL) is
+ *   RAISED to max |w_eff|, |b_eff| when that is greater (a NaN counts as +inf), never lowered: uav_clip_adam's pmax_out slot.
+ * uav_obs_unfold_grad: the chain rule of the fold, in place: dw[r][j] = (float)((dw[r][j] - db[r] * mu[j]) * inv_sigma[j]) in
+ *   f64; db is read only (the bias's gradient is its own).
+ * uav_obs_unfold: the fold inverted: w[r][j] = w_eff[r][j] / inv_sigma[j], b[r] = (float)(b_eff[r] + sum_j w_eff[r][j] * mu[j]);
+ *   w may be w_eff and b may be b_eff.
+ * All five return 2 (uav_last_error() names the argument) for a NULL pointer other than pmax_inout, D outside 6 .. 8,
+ * rows <= 0, row_stride < D and eps <= 0.  Added without a change of UAV_ABI_VERSION (symbols only). */
+#define UAV_OBSNORM_STATE_N(D) (2 + 2 * (D))
+int uav_obs_stats(uav_ctx* ctx, const float* obs, int64_t rows, int D, int64_t row_stride, double* stats, uav_stream stream);
+int uav_obs_norm_merge(uav_ctx* ctx, double* state, const double* stats, int D, unsigned mask, double eps, float* mu,
+                       float* inv_sigma, uav_stream stream);
+int uav_obs_fold(uav_ctx* ctx, const float* w, const float* b, int rows, int D, const float* mu, const float* inv_sigma,
+                 float* w_eff, float* b_eff, float* pmax_inout, uav_stream stream);
+int uav_obs_unfold_grad(uav_ctx* ctx, float* dw, const float* db, int rows, int D, const float* mu, const float* inv_sigma,
+                        uav_stream stream);
+int uav_obs_unfold(uav_ctx* ctx, const float* w_eff, const float* b_eff, int rows, int D, const float* mu, const float* inv_sigma,
+                   float* w, float* b, uav_stream stream);
+
 /* ---- T1 input (the curriculum of model.py:131-164 consumes one success flag per finished episode): the success bits of
  * the episodes that ended in a rollout, compacted in (env, time) order without a host round trip.  flags u8 [n] as written
  * by uav_rollout / uav_env_step (bit0 done, bit1 reached) -> msg u8 [4 + cap + 1]: count (4 bytes, little endian) | bit1 of

@@ -61,6 +61,8 @@ PPO_DIAGNOSTICS = False  # True: per-epoch approx. KL / clip fractions / explain
 TARGET_KL = None         # a positive number: stop an update's epochs once the epoch's approx. KL (k3) exceeds it; implies PPO_DIAGNOSTICS
 NORMALISE_REWARDS = False  # True: the GAE reads the reward scaled by the running std of the discounted return (reward_norm_state.npz)
 REWARD_CLIP = 10.0       # ... and clamped to +-REWARD_CLIP afterwards (None: no clamp)
+NORMALISE_OBS = False    # True: running per-channel observation statistics folded into the policy's first layer (obs_norm_state.npz); the saved model is the folded one
+OBS_NORM_EPS = 1e-4      # ... with inv_sigma = 1 / sqrt(var + OBS_NORM_EPS): at most 100, the bound of a channel that is constant so far
 GAE_MODE = "reference_exact"   # or "standard" (PPOV1.0/ppo0.0.py:337-350)
 SEED = 1234
 BC_EPOCHS = 10           # behaviour cloning (train_bc.py): passes over the expert set ...

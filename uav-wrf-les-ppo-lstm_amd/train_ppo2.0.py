@@ -13,7 +13,7 @@ import torch
 
 from config import (BATCH_SIZE, BPTT_LEN, CLIP_EPSILON, DIST_BACKEND, ENTROPY_BETA, ENV_VARIANT, EPISODES, EPOCHS, FIELD_BANK, GAE_MODE, GAMMA,
                     GRID_SIZE, HIDDEN, HORIZON, ITERATIONS, LAMBDA, LEARNING_RATE, LOCAL_RANK, MAX_STEPS, NUM_ENVS, NUM_LAYERS,
-                    NORMALISE_REWARDS, NUM_MINIBATCHES, POLICY, PPO_DIAGNOSTICS, RANK, REWARD_CLIP, SEED, SHUFFLE_ENVS, TARGET_KL, TREND_K,
+                    NORMALISE_OBS, NORMALISE_REWARDS, NUM_MINIBATCHES, OBS_NORM_EPS, POLICY, PPO_DIAGNOSTICS, RANK, REWARD_CLIP, SEED, SHUFFLE_ENVS, TARGET_KL, TREND_K,
                     WORLD_SIZE)  # noqa: F401
 from environment import MethaneEnv
 from model import PPOActorCritic, PPOBuffer, PPOTrainer
@@ -181,7 +181,7 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
                        gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, bptt_len=BPTT_LEN, log_info=True, gamma=GAMMA, lam=LAMBDA,
                        clip=CLIP_EPSILON, ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, rank=rank, world_size=world,
                        bank=bank, bank_sources=bank_src, trend_k=TREND_K, diagnostics=PPO_DIAGNOSTICS, target_kl=TARGET_KL,
-                       normalise_rewards=NORMALISE_REWARDS, reward_clip=REWARD_CLIP)
+                       normalise_rewards=NORMALISE_REWARDS, reward_clip=REWARD_CLIP, normalise_obs=NORMALISE_OBS, obs_norm_eps=OBS_NORM_EPS)
     # config.PPO_DIAGNOSTICS (or TARGET_KL): update_diagnostics.csv beside the episode CSV, one row per iteration (rank 0; the values
     # are over all ranks' samples).  Reading them waits for the update: one host wait per iteration that a run without them does not have.
     diag_log = None
@@ -300,6 +300,9 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
         if tr.reward_norm is not None and model_path:      # config.NORMALISE_REWARDS: the running state beside the model (its own keys unchanged)
             from uavppo.reward_norm import save_state
             save_state(tr.reward_norm, model_path)
+        if tr.obs_norm is not None and model_path:         # config.NORMALISE_OBS: the saved model is the folded one; the running state and the master beside it
+            from uavppo.obs_norm import save_state as save_obs_state
+            save_obs_state(tr.obs_norm, model_path)
     if world > 1:
         dist.barrier()
     return tr, rows

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from config import (BPTT_LEN, CLIP_EPSILON, ENTROPY_BETA, ENV_VARIANT, EPOCHS, GAE_MODE, GAMMA, HIDDEN, HORIZON, LAMBDA, LEARNING_RATE, NUM_ENVS,
-                    NORMALISE_REWARDS, NUM_LAYERS, NUM_MINIBATCHES, POLICY, PPO_DIAGNOSTICS, REWARD_CLIP, SEED, SHUFFLE_ENVS, TARGET_KL)
+                    NORMALISE_OBS, NORMALISE_REWARDS, NUM_LAYERS, NUM_MINIBATCHES, OBS_NORM_EPS, POLICY, PPO_DIAGNOSTICS, REWARD_CLIP, SEED, SHUFFLE_ENVS, TARGET_KL)
 from model import Discriminator, compute_discriminator_loss, get_expert_data  # noqa: F401  (train_ppo_gail.py:24-27)
 from uavppo.gail import GAILTrainer
 
@@ -32,7 +32,8 @@ def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert
                      gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, bptt_len=BPTT_LEN, gamma=GAMMA, lam=LAMBDA, clip=CLIP_EPSILON,
                      ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, expert=(states, actions), gail_coef=gail_coef,
                      env_coef=env_coef, disc_lr=disc_lr, disc_steps=disc_steps, update_form=update_form, minibatch_rows=minibatch_rows,
-                     diagnostics=PPO_DIAGNOSTICS, target_kl=TARGET_KL, normalise_rewards=NORMALISE_REWARDS, reward_clip=REWARD_CLIP)
+                     diagnostics=PPO_DIAGNOSTICS, target_kl=TARGET_KL, normalise_rewards=NORMALISE_REWARDS, reward_clip=REWARD_CLIP,
+                     normalise_obs=NORMALISE_OBS, obs_norm_eps=OBS_NORM_EPS)
     if init_model is not None:
         tr.policy.load_state_dict(torch.load(init_model, map_location="cpu"))
     # config.PPO_DIAGNOSTICS (or TARGET_KL): update_diagnostics.csv beside the saved policy, one row per iteration (one host wait each)
@@ -67,6 +68,9 @@ def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert
     if tr.reward_norm is not None and model_path:          # config.NORMALISE_REWARDS: the running state beside the policy
         from uavppo.reward_norm import save_state
         save_state(tr.reward_norm, model_path)
+    if tr.obs_norm is not None and model_path:             # config.NORMALISE_OBS: the saved policy is the folded one; state and master beside it
+        from uavppo.obs_norm import save_state as save_obs_state
+        save_obs_state(tr.obs_norm, model_path)
     print(f"training finished: {tr.episodes_done} episodes, {it} iterations; policy saved as {model_path}, discriminator as {disc_path}")
     return tr
 

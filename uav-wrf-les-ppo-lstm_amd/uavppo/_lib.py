@@ -69,6 +69,11 @@ SIGNATURES = {
     "uav_return_stats": (I32, [P, P, P, P, I32, I32, C.c_double, P, P, P]),
     "uav_return_norm_merge": (I32, [P, P, P, C.c_double, P, P]),
     "uav_reward_scale": (I32, [P, P, I64, P, F32, P, P]),
+    "uav_obs_stats": (I32, [P, P, I64, I32, I64, P, P]),
+    "uav_obs_norm_merge": (I32, [P, P, P, I32, C.c_uint, C.c_double, P, P, P]),
+    "uav_obs_fold": (I32, [P, P, P, I32, I32, P, P, P, P, P, P]),
+    "uav_obs_unfold_grad": (I32, [P, P, P, I32, I32, P, P, P]),
+    "uav_obs_unfold": (I32, [P, P, P, I32, I32, P, P, P, P, P]),
     "uav_pack_success_bits": (I32, [P, P, I64, I32, P, P]),
     "uav_episode_rows": (I32, [P, P, P, P, I32, I32, I32, P, P, I32, P, P]),
     "uav_curriculum_state_bytes": (SZ, []),

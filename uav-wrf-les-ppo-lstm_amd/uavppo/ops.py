@@ -177,6 +177,66 @@ def reward_scale(rew, scale, clip=0.0, out=None):
     return out
 
 
+def obs_norm_state_n(D):
+    """UAV_OBSNORM_STATE_N(D): count, skipped, D means, D M2s."""
+    return 2 + 2 * int(D)
+
+
+def obs_stats(obs, stats=None):
+    """O1: obs f32 [..., D] contiguous, or a 2-D view [rows, D] whose rows lie row_stride >= D floats apart -> stats f64
+    [1 + 2 D] = {rows, channel sums, channel sums of squares} in the fixed order of obs_norm.batch_stats.  obs is not written."""
+    if not obs.is_cuda or obs.dtype != F32 or obs.dim() < 2:
+        raise RuntimeError("obs: expected a GPU f32 tensor [..., D]")
+    D = obs.shape[-1]
+    if obs.is_contiguous():
+        rows, stride = obs.numel() // D, D
+    elif obs.dim() == 2 and obs.stride(1) == 1 and obs.stride(0) >= D:
+        rows, stride = obs.shape[0], obs.stride(0)
+    else:
+        raise RuntimeError("obs: expected a contiguous tensor, or a 2-D view with unit stride along the channels")
+    stats = torch.empty(1 + 2 * D, dtype=F64, device=obs.device) if stats is None else stats
+    check(lib().uav_obs_stats(_h(obs), C.c_void_p(obs.data_ptr()), rows, D, stride, _p(stats, F64, (1 + 2 * D,), "stats"), _stream()),
+          "uav_obs_stats")
+    return stats
+
+
+def obs_norm_merge(state, stats, mask, eps, mu, inv_sigma):
+    """O2: Chan's update per channel of state f64 [2 + 2 D] = {count, skipped, means, M2s} (in place) by the batch sums `stats`;
+    writes mu, inv_sigma f32 [D].  mask: bit j set = channel j is normalised.  No host sync."""
+    D = mu.numel()
+    check(lib().uav_obs_norm_merge(_h(state), _p(state, F64, (obs_norm_state_n(D),), "state"), _p(stats, F64, (1 + 2 * D,), "stats"), D,
+                                   int(mask), float(eps), _p(mu, F32, (D,), "mu"), _p(inv_sigma, F32, (D,), "inv_sigma"), _stream()),
+          "uav_obs_norm_merge")
+    return mu, inv_sigma
+
+
+def obs_fold(w, b, mu, inv_sigma, w_eff, b_eff, pmax=None):
+    """O3: the master first layer w [rows, D], b [rows] -> w_eff = w * inv_sigma, b_eff = b - w_eff . mu; pmax f32 [1] is raised
+    to max |w_eff|, |b_eff|."""
+    rows, D = w.shape
+    check(lib().uav_obs_fold(_h(w), _p(w, F32, name="w"), _p(b, F32, (rows,), "b"), rows, D, _p(mu, F32, (D,), "mu"),
+                             _p(inv_sigma, F32, (D,), "inv_sigma"), _p(w_eff, F32, (rows, D), "w_eff"), _p(b_eff, F32, (rows,), "b_eff"),
+                             _p(pmax, F32, (1,), "pmax"), _stream()), "uav_obs_fold")
+    return w_eff, b_eff
+
+
+def obs_unfold_grad(dw, db, mu, inv_sigma):
+    """O4, in place: dw [rows, D] <- (dw - db mu) * inv_sigma; db [rows] is only read."""
+    rows, D = dw.shape
+    check(lib().uav_obs_unfold_grad(_h(dw), _p(dw, F32, name="dw"), _p(db, F32, (rows,), "db"), rows, D, _p(mu, F32, (D,), "mu"),
+                                    _p(inv_sigma, F32, (D,), "inv_sigma"), _stream()), "uav_obs_unfold_grad")
+    return dw
+
+
+def obs_unfold(w_eff, b_eff, mu, inv_sigma, w, b):
+    """O5: the fold inverted: w = w_eff / inv_sigma, b = b_eff + w_eff . mu (w may be w_eff, b may be b_eff)."""
+    rows, D = w_eff.shape
+    check(lib().uav_obs_unfold(_h(w_eff), _p(w_eff, F32, name="w_eff"), _p(b_eff, F32, (rows,), "b_eff"), rows, D,
+                               _p(mu, F32, (D,), "mu"), _p(inv_sigma, F32, (D,), "inv_sigma"), _p(w, F32, (rows, D), "w"),
+                               _p(b, F32, (rows,), "b"), _stream()), "uav_obs_unfold")
+    return w, b
+
+
 def pack_success_bits(flags, cap, out=None):
     """flags u8 [..] -> u8 [4 + cap + 1] message (count LE | success bits of the ended episodes in order | spare)."""
     f = flags.reshape(-1)

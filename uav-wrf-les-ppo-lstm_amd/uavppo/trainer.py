@@ -19,6 +19,7 @@ from .curriculum_link import CurriculumLink
 from .dist_utils import allreduce_adv_stats, allreduce_grad, allreduce_sum, collectives_on, env_shard
 from .policy import LSTMActorCritic, MLPActorCritic
 from .range_guard import RangeGuard
+from .obs_norm import ObsNormaliser, check_obs_norm
 from .reward_norm import RewardNormaliser, check_reward_norm
 
 # reference hyper-parameters, PPOV2.0/config.py:12-18 and train_ppo2.0.py:87,114
@@ -162,7 +163,8 @@ class VecPPOTrainer:
                  seed=1234, gae_mode="reference_exact", num_minibatches=1, bank=None, bank_sources=None,
                  rank=0, world_size=1, use_curriculum=True, trend_k=0, log_info=False, device_curriculum=None,
                  update_form="update_model", minibatch_rows=None, shuffle_envs=False, bptt_len=None, diagnostics=False,
-                 target_kl=None, normalise_rewards=False, reward_clip=10.0, reward_norm_gamma=None, dgates_tile=None, **hp):
+                 target_kl=None, normalise_rewards=False, reward_clip=10.0, reward_norm_gamma=None, dgates_tile=None,
+                 normalise_obs=False, obs_norm_eps=1e-4, obs_norm_channels=None, **hp):
         self.hp = dict(DEFAULTS)
         self.dgates_tile = dgates_tile       # gate gradients of the update in tile form: None = the rule of _request_dgates_tile, True / False = A/B
         self.hp.update(hp)
@@ -171,6 +173,11 @@ class VecPPOTrainer:
         # that return, None = hp["gamma"].  buf["rew"] is never written.  Off: update() issues exactly the launches it did without it.
         self.normalise_rewards = bool(normalise_rewards)
         self.reward_clip, self.reward_norm_gamma = check_reward_norm(reward_clip, reward_norm_gamma, self.hp["gamma"])
+        # normalise_obs: running per-channel observation statistics folded into the first layer, self.obs_norm (uavppo/obs_norm.py):
+        # policy.flat holds the folded parameters, Adam updates the normaliser's master; obs_norm_channels: the channels that are
+        # normalised (None: all).  buf["obs"] is never written.  Off: update() issues exactly the launches it did without it.
+        self.normalise_obs, self.obs_norm_eps, self.obs_norm_mask = check_obs_norm(normalise_obs, obs_norm_eps, obs_norm_channels,
+                                                                                   6 + int(trend_k))
         # diagnostics: every optimiser step's loss kernel also leaves eight sums (include/uavppo.h, uav_set_ppo_diag) that
         # update() adds up per epoch -- diagnostics() turns them into approx. KL, clip fractions and explained variance.
         # target_kl: after each epoch those sums are all-reduced and read (the update's one host wait per epoch) and the
@@ -261,6 +268,7 @@ class VecPPOTrainer:
         self.link = CurriculumLink(d, self.world, self._coll, use_curriculum, device_curriculum)
         self.reward_norm = (RewardNormaliser(N, self.T, self.reward_norm_gamma, self.reward_clip or None, device=d)
                             if self.normalise_rewards else None)
+        self.obs_norm = ObsNormaliser(self.policy, self.kind, self.obs_norm_eps, self.obs_norm_mask, device=d) if self.normalise_obs else None
 
     def _alloc_policy_work(self, hidden, layers):
         """The recurrent state and the work arrays the update's kernels write their forward pass to."""
@@ -408,6 +416,8 @@ class VecPPOTrainer:
             self.c.zero_()
         if self.reward_norm is not None:
             self.reward_norm.reset()
+        if self.obs_norm is not None:
+            self.obs_norm.reset()
 
     # ------------------------------------------------------------------------------------------ R1
     def _stepwise_lstm_route(self):
@@ -633,11 +643,17 @@ class VecPPOTrainer:
         if self._diag_row is not None:   # diagnostics: this step's eight sums (its loss kernel just wrote them) into the epoch's row
             self._diag_row.add_(self._diag_sums)
         allreduce_grad(grad)              # RCCL sum over ranks; inv_n already holds 1/global count
+        on, params = self.obs_norm, self.policy.flat
+        if on is not None:               # the gradient and the parameters Adam sees are the master's (clip norm and moments too)
+            on.unfold_grad(grad)
+            params = on.master
         if self.record_grads:            # (gradient, parameters it was taken at)
-            self.grad_log.append((grad.clone(), self.policy.flat.clone()))
+            self.grad_log.append((grad.clone(), params.clone()))
         self.opt_step += 1
-        ops.clip_adam(self.policy.flat, grad, self.exp_avg, self.exp_avg_sq, self.opt_step, hp["lr"],
+        ops.clip_adam(params, grad, self.exp_avg, self.exp_avg_sq, self.opt_step, hp["lr"],
                       max_norm=hp["max_grad_norm"], gnorm_out=self.gnorm, pmax_out=self.guard.ranges[0:1])
+        if on is not None:               # policy.flat <- fold(master); the guard's slot raised to max |policy.flat|
+            on.fold(self.guard.ranges[0:1])
         if self.record:
             self.log.append((self.loss_sums.clone(), self.gnorm.clone()))
 
@@ -726,6 +742,8 @@ class VecPPOTrainer:
                 epoch()
         else:
             self._epochs_with_diagnostics(epoch, int(hp["epochs"]))
+        if self.obs_norm is not None:     # this rollout's observations into the statistics the NEXT rollout and update run on
+            self.obs_norm.after_update(self.buf["obs"], self.guard.ranges[0:1])
         self.guard.after_update()
         return self.loss_sums
 

@@ -26,6 +26,9 @@ def test_library_exports_every_declared_symbol():
     assert len(names) >= 25
     missing = [n for n in names if n not in exported]
     assert not missing, f"declared in uavppo.h but not exported: {missing}"
+    # and nothing else: measurement entry points (the phase-timing readers of `make prof`) stay out of the product library
+    extra = sorted(set(re.findall(r" [A-Za-z] (uav_[a-z0-9_]+)$", out, flags=re.M)) - set(names))
+    assert not extra, f"exported by the product library but not declared in uavppo.h: {extra}"
 
 
 def test_ctypes_table_matches_header():

@@ -6,7 +6,7 @@
 # and everything else still index env-major); only the forward and BPTT launch durations mean anything:
 #   UAVPPO_LIB=tools/libuavppo_A.so python tools/perf_update.py        -> profiles/r05_time_major_probe.log
 set -e
-cd "$(dirname "$0")/../uav-wrf-les-ppo-lstm_amd/csrc"
+cd "$(dirname "$0")/../../uav-wrf-les-ppo-lstm_amd/csrc"
 mkdir -p build_A
 for f in *.hip; do
   b=${f%.hip}; fl=""; case $b in lstm) fl="-ffp-contract=fast -DUAV_TM_PROBE";; wgrad) fl="-ffp-contract=fast";; esac

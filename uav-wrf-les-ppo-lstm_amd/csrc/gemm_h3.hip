@@ -9,7 +9,8 @@
 // tiles twice (main, cross) = up to 256 accumulator registers of the 512 a 256-thread workgroup may use per lane.
 // Operands travel global -> registers (f32, one slab ahead) -> split -> LDS piece planes [piece][row][32 k + 8 pad]
 // (16-bit, k-contiguous: every fragment is one conflict-free ds_read_b128) -> MFMA; two LDS buffers, one barrier per slab.
-// Where the time goes at [1 M x 1024]^T [1 M x 256] (profiles/r02_gemm_h3_ablation.log): 2.33 ms whole; 1.27 ms without
+// Where the time goes at [1 M x 1024]^T [1 M x 256] (profiles/r02_gemm_h3_ablation.log; the compile-time ablation switch
+// behind these figures was last present at commit 27bad41): 2.33 ms whole; 1.27 ms without
 // the loop's global loads; 1.84 ms without the MFMAs; 2.04 ms with the split arithmetic replaced by bit moves -- one slab
 // of loads in flight per CU does not cover the loaded memory latency.  Tried and dropped: eight waves with 64 x 64 wave
 // tiles and the loads two slabs ahead (256 registers per wave do not hold 128 accumulators + two stages without
@@ -30,10 +31,6 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-#ifndef H3_ABL
-#define H3_ABL 0        // ablation builds only (tools/ab_gemm_h3.sh): 1 no split arithmetic, 2 no loads, 3 no MFMAs, 4 no commit
-#endif
 
 namespace {
 
@@ -110,14 +107,9 @@ struct Stage {
                 unsigned short a[4], b[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-#if H3_ABL == 1
-                    const unsigned u = __builtin_bit_cast(unsigned, v[4 * i + j]);
-                    a[j] = (unsigned short)u; b[j] = (unsigned short)(u >> 16);
-#else
                     _Float16 p0, p1;
                     split2h(v[4 * i + j] * scale, p0, p1);
                     a[j] = h_bits(p0); b[j] = h_bits(p1);
-#endif
                 }
                 *reinterpret_cast<uint2*>(plane0 + r * HKP + kc) = make_uint2(a[0] | (unsigned)a[1] << 16, a[2] | (unsigned)a[3] << 16);
                 *reinterpret_cast<uint2*>(plane1 + r * HKP + kc) = make_uint2(b[0] | (unsigned)b[1] << 16, b[2] | (unsigned)b[3] << 16);
@@ -129,14 +121,9 @@ struct Stage {
                 f16x8 a, b;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-#if H3_ABL == 1
-                    const unsigned u = __builtin_bit_cast(unsigned, v[8 * i + j]);
-                    a[j] = __builtin_bit_cast(_Float16, (unsigned short)u); b[j] = __builtin_bit_cast(_Float16, (unsigned short)(u >> 16));
-#else
                     _Float16 p0, p1;
                     split2h(v[8 * i + j] * scale, p0, p1);
                     a[j] = p0; b[j] = p1;
-#endif
                 }
                 *reinterpret_cast<f16x8*>(plane0 + r * HKP + 8 * g) = a;
                 *reinterpret_cast<f16x8*>(plane1 + r * HKP + 8 * g) = b;
@@ -220,24 +207,12 @@ __global__ __launch_bounds__(256) void gemm_h3_kernel(int64_t M, int64_t N, int6
     int buf = 0;
     // all slabs but the last: the next slab's loads fly under this slab's MFMAs, its split + LDS writes follow them
     for (int64_t k0 = kb; k0 + HK < ke; k0 += HK) {
-#if H3_ABL != 2
         ra.load(A, lda, m0, k0 + HK, ke);
         rb.load(B, ldb, n0, k0 + HK, ke);
-#endif
-#if H3_ABL != 3
         multiply(buf);
-#endif
         unsigned short* np = sm16 + (buf ^ 1) * TL::BUF;
-#if H3_ABL == 4
-#pragma unroll
-        for (int q = 0; q < decltype(ra)::NF; ++q) asm volatile("" ::"v"(ra.v[q]));
-#pragma unroll
-        for (int q = 0; q < decltype(rb)::NF; ++q) asm volatile("" ::"v"(rb.v[q]));
-        (void)np;
-#else
         ra.commit(np, np + TL::A_PLANE, sa);
         rb.commit(np + 2 * TL::A_PLANE, np + 2 * TL::A_PLANE + TL::B_PLANE, 1.f);
-#endif
         __syncthreads();
         buf ^= 1;
     }
@@ -281,9 +256,7 @@ __global__ __launch_bounds__(256) void gemm_h3_kernel(int64_t M, int64_t N, int6
 //   * EIGHT waves, two per SIMD, 64 x 64 wave tiles: 128 accumulator registers + two slabs of staging (2 x 24) + one column
 //     tile of B fragments ahead fit the 256 registers a wave has at this occupancy.  What binds now is LDS: per slab 128 KB
 //     of fragment reads + 48 KB of piece writes per CU at 128 B per clock take as long as the MFMAs.
-#ifndef TN8_GROUP
-#define TN8_GROUP 3        // MFMAs (with the pair split behind them) per scheduling region; 1 .. 12 measure the same (r04_gemm_tn_ablation.log)
-#endif
+constexpr int TN8_GROUP = 3;   // MFMAs (with the pair split behind them) per scheduling region; 1 .. 12 measure the same (r04_gemm_tn_ablation.log)
 struct Tn8Regs {
     f32x4 a[2];            // A item: rows 4 arg .. + 3 in the components, k = 2 akp + q
     f32x4 b[4];            // B item: rows 4 brg .. + 3, k = 4 bkg + q

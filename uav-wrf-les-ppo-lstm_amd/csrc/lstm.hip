@@ -31,6 +31,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "internal.h"
+#include "phase_prof.h"
 
 constexpr int MT = 16;      // env rows per workgroup (MFMA M)
 constexpr int TC = 32;      // time steps staged per chunk
@@ -228,27 +229,9 @@ struct FwdSplitGeom {
     static constexpr size_t LDS = (2 * P::NP * PLANE + (H / 16) * WPARK + P::NP * HPL) * sizeof(unsigned short) +
                                   (2 * TCX * MT * 8 + 2 * TCX * MT + (H / 16) * 8 * 64 + 4 * H + 8) * sizeof(float);
 };
-#ifdef UAV_X6_PROFILE
-// phase timing of the split-bf16 forward (instrumented build only, -DUAV_X6_PROFILE): s_memtime at four marks
-// per step, summed over the sequence by wave 0 and the last wave of workgroup 0
-__device__ unsigned long long g_x6_prof[2][8];
-#define X6_PROF_DECL unsigned long long pm_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pl_ = __builtin_readcyclecounter()
-#define X6_PROF_MARK(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); pm_[i] += n_ - pl_; pl_ = n_; } while (0)
-#define X6_PROF_DEP(v) asm volatile("" ::"v"(v))
-#define X6_PROF_FLUSH() do { if (blockIdx.x == 0 && lane == 0 && (w == 0 || w == H / 16 - 1)) \
-        for (int i_ = 0; i_ < 4; ++i_) g_x6_prof[w ? 1 : 0][i_] = pm_[i_]; } while (0)
-#define X6_PROF_FLUSH8() do { if (blockIdx.x == 0 && lane == 0 && (w == 0 || w == H / 16 - 1)) \
-        for (int i_ = 0; i_ < 8; ++i_) g_x6_prof[w ? 1 : 0][i_] = pm_[i_]; } while (0)
-extern "C" int uav_x6_prof_read(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_x6_prof), sizeof(g_x6_prof)) == hipSuccess ? 0 : 1;
-}
-#else
-#define X6_PROF_DECL
-#define X6_PROF_MARK(i)
-#define X6_PROF_DEP(v)
-#define X6_PROF_FLUSH()
-#define X6_PROF_FLUSH8()
-#endif
+// phase timing of the split forward (four marks per step) and the BPTT (seven), summed over the sequence by wave 0 and the
+// last wave of workgroup 0 (phase_prof.h)
+PROF_TABLE(g_x6_prof, [2][8], uav_x6_prof_read)
 
 // Orientation: gates^T = W h^T, i.e. the WEIGHTS are the MFMA A operand (16 units of one gate) and h^T the B
 // operand (16 envs), so a lane's four accumulator rows are four CONSECUTIVE units of ONE env: y and the five
@@ -409,7 +392,7 @@ __device__ __forceinline__ void lstm_fwd_split(
     stage_commit(0);
     int cur = 0;
     float kcur = 1.f;            // keep of the step about to run (the mask on the incoming h); h0 is masked above
-    X6_PROF_DECL;
+    PROF_DECL(8);
     lds_barrier();
 
     const int nchunk = (T + TC - 1) / TC;
@@ -419,7 +402,7 @@ __device__ __forceinline__ void lstm_fwd_split(
         for (int tt = 0; tt < tc; ++tt) {
             const int t = t0 + tt;
             const size_t row = (size_t)n * T + t;
-            X6_PROF_MARK(0);
+            PROF_MARK(0);
             if (heads && w == NW - 1 && t > 0) emit_heads(cur, t - 1);   // heads of h_{t-1}, while no accumulator is live
             // the planes hold h_{t-1} UNMASKED (the heads need it so); the episode mask k_t is a per-env scalar, so it
             // is applied to the finished h-part of the accumulator: acc = k_t (W_hh h_{t-1}) + bias + W_ih x_t
@@ -449,8 +432,8 @@ __device__ __forceinline__ void lstm_fwd_split(
                     acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(wxw[(2 * q + 1) * 64], ax.y, acc[q], 0, 0, 0);
                 }
             }
-            X6_PROF_DEP(acc[0][0]); X6_PROF_DEP(acc[1][1]); X6_PROF_DEP(acc[2][2]); X6_PROF_DEP(acc[3][3]);
-            X6_PROF_MARK(1);
+            PROF_DEP(acc[0][0]); PROF_DEP(acc[1][1]); PROF_DEP(acc[2][2]); PROF_DEP(acc[3][3]);
+            PROF_MARK(1);
             const float kn = kbuf[(xb * TC + tt) * MT + j];              // keep of step t+1 (1 past the end)
             // the stash stores are issued as soon as their values exist, so the write stream starts under the rest of
             // the gate math instead of in one burst before the barrier.
@@ -494,9 +477,9 @@ __device__ __forceinline__ void lstm_fwd_split(
                 }
             }
             cur ^= 1;
-            X6_PROF_MARK(2);
+            PROF_MARK(2);
             lds_barrier();
-            X6_PROF_MARK(3);
+            PROF_MARK(3);
         }
         if (ch + 1 < nchunk) {
             stage_commit(xb ^ 1);
@@ -504,7 +487,7 @@ __device__ __forceinline__ void lstm_fwd_split(
         }
     }
     if (heads && w == NW - 1) emit_heads(cur, T - 1);                     // planes `cur` hold h_{T-1}
-    X6_PROF_FLUSH();
+    PROF_FLUSH(g_x6_prof[w ? 1 : 0], 4, blockIdx.x == 0 && lane == 0 && (w == 0 || w == H / 16 - 1));
 }
 
 // the entry points, one per arithmetic: profiles and bench.py find the kernels by these names in a kernel trace
@@ -806,9 +789,9 @@ __device__ __forceinline__ void lstm_bwd_split(
         issue_small(T >= 2 ? T - 2 : 0, (T - 2) & 1);
     }
     bool first = true;
-    X6_PROF_DECL;
+    PROF_DECL(8);
     for (int t = T - 1; t >= 0; --t) {
-        X6_PROF_MARK(0);
+        PROF_MARK(0);
         if (first) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else if (small_wave) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
@@ -819,9 +802,9 @@ __device__ __forceinline__ void lstm_bwd_split(
         for (int q = 0; q < 5; ++q) pf[q] = *reinterpret_cast<const float4*>(sl + q * 256);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the slot is in registers: refill it with step t-1
         issue(t >= 1 ? t - 1 : 0);
-        X6_PROF_MARK(1);
+        PROF_MARK(1);
         lds_barrier();           // b2: the partials of step t+1 have been summed by everyone; small image of step t landed
-        X6_PROF_MARK(2);
+        PROF_MARK(2);
         const float* sm = small + (t & 1) * SMALL;
         f32x4 dyacc = {0.f, 0.f, 0.f, 0.f};
         {
@@ -890,8 +873,8 @@ __device__ __forceinline__ void lstm_bwd_split(
             }
             if constexpr (!P::DG_STORES_LATE) store_dg(q);
         }
-        X6_PROF_DEP(bp[1][NP - 1]); X6_PROF_DEP(bp[0][0]);
-        X6_PROF_MARK(3);
+        PROF_DEP(bp[1][NP - 1]); PROF_DEP(bp[0][0]);
+        PROF_MARK(3);
         // partial dh^T tiles: D_m[unit 16m + 4kq + r][env j] over this wave's K range
 #pragma unroll
         for (int m = 0; m < NW; ++m) {
@@ -908,19 +891,19 @@ __device__ __forceinline__ void lstm_bwd_split(
             for (int q = 0; q < 4; ++q) store_dg(q);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        X6_PROF_MARK(4);
+        PROF_MARK(4);
         lds_barrier();           // b1: all partials written; nobody reads the small image of step t any more
-        X6_PROF_MARK(5);
+        PROF_MARK(5);
         if (small_wave) issue_small(t >= 2 ? t - 2 : 0, t & 1);
         f32x4 sum = part[(w * NW) * 64 + lane];
 #pragma unroll
         for (int ww = 1; ww < NW; ++ww) sum += part[(w * NW + ww) * 64 + lane];      // fixed order: deterministic
 #pragma unroll
         for (int r = 0; r < 4; ++r) dh_rec[r] = sum[r] * kp;
-        X6_PROF_DEP(dh_rec[3]);
-        X6_PROF_MARK(6);
+        PROF_DEP(dh_rec[3]);
+        PROF_MARK(6);
     }
-    X6_PROF_FLUSH8();
+    PROF_FLUSH(g_x6_prof[w ? 1 : 0], 8, blockIdx.x == 0 && lane == 0 && (w == 0 || w == H / 16 - 1));
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // retire the clamped tail DMAs before the LDS is released
     if (live) {
         if (dh0) *reinterpret_cast<float4*>(dh0 + (size_t)n * H + uo) = float4{dh_rec[0], dh_rec[1], dh_rec[2], dh_rec[3]};

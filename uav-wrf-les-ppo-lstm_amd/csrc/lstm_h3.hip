@@ -17,15 +17,10 @@
 
 #include <type_traits>
 
+// Where the step kernels' time goes: step_fwd 21 us per step and layer whole, 9.8 without the cell epilogue, 18.6 without the MFMAs
+// (profiles/r02_step_fwd_ablation.log); the cell_bwd and fragment-sharing figures are quoted at the kernels below.  The compile-time
+// ablation switches of the step and cell kernels behind these logs were last present at commit 27bad41.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#ifndef CELL_ABL
-#define CELL_ABL 0      // ablation builds of cell_bwd_h3_kernel only (tools/ab_step_fwd.sh): 1 no piece stores, 2 no f32 dG stores, 3 neither
-#endif
-#ifndef STEP_ABL
-#define STEP_ABL 0      // ablation builds of the step kernels only (tools/ab_step_fwd.sh): step_fwd_h3_kernel 1 no MFMAs, 2 no recurrent loads,
-#endif                  // 3 no epilogue, 4 each wave loads ONE of the four B column tiles (what sharing B through LDS would leave on the L1
-                        // path); 5 step_bwd_h3_kernel: each wave loads one of its two A and one of its two B tiles (the same question)
 
 // ================================================================================================ fp16-split step kernels
 // MFMA-fragment order of an operand matrix M [R][K] (R rows = A rows or B columns, K a multiple of 32): the 8 consecutive
@@ -130,11 +125,6 @@ __device__ __forceinline__ void step_fwd_h3_body(const unsigned short* __restric
         }
     }
     auto mac = [&](const f16x8 (&a)[4][2], const f16x8 (&b)[NC][2]) {
-#if STEP_ABL == 1
-        asm volatile("" ::"v"(a[0][0]), "v"(a[1][0]), "v"(a[2][0]), "v"(a[3][0]), "v"(a[0][1]), "v"(a[1][1]), "v"(a[2][1]), "v"(a[3][1]),
-                     "v"(b[0][0]), "v"(b[0][1]), "v"(b[1][0]), "v"(b[1][1]));
-        return;
-#endif
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -175,9 +165,6 @@ __device__ __forceinline__ void step_fwd_h3_body(const unsigned short* __restric
             }
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-#if STEP_ABL == 4
-                if (c != w) continue;
-#endif
                 const unsigned short* p = rec ? bp[c] : bxp[c];
                 b[buf][c][0] = ldh8(p + (1024 * q + lo));
                 b[buf][c][1] = ldh8(p + (1024 * q + 512 + lo));
@@ -216,9 +203,6 @@ __device__ __forceinline__ void step_fwd_h3_body(const unsigned short* __restric
             for (int g = 0; g < 4; ++g) { a[buf][g][0] = ldh8(ap[g] + (1024 * s + lo)); a[buf][g][1] = ldh8(ap[g] + (1024 * s + 512 + lo)); }
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-#if STEP_ABL == 4
-                if (c != w) continue;
-#endif
                 b[buf][c][0] = ldh8(bp[c] + (1024 * s + lo)); b[buf][c][1] = ldh8(bp[c] + (1024 * s + 512 + lo));
             }
         };
@@ -226,15 +210,11 @@ __device__ __forceinline__ void step_fwd_h3_body(const unsigned short* __restric
         for (int d = 0; d < DEPTH - 1; ++d) fetch(d, d);
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
-#if STEP_ABL == 2
-            mac(a[0], b[0]);
-#else
             if (s + DEPTH - 1 < NS) fetch(s + DEPTH - 1, (s + DEPTH - 1) % DEPTH);
             if (DEPTH > 2) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int c = 0; c < NC; ++c) { b[s % DEPTH][c][0] = masked(b[s % DEPTH][c][0], kmask[c]); b[s % DEPTH][c][1] = masked(b[s % DEPTH][c][1], kmask[c]); }
             mac(a[s % DEPTH], b[s % DEPTH]);
-#endif
         }
     }
     // ---- input projection: x_t [n][I] f32 -> two fp16 pieces per value, K = 32 IPS; the next slab's weight fragments and
@@ -293,9 +273,6 @@ __device__ __forceinline__ void step_fwd_h3_body(const unsigned short* __restric
     }
     }
     // ---- cell (gen_cell_fwd's arithmetic) and outputs
-#if STEP_ABL == 3
-    if (acc[0][0][0] == 123.456f)
-#endif
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
         const int n = e0 + 16 * c + r16;
@@ -422,12 +399,9 @@ __global__ void add2v_kernel(const float* a0, const float* a1, float* b, int n) 
 // 20 (profiles/r02_cell_bwd_ablation.log).  LDS image: chunk (slab, piece) at CB_CH halves, kq rows at CB_KQ: strides chosen
 // so that the 32 (slab, kq) positions one store instruction touches fall on different banks (2-way at worst).
 constexpr int CB_KQ = 136, CB_CH = 592;                 // halves: 272 B per kq row (16 envs x 16 B + 16), 1184 B per chunk
-#ifndef BWD_DX_DEPTH
-#define BWD_DX_DEPTH 5                                  // prefetch ring of step_bwd_h3_kernel<DX>: 5 slabs = 364 registers, so that two
-#endif                                                  // cell_bwd waves (2 x 64) of the other layer's stream fit the SIMD's 512 beside it (6: 412)
-#ifndef CELL_EPW
-#define CELL_EPW 8                                      // envs per workgroup of cell_bwd_h3_kernel (16 = one workgroup per row tile)
-#endif
+constexpr int BWD_DX_DEPTH = 5;                         // prefetch ring of step_bwd_h3_kernel<DX>: 5 slabs = 364 registers, so that two
+                                                        // cell_bwd waves (2 x 64) of the other layer's stream fit the SIMD's 512 beside it (6: 412)
+constexpr int CELL_EPW = 8;                             // envs per workgroup of cell_bwd_h3_kernel (16 = one workgroup per row tile)
 constexpr size_t CELL_BWD_LDS = (size_t)64 * CB_CH * 2;
 template <int H, int EPW>
 __global__ __launch_bounds__(EPW * 64) void cell_bwd_h3_kernel(const float* __restrict__ stash, const float* __restrict__ keep,
@@ -542,7 +516,6 @@ __global__ __launch_bounds__(EPW * 64) void cell_bwd_h3_kernel(const float* __re
         }
     }
     __syncthreads();
-#if CELL_ABL != 1 && CELL_ABL != 3
     // the tile's piece block is 64 chunks x 1 KB of consecutive memory (frag_index): a linear copy, 16 bytes per thread
     // (EPW = 8: this workgroup's eight envs = one 128-byte line of each kq row)
     unsigned short* gout = dgp + (size_t)tile * 64 * 512;
@@ -554,7 +527,6 @@ __global__ __launch_bounds__(EPW * 64) void cell_bwd_h3_kernel(const float* __re
         const uint4 v = *reinterpret_cast<const uint4*>(cb_lds + (size_t)c * CB_CH + kq * CB_KQ + r * 8);
         *reinterpret_cast<uint4*>(gout + ((size_t)c * 64 + kq * 16 + r) * 8) = v;
     }
-#endif
 }
 
 // dh_{t-1}[n][u] = keep[n][t] * sum_k dG_t[n][k] W_hh[k][u]: A = W_hh^T pieces [2][H][4H] (rows = units), B = the scaled dG
@@ -595,25 +567,16 @@ __global__ __launch_bounds__(256) void step_bwd_h3_kernel(const unsigned short* 
     auto fetch = [&](int s, int buf) {
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
-#if STEP_ABL == 5
-            if (r != (w >> 1)) continue;
-#endif
             a[buf][r][0] = ldh8(ap[r] + (1024 * s + lo)); a[buf][r][1] = ldh8(ap[r] + (1024 * s + 512 + lo));
         }
         if (DX) {
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
-#if STEP_ABL == 5
-                if (r != (w >> 1)) continue;
-#endif
                 ax[buf][r][0] = ldh8(axp[r] + (1024 * s + lo)); ax[buf][r][1] = ldh8(axp[r] + (1024 * s + 512 + lo));
             }
         }
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-#if STEP_ABL == 5
-            if (c != (w & 1)) continue;
-#endif
             b[buf][c][0] = ldh8(bp[c] + (1024 * s + lo)); b[buf][c][1] = ldh8(bp[c] + (1024 * s + 512 + lo));
         }
     };

@@ -3,7 +3,7 @@
 // tiles of 32 samples; LayerNorm statistics, activations and their gradients never leave the CU, weight gradients accumulate
 // in registers over all of a workgroup's tiles and leave as one slab per workgroup.  HBM traffic = the 44 algorithmic bytes
 // per sample.  The forward is mlp_tile_core.h's, shared with the rollout (mlp_rollout.hip).  The tile loop's ten
-// phases (M_PROF_MARK 0 .. 9, the names tools/perf_mlp_fused.py prints) stay written out in the kernel body: at 256 VGPRs
+// phases (PROF_MARK 0 .. 9, the names tools/perf_mlp_fused.py prints) stay written out in the kernel body: at 256 VGPRs
 // every phase tried as a function of its own -- and the LDS pointers gathered in a struct -- raised the scratch of some of
 // the 16 forms (profiles/mlp_split_static_table.md).
 #include <type_traits>
@@ -11,22 +11,10 @@
 #include "internal.h"
 #include "loss_core.h"
 #include "mlp_tile_core.h"
+#include "phase_prof.h"
 
-#ifdef UAV_X6_PROFILE
-// phase timing (instrumented build only, tools/build_prof.sh): cycles per phase summed over the tiles of workgroup 0,
-// waves 0 (loss wave) and 1
-__device__ unsigned long long g_mlp_prof[2][16];
-#define M_PROF_DECL unsigned long long pm_[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pl_ = __builtin_readcyclecounter()
-#define M_PROF_MARK(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); pm_[i] += n_ - pl_; pl_ = n_; } while (0)
-#define M_PROF_FLUSH() do { if (blockIdx.x == 0 && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) < 2) for (int i_ = 0; i_ < 16; ++i_) g_mlp_prof[threadIdx.x >> 6][i_] = pm_[i_]; } while (0)
-extern "C" int uav_mlp_prof_read(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mlp_prof), sizeof(g_mlp_prof)) == hipSuccess ? 0 : 1;
-}
-#else
-#define M_PROF_DECL
-#define M_PROF_MARK(i)
-#define M_PROF_FLUSH()
-#endif
+// phase timing: cycles per phase summed over the tiles of workgroup 0, waves 0 (loss wave) and 1 (phase_prof.h)
+PROF_TABLE(g_mlp_prof, [2][16], uav_mlp_prof_read)
 
 namespace {
 
@@ -133,7 +121,7 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
     // the exponent drops and the accumulators are rescaled (exact)
     int e_run = 100;
     const int64_t ntile = (Bn + MS - 1) / MS;
-    M_PROF_DECL;
+    PROF_DECL(16);
     // ROWS: the buffer row of launch sample s (0 past the end: never used), and the rows of this thread's X element / loss sample
     auto row_of = [&](int64_t s) {
         int r = s < Bn ? rows[s] : 0;
@@ -171,7 +159,7 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
             if constexpr (ROWS) rl_next = row_of(s0 + (int64_t)gridDim.x * MS + lane);
         }
         lds_barrier();
-        M_PROF_MARK(0);
+        PROF_MARK(0);
         // ---- forward
         f32x4 xh1[NC][2], xh2[NC];
         float r1[NC], r2[NC];
@@ -184,7 +172,7 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
             layer1<NC, H3>(L, w1a, w, j, kq, xh1, r1);
         }
         lds_barrier();
-        M_PROF_MARK(1);
+        PROF_MARK(1);
         if constexpr (H3) {
             // ONE address register pair, advanced 4 KB per two-slab chunk, the four fragments of a chunk at immediate offsets:
             // sixteen separate 64-bit addresses (what the compiler makes of w2f + constant) are sixteen spilled pairs
@@ -196,14 +184,14 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
             }, w, j, kq, xh2, r2);
         } else layer2<NC>(L, [&](int s) { return ld4(wfw + 16 * s); }, w, j, kq, xh2, r2);
         lds_barrier();
-        M_PROF_MARK(2);
+        PROF_MARK(2);
         {
             float wh[4];
 #pragma unroll
             for (int s = 0; s < 4; ++s) wh[s] = j < 8 ? WHL[j * H2 + 16 * w + 4 * s + kq] : 0.f;
             heads_fwd<NC>(L, wh, bh, w, lane);
         }
-        M_PROF_MARK(3);
+        PROF_MARK(3);
         // ---- loss + d(total)/d(heads) for the tile's samples (lanes 0..MS-1 of wave 0)
         if (w == 0) {
             __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -242,7 +230,7 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
             }
         }
         lds_barrier();
-        M_PROF_MARK(4);
+        PROF_MARK(4);
         // ---- heads backward: dWh += dheads^T a2 (K = the tile's samples), da2 = Wh^T dheads
 #pragma unroll
         for (int s = 0; s < MS / 4; ++s) {
@@ -361,7 +349,7 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
             }
         }
         lds_barrier();                                       // dz2 visible
-        M_PROF_MARK(5);
+        PROF_MARK(5);
         // ---- dW2 += dz2^T a1 (row tile w, all 16 column tiles; K = the tile's samples), da1 = W2^T dz2
         if constexpr (H3) {
             // one K = 32 slab (the tile's samples): A = this wave's 16 dz2 rows from P2w, B = a1 from the SAME planes layer 2
@@ -390,7 +378,7 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
                 if ((tj & 3) == 3) asm volatile("" ::: "memory");      // four column tiles' fragments at a time
             }
         }
-        M_PROF_MARK(6);
+        PROF_MARK(6);
         f32x4 da1[NC][2];
 #pragma unroll
         for (int c = 0; c < NC; ++c) da1[c][0] = da1[c][1] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -461,7 +449,7 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
                 asm volatile("" ::: "memory");
             }
         }
-        M_PROF_MARK(7);
+        PROF_MARK(7);
         // ---- LayerNorm 1 + ReLU backward
         {
             f32x4 dxh[NC][2];                                // da1 becomes dxhat in place
@@ -508,7 +496,7 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
             }
         }
         lds_barrier();                                       // dz1 visible
-        M_PROF_MARK(8);
+        PROF_MARK(8);
         // ---- dW1 += dz1^T x
 #pragma unroll
         for (int s = 0; s < MS / 4; ++s) {
@@ -518,9 +506,9 @@ __global__ __launch_bounds__(512) void mlp_ppo_grad_kernel(
             for (int t = 0; t < 2; ++t) dW1[t] = mfma4(L.A1[(4 * s + kq) * AS1 + 32 * w + 16 * t + j], b, dW1[t]);
         }
         lds_barrier();                                       // X, A1, A2, DH free for the next tile
-        M_PROF_MARK(9);
+        PROF_MARK(9);
     }
-    M_PROF_FLUSH();
+    PROF_FLUSH(g_mlp_prof[threadIdx.x >> 6], 16, blockIdx.x == 0 && (threadIdx.x & 63) == 0 && (threadIdx.x >> 6) < 2);
 
     // ---- this workgroup's gradient slab (flat parameter layout) and loss partial
     float* slab = slabs + (size_t)blockIdx.x * O.N;

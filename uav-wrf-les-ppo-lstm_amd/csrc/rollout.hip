@@ -20,26 +20,15 @@
 // 44 B per env-step (obs 24, act 4, rew 4, val 4, logp 4, done 4) + 5 B (keep, flags).
 #include "internal_env.h"
 #include "loss_core.h"
+#include "phase_prof.h"
 #include "rows_dot_core.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RMT = 16;
 
-#ifdef UAV_X6_PROFILE
-// phase timing of wave 0 (instrumented build only, tools/build_prof.sh): cycles summed over the rollout by workgroup 0
-__device__ unsigned long long g_roll_prof[8];
-#define R_PROF_DECL unsigned long long pm_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pl_ = __builtin_readcyclecounter()
-#define R_PROF_MARK(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); pm_[i] += n_ - pl_; pl_ = n_; } while (0)
-#define R_PROF_FLUSH() do { if (blockIdx.x == 0 && threadIdx.x == 0) for (int i_ = 0; i_ < 8; ++i_) g_roll_prof[i_] = pm_[i_]; } while (0)
-extern "C" int uav_roll_prof_read(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_roll_prof), sizeof(g_roll_prof)) == hipSuccess ? 0 : 1;
-}
-#else
-#define R_PROF_DECL
-#define R_PROF_MARK(i)
-#define R_PROF_FLUSH()
-#endif
+// phase timing of wave 0: cycles summed over the rollout by workgroup 0 (phase_prof.h)
+PROF_TABLE(g_roll_prof, [8], uav_roll_prof_read)
 
 #define r_sigmoid fast_sigmoid
 #define r_tanh fast_tanh
@@ -441,12 +430,12 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         float bh[NH];                            // head biases: read once (a load inside the loop could not be hoisted past the stores)
 #pragma unroll
         for (int a = 0; a < NH; ++a) bh[a] = b_hd[a];
-        R_PROF_DECL;
+        PROF_DECL(8);
         for (int t = 0; t < steps; ++t) {
             const bool value_only = (t == T);
-            R_PROF_MARK(7);
+            PROF_MARK(7);
             finish_cell(t, value_only);
-            R_PROF_MARK(0);
+            PROF_MARK(0);
             // the step's action-independent part (sampling uniform, the wind displacement from its two normals), computed
             // while the other waves finish their cells: off the heads -> action -> env chain that paces the kernel
             uint32_t u_act = 0;
@@ -457,9 +446,9 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                 if (!GREEDY && !B.forced_act) u_act = philox4x32_10(P.seed, (uint32_t)t, (uint32_t)eg, (uint32_t)iter, RNG_ACTION).x;
                 env_step_draw_wind(P, eg, es_s[lane], B.noise, row, wind_x, wind_y);
             }
-            R_PROF_MARK(6);
+            PROF_MARK(6);
             lds_barrier();                       // barrier 1: h_t visible
-            R_PROF_MARK(1);
+            PROF_MARK(1);
             // heads of h_t: D[head 4 kq + r][env j] = W_head h_t^T, three piece products per slab
             f32x4 ha = {0.f, 0.f, 0.f, 0.f}, hb2 = ha;
             {
@@ -483,7 +472,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
             for (int r = 0; r < 4; ++r) hd[j * 16 + 4 * kq + r] = ha[r];
             __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): the hd tile is written (single wave)
             __builtin_amdgcn_wave_barrier();
-            R_PROF_MARK(2);
+            PROF_MARK(2);
             if (lane < RMT) {
                 float z[NA];
 #pragma unroll
@@ -552,12 +541,12 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                     bool bad;
                     const int a_sel = rollout_draw<NA>(z, B.forced_act, row, [&]() { return u_act; }, lp, bad);
                     if (bad && env_lane) atomicAdd(B.nan_count, 1);
-                    R_PROF_MARK(3);
+                    PROF_MARK(3);
                     // environment step (f64, env_core.h) + auto reset
                     EnvState es = es_s[lane];
                     StepOut so;
                     env_step_core(P, eg, es, myvis, a_sel, wind_x, wind_y, so);
-                    R_PROF_MARK(4);
+                    PROF_MARK(4);
                     // park the transition in LDS for store_transition()
                     float* tr = trs + lane * 8;
                     tr[0] = __int_as_float(a_sel);
@@ -594,7 +583,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
                     kbuf[lane] = so.done ? 0.f : 1.f;
                 }
             }
-            R_PROF_MARK(5);
+            PROF_MARK(5);
             lds_barrier();                       // barrier 2: the gate waves have left bias + W_hh h_t of this wave's units in acc0
             if (!value_only && t + 1 < steps) {
 #pragma unroll
@@ -602,7 +591,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
             }
             if (!value_only) keep_fixup(t);
         }
-        R_PROF_FLUSH();
+        PROF_FLUSH(g_roll_prof, 8, blockIdx.x == 0 && threadIdx.x == 0);
     }
     // ------------------------------------------------------------------ write back persistent state
     if (live) *reinterpret_cast<float4*>(B.c + (size_t)(n0 + j) * H + uo) = float4{c_reg[0], c_reg[1], c_reg[2], c_reg[3]};

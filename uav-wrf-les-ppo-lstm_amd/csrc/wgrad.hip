@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "internal.h"
+#include "phase_prof.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -322,22 +323,8 @@ struct WGS {
     static constexpr int DV = (8 * KS6 + NT - 1) / NT;               // dheads elements per thread per slab
 };
 
-#ifdef UAV_X6_PROFILE
-__device__ unsigned long long g_wx6_prof[2][8];
-#define WX_PROF_DECL unsigned long long pm_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pl_ = __builtin_readcyclecounter()
-#define WX_PROF_MARK(i) do { const unsigned long long n_ = __builtin_readcyclecounter(); pm_[i] += n_ - pl_; pl_ = n_; } while (0)
-#define WX_PROF_DEP(v) asm volatile("" ::"v"(v))
-#define WX_PROF_FLUSH() do { if (blockIdx.x == 0 && lane == 0 && (w == 0 || w == H / 16 - 1)) \
-        for (int i_ = 0; i_ < 8; ++i_) g_wx6_prof[w ? 1 : 0][i_] = pm_[i_]; } while (0)
-extern "C" int uav_wx6_prof_read(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_wx6_prof), sizeof(g_wx6_prof)) == hipSuccess ? 0 : 1;
-}
-#else
-#define WX_PROF_DECL
-#define WX_PROF_MARK(i)
-#define WX_PROF_DEP(v)
-#define WX_PROF_FLUSH()
-#endif
+// phase timing of the slab loop, summed over the slabs by wave 0 and the last wave of workgroup 0 (phase_prof.h)
+PROF_TABLE(g_wx6_prof, [2][8], uav_wx6_prof_read)
 
 template <int H, bool HEADS, class P, bool TILE = false>
 __device__ __forceinline__ void lstm_wgrad_split(
@@ -551,31 +538,31 @@ __device__ __forceinline__ void lstm_wgrad_split(
     load_b(1);
     split_pair(0, 0);
     lds_barrier();
-    WX_PROF_DECL;
+    PROF_DECL(8);
     // one body for both groups -- mfma0 commit split1 mfma1 split0(next) -- and the group decides where in it the
     // slab barrier sits: EARLY waves wait before split0(next), LATE waves after it, so after every barrier the
     // LATE wave of a SIMD streams MFMAs while the EARLY one still splits, and so on round the slab
     for (int sl = 0; sl < nslab; ++sl) {
         const int buf = sl & 1;
-        WX_PROF_MARK(0);
+        PROF_MARK(0);
         mfma_pair(buf, 0, sl);
-        WX_PROF_DEP(acc[0][NT_ - 1]); WX_PROF_DEP(acc[1][NT_ - 1]); WX_PROF_MARK(2);
+        PROF_DEP(acc[0][NT_ - 1]); PROF_DEP(acc[1][NT_ - 1]); PROF_MARK(2);
         // commit_b is the first reader of the B-side loads, the youngest in flight at the top of the slab: nothing of it may be
         // scheduled up into pair 0's block, or its wait for them (all loads, at that point) lands there as well
         __builtin_amdgcn_sched_barrier(0);
         commit_b(buf ^ 1);                                // planes of slab sl + 1 (a clamped copy on the last slab)
         if constexpr (!P::LOADS_BETWEEN_TILES) load_b(sl + 2);
-        WX_PROF_MARK(5);
+        PROF_MARK(5);
         split_pair(sl, 1);
-        WX_PROF_DEP(ap[0][0]); WX_PROF_DEP(ap[1][NP - 1]); WX_PROF_MARK(3);
+        PROF_DEP(ap[0][0]); PROF_DEP(ap[1][NP - 1]); PROF_MARK(3);
         mfma_pair(buf, 1, sl);
-        WX_PROF_DEP(acc[2][NT_ - 1]); WX_PROF_DEP(acc[3][NT_ - 1]); WX_PROF_MARK(4);
-        if (!late) { lds_barrier(); WX_PROF_MARK(7); }
+        PROF_DEP(acc[2][NT_ - 1]); PROF_DEP(acc[3][NT_ - 1]); PROF_MARK(4);
+        if (!late) { lds_barrier(); PROF_MARK(7); }
         split_pair(sl + 1, 0);                            // pair 0 of the NEXT slab (raw loaded one slab ago)
-        WX_PROF_DEP(ap[0][0]); WX_PROF_DEP(ap[1][NP - 1]); WX_PROF_MARK(1);
-        if (late) { lds_barrier(); WX_PROF_MARK(7); }
+        PROF_DEP(ap[0][0]); PROF_DEP(ap[1][NP - 1]); PROF_MARK(1);
+        if (late) { lds_barrier(); PROF_MARK(7); }
     }
-    WX_PROF_FLUSH();
+    PROF_FLUSH(g_wx6_prof[w ? 1 : 0], 8, blockIdx.x == 0 && lane == 0 && (w == 0 || w == H / 16 - 1));
     float* slab = slabs + (size_t)blockIdx.x * WG<H>::SLAB;
     // the lane's coordinates once more, from the hardware: so none of them stays in a register through the loop for this
     const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));

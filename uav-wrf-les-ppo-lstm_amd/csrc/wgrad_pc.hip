@@ -24,11 +24,10 @@
 // Results differ from the round-4 path (f32 rows through gemm_h3_tn8_kernel) only in where the power-of-two scale is applied.
 #include "internal.h"
 
+// Where gemm_pc_kernel's time goes (profiles/r05_wgrad_pc_ablation.log, C5's two layer shapes): 2.63 / 4.29 ms whole; no MFMAs
+// -0.57 / -1.27, no B loads in the loop -0.29 / -0.64, no DMA in the loop -0.27 / -0.43, no split / piece writes -0.25 / -0.67.
+// The compile-time ablation switch behind these figures was last present at commit 27bad41.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#ifndef PC_ABL
-#define PC_ABL 0        // ablation builds of gemm_pc_kernel only (tools/ab_wgrad_pc.sh; wrong results, same launches): 1 no MFMAs, 2 no B
-#endif                  // loads in the loop, 3 no DMA in the loop, 4 no split / piece writes
 
 namespace {
 
@@ -344,9 +343,7 @@ __global__ __launch_bounds__(512) void gemm_pc_kernel(const PcArgs a) {
         bq[0][1] = *reinterpret_cast<const f16x8*>(b0p + B_PLANE);
     };
     auto slab_body = [&](PcRegs& r, int buf, int sl) {
-#if PC_ABL != 3
         issue_dma(pa, (sl + 2) % A_STAGES);
-#endif
         unsigned short* np = b_lds + (buf ^ 1) * (B_BUF / 2);
         const unsigned short* b0p = b_lds + buf * (B_BUF / 2) + (wn * 64 + fi) * PKP + 8 * kq;
 #pragma unroll
@@ -356,21 +353,11 @@ __global__ __launch_bounds__(512) void gemm_pc_kernel(const PcArgs a) {
 #pragma unroll
             for (int m = 0; m < 12; ++m) {
                 const int i = m & 3;
-#if PC_ABL != 1
                 if (m < 4) PC_MFMA(acc0[i][j], a0[i], bq[j & 1][0]);
                 else if (m < 8) PC_MFMA(acc1[i][j], a0[i], bq[j & 1][1]);
                 else PC_MFMA(acc1[i][j], a1[i], bq[j & 1][0]);
-#else
-                asm volatile("" :: "v"(a0[i]), "v"(a1[i]), "v"(bq[j & 1][0]), "v"(bq[j & 1][1]));
-#endif
-#if PC_ABL != 4
                 if (m < 6 && (m & 1) && 3 * j + (m >> 1) < 8) commit_pair(r, np, 3 * j + (m >> 1));
-#else
-                if (m == 0 && j == 0) asm volatile("" :: "v"(r.b[0]), "v"(r.b[1]), "v"(r.b[2]), "v"(r.b[3]), "v"(r.sc));
-#endif
-#if PC_ABL != 2
                 if (j == 2 && m >= 4 && (m & 1) == 0) load_b(r, pb, (m - 4) >> 1);          // m = 4, 6, 8, 10
-#endif
                 if (m % 3 == 2) __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -393,24 +380,18 @@ __global__ __launch_bounds__(512) void gemm_pc_kernel(const PcArgs a) {
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int i0 = 2 * h, i1 = 2 * h + 1;
-#if PC_ABL != 1
                 PC_MFMA(acc0[i0][j], a0[i0], bq[1][0]);
                 PC_MFMA(acc0[i1][j], a0[i1], bq[1][0]);
                 PC_MFMA(acc1[i0][j], a0[i0], bq[1][1]);
                 PC_MFMA(acc1[i1][j], a0[i1], bq[1][1]);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 a0[i0] = a_frag(as, ah, i0, 0);
                 a0[i1] = a_frag(as, ah, i1, 0);
-#if PC_ABL != 2
                 if (h == 0) load_sc(r, pb, sl + 3 < nslab);
-#endif
                 asm volatile("" ::: "memory");
                 __builtin_amdgcn_sched_barrier(0);
-#if PC_ABL != 1
                 PC_MFMA(acc1[i0][j], a1[i0], bq[1][0]);
                 PC_MFMA(acc1[i1][j], a1[i1], bq[1][0]);
-#endif
                 __builtin_amdgcn_sched_barrier(0);
                 a1[i0] = a_frag(as, ah, i0, 1);
                 a1[i1] = a_frag(as, ah, i1, 1);

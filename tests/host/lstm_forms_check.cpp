@@ -1,10 +1,14 @@
-// The buffer-form rules of csrc/lstm_forms.h, exercised on the CPU: plain C++17, no HIP header, no device.  Built and run by
+// The buffer-form rules and the mode table of csrc/lstm_forms.h and the workspace carve of csrc/scratch.h, exercised on the CPU:
+// plain C++17, no HIP header, no device.  Built and run by
 // tests/test_lstm_forms_host.py under AddressSanitizer + UBSan; exits 0 when every rule holds, else prints the line and exits 1.
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "lstm_forms.h"
+#include "scratch.h"
 
 static int g_failed = 0;
 #define CHECK(cond)                                                        \
@@ -183,6 +187,117 @@ static void layouts() {
     CHECK(P.NP == 128 && P.RT == 8 && P.bytes() == (size_t)128 * 8 * 4 * 256 * 4 + 2 * (size_t)8 * 128 * 4);
 }
 
+// ---- uav_lstm_mode: 3 arithmetics x the 16 combinations of the four debug bits x H in {64, 96, 128, 256} x I in {6, 256}.
+// The expected values are literals written out from the rules: the step path runs at H = 256 on fp16x3 without STEP_F32; its
+// gate gradients are packed without DG_F32; its BPTT takes dheads (2), and with I = H also fuses dx (1) and stacks (4);
+// X_F32 and GEMM_TN_OFF decide nothing but x_pieces / gemm_tn.
+static void mode_table() {
+    static_assert(UAV_DEBUG_STEP_F32 == 1u && UAV_DEBUG_X_F32 == 2u && UAV_DEBUG_DG_F32 == 4u && UAV_DEBUG_GEMM_TN_OFF == 0x10u, "the rows below");
+    static_assert(UAV_BWD_FUSES_DX == 1 && UAV_BWD_TAKES_DHEADS == 2 && UAV_BWD_STACKS == 4, "the caps below");
+    struct row { unsigned flags; bool step, packed; int caps_i6, caps_i256; bool x_pieces, gemm_tn; };
+    static const row fp16x3_h256[16] = {          // what UAV_ARITH_FP16X3 decides at H = 256
+        {0x00u, true, true, 2, 7, true, true},     {0x01u, false, false, 0, 0, true, true},
+        {0x02u, true, true, 2, 7, false, true},    {0x03u, false, false, 0, 0, false, true},
+        {0x04u, true, false, 2, 7, true, true},    {0x05u, false, false, 0, 0, true, true},
+        {0x06u, true, false, 2, 7, false, true},   {0x07u, false, false, 0, 0, false, true},
+        {0x10u, true, true, 2, 7, true, false},    {0x11u, false, false, 0, 0, true, false},
+        {0x12u, true, true, 2, 7, false, false},   {0x13u, false, false, 0, 0, false, false},
+        {0x14u, true, false, 2, 7, true, false},   {0x15u, false, false, 0, 0, true, false},
+        {0x16u, true, false, 2, 7, false, false},  {0x17u, false, false, 0, 0, false, false},
+    };
+    const int arith[3] = {UAV_ARITH_FP16X3, UAV_ARITH_BF16X6, UAV_ARITH_F32_MFMA}, Hs[4] = {64, 96, 128, 256}, Is[2] = {6, 256};
+    int cases = 0;
+    for (int a : arith)
+        for (const row& r : fp16x3_h256)
+            for (int H : Hs)
+                for (int I : Is) {
+                    const uav_lstm_mode m{a, r.flags};
+                    const bool here = a == UAV_ARITH_FP16X3 && H == 256;      // every other arithmetic, every other H: nothing
+                    CHECK(m.f32_mfma() == (a == 2) && m.bf16x6() == (a == 1));
+                    CHECK(m.step_path(H) == (here ? r.step : false));
+                    CHECK(m.dg_packed(H) == (here ? r.packed : false));
+                    CHECK(m.bwd_caps(I, H) == (here ? (I == 6 ? r.caps_i6 : r.caps_i256) : 0));
+                    CHECK(m.x_pieces() == r.x_pieces && m.gemm_tn() == r.gemm_tn);
+                    ++cases;
+                }
+    CHECK(cases == 3 * 16 * 4 * 2);
+    // the issue's examples, spelled out
+    CHECK((uav_lstm_mode{UAV_ARITH_FP16X3, 0u}.bwd_caps(256, 256)) == (UAV_BWD_TAKES_DHEADS | UAV_BWD_FUSES_DX | UAV_BWD_STACKS));
+    CHECK((uav_lstm_mode{UAV_ARITH_BF16X6, 0u}.bwd_caps(256, 256)) == 0 && (uav_lstm_mode{UAV_ARITH_F32_MFMA, 0u}.bwd_caps(256, 256)) == 0);
+    CHECK((uav_lstm_mode{UAV_ARITH_FP16X3, UAV_DEBUG_STEP_F32}.bwd_caps(256, 256)) == 0 && !(uav_lstm_mode{UAV_ARITH_FP16X3, UAV_DEBUG_STEP_F32}.dg_packed(256)));
+    CHECK((uav_lstm_mode{UAV_ARITH_FP16X3, UAV_DEBUG_DG_F32}.step_path(256)) && !(uav_lstm_mode{UAV_ARITH_FP16X3, UAV_DEBUG_DG_F32}.dg_packed(256)));
+}
+
+// ---- uav_scratch::carve against the seven tail computations it replaced, each written here as its call site wrote it by hand
+// (`ws` + `ws_bytes` arithmetic, its own required front), on a 256 MiB workspace that is never touched.
+template <class T>
+static void carve_is(const uav_scratch& w, size_t n, size_t front, const T* want_tail, size_t want_front_bytes) {
+    T* tail = nullptr;
+    const uav_scratch f = w.carve(n, front, &tail);
+    CHECK(tail == want_tail && f.p == w.p && f.bytes == want_front_bytes && f.num_cu == w.num_cu);
+}
+static void carve_sites(char* ws, size_t ws_bytes, int N, int T, int H, int I, size_t h3_total) {
+    const uav_scratch w{ws, ws_bytes, 256};
+    const size_t slack = 64u << 20;
+    {   // mlp.hip, uav_mlp_bwd: the column-reduction scratch behind the split-K slabs
+        const size_t red_floats = (size_t)512 * 2 * 512 + 2 * 512 + 1024 * 512;
+        carve_is(w, red_floats * sizeof(float), (size_t)(1 << 18) * sizeof(float), (float*)((char*)ws + ws_bytes) - red_floats,
+                 ws_bytes - red_floats * sizeof(float));
+    }
+    {   // lstm_api.hip, LstmWgrad::split_workspace, then ::rows' f32 copy of packed gate gradients + h_prev in front of it
+        const size_t red_floats = (size_t)1024 * 9 * 4 * H + 64;
+        carve_is(w, red_floats * sizeof(float), red_floats * sizeof(float), (float*)((char*)ws + ws_bytes) - red_floats,
+                 ws_bytes - red_floats * sizeof(float));
+        float* red;
+        const uav_scratch sub = w.carve(red_floats * sizeof(float), red_floats * sizeof(float), &red);
+        const size_t f32_bytes = (size_t)N * T * 5 * H * sizeof(float);
+        carve_is(sub, f32_bytes, slack, (float*)((char*)sub.p + sub.bytes - f32_bytes), sub.bytes - f32_bytes);
+        CHECK((char*)red - (sub.p + sub.bytes - f32_bytes) == (ptrdiff_t)f32_bytes);        // the rows end where `red` begins
+    }
+    {   // lstm_generic.hip, forward and backward: the recurrent state / its gradient, 2 N H floats
+        const int64_t NH = (int64_t)N * H;
+        carve_is(w, (size_t)(2 * NH) * sizeof(float), slack, (float*)((char*)ws + ws_bytes) - 2 * NH, ws_bytes - 2 * NH * sizeof(float));
+    }
+    {   // wgrad_pc.hip, lstm_pc_wgrad: 256 blocks' partial sums (1 + CI columns of 4 * 256 values) + the max-scale word's 64 floats
+        const int CI = I == 256 ? 0 : I;
+        const size_t part_floats = (size_t)256 * (1 + CI) * 1024 + 64;
+        carve_is(w, part_floats * 4, slack, (float*)((char*)ws + ws_bytes) - part_floats, ws_bytes - part_floats * 4);
+    }
+    {   // lstm_h3.hip, lstm_h3_fwd: the layer state (H3Layout::total, worked out by hand as in test_lstm_h3_layout_host.py); the
+        // x piece planes lie in front of it, in what the front leaves over the slack
+        carve_is(w, h3_total, slack, (char*)ws + ws_bytes - h3_total, ws_bytes - h3_total);
+        char* base;
+        CHECK(w.carve(h3_total, slack, &base).bytes - slack == ws_bytes - h3_total - slack);
+    }
+}
+static void scratch_carving() {
+    const size_t W = (size_t)256 << 20;
+    char* ws = (char*)malloc(W);
+    CHECK(ws != nullptr);
+    if (!ws) return;
+    carve_sites(ws, W, 64, 8, 256, 256, 2363392);            // N = 64, I = 256: 2 * 65536 + 2 * 65536 + 1048576 + 1048576 + 4096
+    carve_sites(ws, W, 16, 8, 64, 6, 1347584);               // N = 16, I = 6:   2 * 16384 + 2 * 65536 + 1048576 + 131072 + 4096
+    const uav_scratch w{ws, W, 256};
+    float* t = (float*)ws;
+    // refused: more than the slice; the slice exactly but a byte of front asked for; n and front that only together exceed it
+    CHECK(w.carve(W + 1, 0, &t).p == nullptr && t == nullptr);
+    t = (float*)ws;
+    CHECK(w.carve(W, 1, &t).p == nullptr && t == nullptr);
+    t = (float*)ws;
+    CHECK(w.carve(W / 2 + 4, W / 2, &t).p == nullptr && t == nullptr && w.carve(W / 2 + 4, W / 2, &t).bytes == 0);
+    CHECK(w.carve((size_t)-1, (size_t)-1, &t).p == nullptr);                        // no wrap-around in n + front
+    // exactly fitting: granted
+    CHECK(w.carve(W / 2, W / 2, &t).p == ws && (char*)t == ws + W / 2);
+    CHECK(w.carve(W, 0, &t).p == ws && (char*)t == ws && w.carve(W, 0, &t).bytes == 0);
+    // a zero-byte carve returns the slice unchanged
+    const uav_scratch z = w.carve(0, 0, &t);
+    CHECK(z.p == w.p && z.bytes == w.bytes && z.num_cu == w.num_cu && (char*)t == ws + W);
+    // the small workspace the entry points refuse: 1 MiB against the 64 MiB the GEMM slabs are promised
+    const uav_scratch small{ws, (size_t)1 << 20, 256};
+    CHECK(small.carve(4096, 64u << 20, &t).p == nullptr);
+    free(ws);
+}
+
 int main() {
     tile_capacity();
     tile_write_and_read();
@@ -192,6 +307,8 @@ int main() {
     reads_at_h256();
     stash_slots();
     layouts();
+    mode_table();
+    scratch_carving();
     if (g_failed) printf("%d checks failed\n", g_failed);
     else printf("lstm_forms: all checks passed\n");
     return g_failed ? 1 : 0;

@@ -6,18 +6,26 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/uavppo.h"
-#include "lstm_forms.h"      // DgTile, DgPack, uav_lstm_forms
+#include "lstm_forms.h"      // DgTile, DgPack, uav_lstm_forms, uav_lstm_mode
+#include "scratch.h"         // uav_scratch
 
+// One per uav_create, never copied: a helper that needs less than the whole handle takes the part as a value (the mode, a
+// workspace slice).
 struct uav_ctx {
+    uav_ctx() = default;
+    uav_ctx(const uav_ctx&) = delete;
+    uav_ctx& operator=(const uav_ctx&) = delete;
     int device;
     int num_cu;
     void* ws;          // scratch for two-stage reductions / split-K slabs
     size_t ws_bytes;
+    uav_scratch scratch() const { return uav_scratch{(char*)ws, ws_bytes, num_cu}; }      // the whole workspace
     double* pow075;    // device table pow(i, 0.75), i = 0..5000 (env_core.h)
     double* wave;      // device tables sin(0.05 x) | cos(0.07 y), x, y = 0..499 (env_core.h field_at)
     double* ftab;      // device tables of the table-driven f64 log / cos-sin / exp (env_core.h ft_*)
-    int lstm_arith;    // UAV_ARITH_*: how the LSTM sequence kernels evaluate their f32 matrix products (uav_set_lstm_arith)
-    unsigned debug;    // UAV_DEBUG_*: A/B switches of the h = 256 step path (uav_set_debug_flags)
+    // uav_set_lstm_arith / uav_set_debug_flags.  No getenv on any call path: the UAV_LSTM_BF16X6 / UAV_LSTM_F32_MFMA environment
+    // variables are read ONCE, by uav_create, as the handle's initial mode.
+    uav_lstm_mode mode;
     hipStream_t side[3];      // uav_lstm_bwd_stack: one stream per layer below the top (created on first use)
     hipEvent_t side_ev[8];    // fork / join + a small ring of per-step hand-off events per side stream
     void* comm;               // ncclComm_t of this process's rank (comm.hip: uav_comm_init), or NULL
@@ -25,20 +33,6 @@ struct uav_ctx {
     uav_lstm_forms forms;     // what the dgates / stash buffers of the LSTM update hold (lstm_forms.h; decided in lstm_api.hip)
     double* ppo_diag;  // device f64[UAV_PPO_DIAG_N] the loss-bearing entry points overwrite with their diagnostic sums, or NULL (uav_set_ppo_diag)
 };
-// arithmetic / debug switches of the call in flight on this thread (set from the handle by the LSTM entry points; the
-// launch helpers below them have no ctx argument).  No getenv on any call path: the UAV_LSTM_BF16X6 / UAV_LSTM_F32_MFMA
-// environment variables are read ONCE, by uav_create, as the handle's initial mode.
-extern thread_local int g_uav_arith;
-extern thread_local unsigned g_uav_debug;
-static inline bool uav_want_f32_mfma() { return g_uav_arith == UAV_ARITH_F32_MFMA; }
-static inline bool uav_want_bf16x6() { return g_uav_arith == UAV_ARITH_BF16X6; }
-static inline bool uav_debug(unsigned bit) { return (g_uav_debug & bit) != 0; }
-static inline void uav_enter(const struct uav_ctx* ctx);
-
-static inline void uav_enter(const uav_ctx* ctx) {
-    g_uav_arith = ctx->lstm_arith;
-    g_uav_debug = ctx->debug;
-}
 
 void uav_set_error(const char* fmt, ...);
 

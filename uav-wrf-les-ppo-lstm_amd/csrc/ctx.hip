@@ -6,8 +6,6 @@
 #include "internal.h"
 
 static thread_local char g_err[512] = "";
-thread_local int g_uav_arith = 0;
-thread_local unsigned g_uav_debug = 0;
 
 void uav_set_error(const char* fmt, ...) {
     va_list ap;
@@ -54,9 +52,9 @@ int uav_create(uav_ctx** out, int device, size_t ws_bytes) {
     c->comm_world = 0;
     c->ppo_diag = nullptr;
     // process-level override of the default arithmetic, read here once (never on a call path)
-    c->lstm_arith = getenv("UAV_LSTM_F32_MFMA") ? UAV_ARITH_F32_MFMA : (getenv("UAV_LSTM_BF16X6") ? UAV_ARITH_BF16X6 : UAV_ARITH_FP16X3);
-    c->debug = (getenv("UAV_LSTM_STEP_F32") ? UAV_DEBUG_STEP_F32 : 0u) | (getenv("UAV_LSTM_X_F32") ? UAV_DEBUG_X_F32 : 0u) |
-               (getenv("UAV_LSTM_DG_F32") ? UAV_DEBUG_DG_F32 : 0u);
+    c->mode.arith = getenv("UAV_LSTM_F32_MFMA") ? UAV_ARITH_F32_MFMA : (getenv("UAV_LSTM_BF16X6") ? UAV_ARITH_BF16X6 : UAV_ARITH_FP16X3);
+    c->mode.debug = (getenv("UAV_LSTM_STEP_F32") ? UAV_DEBUG_STEP_F32 : 0u) | (getenv("UAV_LSTM_X_F32") ? UAV_DEBUG_X_F32 : 0u) |
+                    (getenv("UAV_LSTM_DG_F32") ? UAV_DEBUG_DG_F32 : 0u);
     if (hipMalloc(&c->ws, ws_bytes) != hipSuccess) {
         (void)hipFree(c->ws);
         delete c;
@@ -77,14 +75,14 @@ int uav_create(uav_ctx** out, int device, size_t ws_bytes) {
 
 int uav_set_lstm_arith(uav_ctx* ctx, int mode) {
     UAV_REQUIRE(ctx && mode >= UAV_ARITH_FP16X3 && mode <= UAV_ARITH_F32_MFMA, "uav_set_lstm_arith: bad argument");
-    ctx->lstm_arith = mode;
+    ctx->mode.arith = mode;
     return 0;
 }
-int uav_get_lstm_arith(const uav_ctx* ctx) { return ctx ? ctx->lstm_arith : -1; }
+int uav_get_lstm_arith(const uav_ctx* ctx) { return ctx ? ctx->mode.arith : -1; }
 
 int uav_set_debug_flags(uav_ctx* ctx, unsigned flags) {
     UAV_REQUIRE(ctx && (flags & ~(UAV_DEBUG_STEP_F32 | UAV_DEBUG_X_F32 | UAV_DEBUG_DG_F32 | UAV_DEBUG_GEMM_TN_OFF)) == 0, "uav_set_debug_flags: bad argument");
-    ctx->debug = flags;
+    ctx->mode.debug = flags;
     return 0;
 }
 

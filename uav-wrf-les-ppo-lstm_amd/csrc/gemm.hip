@@ -264,14 +264,14 @@ __global__ __launch_bounds__(256) void rows_dot_kernel(int64_t M, int K, const f
     }
 }
 
-int gemm_f32(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k,
+int gemm_f32(const uav_scratch& ws, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k,
              const float* B, int64_t sb_k, int64_t sb_n, float* C, int64_t ldc, const float* bias,
              int accumulate, hipStream_t st) {
     // the few-columns form (see rows_dot_kernel): NT operands with contiguous k, 16-byte aligned rows
-    if (ctx && A && B && C && N >= 1 && N <= 8 && K >= 4 && K <= 512 && K % 4 == 0 && sa_k == 1 && sb_k == 1 && !accumulate && M >= 1 &&
+    if (A && B && C && N >= 1 && N <= 8 && K >= 4 && K <= 512 && K % 4 == 0 && sa_k == 1 && sb_k == 1 && !accumulate && M >= 1 &&
         sa_m % 4 == 0 && sb_n % 4 == 0 && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0) {
         int64_t nb = (M + 15) / 16;                                     // 4 waves x 4 rows per trip
-        if (nb > 8 * ctx->num_cu) nb = 8 * ctx->num_cu;
+        if (nb > 8 * ws.num_cu) nb = 8 * ws.num_cu;
         if (K <= 256)
             hipLaunchKernelGGL((rows_dot_kernel<8, 1>), dim3((unsigned)nb), dim3(256), 0, st, M, (int)K, A, sa_m, B, sb_n, (int)N, C, ldc, bias);
         else
@@ -279,7 +279,7 @@ int gemm_f32(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int6
         UAV_LAUNCH_CHECK();
         return 0;
     }
-    UAV_REQUIRE(ctx && A && B && C && M > 0 && N > 0 && K > 0, "uav_gemm_f32: bad argument");
+    UAV_REQUIRE(A && B && C && M > 0 && N > 0 && K > 0, "uav_gemm_f32: bad argument");
     const bool big = (M >= 128 && N >= 128);          // 128x128 tile for the large shapes
     const int bm = big ? BM2 : BM, bn = big ? BN2 : BN;
     const int64_t tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
@@ -287,17 +287,17 @@ int gemm_f32(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int6
     // split K when the tile grid cannot fill the chip and K is deep
     int64_t S = 1;
     const int64_t tiles = tm * tn;
-    if (tiles < 2 * ctx->num_cu && K >= 16 * BK) {
-        S = (2 * ctx->num_cu + tiles - 1) / tiles;
+    if (tiles < 2 * ws.num_cu && K >= 16 * BK) {
+        S = (2 * ws.num_cu + tiles - 1) / tiles;
         const int64_t maxS_k = K / (8 * BK);
         if (S > maxS_k) S = maxS_k;
-        const int64_t maxS_ws = (int64_t)(ctx->ws_bytes / sizeof(float)) / (M * N);
+        const int64_t maxS_ws = (int64_t)(ws.bytes / sizeof(float)) / (M * N);
         if (S > maxS_ws) S = maxS_ws;
         if (S < 1) S = 1;
     }
     int64_t kps = ((K + S - 1) / S + BK - 1) / BK * BK;
     S = (K + kps - 1) / kps;
-    float* slabs = (S > 1) ? (float*)ctx->ws : nullptr;
+    float* slabs = (S > 1) ? (float*)ws.p : nullptr;
     if (big)
         hipLaunchKernelGGL(gemm_f32_128_kernel, dim3((unsigned)tm, (unsigned)tn, (unsigned)S), dim3(256), 0, st, M, N, K, A,
                            sa_m, sa_k, B, sb_k, sb_n, C, ldc, bias, accumulate, kps, slabs);
@@ -316,5 +316,6 @@ int gemm_f32(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int6
 extern "C" int uav_gemm_f32(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m,
                             int64_t sa_k, const float* B, int64_t sb_k, int64_t sb_n, float* C, int64_t ldc,
                             const float* bias, int accumulate, uav_stream stream) {
-    return gemm_f32(ctx, M, N, K, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, bias, accumulate, as_stream(stream));
+    UAV_REQUIRE(ctx, "uav_gemm_f32: bad argument");
+    return gemm_f32(ctx->scratch(), M, N, K, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, bias, accumulate, as_stream(stream));
 }

@@ -461,12 +461,12 @@ __global__ __launch_bounds__(256) void h3_splitk_reduce_kernel(const float* __re
 }
 
 // split-K plan shared by the two kernels: whole groups of 8 splits (one per XCD) when the tile grid cannot fill the chip
-static void h3_plan(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, int64_t tiles, int64_t& S, int64_t& kps) {
+static void h3_plan(const uav_scratch& ws, int64_t M, int64_t N, int64_t K, int64_t tiles, int64_t& S, int64_t& kps) {
     S = 1;
-    if (tiles < ctx->num_cu && K >= 64 * HK) {
-        S = (ctx->num_cu + tiles - 1) / tiles;
+    if (tiles < ws.num_cu && K >= 64 * HK) {
+        S = (ws.num_cu + tiles - 1) / tiles;
         S = (S + 7) / 8 * 8;
-        const int64_t max_k = K / (16 * HK), max_ws = (int64_t)(ctx->ws_bytes / sizeof(float)) / (M * N);
+        const int64_t max_k = K / (16 * HK), max_ws = (int64_t)(ws.bytes / sizeof(float)) / (M * N);
         if (S > max_k) S = max_k;
         if (S > max_ws) S = max_ws;
         if (S < 1) S = 1;
@@ -476,14 +476,14 @@ static void h3_plan(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, int64_t tiles
 }
 
 // dW-shaped products (see gemm_h3_tn8_kernel): A [K][M] and B [K][N] contiguous along their rows
-int launch_h3_tn(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
+int launch_h3_tn(const uav_scratch& ws, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
                  float* C, int64_t ldc, int accumulate, const unsigned* a_absmax, hipStream_t st) {
     constexpr int BN = 256;
     const int tm = (int)(M / HM), tn = (int)(N / BN);
     const int64_t tiles = (int64_t)tm * tn;
     int64_t S, kps;
-    h3_plan(ctx, M, N, K, tiles, S, kps);
-    float* slabs = (S > 1) ? (float*)ctx->ws : nullptr;
+    h3_plan(ws, M, N, K, tiles, S, kps);
+    float* slabs = (S > 1) ? (float*)ws.p : nullptr;
     const int64_t G = (S > 1) ? tiles : tn, ngroups = (S > 1) ? S : tm;
     const int64_t grid = 8 * G * ((ngroups + 7) / 8);
     UAV_REQUIRE(grid < (1ll << 31), "gemm_h3: grid too large");
@@ -501,13 +501,13 @@ int launch_h3_tn(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, 
 }
 
 template <int BN, bool AKC, bool BKC>
-int launch_h3(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+int launch_h3(const uav_scratch& ws, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
               int64_t ldc, const float* bias, int accumulate, const unsigned* a_absmax, hipStream_t st) {
     const int tm = (int)(M / HM), tn = (int)(N / BN);
     const int64_t tiles = (int64_t)tm * tn;
     int64_t S, kps;
-    h3_plan(ctx, M, N, K, tiles, S, kps);
-    float* slabs = (S > 1) ? (float*)ctx->ws : nullptr;
+    h3_plan(ws, M, N, K, tiles, S, kps);
+    float* slabs = (S > 1) ? (float*)ws.p : nullptr;
     const int64_t G = (S > 1) ? tiles : tn, ngroups = (S > 1) ? S : tm;
     const int64_t grid = 8 * G * ((ngroups + 7) / 8);
     UAV_REQUIRE(grid < (1ll << 31), "gemm_h3: grid too large");
@@ -540,28 +540,29 @@ bool gemm_h3_ok(int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, i
 }
 
 // The dW shape (both operands contiguous along their row index, whole 32-row slabs, 256-column tiles, dwordx4 loads) goes to
-// gemm_h3_tn8_kernel unless UAV_DEBUG_GEMM_TN_OFF asks for the older kernel (same results bit for bit: an A/B switch).
-bool gemm_h3_tn_ok(int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k, const float* B, int64_t sb_k,
-                   int64_t sb_n) {
-    if (uav_debug(UAV_DEBUG_GEMM_TN_OFF)) return false;
+// gemm_h3_tn8_kernel unless UAV_DEBUG_GEMM_TN_OFF asks for the older kernel (same results bit for bit: an A/B switch; `tn` is the
+// caller's uav_lstm_mode::gemm_tn).
+static bool gemm_h3_tn_ok(bool tn, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k, const float* B,
+                          int64_t sb_k, int64_t sb_n) {
+    if (!tn) return false;
     if (sa_m != 1 || sb_n != 1 || sa_k == 1 || sb_k == 1) return false;
     if (M < HM || M % HM || N < 256 || N % 256 || K < HK || K % HK) return false;
     if ((sa_k & 3) || (sb_k & 3) || sa_k >= (1 << 23) || sb_k >= (1 << 23)) return false;
     return ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0;
 }
 
-int gemm_h3(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k, const float* B,
-            int64_t sb_k, int64_t sb_n, float* C, int64_t ldc, const float* bias, int accumulate, const unsigned* a_absmax,
-            hipStream_t st) {
-    UAV_REQUIRE(ctx && A && B && C, "gemm_h3: NULL argument");
+int gemm_h3(const uav_scratch& ws, bool tn, int64_t M, int64_t N, int64_t K, const float* A, int64_t sa_m, int64_t sa_k,
+            const float* B, int64_t sb_k, int64_t sb_n, float* C, int64_t ldc, const float* bias, int accumulate,
+            const unsigned* a_absmax, hipStream_t st) {
+    UAV_REQUIRE(A && B && C, "gemm_h3: NULL argument");
     UAV_REQUIRE(gemm_h3_ok(M, N, K, A, sa_m, sa_k, B, sb_k, sb_n), "gemm_h3: shape / strides not supported (M %% 128, N %% 128, "
                 "unit stride along k or along the row index of each operand)");
     const bool akc = sa_k == 1, bkc = sb_k == 1;
     const int64_t lda = akc ? sa_m : sa_k, ldb = bkc ? sb_n : sb_k;
     const bool wide = N % 256 == 0;
-    if (!bias && gemm_h3_tn_ok(M, N, K, A, sa_m, sa_k, B, sb_k, sb_n))
-        return launch_h3_tn(ctx, M, N, K, A, lda, B, ldb, C, ldc, accumulate, a_absmax, st);
-#define H3_GO(BN, AK, BK_) return launch_h3<BN, AK, BK_>(ctx, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, a_absmax, st)
+    if (!bias && gemm_h3_tn_ok(tn, M, N, K, A, sa_m, sa_k, B, sb_k, sb_n))
+        return launch_h3_tn(ws, M, N, K, A, lda, B, ldb, C, ldc, accumulate, a_absmax, st);
+#define H3_GO(BN, AK, BK_) return launch_h3<BN, AK, BK_>(ws, M, N, K, A, lda, B, ldb, C, ldc, bias, accumulate, a_absmax, st)
     if (wide) {
         if (akc && bkc) H3_GO(256, true, true);
         if (akc) H3_GO(256, true, false);
@@ -579,7 +580,6 @@ extern "C" int uav_gemm_f16x3(uav_ctx* ctx, int64_t M, int64_t N, int64_t K, con
                               const float* B, int64_t sb_k, int64_t sb_n, float* C, int64_t ldc, const float* bias,
                               int accumulate, const float* a_absmax, uav_stream stream) {
     UAV_REQUIRE(ctx, "uav_gemm_f16x3: NULL handle");
-    uav_enter(ctx);
-    return gemm_h3(ctx, M, N, K, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, bias, accumulate,
+    return gemm_h3(ctx->scratch(), ctx->mode.gemm_tn(), M, N, K, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, bias, accumulate,
                    reinterpret_cast<const unsigned*>(a_absmax), as_stream(stream));
 }

@@ -957,10 +957,10 @@ static constexpr auto bwd_split_kernel() {
     else return TILE ? &lstm_bwd_x6k_kernel_tile<H> : &lstm_bwd_x6k_kernel<H>;
 }
 
-// f(P{}) with the split policy of the handle's mode
+// f(P{}) with the split policy of mode m
 template <class F>
-static int with_split(F&& f) {
-    return uav_want_bf16x6() ? f(SplitBf16x6{}) : f(SplitF16x3{});
+static int with_split(const uav_lstm_mode& m, F&& f) {
+    return m.bf16x6() ? f(SplitBf16x6{}) : f(SplitF16x3{});
 }
 
 template <class P, int H>
@@ -993,13 +993,13 @@ static int launch_fwd_split(bool fuse, const float* x, const float* keep, const 
 }
 
 template <int H>
-static int launch_fwd(bool fuse, const float* x, const float* keep, const float* h0, const float* c0,
+static int launch_fwd(const uav_lstm_mode& m, bool fuse, const float* x, const float* keep, const float* h0, const float* c0,
                       const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, int N, int T, int I,
                       float* y, float* hn, float* cn, float* stash, const float* w_head, const float* b_head, int NHD,
                       float* heads, bool* heads_done, hipStream_t st) {
-    if (!uav_want_f32_mfma()) {          // the matrix products as 16-bit piece products at f32 accuracy, heads fused
+    if (!m.f32_mfma()) {                 // the matrix products as 16-bit piece products at f32 accuracy, heads fused
         *heads_done = heads != nullptr;
-        return with_split([&](auto p) {
+        return with_split(m, [&](auto p) {
             return launch_fwd_split<decltype(p), H>(fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash,
                                                     w_head, b_head, NHD, heads, st);
         });
@@ -1031,18 +1031,18 @@ static int launch_bwd(const float* keep, const float* stash, const float* w_hh, 
 static_assert(MT == DgTile::MT, "a tile of the gate-gradient tile form is one BPTT workgroup's envs");
 
 // ---- what this file gives the entry points (lstm_api.hip, through internal.h)
-int lstm_fwd_seq(bool fuse, const float* x, const float* keep, const float* h0, const float* c0, const float* w_ih, const float* w_hh,
-                 const float* b_ih, const float* b_hh, int N, int T, int I, int H, float* y, float* hn, float* cn, float* stash,
-                 const float* w_head, const float* b_head, int NHD, float* heads, bool* heads_done, hipStream_t st) {
-    return H == 64 ? launch_fwd<64>(fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, NHD, heads, heads_done, st)
-                   : launch_fwd<128>(fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, NHD, heads, heads_done, st);
+int lstm_fwd_seq(const uav_lstm_mode& m, bool fuse, const float* x, const float* keep, const float* h0, const float* c0, const float* w_ih,
+                 const float* w_hh, const float* b_ih, const float* b_hh, int N, int T, int I, int H, float* y, float* hn, float* cn,
+                 float* stash, const float* w_head, const float* b_head, int NHD, float* heads, bool* heads_done, hipStream_t st) {
+    return H == 64 ? launch_fwd<64>(m, fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, NHD, heads, heads_done, st)
+                   : launch_fwd<128>(m, fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, y, hn, cn, stash, w_head, b_head, NHD, heads, heads_done, st);
 }
 
-int lstm_bwd_seq(const float* keep, const float* stash, const float* w_hh, const float* dy, const float* dheads,
-                 const float* w_head, int NH, const float* dhn, const float* dcn, int N, int T, int H, float* dgates, bool tile,
-                 float* dh0, float* dc0, hipStream_t st) {
-    if (dheads && NH <= 7 && !uav_want_f32_mfma()) {   // the PPO path: split MFMA, K split over waves
-        return with_split([&](auto p) {
+int lstm_bwd_seq(const uav_lstm_mode& m, const float* keep, const float* stash, const float* w_hh, const float* dy, const float* dheads,
+                 const float* w_head, int NH, const float* dhn, const float* dcn, int N, int T, int H, float* dgates, bool tile, float* dh0,
+                 float* dc0, hipStream_t st) {
+    if (dheads && NH <= 7 && !m.f32_mfma()) {   // the PPO path: split MFMA, K split over waves
+        return with_split(m, [&](auto p) {
             using P = decltype(p);
             return H == 64 ? launch_bwd_split<P, 64>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, tile, dh0, dc0, st)
                            : launch_bwd_split<P, 128>(keep, stash, w_hh, dheads, w_head, NH, dhn, dcn, N, T, dgates, tile, dh0, dc0, st);

@@ -38,7 +38,7 @@ struct LstmWgrad {
     hipStream_t st;
     // what the trailing dx = dG W_ih product takes over from the path that ran: the workspace its slabs may use, where max |dG|
     // lies for the fp16-split product (NULL: exact f32), and the gate gradients as f32 rows
-    uav_ctx ws;
+    uav_scratch ws;
     float* red = nullptr;
     unsigned* amax = nullptr;
 
@@ -51,24 +51,23 @@ struct LstmWgrad {
     int product(int64_t M, int64_t Nn, int64_t K, const float* A, int64_t sa_m, int64_t sa_k, const float* B, int64_t sb_k,
                 int64_t sb_n, float* C, int64_t ldc) {
         if (amax && gemm_h3_ok(M, Nn, K, A, sa_m, sa_k, B, sb_k, sb_n))
-            return gemm_h3(&ws, M, Nn, K, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, nullptr, 0, amax, st);
-        return gemm_f32(&ws, M, Nn, K, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, nullptr, 0, st);
+            return gemm_h3(ws, ctx->mode.gemm_tn(), M, Nn, K, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, nullptr, 0, amax, st);
+        return gemm_f32(ws, M, Nn, K, A, sa_m, sa_k, B, sb_k, sb_n, C, ldc, nullptr, 0, st);
     }
 
     // the other two paths: column sums use the tail of the workspace, the split-K slabs everything in front of it
     int split_workspace() {
         UAV_REQUIRE(stash, "uav_lstm_wgrad: stash is required when I > 6");
         const size_t red_floats = (size_t)1024 * 9 * 4 * H + 64;      // colsum (+ dG^T x) partials + the word for max |dG|
-        UAV_REQUIRE(ctx->ws_bytes >= red_floats * sizeof(float) * 2, "uav_lstm_wgrad: workspace too small");
-        red = (float*)((char*)ctx->ws + ctx->ws_bytes) - red_floats;
-        ws.ws_bytes = ctx->ws_bytes - red_floats * sizeof(float);
+        ws = ctx->scratch().carve(red_floats * sizeof(float), red_floats * sizeof(float), &red);
+        UAV_REQUIRE(ws.p, "uav_lstm_wgrad: workspace too small");
         return 0;
     }
     int head_grad() {        // dW_head = dheads^T y [n_heads][H]: a stream over y with the few dheads columns riding along
         if (!dheads) return 0;
         if (H % 4 == 0 && (reinterpret_cast<uintptr_t>(y) & 15) == 0)
-            return colsum_xw(&ws, y, NT(), H, dheads, n_heads, nullptr, dw_head, red, nullptr, st, 1);
-        return gemm_f32(&ws, n_heads, H, NT(), dheads, 1, n_heads, y, H, 1, dw_head, H, nullptr, 0, st);
+            return colsum_xw(ws, y, NT(), H, dheads, n_heads, nullptr, dw_head, red, nullptr, st, 1);
+        return gemm_f32(ws, n_heads, H, NT(), dheads, 1, n_heads, y, H, 1, dw_head, H, nullptr, 0, st);
     }
 
     // h = 256 on the fp16-split step path: `dgates` is the BPTT's piece chunks (lstm_forms.h: DgPack), read as they are by
@@ -90,10 +89,10 @@ struct LstmWgrad {
         int64_t ld_hprev = 6 * H;
         if (packed) {
             const size_t f32_bytes = (size_t)NT() * 5 * H * sizeof(float);     // gate gradients 4H + h_prev H (this mode's forward
-            UAV_REQUIRE(ws.ws_bytes >= f32_bytes + (64u << 20), "uav_lstm_wgrad (h=256, I=%d%s): needs %zu bytes of workspace for "
+            float* out;
+            ws = ws.carve(f32_bytes, 64u << 20, &out);
+            UAV_REQUIRE(ws.p, "uav_lstm_wgrad (h=256, I=%d%s): needs %zu bytes of workspace for "
                         "the gate gradients and h_prev as f32 rows", I, dx ? ", dx" : "", f32_bytes + (64u << 20));   // writes no slot)
-            float* out = (float*)((char*)ws.ws + ws.ws_bytes - f32_bytes);
-            ws.ws_bytes -= f32_bytes;
             if ((rc = lstm_pc_unpack(dgates, N, T, out, st))) return rc;
             float* hp = out + (size_t)NT() * 4 * H;
             if ((rc = lstm_pc_hprev_rows(y, keep, h0, N, T, hp, st))) return rc;
@@ -102,11 +101,11 @@ struct LstmWgrad {
             ld_hprev = H;
         }
         const bool aligned = (reinterpret_cast<uintptr_t>(dgates) & 15) == 0;
-        if (!uav_want_f32_mfma() && !uav_want_bf16x6() && aligned) amax = reinterpret_cast<unsigned*>(red + (size_t)1024 * 9 * 4 * H);
+        if (!ctx->mode.f32_mfma() && !ctx->mode.bf16x6() && aligned) amax = reinterpret_cast<unsigned*>(red + (size_t)1024 * 9 * 4 * H);
         // a narrow input (layer 1: obs + trend, I <= 8): dW_ih = dG^T x rides on the bias gradient's pass over dG
         const bool narrow = I <= 8 && aligned;
-        if (narrow) rc = colsum_xw(&ws, dgates, NT(), 4 * H, x, I, db, dw_ih, red, amax, st);
-        else rc = colsum_absmax(&ws, dgates, NT(), 4 * H, db, red, amax, st);
+        if (narrow) rc = colsum_xw(ws, dgates, NT(), 4 * H, x, I, db, dw_ih, red, amax, st);
+        else rc = colsum_absmax(ws, dgates, NT(), 4 * H, db, red, amax, st);
         if (rc) return rc;
         if (db_hh) UAV_CHECK_HIP(hipMemcpyAsync(db_hh, db, (size_t)4 * H * sizeof(float), hipMemcpyDeviceToDevice, st));
         if ((rc = product(4 * H, H, NT(), dgates, 1, 4 * H, hprev, ld_hprev, 1, dw_hh, H))) return rc;
@@ -119,20 +118,20 @@ struct LstmWgrad {
 static int lstm_bwd_steps(uav_ctx* ctx, const float* keep, const float* stash, const float* w_hh, const float* dy, const float* dheads,
                           const float* w_head, int n_heads, const float* dhn, const float* dcn, int N, int T, int H, float* dgates,
                           float* dh0, float* dc0, const float* w_ih, int I, float* dx, hipStream_t st) {
-    const bool h3 = lstm_h3_step_path(H);
+    const bool h3 = ctx->mode.step_path(H);
     UAV_REQUIRE(dy || h3, "uav_lstm_bwd: this hidden size / arithmetic takes dy (form dheads . w_head with uav_gemm_f32); "
                 "see uav_lstm_bwd_caps");
-    UAV_REQUIRE(!dx || (w_ih && (lstm_h3_bwd_caps(I, H) & UAV_BWD_FUSES_DX)), "uav_lstm_bwd: dx is formed here only when uav_lstm_bwd_caps(ctx, I, H) "
+    UAV_REQUIRE(!dx || (w_ih && (ctx->mode.bwd_caps(I, H) & UAV_BWD_FUSES_DX)), "uav_lstm_bwd: dx is formed here only when uav_lstm_bwd_caps(ctx, I, H) "
                 "says so (H = 256 = I on the fp16-split arithmetic); otherwise ask uav_lstm_wgrad for it");
     if (h3) return lstm_h3_bwd(ctx, keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, dgates, dh0, dc0, w_ih, dx, st);
     return lstm_generic_bwd(ctx, keep, stash, w_hh, dy, dhn, dcn, N, T, H, dgates, dh0, dc0, st);
 }
 
 // the checks of one stepper step, in the name of the entry point `who`
-static int stepper_check(const char* who, const uav_stepper_call& c, int N, int T, int H) {
+static int stepper_check(const char* who, const uav_lstm_mode& m, const uav_stepper_call& c, int N, int T, int H) {
     UAV_REQUIRE(c.state && c.x && c.y && c.stash && c.hn && c.cn, "%s: NULL argument", who);
     UAV_REQUIRE(uav_lstm_stepper_bytes(N, c.I, H) != 0 && T > 0 && c.t >= 0 && c.t < T, "%s: bad shape (N=%d T=%d t=%d I=%d H=%d)", who, N, T, c.t, c.I, H);
-    UAV_REQUIRE(lstm_h3_step_path(H), "%s: only the fp16-split arithmetic steps (uav_set_lstm_arith)", who);
+    UAV_REQUIRE(m.step_path(H), "%s: only the fp16-split arithmetic steps (uav_set_lstm_arith)", who);
     UAV_REQUIRE(!c.below || c.I == 256, "%s: `below` needs I = 256 (the layer below's hidden size), got %d", who, c.I);
     return 0;
 }
@@ -144,59 +143,54 @@ int uav_lstm_fwd(uav_ctx* ctx, const float* x, const float* keep, const float* h
                  float* hn, float* cn, float* stash, const float* w_head, const float* b_head, int n_heads, float* heads,
                  uav_stream stream) {
     UAV_REQUIRE(ctx && x && h0 && c0 && w_ih && w_hh && b_ih && b_hh && y && hn && cn, "uav_lstm_fwd: NULL argument");
-    uav_enter(ctx);
     UAV_REQUIRE(N > 0 && T > 0 && I > 0, "uav_lstm_fwd: N=%d T=%d I=%d", N, T, I);
     UAV_REQUIRE(!heads || (w_head && b_head && n_heads > 0 && n_heads <= 8), "uav_lstm_fwd: heads needs w_head, b_head, 1..8 heads");
     hipStream_t st = as_stream(stream);
+    const uav_lstm_mode& m = ctx->mode;
     const bool persistent = (H == 64 || H == 128);
     const bool fuse = I <= 8 && persistent;
-    const bool step256 = lstm_h3_step_path(H);      // h = 256: one fused launch per step, input projection inside
+    const bool step256 = m.step_path(H);      // h = 256: one fused launch per step, input projection inside
     if (step256) UAV_REQUIRE(stash, "uav_lstm_fwd: stash is required when H is not 64/128");
     if (!fuse && !step256) {
         // time-batched input projection into the gates slot of the stash: pre = x W_ih^T + (b_ih + b_hh)
         UAV_REQUIRE(stash, "uav_lstm_fwd: stash is required when I > 8 or H is not 64/128");
         float* bsum = (float*)ctx->ws;   // 4H floats at the head of the workspace... kept clear of GEMM slabs below
-        uav_ctx sub = *ctx;
-        sub.ws = (char*)ctx->ws + 65536;
-        sub.ws_bytes = ctx->ws_bytes - 65536;
+        const uav_scratch sub{(char*)ctx->ws + 65536, ctx->ws_bytes - 65536, ctx->num_cu};
         hipLaunchKernelGGL(add2_kernel, dim3((4 * H + 255) / 256), dim3(256), 0, st, b_ih, b_hh, bsum, 4 * H);
-        int rc = gemm_f32(&sub, (int64_t)N * T, 4 * H, I, x, I, 1, w_ih, 1, I, stash, 6 * H, bsum, 0, st);
+        int rc = gemm_f32(sub, (int64_t)N * T, 4 * H, I, x, I, 1, w_ih, 1, I, stash, 6 * H, bsum, 0, st);
         if (rc) return rc;
     }
     bool heads_done = false;
     int rc;
     if (persistent)
-        rc = lstm_fwd_seq(fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, H, y, hn, cn, stash, w_head, b_head, n_heads, heads, &heads_done, st);
+        rc = lstm_fwd_seq(m, fuse, x, keep, h0, c0, w_ih, w_hh, b_ih, b_hh, N, T, I, H, y, hn, cn, stash, w_head, b_head, n_heads, heads, &heads_done, st);
     else  // any other hidden size: one launch per time step (lstm_h3.hip, lstm_generic.hip)
         rc = step256 ? lstm_h3_fwd(ctx, x, I, w_ih, b_ih, b_hh, keep, h0, c0, w_hh, N, T, y, hn, cn, stash, st)
                      : lstm_generic_fwd(ctx, keep, h0, c0, w_hh, N, T, H, y, hn, cn, stash, st);
     if (rc) return rc;
     // h = 256: whether this stash's h_prev slot was written (the fp16-split step path with packed gate gradients leaves it out)
-    if (H == DgPack::H) ctx->forms.stash_written(stash, step256 && lstm_h3_dg_packed(H) ? 0 : 1);
+    if (H == DgPack::H) ctx->forms.stash_written(stash, m.dg_packed(H) ? 0 : 1);
     // kernels without the fused head product: heads = y W_head^T + b_head as one GEMM over the rows of y
     if (heads && !heads_done)
-        return gemm_f32(ctx, (int64_t)N * T, n_heads, H, y, H, 1, w_head, 1, H, heads, n_heads, b_head, 0, st);
+        return gemm_f32(ctx->scratch(), (int64_t)N * T, n_heads, H, y, H, 1, w_head, 1, H, heads, n_heads, b_head, 0, st);
     return 0;
 }
 
 int uav_lstm_bwd_caps(uav_ctx* ctx, int I, int H) {
     if (!ctx) return 0;
     if (H == 64 || H == 128) return UAV_BWD_TAKES_DHEADS;            // the persistent sequence kernels
-    uav_enter(ctx);
-    return lstm_h3_bwd_caps(I, H);                                   // the exact-f32 step path: none
+    return ctx->mode.bwd_caps(I, H);                                 // the exact-f32 step path: none
 }
 
 size_t uav_lstm_dgates_bytes(uav_ctx* ctx, int N, int T, int H) {
     if (!ctx || N <= 0 || T <= 0 || H <= 0) return 0;
-    uav_enter(ctx);
-    if (H == DgPack::H && lstm_h3_dg_packed(H)) return DgPack(N, T).bytes();
+    if (ctx->mode.dg_packed(H)) return DgPack(N, T).bytes();
     return (size_t)N * T * 4 * H * sizeof(float);
 }
 
 int uav_lstm_dgates_f32(uav_ctx* ctx, const float* dgates, int N, int T, int H, float* out, uav_stream stream) {
     UAV_REQUIRE(ctx && dgates && out && N > 0 && T > 0 && H > 0, "uav_lstm_dgates_f32: bad argument");
-    uav_enter(ctx);
-    const int form = ctx->forms.f32_read(dgates, N, T, H, lstm_h3_dg_packed(H));
+    const int form = ctx->forms.f32_read(dgates, N, T, H, ctx->mode.dg_packed(H));
     if (form < 0) return 2;
     if (form == UAV_DG_TILE) return lstm_dg_tile_to_rows(dgates, N, T, H, out, as_stream(stream));
     if (form == UAV_DG_PIECES) return lstm_pc_unpack(dgates, N, T, out, as_stream(stream));
@@ -206,7 +200,6 @@ int uav_lstm_dgates_f32(uav_ctx* ctx, const float* dgates, int N, int T, int H, 
 
 size_t uav_lstm_dgates_tile_bytes(uav_ctx* ctx, int N, int T, int I, int H) {
     if (!ctx || N <= 0 || T <= 0 || I <= 0 || H <= 0) return 0;
-    uav_enter(ctx);
     if (const char* why = lstm_wgrad_tile_refusal(ctx, N, T, I, H)) {
         uav_set_error("uav_lstm_dgates_tile_bytes(N=%d, T=%d, I=%d, H=%d): %s", N, T, I, H, why);
         return 0;
@@ -216,7 +209,6 @@ size_t uav_lstm_dgates_tile_bytes(uav_ctx* ctx, int N, int T, int I, int H) {
 
 int uav_lstm_dgates_tile(uav_ctx* ctx, float* dgates, int N, int T, int I, int H) {
     UAV_REQUIRE(ctx && dgates && N > 0 && T > 0 && I > 0 && H > 0, "uav_lstm_dgates_tile: bad argument");
-    uav_enter(ctx);
     const char* why = lstm_wgrad_tile_refusal(ctx, N, T, I, H);
     UAV_REQUIRE(!why, "uav_lstm_dgates_tile(N=%d, T=%d, I=%d, H=%d): %s", N, T, I, H, why);
     return ctx->forms.arm(dgates, N, T, H) < 0 ? 2 : 0;
@@ -236,15 +228,14 @@ int uav_lstm_dgates_forget(uav_ctx* ctx, const float* dgates) {
 int uav_lstm_bwd_stack(uav_ctx* ctx, int n_layers, const uav_lstm_bwd_layer* layers, const float* dy, const float* dheads,
                        const float* w_head, int n_heads, int N, int T, int H, uav_stream stream) {
     UAV_REQUIRE(ctx && layers, "uav_lstm_bwd_stack: NULL argument");
-    uav_enter(ctx);
     UAV_REQUIRE((dy != nullptr) != (dheads != nullptr), "uav_lstm_bwd_stack: give exactly one of dy / dheads");
     UAV_REQUIRE(!dheads || (w_head && n_heads > 0 && n_heads <= 8), "uav_lstm_bwd_stack: dheads needs w_head and 1..8 heads");
     UAV_REQUIRE(N > 0 && T > 0, "uav_lstm_bwd_stack: N=%d T=%d", N, T);
-    UAV_REQUIRE(H == 256 && lstm_h3_step_path(H), "uav_lstm_bwd_stack: H = 256 on the fp16-split arithmetic only (uav_lstm_bwd_caps)");
+    UAV_REQUIRE(ctx->mode.step_path(H), "uav_lstm_bwd_stack: H = 256 on the fp16-split arithmetic only (uav_lstm_bwd_caps)");
     const int nl = n_layers < 4 ? n_layers : 4;
     for (int l = 0; l < nl; ++l) ctx->forms.forget(layers[l].dgates);       // h = 256 never writes tile form
     const int rc = lstm_h3_bwd_stack(ctx, n_layers, layers, dy, dheads, w_head, n_heads, N, T, as_stream(stream));
-    for (int l = 0; l < nl; ++l) ctx->forms.bwd_end(layers[l].dgates, lstm_h3_dg_packed(H) ? UAV_DG_PIECES : UAV_DG_ROWS, rc == 0);
+    for (int l = 0; l < nl; ++l) ctx->forms.bwd_end(layers[l].dgates, ctx->mode.dg_packed(H) ? UAV_DG_PIECES : UAV_DG_ROWS, rc == 0);
     return rc;
 }
 
@@ -253,7 +244,6 @@ int uav_lstm_bwd(uav_ctx* ctx, const float* keep, const float* stash, const floa
                  int T, int H, float* dgates, float* dh0, float* dc0, const float* w_ih, int I, float* dx,
                  uav_stream stream) {
     UAV_REQUIRE(ctx && stash && w_hh && dgates, "uav_lstm_bwd: NULL argument");
-    uav_enter(ctx);
     UAV_REQUIRE((dy != nullptr) != (dheads != nullptr), "uav_lstm_bwd: give exactly one of dy / dheads");
     UAV_REQUIRE(!dheads || (w_head && n_heads > 0 && n_heads <= 8), "uav_lstm_bwd: dheads needs w_head and 1..8 heads");
     UAV_REQUIRE(N > 0 && T > 0, "uav_lstm_bwd: N=%d T=%d", N, T);
@@ -261,15 +251,16 @@ int uav_lstm_bwd(uav_ctx* ctx, const float* keep, const float* stash, const floa
     // record then says so until the next uav_lstm_bwd on the buffer; every other call writes f32 rows (h = 256: or pieces).
     const int form = ctx->forms.bwd_begin(dgates, N, T, H, dx != nullptr);
     if (form < 0) return 2;
+    const uav_lstm_mode& m = ctx->mode;
     int rc, wrote;
     if (H != 64 && H != 128) {
-        wrote = lstm_h3_dg_packed(H) ? UAV_DG_PIECES : UAV_DG_ROWS;
+        wrote = m.dg_packed(H) ? UAV_DG_PIECES : UAV_DG_ROWS;
         rc = lstm_bwd_steps(ctx, keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, H, dgates, dh0, dc0, w_ih, I, dx,
                             as_stream(stream));
     } else {
         UAV_REQUIRE(!dx, "uav_lstm_bwd: dx is not formed by the H = 64 / 128 sequence kernels (uav_lstm_wgrad does it)");
         wrote = form == UAV_DG_TILE ? UAV_DG_TILE : -1;             // their f32 rows are not recorded
-        rc = lstm_bwd_seq(keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, H, dgates, form == UAV_DG_TILE, dh0, dc0,
+        rc = lstm_bwd_seq(m, keep, stash, w_hh, dy, dheads, w_head, n_heads, dhn, dcn, N, T, H, dgates, form == UAV_DG_TILE, dh0, dc0,
                           as_stream(stream));
     }
     ctx->forms.bwd_end(dgates, wrote, rc == 0);
@@ -281,17 +272,17 @@ int uav_lstm_wgrad(uav_ctx* ctx, const float* x, const float* keep, const float*
                    int T, int I, int H, float* dw_ih, float* dw_hh, float* db, float* db_hh, float* dw_head, float* dx,
                    uav_stream stream) {
     UAV_REQUIRE(ctx && x && h0 && y && dgates && w_ih && dw_ih && dw_hh && db, "uav_lstm_wgrad: NULL argument");
-    uav_enter(ctx);
     UAV_REQUIRE(N > 0 && T > 0 && I > 0 && H > 0, "uav_lstm_wgrad: N=%d T=%d I=%d H=%d", N, T, I, H);
     UAV_REQUIRE(!dheads || (dw_head && n_heads > 0 && n_heads <= 8), "uav_lstm_wgrad: dheads needs dw_head, 1..8 heads");
     // 1. what the buffer holds, and whether this call under the handle's mode may read it
-    const bool packed = lstm_h3_dg_packed(H);
+    const uav_lstm_mode& m = ctx->mode;
+    const bool packed = m.dg_packed(H);
     const char* no_tile = ctx->forms.form(dgates) == UAV_DG_TILE ? lstm_wgrad_tile_refusal(ctx, N, T, I, H) : nullptr;
     const int form = ctx->forms.wgrad_read(dgates, stash, N, T, H, dx != nullptr, packed, no_tile);
     if (form < 0) return 2;
     // 2. the weight gradients
     LstmWgrad g{ctx, x, keep, h0, y, stash, dgates, w_ih, dheads, n_heads, N, T, I, H, dw_ih, dw_hh, db, db_hh, dw_head, dx,
-                as_stream(stream), *ctx};
+                as_stream(stream), ctx->scratch()};
     int rc;
     if (I <= 6 && (H == 64 || H == 128))     // one fused pass over rows or tile blocks (wgrad.hip)
         rc = lstm_wgrad_fused(ctx, dgates, y, keep, h0, x, I, dheads, n_heads, N, T, H, dw_ih, dw_hh, db, db_hh, dw_head, form == UAV_DG_TILE, as_stream(stream));
@@ -313,34 +304,32 @@ int uav_lstm_stepper_begin(uav_ctx* ctx, void* state, const float* w_ih, const f
                            const float* b_hh, const float* h0, const float* c0, int N, int I, int H, uav_stream stream) {
     UAV_REQUIRE(ctx && state && w_ih && w_hh && b_ih && b_hh && h0 && c0, "uav_lstm_stepper_begin: NULL argument");
     UAV_REQUIRE(uav_lstm_stepper_bytes(N, I, H) != 0, "uav_lstm_stepper_begin: H = %d, I = %d not supported (H = 256, I <= 256)", H, I);
-    uav_enter(ctx);
-    UAV_REQUIRE(lstm_h3_step_path(H), "uav_lstm_stepper_begin: only the fp16-split arithmetic steps (uav_set_lstm_arith)");
+    UAV_REQUIRE(ctx->mode.step_path(H), "uav_lstm_stepper_begin: only the fp16-split arithmetic steps (uav_set_lstm_arith)");
     return lstm_h3_stepper_begin(state, w_ih, w_hh, b_ih, b_hh, h0, c0, N, I, as_stream(stream));
 }
 
 int uav_lstm_stepper_step(uav_ctx* ctx, void* state, const float* x, const void* below, const float* keep_t, int N, int T, int t,
                           int I, int H, float* y, float* stash, float* hn, float* cn, uav_stream stream) {
     UAV_REQUIRE(ctx, "uav_lstm_stepper_step: NULL argument");
-    uav_enter(ctx);
     const uav_stepper_call c{state, x, below, keep_t, t, I, y, stash, hn, cn};
     int rc;
-    if ((rc = stepper_check("uav_lstm_stepper_step", c, N, T, H))) return rc;
-    ctx->forms.stash_step(stash, t, lstm_h3_dg_packed(H) ? 0 : 1);
-    return lstm_h3_stepper_step(c, N, T, as_stream(stream));
+    if ((rc = stepper_check("uav_lstm_stepper_step", ctx->mode, c, N, T, H))) return rc;
+    const int hslot = ctx->mode.dg_packed(H) ? 0 : 1;
+    ctx->forms.stash_step(stash, t, hslot);
+    return lstm_h3_stepper_step(c, N, T, hslot, as_stream(stream));
 }
 
 int uav_lstm_stepper_step_pair(uav_ctx* ctx, const uav_stepper_call* a, const uav_stepper_call* b, int N, int T, int H,
                                uav_stream stream) {
     UAV_REQUIRE(ctx && a && b, "uav_lstm_stepper_step_pair: NULL argument");
-    uav_enter(ctx);
-    UAV_REQUIRE(lstm_h3_step_path(H), "uav_lstm_stepper_step_pair: only the fp16-split arithmetic steps (uav_set_lstm_arith)");
+    UAV_REQUIRE(ctx->mode.step_path(H), "uav_lstm_stepper_step_pair: only the fp16-split arithmetic steps (uav_set_lstm_arith)");
     int rc;
-    if ((rc = stepper_check("uav_lstm_stepper_step_pair", *a, N, T, H)) || (rc = stepper_check("uav_lstm_stepper_step_pair", *b, N, T, H)))
+    if ((rc = stepper_check("uav_lstm_stepper_step_pair", ctx->mode, *a, N, T, H)) || (rc = stepper_check("uav_lstm_stepper_step_pair", ctx->mode, *b, N, T, H)))
         return rc;
-    const int hslot = lstm_h3_dg_packed(H) ? 0 : 1;
+    const int hslot = ctx->mode.dg_packed(H) ? 0 : 1;
     ctx->forms.stash_step(a->stash, a->t, hslot);
     ctx->forms.stash_step(b->stash, b->t, hslot);
-    return lstm_h3_stepper_step_pair(*a, *b, N, T, as_stream(stream));
+    return lstm_h3_stepper_step_pair(*a, *b, N, T, hslot, as_stream(stream));
 }
 
 }  // extern "C"

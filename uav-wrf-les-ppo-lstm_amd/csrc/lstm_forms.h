@@ -1,7 +1,8 @@
 // lstm_forms.h -- the storage forms of the LSTM update's gate-gradient (`dgates`) and `stash` buffers: their layouts, the one
-// record a device handle keeps per buffer, and every decision taken from that record.  Host-only and free of HIP (plain C++17:
-// tests/host/lstm_forms_check.cpp); the kernels see the two layout structs through common.h.  The entry points (lstm_api.hip,
-// the stepper's among them) hand in the handle's mode as plain values and never touch an entry themselves.
+// record a device handle keeps per buffer, and every decision taken from that record; and the handle's arithmetic mode with the
+// path decisions taken from it (uav_lstm_mode).  Host-only and free of HIP (plain C++17: tests/host/lstm_forms_check.cpp); the
+// kernels see the two layout structs through common.h.  The entry points (lstm_api.hip, the stepper's among them) hand in what
+// the handle's mode decides as plain values and never touch an entry themselves.
 #pragma once
 #include <stddef.h>
 #include "../../include/uavppo.h"
@@ -49,6 +50,28 @@ struct DgPack {
     __host__ __device__ const float* isc(const void* base, int t) const { return (const float*)((const char*)base + piece_bytes()) + (size_t)t * NP; }
     __host__ __device__ float* iscm(void* base, int t) const { return isc(base, T) + (size_t)t * NP; }
     __host__ __device__ const float* iscm(const void* base, int t) const { return isc(base, T) + (size_t)t * NP; }
+};
+
+// ---- the arithmetic mode of a handle (uav_set_lstm_arith, uav_set_debug_flags) as a plain value, and every path decision taken
+// from it.  The handle keeps one; whoever launches reads it from its ctx or is handed it (or the value already decided from it).
+struct uav_lstm_mode {
+    int arith;         // UAV_ARITH_*: how the LSTM sequence kernels evaluate their f32 matrix products
+    unsigned debug;    // UAV_DEBUG_*: A/B switches of the h = 256 step path and the dW-shaped split product
+    bool f32_mfma() const { return arith == UAV_ARITH_F32_MFMA; }
+    bool bf16x6() const { return arith == UAV_ARITH_BF16X6; }
+    // The h = 256 step kernels exist in the fp16-split form only (|w| < 65504, |x| < 4096): BOTH other modes -- exact f32 and the
+    // bf16 split, which callers select precisely because operands left that range -- take the generic exact-f32 step path
+    // (lstm_generic.hip), uav_lstm_bwd_caps reports 0 and the stepper refuses.
+    bool step_path(int H) const { return H == 256 && !f32_mfma() && !bf16x6() && !(debug & UAV_DEBUG_STEP_F32); }
+    // the gate gradients stay in the packed form only (DgPack) unless the A/B switch asks for the round-4 f32 rows too
+    bool dg_packed(int H) const { return step_path(H) && !(debug & UAV_DEBUG_DG_F32); }
+    // what the step path's BPTT can do itself: take dheads + w_head; with an input as wide as the state, form dx = dG W_ih in its
+    // recurrent product (no separate GEMM) and run a stack as a pipeline
+    int bwd_caps(int I, int H) const {
+        return step_path(H) ? ((I == H ? UAV_BWD_FUSES_DX | UAV_BWD_STACKS : 0) | UAV_BWD_TAKES_DHEADS) : 0;
+    }
+    bool x_pieces() const { return !(debug & UAV_DEBUG_X_F32); }            // a wide input of the step path as fp16 piece planes
+    bool gemm_tn() const { return !(debug & UAV_DEBUG_GEMM_TN_OFF); }       // dW-shaped split products on gemm_h3_tn8_kernel
 };
 
 void uav_set_error(const char* fmt, ...);       // ctx.hip (the check program brings its own)

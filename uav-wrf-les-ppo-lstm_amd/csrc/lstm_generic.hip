@@ -86,16 +86,15 @@ void lstm_fill(float* x, const float* src, int64_t n, hipStream_t st) {
 int lstm_generic_fwd(uav_ctx* ctx, const float* keep, const float* h0, const float* c0, const float* w_hh, int N, int T,
                      int H, float* y, float* hn, float* cn, float* stash, hipStream_t st) {
     const int64_t NH = (int64_t)N * H;
-    UAV_REQUIRE((size_t)(2 * NH) * sizeof(float) + (64u << 20) <= ctx->ws_bytes, "lstm (generic): workspace too small");
-    float* hs = (float*)((char*)ctx->ws + ctx->ws_bytes) - 2 * NH;     // recurrent state at the tail of the workspace
+    float* hs;                                                         // recurrent state at the tail of the workspace
+    const uav_scratch sub = ctx->scratch().carve((size_t)(2 * NH) * sizeof(float), 64u << 20, &hs);
+    UAV_REQUIRE(sub.p, "lstm (generic): workspace too small");
     float* cs = hs + NH;
-    uav_ctx sub = *ctx;
-    sub.ws_bytes = ctx->ws_bytes - 2 * NH * sizeof(float);
     const unsigned nb = (unsigned)((NH + 255) / 256);
     hipLaunchKernelGGL(gen_init_state, dim3(nb), dim3(256), 0, st, h0, c0, keep, N, T, H, hs, cs);
     for (int t = 0; t < T; ++t) {
         // gates_t += h_{t-1} W_hh^T   (rows = envs, row stride T*6H inside the stash)
-        int rc = gemm_f32(&sub, N, 4 * H, H, hs, H, 1, w_hh, 1, H, stash + (size_t)t * 6 * H, (int64_t)T * 6 * H, nullptr, 1, st);
+        int rc = gemm_f32(sub, N, 4 * H, H, hs, H, 1, w_hh, 1, H, stash + (size_t)t * 6 * H, (int64_t)T * 6 * H, nullptr, 1, st);
         if (rc) return rc;
         hipLaunchKernelGGL(gen_cell_fwd, dim3(nb), dim3(256), 0, st, stash, keep, N, T, H, t, hs, cs, y, hn, cn);
     }
@@ -107,18 +106,17 @@ int lstm_generic_fwd(uav_ctx* ctx, const float* keep, const float* h0, const flo
 int lstm_generic_bwd(uav_ctx* ctx, const float* keep, const float* stash, const float* w_hh, const float* dy, const float* dhn,
                      const float* dcn, int N, int T, int H, float* dgates, float* dh0, float* dc0, hipStream_t st) {
     const int64_t NH = (int64_t)N * H;
-    UAV_REQUIRE((size_t)(2 * NH) * sizeof(float) + (64u << 20) <= ctx->ws_bytes, "lstm (generic): workspace too small");
-    float* dh = (float*)((char*)ctx->ws + ctx->ws_bytes) - 2 * NH;
+    float* dh;
+    const uav_scratch sub = ctx->scratch().carve((size_t)(2 * NH) * sizeof(float), 64u << 20, &dh);
+    UAV_REQUIRE(sub.p, "lstm (generic): workspace too small");
     float* dc = dh + NH;
-    uav_ctx sub = *ctx;
-    sub.ws_bytes = ctx->ws_bytes - 2 * NH * sizeof(float);
     const unsigned nb = (unsigned)((NH + 255) / 256);
     lstm_fill(dh, dhn, NH, st);
     lstm_fill(dc, dcn, NH, st);
     for (int t = T - 1; t >= 0; --t) {
         hipLaunchKernelGGL(gen_cell_bwd, dim3(nb), dim3(256), 0, st, stash, keep, dy, N, T, H, t, dh, dc, dgates);
         // dh_{t-1} = dgates_t W_hh  ([N,4H] x [4H,H]); then the mask of step t
-        int rc = gemm_f32(&sub, N, H, 4 * H, dgates + (size_t)t * 4 * H, (int64_t)T * 4 * H, 1, w_hh, H, 1, dh, H, nullptr, 0, st);
+        int rc = gemm_f32(sub, N, H, 4 * H, dgates + (size_t)t * 4 * H, (int64_t)T * 4 * H, 1, w_hh, H, 1, dh, H, nullptr, 0, st);
         if (rc) return rc;
         if (keep) hipLaunchKernelGGL(gen_mask_rows, dim3(nb), dim3(256), 0, st, dh, keep, N, T, H, t);
     }

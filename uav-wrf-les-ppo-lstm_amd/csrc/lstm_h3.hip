@@ -648,22 +648,6 @@ __global__ __launch_bounds__(256) void split_x_kernel(const float* __restrict__ 
 }
 
 // ================================================================================================ host side
-// The h = 256 step kernels exist in the fp16-split form only (|w| < 65504, |x| < 4096): BOTH other modes -- exact f32 and the
-// bf16 split, which callers select precisely because operands left that range -- take the generic exact-f32 step path
-// (lstm_generic.hip), uav_lstm_bwd_caps reports 0 and the stepper refuses.
-bool lstm_h3_step_path(int H) {
-    return H == 256 && !uav_want_f32_mfma() && !uav_want_bf16x6() && !uav_debug(UAV_DEBUG_STEP_F32);
-}
-
-// the gate gradients stay in the packed form only (lstm_forms.h: DgPack) unless the A/B switch asks for the round-4 f32 rows too
-bool lstm_h3_dg_packed(int H) { return lstm_h3_step_path(H) && !uav_debug(UAV_DEBUG_DG_F32); }
-
-// what the step path's BPTT can do itself: take dheads + w_head; with an input as wide as the state, form dx = dG W_ih in its
-// recurrent product (no separate GEMM) and run a stack as a pipeline
-int lstm_h3_bwd_caps(int I, int H) {
-    return lstm_h3_step_path(H) ? ((I == H ? UAV_BWD_FUSES_DX | UAV_BWD_STACKS : 0) | UAV_BWD_TAKES_DHEADS) : 0;
-}
-
 // One layer's forward state, as offsets into a block of `total` bytes: hs, cs f32 [N][H] | two ping-pong sets of h pieces | W_hh
 // pieces | W_ih pieces | b_ih + b_hh.  The block is the stepper's caller-owned state, or the tail of the workspace for a sequence
 // call.  (Every term is a multiple of 1024 bytes: the round-up to 256 changes nothing.)
@@ -724,22 +708,23 @@ int lstm_h3_fwd(uav_ctx* ctx, const float* x, int I, const float* w_ih, const fl
     constexpr int H = 256;
     UAV_REQUIRE(I <= 256, "lstm (h=256): input width %d > 256", I);
     const H3Layout L = h3_layout(N, I);                     // at the tail of the workspace
-    UAV_REQUIRE(L.total + (64u << 20) <= ctx->ws_bytes, "lstm (h=256): workspace too small");
-    char* base = (char*)ctx->ws + ctx->ws_bytes - L.total;
+    char* base;
+    const uav_scratch front = ctx->scratch().carve(L.total, 64u << 20, &base);
+    UAV_REQUIRE(front.p, "lstm (h=256): workspace too small");
     int rc;
     if ((rc = h3_prepare(base, L, w_ih, w_hh, b_ih, b_hh, h0, c0, keep, N, T, I, st))) return rc;
     unsigned short* hp0 = (unsigned short*)(base + L.hp0);
     unsigned short* hp1 = (unsigned short*)(base + L.hp1);
     const int IP = L.IP;
-    const int hslot = lstm_h3_dg_packed(H) ? 0 : 1;         // the stash's h_prev slot is only read by the f32-rows weight gradients
+    const int hslot = ctx->mode.dg_packed(H) ? 0 : 1;       // the stash's h_prev slot is only read by the f32-rows weight gradients
     // a wide input (the layer below's output, I = 64 .. 256): x is converted to piece planes a chunk of time steps at a
     // time (split_x_kernel, in front of the state in the workspace), so the step kernel's input projection streams
     // 1 KB fragment chunks like its recurrent product instead of gathering f32 rows and splitting them in every workgroup
     const int ntile = (N + 63) / 64 * 4;
     const size_t x_step = (size_t)ntile * (IP / 32) * 1024 * 2;            // bytes of one step's planes
     int TC = 0;
-    if (I == IP && I >= 64 && !uav_debug(UAV_DEBUG_X_F32)) {
-        const size_t room = ctx->ws_bytes - L.total - (64u << 20);
+    if (I == IP && I >= 64 && ctx->mode.x_pieces()) {
+        const size_t room = front.bytes - (64u << 20);
         TC = (int)(room / x_step < 16 ? room / x_step : 16);
     }
     unsigned short* xbuf = TC > 0 ? (unsigned short*)(base - (size_t)TC * x_step) : nullptr;
@@ -785,7 +770,7 @@ int lstm_h3_stepper_begin(void* state, const float* w_ih, const float* w_hh, con
 }
 
 // the kernel arguments of one stepper step; returns its input slab count
-static int stepper_args(const uav_stepper_call& c, int N, int T, StepFwdArgs& A) {
+static int stepper_args(const uav_stepper_call& c, int N, int T, int hslot, StepFwdArgs& A) {
     const H3Layout L = h3_layout(N, c.I);
     char* b = (char*)c.state;
     unsigned short* hp0 = (unsigned short*)(b + L.hp0);
@@ -797,21 +782,21 @@ static int stepper_args(const uav_stepper_call& c, int N, int T, StepFwdArgs& A)
     if (c.below) xp = (const unsigned short*)((const char*)c.below + (((c.t + 1) & 1) ? L.hp1 : L.hp0));
     A = StepFwdArgs{(const unsigned short*)(b + L.wxp), (const unsigned short*)(b + L.wp), (const float*)(b + L.bsum), c.x, c.I, xp, 1,
                     (c.t & 1) ? hp1 : hp0, (c.t & 1) ? hp0 : hp1, (float*)(b + L.hs), (float*)(b + L.cs), c.stash, c.keep_t, (int64_t)1,
-                    (int64_t)0, N, T, c.t, c.y, c.hn, c.cn, lstm_h3_dg_packed(256) ? 0 : 1};
+                    (int64_t)0, N, T, c.t, c.y, c.hn, c.cn, hslot};
     return L.IP / 32;
 }
 
-int lstm_h3_stepper_step(const uav_stepper_call& c, int N, int T, hipStream_t st) {
+int lstm_h3_stepper_step(const uav_stepper_call& c, int N, int T, int hslot, hipStream_t st) {
     StepFwdArgs A;
-    const int ips = stepper_args(c, N, T, A);
+    const int ips = stepper_args(c, N, T, hslot, A);
     h3_launch_step(A, ips, st);
     UAV_LAUNCH_CHECK();
     return 0;
 }
 
-int lstm_h3_stepper_step_pair(const uav_stepper_call& a, const uav_stepper_call& b, int N, int T, hipStream_t st) {
+int lstm_h3_stepper_step_pair(const uav_stepper_call& a, const uav_stepper_call& b, int N, int T, int hslot, hipStream_t st) {
     StepFwdArgs A, B;
-    const int ia = stepper_args(a, N, T, A), ib = stepper_args(b, N, T, B);
+    const int ia = stepper_args(a, N, T, hslot, A), ib = stepper_args(b, N, T, hslot, B);
     if (ia == 1 && ib == 8) {                 // (layer 1 of a narrow input, layer 2 on the layer below's planes): the one instantiated pair
         hipLaunchKernelGGL((step_fwd_h3_pair_kernel<256, 1, 8>), dim3((N + 63) / 64, 256 / 64, 2), dim3(256), 0, st, A, B);
     } else {                                  // any other pair of widths: the two steps one after the other (same results)
@@ -905,7 +890,7 @@ static int h3_bwd_run(uav_ctx* ctx, int nl, const uav_lstm_bwd_layer* layers, co
     for (int l = 0; l < nl; ++l) {
         const uav_lstm_bwd_layer& a = layers[l];
         L[l] = H3Bwd{a.keep, a.stash, l == 0 ? dy : layers[l - 1].dx, l == 0 ? dheads : nullptr, l == 0 ? w_head : nullptr,
-                     l == 0 ? n_heads : 0, N, T, a.dgates, a.dx, lstm_h3_dg_packed(H3Bwd::H)};
+                     l == 0 ? n_heads : 0, N, T, a.dgates, a.dx, ctx->mode.dg_packed(H3Bwd::H)};
         L[l].prepare((char*)ctx->ws + ctx->ws_bytes - (size_t)(l + 1) * need, a.w_hh, a.w_ih, a.dhn, a.dcn, str[l]);
     }
     // the wave front: at round r layer l runs its step T - 1 - (r - l); the hand-off events form a ring per boundary.

@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256) void colsum_xw_reduce_kernel(const float* __re
 }
 // colsum of X [B][C] (colsum_out may be NULL) + X^T x for x [B][I] (or x^T X with xw_transposed), I <= 8, C % 4 == 0,
 // X 16-byte aligned; scratch >= 1024 * 9 * C floats
-int colsum_xw(uav_ctx* ctx, const float* X, int64_t B, int C, const float* x, int I, float* colsum_out, float* xw_out,
+int colsum_xw(const uav_scratch& ws, const float* X, int64_t B, int C, const float* x, int I, float* colsum_out, float* xw_out,
               float* scratch, unsigned* absmax_bits, hipStream_t st, int xw_transposed) {
     UAV_REQUIRE(I >= 1 && I <= 8 && C % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0, "colsum_xw: I <= 8, cols %% 4 == 0, aligned X");
     int nb = (int)((B + 255) / 256);
@@ -281,11 +281,11 @@ int colsum_xw(uav_ctx* ctx, const float* X, int64_t B, int C, const float* x, in
     return 0;
 }
 
-int colsum(uav_ctx* ctx, const float* X, int64_t B, int C, float* out, float* scratch, hipStream_t st) {
-    return colsum_absmax(ctx, X, B, C, out, scratch, nullptr, st);
+static int colsum(const uav_scratch& ws, const float* X, int64_t B, int C, float* out, float* scratch, hipStream_t st) {
+    return colsum_absmax(ws, X, B, C, out, scratch, nullptr, st);
 }
 // absmax_bits (optional; C % 4 == 0 and X 16-byte aligned required with it): device word that receives the bits of max |X|
-int colsum_absmax(uav_ctx* ctx, const float* X, int64_t B, int C, float* out, float* scratch, unsigned* absmax_bits,
+int colsum_absmax(const uav_scratch& ws, const float* X, int64_t B, int C, float* out, float* scratch, unsigned* absmax_bits,
                   hipStream_t st) {
     // column sums are tiny next to the GEMMs; keep them simple and deterministic
     int nb = (int)((B + 255) / 256);
@@ -328,7 +328,7 @@ static int ln_fwd_any(int C, float* z, float* a, float* rstd, const float* g, co
 
 constexpr int LNB_BLOCKS = 512;
 template <int VPT>
-static int ln_bwd(uav_ctx* ctx, float* d, const float* xhat, const float* rstd, const float* g, const float* be,
+static int ln_bwd(const uav_scratch& ws, float* d, const float* xhat, const float* rstd, const float* g, const float* be,
                   int64_t B, float* dg_out, float* db_out, float* scratch, hipStream_t st) {
     constexpr int C = VPT * 64;
     int nb = (int)((B + 3) / 4);
@@ -344,13 +344,13 @@ static int ln_bwd(uav_ctx* ctx, float* d, const float* xhat, const float* rstd, 
     UAV_LAUNCH_CHECK();
     return 0;
 }
-static int ln_bwd_any(uav_ctx* ctx, int C, float* d, const float* xhat, const float* rstd, const float* g,
+static int ln_bwd_any(const uav_scratch& ws, int C, float* d, const float* xhat, const float* rstd, const float* g,
                       const float* be, int64_t B, float* dg, float* db, float* scratch, hipStream_t st) {
     switch (C) {
-        case 64: return ln_bwd<1>(ctx, d, xhat, rstd, g, be, B, dg, db, scratch, st);
-        case 128: return ln_bwd<2>(ctx, d, xhat, rstd, g, be, B, dg, db, scratch, st);
-        case 256: return ln_bwd<4>(ctx, d, xhat, rstd, g, be, B, dg, db, scratch, st);
-        case 512: return ln_bwd<8>(ctx, d, xhat, rstd, g, be, B, dg, db, scratch, st);
+        case 64: return ln_bwd<1>(ws, d, xhat, rstd, g, be, B, dg, db, scratch, st);
+        case 128: return ln_bwd<2>(ws, d, xhat, rstd, g, be, B, dg, db, scratch, st);
+        case 256: return ln_bwd<4>(ws, d, xhat, rstd, g, be, B, dg, db, scratch, st);
+        case 512: return ln_bwd<8>(ws, d, xhat, rstd, g, be, B, dg, db, scratch, st);
     }
     uav_set_error("mlp: LayerNorm width %d unsupported (64/128/256/512)", C);
     return 2;
@@ -368,13 +368,13 @@ int uav_ln_relu_bwd(uav_ctx* ctx, float* d, const float* xhat, const float* rstd
                     int64_t rows, int cols, float* dgamma, float* dbeta, uav_stream stream) {
     UAV_REQUIRE(ctx && d && xhat && rstd && gamma && beta && dgamma && dbeta && rows > 0, "uav_ln_relu_bwd: bad argument");
     UAV_REQUIRE(ctx->ws_bytes >= ((size_t)LNB_BLOCKS * 2 * cols + 2 * cols) * sizeof(float), "uav_ln_relu_bwd: workspace too small");
-    return ln_bwd_any(ctx, cols, d, xhat, rstd, gamma, beta, rows, dgamma, dbeta, (float*)ctx->ws, as_stream(stream));
+    return ln_bwd_any(ctx->scratch(), cols, d, xhat, rstd, gamma, beta, rows, dgamma, dbeta, (float*)ctx->ws, as_stream(stream));
 }
 
 int uav_colsum(uav_ctx* ctx, const float* x, int64_t rows, int cols, float* out, uav_stream stream) {
     UAV_REQUIRE(ctx && x && out && rows > 0 && cols > 0 && cols <= 1024, "uav_colsum: bad argument");
     UAV_REQUIRE(ctx->ws_bytes >= (size_t)1024 * 1024 * sizeof(float), "uav_colsum: workspace too small");
-    return colsum(ctx, x, rows, cols, out, (float*)ctx->ws, as_stream(stream));
+    return colsum(ctx->scratch(), x, rows, cols, out, (float*)ctx->ws, as_stream(stream));
 }
 
 int64_t uav_mlp_param_count(int in_dim, int h1, int h2, int n_act) { return mlp_layout(in_dim, h1, h2, n_act).total; }
@@ -393,11 +393,11 @@ int uav_mlp_fwd(uav_ctx* ctx, const float* params, const float* x, int64_t B, in
     float* rstd2 = rstd1 + B;
     int rc;
     // z1 = x W1^T + b1   (NT: op(B)[k][j] = W1[j][k])
-    if ((rc = gemm_f32(ctx, B, h1, in_dim, x, in_dim, 1, params + L.W1, 1, in_dim, xhat1, h1, params + L.b1, 0, st))) return rc;
+    if ((rc = gemm_f32(ctx->scratch(), B, h1, in_dim, x, in_dim, 1, params + L.W1, 1, in_dim, xhat1, h1, params + L.b1, 0, st))) return rc;
     if ((rc = ln_fwd_any(h1, xhat1, a1, rstd1, params + L.g1, params + L.be1, B, st))) return rc;
-    if ((rc = gemm_f32(ctx, B, h2, h1, a1, h1, 1, params + L.W2, 1, h1, xhat2, h2, params + L.b2, 0, st))) return rc;
+    if ((rc = gemm_f32(ctx->scratch(), B, h2, h1, a1, h1, 1, params + L.W2, 1, h1, xhat2, h2, params + L.b2, 0, st))) return rc;
     if ((rc = ln_fwd_any(h2, xhat2, a2, rstd2, params + L.g2, params + L.be2, B, st))) return rc;
-    return gemm_f32(ctx, B, n_act + 1, h2, a2, h2, 1, params + L.Wh, 1, h2, heads, n_act + 1, params + L.bh, 0, st);
+    return gemm_f32(ctx->scratch(), B, n_act + 1, h2, a2, h2, 1, params + L.Wh, 1, h2, heads, n_act + 1, params + L.bh, 0, st);
 }
 
 int uav_mlp_bwd(uav_ctx* ctx, const float* params, const float* x, float* stash, const float* dheads, int64_t B,
@@ -414,24 +414,23 @@ int uav_mlp_bwd(uav_ctx* ctx, const float* params, const float* x, float* stash,
     const int A1 = n_act + 1;
     // scratch for column reductions lives behind the split-K slab area of the workspace
     const size_t red_floats = (size_t)LNB_BLOCKS * 2 * 512 + 2 * 512 + 1024 * 512;
-    UAV_REQUIRE(ctx->ws_bytes >= (red_floats + (1 << 18)) * sizeof(float), "uav_mlp_bwd: workspace too small");
-    float* red = (float*)((char*)ctx->ws + ctx->ws_bytes) - red_floats;
-    uav_ctx sub = *ctx;                       // GEMM slabs may use everything in front of `red`
-    sub.ws_bytes = ctx->ws_bytes - red_floats * sizeof(float);
+    float* red;                               // GEMM slabs may use everything in front of `red`
+    const uav_scratch sub = ctx->scratch().carve(red_floats * sizeof(float), (size_t)(1 << 18) * sizeof(float), &red);
+    UAV_REQUIRE(sub.p, "uav_mlp_bwd: workspace too small");
     int rc;
     // heads: dWh = dheads^T a2 ; dbh = colsum(dheads) ; da2 = dheads Wh   (da2 overwrites a2)
-    if ((rc = gemm_f32(&sub, A1, h2, B, dheads, 1, A1, a2, h2, 1, grad + L.Wh, h2, nullptr, 0, st))) return rc;
-    if ((rc = colsum(&sub, dheads, B, A1, grad + L.bh, red, st))) return rc;
-    if ((rc = gemm_f32(&sub, B, h2, A1, dheads, A1, 1, params + L.Wh, h2, 1, a2, h2, nullptr, 0, st))) return rc;
-    if ((rc = ln_bwd_any(&sub, h2, a2, xhat2, rstd2, params + L.g2, params + L.be2, B, grad + L.g2, grad + L.be2, red, st))) return rc;
+    if ((rc = gemm_f32(sub, A1, h2, B, dheads, 1, A1, a2, h2, 1, grad + L.Wh, h2, nullptr, 0, st))) return rc;
+    if ((rc = colsum(sub, dheads, B, A1, grad + L.bh, red, st))) return rc;
+    if ((rc = gemm_f32(sub, B, h2, A1, dheads, A1, 1, params + L.Wh, h2, 1, a2, h2, nullptr, 0, st))) return rc;
+    if ((rc = ln_bwd_any(sub, h2, a2, xhat2, rstd2, params + L.g2, params + L.be2, B, grad + L.g2, grad + L.be2, red, st))) return rc;
     // layer 2: dW2 = dz2^T a1 ; db2 ; da1 = dz2 W2  (overwrites a1)
-    if ((rc = gemm_f32(&sub, h2, h1, B, a2, 1, h2, a1, h1, 1, grad + L.W2, h1, nullptr, 0, st))) return rc;
-    if ((rc = colsum(&sub, a2, B, h2, grad + L.b2, red, st))) return rc;
-    if ((rc = gemm_f32(&sub, B, h1, h2, a2, h2, 1, params + L.W2, h1, 1, a1, h1, nullptr, 0, st))) return rc;
-    if ((rc = ln_bwd_any(&sub, h1, a1, xhat1, rstd1, params + L.g1, params + L.be1, B, grad + L.g1, grad + L.be1, red, st))) return rc;
+    if ((rc = gemm_f32(sub, h2, h1, B, a2, 1, h2, a1, h1, 1, grad + L.W2, h1, nullptr, 0, st))) return rc;
+    if ((rc = colsum(sub, a2, B, h2, grad + L.b2, red, st))) return rc;
+    if ((rc = gemm_f32(sub, B, h1, h2, a2, h2, 1, params + L.W2, h1, 1, a1, h1, nullptr, 0, st))) return rc;
+    if ((rc = ln_bwd_any(sub, h1, a1, xhat1, rstd1, params + L.g1, params + L.be1, B, grad + L.g1, grad + L.be1, red, st))) return rc;
     // layer 1: dW1 = dz1^T x ; db1
-    if ((rc = gemm_f32(&sub, h1, in_dim, B, a1, 1, h1, x, in_dim, 1, grad + L.W1, in_dim, nullptr, 0, st))) return rc;
-    return colsum(&sub, a1, B, h1, grad + L.b1, red, st);
+    if ((rc = gemm_f32(sub, h1, in_dim, B, a1, 1, h1, x, in_dim, 1, grad + L.W1, in_dim, nullptr, 0, st))) return rc;
+    return colsum(sub, a1, B, h1, grad + L.b1, red, st);
 }
 
 }  // extern "C"

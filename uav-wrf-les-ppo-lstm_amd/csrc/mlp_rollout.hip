@@ -271,7 +271,7 @@ int launch_rollout_mlp(uav_ctx* ctx, void* env_state, int n_env, const uav_env_c
     EnvBlob blob = env_blob_view(env_state, n_env);
     // the handle's arithmetic (uav_set_lstm_arith): FP16X3 = the 256 x 128 layer on the fp16 matrix pipe (max |param| < 2048);
     // anything else = exact-f32 MFMA
-    return ctx->lstm_arith == UAV_ARITH_FP16X3 ? launch_rollout_mlp_form<true, false, false>(P, blob, n_env, horizon, iter, params, B, st)
+    return ctx->mode.arith == UAV_ARITH_FP16X3 ? launch_rollout_mlp_form<true, false, false>(P, blob, n_env, horizon, iter, params, B, st)
                                                : launch_rollout_mlp_form<false, false, false>(P, blob, n_env, horizon, iter, params, B, st);
 }
 

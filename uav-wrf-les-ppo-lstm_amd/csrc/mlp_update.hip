@@ -633,7 +633,7 @@ static int mlp_ppo_grad_impl(const char* who, uav_ctx* ctx, const float* params,
     const int64_t ntile = (n + UMS - 1) / UMS;
     int nb = ctx->num_cu;
     if (nb > ntile) nb = (int)ntile;
-    const bool h3 = ctx->lstm_arith == UAV_ARITH_FP16X3;       // the handle's arithmetic (uav_set_lstm_arith); else exact-f32 MFMA
+    const bool h3 = ctx->mode.arith == UAV_ARITH_FP16X3;       // the handle's arithmetic (uav_set_lstm_arith); else exact-f32 MFMA
     const size_t head = 65536, w2t_bytes = (size_t)H1 * H2 * sizeof(float) * 2;  // loss partials | W2^T or both piece sets | slabs
     UAV_REQUIRE(ctx->ws_bytes >= head + w2t_bytes + (size_t)nb * O.N * sizeof(float), "%s: workspace too small", who);
     double* partial = (double*)ctx->ws;

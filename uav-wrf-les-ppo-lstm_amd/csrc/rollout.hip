@@ -756,8 +756,8 @@ static int greedy_episodes_impl(const char* who, uav_ctx* ctx, void* env_state, 
     UAV_REQUIRE(n_env > 0 && steps > 0, "%s: n_env=%d steps=%d", who, n_env, steps);
     UAV_REQUIRE(policy_kind >= 0 && policy_kind <= 2, "%s: policy_kind %d (0 = MLP, 1 = LSTM, 2 = MLP with 6 + trend_k inputs)", who,
                 policy_kind);
-    UAV_REQUIRE(ctx->lstm_arith == UAV_ARITH_FP16X3,
-                "%s: the fused greedy kernels exist in the fp16x3 arithmetic only (handle mode %d)", who, ctx->lstm_arith);
+    UAV_REQUIRE(ctx->mode.arith == UAV_ARITH_FP16X3,
+                "%s: the fused greedy kernels exist in the fp16x3 arithmetic only (handle mode %d)", who, ctx->mode.arith);
     StopRule R{};
     if (rule) {
         UAV_REQUIRE(rule->window >= 1 && rule->window <= STOP_WIN_MAX, "%s: rule window=%d (1 .. %d)", who, rule->window,

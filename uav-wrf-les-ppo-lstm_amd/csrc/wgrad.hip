@@ -682,7 +682,7 @@ struct WgradPlan {
         rpx = (NTr + nb - 1) / nb;
         rpx = (rpx + KS6 - 1) / KS6 * KS6;
         nbx = (int)((NTr + rpx - 1) / rpx);
-        split_ok = (NTr % rpx == 0) && T >= 8 && I <= 6 && (!heads || NH <= 8) && NTr * 4 * H < (1ll << 30) && !uav_want_f32_mfma();
+        split_ok = (NTr % rpx == 0) && T >= 8 && I <= 6 && (!heads || NH <= 8) && NTr * 4 * H < (1ll << 30) && !ctx->mode.f32_mfma();
     }
 };
 
@@ -695,7 +695,7 @@ static int launch_wgrad(uav_ctx* ctx, const float* dgates, bool tile, const floa
     UAV_REQUIRE(pl.nb >= 1, "uav_lstm_wgrad: workspace too small for one slab");
     float* slabs = (float*)ctx->ws;
     if (pl.split_ok) {
-        const int rc = uav_want_bf16x6()
+        const int rc = ctx->mode.bf16x6()
                            ? launch_wgrad_split<WgBf16x6, H>(dgates, tile, y, keep, h0, x, I, dheads, NH, N, T, pl.nbx, (int)pl.rpx, slabs, st)
                            : launch_wgrad_split<WgF16x3, H>(dgates, tile, y, keep, h0, x, I, dheads, NH, N, T, pl.nbx, (int)pl.rpx, slabs, st);
         if (rc) return rc;
@@ -722,7 +722,7 @@ const char* lstm_wgrad_tile_refusal(const uav_ctx* ctx, int N, int T, int I, int
     if (H != 64 && H != 128) return "tile form exists for H = 64 / 128 only";
     if (I > 6) return "tile form needs an input of at most 6 features (the fused weight-gradient pass)";
     if (T % KS6 != 0) return "tile form needs T to be a multiple of 32, the weight-gradient kernels' K slab";
-    if (uav_want_f32_mfma()) return "the exact-f32 kernels (UAV_ARITH_F32_MFMA) read and write f32 rows only";
+    if (ctx->mode.f32_mfma()) return "the exact-f32 kernels (UAV_ARITH_F32_MFMA) read and write f32 rows only";
     if ((int64_t)DgTile::rows(N, T) * 4 * H >= (1ll << 30)) return "tile form needs fewer than 2^30 values in the buffer, padded to whole 16-env tiles";
     const bool ok = H == 64 ? WgradPlan<64>(ctx, N, T, I, true, 8).split_ok : WgradPlan<128>(ctx, N, T, I, true, 8).split_ok;
     return ok ? nullptr : "the split weight-gradient kernels do not take this shape (N * T rows in whole 32-row slabs per workgroup)";

@@ -501,8 +501,9 @@ int lstm_pc_wgrad(uav_ctx* ctx, const float* x, const float* y, const float* h0,
     const bool wide = I == H;
     const int nb = 256, CI = wide ? 0 : I;
     const size_t part_floats = (size_t)nb * (1 + CI) * G4 + 64;
-    UAV_REQUIRE(ctx->ws_bytes >= part_floats * 4 + (64u << 20), "uav_lstm_wgrad: workspace too small");
-    float* partial = (float*)((char*)ctx->ws + ctx->ws_bytes) - part_floats;
+    float* partial;
+    const uav_scratch ws = ctx->scratch().carve(part_floats * 4, 64u << 20, &partial);       // the slabs: everything in front
+    UAV_REQUIRE(ws.p, "uav_lstm_wgrad: workspace too small");
     unsigned* iscmax = reinterpret_cast<unsigned*>(partial + (size_t)nb * (1 + CI) * G4);
     UAV_CHECK_HIP(hipMemsetAsync(iscmax, 0, sizeof(unsigned), st));
     const int64_t tiles = (int64_t)T * P.RT;
@@ -539,17 +540,17 @@ int lstm_pc_wgrad(uav_ctx* ctx, const float* x, const float* y, const float* h0,
     UAV_REQUIRE((int64_t)4 * T * H * 4 < (1ll << 31), "uav_lstm_wgrad (h=256): T = %d too long for 32-bit lane offsets", T);
     // split-K: whole groups of 8 splits (one per XCD), each split at least 16 slabs, the slabs inside the workspace
     const int tiles_mn = a.tm * a.tn;
-    int64_t S = (ctx->num_cu + tiles_mn - 1) / tiles_mn;
+    int64_t S = (ws.num_cu + tiles_mn - 1) / tiles_mn;
     S = (S + 7) / 8 * 8;
     const int64_t max_k = a.total / 16 > 0 ? a.total / 16 : 1;
-    const int64_t max_ws = (int64_t)((ctx->ws_bytes - part_floats * 4) / sizeof(float)) / ((int64_t)G4 * a.Ntot);
+    const int64_t max_ws = (int64_t)(ws.bytes / sizeof(float)) / ((int64_t)G4 * a.Ntot);
     if (S > max_k) S = max_k;
     if (S > max_ws) S = max_ws;
     UAV_REQUIRE(S >= 1, "uav_lstm_wgrad: workspace too small for one slab of the weight-gradient product");
     a.sps = (a.total + S - 1) / S;
     S = (a.total + a.sps - 1) / a.sps;
     a.S = (int)S;
-    a.slabs = (float*)ctx->ws;
+    a.slabs = (float*)ws.p;
     const int64_t grid = 8 * (int64_t)tiles_mn * ((S + 7) / 8);
     UAV_CHECK_HIP(uav_dyn_lds(reinterpret_cast<const void*>(&gemm_pc_kernel), (int)PC_LDS));
     hipLaunchKernelGGL(gemm_pc_kernel, dim3((unsigned)grid), dim3(512), PC_LDS, st, a);

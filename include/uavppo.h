@@ -272,6 +272,42 @@ int uav_clip_adam(uav_ctx* ctx, float* param, const float* grad, float* exp_avg,
 int uav_clip_adamw(uav_ctx* ctx, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                    int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm,
                    float* gnorm_out, uav_stream stream);
+/* uav_clip_adam with the step size read from device memory: lr_dev (device f32 [1], read by the step kernel on `stream`, so
+ * a kernel earlier on the stream -- uav_lr_adapt, uav_lr_init -- may have written it and the host never sees it) in place of
+ * `float lr`; every other argument, the norm pass, max_norm <= 0, NaN handling, gnorm_out and pmax_out as uav_clip_adam.
+ * The step kernel forms step_size = (float)((double)lr_dev[0] / bc1) with bc1 = 1 - beta1^step passed as a double: the
+ * host's expression in uav_clip_adam on the same operands, and an f64 division is correctly rounded on both sides.  The
+ * result -- parameters, both moments, gnorm_out, pmax_out -- is uav_clip_adam's with lr = lr_dev[0], bit for bit.  Refuses
+ * what uav_clip_adam refuses and a NULL lr_dev.  Added without a change of UAV_ABI_VERSION (symbols only). */
+int uav_clip_adam_dlr(uav_ctx* ctx, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                      int64_t step, const float* lr_dev, float beta1, float beta2, float eps, float max_norm,
+                      float* gnorm_out, float* pmax_out, uav_stream stream);
+
+/* ---- L1-L2: the KL-adaptive step size, kept on the device (csrc/lr_control.hip; no counterpart in the reference).  state
+ * f64 [UAV_LR_STATE_N] (device) = {lr, last_kl, raised, lowered, held, skipped}; lr_out f32 [1] (device) is what
+ * uav_clip_adam_dlr reads.  One thread each, plain f64, nothing read by the host.
+ * uav_lr_init: state = {lr, 0, 0, 0, 0, 0}, lr_out[0] = (float)lr: a fresh start, and how a saved rate is put back, on the
+ * stream.  lr positive and finite.  Added without a change of UAV_ABI_VERSION (symbols only). */
+#define UAV_LR_STATE_N 6
+#define UAV_LR_STATE_LR 0
+#define UAV_LR_STATE_LAST_KL 1
+#define UAV_LR_STATE_RAISED 2
+#define UAV_LR_STATE_LOWERED 3
+#define UAV_LR_STATE_HELD 4
+#define UAV_LR_STATE_SKIPPED 5
+int uav_lr_init(uav_ctx* ctx, double* state, double lr, float* lr_out, uav_stream stream);
+/* One update's decision from diag8 (device f64 [UAV_PPO_DIAG_N]: the sums of the update's last epoch, all-reduced over the
+ * ranks, so that every rank decides alike).  n = diag8[UAV_PPO_DIAG_COUNT]; where n > 0, kl = diag8[UAV_PPO_DIAG_KL_K3] / n.
+ *   n > 0 is false, or kl is a NaN:   lr stays, skipped += 1, last_kl = NaN
+ *   kl > 2 * desired_kl (so +inf):    lr = max(lr / factor, lr_min), lowered += 1
+ *   kl < desired_kl / 2:              lr = min(lr * factor, lr_max), raised += 1
+ *   otherwise (both edges included):  lr stays, held += 1
+ * last_kl = kl in the last three cases; then lr_out[0] = (float)lr.  Plain comparisons and one f64 operation per line, in the
+ * order of uavppo/lr_control.py's adapt_rule: the state is bit-equal to that rule's in numpy.  Refuses NULL pointers, a
+ * desired_kl that is not positive and finite, factor <= 1, lr_min <= 0 and lr_min > lr_max (a NaN fails each of these).
+ * Added without a change of UAV_ABI_VERSION (symbols only). */
+int uav_lr_adapt(uav_ctx* ctx, double* state, const double* diag8, double desired_kl, double factor, double lr_min,
+                 double lr_max, float* lr_out, uav_stream stream);
 /* nn.SmoothL1Loss(beta), reduction mean (train_lstm.py:66), forward + backward: loss_mean f64[1] device,
  * dpred [n] = d(loss)/d(pred).  |pred - target| == beta takes the linear branch (gradient +-1/n), as in torch.  A NaN element
  * makes the loss NaN and its own dpred NaN; the other elements' gradients are unaffected. */

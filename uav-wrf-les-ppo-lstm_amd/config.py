@@ -63,6 +63,14 @@ NORMALISE_REWARDS = False  # True: the GAE reads the reward scaled by the runnin
 REWARD_CLIP = 10.0       # ... and clamped to +-REWARD_CLIP afterwards (None: no clamp)
 NORMALISE_OBS = False    # True: running per-channel observation statistics folded into the policy's first layer (obs_norm_state.npz); the saved model is the folded one
 OBS_NORM_EPS = 1e-4      # ... with inv_sigma = 1 / sqrt(var + OBS_NORM_EPS): at most 100, the bound of a channel that is constant so far
+LR_SCHEDULE = "constant" # "linear": LEARNING_RATE -> LR_FINAL over SCHEDULE_ITERATIONS iterations | "adaptive": the rate follows the update's approx. KL (lr_state.npz)
+LR_FINAL = None          # "linear": the rate from iteration SCHEDULE_ITERATIONS on
+ENTROPY_BETA_FINAL = None  # a number: ENTROPY_BETA -> this over SCHEDULE_ITERATIONS iterations, under any LR_SCHEDULE; None keeps ENTROPY_BETA
+SCHEDULE_ITERATIONS = None  # the iterations the two linear schedules run over (they hold their final value afterwards)
+DESIRED_KL = None        # "adaptive": the rate is divided by LR_FACTOR after an update whose approx. KL (k3) exceeds 2 x this, multiplied below half of it; implies PPO_DIAGNOSTICS
+LR_FACTOR = 1.5          # ... the factor of one such change
+LR_MIN = 1e-6            # ... the lowest rate it reaches
+LR_MAX = 1e-2            # ... and the highest; LEARNING_RATE starts inside [LR_MIN, LR_MAX]
 GAE_MODE = "reference_exact"   # or "standard" (PPOV1.0/ppo0.0.py:337-350)
 SEED = 1234
 BC_EPOCHS = 10           # behaviour cloning (train_bc.py): passes over the expert set ...

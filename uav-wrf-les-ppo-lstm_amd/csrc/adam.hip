@@ -24,6 +24,7 @@ __global__ __launch_bounds__(256) void sumsq_partial(const float* __restrict__ g
 // decay = 1 - lr * weight_decay (torch.optim.AdamW: param.mul_(decay) before the Adam update; 1 for plain Adam).
 // Every block first finishes the norm itself from the (<= 256) partial sums -- the same fixed-order reduction in each, so
 // all blocks get the same bits -- instead of a one-block kernel launch in between; block 0 publishes the norm.
+// The body is adam_step_body.h, shared with adam_dlr_kernel; here step_size = lr / bc1 was formed on the host.
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                    const double* __restrict__ partial, int nb, float max_norm,
@@ -31,42 +32,21 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    float step_size, float sqrt_bc2, float eps, float decay,
                                                    unsigned* __restrict__ pmax_bits) {
 #pragma clang fp contract(off)
-    __shared__ double sm[4];
-    __shared__ float coef_s;
-    double q = 0.0;
-    for (int i = threadIdx.x; i < nb; i += 256) q += partial[i];
-    q = block256_sum(q, sm);
-    if (threadIdx.x == 0) {
-        const float norm = (float)sqrt(q);
-        float coef = max_norm / (norm + 1e-6f);        // torch clip_grad_norm_
-        coef = coef > 1.0f ? 1.0f : coef;
-        if (!(max_norm > 0.f)) coef = 1.0f;            // max_norm <= 0: clipping disabled
-        coef_s = coef;
-        if (gnorm_out && blockIdx.x == 0) *gnorm_out = norm;
-    }
-    __syncthreads();
-    const float coef = coef_s;
-    float amax = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float gi = g[i] * coef;
-        const float mi = m[i] + (gi - m[i]) * (1.0f - b1);          // exp_avg.lerp_(grad, 1-beta1)
-        const float vi = v[i] * b2 + (1.0f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / sqrt_bc2 + eps;      // (exp_avg_sq.sqrt() / sqrt(bc2)).add_(eps)
-        const float pn = p[i] * decay - step_size * (mi / denom);
-        p[i] = pn;
-        amax = fmaxf(amax, pn == pn ? fabsf(pn) : __builtin_inff());      // a NaN parameter reads as "out of range"
-    }
-    if (pmax_bits) {       // max |param| after this step (bit patterns of non-negative floats order like the floats)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-        __shared__ float wmax[4];
-        if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = amax;
-        __syncthreads();
-        if (threadIdx.x == 0)      // ONE atomic per block: a few hundred to one address, not a few thousand
-            atomicMax(pmax_bits, __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]))));
-    }
+#include "adam_step_body.h"
+}
+
+// The rate read from device memory (uav_clip_adam_dlr): the host's expression (float)((double)lr / bc1) on the same operands --
+// an f64 division, correctly rounded here as there -- so the step is uav_clip_adam's to the bit.  No weight decay.
+__global__ __launch_bounds__(256) void adam_dlr_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                       float* __restrict__ m, float* __restrict__ v, int64_t n,
+                                                       const double* __restrict__ partial, int nb, float max_norm,
+                                                       float* __restrict__ gnorm_out, float b1, float b2,
+                                                       const float* __restrict__ lr_dev, double bc1, float sqrt_bc2, float eps,
+                                                       unsigned* __restrict__ pmax_bits) {
+#pragma clang fp contract(off)
+    const float step_size = (float)((double)lr_dev[0] / bc1);
+    const float decay = 1.0f;
+#include "adam_step_body.h"
 }
 
 // out[0] = max |x[i]| (NaN counts as +inf); *out zeroed by the memset in front of the launch.
@@ -91,23 +71,50 @@ extern "C" int uav_absmax(uav_ctx* ctx, const float* x, int64_t n, float* out, u
     return 0;
 }
 
+// What both step launches take from the norm pass and the step count.
+struct adam_plan {
+    double* partial;
+    int nb, ab;
+    double bc1;
+    float sqrt_bc2;
+};
+
+// The norm pass (launched here) and the step kernel's grid and bias corrections.
+static adam_plan adam_norm_pass(uav_ctx* ctx, const float* grad, int64_t n, int64_t step, float beta1, float beta2,
+                                unsigned* pmax_bits, uav_stream stream) {
+    adam_plan a;
+    a.partial = (double*)ctx->ws;
+    a.nb = (int)((n + 1023) / 1024);
+    if (a.nb > NORM_BLOCKS) a.nb = NORM_BLOCKS;
+    hipLaunchKernelGGL(sumsq_partial, dim3(a.nb), dim3(256), 0, as_stream(stream), grad, n, a.partial, pmax_bits);
+    a.bc1 = 1.0 - pow((double)beta1, (double)step);
+    a.sqrt_bc2 = (float)sqrt(1.0 - pow((double)beta2, (double)step));
+    a.ab = (int)((n + 255) / 256);
+    if (a.ab > 2048) a.ab = 2048;
+    return a;
+}
+
 static int clip_adam_impl(uav_ctx* ctx, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                           int64_t step, float lr, float beta1, float beta2, float eps, float weight_decay, float max_norm,
                           float* gnorm_out, float* pmax_out, uav_stream stream) {
     UAV_REQUIRE(ctx && param && grad && exp_avg && exp_avg_sq && n > 0 && step >= 1, "uav_clip_adam: bad argument");
     unsigned* pmax_bits = reinterpret_cast<unsigned*>(pmax_out);
-    double* partial = (double*)ctx->ws;
-    int nb = (int)((n + 1023) / 1024);
-    if (nb > NORM_BLOCKS) nb = NORM_BLOCKS;
-    hipLaunchKernelGGL(sumsq_partial, dim3(nb), dim3(256), 0, as_stream(stream), grad, n, partial, pmax_bits);
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float sqrt_bc2 = (float)sqrt(bc2);
-    int ab = (int)((n + 255) / 256);
-    if (ab > 2048) ab = 2048;
-    hipLaunchKernelGGL(adam_kernel, dim3(ab), dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq, n,
-                       partial, nb, max_norm, gnorm_out, beta1, beta2, step_size, sqrt_bc2, eps, 1.0f - lr * weight_decay, pmax_bits);
+    const adam_plan a = adam_norm_pass(ctx, grad, n, step, beta1, beta2, pmax_bits, stream);
+    const float step_size = (float)((double)lr / a.bc1);
+    hipLaunchKernelGGL(adam_kernel, dim3(a.ab), dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq, n,
+                       a.partial, a.nb, max_norm, gnorm_out, beta1, beta2, step_size, a.sqrt_bc2, eps, 1.0f - lr * weight_decay, pmax_bits);
+    UAV_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int uav_clip_adam_dlr(uav_ctx* ctx, float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                 int64_t step, const float* lr_dev, float beta1, float beta2, float eps, float max_norm,
+                                 float* gnorm_out, float* pmax_out, uav_stream stream) {
+    UAV_REQUIRE(ctx && param && grad && exp_avg && exp_avg_sq && lr_dev && n > 0 && step >= 1, "uav_clip_adam_dlr: bad argument");
+    unsigned* pmax_bits = reinterpret_cast<unsigned*>(pmax_out);
+    const adam_plan a = adam_norm_pass(ctx, grad, n, step, beta1, beta2, pmax_bits, stream);
+    hipLaunchKernelGGL(adam_dlr_kernel, dim3(a.ab), dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq, n,
+                       a.partial, a.nb, max_norm, gnorm_out, beta1, beta2, lr_dev, a.bc1, a.sqrt_bc2, eps, pmax_bits);
     UAV_LAUNCH_CHECK();
     return 0;
 }

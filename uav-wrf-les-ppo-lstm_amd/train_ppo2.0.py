@@ -15,6 +15,7 @@ from config import (BATCH_SIZE, BPTT_LEN, CLIP_EPSILON, DIST_BACKEND, ENTROPY_BE
                     GRID_SIZE, HIDDEN, HORIZON, ITERATIONS, LAMBDA, LEARNING_RATE, LOCAL_RANK, MAX_STEPS, NUM_ENVS, NUM_LAYERS,
                     NORMALISE_OBS, NORMALISE_REWARDS, NUM_MINIBATCHES, OBS_NORM_EPS, POLICY, PPO_DIAGNOSTICS, RANK, REWARD_CLIP, SEED, SHUFFLE_ENVS, TARGET_KL, TREND_K,
                     WORLD_SIZE)  # noqa: F401
+from config import DESIRED_KL, ENTROPY_BETA_FINAL, LR_FACTOR, LR_FINAL, LR_MAX, LR_MIN, LR_SCHEDULE, SCHEDULE_ITERATIONS
 from environment import MethaneEnv
 from model import PPOActorCritic, PPOBuffer, PPOTrainer
 from uavppo import ops
@@ -181,13 +182,19 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
                        gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, bptt_len=BPTT_LEN, log_info=True, gamma=GAMMA, lam=LAMBDA,
                        clip=CLIP_EPSILON, ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, rank=rank, world_size=world,
                        bank=bank, bank_sources=bank_src, trend_k=TREND_K, diagnostics=PPO_DIAGNOSTICS, target_kl=TARGET_KL,
-                       normalise_rewards=NORMALISE_REWARDS, reward_clip=REWARD_CLIP, normalise_obs=NORMALISE_OBS, obs_norm_eps=OBS_NORM_EPS)
-    # config.PPO_DIAGNOSTICS (or TARGET_KL): update_diagnostics.csv beside the episode CSV, one row per iteration (rank 0; the values
+                       normalise_rewards=NORMALISE_REWARDS, reward_clip=REWARD_CLIP, normalise_obs=NORMALISE_OBS, obs_norm_eps=OBS_NORM_EPS,
+                       lr_schedule=LR_SCHEDULE, lr_final=LR_FINAL, ent_beta_final=ENTROPY_BETA_FINAL, schedule_iterations=SCHEDULE_ITERATIONS,
+                       desired_kl=DESIRED_KL, lr_factor=LR_FACTOR, lr_min=LR_MIN, lr_max=LR_MAX)
+    # config.PPO_DIAGNOSTICS (or TARGET_KL, or LR_SCHEDULE "adaptive"): update_diagnostics.csv beside the episode CSV, one row per iteration (rank 0; the values
     # are over all ranks' samples).  Reading them waits for the update: one host wait per iteration that a run without them does not have.
-    diag_log = None
-    if PPO_DIAGNOSTICS or TARGET_KL is not None:
-        from uavppo.update_log import UpdateDiagnosticsLog, path_beside, progress_text
-        diag_log = UpdateDiagnosticsLog(path_beside(csv_path) if rank == 0 else None)
+    # With a schedule in force the row ends in the step size and entropy weight its update ran with: read when the row before it was
+    # written (the adaptive rate is on the device, and by then the update that set it has been waited for).
+    diag_log, sched = None, ()
+    if PPO_DIAGNOSTICS or TARGET_KL is not None or LR_SCHEDULE == "adaptive":
+        from uavppo.update_log import SCHEDULE_COLUMNS, UpdateDiagnosticsLog, path_beside, progress_text
+        scheduled = LR_SCHEDULE != "constant" or ENTROPY_BETA_FINAL is not None
+        diag_log = UpdateDiagnosticsLog(path_beside(csv_path) if rank == 0 else None, SCHEDULE_COLUMNS if scheduled else ())
+        sched = (tr.learning_rate(), tr.entropy_beta()) if scheduled else ()
     rows_per_iter = []                  # this rank's rows, iteration by iteration (merged in rank order at the end)
     traj = None
     # The CSV rows are reduced on the device (uav_episode_rows: f64 running sums per env row, one 12-double row per ended episode)
@@ -271,7 +278,8 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
         it += 1
         diag = tr.diagnostics() if diag_log is not None else None
         if diag is not None:
-            diag_log.add(it, diag)
+            diag_log.add(it, diag, sched)
+            sched = (tr.learning_rate(), tr.entropy_beta()) if sched else ()      # the next update's
         if log_every and it % log_every == 0:
             pl, vl, ent = tr.losses()              # (also where NaN probabilities raise, on every rank together)
             if rank == 0:
@@ -303,6 +311,9 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
         if tr.obs_norm is not None and model_path:         # config.NORMALISE_OBS: the saved model is the folded one; the running state and the master beside it
             from uavppo.obs_norm import save_state as save_obs_state
             save_obs_state(tr.obs_norm, model_path)
+        if tr.lr_control is not None and model_path:       # config.LR_SCHEDULE "adaptive": the rate the run ended at and the rule's counters
+            from uavppo.lr_control import save_state as save_lr_state
+            save_lr_state(tr.lr_control, model_path)
     if world > 1:
         dist.barrier()
     return tr, rows

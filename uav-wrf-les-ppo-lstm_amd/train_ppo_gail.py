@@ -14,6 +14,7 @@ import torch
 
 from config import (BPTT_LEN, CLIP_EPSILON, ENTROPY_BETA, ENV_VARIANT, EPOCHS, GAE_MODE, GAMMA, HIDDEN, HORIZON, LAMBDA, LEARNING_RATE, NUM_ENVS,
                     NORMALISE_OBS, NORMALISE_REWARDS, NUM_LAYERS, NUM_MINIBATCHES, OBS_NORM_EPS, POLICY, PPO_DIAGNOSTICS, REWARD_CLIP, SEED, SHUFFLE_ENVS, TARGET_KL)
+from config import DESIRED_KL, ENTROPY_BETA_FINAL, LR_FACTOR, LR_FINAL, LR_MAX, LR_MIN, LR_SCHEDULE, SCHEDULE_ITERATIONS
 from model import Discriminator, compute_discriminator_loss, get_expert_data  # noqa: F401  (train_ppo_gail.py:24-27)
 from uavppo.gail import GAILTrainer
 
@@ -33,20 +34,27 @@ def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert
                      ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, expert=(states, actions), gail_coef=gail_coef,
                      env_coef=env_coef, disc_lr=disc_lr, disc_steps=disc_steps, update_form=update_form, minibatch_rows=minibatch_rows,
                      diagnostics=PPO_DIAGNOSTICS, target_kl=TARGET_KL, normalise_rewards=NORMALISE_REWARDS, reward_clip=REWARD_CLIP,
-                     normalise_obs=NORMALISE_OBS, obs_norm_eps=OBS_NORM_EPS)
+                     normalise_obs=NORMALISE_OBS, obs_norm_eps=OBS_NORM_EPS, lr_schedule=LR_SCHEDULE, lr_final=LR_FINAL,
+                     ent_beta_final=ENTROPY_BETA_FINAL, schedule_iterations=SCHEDULE_ITERATIONS, desired_kl=DESIRED_KL, lr_factor=LR_FACTOR,
+                     lr_min=LR_MIN, lr_max=LR_MAX)
     if init_model is not None:
         tr.policy.load_state_dict(torch.load(init_model, map_location="cpu"))
-    # config.PPO_DIAGNOSTICS (or TARGET_KL): update_diagnostics.csv beside the saved policy, one row per iteration (one host wait each)
+    # config.PPO_DIAGNOSTICS (or TARGET_KL, or LR_SCHEDULE "adaptive"): update_diagnostics.csv beside the saved policy, one row per
+    # iteration (one host wait each); with a schedule in force the row ends in the step size and entropy weight its update ran with
     diag_log = diag = None
-    if PPO_DIAGNOSTICS or TARGET_KL is not None:
-        from uavppo.update_log import UpdateDiagnosticsLog, path_beside, progress_text
-        diag_log = UpdateDiagnosticsLog(path_beside(model_path or "ppo_gail_model.pth"))
+    sched = ()
+    if PPO_DIAGNOSTICS or TARGET_KL is not None or LR_SCHEDULE == "adaptive":
+        from uavppo.update_log import SCHEDULE_COLUMNS, UpdateDiagnosticsLog, path_beside, progress_text
+        scheduled = LR_SCHEDULE != "constant" or ENTROPY_BETA_FINAL is not None
+        diag_log = UpdateDiagnosticsLog(path_beside(model_path or "ppo_gail_model.pth"), SCHEDULE_COLUMNS if scheduled else ())
+        sched = (tr.learning_rate(), tr.entropy_beta()) if scheduled else ()
     it, mean_rewards = 0, []
     while tr.episodes_lagged < num_episodes and (max_iterations is None or it < max_iterations):
         tr.train_iteration()
         if diag_log is not None:
             diag = tr.diagnostics()
-            diag_log.add(it + 1, diag)
+            diag_log.add(it + 1, diag, sched)
+            sched = (tr.learning_rate(), tr.entropy_beta()) if sched else ()      # the next update's
         if it % 10 == 0:
             ended = tr.buf["done"].sum().clamp(min=1.0)
             mean_rewards.append(float(tr.buf["rew"].sum() / ended))          # reward collected per episode ended in this rollout
@@ -71,6 +79,9 @@ def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert
     if tr.obs_norm is not None and model_path:             # config.NORMALISE_OBS: the saved policy is the folded one; state and master beside it
         from uavppo.obs_norm import save_state as save_obs_state
         save_obs_state(tr.obs_norm, model_path)
+    if tr.lr_control is not None and model_path:           # config.LR_SCHEDULE "adaptive": the rate the run ended at and the rule's counters
+        from uavppo.lr_control import save_state as save_lr_state
+        save_lr_state(tr.lr_control, model_path)
     print(f"training finished: {tr.episodes_done} episodes, {it} iterations; policy saved as {model_path}, discriminator as {disc_path}")
     return tr
 

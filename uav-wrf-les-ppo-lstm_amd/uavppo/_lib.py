@@ -89,6 +89,9 @@ SIGNATURES = {
     "uav_rollout_tail": (I32, [P, P, I32, P, P, I64, I32, P, P, I32, P, I64, I32, I32, U64, U64, I64, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "uav_clip_adam": (I32, [P, P, P, P, P, I64, I64, F32, F32, F32, F32, F32, P, P, P]),
     "uav_clip_adamw": (I32, [P, P, P, P, P, I64, I64, F32, F32, F32, F32, F32, F32, P, P]),
+    "uav_clip_adam_dlr": (I32, [P, P, P, P, P, I64, I64, P, F32, F32, F32, F32, P, P, P]),
+    "uav_lr_init": (I32, [P, P, F64, P, P]),
+    "uav_lr_adapt": (I32, [P, P, P, F64, F64, F64, F64, P, P]),
     "uav_smooth_l1": (I32, [P, P, P, I64, F32, P, P, P]),
     "uav_mse_bce": (I32, [P, P, P, I64, P, P, P]),
     "uav_disc_param_count": (SZ, [I32, I32, I32]),

@@ -537,6 +537,46 @@ def clip_adam(param, grad, exp_avg, exp_avg_sq, step, lr, beta1=0.9, beta2=0.999
           "uav_clip_adam")
 
 
+def clip_adam_dlr(param, grad, exp_avg, exp_avg_sq, step, lr_dev, beta1=0.9, beta2=0.999, eps=1e-8, max_norm=0.5,
+                  gnorm_out=None, pmax_out=None):
+    """clip_adam with the step size read from lr_dev (device f32 [1]) by the step kernel: clip_adam's bits for lr = lr_dev[0],
+    with no host read of the rate (uav_clip_adam_dlr)."""
+    n = param.numel()
+    for t, nm in ((grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        if t.numel() != n:
+            raise RuntimeError(f"clip_adam_dlr: {nm} has {t.numel()} elements, param has {n}")
+    if lr_dev is None:
+        raise RuntimeError("clip_adam_dlr: lr_dev is a device f32 [1] tensor")
+    check(lib().uav_clip_adam_dlr(_h(param), _p(param, F32, name="param"), _p(grad, F32, name="grad"),
+                                  _p(exp_avg, F32, name="exp_avg"), _p(exp_avg_sq, F32, name="exp_avg_sq"), n, int(step),
+                                  _p(lr_dev, F32, (1,), "lr_dev"), float(beta1), float(beta2), float(eps), float(max_norm),
+                                  _p(gnorm_out, F32, (1,), "gnorm_out"), _p(pmax_out, F32, (1,), "pmax_out"), _stream()),
+          "uav_clip_adam_dlr")
+
+
+LR_STATE_N = 6             # UAV_LR_STATE_N
+# the six slots, include/uavppo.h UAV_LR_STATE_*
+LR_STATE_NAMES = ("lr", "last_kl", "raised", "lowered", "held", "skipped")
+
+
+def lr_init(state, lr, lr_out=None):
+    """L1: state f64 [LR_STATE_N] = {lr, 0, 0, 0, 0, 0}; returns lr_out f32 [1] = (float)lr.  No host sync."""
+    lr_out = torch.empty(1, dtype=F32, device=state.device) if lr_out is None else lr_out
+    check(lib().uav_lr_init(_h(state), _p(state, F64, (LR_STATE_N,), "state"), float(lr), _p(lr_out, F32, (1,), "lr_out"), _stream()),
+          "uav_lr_init")
+    return lr_out
+
+
+def lr_adapt(state, diag8, desired_kl, factor, lr_min, lr_max, lr_out=None):
+    """L2: one update's decision (lr_control.adapt_rule) on state f64 [LR_STATE_N], in place, from the all-reduced diagnostic
+    sums diag8 f64 [PPO_DIAG_N] of the update's last epoch; returns lr_out f32 [1] = (float)lr.  No host sync."""
+    lr_out = torch.empty(1, dtype=F32, device=state.device) if lr_out is None else lr_out
+    check(lib().uav_lr_adapt(_h(state), _p(state, F64, (LR_STATE_N,), "state"), _p(diag8, F64, (PPO_DIAG_N,), "diag8"),
+                             float(desired_kl), float(factor), float(lr_min), float(lr_max), _p(lr_out, F32, (1,), "lr_out"),
+                             _stream()), "uav_lr_adapt")
+    return lr_out
+
+
 # ----------------------------------------------------------------------------- GEMM
 def gemm_rows(a, b_t, bias, out):
     """out[n, :] = a[n, :] @ b_t.T + bias for ROW-STRIDED 2-D views a [N, K] and out [N, M] (unit stride along the last

@@ -18,6 +18,7 @@ from . import ops
 from .curriculum_link import CurriculumLink
 from .dist_utils import allreduce_adv_stats, allreduce_grad, allreduce_sum, collectives_on, env_shard
 from .policy import LSTMActorCritic, MLPActorCritic
+from .lr_control import LrController, check_lr_control, linear_value
 from .range_guard import RangeGuard
 from .obs_norm import ObsNormaliser, check_obs_norm
 from .reward_norm import RewardNormaliser, check_reward_norm
@@ -164,7 +165,8 @@ class VecPPOTrainer:
                  rank=0, world_size=1, use_curriculum=True, trend_k=0, log_info=False, device_curriculum=None,
                  update_form="update_model", minibatch_rows=None, shuffle_envs=False, bptt_len=None, diagnostics=False,
                  target_kl=None, normalise_rewards=False, reward_clip=10.0, reward_norm_gamma=None, dgates_tile=None,
-                 normalise_obs=False, obs_norm_eps=1e-4, obs_norm_channels=None, **hp):
+                 normalise_obs=False, obs_norm_eps=1e-4, obs_norm_channels=None, lr_schedule="constant", lr_final=None,
+                 ent_beta_final=None, schedule_iterations=None, desired_kl=None, lr_factor=1.5, lr_min=1e-6, lr_max=1e-2, **hp):
         self.hp = dict(DEFAULTS)
         self.dgates_tile = dgates_tile       # gate gradients of the update in tile form: None = the rule of _request_dgates_tile, True / False = A/B
         self.hp.update(hp)
@@ -185,7 +187,17 @@ class VecPPOTrainer:
         self.target_kl = check_target_kl(target_kl)
         self.gae_mode, self.minibatch_rows, self._C = check_options(num_envs, horizon, policy, trend_k, update_form, gae_mode,
                                                                     num_minibatches, minibatch_rows, shuffle_envs, bptt_len)
-        self._diag_on = bool(diagnostics) or self.target_kl is not None
+        # lr_schedule / ent_beta_final (uavppo/lr_control.py): "linear" interpolates hp["lr"] -> lr_final over schedule_iterations
+        # iterations, by value into the same Adam kernel; ent_beta_final does the same for the entropy weight under any schedule;
+        # "adaptive" divides / multiplies the rate by lr_factor after an update whose last epoch's approx. KL left
+        # [desired_kl / 2, 2 desired_kl], on the device (self.lr_control), and implies the diagnostics.  hp["lr"] and
+        # hp["ent_beta"] stay the starting values.  "constant" without ent_beta_final: update() issues exactly the launches it did.
+        rows = self.minibatch_rows
+        steps = int(num_minibatches) if rows is None else -(-int(num_envs) * int(horizon) // rows)       # optimiser steps per epoch
+        self.schedule = check_lr_control(lr_schedule, self.hp["lr"], lr_final, ent_beta_final, schedule_iterations, desired_kl,
+                                         lr_factor, lr_min, lr_max, optimiser_steps=int(self.hp["epochs"]) * steps)
+        self.lr_schedule = self.schedule["lr_schedule"]
+        self._diag_on = bool(diagnostics) or self.target_kl is not None or self.lr_schedule == "adaptive"
         self.N, self.T = int(num_envs), int(horizon)
         self.rank, self.world = int(rank), int(world_size)
         self._coll = self.world > 1 or collectives_on()          # the three exchanges of an iteration are issued
@@ -218,6 +230,7 @@ class VecPPOTrainer:
         self._st = None              # scratch of one step of the step-wise rollouts: _step_scratch()
         self.opt_step = 0
         self.iteration = 0
+        self._lr = self._ent_beta = None       # the values update() runs with, set at its top
         if policy == "lstm":
             self.policy = LSTMActorCritic(D, hidden, layers, 5, self.device, seed=self.seed)
         else:
@@ -269,6 +282,9 @@ class VecPPOTrainer:
         self.reward_norm = (RewardNormaliser(N, self.T, self.reward_norm_gamma, self.reward_clip or None, device=d)
                             if self.normalise_rewards else None)
         self.obs_norm = ObsNormaliser(self.policy, self.kind, self.obs_norm_eps, self.obs_norm_mask, device=d) if self.normalise_obs else None
+        sc = self.schedule
+        self.lr_control = (LrController(self.hp["lr"], sc["desired_kl"], sc["lr_factor"], sc["lr_min"], sc["lr_max"], device=d)
+                           if self.lr_schedule == "adaptive" else None)
 
     def _alloc_policy_work(self, hidden, layers):
         """The recurrent state and the work arrays the update's kernels write their forward pass to."""
@@ -418,6 +434,8 @@ class VecPPOTrainer:
             self.reward_norm.reset()
         if self.obs_norm is not None:
             self.obs_norm.reset()
+        if self.lr_control is not None:
+            self.lr_control.reset(self.hp["lr"])
 
     # ------------------------------------------------------------------------------------------ R1
     def _stepwise_lstm_route(self):
@@ -650,8 +668,12 @@ class VecPPOTrainer:
         if self.record_grads:            # (gradient, parameters it was taken at)
             self.grad_log.append((grad.clone(), params.clone()))
         self.opt_step += 1
-        ops.clip_adam(params, grad, self.exp_avg, self.exp_avg_sq, self.opt_step, hp["lr"],
-                      max_norm=hp["max_grad_norm"], gnorm_out=self.gnorm, pmax_out=self.guard.ranges[0:1])
+        if self.lr_control is not None:  # the rate the last update's KL left on the device; never read here
+            ops.clip_adam_dlr(params, grad, self.exp_avg, self.exp_avg_sq, self.opt_step, self.lr_control.lr_dev,
+                              max_norm=hp["max_grad_norm"], gnorm_out=self.gnorm, pmax_out=self.guard.ranges[0:1])
+        else:
+            ops.clip_adam(params, grad, self.exp_avg, self.exp_avg_sq, self.opt_step, self._lr,
+                          max_norm=hp["max_grad_norm"], gnorm_out=self.gnorm, pmax_out=self.guard.ranges[0:1])
         if on is not None:               # policy.flat <- fold(master); the guard's slot raised to max |policy.flat|
             on.fold(self.guard.ranges[0:1])
         if self.record:
@@ -665,7 +687,7 @@ class VecPPOTrainer:
         for rows in self._next_perm().split(self.minibatch_rows):
             self._last_n = rows.numel()
             grad = ops.mlp_ppo_grad_rows(self.policy.flat, *flat, rows.contiguous(), 1.0 / float(rows.numel() * self.world),
-                                         hp["clip"], hp["ent_beta"], self.loss_sums, self.policy.grad, self.trend_k)
+                                         hp["clip"], self._ent_beta, self.loss_sums, self.policy.grad, self.trend_k)
             self._optimiser_step(grad)
 
     def _epoch_envs(self, grad_of, inv_n):
@@ -677,7 +699,7 @@ class VecPPOTrainer:
         if self.record:
             self.perm_log.append(perm)
         loss = (pk["act"].view(-1), pk["logp"].view(-1), pk["adv_n"].view(-1), pk["ret"].view(-1), pk["val"].view(-1), inv_n,
-                hp["clip"], hp["ent_beta"], self.loss_sums, self.dheads, self.dhead_bias)
+                hp["clip"], self._ent_beta, self.loss_sums, self.dheads, self.dhead_bias)
         for m in range(self.num_minibatches):
             ops.gather_rows_multi(perm[m * nb:(m + 1) * nb], self._pack_plan)
             self._optimiser_step(grad_of(None, loss, pk))
@@ -716,6 +738,9 @@ class VecPPOTrainer:
         shuffled rows.  With diagnostics / target_kl the epochs run under _epochs_with_diagnostics, which may end them early."""
         if self.check_ranges() != "fp16x3":
             self._rollout_forward_valid = False
+        # this iteration's step size and entropy weight, for all its steps (adaptive: the rate stays on the device, unread)
+        self._lr = None if self.lr_control is not None else self.learning_rate()
+        self._ent_beta = self.entropy_beta()
         self.compute_advantages()
         self.link.in_update()             # (the success exchange, behind the advantage-statistics all-reduce)
         u, hp = self._u, self.hp
@@ -733,7 +758,7 @@ class VecPPOTrainer:
             for m in range(self.num_minibatches):
                 sl = slice(m * nb, (m + 1) * nb)
                 grad = grad_of(sl, (u["act"][sl].reshape(-1), u["logp"][sl].reshape(-1), u["adv_n"][sl].reshape(-1),
-                                    u["ret"][sl].reshape(-1), u["val"][sl].reshape(-1), inv_n, hp["clip"], hp["ent_beta"],
+                                    u["ret"][sl].reshape(-1), u["val"][sl].reshape(-1), inv_n, hp["clip"], self._ent_beta,
                                     self.loss_sums, self.dheads, self.dhead_bias))
                 self._optimiser_step(grad)
 
@@ -774,6 +799,8 @@ class VecPPOTrainer:
             ops.set_ppo_diag(None, self.device)
         if self.target_kl is None and self._coll:
             allreduce_sum(self._diag_epochs)
+        if self.lr_control is not None:   # once per update, behind the all-reduce of the row it reads: the next update's rate
+            self.lr_control.adapt(self._diag_epochs[self._diag_epochs_run - 1])
 
     def diagnostics(self):
         """The last update()'s per-epoch diagnostics (diagnostics_from_sums: approx_kl, approx_kl_k1, clip_fraction,
@@ -782,6 +809,23 @@ class VecPPOTrainer:
         if not self._diag_on:
             raise RuntimeError("diagnostics(): build the trainer with diagnostics=True (or a target_kl)")
         return diagnostics_from_sums(self._diag_epochs.cpu().numpy(), epochs_run=self._diag_epochs_run)
+
+    def learning_rate(self):
+        """The step size the NEXT update() runs with: hp["lr"], its linear interpolation at self.iteration, or -- adaptive -- the
+        controller's rate, which is a host read (for logs, not for the loop: update() never calls it then)."""
+        sc = self.schedule
+        if self.lr_control is not None:
+            return self.lr_control.lr()
+        if self.lr_schedule == "linear":
+            return float(linear_value(self.hp["lr"], sc["lr_final"], self.iteration, sc["schedule_iterations"]))
+        return self.hp["lr"]
+
+    def entropy_beta(self):
+        """The entropy weight the NEXT update() runs with: hp["ent_beta"], or its linear interpolation at self.iteration."""
+        sc = self.schedule
+        if sc["ent_beta_final"] is None:
+            return self.hp["ent_beta"]
+        return float(linear_value(self.hp["ent_beta"], sc["ent_beta_final"], self.iteration, sc["schedule_iterations"]))
 
     def time_rollouts(self, event_pairs):
         """Measurement hook (bench.py): the next len(event_pairs) calls of train_iteration() record a (start, end) pair of

@@ -9,6 +9,7 @@ import os
 FILE_NAME = "update_diagnostics.csv"
 VALUES = ("approx_kl", "approx_kl_k1", "clip_fraction", "value_clip_fraction", "explained_variance")
 COLUMNS = ("Iteration", "Epochs_Run") + tuple(v.title() for v in VALUES)
+SCHEDULE_COLUMNS = ("Learning_Rate", "Entropy_Beta")      # the values the iteration's update ran with, when a schedule is in force
 
 
 def path_beside(csv_path):
@@ -29,20 +30,24 @@ def progress_text(diag):
 
 class UpdateDiagnosticsLog:
     """Rows are flushed as they come: a run that is interrupted keeps what it measured.  path None (a rank other than 0, or a run
-    without a CSV) keeps the rows in memory only."""
+    without a CSV) keeps the rows in memory only.  extra_columns: names of further columns behind COLUMNS (a run with a
+    schedule: SCHEDULE_COLUMNS), whose values add() then takes; without them the file is what it has always been."""
 
-    def __init__(self, path):
+    def __init__(self, path, extra_columns=()):
         self.path, self.rows = path, []
+        self.extra_columns = tuple(extra_columns)
         self._f = self._w = None
         if path:
             os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
             self._f = open(path, "w", newline="")
             self._w = csv.writer(self._f, lineterminator="\n")
-            self._w.writerow(COLUMNS)
+            self._w.writerow(COLUMNS + self.extra_columns)
             self._f.flush()
 
-    def add(self, iteration, diag):
-        row = last_epoch_row(iteration, diag)
+    def add(self, iteration, diag, extra=()):
+        if len(extra) != len(self.extra_columns):
+            raise ValueError(f"{len(extra)} extra values for the columns {self.extra_columns}")
+        row = last_epoch_row(iteration, diag) + [float(v) for v in extra]
         self.rows.append(row)
         if self._w is not None:
             self._w.writerow(row)

@@ -19,6 +19,13 @@ sequence:
 Forward (uav_lstm_fwd), H in {64, 128}, T in {8, 9, 17, 40} (one chunk of 8 steps; a one-step tail chunk; three chunks; five),
 N in {16, 20} (a full tile of 16 envs; a second tile with 12 dead env lanes), every combination of stash / heads / keep given or not
 and I = 6 or 3 (padding features), plus the form that reads its input projection from the stash (I = 16).
+BPTT + weight gradients (uav_lstm_bwd + uav_lstm_wgrad on the stash and y of run_fwd in the same arithmetic), H in {64, 128}, I = 6, keep,
+non-zero dhn / dcn, (N, T) in {(16, 8), (20, 9), (20, 40)} (a full tile; a second tile with 12 dead env lanes and an odd T; several
+staging chunks), driven once by dheads + w_head (the split BPTT) and once by plain dy (the exact-f32 lstm_bwd_kernel in every
+arithmetic): the gate gradients as f32 rows, dh0, dc0 and every weight gradient.  (N, T) = (20, 32) once more with the gate gradients
+in tile form (the _tile kernels' own bits).
+Every case above runs on fp16x3.  A case whose name ends in -bf16x6 or -f32_mfma runs on that arithmetic: the forward at T in {9, 17},
+N = 20 (i6-stash-heads-keep and i16), the BPTT at (20, 9), the weight gradients at (48, 40) and (20, 8).
 """
 import hashlib
 import itertools
@@ -38,6 +45,11 @@ DEV = "cuda:0"
 PATH = os.path.join(ROOT, "tests", "golden", "update_bits.json")
 WGRAD_SHAPES = ((256, 96), (48, 40), (20, 8), (20, 9))
 FWD_T, FWD_N = (8, 9, 17, 40), (16, 20)
+BWD_SHAPES, BWD_TILE_SHAPE = ((16, 8), (20, 9), (20, 40)), (20, 32)
+ARITHS = ("fp16x3", "bf16x6", "f32_mfma")
+OTHER_FWD_T, OTHER_FWD_N, OTHER_BWD_SHAPE, OTHER_WGRAD_SHAPES = (9, 17), 20, (20, 9), ((48, 40), (20, 8))
+OTHER_FWD_COMBOS = ((6, True, True, True), (16, True, True, True), (16, True, False, True))
+BWD_DRIVES = ("heads", "dy")
 NHD = 6
 
 
@@ -111,9 +123,9 @@ def fwd_inputs(H, T, N, I):
             "w_head": _uni(rs, (NHD, H), 3 * b), "b_head": _uni(rs, NHD, 0.5)}
 
 
-def run_fwd(inp, stash, heads, keep, arith="fp16x3"):
+def run_fwd(inp, stash, heads, keep, arith="fp16x3", whole_stash=False):
     """{y, hn, cn[, stash][, heads]} of uav_lstm_fwd.  Of the stash rows the gates and c_prev are always part of the contract, the
-    h_prev slot only where the kernel writes it (I > 6)."""
+    h_prev slot only where the kernel writes it (I > 6); whole_stash: the buffer as it is, for the BPTT to read."""
     from uavppo import ops
     N, T, I = inp["x"].shape
     hb = torch.full((N, T, NHD), float("nan"), device=DEV) if heads else None
@@ -125,7 +137,7 @@ def run_fwd(inp, stash, heads, keep, arith="fp16x3"):
     out = {"y": y, "hn": hn, "cn": cn}
     if stash:
         H = y.shape[-1]
-        out["stash"] = st if I > 6 else st[..., :5 * H].contiguous()
+        out["stash"] = st if I > 6 or whole_stash else st[..., :5 * H].contiguous()
     if heads:
         out["heads"] = hb
     return out
@@ -152,7 +164,67 @@ def want_fwd(inp, keep):
     return {"y": y, "hn": h, "cn": c, "stash": torch.stack(st, 1), "heads": y @ d["w_head"].T + d["b_head"]}
 
 
+# ------------------------------------------------------------------------------------------------ BPTT + weight gradients
+BWD_BUFFERS = ("dgates", "dh0", "dc0", "dw_ih", "dw_hh", "db", "dw_head")
+
+
+def bwd_inputs(H, N, T):
+    """fwd_inputs at I = 6 and what drives the backward: head gradients, plain dy, and gradients of the final state"""
+    inp = fwd_inputs(H, T, N, 6)
+    rs = np.random.RandomState(1000 * H + 10 * T + N + 5)
+    inp.update(dheads=(rs.randn(N, T, NHD) * 1e-2).astype(np.float32), dy=(rs.randn(N, T, H) * 1e-2).astype(np.float32),
+               dhn=_uni(rs, (N, H), 1e-2), dcn=_uni(rs, (N, H), 1e-2))
+    return inp
+
+
+def run_bwd(inp, drive, arith="fp16x3", tile=False):
+    """{dgates (f32 rows), dh0, dc0, dw_ih, dw_hh, db[, dw_head]} of uav_lstm_bwd + uav_lstm_wgrad, driven by dheads + w_head ("heads")
+    or by plain dy ("dy"), on the stash and y of run_fwd in the same arithmetic; tile: the gate gradients in tile form"""
+    from uavppo import ops
+    N, T, I = inp["x"].shape
+    f = run_fwd(inp, True, False, True, arith, whole_stash=True)
+    H = f["y"].shape[-1]
+    by = ({"dheads": _dev(inp["dheads"]), "w_head": _dev(inp["w_head"])} if drive == "heads" else {"dy": _dev(inp["dy"])})
+    with ops.lstm_arith(arith):
+        dg = None
+        if tile:
+            dg = ops.lstm_dgates_tile(N, T, I, H, DEV)
+            assert dg is not None, ops.lib().uav_last_error()
+            dg.fill_(float("nan"))
+        try:
+            g = ops.lstm_bwd(_dev(inp["x"]), _dev(inp["keep"]), f["stash"], _dev(inp["w_ih"]), _dev(inp["w_hh"]), f["y"], _dev(inp["h0"]),
+                             dhn=_dev(inp["dhn"]), dcn=_dev(inp["dcn"]), dgates=dg, dgates_tile=tile, **by)
+            g["dgates"] = ops.lstm_dgates_f32(g["dgates"], N, T, H)
+        finally:
+            if tile:
+                ops.lstm_dgates_forget(dg)
+    torch.cuda.synchronize()
+    return {k: g[k] for k in BWD_BUFFERS if g[k] is not None}
+
+
 # ------------------------------------------------------------------------------------------------ the cases
+def _bwd_case(H, N, T, arith, tile=False):
+    def bwd():
+        inp = bwd_inputs(H, N, T)
+        return {d + "." + k: v for d in (("heads",) if tile else BWD_DRIVES) for k, v in run_bwd(inp, d, arith, tile).items()}
+    return bwd
+
+
+def _fwd_case(H, T, N, combos, arith):
+    def fwd():
+        out = {}
+        for I, s, h, k in combos:
+            for name, v in run_fwd(fwd_inputs(H, T, N, I), s, h, k, arith).items():
+                out[combo_name(I, s, h, k) + "." + name] = v
+        return out
+    return fwd
+
+
+def case_arith(name):
+    """the arithmetic a case runs on: its name's suffix, fp16x3 without one"""
+    return next((a for a in ARITHS if name.endswith("-" + a)), "fp16x3")
+
+
 def cases():
     """name -> callable() -> {buffer name: tensor}"""
     c = {}
@@ -163,19 +235,25 @@ def cases():
                     lambda H=H, N=N, T=T, hd=heads: run_wgrad(wgrad_inputs(H, N, T), hd))
         for T in FWD_T:
             for N in FWD_N:
-                def fwd(H=H, T=T, N=N):
-                    out = {}
-                    for I, s, h, k in fwd_combos():
-                        for name, v in run_fwd(fwd_inputs(H, T, N, I), s, h, k).items():
-                            out[combo_name(I, s, h, k) + "." + name] = v
-                    return out
-                c["fwd-h%d-t%d-n%d" % (H, T, N)] = fwd
+                c["fwd-h%d-t%d-n%d" % (H, T, N)] = _fwd_case(H, T, N, fwd_combos(), "fp16x3")
+        for N, T in BWD_SHAPES:
+            c["bwd-h%d-n%d-t%d-fp16x3" % (H, N, T)] = _bwd_case(H, N, T, "fp16x3")
+        for a in ARITHS[:2]:                                                      # the exact-f32 kernels read rows only
+            c["bwd-tile-h%d-n%d-t%d-%s" % ((H,) + BWD_TILE_SHAPE + (a,))] = _bwd_case(H, *BWD_TILE_SHAPE, a, tile=True)
+        for a in ARITHS[1:]:
+            for T in OTHER_FWD_T:
+                c["fwd-h%d-t%d-n%d-%s" % (H, T, OTHER_FWD_N, a)] = _fwd_case(H, T, OTHER_FWD_N, OTHER_FWD_COMBOS, a)
+            c["bwd-h%d-n%d-t%d-%s" % ((H,) + OTHER_BWD_SHAPE + (a,))] = _bwd_case(H, *OTHER_BWD_SHAPE, a)
+            for N, T in OTHER_WGRAD_SHAPES:
+                for heads in (False, True):
+                    c["wgrad-h%d-n%d-t%d-%s-%s" % (H, N, T, "heads" if heads else "noheads", a)] = (
+                        lambda H=H, N=N, T=T, hd=heads, a=a: run_wgrad(wgrad_inputs(H, N, T), hd, a))
     return c
 
 
 def run_case(name):
     from uavppo import ops
-    with ops.lstm_arith("fp16x3"):
+    with ops.lstm_arith(case_arith(name)):
         return {k: _sha(v) for k, v in cases()[name]().items()}
 
 

@@ -3,7 +3,10 @@ lane-spill traffic (v_readlane + v_writelane) of every kernel, before and after 
 
     python tools/kernel_static_table.py OLD_CSRC NEW_CSRC rollout mlp_fused greedy_tail env loss > profiles/NAME.md
 
-Each file is compiled to device assembly with the Makefile's flags (FAST_TU files with -ffp-contract=fast).  The kernels of all
+Each file is compiled to device assembly with its own tree's flags: the files a tree's csrc/Makefile names in a `FAST_TU :=` line
+(trees from before the sequence kernels' FMAs were written out) get -ffp-contract=fast, a tree without that line has one flag set.
+OLD_EXTRA_FLAGS in the environment is appended for the first tree only: with the same tree given twice, a what-if build against
+the real one (`OLD_EXTRA_FLAGS=-ffp-contract=fast ... NEW_CSRC NEW_CSRC lstm wgrad`: what is left to contract).  The kernels of all
 named files are collected per tree -- a file that a tree does not have is skipped -- and matched by kernel name, so a kernel
 that moved between files is followed (`... OLD_CSRC NEW_CSRC mlp_fused mlp_rollout mlp_update`).  A template kernel whose
 argument list gained a trailing `false` (a new defaulted bool) is matched with its old name; a kernel only one tree has is listed
@@ -22,14 +25,19 @@ import tempfile
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
-FAST_TU = ("lstm", "wgrad")
 
 
-def kernels(csrc, tu):
+def fast_tu(csrc):
+    """the files of this tree that its Makefile builds with -ffp-contract=fast: none unless it has a FAST_TU line"""
+    m = re.search(r"^FAST_TU\s*:?=(.*)$", open(os.path.join(csrc, "Makefile")).read(), re.M)
+    return m.group(1).split() if m else []
+
+
+def kernels(csrc, tu, what_if=()):
     """{demangled kernel name: dict(tu, vgpr, sgpr, scratch, lds, insts, lanes, sha, ops)} of csrc/tu.hip"""
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, tu + ".s")
-        extra = ["-ffp-contract=fast"] if tu in FAST_TU else []
+        extra = (["-ffp-contract=fast"] if tu in fast_tu(csrc) else []) + list(what_if)
         subprocess.run([HIPCC, *FLAGS, *extra, "--cuda-device-only", "-S", os.path.join(csrc, tu + ".hip"), "-o", out], check=True)
         txt = open(out).read()
     res = {}
@@ -54,12 +62,12 @@ def kernels(csrc, tu):
     return res
 
 
-def tree(csrc, tus):
+def tree(csrc, tus, what_if=()):
     """the kernels of every file of `tus` that the tree has, by kernel name"""
     res = {}
     for tu in tus:
         if os.path.exists(os.path.join(csrc, tu + ".hip")):
-            res.update(kernels(csrc, tu))
+            res.update(kernels(csrc, tu, what_if))
     return res
 
 
@@ -68,7 +76,7 @@ def main():
     print("| file | kernel | VGPR | SGPR | scratch B | static LDS B | instructions | v_readlane + v_writelane | stream |")
     print("|---|---|---|---|---|---|---|---|---|")
     cell = lambda a, b: str(a) if a == b else f"{a} -> {b}"                                         # noqa: E731
-    a, b = tree(old, tus), tree(new, tus)
+    a, b = tree(old, tus, os.environ.get("OLD_EXTRA_FLAGS", "").split()), tree(new, tus)
     # a template that gained a defaulted trailing bool: old `name<args>` is new `name<args, false>`, listed under the new name
     for k in [k for k in a if k not in b and k.endswith(">") and k[:-1] + ", false>" in b]:
         a[k[:-1] + ", false>"] = a.pop(k)

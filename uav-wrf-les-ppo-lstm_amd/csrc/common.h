@@ -103,6 +103,18 @@ __device__ __forceinline__ float fast_tanh(float x) {
     p = __builtin_fmaf(p, x2, 1.0f);
     return __builtin_fabsf(x) < 0.25f ? x * p : big;
 }
+// The same function with `big` as ONE fma, 1 - 2 r rounded once: what the h = 64 / 128 sequence kernels of lstm.hip compute (forward
+// and BPTT, every arithmetic).  The plain form above is everybody else's: the fused rollout, greedy and tail kernels (rollout.hip),
+// the h = 256 step path (lstm_h3.hip), lstm_generic.hip and peak_stop.hip.  The two differ in the last bit of some results.
+__device__ __forceinline__ float fast_tanh_fma(float x) {
+    const float big = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(__expf(2.0f * x) + 1.0f), 1.0f);
+    const float x2 = x * x;
+    float p = __builtin_fmaf(x2, 62.0f / 2835.0f, -17.0f / 315.0f);
+    p = __builtin_fmaf(p, x2, 2.0f / 15.0f);
+    p = __builtin_fmaf(p, x2, -1.0f / 3.0f);
+    p = __builtin_fmaf(p, x2, 1.0f);
+    return __builtin_fabsf(x) < 0.25f ? x * p : big;
+}
 
 // ---- split-bf16 ("x6") arithmetic: an f32 value as three bf16 pieces a = p0 + p1 + p2 (8 significand bits each, so
 // the split is exact); products of two split operands keep the six piece products with i + j <= 2 and accumulate them
@@ -168,7 +180,11 @@ struct SplitF16x3 {          // UAV_ARITH_FP16X3 (the default): two fp16 pieces,
         hb = mma(w(0), h(1), hb);
         ha = mma(w(0), h(0), ha);
     }
-    template <class V> __device__ __forceinline__ static V sum(V acc, V acl) { return acc + acl * H3_LO; }
+    // acc + 2^-11 acl as one fma, per element (only lstm.hip's kernels combine their accumulators through the policy)
+    __device__ __forceinline__ static float sum(float acc, float acl) { return __builtin_fmaf(acl, H3_LO, acc); }
+    __device__ __forceinline__ static f32x4 sum(f32x4 acc, f32x4 acl) {
+        return __builtin_elementwise_fma(acl, f32x4{H3_LO, H3_LO, H3_LO, H3_LO}, acc);
+    }
     // backward, one partial tile: the same three products over two accumulators
     template <class W>
     __device__ __forceinline__ static void tile_slab(f32x4& a0, f32x4& a1, W w, const vec (&b)[NP]) {
@@ -176,7 +192,7 @@ struct SplitF16x3 {          // UAV_ARITH_FP16X3 (the default): two fp16 pieces,
         a0 = mma(w(0), b[0], a0);
         a1 = mma(w(0), b[1], a1);
     }
-    __device__ __forceinline__ static f32x4 tile_sum(f32x4 a0, f32x4 a1) { return a0 + a1 * H3_LO; }
+    __device__ __forceinline__ static f32x4 tile_sum(f32x4 a0, f32x4 a1) { return sum(a0, a1); }
 };
 
 struct SplitBf16x6 {         // UAV_ARITH_BF16X6: three bf16 pieces, six products, f32's exponent range

@@ -36,9 +36,9 @@
 constexpr int MT = 16;      // env rows per workgroup (MFMA M)
 constexpr int TC = 32;      // time steps staged per chunk
 
-#define sigmoidf_ fast_sigmoid
-#define tanhf_ fast_tanh
-
+// Every tanh of this file is common.h's fast_tanh_fma, and every a b + c that is ONE rounding is written as an fma: the file is built
+// without contraction, like the rest of the library, so the bits are the source's ("Contraction").  Where two
+// instantiations round a quantity differently (the compiler once chose, and the recorded bits hold both), the site says so.
 template <int H>
 struct FwdGeom {
     static constexpr int NW = H / 16;          // waves per workgroup
@@ -166,11 +166,11 @@ __global__ __launch_bounds__(H * 4) void lstm_fwd_kernel(
             for (int r = 0; r < 4; ++r) {
                 const int e = 4 * kq + r;
                 const int n = n0 + e;
-                const float gi = sigmoidf_(acc[0][r]), gf = sigmoidf_(acc[1][r]);
-                const float gg = tanhf_(acc[2][r]), go = sigmoidf_(acc[3][r]);
+                const float gi = fast_sigmoid(acc[0][r]), gf = fast_sigmoid(acc[1][r]);
+                const float gg = fast_tanh_fma(acc[2][r]), go = fast_sigmoid(acc[3][r]);
                 const float cp = c_reg[r];
                 const float c = gf * cp + gi * gg;
-                const float h = go * tanhf_(c);
+                const float h = go * fast_tanh_fma(c);
                 const float kn = kbuf[(tt + 1) * MT + e];     // keep of step t+1 (1 past the end)
                 if (n < N) {
                     const size_t row = (size_t)n * T + t;
@@ -422,7 +422,7 @@ __device__ __forceinline__ void lstm_fwd_split(
             for (int q = 0; q < 4; ++q) {
                 const float4 v = FUSE_X ? *reinterpret_cast<const float4*>(bl + q * H + uo)
                                         : *reinterpret_cast<const float4*>(stash + row * (6 * H) + q * H + uo);
-                acc[q] = P::sum(acc[q], acl[q]) * kcur + f32x4{v.x, v.y, v.z, v.w};
+                acc[q] = __builtin_elementwise_fma(P::sum(acc[q], acl[q]), f32x4{kcur, kcur, kcur, kcur}, f32x4{v.x, v.y, v.z, v.w});
             }
             if (FUSE_X) {       // K = I <= 8 input projection: two exact-f32 k-steps
                 const float2 ax = *reinterpret_cast<const float2*>(&xbuf[((xb * TC + tt) * MT + j) * 8 + 2 * kq]);
@@ -437,14 +437,14 @@ __device__ __forceinline__ void lstm_fwd_split(
             const float kn = kbuf[(xb * TC + tt) * MT + j];              // keep of step t+1 (1 past the end)
             // the stash stores are issued as soon as their values exist, so the write stream starts under the rest of
             // the gate math instead of in one burst before the barrier.
-            // c = f c_prev + i g fuses one of its two products into an fma.  Which one was left to -ffp-contract=fast, and
-            // the choice (it changes the last bit of c, and so the whole sequence) followed unrelated code around it; it is
-            // spelled out as the compiler had made it (forward: by H; backward: f c_prev), so the bits are the source's.
+            // c = f c_prev + i g fuses one of its two products into an fma.  Which one was once left to the compiler, and the
+            // choice (it changes the last bit of c, and so the whole sequence) followed unrelated code around it; it is spelled
+            // out as the compiler had made it (forward: by H; backward: f c_prev), like every other fma of this file.
             float gi[4], gf[4], gg[4], go[4], cp[4], hh[4], hm[4], cc[4];
             float* sp = stash + row * (6 * H) + uo;
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                gi[r] = sigmoidf_(acc[0][r]); gf[r] = sigmoidf_(acc[1][r]); gg[r] = tanhf_(acc[2][r]);
+                gi[r] = fast_sigmoid(acc[0][r]); gf[r] = fast_sigmoid(acc[1][r]); gg[r] = fast_tanh_fma(acc[2][r]);
                 cp[r] = c_reg[r];
                 cc[r] = H >= 128 ? __builtin_fmaf(gi[r], gg[r], gf[r] * cp[r])
                                  : __builtin_fmaf(gf[r], cp[r], gi[r] * gg[r]);
@@ -457,8 +457,8 @@ __device__ __forceinline__ void lstm_fwd_split(
             }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                go[r] = sigmoidf_(acc[3][r]);
-                hh[r] = go[r] * tanhf_(cc[r]);
+                go[r] = fast_sigmoid(acc[3][r]);
+                hh[r] = go[r] * fast_tanh_fma(cc[r]);
                 hm[r] = hh[r] * kn;
                 c_reg[r] = (t == T - 1) ? cc[r] : cc[r] * kn;            // cn is the unmasked final cell state
             }
@@ -602,12 +602,12 @@ __global__ __launch_bounds__(H * 4) void lstm_bwd_kernel(
                 const float gi = pf[r][0], gf = pf[r][1], gg = pf[r][2], go = pf[r][3], cp = pf[r][4];
                 const float dyv = dheads ? dyacc[r] : pdy[r];
                 const float dh = dyv + dh_rec[r];
-                const float c = gf * cp + gi * gg;
-                const float tch = tanhf_(c);
-                const float dc = dh * go * (1.0f - tch * tch) + dc_next[r];
+                const float c = gf * cp + gi * gg;              // both products rounded, unlike the split kernels' c
+                const float tch = fast_tanh_fma(c);
+                const float dc = __builtin_fmaf(dh * go, __builtin_fmaf(-tch, tch, 1.0f), dc_next[r]);
                 const float dgi = dc * gg * gi * (1.0f - gi);
                 const float dgf = dc * cp * gf * (1.0f - gf);
-                const float dgg = dc * gi * (1.0f - gg * gg);
+                const float dgg = dc * gi * __builtin_fmaf(-gg, gg, 1.0f);
                 const float dgo = dh * tch * go * (1.0f - go);
                 const float kp = kbuf[tt * MT + e];            // keep[t]: the incoming state was masked by it
                 dc_next[r] = dc * gf * kp;
@@ -822,11 +822,11 @@ __device__ __forceinline__ void lstm_bwd_split(
         for (int r = 0; r < 4; ++r) {
             const float dh = dyacc[r] + dh_rec[r];
             const float c = __builtin_fmaf(gf[r], cp[r], gi[r] * gg[r]);    // the fused product: comment at lstm_fwd_split
-            const float tch = tanhf_(c);
-            const float dc = dh * go[r] * (1.0f - tch * tch) + dc_next[r];
+            const float tch = fast_tanh_fma(c);
+            const float dc = __builtin_fmaf(dh * go[r], __builtin_fmaf(-tch, tch, 1.0f), dc_next[r]);
             dg[0][r] = dc * gg[r] * gi[r] * (1.0f - gi[r]);
             dg[1][r] = dc * cp[r] * gf[r] * (1.0f - gf[r]);
-            dg[2][r] = dc * gi[r] * (1.0f - gg[r] * gg[r]);
+            dg[2][r] = dc * gi[r] * __builtin_fmaf(-gg[r], gg[r], 1.0f);
             dg[3][r] = dh * tch * go[r] * (1.0f - go[r]);
             dc_next[r] = dc * gf[r] * kp;
         }

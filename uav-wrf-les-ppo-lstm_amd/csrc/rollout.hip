@@ -30,9 +30,7 @@ constexpr int RMT = 16;
 // phase timing of wave 0: cycles summed over the rollout by workgroup 0 (phase_prof.h)
 PROF_TABLE(g_roll_prof, [8], uav_roll_prof_read)
 
-#define r_sigmoid fast_sigmoid
-#define r_tanh fast_tanh
-
+// (the activations are common.h's plain fast_sigmoid / fast_tanh: the update's sequence kernels use fast_tanh_fma)
 
 // LDS geometry of the split-fp16 rollout (dynamic part; the env role's small arrays are static)
 template <int H>
@@ -307,7 +305,7 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         float gi[4], gf[4], gg[4], cc[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            gi[r] = r_sigmoid(acc[0][r]); gf[r] = r_sigmoid(acc[1][r]); gg[r] = r_tanh(acc[2][r]);
+            gi[r] = fast_sigmoid(acc[0][r]); gf[r] = fast_sigmoid(acc[1][r]); gg[r] = fast_tanh(acc[2][r]);
             cc[r] = gf[r] * c_reg[r] + gi[r] * gg[r];
         }
         if (st) {
@@ -319,8 +317,8 @@ __global__ __launch_bounds__(H * 4) void rollout_lstm_kernel(EnvParams P_arg, En
         float go[4], hh[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            go[r] = r_sigmoid(acc[3][r]);
-            hh[r] = go[r] * r_tanh(cc[r]);
+            go[r] = fast_sigmoid(acc[3][r]);
+            hh[r] = go[r] * fast_tanh(cc[r]);
             if (!value_only && on) c_reg[r] = cc[r];
         }
         if (on) put_h(hh);

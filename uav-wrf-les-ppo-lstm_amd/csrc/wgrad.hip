@@ -206,6 +206,17 @@ __device__ __forceinline__ void split8(const float (&v)[8], typename P::vec (&p)
         for (int k = 0; k < P::NP; ++k) p[k][i] = q[k];
     }
 }
+// ... of a row of 8 products a[i] b[i] (P::split_prod: the residual comes from the unrounded product)
+template <class P>
+__device__ __forceinline__ void split8_prod(const float (&a)[8], const float (&b)[8], typename P::vec (&p)[P::NP]) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        typename P::piece q[P::NP];
+        P::split_prod(a[i], b[i], q);
+#pragma unroll
+        for (int k = 0; k < P::NP; ++k) p[k][i] = q[k];
+    }
+}
 
 // ---- the two arithmetics of the split kernel.  Not common.h's SplitBf16x6 / SplitF16x3: the fp16 split here keeps its
 // residual unscaled and one accumulator per tile, and the products go in another order.  A policy fixes the pieces, the
@@ -219,6 +230,13 @@ struct WgBf16x6 {            // UAV_ARITH_BF16X6: three bf16 pieces, six product
     // the loads go in bursts: B after commit_b, A behind each split
     static constexpr bool LOADS_BETWEEN_TILES = false;
     __device__ __forceinline__ static void split(float a, piece (&p)[NP]) { split3(a, p[0], p[1], p[2]); }
+    // the pieces of a b: the first is that of the rounded product, the residual is taken from the unrounded one (one fma)
+    __device__ __forceinline__ static void split_prod(float a, float b, piece (&p)[NP]) {
+        p[0] = (__bf16)(a * b);
+        const float r1 = __builtin_fmaf(a, b, -(float)p[0]);
+        p[1] = (__bf16)r1;
+        p[2] = (__bf16)(r1 - (float)p[1]);
+    }
     __device__ __forceinline__ static unsigned short bits(piece v) { return bf_bits(v); }
     __device__ __forceinline__ static void mac(f32x4& d, const vec (&a)[NP], const vec (&b)[NP]) { mac6(d, a, b); }
     template <int NT_>
@@ -250,6 +268,11 @@ struct WgF16x3 {             // UAV_ARITH_FP16X3 (the default)
     __device__ __forceinline__ static void split(float a, piece (&p)[NP]) {
         p[0] = (_Float16)a;
         p[1] = (_Float16)(a - (float)p[0]);
+    }
+    // the pieces of a b: the main piece is that of the rounded product, the residual is taken from the unrounded one (one fma)
+    __device__ __forceinline__ static void split_prod(float a, float b, piece (&p)[NP]) {
+        p[0] = (_Float16)(a * b);
+        p[1] = (_Float16)__builtin_fmaf(a, b, -(float)p[0]);
     }
     __device__ __forceinline__ static unsigned short bits(piece v) { return h_bits(v); }
     // three products into one accumulator (unscaled residuals), smallest first
@@ -444,16 +467,17 @@ __device__ __forceinline__ void lstm_wgrad_split(
         unsigned short* bp = sm16 + buf * BUF;
         unsigned short* yp = bp + NP * BPL;
         unsigned short* dp = yp + 3 * YPL;
-        float hp[8], yy[8];
+        float hp[8], hk[8], yy[8];              // h_prev = hp[i] hk[i]: the row's value times its keep and column scale
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const float kld = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, kv), i));
             const float kpi = keep ? kld : 1.f;
-            hp[i] = ((i == i_start) ? hz : v[i]) * (kpi * P::BSCALE);
+            hp[i] = (i == i_start) ? hz : v[i];
+            hk[i] = kpi * P::BSCALE;
             yy[i] = HEADS ? v[i + 1 < NV ? i + 1 : 0] : 0.f;
         }
         vec hq[NP];
-        split8<P>(hp, hq);
+        split8_prod<P>(hp, hk, hq);
 #pragma unroll
         for (int p = 0; p < NP; ++p) *reinterpret_cast<vec*>(bp + p * BPL + c * KP + 8 * rg) = hq[p];
         if (HEADS) {
@@ -466,7 +490,7 @@ __device__ __forceinline__ void lstm_wgrad_split(
         for (int k = 0; k < XV; ++k) {
             const int idx = tid + k * NT, q = idx >> 4, f = idx & 15;
             typename P::piece xq[NP];
-            P::split(((f < I) ? xv[k] : (f == 6 ? 1.f : 0.f)) * P::XSCALE, xq);       // column 6 = ones -> db
+            P::split_prod((f < I) ? xv[k] : (f == 6 ? 1.f : 0.f), P::XSCALE, xq);     // column 6 = ones -> db
             unsigned short* d = bp + (H + f) * KP + q;
 #pragma unroll
             for (int p = 0; p < NP; ++p) d[p * BPL] = P::bits(xq[p]);

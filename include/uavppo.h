@@ -890,6 +890,58 @@ int uav_greedy_tail(uav_ctx* ctx, void* env_state, int n_env, const uav_env_cfg*
                     float* cur_obs, uint8_t* active, int32_t* act, float* obs, float* pos, uint8_t* flags, int32_t* nan_count,
                     const uav_stop_rule* rule /*host*/, float* stop_win, int32_t* stop_cnt, float* rule_val, uav_stream stream);
 
+/* ---- In-training greedy evaluation (csrc/eval_track.hip; uavppo/eval_track.py states each in numpy): the bookkeeping of
+ * evaluate_with_lstm.py's _Episodes on the device, with no host read.
+ *
+ * uav_greedy_reduce: one chunk of k greedy records of n envs, as the fused greedy-episode entry points (with or without the stop
+ * rule) and the per-step greedy tail write them -- flags u8 [n][k], obs f32 [n][k][D], pos f32 [n][k][2] -- after t0 earlier steps.  In/out per env: ep_steps i32 [n],
+ * ep_state u8 [n] (bit0 ended, bit1 ended by the stop rule), ep_pos f64 [n][2]; all zeros start an evaluation.  An env that comes in
+ * ended is left alone to the bit.  Otherwise its episode ends at the first record i with flags bit0 (done) or bit3 (rule fired); a
+ * record with bit2 (not stepped) is never an end and its obs / pos are never read.  On an end ep_steps = t0 + i + 1, ep_state bit0
+ * is set and bit1 iff the record has bit3, and ep_pos = f64(obs[i][0:2]) * 500.0 where bit0 is set (the terminal observation), else
+ * f64(pos[i]).  Where nothing ends it ep_pos = f64(pos[k-1]) (left as it was if that record has bit2) and the env stays running:
+ * the position an episode cut off by the step limit stands at.  Calls over the pieces of a chunk leave what one call leaves, bit
+ * for bit.  Refused with a reason: a NULL argument, n or k below 1, D below 2, t0 negative, n * k * D of 2^31 or more.
+ *
+ * uav_greedy_summary: after the last chunk.  src f64 [n][2]: the sources.  Per env steps = ended ? ep_steps : limit, deviation =
+ * sqrt(dx * dx + dy * dy) in f64 with dx = ep_pos - src, success = deviation <= success_distance (what _Episodes.metrics computes);
+ * the per-env outputs deviation f64 [n], steps i32 [n], success u8 [n] may each be NULL.  sums f64 [UAV_EVAL_SUM_N] is always written,
+ * in one fixed order of summation (eval_track.summarise): thread j of one block of 256 adds the envs j, j + 256, ... in turn, then the
+ * block tree.  nan_count i32 [1] (device) or NULL fills sums[7].  A NaN position gives a NaN deviation, success 0, and NaN in the
+ * sums it enters: defined, not an error.  Refused: a NULL required argument, n or limit below 1, a NaN success_distance.
+ *
+ * uav_keep_best: state f64 [UAV_BEST_N] (device; all zeros = fresh), sums = the (all-reduced) row of uav_greedy_summary.  A row
+ * holding a NaN, with sums[7] > 0 or without episodes is skipped and counted.  Otherwise it is better iff it is the first valid
+ * row, or has strictly more successes, or as many and a strictly smaller step sum (a tie keeps the earlier model); then
+ * best[0 .. n_params) = cand[..] and the state takes the row and `iteration`.  state[UAV_BEST_TOOK] = 1 if this call copied, else 0.
+ * Two launches: the decision by one thread, then the copy under its flag, so no block of the copy sees a half-made decision; a call
+ * that does not improve leaves every bit of `best`.  Refused: a NULL argument, n_params below 1, cand == best.
+ * Added without a change of UAV_ABI_VERSION (symbols only). */
+#define UAV_EVAL_SUM_N 8
+#define UAV_EVAL_SUM_EPISODES 0
+#define UAV_EVAL_SUM_SUCCESSES 1
+#define UAV_EVAL_SUM_STEPS 2
+#define UAV_EVAL_SUM_DEV 3
+#define UAV_EVAL_SUM_DEV_SQ 4
+#define UAV_EVAL_SUM_DEV_SUCCESS 5
+#define UAV_EVAL_SUM_CUT_OFF 6
+#define UAV_EVAL_SUM_NAN 7
+#define UAV_BEST_N 7
+#define UAV_BEST_SUCCESSES 0
+#define UAV_BEST_STEPS 1
+#define UAV_BEST_ITERATION 2
+#define UAV_BEST_SEEN 3
+#define UAV_BEST_IMPROVED 4
+#define UAV_BEST_SKIPPED 5
+#define UAV_BEST_TOOK 6
+int uav_greedy_reduce(uav_ctx* ctx, const uint8_t* flags, const float* obs, const float* pos, int n, int k, int D, int t0,
+                      int32_t* ep_steps, uint8_t* ep_state, double* ep_pos, uav_stream stream);
+int uav_greedy_summary(uav_ctx* ctx, const int32_t* ep_steps, const uint8_t* ep_state, const double* ep_pos, const double* src, int n,
+                       int limit, double success_distance, const int32_t* nan_count, double* deviation, int32_t* steps,
+                       uint8_t* success, double* sums, uav_stream stream);
+int uav_keep_best(uav_ctx* ctx, double* state, const double* sums, int iteration, const float* cand, float* best, int64_t n_params,
+                  uav_stream stream);
+
 /* ---- K9: the iteration's exchanges over RCCL / xGMI (SURVEY 8b `uav_allreduce`, 8e).  One process per GPU, one communicator per
  * handle; RCCL is bound at run time (dlopen librccl.so.1 -- inside a PyTorch process the copy torch already loaded; $UAV_RCCL_LIB
  * overrides), so the library itself has no link-time dependency on it.  A host that is not PyTorch uses these instead of

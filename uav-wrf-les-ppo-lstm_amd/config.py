@@ -71,6 +71,11 @@ DESIRED_KL = None        # "adaptive": the rate is divided by LR_FACTOR after an
 LR_FACTOR = 1.5          # ... the factor of one such change
 LR_MIN = 1e-6            # ... the lowest rate it reaches
 LR_MAX = 1e-2            # ... and the highest; LEARNING_RATE starts inside [LR_MIN, LR_MAX]
+EVAL_EVERY = None        # a number K: every K iterations one greedy episode on each of EVAL_ENVS fixed evaluation envs, on the device (eval_curve.csv, best_model.pth)
+EVAL_ENVS = 256          # ... the evaluation envs per rank (their own env: the default radius, never touched by the curriculum)
+EVAL_SEED = 4321         # ... and their seed; every evaluation runs the same episodes
+EVAL_MAX_STEPS = None    # ... the step limit of an evaluation episode (None: the env's own)
+KEEP_BEST = True         # ... keep the parameters of the best evaluation so far (most successes, then fewest steps) as best_model.pth
 GAE_MODE = "reference_exact"   # or "standard" (PPOV1.0/ppo0.0.py:337-350)
 SEED = 1234
 BC_EPOCHS = 10           # behaviour cloning (train_bc.py): passes over the expert set ...

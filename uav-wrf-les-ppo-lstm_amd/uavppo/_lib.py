@@ -139,6 +139,9 @@ SIGNATURES = {
                                        C.POINTER(StopRule), P, P, P, P]),
     "uav_greedy_tail": (I32, [P, P, I32, C.POINTER(EnvCfg), P, I64, I32, P, P, I32, I32, I32, P, P, P, P, P, P, P, P,
                               C.POINTER(StopRule), P, P, P, P]),
+    "uav_greedy_reduce": (I32, [P, P, P, P, I32, I32, I32, I32, P, P, P, P]),
+    "uav_greedy_summary": (I32, [P, P, P, P, P, I32, I32, F64, P, P, P, P, P, P]),
+    "uav_keep_best": (I32, [P, P, P, I32, P, P, I64, P]),
     "uav_stop_stability": (I32, [P, I32, C.POINTER(StopRule), P, P, I64, P, P, P, P, P, P]),
     "uav_peak_stop_param_count": (SZ, [I32]),
     "uav_peak_stop_scan": (I32, [P, P, I32, I32, P, I64, I64, I32, I32, P, P, P, F32, P, P, P, P]),

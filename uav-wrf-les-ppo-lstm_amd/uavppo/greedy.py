@@ -184,6 +184,22 @@ class GreedyRun:
             self.seg_t = 0                                   # the step of the current segment the next layers_step() runs
             self._begin_segment([(self.h[l], self.c[l]) for l in range(L)])
 
+    def restart(self):
+        """Start over for another run of episodes on the same env (reset by the caller) and the same policy object, whose
+        parameters may have changed: h, c, active, nan_count, the rule's window and the tail's segment state as __init__ leaves
+        them, in place -- nothing is reallocated and the host reads nothing."""
+        if self.h is not None:
+            self.h.zero_()
+            self.c.zero_()
+        self.active.fill_(1)
+        self.nan_count.zero_()
+        if self.stop_win is not None:
+            self.stop_win.zero_()
+            self.stop_cnt.zero_()
+        if self.tail and self.steppers is not None:
+            self.seg_t = 0
+            self._begin_segment([(self.h[l], self.c[l]) for l in range(self.core.num_layers)])
+
     def _begin_segment(self, states):
         v = self.core.views
         for l, (sp, (h, c)) in enumerate(zip(self.steppers, states)):

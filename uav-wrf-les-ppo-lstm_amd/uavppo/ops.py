@@ -1344,6 +1344,48 @@ def greedy_tail(env_state, cfg, y, w_head, b_head, t, cur_obs, active, recs, nan
                                 _p(nan_count, I32, (1,), "nan_count"), *tail, _stream()), "uav_greedy_tail")
 
 
+EVAL_SUM_N = 8             # UAV_EVAL_SUM_N
+# the eight sums of uav_greedy_summary, include/uavppo.h UAV_EVAL_SUM_*
+EVAL_SUM_NAMES = ("episodes", "successes", "steps", "dev", "dev_sq", "dev_success", "cut_off", "nan")
+BEST_N = 7                 # UAV_BEST_N
+# the seven slots of uav_keep_best's state, include/uavppo.h UAV_BEST_*
+BEST_NAMES = ("successes", "steps", "iteration", "seen", "improved", "skipped", "took")
+
+
+def greedy_reduce(recs, t0, ep_steps, ep_state, ep_pos):
+    """E1 (uav_greedy_reduce): the records of one chunk (greedy_recs: flags [N, k], obs [N, k, D], pos [N, k, 2]) after t0 earlier
+    steps -> ep_steps i32 [N], ep_state u8 [N] (bit0 ended, bit1 by the rule), ep_pos f64 [N, 2], in place (eval_track.reduce_chunk).
+    No host sync."""
+    N, k, D = recs["obs"].shape
+    check(lib().uav_greedy_reduce(_h(ep_pos), _p(recs["flags"], U8, (N, k), "flags"), _p(recs["obs"], F32, (N, k, D), "obs"),
+                                  _p(recs["pos"], F32, (N, k, 2), "pos"), N, k, D, int(t0), _p(ep_steps, I32, (N,), "ep_steps"),
+                                  _p(ep_state, U8, (N,), "ep_state"), _p(ep_pos, F64, (N, 2), "ep_pos"), _stream()), "uav_greedy_reduce")
+
+
+def greedy_summary(ep_steps, ep_state, ep_pos, src, limit, success_distance, sums, nan_count=None, deviation=None, steps=None,
+                   success=None):
+    """E2 (uav_greedy_summary): sums f64 [EVAL_SUM_N] of an evaluation whose episodes stand as ep_* say, against the sources src
+    f64 [N, 2] (eval_track.summarise, its order of summation); optional per-env outputs deviation f64 [N], steps i32 [N], success
+    u8 [N]; nan_count i32 [1] or None -> sums[7].  No host sync."""
+    N = ep_steps.numel()
+    check(lib().uav_greedy_summary(_h(sums), _p(ep_steps, I32, (N,), "ep_steps"), _p(ep_state, U8, (N,), "ep_state"),
+                                   _p(ep_pos, F64, (N, 2), "ep_pos"), _p(src, F64, (N, 2), "src"), N, int(limit), float(success_distance),
+                                   _p(nan_count, I32, (1,), "nan_count"), _p(deviation, F64, (N,), "deviation"),
+                                   _p(steps, I32, (N,), "steps"), _p(success, U8, (N,), "success"),
+                                   _p(sums, F64, (EVAL_SUM_N,), "sums"), _stream()), "uav_greedy_summary")
+    return sums
+
+
+def keep_best(state, sums, iteration, cand, best):
+    """E3 (uav_keep_best): the decision of eval_track.better_rule on state f64 [BEST_N] (zeros = fresh) from the all-reduced sums,
+    and best[:] = cand[:] under it (f32, the same number of elements).  Two launches, no host sync."""
+    n = cand.numel()
+    if best.numel() != n:
+        raise RuntimeError(f"keep_best: best has {best.numel()} elements, cand has {n}")
+    check(lib().uav_keep_best(_h(state), _p(state, F64, (BEST_N,), "state"), _p(sums, F64, (EVAL_SUM_N,), "sums"), int(iteration),
+                              _p(cand, F32, name="cand"), _p(best, F32, name="best"), n, _stream()), "uav_keep_best")
+
+
 def stop_stability(rule, pos, obs2, stop_win, stop_cnt, active=None, stop=None, value=None):
     """One step of the stop rule for envs stepped by other means (uav_stop_stability): pos f32 [N, 2] (agent_pos after the
     move), obs2 f32 [N] or a column view such as obs[:, 2] (any element stride), active u8 [N] or None (all).  Updates

@@ -18,6 +18,7 @@ from . import ops
 from .curriculum_link import CurriculumLink
 from .dist_utils import allreduce_adv_stats, allreduce_grad, allreduce_sum, collectives_on, env_shard
 from .policy import LSTMActorCritic, MLPActorCritic
+from .eval_track import EvalTracker, check_eval
 from .lr_control import LrController, check_lr_control, linear_value
 from .range_guard import RangeGuard
 from .obs_norm import ObsNormaliser, check_obs_norm
@@ -166,8 +167,16 @@ class VecPPOTrainer:
                  update_form="update_model", minibatch_rows=None, shuffle_envs=False, bptt_len=None, diagnostics=False,
                  target_kl=None, normalise_rewards=False, reward_clip=10.0, reward_norm_gamma=None, dgates_tile=None,
                  normalise_obs=False, obs_norm_eps=1e-4, obs_norm_channels=None, lr_schedule="constant", lr_final=None,
-                 ent_beta_final=None, schedule_iterations=None, desired_kl=None, lr_factor=1.5, lr_min=1e-6, lr_max=1e-2, **hp):
+                 ent_beta_final=None, schedule_iterations=None, desired_kl=None, lr_factor=1.5, lr_min=1e-6, lr_max=1e-2,
+                 eval_every=None, eval_envs=256, eval_seed=4321, eval_max_steps=None, eval_chunk=None, eval_radius=None, keep_best=True,
+                 **hp):
         self.hp = dict(DEFAULTS)
+        # eval_every: every so many iterations the policy runs one greedy episode on each of eval_envs envs of a separate, fixed
+        # evaluation env (seed eval_seed, eval_radius or the env's default radius, eval_max_steps or the env's step limit, eval_chunk
+        # steps per launch) and keep_best keeps the parameters of the best evaluation so far on the device, self.eval_tracker
+        # (uavppo/eval_track.py).  No host read, and nothing training computes changes by a bit.  None: the iteration issues exactly
+        # the launches it did without it.
+        self.eval = check_eval(eval_every, eval_envs, eval_seed, eval_max_steps, eval_chunk, eval_radius, keep_best)
         self.dgates_tile = dgates_tile       # gate gradients of the update in tile form: None = the rule of _request_dgates_tile, True / False = A/B
         self.hp.update(hp)
         # normalise_rewards: the GAE reads the reward scaled by a running estimate of the discounted return's standard deviation
@@ -285,6 +294,13 @@ class VecPPOTrainer:
         sc = self.schedule
         self.lr_control = (LrController(self.hp["lr"], sc["desired_kl"], sc["lr_factor"], sc["lr_min"], sc["lr_max"], device=d)
                            if self.lr_schedule == "adaptive" else None)
+        ev = self.eval
+        self.eval_tracker = None
+        if ev["eval_every"] is not None:
+            self.eval_tracker = EvalTracker(self.policy, self.kind, ev["eval_envs"], self.variant, self.trend_k, ev["eval_seed"],
+                                            self.bank, self.bank_sources, d, self.rank, self.world, ev["eval_max_steps"],
+                                            ev["eval_chunk"], keep_best=ev["keep_best"], eval_radius=ev["eval_radius"],
+                                            guard=self.guard, collectives=self._coll)
 
     def _alloc_policy_work(self, hidden, layers):
         """The recurrent state and the work arrays the update's kernels write their forward pass to."""
@@ -835,6 +851,12 @@ class VecPPOTrainer:
     def _after_update(self):
         """Between update() and update_curriculum() of an iteration (GAILTrainer: the discriminator steps)."""
 
+    def evaluate_if_due(self):
+        """The in-training greedy evaluation (eval_every), at the end of an iteration: after self.iteration was advanced, so the
+        evaluation tagged k sees the parameters after k updates.  The scripts' loops call it where train_iteration() does."""
+        if self.eval_tracker is not None and self.iteration % self.eval["eval_every"] == 0:
+            self.eval_tracker.run(self.iteration)
+
     def train_iteration(self):
         ev = self._iter_events.pop() if self._iter_events else None
         if ev is not None:
@@ -847,6 +869,7 @@ class VecPPOTrainer:
         self.update_curriculum()
         self.poll_param_range()
         self.iteration += 1
+        self.evaluate_if_due()
         return sums
 
     def losses(self):

@@ -942,6 +942,70 @@ int uav_greedy_summary(uav_ctx* ctx, const int32_t* ep_steps, const uint8_t* ep_
 int uav_keep_best(uav_ctx* ctx, double* state, const double* sums, int iteration, const float* cand, float* best, int64_t n_params,
                   uav_stream stream);
 
+/* ---- Source estimate from greedy-episode records (csrc/source_fit.hip; uavppo/source_fit.py states each in numpy).  The field is
+ * 100 exp(-d^2 / 2 sigma^2) + tke clipped to 0 .. 100 and a record carries conc / 100 (obs[2]) and tke / 9 (obs[3]) of the cell it
+ * was sampled in, so the plume term b is known per record and ln b is linear in (1, x, y, x^2 + y^2): a weighted least-squares fit
+ * with four parameters per env (weights b^2) gives the source, the width and the peak in closed form.  No host read anywhere.
+ *
+ * uav_source_moments: one chunk of k greedy records of n envs in uav_greedy_reduce's layout.  ended u8 [n] or NULL: an env with
+ * ended[i] != 0 is left alone to the bit (pass ep_state as it stands BEFORE the chunk's uav_greedy_reduce).  Otherwise records are
+ * taken in time order up to and including the first with flags bit0 or bit3; a bit2 record is never read and never used.  Per
+ * record the cell is x = min(max((int)pos_x, 0), 499), likewise y (a NaN counts as 0); b = 100 obs[2] - 9 obs[3] (use_tke) or
+ * 100 obs[2] - background, in f64; the record is used iff b > floor and obs[2] < 1.0f (not clipped), so never with a NaN.
+ * state f64 [n][UAV_SRC_STATE_N], zeros = fresh: {count, cx, cy, A (10: the upper triangle by rows), g (4), largest b, its x, its y}
+ * with (cx, cy) the cell of the env's first used record, fixed from then on, w = b * b, phi = (1, p, q, p * p + q * q),
+ * p = (x - cx) / 32, q = (y - cy) / 32, A += w phi phi^T formed as (w phi_i) phi_j, g += (w phi_i) ln b; of equal largest b the
+ * earliest record stays.  One wave per env: lane l adds the records i = l (mod 64) in increasing i from zero, the 64 partials are
+ * added by the tree of strides 32 .. 1, the state adds the total -- the statement's order, so the count, the centre, A and the
+ * largest sample are its bits and g differs by log's last bit only.
+ *
+ * uav_source_solve: one thread per env.  count < min_samples -> UAV_SRC_FEW.  S = A scaled by d_j = sqrt(A_jj), Cholesky by
+ * columns; a pivot (the diagonal before its square root) that is not finite or below min_pivot -> UAV_SRC_DEGENERATE (a straight
+ * track).  Solve, unscale to a0 .. a3; a3 >= 0 or a non-finite a -> UAV_SRC_NOT_A_PEAK.  Else UAV_SRC_FITTED with
+ * s2 = -1 / (2 a3), mu = c + 32 (a1, a2) s2, sigma = 32 sqrt(s2), peak = exp(a0 + (a1^2 + a2^2) s2 / 2), strength = 2 pi sigma^2 peak.
+ * est f64 [n][UAV_SRC_EST_N] = {mu_x, mu_y, sigma, peak, strength, largest sample's x, y, b}: the first five NaN unless fitted, all
+ * eight NaN for a count of 0.  status u8 [n].
+ *
+ * uav_source_summary: sums f64 [UAV_SRC_SUM_N] against the sources src f64 [n][2] in uav_greedy_summary's order of summation.
+ * err = sqrt(dx * dx + dy * dy) of a fitted env (a NaN source gives NaN); the relative errors of sigma and peak are 0 where the truth
+ * is not finite and positive.  loc_err f64 [n] or NULL takes err (NaN unless fitted).
+ *
+ * Refused with a reason: a NULL required argument, n or k below 1, D below 4 (3 without use_tke), n * k * D of 2^31 or more,
+ * min_samples below 4, a floor that is not finite or negative, a background or min_pivot that is not finite, min_pivot not
+ * positive, pos not 8-byte aligned, a NaN loc_tol.  Added without a change of UAV_ABI_VERSION (symbols only). */
+#define UAV_SRC_STATE_N 20
+#define UAV_SRC_EST_N 8
+#define UAV_SRC_FITTED 0
+#define UAV_SRC_FEW 1
+#define UAV_SRC_DEGENERATE 2
+#define UAV_SRC_NOT_A_PEAK 3
+#define UAV_SRC_SUM_N 12
+#define UAV_SRC_SUM_ENVS 0
+#define UAV_SRC_SUM_FITTED 1
+#define UAV_SRC_SUM_FEW 2
+#define UAV_SRC_SUM_DEGENERATE 3
+#define UAV_SRC_SUM_NOT_A_PEAK 4
+#define UAV_SRC_SUM_ERR 5
+#define UAV_SRC_SUM_ERR_SQ 6
+#define UAV_SRC_SUM_WITHIN 7
+#define UAV_SRC_SUM_SIGMA_REL 8
+#define UAV_SRC_SUM_PEAK_REL 9
+#define UAV_SRC_SUM_MAX_ERR 10
+#define UAV_SRC_SUM_MAX_ENVS 11
+typedef struct uav_source_fit_cfg {
+    int32_t use_tke;      /* 1: b = 100*obs[2] - 9*obs[3];  0: b = 100*obs[2] - background */
+    int32_t min_samples;  /* >= 4; default 5 */
+    double  background;   /* read when use_tke == 0 */
+    double  floor;        /* a record is used iff b > floor and obs[2] < 1.0f (not clipped); default 1.0 */
+    double  min_pivot;    /* smallest accepted pivot of the scaled Cholesky; default 1e-6 */
+} uav_source_fit_cfg;
+int uav_source_moments(uav_ctx* ctx, const uint8_t* flags, const float* obs, const float* pos, int n, int k, int D,
+                       const uav_source_fit_cfg* cfg /*host*/, const uint8_t* ended, double* state, uav_stream stream);
+int uav_source_solve(uav_ctx* ctx, const double* state, int n, const uav_source_fit_cfg* cfg /*host*/, double* est, uint8_t* status,
+                     uav_stream stream);
+int uav_source_summary(uav_ctx* ctx, const double* est, const uint8_t* status, const double* src, int n, double sigma_true,
+                       double peak_true, double loc_tol, double* loc_err, double* sums, uav_stream stream);
+
 /* ---- K9: the iteration's exchanges over RCCL / xGMI (SURVEY 8b `uav_allreduce`, 8e).  One process per GPU, one communicator per
  * handle; RCCL is bound at run time (dlopen librccl.so.1 -- inside a PyTorch process the copy torch already loaded; $UAV_RCCL_LIB
  * overrides), so the library itself has no link-time dependency on it.  A host that is not PyTorch uses these instead of

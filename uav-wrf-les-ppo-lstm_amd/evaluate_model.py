@@ -17,12 +17,16 @@ device function).  No CPU fallback: everything goes through uavppo.ops.
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
 from config import CONC_PEAK, CONC_REWARD_COEF
 from uavppo import ops
 from uavppo.greedy import GreedyRun, fused_refusal, policy_core, policy_route, stepwise_policy_probs  # noqa: F401  (fused_refusal: tests)
+from uavppo.source_fit import ESTIMATE_FILE, SourceFit, variant_truth, write_estimates
+from uavppo.source_fit import option as source_fit_option
 
 F32 = torch.float32
 CSV_COLUMNS = ("episode", "steps", "deviation", "success", "final_conc")
@@ -72,7 +76,8 @@ class ModelEvaluator:
         return ops.make_stop_rule(self.position_window, self.stability_threshold, CONC_REWARD_COEF, CONC_PEAK, self.conc_threshold)
 
     @torch.no_grad()
-    def run_evaluation(self, noise=None, max_steps=2000, fused=None, chunk=None, csv_path="evaluation_results.csv", tail=None):
+    def run_evaluation(self, noise=None, max_steps=2000, fused=None, chunk=None, csv_path="evaluation_results.csv", tail=None,
+                       source_fit=None):
         """One greedy episode per environment, all together, each until done, the stop rule, or `max_steps` (:52).
         noise: optional f64 [max_steps, N, 2] standard normals (parity tests).  fused: None = the fused kernels where
         fused_refusal allows, else step-wise; True = fused or a RuntimeError naming why not; False = step-wise.  tail: None = the
@@ -82,18 +87,28 @@ class ModelEvaluator:
         host visit of the tail route (default 250).  csv_path: where the reference's CSV goes (None: not written).
         Returns numpy arrays of length N: steps, deviations (f64), success (deviation < current_radius), final_conc (f32,
         (CONC_REWARD_COEF * obs[2]) * CONC_PEAK of the last step) and stopped_early (the rule fired on the last step).
-        A NaN logit raises RuntimeError("NaN in probs")."""
+        A NaN logit raises RuntimeError("NaN in probs").
+        source_fit: None (off), True or a dict of uavppo.source_fit.check_source_fit's keywords: where each episode's measurements
+        say the source is (uav_source_moments per chunk of records -- the stop rule's bit3 ends an episode for it as `done` does --
+        then uav_source_solve / uav_source_summary).  The result gains evaluate()'s source_* arrays and source_estimates.csv is
+        written beside csv_path; evaluation_results.csv stays byte for byte.  Fused and tail routes only (ValueError otherwise)."""
         kind, core = _policy_core_checked(self.model)
         env = self.env
+        fit_cfg = source_fit_option(source_fit)
         route = policy_route(self.model, env, fused, tail, "run_evaluation")
+        if route == "stepwise" and fit_cfg is not None:
+            raise ValueError("run_evaluation(source_fit=...): the estimator reads the records of the fused and tail routes; the "
+                             "step-wise route keeps none")
         if route == "stepwise" and chunk is not None:
             raise ValueError("run_evaluation(chunk=...): chunks belong to the fused path")
         env.reset()
         _, src, _, _ = env.peek()
+        fit = SourceFit(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
+        src_dev = src.to(torch.float64).clone() if fit is not None else None
         src = src.cpu().numpy()
         if route != "stepwise":
             steps, pos, obs2, stopped = self._episodes_fused(kind, core, noise, int(max_steps), int(chunk or 250),
-                                                             tail=route == "tail")
+                                                             tail=route == "tail", fit=fit)
         else:
             steps, pos, obs2, stopped = self._episodes_stepwise(kind, core, noise, int(max_steps))
         pos, obs2 = pos.cpu().numpy().astype(np.float32), obs2.cpu().numpy().astype(np.float32)
@@ -104,9 +119,14 @@ class ModelEvaluator:
                "stopped_early": stopped.cpu().numpy()}
         if csv_path is not None:
             write_results_csv(csv_path, out["steps"], out["deviations"], out["success"], out["final_conc"])
+        if fit is not None:
+            fit.finish(src_dev, *(variant_truth(env.variant) if env.bank is None else (float("nan"), float("nan"))))
+            out.update(fit.metrics())
+            if csv_path is not None:
+                write_estimates(os.path.join(os.path.dirname(csv_path) or ".", ESTIMATE_FILE), out)
         return out
 
-    def _episodes_fused(self, kind, core, noise, limit, chunk, want=None, tail=False):
+    def _episodes_fused(self, kind, core, noise, limit, chunk, want=None, tail=False, fit=None):
         """Per env: steps, final agent_pos (f32), obs[2] of the last step, stopped-by-the-rule -- reduced from the records of
         uav_greedy_episodes_stop, or with tail=True of GreedyRun's tail backend; the position of a step that ended its episode
         by `done` is then obs[:2] * 500 of the terminal observation rounded to f32, as _episodes_stepwise takes it (within an
@@ -127,6 +147,8 @@ class ModelEvaluator:
             k = min(chunk, limit - t0)
             rv = torch.empty(N, k, dtype=F32, device=dev) if want is not None else None
             recs = run.chunk(t0, k, noise, rule_val=rv)
+            if fit is not None:                                        # before this chunk's ends are taken
+                fit.chunk(recs, (~active).to(torch.uint8))
             if want is not None:
                 kept.append(dict(recs, rule_val=rv))
             end_c = (recs["flags"] & (DONE | STOPPED)) != 0            # an episode ends at its first such record

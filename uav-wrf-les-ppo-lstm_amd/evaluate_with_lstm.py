@@ -28,6 +28,8 @@ from config import EVALUATE_SIZE, SUCCESS_DISTANCE_THRESHOLD
 from uavppo import ops
 from uavppo.greedy import (GreedyRun, fused_refusal, policy_core, policy_route, stepwise_policy_probs,  # noqa: F401
                            tail_refusal)                                    # (fused_refusal, tail_refusal: tests, docs)
+from uavppo.source_fit import SourceFit, variant_truth
+from uavppo.source_fit import option as source_fit_option
 
 F32 = torch.float32
 
@@ -390,7 +392,7 @@ def _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, thresh
 @torch.no_grad()
 def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21=20, noise=None, max_steps=None,
              success_distance=SUCCESS_DISTANCE_THRESHOLD, fused=None, chunk=None, peak_stop_device=False, threshold_device=False,
-             tail=None):
+             tail=None, source_fit=None):
     """One greedy episode per environment of `env` (a uavppo VecMethaneEnv), all N together.
 
     policy_probs(obs [N, obs_dim]) -> probs or logits [N, 5] (argmax is taken), or a policy object: LSTMActorCritic,
@@ -415,7 +417,16 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     controller's predictor over the chunk's windows, and uav_threshold_rule, or the rule kernel with steps = 1 per env step on the
     step-wise path (windows and predictor on update steps only).  Same decisions and metrics as the default (the window mean is
     summed in np.mean's order, as the reference's, where the host replay uses torch's sum).  On return controller.current_threshold
-    holds the device's thresholds (f64 [N], NaN = None; an env that ended inside a fused chunk has that chunk's last)."""
+    holds the device's thresholds (f64 [N], NaN = None; an env that ended inside a fused chunk has that chunk's last).
+    source_fit: None (off), True or a dict of uavppo.source_fit.check_source_fit's keywords: where the episode's measurements say
+    the source is -- one uav_source_moments per chunk of records, uav_source_solve and uav_source_summary after the last.  The
+    metrics gain source_estimate f64 [N, 2], source_sigma, source_peak, source_strength, source_status u8 (ops.SRC_STATUS_NAMES),
+    source_error (NaN unless fitted) and source_max_sample f64 [N, 3] (x, y, b of the largest sample); nothing else changes.
+    Fused and tail routes only, and without controller / peak_stop (their hits are not in the records' flags): else ValueError."""
+    fit_cfg = source_fit_option(source_fit)
+    if fit_cfg is not None and (controller is not None or peak_stop is not None):
+        raise ValueError("evaluate(source_fit=...): not together with controller / peak_stop: their hits are not in the records' "
+                         "flags, so the estimator could not know where those episodes ended")
     pc, nan = policy_core(policy_probs), None
     if pc is None and fused:
         raise RuntimeError("evaluate(fused=True): a policy_probs function has no fused kernel; pass the policy object")
@@ -428,8 +439,11 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
         route = policy_route(policy_probs, env, fused, tail, "evaluate")
         if route != "stepwise":
             return _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
-                                   chunk, peak_stop_device, threshold_device, tail=route == "tail")
+                                   chunk, peak_stop_device, threshold_device, tail=route == "tail", fit_cfg=fit_cfg)
         policy_probs, nan = stepwise_policy_probs(kind, core, env)
+    if fit_cfg is not None:
+        raise ValueError("evaluate(source_fit=...): the estimator reads the records of the fused and tail routes; the step-wise "
+                         "route keeps none")
     src, ep, rules, limit = _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, threshold_device, max_steps)
     N, obs = env.num_envs, env.obs
     for t in range(1, limit + 1):
@@ -452,7 +466,7 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
 
 
 def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance, chunk,
-                    peak_stop_device=False, threshold_device=False, tail=False):
+                    peak_stop_device=False, threshold_device=False, tail=False, fit_cfg=None):
     """evaluate() on uav_greedy_episodes: `chunk` steps per launch (tail: on GreedyRun's tail backend, `chunk` steps per host visit); the metrics (and the stop controllers) are computed from
     the records by the step-wise loop's own _StopRules.step / _Episodes.end, so the same actions give the same arrays bit for
     bit.  An env the kernel has ended stays frozen (no auto-reset); an env a rule stopped goes into the next chunk inactive.
@@ -460,11 +474,14 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
     flags among them; otherwise -- every rule on the device, or none given -- a chunk is one _Episodes.end_chunk."""
     src, ep, rules, limit = _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, threshold_device, max_steps)
     run = GreedyRun(kind, core, env, tail=tail)
+    fit = SourceFit(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
     chunk = int(chunk or (50 if rules.any else 250))
     t0 = 0
     while t0 < limit:
         k = min(chunk, limit - t0)
         recs = run.chunk(t0, k, noise)
+        if fit is not None:                          # before this chunk's ends are taken: `active` is as the chunk found it
+            fit.chunk(recs, (~ep.active).to(torch.uint8))
         done_c = (recs["flags"] & 1) != 0
         conc = recs["obs"][:, :, 2]                  # the record is the terminal obs where done
         rules.scan(conc, ep.active, t0, rules.replay)   # `active` is the kernel's as the launch found it (the kernel clears it at `done`)
@@ -483,7 +500,12 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
         if not bool(ep.active.any()):
             break
     run.raise_on_nan()
-    return rules.finish(ep.metrics(src, limit, last_pos, success_distance))
+    out = rules.finish(ep.metrics(src, limit, last_pos, success_distance))
+    if fit is not None:
+        sigma_true, peak_true = variant_truth(env.variant) if env.bank is None else (float("nan"), float("nan"))
+        fit.finish(src.to(torch.float64).contiguous(), sigma_true, peak_true)
+        out.update(fit.metrics())
+    return out
 
 
 def load_lstm_policy(path, device="cuda"):

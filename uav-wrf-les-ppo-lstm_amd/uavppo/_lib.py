@@ -52,6 +52,12 @@ class GatherSpec(C.Structure):
 GATHER_MAX_SPECS = 12      # UAV_GATHER_MAX_SPECS
 
 
+class SourceFitCfg(C.Structure):
+    """struct uav_source_fit_cfg (include/uavppo.h)."""
+    _fields_ = [("use_tke", C.c_int32), ("min_samples", C.c_int32), ("background", C.c_double), ("floor", C.c_double),
+                ("min_pivot", C.c_double)]
+
+
 # name -> (restype, argtypes); mirrors include/uavppo.h one to one
 SIGNATURES = {
     "uav_abi_version": (I32, []),
@@ -142,6 +148,9 @@ SIGNATURES = {
     "uav_greedy_reduce": (I32, [P, P, P, P, I32, I32, I32, I32, P, P, P, P]),
     "uav_greedy_summary": (I32, [P, P, P, P, P, I32, I32, F64, P, P, P, P, P, P]),
     "uav_keep_best": (I32, [P, P, P, I32, P, P, I64, P]),
+    "uav_source_moments": (I32, [P, P, P, P, I32, I32, I32, C.POINTER(SourceFitCfg), P, P, P]),
+    "uav_source_solve": (I32, [P, P, I32, C.POINTER(SourceFitCfg), P, P, P]),
+    "uav_source_summary": (I32, [P, P, P, P, I32, F64, F64, F64, P, P, P]),
     "uav_stop_stability": (I32, [P, I32, C.POINTER(StopRule), P, P, I64, P, P, P, P, P, P]),
     "uav_peak_stop_param_count": (SZ, [I32]),
     "uav_peak_stop_scan": (I32, [P, P, I32, I32, P, I64, I64, I32, I32, P, P, P, F32, P, P, P, P]),

@@ -162,8 +162,12 @@ def better_rule(state, sums, iteration):
     return st
 
 
-def curve_row(iteration, sums, state):
-    """One eval_curve.csv row (CURVE_COLUMNS) from an evaluation's sums and the state behind it: plain python numbers."""
+def curve_row(iteration, sums, state, source=None):
+    """One eval_curve.csv row (CURVE_COLUMNS) from an evaluation's sums and the state behind it: plain python numbers.  source: the
+    twelve sums of uav_source_summary or None -> source_fit.SOURCE_COLUMNS behind them."""
+    if source is not None:
+        from .source_fit import source_row
+        return curve_row(iteration, sums, state) + source_row(source)
     S = np.asarray(sums, np.float64)
     n, ok = float(S[0]), float(S[1])
     mean = float(S[3] / n) if n > 0 else float("nan")
@@ -173,31 +177,37 @@ def curve_row(iteration, sums, state):
             float(S[5] / ok) if ok > 0 else float("nan"), int(S[6]) if S[6] == S[6] else 0, int(np.asarray(state)[6] == 1.0)]
 
 
+def curve_columns(source=False):
+    """eval_curve.csv's header: CURVE_COLUMNS, and source_fit.SOURCE_COLUMNS behind them where the source estimate is on."""
+    from .source_fit import SOURCE_COLUMNS
+    return CURVE_COLUMNS + (SOURCE_COLUMNS if source else [])
+
+
 def write_curve(path, rows):
     """eval_curve.csv: curve_row of every landed evaluation (EvalTracker.curve()), NaN written as "nan"."""
     import csv
     with open(path, "w", newline="") as f:
         w = csv.writer(f, lineterminator="\n")
-        w.writerow(CURVE_COLUMNS)
-        w.writerows(curve_row(r["iteration"], r["sums"], r["state"]) for r in rows)
+        w.writerow(curve_columns(any("source" in r for r in rows)))
+        w.writerows(curve_row(r["iteration"], r["sums"], r["state"], r.get("source")) for r in rows)
 
 
 class CurveLog:
     """eval_curve.csv of a training script, written as the rows land (one evaluation late, like the episode rows): add() after an
     iteration writes what has landed since, close() waits for the rest.  path None (ranks other than 0): nothing is written."""
 
-    def __init__(self, path):
+    def __init__(self, path, source=False):
         import csv
         self.n, self.f, self.w = 0, None, None
         if path:
             self.f = open(path, "w", newline="")
             self.w = csv.writer(self.f, lineterminator="\n")
-            self.w.writerow(CURVE_COLUMNS)
+            self.w.writerow(curve_columns(source))
 
     def add(self, tracker, wait=False):
         rows = tracker.curve(wait)
         if self.w is not None:
-            self.w.writerows(curve_row(r["iteration"], r["sums"], r["state"]) for r in rows[self.n:])
+            self.w.writerows(curve_row(r["iteration"], r["sums"], r["state"], r.get("source")) for r in rows[self.n:])
         self.n = len(rows)
 
     def close(self, tracker):
@@ -237,14 +247,19 @@ class EvalTracker:
     every rank keeps the same model.  guard: the trainer's RangeGuard or None: once its lagged mirror says the parameters left the
     fp16-split range (guard.arith != "fp16x3", never a fresh read) an LSTM's later evaluations run on the tail route; until then an
     out-of-range evaluation on the fused kernels shows as sums[7] > 0 and is skipped by the rule.  An MLP has no tail route: its
-    later evaluations are not run and are counted in `dropped`."""
+    later evaluations are not run and are counted in `dropped`.  source_fit: None, True or a dict of check_source_fit's keywords
+    (source_fit.py): one uav_source_moments per chunk in front of its uav_greedy_reduce, uav_source_solve and uav_source_summary
+    behind uav_greedy_summary; the twelve sums ride in the mirrored row and are all-reduced with the eight.  No host read is
+    added and the keep-best rule does not see them."""
 
     RING = 8            # evaluations whose rows may be on their way to the host at once
 
     def __init__(self, policy, kind, num_envs=256, variant="v2.0", trend_k=0, seed=4321, bank=None, bank_sources=None, device="cuda",
                  rank=0, world=1, max_steps=None, chunk=None, success_distance=40.0, keep_best=True, eval_radius=None, guard=None,
-                 collectives=False):
+                 collectives=False, source_fit=None):
+        from .source_fit import SUM_N as SRC_SUM_N, SourceFit, option, variant_truth
         c = check_eval(1, num_envs, seed, max_steps, chunk, eval_radius, keep_best)
+        fit_cfg = option(source_fit)
         self.policy, self.kind, self.guard, self.collectives = policy, kind, guard, bool(collectives)
         self.N, self.device = c["eval_envs"], torch.device(device)
         self.success_distance, self.keep = float(success_distance), c["keep_best"]
@@ -273,10 +288,17 @@ class EvalTracker:
         self.deviation = torch.zeros(N, dtype=torch.float64, device=d)
         self.steps = torch.zeros(N, dtype=torch.int32, device=d)
         self.success = torch.zeros(N, dtype=torch.uint8, device=d)
-        self.row = torch.zeros(SUM_N + BEST_N, dtype=torch.float64, device=d)      # [sums | state]: what the ring mirrors
-        self.sums, self.state = self.row[:SUM_N], self.row[SUM_N:]
+        # [sums | source sums | state]: what the ring mirrors; the sums stand together, so one all-reduce takes both
+        self.n_src = SRC_SUM_N if fit_cfg is not None else 0
+        self.row = torch.zeros(SUM_N + self.n_src + BEST_N, dtype=torch.float64, device=d)
+        self.sums, self.state = self.row[:SUM_N], self.row[SUM_N + self.n_src:]
+        self.fit = None          # source_fit.SourceFit: where the records say the source is, beside the bookkeeping
+        if fit_cfg is not None:
+            self.fit = SourceFit(N, d, **fit_cfg)
+            self.src_sums = self.row[SUM_N:SUM_N + self.n_src]
+            self.truth = variant_truth(variant) if bank is None else (float("nan"), float("nan"))
         self.best = torch.zeros_like(policy.flat)
-        self.ring = MirrorRing((SUM_N + BEST_N,), torch.float64, slots=self.RING)
+        self.ring = MirrorRing((self.row.numel(),), torch.float64, slots=self.RING)
         self._iters = []             # iteration of every slot in flight, oldest first
         self._rows = []              # landed rows
 
@@ -304,17 +326,23 @@ class EvalTracker:
         ops.env_peek(env.state, N, source=self.src)
         greedy.restart()
         self._blob.zero_()
+        if self.fit is not None:
+            self.fit.restart()
         t0 = 0
         while t0 < self.limit:
             k = min(self.chunk, self.limit - t0)
             recs = greedy.chunk(t0, k)
+            if self.fit is not None:
+                self.fit.chunk(recs, self.ep_state)          # ep_state as it stands before this chunk's reduce
             ops.greedy_reduce(recs, t0, self.ep_steps, self.ep_state, self.ep_pos)
             t0 += k
         ops.greedy_summary(self.ep_steps, self.ep_state, self.ep_pos, self.src, self.limit, self.success_distance, self.sums,
                            nan_count=greedy.nan_count, deviation=self.deviation, steps=self.steps, success=self.success)
+        if self.fit is not None:
+            self.fit.finish(self.src, *self.truth, sums=self.src_sums)
         if self.collectives:
             from .dist_utils import allreduce_sum
-            allreduce_sum(self.sums)
+            allreduce_sum(self.row[:SUM_N + self.n_src])
         if self.keep:
             ops.keep_best(self.state, self.sums, iteration, self.policy.flat, self.best)
         if len(self.ring) == self.ring.slots:
@@ -328,11 +356,15 @@ class EvalTracker:
         while ring.in_flight and ring.events[ring.in_flight[0]].query():
             k = ring.in_flight.pop(0)
             row = ring.host[k].numpy().copy()
-            self._rows.append({"iteration": self._iters.pop(0), "sums": row[:SUM_N], "state": row[SUM_N:]})
+            r = {"iteration": self._iters.pop(0), "sums": row[:SUM_N], "state": row[SUM_N + self.n_src:]}
+            if self.n_src:
+                r["source"] = row[SUM_N:SUM_N + self.n_src]
+            self._rows.append(r)
 
     def curve(self, wait=False):
         """The evaluations whose rows have landed, oldest first: dicts of iteration, sums f64 [8], state f64 [7] (after that
-        evaluation's decision; state[6] == 1: it became the best).  wait=True waits for every evaluation issued so far."""
+        evaluation's decision; state[6] == 1: it became the best), and with source_fit on source f64 [12], uav_source_summary's
+        sums.  wait=True waits for every evaluation issued so far."""
         if wait:
             for k in list(self.ring.in_flight):
                 self.ring.events[k].synchronize()

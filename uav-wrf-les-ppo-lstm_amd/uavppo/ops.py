@@ -1386,6 +1386,45 @@ def keep_best(state, sums, iteration, cand, best):
                               _p(cand, F32, name="cand"), _p(best, F32, name="best"), n, _stream()), "uav_keep_best")
 
 
+SRC_STATE_N, SRC_EST_N, SRC_SUM_N = 20, 8, 12      # UAV_SRC_STATE_N, UAV_SRC_EST_N, UAV_SRC_SUM_N
+# uav_source_solve's status codes and the twelve sums of uav_source_summary, include/uavppo.h UAV_SRC_*
+SRC_STATUS_NAMES = ("fitted", "few", "degenerate", "not_a_peak")
+SRC_SUM_NAMES = ("envs", "fitted", "few", "degenerate", "not_a_peak", "err", "err_sq", "within", "sigma_rel", "peak_rel", "max_err",
+                 "max_envs")
+
+
+def source_fit_cfg(use_tke=True, min_samples=5, background=0.0, floor=1.0, min_pivot=1e-6, **_):
+    """struct uav_source_fit_cfg from source_fit.check_source_fit's dict (keys that are not the struct's are ignored)."""
+    return _lib.SourceFitCfg(int(bool(use_tke)), int(min_samples), float(background), float(floor), float(min_pivot))
+
+
+def source_moments(recs, cfg, state, ended=None):
+    """S1 (uav_source_moments): the records of one chunk (greedy_recs: flags [N, k], obs [N, k, D], pos [N, k, 2]) added to state f64
+    [N, SRC_STATE_N] in place (source_fit.moments_chunk); ended u8 [N] or None: envs left alone.  No host sync."""
+    N, k, D = recs["obs"].shape
+    check(lib().uav_source_moments(_h(state), _p(recs["flags"], U8, (N, k), "flags"), _p(recs["obs"], F32, (N, k, D), "obs"),
+                                   _p(recs["pos"], F32, (N, k, 2), "pos"), N, k, D, C.byref(cfg), _p(ended, U8, (N,), "ended"),
+                                   _p(state, F64, (N, SRC_STATE_N), "state"), _stream()), "uav_source_moments")
+
+
+def source_solve(state, cfg, est, status):
+    """S2 (uav_source_solve): state f64 [N, SRC_STATE_N] -> est f64 [N, SRC_EST_N], status u8 [N] (source_fit.solve).  No host sync."""
+    N = state.shape[0]
+    check(lib().uav_source_solve(_h(state), _p(state, F64, (N, SRC_STATE_N), "state"), N, C.byref(cfg),
+                                 _p(est, F64, (N, SRC_EST_N), "est"), _p(status, U8, (N,), "status"), _stream()), "uav_source_solve")
+
+
+def source_summary(est, status, src, sigma_true, peak_true, loc_tol, sums, loc_err=None):
+    """S3 (uav_source_summary): sums f64 [SRC_SUM_N] of the estimates against the sources src f64 [N, 2] (source_fit.summarise, its
+    order of summation); loc_err f64 [N] or None takes each fitted env's error.  No host sync."""
+    N = status.numel()
+    check(lib().uav_source_summary(_h(sums), _p(est, F64, (N, SRC_EST_N), "est"), _p(status, U8, (N,), "status"),
+                                   _p(src, F64, (N, 2), "src"), N, float(sigma_true), float(peak_true), float(loc_tol),
+                                   _p(loc_err, F64, (N,), "loc_err"), _p(sums, F64, (SRC_SUM_N,), "sums"), _stream()),
+          "uav_source_summary")
+    return sums
+
+
 def stop_stability(rule, pos, obs2, stop_win, stop_cnt, active=None, stop=None, value=None):
     """One step of the stop rule for envs stepped by other means (uav_stop_stability): pos f32 [N, 2] (agent_pos after the
     move), obs2 f32 [N] or a column view such as obs[:, 2] (any element stride), active u8 [N] or None (all).  Updates

@@ -1006,6 +1006,46 @@ int uav_source_solve(uav_ctx* ctx, const double* state, int n, const uav_source_
 int uav_source_summary(uav_ctx* ctx, const double* est, const uint8_t* status, const double* src, int n, double sigma_true,
                        double peak_true, double loc_tol, double* loc_err, double* sums, uav_stream stream);
 
+/* ---- The estimator as a stop rule (csrc/source_fit.hip; uavppo/source_stop.py states it in numpy).  One chunk of k greedy records of
+ * n envs after t0 earlier steps, in uav_source_moments' layout and with its eligibility: records up to and including the env's
+ * first with bit0 or bit3, never one with bit2, none of an env with ended[e] != 0 or whose state already holds a hit step.  A
+ * record that is not eligible changes nothing.  After eligible record i, E_i is uav_source_solve's answer on the moments of the
+ * episode's used records 0 .. i.  The record is settled iff E_i and the previous eligible record's estimate are both FITTED and
+ * mu moved by at most settle_tol (squares compared in f64); run_i counts the settled eligible records that end at i.  The rule
+ * hits at i iff run_i >= patience, E_i is FITTED, |f64(pos_i) - mu_i|^2 <= near^2 (near may be +inf) and t0 + i + 1 >= min_steps;
+ * an env's first hit ends its episode.
+ * One wave per env; per block of 64 records (aligned to the chunk's start) the 15 contributions are scanned over the lanes with
+ * offsets 1, 2, 4, 8, 16, 32 (lane l adds lane l - o's old value), prefix = carry + scan, and the carry into the next block is the
+ * prefix at the block's last eligible lane: the statement's order, so the count, the centre and A are its bits.
+ * state f64 [n][UAV_SRC_STOP_STATE_N], zeros = fresh: {count, cx, cy, A (10), g (4) as in UAV_SRC_STATE_N's first 17 | the previous
+ * eligible record's mu_x, mu_y (0 unless fitted), its fitted bit, the run length, the hit's step t0 + i + 1 (0: none) | mu_x, mu_y,
+ * sigma, peak, strength at the hit}; it is written at the hit, else at the chunk's last eligible record, and holds no NaN.
+ * first_hit i32 [n]: the chunk's record of the hit, -1 without one.  mu_steps f64 [n][k][2] or NULL: NaN where the record is not
+ * eligible, lies behind the hit or is not FITTED; status_steps u8 [n][k] or NULL: 255 where not eligible or behind the hit.
+ * mark != 0: the env's flags are rewritten in place -- bit3 set on the hit record, bit2 set on every record behind it in the chunk
+ * (their obs / pos stay and are by contract never read) -- and active[e] = 0 where active is not NULL, so that
+ * uav_source_moments, uav_greedy_reduce and the next greedy chunk see the episode end there.  An idle env (ended, or hit earlier)
+ * is untouched to the bit and gets first_hit = -1.
+ * Refused with a reason: uav_source_moments' refusals; a NULL stop cfg, state or first_hit; settle_tol not finite or negative; near
+ * a NaN or negative; patience below 1; min_steps or t0 negative.  Added without a change of UAV_ABI_VERSION (a symbol only). */
+#define UAV_SRC_STOP_STATE_N 27
+#define UAV_SRC_STOP_PREV_X 17
+#define UAV_SRC_STOP_PREV_Y 18
+#define UAV_SRC_STOP_PREV_FITTED 19
+#define UAV_SRC_STOP_RUN 20
+#define UAV_SRC_STOP_HIT_STEP 21
+#define UAV_SRC_STOP_EST 22
+typedef struct uav_source_stop_cfg {
+    double  settle_tol;   /* cells; default 0.5 */
+    double  near;         /* cells, +inf: anywhere */
+    int32_t patience;     /* >= 1; default 3 */
+    int32_t min_steps;    /* >= 0 */
+} uav_source_stop_cfg;
+int uav_source_stop_scan(uav_ctx* ctx, uint8_t* flags /*in/out*/, const float* obs, const float* pos, int n, int k, int D, int t0,
+                         const uav_source_fit_cfg* cfg /*host*/, const uav_source_stop_cfg* stop /*host*/, const uint8_t* ended,
+                         uint8_t* active /*may be NULL*/, double* state, int32_t* first_hit, double* mu_steps, uint8_t* status_steps,
+                         int mark, uav_stream stream);
+
 /* ---- K9: the iteration's exchanges over RCCL / xGMI (SURVEY 8b `uav_allreduce`, 8e).  One process per GPU, one communicator per
  * handle; RCCL is bound at run time (dlopen librccl.so.1 -- inside a PyTorch process the copy torch already loaded; $UAV_RCCL_LIB
  * overrides), so the library itself has no link-time dependency on it.  A host that is not PyTorch uses these instead of

@@ -30,6 +30,8 @@ from uavppo.greedy import (GreedyRun, fused_refusal, policy_core, policy_route, 
                            tail_refusal)                                    # (fused_refusal, tail_refusal: tests, docs)
 from uavppo.source_fit import SourceFit, variant_truth
 from uavppo.source_fit import option as source_fit_option
+from uavppo.source_stop import SourceStop
+from uavppo.source_stop import option as source_stop_option
 
 F32 = torch.float32
 
@@ -392,7 +394,7 @@ def _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, thresh
 @torch.no_grad()
 def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21=20, noise=None, max_steps=None,
              success_distance=SUCCESS_DISTANCE_THRESHOLD, fused=None, chunk=None, peak_stop_device=False, threshold_device=False,
-             tail=None, source_fit=None):
+             tail=None, source_fit=None, source_stop=None):
     """One greedy episode per environment of `env` (a uavppo VecMethaneEnv), all N together.
 
     policy_probs(obs [N, obs_dim]) -> probs or logits [N, 5] (argmax is taken), or a policy object: LSTMActorCritic,
@@ -422,8 +424,20 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     the source is -- one uav_source_moments per chunk of records, uav_source_solve and uav_source_summary after the last.  The
     metrics gain source_estimate f64 [N, 2], source_sigma, source_peak, source_strength, source_status u8 (ops.SRC_STATUS_NAMES),
     source_error (NaN unless fitted) and source_max_sample f64 [N, 3] (x, y, b of the largest sample); nothing else changes.
-    Fused and tail routes only, and without controller / peak_stop (their hits are not in the records' flags): else ValueError."""
-    fit_cfg = source_fit_option(source_fit)
+    Fused and tail routes only, and without controller / peak_stop (their hits are not in the records' flags): else ValueError.
+    source_stop: None (off), True or a dict of uavppo.source_stop.check_source_stop's keywords: the estimator as the stop rule --
+    per chunk the greedy chunk, uav_source_stop_scan (which writes its hits into the records' flags), then uav_source_moments.  An
+    episode ends where the fit has settled and the UAV stands within `near` of it: stopped_early is true for those, steps,
+    deviations and success refer to where the UAV stopped, the source_* metrics are the estimator on the records up to the stop
+    (source_stop implies source_fit; its keywords are the source_fit= dict or the defaults), and source_stop_step i64 [N] is the
+    step the rule fired at, 0 where it did not.  The env's own success radius still ends episodes: make it small where the rule is
+    to do the stopping.  Refused as source_fit is: with controller / peak_stop, and on the step-wise route."""
+    fit_cfg, stop_cfg = source_fit_option(source_fit), source_stop_option(source_stop)
+    if stop_cfg is not None:
+        if controller is not None or peak_stop is not None:
+            raise ValueError("evaluate(source_stop=...): not together with controller / peak_stop: their hits are not in the records' "
+                             "flags, so the estimator could not know where those episodes ended")
+        fit_cfg = fit_cfg if fit_cfg is not None else source_fit_option(True)
     if fit_cfg is not None and (controller is not None or peak_stop is not None):
         raise ValueError("evaluate(source_fit=...): not together with controller / peak_stop: their hits are not in the records' "
                          "flags, so the estimator could not know where those episodes ended")
@@ -439,8 +453,11 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
         route = policy_route(policy_probs, env, fused, tail, "evaluate")
         if route != "stepwise":
             return _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
-                                   chunk, peak_stop_device, threshold_device, tail=route == "tail", fit_cfg=fit_cfg)
+                                   chunk, peak_stop_device, threshold_device, tail=route == "tail", fit_cfg=fit_cfg, stop_cfg=stop_cfg)
         policy_probs, nan = stepwise_policy_probs(kind, core, env)
+    if stop_cfg is not None:
+        raise ValueError("evaluate(source_stop=...): the rule reads the records of the fused and tail routes; the step-wise route "
+                         "keeps none")
     if fit_cfg is not None:
         raise ValueError("evaluate(source_fit=...): the estimator reads the records of the fused and tail routes; the step-wise "
                          "route keeps none")
@@ -466,22 +483,29 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
 
 
 def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance, chunk,
-                    peak_stop_device=False, threshold_device=False, tail=False, fit_cfg=None):
+                    peak_stop_device=False, threshold_device=False, tail=False, fit_cfg=None, stop_cfg=None):
     """evaluate() on uav_greedy_episodes: `chunk` steps per launch (tail: on GreedyRun's tail backend, `chunk` steps per host visit); the metrics (and the stop controllers) are computed from
     the records by the step-wise loop's own _StopRules.step / _Episodes.end, so the same actions give the same arrays bit for
     bit.  An env the kernel has ended stays frozen (no auto-reset); an env a rule stopped goes into the next chunk inactive.
     Only while some rule given is NOT on the device (rules.replay) are the records walked step by step, the device rules' per-step
-    flags among them; otherwise -- every rule on the device, or none given -- a chunk is one _Episodes.end_chunk."""
+    flags among them; otherwise -- every rule on the device, or none given -- a chunk is one _Episodes.end_chunk.  stop_cfg: the
+    estimator's stop rule scans each chunk before anything else reads it; its first hits go into end_chunk as a device rule's do."""
     src, ep, rules, limit = _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, threshold_device, max_steps)
     run = GreedyRun(kind, core, env, tail=tail)
     fit = SourceFit(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
+    stop = SourceStop(env.num_envs, env.device, fit_cfg=fit_cfg, **stop_cfg) if stop_cfg is not None else None
     chunk = int(chunk or (50 if rules.any else 250))
     t0 = 0
     while t0 < limit:
         k = min(chunk, limit - t0)
         recs = run.chunk(t0, k, noise)
-        if fit is not None:                          # before this chunk's ends are taken: `active` is as the chunk found it
-            fit.chunk(recs, (~ep.active).to(torch.uint8))
+        ended = (~ep.active).to(torch.uint8) if fit is not None else None     # before this chunk's ends are taken
+        at_stop = k
+        if stop is not None:                         # marks its hits in the flags and clears the kernel's `active` there
+            hit = stop.scan(recs, t0, ended, run.active)
+            at_stop = torch.where(hit >= 0, hit.to(torch.int64), k)
+        if fit is not None:
+            fit.chunk(recs, ended)
         done_c = (recs["flags"] & 1) != 0
         conc = recs["obs"][:, :, 2]                  # the record is the terminal obs where done
         rules.scan(conc, ep.active, t0, rules.replay)   # `active` is the kernel's as the launch found it (the kernel clears it at `done`)
@@ -492,7 +516,9 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
                 stop_now = rules.step(i, t0 + i + 1, conc[:, i], ep.active)
                 ep.end(ep.active & (done_b | stop_now), t0 + i + 1, stop_now, pos_end)
         else:
-            rules.peak_pred = ep.end_chunk(t0, k, done_c, recs["obs"], recs["pos"], *rules.first_hits(k), rules.peak_c, rules.peak_pred)
+            at_peak, at_thr = rules.first_hits(k)
+            rules.peak_pred = ep.end_chunk(t0, k, done_c, recs["obs"], recs["pos"], at_peak, at_thr if stop is None else at_stop,
+                                           rules.peak_c, rules.peak_pred)
         if rules.any:
             run.retire(ep.active)
         last_pos = recs["pos"][:, k - 1]             # episodes cut off by `max_steps` are still active, so stepped through the last record
@@ -505,6 +531,8 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
         sigma_true, peak_true = variant_truth(env.variant) if env.bank is None else (float("nan"), float("nan"))
         fit.finish(src.to(torch.float64).contiguous(), sigma_true, peak_true)
         out.update(fit.metrics())
+    if stop is not None:
+        out["source_stop_step"] = stop.stop_steps().cpu().numpy()
     return out
 
 
@@ -521,15 +549,18 @@ def load_lstm_policy(path, device="cuda"):
     return pol
 
 
-def main(num_envs=1000, model_dir="model", device="cuda", policy="mlp", threshold_device=False):
+def main(num_envs=1000, model_dir="model", device="cuda", policy="mlp", threshold_device=False, source_stop=False):
     """The reference's main() (evaluate_with_lstm.py:39-134) with its 1000 episodes run as 1000 parallel environments.
     policy="mlp": the reference's PPOActorCritic; "lstm": the vectorised trainer's LSTM actor-critic (same file name).
-    threshold_device (--device-rule): the ThresholdController's rule on the device (evaluate(threshold_device=True))."""
+    threshold_device (--device-rule): the ThresholdController's rule on the device (evaluate(threshold_device=True)).
+    source_stop (--source-stop, with --lstm): no ThresholdController -- the source estimator itself stops the episodes
+    (evaluate(source_stop=True)) in an env of success radius 2; prints where it stopped and how well it located the source."""
     from model import PPOActorCritic
     from uavppo.vec_env import VecMethaneEnv
     if policy not in ("mlp", "lstm"):
         raise ValueError(f"main: policy must be 'mlp' or 'lstm', got {policy!r}")
-    lstm_model = ConcentrationThresholdPredictor(device=device)
+    if source_stop and policy != "lstm":
+        raise ValueError("main: --source-stop reads the records of a policy object; use it with --lstm")
     try:
         path = os.path.join(model_dir, "ppo_successful_models.pth")
         if policy == "lstm":
@@ -538,15 +569,24 @@ def main(num_envs=1000, model_dir="model", device="cuda", policy="mlp", threshol
             sd = torch.load(path, map_location="cpu")
             ppo_model = PPOActorCritic(int(sd["feature.0.weight"].shape[1]), 5, device=device)     # 6, or 6 + TREND_K
             ppo_model.load_state_dict(sd)
-        lstm_model.load_state_dict(torch.load(os.path.join(model_dir, "lstm_threshold_predictor.pth"), map_location="cpu"))
-        scaler_params = np.load(os.path.join(model_dir, "scaler_params.npy"))
+        if not source_stop:                                      # the estimator's rule needs no predictor and no scaler
+            lstm_model = ConcentrationThresholdPredictor(device=device)
+            lstm_model.load_state_dict(torch.load(os.path.join(model_dir, "lstm_threshold_predictor.pth"), map_location="cpu"))
+            scaler_params = np.load(os.path.join(model_dir, "scaler_params.npy"))
     except FileNotFoundError as e:
         print(f"model files missing: {e}")
         return None
     trend_k = (ppo_model.obs_dim if policy == "lstm" else ppo_model.core.in_dim) - 6
     env = VecMethaneEnv(num_envs, "v2.0", device, trend_k=trend_k)
-    controller = ThresholdController(lstm_model, (scaler_params.min(), scaler_params.max()), num_envs, device=device)
-    if policy == "lstm":
+    if not source_stop:
+        controller = ThresholdController(lstm_model, (scaler_params.min(), scaler_params.max()), num_envs, device=device)
+    if source_stop:
+        env.current_radius = 2.0
+        metrics = evaluate(ppo_model, env, source_stop=True)
+        fit = metrics["source_status"] == 0
+        print(f"stopped by the estimator: {metrics['stopped_early'].mean() * 100:.1f}%  fitted: {fit.mean() * 100:.1f}%  "
+              f"median estimate error: {np.median(metrics['source_error'][fit]) if fit.any() else float('nan'):.2f} px")
+    elif policy == "lstm":
         metrics = evaluate(ppo_model, env, controller, threshold_device=threshold_device)
     else:                                                                                  # argmax of logits == argmax of probs
         metrics = evaluate(lambda o: ppo_model.core.heads(o)[:, :5], env, controller, threshold_device=threshold_device)
@@ -564,4 +604,5 @@ def main(num_envs=1000, model_dir="model", device="cuda", policy="mlp", threshol
 
 if __name__ == "__main__":
     import sys
-    main(policy="lstm" if "--lstm" in sys.argv[1:] else "mlp", threshold_device="--device-rule" in sys.argv[1:])
+    main(policy="lstm" if "--lstm" in sys.argv[1:] else "mlp", threshold_device="--device-rule" in sys.argv[1:],
+         source_stop="--source-stop" in sys.argv[1:])

@@ -16,7 +16,7 @@ from config import (BATCH_SIZE, BPTT_LEN, CLIP_EPSILON, DIST_BACKEND, ENTROPY_BE
                     NORMALISE_OBS, NORMALISE_REWARDS, NUM_MINIBATCHES, OBS_NORM_EPS, POLICY, PPO_DIAGNOSTICS, RANK, REWARD_CLIP, SEED, SHUFFLE_ENVS, TARGET_KL, TREND_K,
                     WORLD_SIZE)  # noqa: F401
 from config import DESIRED_KL, ENTROPY_BETA_FINAL, LR_FACTOR, LR_FINAL, LR_MAX, LR_MIN, LR_SCHEDULE, SCHEDULE_ITERATIONS
-from config import EVAL_ENVS, EVAL_EVERY, EVAL_MAX_STEPS, EVAL_SEED, EVAL_SOURCE_FIT, KEEP_BEST
+from config import EVAL_ENVS, EVAL_EVERY, EVAL_MAX_STEPS, EVAL_SEED, EVAL_SOURCE_FIT, EVAL_SOURCE_STOP, KEEP_BEST
 from environment import MethaneEnv
 from model import PPOActorCritic, PPOBuffer, PPOTrainer
 from uavppo import ops
@@ -187,13 +187,13 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
                        lr_schedule=LR_SCHEDULE, lr_final=LR_FINAL, ent_beta_final=ENTROPY_BETA_FINAL, schedule_iterations=SCHEDULE_ITERATIONS,
                        desired_kl=DESIRED_KL, lr_factor=LR_FACTOR, lr_min=LR_MIN, lr_max=LR_MAX,
                        eval_every=EVAL_EVERY, eval_envs=EVAL_ENVS, eval_seed=EVAL_SEED, eval_max_steps=EVAL_MAX_STEPS, keep_best=KEEP_BEST,
-                       eval_source_fit=EVAL_SOURCE_FIT)
+                       eval_source_fit=EVAL_SOURCE_FIT, eval_source_stop=EVAL_SOURCE_STOP)
     # config.EVAL_EVERY: eval_curve.csv beside the episode CSV, one row per greedy evaluation, written one evaluation late as the rows
     # land (rank 0; the sums are over all ranks' evaluation envs); best_model.pth beside the model at the end.  No host wait in the loop.
     eval_log = None
     if tr.eval_tracker is not None:
         from uavppo.eval_track import CurveLog, curve_path, save_best_model
-        eval_log = CurveLog(curve_path(csv_path or model_path or "") if rank == 0 else None, source=tr.eval_tracker.fit is not None)
+        eval_log = CurveLog(curve_path(csv_path or model_path or "") if rank == 0 else None, source=tr.eval_tracker.fit is not None, stop=tr.eval_tracker.stop is not None)
     # config.PPO_DIAGNOSTICS (or TARGET_KL, or LR_SCHEDULE "adaptive"): update_diagnostics.csv beside the episode CSV, one row per iteration (rank 0; the values
     # are over all ranks' samples).  Reading them waits for the update: one host wait per iteration that a run without them does not have.
     # With a schedule in force the row ends in the step size and entropy weight its update ran with: read when the row before it was

@@ -15,7 +15,7 @@ import torch
 from config import (BPTT_LEN, CLIP_EPSILON, ENTROPY_BETA, ENV_VARIANT, EPOCHS, GAE_MODE, GAMMA, HIDDEN, HORIZON, LAMBDA, LEARNING_RATE, NUM_ENVS,
                     NORMALISE_OBS, NORMALISE_REWARDS, NUM_LAYERS, NUM_MINIBATCHES, OBS_NORM_EPS, POLICY, PPO_DIAGNOSTICS, REWARD_CLIP, SEED, SHUFFLE_ENVS, TARGET_KL)
 from config import DESIRED_KL, ENTROPY_BETA_FINAL, LR_FACTOR, LR_FINAL, LR_MAX, LR_MIN, LR_SCHEDULE, SCHEDULE_ITERATIONS
-from config import EVAL_ENVS, EVAL_EVERY, EVAL_MAX_STEPS, EVAL_SEED, EVAL_SOURCE_FIT, KEEP_BEST
+from config import EVAL_ENVS, EVAL_EVERY, EVAL_MAX_STEPS, EVAL_SEED, EVAL_SOURCE_FIT, EVAL_SOURCE_STOP, KEEP_BEST
 from model import Discriminator, compute_discriminator_loss, get_expert_data  # noqa: F401  (train_ppo_gail.py:24-27)
 from uavppo.gail import GAILTrainer
 
@@ -38,7 +38,7 @@ def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert
                      normalise_obs=NORMALISE_OBS, obs_norm_eps=OBS_NORM_EPS, lr_schedule=LR_SCHEDULE, lr_final=LR_FINAL,
                      ent_beta_final=ENTROPY_BETA_FINAL, schedule_iterations=SCHEDULE_ITERATIONS, desired_kl=DESIRED_KL, lr_factor=LR_FACTOR,
                      lr_min=LR_MIN, lr_max=LR_MAX, eval_every=EVAL_EVERY, eval_envs=EVAL_ENVS, eval_seed=EVAL_SEED,
-                     eval_max_steps=EVAL_MAX_STEPS, keep_best=KEEP_BEST, eval_source_fit=EVAL_SOURCE_FIT)
+                     eval_max_steps=EVAL_MAX_STEPS, keep_best=KEEP_BEST, eval_source_fit=EVAL_SOURCE_FIT, eval_source_stop=EVAL_SOURCE_STOP)
     if init_model is not None:
         tr.policy.load_state_dict(torch.load(init_model, map_location="cpu"))
     # config.EVAL_EVERY: eval_curve.csv beside the saved policy, one row per greedy evaluation (train_iteration() runs it), written one
@@ -46,7 +46,7 @@ def train_ppo_gail(num_episodes=2000, num_envs=NUM_ENVS, horizon=HORIZON, expert
     eval_log = None
     if tr.eval_tracker is not None:
         from uavppo.eval_track import CurveLog, curve_path, save_best_model
-        eval_log = CurveLog(curve_path(model_path or "ppo_gail_model.pth"), source=tr.eval_tracker.fit is not None)
+        eval_log = CurveLog(curve_path(model_path or "ppo_gail_model.pth"), source=tr.eval_tracker.fit is not None, stop=tr.eval_tracker.stop is not None)
     # config.PPO_DIAGNOSTICS (or TARGET_KL, or LR_SCHEDULE "adaptive"): update_diagnostics.csv beside the saved policy, one row per
     # iteration (one host wait each); with a schedule in force the row ends in the step size and entropy weight its update ran with
     diag_log = diag = None

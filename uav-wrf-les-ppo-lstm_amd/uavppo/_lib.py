@@ -58,6 +58,11 @@ class SourceFitCfg(C.Structure):
                 ("min_pivot", C.c_double)]
 
 
+class SourceStopCfg(C.Structure):
+    """struct uav_source_stop_cfg (include/uavppo.h)."""
+    _fields_ = [("settle_tol", C.c_double), ("near", C.c_double), ("patience", C.c_int32), ("min_steps", C.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/uavppo.h one to one
 SIGNATURES = {
     "uav_abi_version": (I32, []),
@@ -151,6 +156,8 @@ SIGNATURES = {
     "uav_source_moments": (I32, [P, P, P, P, I32, I32, I32, C.POINTER(SourceFitCfg), P, P, P]),
     "uav_source_solve": (I32, [P, P, I32, C.POINTER(SourceFitCfg), P, P, P]),
     "uav_source_summary": (I32, [P, P, P, P, I32, F64, F64, F64, P, P, P]),
+    "uav_source_stop_scan": (I32, [P, P, P, P, I32, I32, I32, I32, C.POINTER(SourceFitCfg), C.POINTER(SourceStopCfg), P, P, P, P, P, P,
+                                   I32, P]),
     "uav_stop_stability": (I32, [P, I32, C.POINTER(StopRule), P, P, I64, P, P, P, P, P, P]),
     "uav_peak_stop_param_count": (SZ, [I32]),
     "uav_peak_stop_scan": (I32, [P, P, I32, I32, P, I64, I64, I32, I32, P, P, P, F32, P, P, P, P]),

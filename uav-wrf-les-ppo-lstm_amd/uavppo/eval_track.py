@@ -15,7 +15,7 @@ valid row is better; later rows are better iff successes are strictly greater, o
 keeps the earlier model.
 
 EvalTracker.run() issues launches and one non-blocking copy only; curve() returns the rows that have landed.  What is NOT in
-here: stop controllers inside the evaluation, a side stream, an early exit once every episode has ended (the number of chunks is
+here: the learned stop controllers inside the evaluation (the estimator's own rule is: source_stop=), a side stream, an early exit once every episode has ended (the number of chunks is
 fixed at ceil(limit / chunk)).
 """
 from __future__ import annotations
@@ -162,9 +162,13 @@ def better_rule(state, sums, iteration):
     return st
 
 
-def curve_row(iteration, sums, state, source=None):
+def curve_row(iteration, sums, state, source=None, stopped=None):
     """One eval_curve.csv row (CURVE_COLUMNS) from an evaluation's sums and the state behind it: plain python numbers.  source: the
-    twelve sums of uav_source_summary or None -> source_fit.SOURCE_COLUMNS behind them."""
+    twelve sums of uav_source_summary or None -> source_fit.SOURCE_COLUMNS behind them; stopped: the number of episodes the
+    estimator's stop rule ended or None -> source_stop.STOP_COLUMN (their share of the episodes) behind those."""
+    if stopped is not None:
+        n = float(np.asarray(sums, np.float64)[0])
+        return curve_row(iteration, sums, state, source) + [float(stopped) / n if n > 0 else float("nan")]
     if source is not None:
         from .source_fit import source_row
         return curve_row(iteration, sums, state) + source_row(source)
@@ -177,10 +181,12 @@ def curve_row(iteration, sums, state, source=None):
             float(S[5] / ok) if ok > 0 else float("nan"), int(S[6]) if S[6] == S[6] else 0, int(np.asarray(state)[6] == 1.0)]
 
 
-def curve_columns(source=False):
-    """eval_curve.csv's header: CURVE_COLUMNS, and source_fit.SOURCE_COLUMNS behind them where the source estimate is on."""
+def curve_columns(source=False, stop=False):
+    """eval_curve.csv's header: CURVE_COLUMNS, source_fit.SOURCE_COLUMNS behind them where the source estimate is on, and
+    source_stop.STOP_COLUMN behind those where the estimator also stops the episodes."""
     from .source_fit import SOURCE_COLUMNS
-    return CURVE_COLUMNS + (SOURCE_COLUMNS if source else [])
+    from .source_stop import STOP_COLUMN
+    return CURVE_COLUMNS + (SOURCE_COLUMNS if source or stop else []) + ([STOP_COLUMN] if stop else [])
 
 
 def write_curve(path, rows):
@@ -188,26 +194,26 @@ def write_curve(path, rows):
     import csv
     with open(path, "w", newline="") as f:
         w = csv.writer(f, lineterminator="\n")
-        w.writerow(curve_columns(any("source" in r for r in rows)))
-        w.writerows(curve_row(r["iteration"], r["sums"], r["state"], r.get("source")) for r in rows)
+        w.writerow(curve_columns(any("source" in r for r in rows), any("stopped" in r for r in rows)))
+        w.writerows(curve_row(r["iteration"], r["sums"], r["state"], r.get("source"), r.get("stopped")) for r in rows)
 
 
 class CurveLog:
     """eval_curve.csv of a training script, written as the rows land (one evaluation late, like the episode rows): add() after an
     iteration writes what has landed since, close() waits for the rest.  path None (ranks other than 0): nothing is written."""
 
-    def __init__(self, path, source=False):
+    def __init__(self, path, source=False, stop=False):
         import csv
         self.n, self.f, self.w = 0, None, None
         if path:
             self.f = open(path, "w", newline="")
             self.w = csv.writer(self.f, lineterminator="\n")
-            self.w.writerow(curve_columns(source))
+            self.w.writerow(curve_columns(source, stop))
 
     def add(self, tracker, wait=False):
         rows = tracker.curve(wait)
         if self.w is not None:
-            self.w.writerows(curve_row(r["iteration"], r["sums"], r["state"], r.get("source")) for r in rows[self.n:])
+            self.w.writerows(curve_row(r["iteration"], r["sums"], r["state"], r.get("source"), r.get("stopped")) for r in rows[self.n:])
         self.n = len(rows)
 
     def close(self, tracker):
@@ -250,16 +256,23 @@ class EvalTracker:
     later evaluations are not run and are counted in `dropped`.  source_fit: None, True or a dict of check_source_fit's keywords
     (source_fit.py): one uav_source_moments per chunk in front of its uav_greedy_reduce, uav_source_solve and uav_source_summary
     behind uav_greedy_summary; the twelve sums ride in the mirrored row and are all-reduced with the eight.  No host read is
-    added and the keep-best rule does not see them."""
+    added and the keep-best rule does not see them.  source_stop: None, True or a dict of check_source_stop's keywords
+    (source_stop.py; implies source_fit): one uav_source_stop_scan per chunk in front of the moments, which writes the estimator's
+    stop into the records' flags and clears the greedy kernel's `active` there, so the bookkeeping and the estimate see the episode
+    end where the rule said; one more value rides behind the twelve, the number of episodes the rule ended.  Give the evaluation
+    env a small eval_radius where the rule is to do the stopping: its own success radius still ends episodes."""
 
     RING = 8            # evaluations whose rows may be on their way to the host at once
 
     def __init__(self, policy, kind, num_envs=256, variant="v2.0", trend_k=0, seed=4321, bank=None, bank_sources=None, device="cuda",
                  rank=0, world=1, max_steps=None, chunk=None, success_distance=40.0, keep_best=True, eval_radius=None, guard=None,
-                 collectives=False, source_fit=None):
+                 collectives=False, source_fit=None, source_stop=None):
         from .source_fit import SUM_N as SRC_SUM_N, SourceFit, option, variant_truth
+        from .source_stop import SourceStop, option as stop_option
         c = check_eval(1, num_envs, seed, max_steps, chunk, eval_radius, keep_best)
-        fit_cfg = option(source_fit)
+        fit_cfg, stop_cfg = option(source_fit), stop_option(source_stop)
+        if stop_cfg is not None and fit_cfg is None:
+            fit_cfg = option(True)
         self.policy, self.kind, self.guard, self.collectives = policy, kind, guard, bool(collectives)
         self.N, self.device = c["eval_envs"], torch.device(device)
         self.success_distance, self.keep = float(success_distance), c["keep_best"]
@@ -288,15 +301,21 @@ class EvalTracker:
         self.deviation = torch.zeros(N, dtype=torch.float64, device=d)
         self.steps = torch.zeros(N, dtype=torch.int32, device=d)
         self.success = torch.zeros(N, dtype=torch.uint8, device=d)
-        # [sums | source sums | state]: what the ring mirrors; the sums stand together, so one all-reduce takes both
+        # [sums | source sums | stopped | state]: what the ring mirrors; the sums stand together, so one all-reduce takes them all
         self.n_src = SRC_SUM_N if fit_cfg is not None else 0
-        self.row = torch.zeros(SUM_N + self.n_src + BEST_N, dtype=torch.float64, device=d)
-        self.sums, self.state = self.row[:SUM_N], self.row[SUM_N + self.n_src:]
+        self.n_stop = 1 if stop_cfg is not None else 0
+        self.n_extra = self.n_src + self.n_stop
+        self.row = torch.zeros(SUM_N + self.n_extra + BEST_N, dtype=torch.float64, device=d)
+        self.sums, self.state = self.row[:SUM_N], self.row[SUM_N + self.n_extra:]
         self.fit = None          # source_fit.SourceFit: where the records say the source is, beside the bookkeeping
         if fit_cfg is not None:
             self.fit = SourceFit(N, d, **fit_cfg)
             self.src_sums = self.row[SUM_N:SUM_N + self.n_src]
             self.truth = variant_truth(variant) if bank is None else (float("nan"), float("nan"))
+        self.stop = None         # source_stop.SourceStop: the estimator as the stop rule, in front of the moments
+        if stop_cfg is not None:
+            self.stop = SourceStop(N, d, fit_cfg=fit_cfg, **stop_cfg)
+            self.stopped = self.row[SUM_N + self.n_src:SUM_N + self.n_extra]
         self.best = torch.zeros_like(policy.flat)
         self.ring = MirrorRing((self.row.numel(),), torch.float64, slots=self.RING)
         self._iters = []             # iteration of every slot in flight, oldest first
@@ -328,10 +347,14 @@ class EvalTracker:
         self._blob.zero_()
         if self.fit is not None:
             self.fit.restart()
+        if self.stop is not None:
+            self.stop.restart()
         t0 = 0
         while t0 < self.limit:
             k = min(self.chunk, self.limit - t0)
             recs = greedy.chunk(t0, k)
+            if self.stop is not None:                        # marks its hits in recs["flags"], clears greedy.active there
+                self.stop.scan(recs, t0, self.ep_state, greedy.active)
             if self.fit is not None:
                 self.fit.chunk(recs, self.ep_state)          # ep_state as it stands before this chunk's reduce
             ops.greedy_reduce(recs, t0, self.ep_steps, self.ep_state, self.ep_pos)
@@ -340,9 +363,12 @@ class EvalTracker:
                            nan_count=greedy.nan_count, deviation=self.deviation, steps=self.steps, success=self.success)
         if self.fit is not None:
             self.fit.finish(self.src, *self.truth, sums=self.src_sums)
+        if self.stop is not None:                            # ep_state bit1, summed: the episodes the rule ended
+            torch.sum((self.ep_state & 2).view(N, 1), dim=0, dtype=torch.float64, out=self.stopped)
+            self.stopped.mul_(0.5)
         if self.collectives:
             from .dist_utils import allreduce_sum
-            allreduce_sum(self.row[:SUM_N + self.n_src])
+            allreduce_sum(self.row[:SUM_N + self.n_extra])
         if self.keep:
             ops.keep_best(self.state, self.sums, iteration, self.policy.flat, self.best)
         if len(self.ring) == self.ring.slots:
@@ -356,15 +382,18 @@ class EvalTracker:
         while ring.in_flight and ring.events[ring.in_flight[0]].query():
             k = ring.in_flight.pop(0)
             row = ring.host[k].numpy().copy()
-            r = {"iteration": self._iters.pop(0), "sums": row[:SUM_N], "state": row[SUM_N + self.n_src:]}
+            r = {"iteration": self._iters.pop(0), "sums": row[:SUM_N], "state": row[SUM_N + self.n_extra:]}
             if self.n_src:
                 r["source"] = row[SUM_N:SUM_N + self.n_src]
+            if self.n_stop:
+                r["stopped"] = float(row[SUM_N + self.n_src])
             self._rows.append(r)
 
     def curve(self, wait=False):
         """The evaluations whose rows have landed, oldest first: dicts of iteration, sums f64 [8], state f64 [7] (after that
         evaluation's decision; state[6] == 1: it became the best), and with source_fit on source f64 [12], uav_source_summary's
-        sums.  wait=True waits for every evaluation issued so far."""
+        sums, and with source_stop on stopped, the number of episodes the estimator's rule ended.  wait=True waits for every
+        evaluation issued so far."""
         if wait:
             for k in list(self.ring.in_flight):
                 self.ring.events[k].synchronize()

@@ -1425,6 +1425,31 @@ def source_summary(est, status, src, sigma_true, peak_true, loc_tol, sums, loc_e
     return sums
 
 
+SRC_STOP_STATE_N = 27      # UAV_SRC_STOP_STATE_N
+# the fields of uav_source_stop_scan's state behind the 17 accumulators, include/uavppo.h UAV_SRC_STOP_*
+SRC_STOP_PREV_X, SRC_STOP_PREV_Y, SRC_STOP_PREV_FITTED, SRC_STOP_RUN, SRC_STOP_HIT_STEP, SRC_STOP_EST = 17, 18, 19, 20, 21, 22
+
+
+def source_stop_cfg(settle_tol=0.5, patience=3, near=float("inf"), min_steps=0):
+    """struct uav_source_stop_cfg from source_stop.check_source_stop's dict."""
+    return _lib.SourceStopCfg(float(settle_tol), float(near), int(patience), int(min_steps))
+
+
+def source_stop_scan(recs, t0, cfg, stop, state, first_hit, ended=None, active=None, mu_steps=None, status_steps=None, mark=True):
+    """S4 (uav_source_stop_scan): the estimator as a stop rule over the records of one chunk (greedy_recs: flags [N, k], obs
+    [N, k, D], pos [N, k, 2]) after t0 earlier steps (source_stop.stop_scan_chunk): state f64 [N, SRC_STOP_STATE_N] in place,
+    first_hit i32 [N] (-1: none); mark: the flags are rewritten in place (bit3 on the hit, bit2 behind it) and active u8 [N] (or
+    None) cleared at the hits; optional mu_steps f64 [N, k, 2], status_steps u8 [N, k].  No host sync."""
+    N, k, D = recs["obs"].shape
+    check(lib().uav_source_stop_scan(_h(state), _p(recs["flags"], U8, (N, k), "flags"), _p(recs["obs"], F32, (N, k, D), "obs"),
+                                     _p(recs["pos"], F32, (N, k, 2), "pos"), N, k, D, int(t0), C.byref(cfg), C.byref(stop),
+                                     _p(ended, U8, (N,), "ended"), _p(active, U8, (N,), "active"),
+                                     _p(state, F64, (N, SRC_STOP_STATE_N), "state"), _p(first_hit, I32, (N,), "first_hit"),
+                                     _p(mu_steps, F64, (N, k, 2), "mu_steps"), _p(status_steps, U8, (N, k), "status_steps"),
+                                     int(bool(mark)), _stream()), "uav_source_stop_scan")
+    return first_hit
+
+
 def stop_stability(rule, pos, obs2, stop_win, stop_cnt, active=None, stop=None, value=None):
     """One step of the stop rule for envs stepped by other means (uav_stop_stability): pos f32 [N, 2] (agent_pos after the
     move), obs2 f32 [N] or a column view such as obs[:, 2] (any element stride), active u8 [N] or None (all).  Updates

@@ -11,8 +11,8 @@ Three kernels (csrc/source_fit.hip), none of which the host waits for:
   uav_source_summary   twelve sums against the true sources, in uav_greedy_summary's order of summation
 
 moments_chunk, solve and summarise state them in numpy, in the kernels' order of operations (chunking included): what the kernels
-are tested against bit for bit.  What is NOT in here: estimates during the episode or as a stop rule, anisotropic or wind-advected
-plumes, a nonlinear refinement of the closed form, stop controllers replayed on the host (their hits are not in the flags).
+are tested against bit for bit.  Estimates during the episode, and the estimator as a stop rule, are in source_stop.py
+(uav_source_stop_scan).  What is NOT in here: anisotropic or wind-advected plumes, a nonlinear refinement of the closed form, stop controllers replayed on the host (their hits are not in the flags).
 """
 from __future__ import annotations
 

@@ -20,6 +20,7 @@ from .dist_utils import allreduce_adv_stats, allreduce_grad, allreduce_sum, coll
 from .policy import LSTMActorCritic, MLPActorCritic
 from .eval_track import EvalTracker, check_eval
 from .source_fit import option as source_fit_option
+from .source_stop import option as source_stop_option
 from .lr_control import LrController, check_lr_control, linear_value
 from .range_guard import RangeGuard
 from .obs_norm import ObsNormaliser, check_obs_norm
@@ -170,7 +171,7 @@ class VecPPOTrainer:
                  normalise_obs=False, obs_norm_eps=1e-4, obs_norm_channels=None, lr_schedule="constant", lr_final=None,
                  ent_beta_final=None, schedule_iterations=None, desired_kl=None, lr_factor=1.5, lr_min=1e-6, lr_max=1e-2,
                  eval_every=None, eval_envs=256, eval_seed=4321, eval_max_steps=None, eval_chunk=None, eval_radius=None, keep_best=True,
-                 eval_source_fit=False, **hp):
+                 eval_source_fit=False, eval_source_stop=False, **hp):
         self.hp = dict(DEFAULTS)
         # eval_every: every so many iterations the policy runs one greedy episode on each of eval_envs envs of a separate, fixed
         # evaluation env (seed eval_seed, eval_radius or the env's default radius, eval_max_steps or the env's step limit, eval_chunk
@@ -180,6 +181,9 @@ class VecPPOTrainer:
         # evaluation also estimates the plume's source from its records (uavppo/source_fit.py); the curve's rows gain "source".
         self.eval = check_eval(eval_every, eval_envs, eval_seed, eval_max_steps, eval_chunk, eval_radius, keep_best)
         self.eval["source_fit"] = source_fit_option(eval_source_fit)
+        # eval_source_stop: False / None, True or a dict of check_source_stop's keywords: the estimator also stops the evaluation's
+        # episodes (uavppo/source_stop.py; implies eval_source_fit); the rows gain "stopped".  Set eval_radius small with it.
+        self.eval["source_stop"] = source_stop_option(eval_source_stop)
         self.dgates_tile = dgates_tile       # gate gradients of the update in tile form: None = the rule of _request_dgates_tile, True / False = A/B
         self.hp.update(hp)
         # normalise_rewards: the GAE reads the reward scaled by a running estimate of the discounted return's standard deviation
@@ -303,7 +307,8 @@ class VecPPOTrainer:
             self.eval_tracker = EvalTracker(self.policy, self.kind, ev["eval_envs"], self.variant, self.trend_k, ev["eval_seed"],
                                             self.bank, self.bank_sources, d, self.rank, self.world, ev["eval_max_steps"],
                                             ev["eval_chunk"], keep_best=ev["keep_best"], eval_radius=ev["eval_radius"],
-                                            guard=self.guard, collectives=self._coll, source_fit=ev["source_fit"])
+                                            guard=self.guard, collectives=self._coll, source_fit=ev["source_fit"],
+                                            source_stop=ev["source_stop"])
 
     def _alloc_policy_work(self, hidden, layers):
         """The recurrent state and the work arrays the update's kernels write their forward pass to."""

@@ -1046,6 +1046,58 @@ int uav_source_stop_scan(uav_ctx* ctx, uint8_t* flags /*in/out*/, const float* o
                          uint8_t* active /*may be NULL*/, double* state, int32_t* first_hit, double* mu_steps, uint8_t* status_steps,
                          int mark, uav_stream stream);
 
+/* ---- Anisotropic plumes (csrc/source_aniso.hip; uavppo/source_aniso.py states each in numpy): a generator of materialised-field
+ * banks whose plume is an elliptical Gaussian centred on the source, and the estimator above with six terms instead of four.
+ *
+ * uav_plume_bank: bank f64 [F][500][500][2] (conc, tke), device memory, 16-byte aligned.  params f64 [F][UAV_PLUME_PARAM_N] in HOST
+ * memory, a row = {sx, sy, sigma_major, sigma_minor, cos theta, sin theta, peak, theta} (theta, the major axis' angle against x, is
+ * carried for the caller; the kernel reads the host's cos / sin).  Cell (x, y) of field f: dx = x - sx, dy = y - sy,
+ * u = dx cos + dy sin, v = dy cos - dx sin, e = u u / (2 sigma_major^2) + v v / (2 sigma_minor^2), base = peak exp(-e) for e <= 300,
+ * else 0; tke is the procedural field's turbulence of global env index0 + f at episode 0 under `seed`, bit for bit;
+ * conc = clip(base + tke, 0, 100).  One thread per cell; the rows travel as kernel arguments, 32 fields per launch.
+ * Refused with a reason: a NULL argument, F below 1, index0 negative, bank not 16-byte aligned, a parameter that is not finite, a
+ * width or a peak that is not positive, |cos^2 + sin^2 - 1| > 1e-12.
+ *
+ * uav_source_moments6: uav_source_moments with phi = (1, p, q, p p, p q, q q): the same records, eligibility, b, w = b b, centre,
+ * p, q, `ended` handling, largest sample and order of summation.  state f64 [n][UAV_SRC6_STATE_N], zeros = fresh: {count, cx, cy,
+ * A (21: the upper triangle by rows, (w phi_i) phi_j), g (6: (w phi_i) ln b), largest b, its x, its y}.
+ *
+ * uav_source_solve6: one thread per env, uav_source_solve's status codes.  count < min_samples -> FEW; the scaled Cholesky by
+ * columns of the 6 x 6 system, a pivot that is not finite or below min_pivot -> DEGENERATE; a0 .. a5, Lambda = -[[2 a3, a4],
+ * [a4, 2 a5]]: NOT_A_PEAK unless det > 0, trace > 0 and everything is finite.  Else FITTED with m = Lambda^-1 (a1, a2),
+ * mu = c + 32 m, disc = sqrt(((l11 - l22) / 2)^2 + l12^2), big = trace / 2 + disc, small = det / big, sigma_major = 32 / sqrt(small),
+ * sigma_minor = 32 / sqrt(big), theta = atan2(-2 l12, l22 - l11) / 2 (+ pi where negative), peak = exp(a0 + (a1 m0 + a2 m1) / 2),
+ * strength = 2 pi sigma_major sigma_minor peak.  est f64 [n][UAV_SRC6_EST_N] = {mu_x, mu_y, sigma_major, sigma_minor, theta, peak,
+ * strength, largest sample's x, y, b}: the first seven NaN unless fitted, all ten NaN for a count of 0.
+ *
+ * uav_source_summary6: sums f64 [UAV_SRC6_SUM_N] in uav_greedy_summary's order of summation: {envs, fitted, few, degenerate, not a
+ * peak, sum err, sum err^2, within loc_tol | the sums of the relative errors of sigma_major and sigma_minor, of the angle error
+ * folded into [0, pi / 2], of the relative errors of peak and strength | the sum of the largest samples' distances, the envs that
+ * have one | the fitted envs whose truth row is finite}.  truth f64 [n][4] = {sigma_major, sigma_minor, theta, peak} or NULL; a row
+ * with a value that is not finite adds 0 to the five truth sums and is not counted.  loc_err f64 [n] or NULL as uav_source_summary's.
+ *
+ * Refused with a reason: what uav_source_moments / _solve / _summary refuse, with min_samples below 6 in place of 4.  Added without
+ * a change of UAV_ABI_VERSION (symbols only). */
+#define UAV_PLUME_PARAM_N 8
+#define UAV_SRC6_STATE_N 33
+#define UAV_SRC6_EST_N 10
+#define UAV_SRC6_SUM_N 16
+#define UAV_SRC6_SUM_SIGMA_MAJOR_REL 8
+#define UAV_SRC6_SUM_SIGMA_MINOR_REL 9
+#define UAV_SRC6_SUM_THETA_ERR 10
+#define UAV_SRC6_SUM_PEAK_REL 11
+#define UAV_SRC6_SUM_STRENGTH_REL 12
+#define UAV_SRC6_SUM_MAX_ERR 13
+#define UAV_SRC6_SUM_MAX_ENVS 14
+#define UAV_SRC6_SUM_TRUTH_ENVS 15
+int uav_plume_bank(uav_ctx* ctx, const double* params /*host*/, int F, uint64_t seed, int index0, double* bank, uav_stream stream);
+int uav_source_moments6(uav_ctx* ctx, const uint8_t* flags, const float* obs, const float* pos, int n, int k, int D,
+                        const uav_source_fit_cfg* cfg /*host*/, const uint8_t* ended, double* state, uav_stream stream);
+int uav_source_solve6(uav_ctx* ctx, const double* state, int n, const uav_source_fit_cfg* cfg /*host*/, double* est, uint8_t* status,
+                      uav_stream stream);
+int uav_source_summary6(uav_ctx* ctx, const double* est, const uint8_t* status, const double* src, const double* truth, int n,
+                        double loc_tol, double* loc_err, double* sums, uav_stream stream);
+
 /* ---- K9: the iteration's exchanges over RCCL / xGMI (SURVEY 8b `uav_allreduce`, 8e).  One process per GPU, one communicator per
  * handle; RCCL is bound at run time (dlopen librccl.so.1 -- inside a PyTorch process the copy torch already loaded; $UAV_RCCL_LIB
  * overrides), so the library itself has no link-time dependency on it.  A host that is not PyTorch uses these instead of

@@ -75,7 +75,7 @@ EVAL_EVERY = None        # a number K: every K iterations one greedy episode on 
 EVAL_ENVS = 256          # ... the evaluation envs per rank (their own env: the default radius, never touched by the curriculum)
 EVAL_SEED = 4321         # ... and their seed; every evaluation runs the same episodes
 EVAL_MAX_STEPS = None    # ... the step limit of an evaluation episode (None: the env's own)
-EVAL_SOURCE_FIT = False  # ... also estimate the plume's source from each evaluation's records (True, or a dict of uavppo.source_fit.check_source_fit's keywords): six more columns in eval_curve.csv
+EVAL_SOURCE_FIT = False  # ... also estimate the plume's source from each evaluation's records (True, or a dict of uavppo.source_fit.check_source_fit's keywords): six more columns in eval_curve.csv; {"model": "aniso"}: the six-term fit of stretched plumes (FIELD_BANK "aniso:F"), nine columns
 EVAL_SOURCE_STOP = False  # ... and let that estimate stop the evaluation's episodes once it has settled (True, or a dict of uavppo.source_stop.check_source_stop's keywords; implies EVAL_SOURCE_FIT): a Stop_Rate column more.  The evaluation env's own success radius still ends episodes: give VecPPOTrainer a small eval_radius with it
 KEEP_BEST = True         # ... keep the parameters of the best evaluation so far (most successes, then fewest steps) as best_model.pth
 GAE_MODE = "reference_exact"   # or "standard" (PPOV1.0/ppo0.0.py:337-350)

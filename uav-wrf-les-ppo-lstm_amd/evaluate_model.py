@@ -25,7 +25,8 @@ import torch
 from config import CONC_PEAK, CONC_REWARD_COEF
 from uavppo import ops
 from uavppo.greedy import GreedyRun, fused_refusal, policy_core, policy_route, stepwise_policy_probs  # noqa: F401  (fused_refusal: tests)
-from uavppo.source_fit import ESTIMATE_FILE, SourceFit, variant_truth, write_estimates
+from uavppo.source_aniso import SourceFitAniso, gather_truth
+from uavppo.source_fit import ESTIMATE_FILE, SourceFit, is_aniso, variant_truth, write_estimates
 from uavppo.source_fit import option as source_fit_option
 
 F32 = torch.float32
@@ -77,7 +78,7 @@ class ModelEvaluator:
 
     @torch.no_grad()
     def run_evaluation(self, noise=None, max_steps=2000, fused=None, chunk=None, csv_path="evaluation_results.csv", tail=None,
-                       source_fit=None):
+                       source_fit=None, bank_truth=None):
         """One greedy episode per environment, all together, each until done, the stop rule, or `max_steps` (:52).
         noise: optional f64 [max_steps, N, 2] standard normals (parity tests).  fused: None = the fused kernels where
         fused_refusal allows, else step-wise; True = fused or a RuntimeError naming why not; False = step-wise.  tail: None = the
@@ -91,7 +92,9 @@ class ModelEvaluator:
         source_fit: None (off), True or a dict of uavppo.source_fit.check_source_fit's keywords: where each episode's measurements
         say the source is (uav_source_moments per chunk of records -- the stop rule's bit3 ends an episode for it as `done` does --
         then uav_source_solve / uav_source_summary).  The result gains evaluate()'s source_* arrays and source_estimates.csv is
-        written beside csv_path; evaluation_results.csv stays byte for byte.  Fused and tail routes only (ValueError otherwise)."""
+        written beside csv_path; evaluation_results.csv stays byte for byte.  Fused and tail routes only (ValueError otherwise).
+        source_fit={"model": "aniso"}: the six-term fit (uavppo/source_aniso.py); source_estimates.csv then has Sigma_Minor and Theta
+        columns behind Sigma (the major width); bank_truth f64 [F, 4] or None: the per-field truth, as evaluate() takes it."""
         kind, core = _policy_core_checked(self.model)
         env = self.env
         fit_cfg = source_fit_option(source_fit)
@@ -103,7 +106,12 @@ class ModelEvaluator:
             raise ValueError("run_evaluation(chunk=...): chunks belong to the fused path")
         env.reset()
         _, src, _, _ = env.peek()
-        fit = SourceFit(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
+        aniso = is_aniso(fit_cfg)
+        if bank_truth is not None and not aniso:
+            raise ValueError("run_evaluation(bank_truth=...): only the six-term estimator (source_fit={\"model\": \"aniso\"}) scores "
+                             "against it")
+        fit = (SourceFitAniso if aniso else SourceFit)(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
+        truth = gather_truth(bank_truth, env) if aniso else None
         src_dev = src.to(torch.float64).clone() if fit is not None else None
         src = src.cpu().numpy()
         if route != "stepwise":
@@ -120,7 +128,10 @@ class ModelEvaluator:
         if csv_path is not None:
             write_results_csv(csv_path, out["steps"], out["deviations"], out["success"], out["final_conc"])
         if fit is not None:
-            fit.finish(src_dev, *(variant_truth(env.variant) if env.bank is None else (float("nan"), float("nan"))))
+            if aniso:
+                fit.finish(src_dev, truth)
+            else:
+                fit.finish(src_dev, *(variant_truth(env.variant) if env.bank is None else (float("nan"), float("nan"))))
             out.update(fit.metrics())
             if csv_path is not None:
                 write_estimates(os.path.join(os.path.dirname(csv_path) or ".", ESTIMATE_FILE), out)

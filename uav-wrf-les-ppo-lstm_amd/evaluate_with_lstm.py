@@ -28,7 +28,8 @@ from config import EVALUATE_SIZE, SUCCESS_DISTANCE_THRESHOLD
 from uavppo import ops
 from uavppo.greedy import (GreedyRun, fused_refusal, policy_core, policy_route, stepwise_policy_probs,  # noqa: F401
                            tail_refusal)                                    # (fused_refusal, tail_refusal: tests, docs)
-from uavppo.source_fit import SourceFit, variant_truth
+from uavppo.source_aniso import SourceFitAniso, gather_truth
+from uavppo.source_fit import SourceFit, is_aniso, variant_truth
 from uavppo.source_fit import option as source_fit_option
 from uavppo.source_stop import SourceStop
 from uavppo.source_stop import option as source_stop_option
@@ -394,7 +395,7 @@ def _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, thresh
 @torch.no_grad()
 def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21=20, noise=None, max_steps=None,
              success_distance=SUCCESS_DISTANCE_THRESHOLD, fused=None, chunk=None, peak_stop_device=False, threshold_device=False,
-             tail=None, source_fit=None, source_stop=None):
+             tail=None, source_fit=None, source_stop=None, bank_truth=None):
     """One greedy episode per environment of `env` (a uavppo VecMethaneEnv), all N together.
 
     policy_probs(obs [N, obs_dim]) -> probs or logits [N, 5] (argmax is taken), or a policy object: LSTMActorCritic,
@@ -431,8 +432,18 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
     deviations and success refer to where the UAV stopped, the source_* metrics are the estimator on the records up to the stop
     (source_stop implies source_fit; its keywords are the source_fit= dict or the defaults), and source_stop_step i64 [N] is the
     step the rule fired at, 0 where it did not.  The env's own success radius still ends episodes: make it small where the rule is
-    to do the stopping.  Refused as source_fit is: with controller / peak_stop, and on the step-wise route."""
+    to do the stopping.  Refused as source_fit is: with controller / peak_stop, and on the step-wise route.
+    source_fit={"model": "aniso"}: the six-term fit of a plume stretched along an axis (uavppo/source_aniso.py; the uav_source_*6
+    kernels).  source_sigma is then the major width and the metrics gain source_sigma_minor and source_theta.  bank_truth: f64
+    [F, 4] = {sigma_major, sigma_minor, theta, peak} per field of the env's bank (field_bank.load_with_truth) or None: what the
+    summary scores the widths, the angle, the peak and the strength against, gathered per env on the device by env_core.h's field
+    rule.  Not together with source_stop (its scan is four-term): ValueError."""
     fit_cfg, stop_cfg = source_fit_option(source_fit), source_stop_option(source_stop)
+    if is_aniso(fit_cfg) and stop_cfg is not None:
+        raise ValueError("evaluate(source_stop=...): not with source_fit model \"aniso\": the stop scan solves the four-term system "
+                         "per record; a six-term scan does not exist")
+    if bank_truth is not None and not is_aniso(fit_cfg):
+        raise ValueError("evaluate(bank_truth=...): only the six-term estimator (source_fit={\"model\": \"aniso\"}) scores against it")
     if stop_cfg is not None:
         if controller is not None or peak_stop is not None:
             raise ValueError("evaluate(source_stop=...): not together with controller / peak_stop: their hits are not in the records' "
@@ -453,7 +464,8 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
         route = policy_route(policy_probs, env, fused, tail, "evaluate")
         if route != "stepwise":
             return _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance,
-                                   chunk, peak_stop_device, threshold_device, tail=route == "tail", fit_cfg=fit_cfg, stop_cfg=stop_cfg)
+                                   chunk, peak_stop_device, threshold_device, tail=route == "tail", fit_cfg=fit_cfg, stop_cfg=stop_cfg,
+                                   bank_truth=bank_truth)
         policy_probs, nan = stepwise_policy_probs(kind, core, env)
     if stop_cfg is not None:
         raise ValueError("evaluate(source_stop=...): the rule reads the records of the fused and tail routes; the step-wise route "
@@ -483,7 +495,7 @@ def evaluate(policy_probs, env, controller=None, peak_stop=None, window_size_v21
 
 
 def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noise, max_steps, success_distance, chunk,
-                    peak_stop_device=False, threshold_device=False, tail=False, fit_cfg=None, stop_cfg=None):
+                    peak_stop_device=False, threshold_device=False, tail=False, fit_cfg=None, stop_cfg=None, bank_truth=None):
     """evaluate() on uav_greedy_episodes: `chunk` steps per launch (tail: on GreedyRun's tail backend, `chunk` steps per host visit); the metrics (and the stop controllers) are computed from
     the records by the step-wise loop's own _StopRules.step / _Episodes.end, so the same actions give the same arrays bit for
     bit.  An env the kernel has ended stays frozen (no auto-reset); an env a rule stopped goes into the next chunk inactive.
@@ -492,7 +504,9 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
     estimator's stop rule scans each chunk before anything else reads it; its first hits go into end_chunk as a device rule's do."""
     src, ep, rules, limit = _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, threshold_device, max_steps)
     run = GreedyRun(kind, core, env, tail=tail)
-    fit = SourceFit(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
+    aniso = is_aniso(fit_cfg)
+    fit = (SourceFitAniso if aniso else SourceFit)(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
+    truth = gather_truth(bank_truth, env) if aniso else None        # where src was taken: after the reset, before the first step
     stop = SourceStop(env.num_envs, env.device, fit_cfg=fit_cfg, **stop_cfg) if stop_cfg is not None else None
     chunk = int(chunk or (50 if rules.any else 250))
     t0 = 0
@@ -527,7 +541,10 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
             break
     run.raise_on_nan()
     out = rules.finish(ep.metrics(src, limit, last_pos, success_distance))
-    if fit is not None:
+    if aniso:
+        fit.finish(src.to(torch.float64).contiguous(), truth)
+        out.update(fit.metrics())
+    elif fit is not None:
         sigma_true, peak_true = variant_truth(env.variant) if env.bank is None else (float("nan"), float("nan"))
         fit.finish(src.to(torch.float64).contiguous(), sigma_true, peak_true)
         out.update(fit.metrics())

@@ -178,7 +178,7 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
     iterations = ITERATIONS if iterations is None and episodes is None and EPISODES is None else iterations
     episodes = EPISODES if episodes is None else episodes
     rank, world, dev = _init_distributed()
-    bank, bank_src = field_bank.load(FIELD_BANK, ENV_VARIANT, dev)
+    bank, bank_src, bank_truth = field_bank.load_with_truth(FIELD_BANK, ENV_VARIANT, dev)      # "aniso:F": stretched plumes and their truth
     tr = VecPPOTrainer(NUM_ENVS, HORIZON, POLICY, hidden=HIDDEN, layers=NUM_LAYERS, variant=ENV_VARIANT, seed=SEED, device=dev,
                        gae_mode=GAE_MODE, num_minibatches=NUM_MINIBATCHES, shuffle_envs=SHUFFLE_ENVS, bptt_len=BPTT_LEN, log_info=True, gamma=GAMMA, lam=LAMBDA,
                        clip=CLIP_EPSILON, ent_beta=ENTROPY_BETA, lr=LEARNING_RATE, epochs=EPOCHS, rank=rank, world_size=world,
@@ -187,13 +187,14 @@ def train_ppo_vectorised(iterations=None, csv_path="training_results2_0.csv", mo
                        lr_schedule=LR_SCHEDULE, lr_final=LR_FINAL, ent_beta_final=ENTROPY_BETA_FINAL, schedule_iterations=SCHEDULE_ITERATIONS,
                        desired_kl=DESIRED_KL, lr_factor=LR_FACTOR, lr_min=LR_MIN, lr_max=LR_MAX,
                        eval_every=EVAL_EVERY, eval_envs=EVAL_ENVS, eval_seed=EVAL_SEED, eval_max_steps=EVAL_MAX_STEPS, keep_best=KEEP_BEST,
-                       eval_source_fit=EVAL_SOURCE_FIT, eval_source_stop=EVAL_SOURCE_STOP)
+                       eval_source_fit=EVAL_SOURCE_FIT, eval_source_stop=EVAL_SOURCE_STOP, bank_truth=bank_truth)
     # config.EVAL_EVERY: eval_curve.csv beside the episode CSV, one row per greedy evaluation, written one evaluation late as the rows
     # land (rank 0; the sums are over all ranks' evaluation envs); best_model.pth beside the model at the end.  No host wait in the loop.
     eval_log = None
     if tr.eval_tracker is not None:
         from uavppo.eval_track import CurveLog, curve_path, save_best_model
-        eval_log = CurveLog(curve_path(csv_path or model_path or "") if rank == 0 else None, source=tr.eval_tracker.fit is not None, stop=tr.eval_tracker.stop is not None)
+        eval_log = CurveLog(curve_path(csv_path or model_path or "") if rank == 0 else None, source=tr.eval_tracker.fit is not None, stop=tr.eval_tracker.stop is not None,
+                            aniso=tr.eval_tracker.aniso)
     # config.PPO_DIAGNOSTICS (or TARGET_KL, or LR_SCHEDULE "adaptive"): update_diagnostics.csv beside the episode CSV, one row per iteration (rank 0; the values
     # are over all ranks' samples).  Reading them waits for the update: one host wait per iteration that a run without them does not have.
     # With a schedule in force the row ends in the step size and entropy weight its update ran with: read when the row before it was

@@ -158,6 +158,10 @@ SIGNATURES = {
     "uav_source_summary": (I32, [P, P, P, P, I32, F64, F64, F64, P, P, P]),
     "uav_source_stop_scan": (I32, [P, P, P, P, I32, I32, I32, I32, C.POINTER(SourceFitCfg), C.POINTER(SourceStopCfg), P, P, P, P, P, P,
                                    I32, P]),
+    "uav_plume_bank": (I32, [P, P, I32, C.c_uint64, I32, P, P]),
+    "uav_source_moments6": (I32, [P, P, P, P, I32, I32, I32, C.POINTER(SourceFitCfg), P, P, P]),
+    "uav_source_solve6": (I32, [P, P, I32, C.POINTER(SourceFitCfg), P, P, P]),
+    "uav_source_summary6": (I32, [P, P, P, P, P, I32, F64, P, P, P]),
     "uav_stop_stability": (I32, [P, I32, C.POINTER(StopRule), P, P, I64, P, P, P, P, P, P]),
     "uav_peak_stop_param_count": (SZ, [I32]),
     "uav_peak_stop_scan": (I32, [P, P, I32, I32, P, I64, I64, I32, I32, P, P, P, F32, P, P, P, P]),

@@ -164,14 +164,16 @@ def better_rule(state, sums, iteration):
 
 def curve_row(iteration, sums, state, source=None, stopped=None):
     """One eval_curve.csv row (CURVE_COLUMNS) from an evaluation's sums and the state behind it: plain python numbers.  source: the
-    twelve sums of uav_source_summary or None -> source_fit.SOURCE_COLUMNS behind them; stopped: the number of episodes the
+    twelve sums of uav_source_summary or None -> source_fit.SOURCE_COLUMNS behind them (the sixteen of uav_source_summary6: those
+    and source_aniso.SOURCE_COLUMNS6); stopped: the number of episodes the
     estimator's stop rule ended or None -> source_stop.STOP_COLUMN (their share of the episodes) behind those."""
     if stopped is not None:
         n = float(np.asarray(sums, np.float64)[0])
         return curve_row(iteration, sums, state, source) + [float(stopped) / n if n > 0 else float("nan")]
     if source is not None:
+        from .source_aniso import SUM_N as SRC6_SUM_N, source_row6
         from .source_fit import source_row
-        return curve_row(iteration, sums, state) + source_row(source)
+        return curve_row(iteration, sums, state) + (source_row6 if len(source) == SRC6_SUM_N else source_row)(source)
     S = np.asarray(sums, np.float64)
     n, ok = float(S[0]), float(S[1])
     mean = float(S[3] / n) if n > 0 else float("nan")
@@ -181,12 +183,15 @@ def curve_row(iteration, sums, state, source=None, stopped=None):
             float(S[5] / ok) if ok > 0 else float("nan"), int(S[6]) if S[6] == S[6] else 0, int(np.asarray(state)[6] == 1.0)]
 
 
-def curve_columns(source=False, stop=False):
-    """eval_curve.csv's header: CURVE_COLUMNS, source_fit.SOURCE_COLUMNS behind them where the source estimate is on, and
-    source_stop.STOP_COLUMN behind those where the estimator also stops the episodes."""
+def curve_columns(source=False, stop=False, aniso=False):
+    """eval_curve.csv's header: CURVE_COLUMNS, source_fit.SOURCE_COLUMNS behind them where the source estimate is on (and
+    source_aniso.SOURCE_COLUMNS6 behind those for the six-term model), and source_stop.STOP_COLUMN behind those where the estimator
+    also stops the episodes."""
+    from .source_aniso import SOURCE_COLUMNS6
     from .source_fit import SOURCE_COLUMNS
     from .source_stop import STOP_COLUMN
-    return CURVE_COLUMNS + (SOURCE_COLUMNS if source or stop else []) + ([STOP_COLUMN] if stop else [])
+    return (CURVE_COLUMNS + (SOURCE_COLUMNS if source or stop or aniso else []) + (SOURCE_COLUMNS6 if aniso else [])
+            + ([STOP_COLUMN] if stop else []))
 
 
 def write_curve(path, rows):
@@ -194,7 +199,8 @@ def write_curve(path, rows):
     import csv
     with open(path, "w", newline="") as f:
         w = csv.writer(f, lineterminator="\n")
-        w.writerow(curve_columns(any("source" in r for r in rows), any("stopped" in r for r in rows)))
+        w.writerow(curve_columns(any("source" in r for r in rows), any("stopped" in r for r in rows),
+                                 any(len(r.get("source", ())) == 16 for r in rows)))
         w.writerows(curve_row(r["iteration"], r["sums"], r["state"], r.get("source"), r.get("stopped")) for r in rows)
 
 
@@ -202,13 +208,13 @@ class CurveLog:
     """eval_curve.csv of a training script, written as the rows land (one evaluation late, like the episode rows): add() after an
     iteration writes what has landed since, close() waits for the rest.  path None (ranks other than 0): nothing is written."""
 
-    def __init__(self, path, source=False, stop=False):
+    def __init__(self, path, source=False, stop=False, aniso=False):
         import csv
         self.n, self.f, self.w = 0, None, None
         if path:
             self.f = open(path, "w", newline="")
             self.w = csv.writer(self.f, lineterminator="\n")
-            self.w.writerow(curve_columns(source, stop))
+            self.w.writerow(curve_columns(source, stop, aniso))
 
     def add(self, tracker, wait=False):
         rows = tracker.curve(wait)
@@ -256,7 +262,9 @@ class EvalTracker:
     later evaluations are not run and are counted in `dropped`.  source_fit: None, True or a dict of check_source_fit's keywords
     (source_fit.py): one uav_source_moments per chunk in front of its uav_greedy_reduce, uav_source_solve and uav_source_summary
     behind uav_greedy_summary; the twelve sums ride in the mirrored row and are all-reduced with the eight.  No host read is
-    added and the keep-best rule does not see them.  source_stop: None, True or a dict of check_source_stop's keywords
+    added and the keep-best rule does not see them.  source_fit={"model": "aniso"}: the six-term kernels (source_aniso.py) and
+    their SIXTEEN sums instead; bank_truth f64 [F, 4] = {sigma_major, sigma_minor, theta, peak} per field of `bank`, or None: each
+    evaluation gathers its envs' rows on the device (env_core.h's field rule) for the summary's truth sums.  Not with source_stop.  source_stop: None, True or a dict of check_source_stop's keywords
     (source_stop.py; implies source_fit): one uav_source_stop_scan per chunk in front of the moments, which writes the estimator's
     stop into the records' flags and clears the greedy kernel's `active` there, so the bookkeeping and the estimate see the episode
     end where the rule said; one more value rides behind the twelve, the number of episodes the rule ended.  Give the evaluation
@@ -266,13 +274,21 @@ class EvalTracker:
 
     def __init__(self, policy, kind, num_envs=256, variant="v2.0", trend_k=0, seed=4321, bank=None, bank_sources=None, device="cuda",
                  rank=0, world=1, max_steps=None, chunk=None, success_distance=40.0, keep_best=True, eval_radius=None, guard=None,
-                 collectives=False, source_fit=None, source_stop=None):
-        from .source_fit import SUM_N as SRC_SUM_N, SourceFit, option, variant_truth
+                 collectives=False, source_fit=None, source_stop=None, bank_truth=None):
+        from .source_aniso import SUM_N as SRC6_SUM_N, SourceFitAniso
+        from .source_fit import SUM_N as SRC_SUM_N, SourceFit, is_aniso, option, variant_truth
         from .source_stop import SourceStop, option as stop_option
         c = check_eval(1, num_envs, seed, max_steps, chunk, eval_radius, keep_best)
         fit_cfg, stop_cfg = option(source_fit), stop_option(source_stop)
         if stop_cfg is not None and fit_cfg is None:
             fit_cfg = option(True)
+        self.aniso = is_aniso(fit_cfg)
+        if self.aniso and stop_cfg is not None:
+            raise ValueError("EvalTracker(source_stop=...): not with source_fit model \"aniso\": the stop scan solves the four-term "
+                             "system per record; a six-term scan does not exist")
+        if bank_truth is not None and not self.aniso:
+            raise ValueError("EvalTracker(bank_truth=...): only the six-term estimator (source_fit={\"model\": \"aniso\"}) scores "
+                             "against it")
         self.policy, self.kind, self.guard, self.collectives = policy, kind, guard, bool(collectives)
         self.N, self.device = c["eval_envs"], torch.device(device)
         self.success_distance, self.keep = float(success_distance), c["keep_best"]
@@ -302,16 +318,21 @@ class EvalTracker:
         self.steps = torch.zeros(N, dtype=torch.int32, device=d)
         self.success = torch.zeros(N, dtype=torch.uint8, device=d)
         # [sums | source sums | stopped | state]: what the ring mirrors; the sums stand together, so one all-reduce takes them all
-        self.n_src = SRC_SUM_N if fit_cfg is not None else 0
+        self.n_src = (SRC6_SUM_N if self.aniso else SRC_SUM_N) if fit_cfg is not None else 0
         self.n_stop = 1 if stop_cfg is not None else 0
         self.n_extra = self.n_src + self.n_stop
         self.row = torch.zeros(SUM_N + self.n_extra + BEST_N, dtype=torch.float64, device=d)
         self.sums, self.state = self.row[:SUM_N], self.row[SUM_N + self.n_extra:]
         self.fit = None          # source_fit.SourceFit: where the records say the source is, beside the bookkeeping
         if fit_cfg is not None:
-            self.fit = SourceFit(N, d, **fit_cfg)
+            self.fit = (SourceFitAniso if self.aniso else SourceFit)(N, d, **fit_cfg)
             self.src_sums = self.row[SUM_N:SUM_N + self.n_src]
             self.truth = variant_truth(variant) if bank is None else (float("nan"), float("nan"))
+            # model "aniso": f64 [F, 4] per field of the bank, or None; each evaluation gathers its envs' rows on the device
+            self.bank_truth = None if bank_truth is None else torch.as_tensor(bank_truth, dtype=torch.float64).to(d)
+            if self.bank_truth is not None:
+                from .source_aniso import gather_truth
+                gather_truth(self.bank_truth, self.env)          # the shape check, once
         self.stop = None         # source_stop.SourceStop: the estimator as the stop rule, in front of the moments
         if stop_cfg is not None:
             self.stop = SourceStop(N, d, fit_cfg=fit_cfg, **stop_cfg)
@@ -343,6 +364,9 @@ class EvalTracker:
         env, N = self.env, self.N
         env.reset()
         ops.env_peek(env.state, N, source=self.src)
+        if self.aniso:                                       # the truth of the episodes whose sources were just taken
+            from .source_aniso import gather_truth
+            truth6 = gather_truth(self.bank_truth, env)
         greedy.restart()
         self._blob.zero_()
         if self.fit is not None:
@@ -361,7 +385,9 @@ class EvalTracker:
             t0 += k
         ops.greedy_summary(self.ep_steps, self.ep_state, self.ep_pos, self.src, self.limit, self.success_distance, self.sums,
                            nan_count=greedy.nan_count, deviation=self.deviation, steps=self.steps, success=self.success)
-        if self.fit is not None:
+        if self.aniso:
+            self.fit.finish(self.src, truth6, sums=self.src_sums)
+        elif self.fit is not None:
             self.fit.finish(self.src, *self.truth, sums=self.src_sums)
         if self.stop is not None:                            # ep_state bit1, summed: the episodes the rule ended
             torch.sum((self.ep_state & 2).view(N, 1), dim=0, dtype=torch.float64, out=self.stopped)
@@ -392,7 +418,7 @@ class EvalTracker:
     def curve(self, wait=False):
         """The evaluations whose rows have landed, oldest first: dicts of iteration, sums f64 [8], state f64 [7] (after that
         evaluation's decision; state[6] == 1: it became the best), and with source_fit on source f64 [12], uav_source_summary's
-        sums, and with source_stop on stopped, the number of episodes the estimator's rule ended.  wait=True waits for every
+        sums (model "aniso": f64 [16], uav_source_summary6's), and with source_stop on stopped, the number of episodes the estimator's rule ended.  wait=True waits for every
         evaluation issued so far."""
         if wait:
             for k in list(self.ring.in_flight):

@@ -1425,6 +1425,56 @@ def source_summary(est, status, src, sigma_true, peak_true, loc_tol, sums, loc_e
     return sums
 
 
+PLUME_PARAM_N, SRC6_STATE_N, SRC6_EST_N, SRC6_SUM_N = 8, 33, 10, 16      # UAV_PLUME_PARAM_N, UAV_SRC6_STATE_N, _EST_N, _SUM_N
+# the sixteen sums of uav_source_summary6, include/uavppo.h UAV_SRC_SUM_* (the first eight) and UAV_SRC6_SUM_*
+SRC6_SUM_NAMES = ("envs", "fitted", "few", "degenerate", "not_a_peak", "err", "err_sq", "within", "sigma_major_rel", "sigma_minor_rel",
+                  "theta_err", "peak_rel", "strength_rel", "max_err", "max_envs", "truth_envs")
+
+
+def plume_bank(params, seed, index0=0, out=None, device="cuda"):
+    """P1 (uav_plume_bank): bank f64 [F, 500, 500, 2] of elliptical-Gaussian plumes with E3's turbulence of the global envs index0 ..
+    index0 + F - 1 at episode 0 under `seed`.  params: HOST f64 [F, PLUME_PARAM_N] (numpy; source_aniso.plume_params builds it).  No
+    host sync."""
+    import numpy as np
+    prm = np.ascontiguousarray(np.asarray(params, np.float64))
+    if prm.ndim != 2 or prm.shape[1] != PLUME_PARAM_N:
+        raise RuntimeError(f"params: expected shape (F, {PLUME_PARAM_N}), got {prm.shape}")
+    F = prm.shape[0]
+    if out is None:
+        out = torch.empty(F, 500, 500, 2, dtype=F64, device=device)
+    check(lib().uav_plume_bank(_h(out), prm.ctypes.data_as(C.c_void_p), F, int(seed) & 0xFFFFFFFFFFFFFFFF, int(index0),
+                               _p(out, F64, (F, 500, 500, 2), "bank"), _stream()), "uav_plume_bank")
+    return out
+
+
+def source_moments6(recs, cfg, state, ended=None):
+    """A1 (uav_source_moments6): source_moments with six basis functions: state f64 [N, SRC6_STATE_N] in place
+    (source_aniso.moments_chunk6).  No host sync."""
+    N, k, D = recs["obs"].shape
+    check(lib().uav_source_moments6(_h(state), _p(recs["flags"], U8, (N, k), "flags"), _p(recs["obs"], F32, (N, k, D), "obs"),
+                                    _p(recs["pos"], F32, (N, k, 2), "pos"), N, k, D, C.byref(cfg), _p(ended, U8, (N,), "ended"),
+                                    _p(state, F64, (N, SRC6_STATE_N), "state"), _stream()), "uav_source_moments6")
+
+
+def source_solve6(state, cfg, est, status):
+    """A2 (uav_source_solve6): state f64 [N, SRC6_STATE_N] -> est f64 [N, SRC6_EST_N], status u8 [N] (source_aniso.solve6).  No host
+    sync."""
+    N = state.shape[0]
+    check(lib().uav_source_solve6(_h(state), _p(state, F64, (N, SRC6_STATE_N), "state"), N, C.byref(cfg),
+                                  _p(est, F64, (N, SRC6_EST_N), "est"), _p(status, U8, (N,), "status"), _stream()), "uav_source_solve6")
+
+
+def source_summary6(est, status, src, truth, loc_tol, sums, loc_err=None):
+    """A3 (uav_source_summary6): sums f64 [SRC6_SUM_N] of the estimates against the sources src f64 [N, 2] and the per-env truth f64
+    [N, 4] = {sigma_major, sigma_minor, theta, peak} or None (source_aniso.summarise6, its order of summation).  No host sync."""
+    N = status.numel()
+    check(lib().uav_source_summary6(_h(sums), _p(est, F64, (N, SRC6_EST_N), "est"), _p(status, U8, (N,), "status"),
+                                    _p(src, F64, (N, 2), "src"), _p(truth, F64, (N, 4), "truth"), N, float(loc_tol),
+                                    _p(loc_err, F64, (N,), "loc_err"), _p(sums, F64, (SRC6_SUM_N,), "sums"), _stream()),
+          "uav_source_summary6")
+    return sums
+
+
 SRC_STOP_STATE_N = 27      # UAV_SRC_STOP_STATE_N
 # the fields of uav_source_stop_scan's state behind the 17 accumulators, include/uavppo.h UAV_SRC_STOP_*
 SRC_STOP_PREV_X, SRC_STOP_PREV_Y, SRC_STOP_PREV_FITTED, SRC_STOP_RUN, SRC_STOP_HIT_STEP, SRC_STOP_EST = 17, 18, 19, 20, 21, 22

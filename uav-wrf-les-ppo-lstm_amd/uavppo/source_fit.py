@@ -12,7 +12,7 @@ Three kernels (csrc/source_fit.hip), none of which the host waits for:
 
 moments_chunk, solve and summarise state them in numpy, in the kernels' order of operations (chunking included): what the kernels
 are tested against bit for bit.  Estimates during the episode, and the estimator as a stop rule, are in source_stop.py
-(uav_source_stop_scan).  What is NOT in here: anisotropic or wind-advected plumes, a nonlinear refinement of the closed form, stop controllers replayed on the host (their hits are not in the flags).
+(uav_source_stop_scan).  Anisotropic plumes: source_aniso.py (model="aniso").  What is NOT in here: a nonlinear refinement of the closed form, stop controllers replayed on the host (their hits are not in the flags).
 """
 from __future__ import annotations
 
@@ -35,15 +35,22 @@ def _num(v):
     return isinstance(v, (int, float, np.integer, np.floating)) and not isinstance(v, (bool, np.bool_))
 
 
-def check_source_fit(use_tke=True, min_samples=5, background=0.0, floor=1.0, min_pivot=1e-6, loc_tol=5.0):
+def check_source_fit(use_tke=True, min_samples=None, background=0.0, floor=1.0, min_pivot=1e-6, loc_tol=5.0, model="iso"):
     """The estimator's keywords, refused with the reason (ValueError); returns them as a dict of plain values.  Pure host arithmetic.
     use_tke: subtract the record's own turbulence channel (else the constant `background`); a record is used iff b > floor and its
     cell was not clipped -- a floor near 0 lets the fit extrapolate from the far tail; min_samples >= 4 used records for a fit;
-    min_pivot: the smallest accepted pivot of the scaled Cholesky; loc_tol: the error (cells) counted as "within"."""
+    min_pivot: the smallest accepted pivot of the scaled Cholesky; loc_tol: the error (cells) counted as "within".
+    model: "iso" (the four-term fit of a round plume; min_samples None = 5) or "aniso" (the six-term fit of source_aniso.py:
+    both widths and the axis angle; min_samples None = 8, never below 6).  The dict carries `model` only where it is "aniso"."""
+    if model not in ("iso", "aniso"):
+        raise ValueError(f"model={model!r}: \"iso\" or \"aniso\"")
+    least = 4 if model == "iso" else 6
+    if min_samples is None:
+        min_samples = 5 if model == "iso" else 8
     if not isinstance(use_tke, (bool, np.bool_)):
         raise ValueError(f"use_tke={use_tke!r}: True or False")
-    if not (isinstance(min_samples, (int, np.integer)) and not isinstance(min_samples, bool) and 4 <= min_samples < 1 << 31):
-        raise ValueError(f"min_samples={min_samples!r}: at least 4 records (the fit has four parameters)")
+    if not (isinstance(min_samples, (int, np.integer)) and not isinstance(min_samples, bool) and least <= min_samples < 1 << 31):
+        raise ValueError(f"min_samples={min_samples!r}: at least {least} records (the fit has {'four' if least == 4 else 'six'} parameters)")
     if not (_num(background) and np.isfinite(background)):
         raise ValueError(f"background={background!r}: a finite concentration")
     if not (_num(floor) and np.isfinite(floor) and floor >= 0.0):
@@ -52,8 +59,16 @@ def check_source_fit(use_tke=True, min_samples=5, background=0.0, floor=1.0, min
         raise ValueError(f"min_pivot={min_pivot!r}: a finite positive pivot")
     if not (_num(loc_tol) and loc_tol == loc_tol and loc_tol >= 0.0):
         raise ValueError(f"loc_tol={loc_tol!r}: a non-negative distance in cells")
-    return dict(use_tke=bool(use_tke), min_samples=int(min_samples), background=float(background), floor=float(floor),
-                min_pivot=float(min_pivot), loc_tol=float(loc_tol))
+    cfg = dict(use_tke=bool(use_tke), min_samples=int(min_samples), background=float(background), floor=float(floor),
+               min_pivot=float(min_pivot), loc_tol=float(loc_tol))
+    if model != "iso":
+        cfg["model"] = model
+    return cfg
+
+
+def is_aniso(cfg):
+    """Whether a check_source_fit dict (or None) asks for the six-term model."""
+    return cfg is not None and cfg.get("model", "iso") == "aniso"
 
 
 def option(source_fit):
@@ -302,15 +317,19 @@ def metrics(est, status, loc_err):
 
 
 def write_estimates(path, m):
-    """source_estimates.csv (ESTIMATE_COLUMNS) from evaluate()'s metrics: one row per episode, NaN written as "nan"."""
+    """source_estimates.csv (ESTIMATE_COLUMNS) from evaluate()'s metrics: one row per episode, NaN written as "nan".  The six-term
+    model's metrics (source_sigma_minor, source_theta) put Sigma_Minor and Theta behind Sigma, for that model only."""
     import csv
     from .ops import SRC_STATUS_NAMES
+    six = "source_sigma_minor" in m
     with open(path, "w", newline="") as f:
         w = csv.writer(f, lineterminator="\n")
-        w.writerow(ESTIMATE_COLUMNS)
+        at = ESTIMATE_COLUMNS.index("Sigma") + 1
+        w.writerow(ESTIMATE_COLUMNS[:at] + ["Sigma_Minor", "Theta"] + ESTIMATE_COLUMNS[at:] if six else ESTIMATE_COLUMNS)
         for i in range(len(m["source_status"])):
+            more = [float(m["source_sigma_minor"][i]), float(m["source_theta"][i])] if six else []
             w.writerow([i + 1, SRC_STATUS_NAMES[int(m["source_status"][i])], *(float(v) for v in m["source_estimate"][i]),
-                        float(m["source_sigma"][i]), float(m["source_peak"][i]), float(m["source_strength"][i]),
+                        float(m["source_sigma"][i]), *more, float(m["source_peak"][i]), float(m["source_strength"][i]),
                         float(m["source_error"][i]), *(float(v) for v in m["source_max_sample"][i])])
 
 

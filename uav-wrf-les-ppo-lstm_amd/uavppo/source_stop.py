@@ -228,6 +228,8 @@ class SourceStop:
         import torch
         from . import ops
         self.fit_cfg = sf.check_source_fit(**(fit_cfg or {}))
+        if sf.is_aniso(self.fit_cfg):
+            raise ValueError("source_stop: not with source_fit model \"aniso\": the scan solves the four-term system per record")
         self.cfg = check_source_stop(**cfg)
         self.n, self.device = int(n), torch.device(device)
         self._f, self._s = ops.source_fit_cfg(**self.fit_cfg), ops.source_stop_cfg(**self.cfg)

@@ -171,7 +171,7 @@ class VecPPOTrainer:
                  normalise_obs=False, obs_norm_eps=1e-4, obs_norm_channels=None, lr_schedule="constant", lr_final=None,
                  ent_beta_final=None, schedule_iterations=None, desired_kl=None, lr_factor=1.5, lr_min=1e-6, lr_max=1e-2,
                  eval_every=None, eval_envs=256, eval_seed=4321, eval_max_steps=None, eval_chunk=None, eval_radius=None, keep_best=True,
-                 eval_source_fit=False, eval_source_stop=False, **hp):
+                 eval_source_fit=False, eval_source_stop=False, bank_truth=None, **hp):
         self.hp = dict(DEFAULTS)
         # eval_every: every so many iterations the policy runs one greedy episode on each of eval_envs envs of a separate, fixed
         # evaluation env (seed eval_seed, eval_radius or the env's default radius, eval_max_steps or the env's step limit, eval_chunk
@@ -180,7 +180,11 @@ class VecPPOTrainer:
         # the launches it did without it.  eval_source_fit: False / None, True or a dict of check_source_fit's keywords: each
         # evaluation also estimates the plume's source from its records (uavppo/source_fit.py); the curve's rows gain "source".
         self.eval = check_eval(eval_every, eval_envs, eval_seed, eval_max_steps, eval_chunk, eval_radius, keep_best)
+        # eval_source_fit={"model": "aniso"}: the six-term fit of plumes stretched along an axis (uavppo/source_aniso.py); bank_truth
+        # f64 [F, 4] per field of `bank` (field_bank.load_with_truth) or None is what its widths, angle and peak are scored against.
+        # It is read by that model only: training itself never sees it.
         self.eval["source_fit"] = source_fit_option(eval_source_fit)
+        self.eval["bank_truth"] = bank_truth if (self.eval["source_fit"] or {}).get("model") == "aniso" else None
         # eval_source_stop: False / None, True or a dict of check_source_stop's keywords: the estimator also stops the evaluation's
         # episodes (uavppo/source_stop.py; implies eval_source_fit); the rows gain "stopped".  Set eval_radius small with it.
         self.eval["source_stop"] = source_stop_option(eval_source_stop)
@@ -308,7 +312,7 @@ class VecPPOTrainer:
                                             self.bank, self.bank_sources, d, self.rank, self.world, ev["eval_max_steps"],
                                             ev["eval_chunk"], keep_best=ev["keep_best"], eval_radius=ev["eval_radius"],
                                             guard=self.guard, collectives=self._coll, source_fit=ev["source_fit"],
-                                            source_stop=ev["source_stop"])
+                                            source_stop=ev["source_stop"], bank_truth=ev["bank_truth"])
 
     def _alloc_policy_work(self, hidden, layers):
         """The recurrent state and the work arrays the update's kernels write their forward pass to."""

@@ -285,13 +285,13 @@ def test_source_summary6_is_summarise6(ops, sa, n):
         assert want["loc_err"][5] == 5.0
 
 
-def test_source_fit_aniso_class_runs_the_three(ops, sa):
-    """SourceFitAniso: restart / chunk / finish over two chunks equals the statement's driver."""
+def test_source_fit_aniso_class_runs_the_three(ops, sa, sf):
+    """SourceFit(model="aniso"): restart / chunk / finish over two chunks equals the statement's driver."""
     from uavppo import eval_track as et
     n, k = 48, 80
     ep = episodes6(n, k, 6, seed=4)
     ep["ended"][:] = 0
-    fit = sa.SourceFitAniso(n, DEV)
+    fit = sf.SourceFit(n, DEV, model="aniso")
     fit.state.fill_(3.0)
     fit.restart()
     state = [dev(a) for a in et.fresh_episodes(n)]
@@ -299,7 +299,7 @@ def test_source_fit_aniso_class_runs_the_three(ops, sa):
         recs = {key: dev(ep[key][:, t0:t0 + 50]) for key in ("flags", "obs", "pos")}
         fit.chunk(recs, state[1])
         ops.greedy_reduce(recs, t0, *state)
-    sums = fit.finish(dev(ep["src"]), dev(ep["truth"])).cpu().numpy()
+    sums = fit.finish(dev(ep["src"]), truth=dev(ep["truth"])).cpu().numpy()
     chunks = [(ep["flags"][:, :50], ep["obs"][:, :50], ep["pos"][:, :50]), (ep["flags"][:, 50:], ep["obs"][:, 50:], ep["pos"][:, 50:])]
     st, est, status = sa.fit_records6(chunks, n)
     assert np.array_equal(bits64(fit.state.cpu().numpy()[:, EXACT]), bits64(st[:, EXACT]))
@@ -465,9 +465,9 @@ def make_trainer(b, **kw):
     return VecPPOTrainer(32, 16, device=DEV, seed=11, variant="v2.0", bank=b[0], bank_sources=b[1], policy="lstm", hidden=64, **kw)
 
 
-def test_trainer_and_tracker_carry_the_sixteen_sums(aniso8, sa):
+def test_trainer_and_tracker_carry_the_sixteen_sums(aniso8, sa, sf):
     """Three iterations on the bank: parameters byte-identical with and without eval_source_fit; one EvalTracker.run() row carries
-    the sums a standalone SourceFitAniso gives on the same evaluation, truth gathered by the field rule; run() reads nothing."""
+    the sums a standalone SourceFit(model="aniso") gives on the same evaluation, truth gathered by the field rule; run() reads nothing."""
     from uavppo import eval_track as et, ops
     ev = dict(eval_every=1, eval_envs=N, eval_max_steps=STEPS, eval_chunk=CHUNK, eval_radius=2.0)
     on = make_trainer(aniso8, eval_source_fit={"model": "aniso"}, bank_truth=aniso8[2], **ev)
@@ -491,7 +491,7 @@ def test_trainer_and_tracker_carry_the_sixteen_sums(aniso8, sa):
         assert r["source"].shape == (16,) and r["source"][0] == N and r["source"][1:5].sum() == N
         assert r["source"][15] == r["source"][1]                            # every fitted env has its truth row
     print(f"\nfitted {[int(r['source'][1]) for r in rows]} of {N}")
-    # a standalone SourceFitAniso over evaluation 4: the tracker's env arguments, the parameters as they stand
+    # a standalone six-term SourceFit over evaluation 4: the tracker's env arguments, the parameters as they stand
     from uavppo.greedy import GreedyRun, policy_core
     from uavppo.vec_env import VecMethaneEnv
     t = on.eval_tracker
@@ -501,13 +501,13 @@ def test_trainer_and_tracker_carry_the_sixteen_sums(aniso8, sa):
     src = env.peek()[1].to(torch.float64).contiguous()
     truth = aniso8[2][torch.arange(N, device=DEV) % 8].contiguous()
     k2, core = policy_core(on.policy)
-    run, fit = GreedyRun(k2, core, env), sa.SourceFitAniso(N, DEV)
+    run, fit = GreedyRun(k2, core, env), sf.SourceFit(N, DEV, model="aniso")
     state = [torch.from_numpy(a).to(DEV) for a in et.fresh_episodes(N)]
     for t0 in range(0, STEPS, CHUNK):
         recs = run.chunk(t0, min(CHUNK, STEPS - t0))
         fit.chunk(recs, state[1])
         ops.greedy_reduce(recs, t0, *state)
-    sums = fit.finish(src, truth).cpu().numpy()
+    sums = fit.finish(src, truth=truth).cpu().numpy()
     assert np.array_equal(bits64(sums), bits64(rows[3]["source"]))
     line = et.curve_row(rows[3]["iteration"], rows[3]["sums"], rows[3]["state"], rows[3]["source"])
     assert len(line) == len(et.curve_columns(True, aniso=True)) == len(et.CURVE_COLUMNS) + 9

@@ -26,7 +26,7 @@ DEV = "cuda:0"
 N = 1024
 # gfx950, hipcc -O3 -ffp-contract=off, the build's flags
 RESOURCES = {"plume_bank_kernel": {"vgprs": 38, "spills": 0, "scratch": 0, "waves_per_simd": 8},
-             "source_moments6_kernel": {"vgprs": 170, "spills": 0, "scratch": 0, "waves_per_simd": 2},
+             "source_moments6_kernel": {"vgprs": 172, "spills": 0, "scratch": 0, "waves_per_simd": 2},
              "source_solve6_kernel": {"vgprs": 96, "spills": 0, "scratch": 0, "waves_per_simd": 5},
              "source_summary6_kernel": {"vgprs": 76, "spills": 0, "scratch": 0, "lds_bytes": 32, "waves_per_simd": 6}}
 

@@ -25,7 +25,7 @@ import torch
 from config import CONC_PEAK, CONC_REWARD_COEF
 from uavppo import ops
 from uavppo.greedy import GreedyRun, fused_refusal, policy_core, policy_route, stepwise_policy_probs  # noqa: F401  (fused_refusal: tests)
-from uavppo.source_aniso import SourceFitAniso, gather_truth
+from uavppo.source_aniso import gather_truth
 from uavppo.source_fit import ESTIMATE_FILE, SourceFit, is_aniso, variant_truth, write_estimates
 from uavppo.source_fit import option as source_fit_option
 
@@ -110,7 +110,7 @@ class ModelEvaluator:
         if bank_truth is not None and not aniso:
             raise ValueError("run_evaluation(bank_truth=...): only the six-term estimator (source_fit={\"model\": \"aniso\"}) scores "
                              "against it")
-        fit = (SourceFitAniso if aniso else SourceFit)(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
+        fit = SourceFit(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
         truth = gather_truth(bank_truth, env) if aniso else None
         src_dev = src.to(torch.float64).clone() if fit is not None else None
         src = src.cpu().numpy()
@@ -128,10 +128,7 @@ class ModelEvaluator:
         if csv_path is not None:
             write_results_csv(csv_path, out["steps"], out["deviations"], out["success"], out["final_conc"])
         if fit is not None:
-            if aniso:
-                fit.finish(src_dev, truth)
-            else:
-                fit.finish(src_dev, *(variant_truth(env.variant) if env.bank is None else (float("nan"), float("nan"))))
+            fit.finish(src_dev, *(variant_truth(env.variant) if env.bank is None else (float("nan"), float("nan"))), truth=truth)
             out.update(fit.metrics())
             if csv_path is not None:
                 write_estimates(os.path.join(os.path.dirname(csv_path) or ".", ESTIMATE_FILE), out)

@@ -28,7 +28,7 @@ from config import EVALUATE_SIZE, SUCCESS_DISTANCE_THRESHOLD
 from uavppo import ops
 from uavppo.greedy import (GreedyRun, fused_refusal, policy_core, policy_route, stepwise_policy_probs,  # noqa: F401
                            tail_refusal)                                    # (fused_refusal, tail_refusal: tests, docs)
-from uavppo.source_aniso import SourceFitAniso, gather_truth
+from uavppo.source_aniso import gather_truth
 from uavppo.source_fit import SourceFit, is_aniso, variant_truth
 from uavppo.source_fit import option as source_fit_option
 from uavppo.source_stop import SourceStop
@@ -505,7 +505,7 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
     src, ep, rules, limit = _begin(env, controller, peak_stop, window_size_v21, peak_stop_device, threshold_device, max_steps)
     run = GreedyRun(kind, core, env, tail=tail)
     aniso = is_aniso(fit_cfg)
-    fit = (SourceFitAniso if aniso else SourceFit)(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
+    fit = SourceFit(env.num_envs, env.device, **fit_cfg) if fit_cfg is not None else None
     truth = gather_truth(bank_truth, env) if aniso else None        # where src was taken: after the reset, before the first step
     stop = SourceStop(env.num_envs, env.device, fit_cfg=fit_cfg, **stop_cfg) if stop_cfg is not None else None
     chunk = int(chunk or (50 if rules.any else 250))
@@ -541,12 +541,9 @@ def _evaluate_fused(kind, core, env, controller, peak_stop, window_size_v21, noi
             break
     run.raise_on_nan()
     out = rules.finish(ep.metrics(src, limit, last_pos, success_distance))
-    if aniso:
-        fit.finish(src.to(torch.float64).contiguous(), truth)
-        out.update(fit.metrics())
-    elif fit is not None:
+    if fit is not None:                              # the four-term model's truth is the variant's, the six-term model's per env
         sigma_true, peak_true = variant_truth(env.variant) if env.bank is None else (float("nan"), float("nan"))
-        fit.finish(src.to(torch.float64).contiguous(), sigma_true, peak_true)
+        fit.finish(src.to(torch.float64).contiguous(), sigma_true, peak_true, truth=truth)
         out.update(fit.metrics())
     if stop is not None:
         out["source_stop_step"] = stop.stop_steps().cpu().numpy()

@@ -275,7 +275,7 @@ class EvalTracker:
     def __init__(self, policy, kind, num_envs=256, variant="v2.0", trend_k=0, seed=4321, bank=None, bank_sources=None, device="cuda",
                  rank=0, world=1, max_steps=None, chunk=None, success_distance=40.0, keep_best=True, eval_radius=None, guard=None,
                  collectives=False, source_fit=None, source_stop=None, bank_truth=None):
-        from .source_aniso import SUM_N as SRC6_SUM_N, SourceFitAniso
+        from .source_aniso import SUM_N as SRC6_SUM_N
         from .source_fit import SUM_N as SRC_SUM_N, SourceFit, is_aniso, option, variant_truth
         from .source_stop import SourceStop, option as stop_option
         c = check_eval(1, num_envs, seed, max_steps, chunk, eval_radius, keep_best)
@@ -325,7 +325,7 @@ class EvalTracker:
         self.sums, self.state = self.row[:SUM_N], self.row[SUM_N + self.n_extra:]
         self.fit = None          # source_fit.SourceFit: where the records say the source is, beside the bookkeeping
         if fit_cfg is not None:
-            self.fit = (SourceFitAniso if self.aniso else SourceFit)(N, d, **fit_cfg)
+            self.fit = SourceFit(N, d, **fit_cfg)
             self.src_sums = self.row[SUM_N:SUM_N + self.n_src]
             self.truth = variant_truth(variant) if bank is None else (float("nan"), float("nan"))
             # model "aniso": f64 [F, 4] per field of the bank, or None; each evaluation gathers its envs' rows on the device
@@ -364,6 +364,7 @@ class EvalTracker:
         env, N = self.env, self.N
         env.reset()
         ops.env_peek(env.state, N, source=self.src)
+        truth6 = None
         if self.aniso:                                       # the truth of the episodes whose sources were just taken
             from .source_aniso import gather_truth
             truth6 = gather_truth(self.bank_truth, env)
@@ -385,10 +386,8 @@ class EvalTracker:
             t0 += k
         ops.greedy_summary(self.ep_steps, self.ep_state, self.ep_pos, self.src, self.limit, self.success_distance, self.sums,
                            nan_count=greedy.nan_count, deviation=self.deviation, steps=self.steps, success=self.success)
-        if self.aniso:
-            self.fit.finish(self.src, truth6, sums=self.src_sums)
-        elif self.fit is not None:
-            self.fit.finish(self.src, *self.truth, sums=self.src_sums)
+        if self.fit is not None:
+            self.fit.finish(self.src, *self.truth, truth=truth6, sums=self.src_sums)
         if self.stop is not None:                            # ep_state bit1, summed: the episodes the rule ended
             torch.sum((self.ep_state & 2).view(N, 1), dim=0, dtype=torch.float64, out=self.stopped)
             self.stopped.mul_(0.5)

@@ -1398,20 +1398,30 @@ def source_fit_cfg(use_tke=True, min_samples=5, background=0.0, floor=1.0, min_p
     return _lib.SourceFitCfg(int(bool(use_tke)), int(min_samples), float(background), float(floor), float(min_pivot))
 
 
+def _source_moments(entry, state_n, recs, cfg, state, ended):
+    """uav_source_moments / uav_source_moments6: one argument list, the state's width apart"""
+    N, k, D = recs["obs"].shape
+    check(getattr(lib(), entry)(_h(state), _p(recs["flags"], U8, (N, k), "flags"), _p(recs["obs"], F32, (N, k, D), "obs"),
+                                _p(recs["pos"], F32, (N, k, 2), "pos"), N, k, D, C.byref(cfg), _p(ended, U8, (N,), "ended"),
+                                _p(state, F64, (N, state_n), "state"), _stream()), entry)
+
+
+def _source_solve(entry, state_n, est_n, state, cfg, est, status):
+    """uav_source_solve / uav_source_solve6: one argument list, the widths of state and est apart"""
+    N = state.shape[0]
+    check(getattr(lib(), entry)(_h(state), _p(state, F64, (N, state_n), "state"), N, C.byref(cfg), _p(est, F64, (N, est_n), "est"),
+                                _p(status, U8, (N,), "status"), _stream()), entry)
+
+
 def source_moments(recs, cfg, state, ended=None):
     """S1 (uav_source_moments): the records of one chunk (greedy_recs: flags [N, k], obs [N, k, D], pos [N, k, 2]) added to state f64
     [N, SRC_STATE_N] in place (source_fit.moments_chunk); ended u8 [N] or None: envs left alone.  No host sync."""
-    N, k, D = recs["obs"].shape
-    check(lib().uav_source_moments(_h(state), _p(recs["flags"], U8, (N, k), "flags"), _p(recs["obs"], F32, (N, k, D), "obs"),
-                                   _p(recs["pos"], F32, (N, k, 2), "pos"), N, k, D, C.byref(cfg), _p(ended, U8, (N,), "ended"),
-                                   _p(state, F64, (N, SRC_STATE_N), "state"), _stream()), "uav_source_moments")
+    _source_moments("uav_source_moments", SRC_STATE_N, recs, cfg, state, ended)
 
 
 def source_solve(state, cfg, est, status):
     """S2 (uav_source_solve): state f64 [N, SRC_STATE_N] -> est f64 [N, SRC_EST_N], status u8 [N] (source_fit.solve).  No host sync."""
-    N = state.shape[0]
-    check(lib().uav_source_solve(_h(state), _p(state, F64, (N, SRC_STATE_N), "state"), N, C.byref(cfg),
-                                 _p(est, F64, (N, SRC_EST_N), "est"), _p(status, U8, (N,), "status"), _stream()), "uav_source_solve")
+    _source_solve("uav_source_solve", SRC_STATE_N, SRC_EST_N, state, cfg, est, status)
 
 
 def source_summary(est, status, src, sigma_true, peak_true, loc_tol, sums, loc_err=None):
@@ -1450,18 +1460,13 @@ def plume_bank(params, seed, index0=0, out=None, device="cuda"):
 def source_moments6(recs, cfg, state, ended=None):
     """A1 (uav_source_moments6): source_moments with six basis functions: state f64 [N, SRC6_STATE_N] in place
     (source_aniso.moments_chunk6).  No host sync."""
-    N, k, D = recs["obs"].shape
-    check(lib().uav_source_moments6(_h(state), _p(recs["flags"], U8, (N, k), "flags"), _p(recs["obs"], F32, (N, k, D), "obs"),
-                                    _p(recs["pos"], F32, (N, k, 2), "pos"), N, k, D, C.byref(cfg), _p(ended, U8, (N,), "ended"),
-                                    _p(state, F64, (N, SRC6_STATE_N), "state"), _stream()), "uav_source_moments6")
+    _source_moments("uav_source_moments6", SRC6_STATE_N, recs, cfg, state, ended)
 
 
 def source_solve6(state, cfg, est, status):
     """A2 (uav_source_solve6): state f64 [N, SRC6_STATE_N] -> est f64 [N, SRC6_EST_N], status u8 [N] (source_aniso.solve6).  No host
     sync."""
-    N = state.shape[0]
-    check(lib().uav_source_solve6(_h(state), _p(state, F64, (N, SRC6_STATE_N), "state"), N, C.byref(cfg),
-                                  _p(est, F64, (N, SRC6_EST_N), "est"), _p(status, U8, (N,), "status"), _stream()), "uav_source_solve6")
+    _source_solve("uav_source_solve6", SRC6_STATE_N, SRC6_EST_N, state, cfg, est, status)
 
 
 def source_summary6(est, status, src, truth, loc_tol, sums, loc_err=None):

@@ -6,34 +6,27 @@ and uav_plume_bank (csrc/source_aniso.hip) fills [F, 500, 500, 2] banks of clip(
 states `base` in numpy.  A record of such a field still carries b = 100 obs[2] - 9 obs[3], and ln b is a full quadratic,
     ln b = a0 + a1 p + a2 q + a3 p^2 + a4 p q + a5 q^2,
 linear in six parameters: the weighted least-squares fit of source_fit.py with two more terms gives the source, both widths, the
-axis angle and the peak in closed form.  p, q, the centre, SCALE, b, w = b^2, which records are used, chunking, the `ended`
-handling and the largest sample are source_fit.moments_chunk's.  Three kernels, none of which the host waits for:
+axis angle and the peak in closed form.  The moments, the Cholesky and the solve are source_fit's own, given the basis ANISO; what
+is stated here is the six-term closed form and the summary's truth columns.  Three kernels, none of which the host waits for:
 
   uav_source_moments6   per chunk of records: A (21), g (6), the count, the centre and the largest sample, per env
   uav_source_solve6     per evaluation: scaled Cholesky of the 6 x 6 system -> mu, sigma_major, sigma_minor, theta, peak, strength
   uav_source_summary6   sixteen sums against the true sources and, where given, the true widths, angle and peak per env
 
-moments_chunk6, coefficients6, solve6 and summarise6 state them in numpy in the kernels' order of operations.  What is NOT in
+moments_chunk6, coefficients6, solve6 and summarise6 state them in numpy in the kernels' order of operations (SourceFit(model="aniso")
+of source_fit.py drives them on the device).  What is NOT in
 here: a six-term stop scan (source_stop is four-term), plumes whose width grows downwind or that vanish upwind of the source.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .source_fit import DEGENERATE, FEW, FITTED, NOT_A_PEAK, SCALE, SLOTS, TWO_PI, _block256, _tree, used_records
+from . import source_fit as sf
+from .source_fit import ANISO, SCALE, TWO_PI
 
-STATE_N, EST_N, SUM_N, PLUME_PARAM_N = 33, 10, 16, 8     # ops.SRC6_STATE_N, SRC6_EST_N, SRC6_SUM_N, PLUME_PARAM_N
-N_PHI, N_A, N_ACC = 6, 21, 28                            # phi = (1, p, q, p p, p q, q q); count | A | g
-ST_A, ST_G, ST_BMAX = 3, 24, 30
+STATE_N, EST_N, SUM_N, PLUME_PARAM_N = ANISO.state_n, ANISO.est_n, ANISO.sum_n, 8     # ops.SRC6_STATE_N, SRC6_EST_N, SRC6_SUM_N, PLUME_PARAM_N
 PI = 3.141592653589793
-MIN_SAMPLES = 8                                          # the default of model="aniso"; six parameters: never below 6
-# A's upper triangle by rows -> its place among the state's 21 entries
-_IDX = [[0] * N_PHI for _ in range(N_PHI)]
-_n = 0
-for _i in range(N_PHI):
-    for _j in range(_i, N_PHI):
-        _IDX[_i][_j] = _IDX[_j][_i] = _n
-        _n += 1
+MIN_SAMPLES = ANISO.min_samples                          # the default of model="aniso"; six parameters: never below 6
 SOURCE_COLUMNS6 = ["Mean_Sigma_Minor_Rel_Error", "Mean_Theta_Error", "Mean_Strength_Rel_Error"]
 ESTIMATE_COLUMNS6 = ["Sigma_Minor", "Theta"]
 
@@ -74,140 +67,55 @@ def plume_base(params, x, y):
 
 
 # ------------------------------------------------------------------------------------------ the numpy definitions
+# moments, Cholesky and solve are source_fit's, written once for any basis: these are its bindings to ANISO
 def fresh_state6(n):
     """state f64 [n, 33] of an evaluation that has not stepped yet: all zeros."""
-    return np.zeros((n, STATE_N), np.float64)
+    return sf.fresh_state(n, ANISO)
 
 
-def moments_chunk6(flags, obs, pos, state, ended=None, use_tke=True, background=0.0, floor=1.0, **_):
-    """uav_source_moments6: the new state f64 [n, 33] after one chunk of records.  source_fit.moments_chunk with phi = (1, p, q,
-    p p, p q, q q): A_ij = (w phi_i) phi_j for i <= j by rows, g_i = (w phi_i) ln b; the same order of summation."""
-    used, b, cell = used_records(flags, obs, pos, ended, use_tke, background, floor)
-    n, k = used.shape
-    st = np.array(state, np.float64).reshape(n, STATE_N).copy()
-    live = np.ones(n, bool) if ended is None else np.asarray(ended) == 0
-    any_used = used.any(1)
-    i0 = used.argmax(1)
-    e = np.arange(n)
-    new_c = live & any_used & ~(st[:, 0] > 0.0)                 # the centre: the cell of the env's first used record, then fixed
-    st[new_c, 1] = cell[e, i0, 0][new_c].astype(np.float64)
-    st[new_c, 2] = cell[e, i0, 1][new_c].astype(np.float64)
-    p = (cell[:, :, 0].astype(np.float64) - st[:, 1:2]) / SCALE
-    q = (cell[:, :, 1].astype(np.float64) - st[:, 2:3]) / SCALE
-    bu = np.where(used, b, 1.0)
-    w, lb = bu * bu, np.log(bu)
-    phi = [np.ones_like(w), p, q, p * p, p * q, q * q]
-    wphi = [w] + [w * phi[j] for j in range(1, N_PHI)]
-    cols = [np.ones_like(w)]
-    cols += [wphi[i] * phi[j] if j else wphi[i] for i in range(N_PHI) for j in range(i, N_PHI)]
-    cols += [wphi[i] * lb for i in range(N_PHI)]
-    c = np.where(used[:, :, None], np.stack(cols, 2), 0.0)
-    nb = (k + 63) // 64
-    c = np.concatenate([c, np.zeros((n, nb * 64 - k, N_ACC))], 1).reshape(n, nb, 64, N_ACC)
-    acc = np.zeros((n, 64, N_ACC), np.float64)
-    for blk in range(nb):
-        acc = acc + c[:, blk]
-    tot = _tree(acc)
-    st[live, 0] = st[live, 0] + tot[live, 0]
-    st[live, ST_A:ST_BMAX] = st[live, ST_A:ST_BMAX] + tot[live, 1:]
-    im = np.where(used, b, -np.inf).argmax(1)                   # the first of equal largest
-    bm = b[e, im]
-    with np.errstate(invalid="ignore"):
-        up = live & any_used & (bm > st[:, ST_BMAX])            # strictly: an earlier chunk's record wins a tie
-    st[up, ST_BMAX] = bm[up]
-    st[up, ST_BMAX + 1] = cell[e, im, 0][up].astype(np.float64)
-    st[up, ST_BMAX + 2] = cell[e, im, 1][up].astype(np.float64)
-    return st
+def moments_chunk6(flags, obs, pos, state, ended=None, **cfg):
+    """uav_source_moments6: source_fit.moments_chunk with phi = (1, p, q, p p, p q, q q)."""
+    return sf.moments_chunk(flags, obs, pos, state, ended, **dict(cfg, basis=ANISO))
 
 
 def scaled_system6(state):
-    """(S f64 [n, 6, 6], h f64 [n, 6], d f64 [n, 6]): A scaled by d_j = sqrt(A_jj) and g / d, the system solve6 factors."""
-    st = np.asarray(state, np.float64).reshape(-1, STATE_N)
-    A = np.stack([np.stack([st[:, ST_A + _IDX[i][j]] for j in range(N_PHI)], 1) for i in range(N_PHI)], 1)
-    with np.errstate(all="ignore"):
-        d = np.sqrt(np.stack([A[:, j, j] for j in range(N_PHI)], 1))
-        S = A / (d[:, :, None] * d[:, None, :])
-        h = st[:, ST_G:ST_G + N_PHI] / d
-    return S, h, d
+    return sf.scaled_system(state, ANISO)
 
 
 def coefficients6(state, min_pivot=1e-6):
-    """(a f64 [n, 6], degenerate bool [n], smallest pivot f64 [n]): source_fit.coefficients on the 6 x 6 system -- the scaled Cholesky
-    by columns, the two triangular solves and the unscaling, every t = t - L * z one after the other, no fused multiply-add."""
-    S, h, d = scaled_system6(state)
-    n, N = S.shape[0], N_PHI
-    L = np.zeros((n, N, N), np.float64)
-    bad = np.zeros(n, bool)
-    low = np.full(n, np.inf)
-    with np.errstate(all="ignore"):
-        for j in range(N):
-            s = S[:, j, j]
-            for c in range(j):
-                s = s - L[:, j, c] * L[:, j, c]
-            bad |= ~(np.isfinite(s) & (s >= np.float64(min_pivot)))
-            low = np.where(np.isfinite(s), np.minimum(low, s), -np.inf)
-            L[:, j, j] = np.sqrt(s)
-            for i in range(j + 1, N):
-                t = S[:, i, j]
-                for c in range(j):
-                    t = t - L[:, i, c] * L[:, j, c]
-                L[:, i, j] = t / L[:, j, j]
-        z = np.zeros((n, N), np.float64)
-        u = np.zeros((n, N), np.float64)
-        for j in range(N):
-            t = h[:, j]
-            for c in range(j):
-                t = t - L[:, j, c] * z[:, c]
-            z[:, j] = t / L[:, j, j]
-        for j in range(N - 1, -1, -1):
-            t = z[:, j]
-            for c in range(j + 1, N):
-                t = t - L[:, c, j] * u[:, c]
-            u[:, j] = t / L[:, j, j]
-        a = u / d
-    return a, bad, low
+    """(a f64 [n, 6], degenerate bool [n], smallest pivot f64 [n]): source_fit.cholesky on the 6 x 6 system."""
+    return sf.cholesky(state, min_pivot, ANISO)
+
+
+def closed_form6(a, cx, cy):
+    """ANISO's closed form: a0 .. a5 and the centre -> ((mu_x, mu_y, sigma_major, sigma_minor, theta, peak, strength), peaked).
+    Lambda = -[[2 a3, a4], [a4, 2 a5]] is the plume's inverse covariance in units of SCALE cells: a peak iff det > 0 and trace > 0
+    (and every value finite)."""
+    l11, l12, l22 = -(2.0 * a[:, 3]), -a[:, 4], -(2.0 * a[:, 5])
+    det = l11 * l22 - l12 * l12
+    trace = l11 + l22
+    m0 = (l22 * a[:, 1] - l12 * a[:, 2]) / det
+    m1 = (l11 * a[:, 2] - l12 * a[:, 1]) / det
+    hd = (l11 - l22) / 2.0
+    disc = np.sqrt(hd * hd + l12 * l12)
+    big = trace / 2.0 + disc
+    small = det / big
+    s_major = SCALE / np.sqrt(small)
+    s_minor = SCALE / np.sqrt(big)
+    th = np.arctan2(-(2.0 * l12), l22 - l11) / 2.0
+    theta = np.where(th < 0.0, th + PI, th)
+    peak = np.exp(a[:, 0] + (a[:, 1] * m0 + a[:, 2] * m1) / 2.0)
+    vals = (cx + SCALE * m0, cy + SCALE * m1, s_major, s_minor, theta, peak, TWO_PI * (s_major * s_minor) * peak)
+    peaked = np.isfinite(a).all(1) & (det > 0.0) & (trace > 0.0)
+    for v in vals:
+        peaked &= np.isfinite(v)
+    return vals, peaked
 
 
 def solve6(state, min_samples=MIN_SAMPLES, min_pivot=1e-6, **_):
     """uav_source_solve6: (est f64 [n, 10], status u8 [n]).  est = {mu_x, mu_y, sigma_major, sigma_minor, theta, peak, strength,
-    largest sample's x, y, b}; the first seven are NaN unless status is FITTED, all ten for a count of 0.  Lambda = -[[2 a3, a4],
-    [a4, 2 a5]] is the plume's inverse covariance in units of SCALE cells: a peak iff det > 0 and trace > 0."""
-    st = np.asarray(state, np.float64).reshape(-1, STATE_N)
-    n = st.shape[0]
-    est = np.full((n, EST_N), np.nan)
-    status = np.zeros(n, np.uint8)
-    count = st[:, 0]
-    some = count > 0.0
-    est[some, 7], est[some, 8], est[some, 9] = st[some, ST_BMAX + 1], st[some, ST_BMAX + 2], st[some, ST_BMAX]
-    few = ~(count >= np.float64(min_samples))
-    a, bad, _ = coefficients6(st, min_pivot)
-    with np.errstate(all="ignore"):
-        l11, l12, l22 = -(2.0 * a[:, 3]), -a[:, 4], -(2.0 * a[:, 5])
-        det = l11 * l22 - l12 * l12
-        trace = l11 + l22
-        m0 = (l22 * a[:, 1] - l12 * a[:, 2]) / det
-        m1 = (l11 * a[:, 2] - l12 * a[:, 1]) / det
-        mx = st[:, 1] + SCALE * m0
-        my = st[:, 2] + SCALE * m1
-        hd = (l11 - l22) / 2.0
-        disc = np.sqrt(hd * hd + l12 * l12)
-        big = trace / 2.0 + disc
-        small = det / big
-        s_major = SCALE / np.sqrt(small)
-        s_minor = SCALE / np.sqrt(big)
-        th = np.arctan2(-(2.0 * l12), l22 - l11) / 2.0
-        theta = np.where(th < 0.0, th + PI, th)
-        peak = np.exp(a[:, 0] + (a[:, 1] * m0 + a[:, 2] * m1) / 2.0)
-        strength = TWO_PI * (s_major * s_minor) * peak
-        vals = (mx, my, s_major, s_minor, theta, peak, strength)
-        peaked = np.isfinite(a).all(1) & (det > 0.0) & (trace > 0.0)
-        for v in vals:
-            peaked &= np.isfinite(v)
-    status[:] = np.where(few, FEW, np.where(bad, DEGENERATE, np.where(peaked, FITTED, NOT_A_PEAK)))
-    ok = status == FITTED
-    for j, v in enumerate(vals):
-        est[ok, j] = v[ok]
-    return est, status
+    largest sample's x, y, b}; the first seven are NaN unless status is FITTED, all ten for a count of 0."""
+    return sf.solve(state, min_samples, min_pivot, ANISO)
 
 
 def summarise6(est, status, src, truth, loc_tol):
@@ -216,16 +124,10 @@ def summarise6(est, status, src, truth, loc_tol):
     theta, peak} is finite: the sums of the relative errors of sigma_major and sigma_minor, of the angle error folded into
     [0, pi / 2], of the relative errors of the peak and of the strength 2 pi sigma_major sigma_minor peak | the sum of the largest
     samples' distances to the source, how many envs have one | how many fitted envs have a finite truth row}.  truth None: as all
-    NaN.  source_fit.summarise's order of summation."""
-    est, status = np.asarray(est, np.float64).reshape(-1, EST_N), np.asarray(status, np.uint8)
-    src = np.asarray(src, np.float64)
-    n = status.shape[0]
-    tr = np.full((n, 4), np.nan) if truth is None else np.asarray(truth, np.float64).reshape(n, 4)
-    fit = status == FITTED
-    with np.errstate(all="ignore"):
-        dx, dy = est[:, 0] - src[:, 0], est[:, 1] - src[:, 1]
-        err = np.where(fit, np.sqrt(dx * dx + dy * dy), np.nan)
-        within = fit & (err <= np.float64(loc_tol))
+    NaN.  source_fit.summary_sums' order of summation."""
+    def truth_columns(est, fit):
+        n = len(fit)
+        tr = np.full((n, 4), np.nan) if truth is None else np.asarray(truth, np.float64).reshape(n, 4)
         known = fit & np.isfinite(tr).all(1)
         r1 = np.abs(est[:, 2] - tr[:, 0]) / tr[:, 0]
         r2 = np.abs(est[:, 3] - tr[:, 1]) / tr[:, 1]
@@ -234,36 +136,13 @@ def summarise6(est, status, src, truth, loc_tol):
         rp = np.abs(est[:, 5] - tr[:, 3]) / tr[:, 3]
         ts = TWO_PI * (tr[:, 0] * tr[:, 1]) * tr[:, 3]
         rs = np.abs(est[:, 6] - ts) / ts
-        has = est[:, 9] == est[:, 9]
-        mx, my = est[:, 7] - src[:, 0], est[:, 8] - src[:, 1]
-        md = np.sqrt(mx * mx + my * my)
-    z = np.zeros(n)
-    vals = np.stack([fit.astype(np.float64), (status == FEW).astype(np.float64), (status == DEGENERATE).astype(np.float64),
-                     (status == NOT_A_PEAK).astype(np.float64), np.where(fit, err, z), np.where(fit, err * err, z),
-                     within.astype(np.float64), np.where(known, r1, z), np.where(known, r2, z), np.where(known, da, z),
-                     np.where(known, rp, z), np.where(known, rs, z), np.where(has, md, z), has.astype(np.float64),
-                     known.astype(np.float64)], axis=1)
-    acc = np.zeros((SLOTS, SUM_N - 1), np.float64)
-    for r0 in range(0, n, SLOTS):
-        c = vals[r0:r0 + SLOTS]
-        acc[:c.shape[0]] += c
-    return {"sums": np.concatenate([[np.float64(n)], _block256(acc)]), "loc_err": err}
+        return [np.where(known, v, 0.0) for v in (r1, r2, da, rp, rs)], [known.astype(np.float64)]
+    return sf.summary_sums(ANISO, est, status, src, loc_tol, truth_columns)
 
 
 def fit_records6(chunks, n, ended_of=None, **cfg):
-    """The statement over a whole episode, as source_fit.fit_records: chunks = [(flags, obs, pos)] in time order -> (state, est,
-    status)."""
-    from .eval_track import fresh_episodes, reduce_chunk
-    from .source_fit import check_source_fit
-    cfg = check_source_fit(**{"model": "aniso", **cfg})
-    st, ep, t0 = fresh_state6(n), fresh_episodes(n), 0
-    for i, (flags, obs, pos) in enumerate(chunks):
-        ended = ep[1] if ended_of is None else ended_of(i)
-        st = moments_chunk6(flags, obs, pos, st, ended, **cfg)
-        ep = reduce_chunk(flags, obs, pos, t0, *ep)
-        t0 += np.asarray(flags).shape[1]
-    est, status = solve6(st, **cfg)
-    return st, est, status
+    """The statement over a whole episode: source_fit.fit_records with model "aniso"."""
+    return sf.fit_records(chunks, n, ended_of, **{"model": "aniso", **cfg})
 
 
 def source_row6(sums):
@@ -312,42 +191,3 @@ def gather_truth(bank_truth, env):
         raise ValueError(f"bank_truth: expected [F = {env.bank.shape[0]}, 4] = {{sigma_major, sigma_minor, theta, peak}}, got {tuple(bt.shape)}")
     episode = env.peek()[3]
     return bt[field_index(env.num_envs, episode, bt.shape[0], env.env_offset, env.n_env_total)].contiguous()
-
-
-# ------------------------------------------------------------------------------------------ the device side
-class SourceFitAniso:
-    """SourceFit's interface on the six-term kernels: restart(), chunk(recs, ended) once per chunk of greedy records BEFORE that
-    chunk's uav_greedy_reduce, finish(src, truth) after the last.  Launches only: nothing is read by the host."""
-
-    def __init__(self, n, device="cuda", **cfg):
-        import torch
-        from . import ops
-        from .source_fit import check_source_fit
-        self.cfg = check_source_fit(**{"model": "aniso", **cfg})
-        self.n, self.device = int(n), torch.device(device)
-        self._c = ops.source_fit_cfg(**self.cfg)
-        self.state = torch.zeros(self.n, STATE_N, dtype=torch.float64, device=self.device)
-        self.est = torch.zeros(self.n, EST_N, dtype=torch.float64, device=self.device)
-        self.status = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-        self.loc_err = torch.zeros(self.n, dtype=torch.float64, device=self.device)
-        self.sums = torch.zeros(SUM_N, dtype=torch.float64, device=self.device)
-
-    def restart(self):
-        self.state.zero_()
-
-    def chunk(self, recs, ended=None):
-        """ended u8 [n]: ep_state as it stands before this chunk's uav_greedy_reduce, or None (nothing has ended)."""
-        from . import ops
-        ops.source_moments6(recs, self._c, self.state, ended)
-
-    def finish(self, src, truth=None, loc_tol=None, sums=None):
-        """uav_source_solve6, then uav_source_summary6 against src f64 [n, 2] and truth f64 [n, 4] or None into `sums` (default:
-        self.sums); returns it."""
-        from . import ops
-        ops.source_solve6(self.state, self._c, self.est, self.status)
-        return ops.source_summary6(self.est, self.status, src, truth, self.cfg["loc_tol"] if loc_tol is None else loc_tol,
-                                   self.sums if sums is None else sums, loc_err=self.loc_err)
-
-    def metrics(self):
-        """evaluate()'s source_* entries as numpy arrays.  Waits for the device."""
-        return metrics6(self.est.cpu().numpy(), self.status.cpu().numpy(), self.loc_err.cpu().numpy())

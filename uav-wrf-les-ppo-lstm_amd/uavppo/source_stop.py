@@ -152,18 +152,7 @@ def stop_scan_chunk(flags, obs, pos, t0, state, ended, fit_cfg, stop_cfg):
     take = eligible_records(flags, idle.astype(np.uint8))
     used, b, cell = sf.used_records(flags, obs, pos, idle.astype(np.uint8), fit_cfg["use_tke"], fit_cfg["background"], fit_cfg["floor"])
     e = np.arange(n)
-    new_c = used.any(1) & ~(st[:, 0] > 0.0)                     # the centre: the cell of the episode's first used record
-    i0 = used.argmax(1)
-    st[new_c, 1] = cell[e, i0, 0][new_c].astype(np.float64)
-    st[new_c, 2] = cell[e, i0, 1][new_c].astype(np.float64)
-    p = (cell[:, :, 0].astype(np.float64) - st[:, 1:2]) / sf.SCALE
-    q = (cell[:, :, 1].astype(np.float64) - st[:, 2:3]) / sf.SCALE
-    r = p * p + q * q
-    bu = np.where(used, b, 1.0)
-    w, lb = bu * bu, np.log(bu)
-    wp, wq, wr = w * p, w * q, w * r
-    c = np.stack([np.ones_like(w), w, wp, wq, wr, wp * p, wp * q, wp * r, wq * q, wq * r, wr * r, w * lb, wp * lb, wq * lb, wr * lb], 2)
-    c = np.where(used[:, :, None], c, 0.0)
+    c = sf.contributions(used, b, cell, st)                     # fixes the centre of an env without one, in st
     nb = (k + 63) // 64
     c = np.concatenate([c, np.zeros((n, nb * 64 - k, 15))], 1)
     tk = np.concatenate([take, np.zeros((n, nb * 64 - k), bool)], 1)

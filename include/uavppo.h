@@ -171,7 +171,10 @@ int uav_pack_success_bits(uav_ctx* ctx, const uint8_t* flags, int64_t n, int cap
  * total = policy + value - ent_beta*entropy, each a mean over 1/inv_n samples.  dhead_bias
  * (f32 [n_act+1], or NULL): column sums of (dlogits | dvalue) = gradient of the head biases.
  * Packed form: value == NULL and dvalue == NULL -> `logits` is the heads buffer [n][n_act+1]
- * (logits | value) and `dlogits` receives d(total)/d(heads) in the same [n][n_act+1] layout. */
+ * (logits | value) and `dlogits` receives d(total)/d(heads) in the same [n][n_act+1] layout.
+ * n_act: 2, 3, 4, 5, 6 or 8.  A ratio that overflows f32 (logp_old below about logp - 88) leaves the gradient of a
+ * sample that is clipped away or has no advantage at 0; where the unclipped side is the minimum, loss and gradient are
+ * infinite as the arithmetic has them. */
 int uav_ppo_loss(uav_ctx* ctx, const float* logits, const float* value, const int32_t* act,
                  const float* logp_old, const float* adv, const float* ret, const float* val_old,
                  int64_t n, int n_act, float inv_n, float clip, float ent_beta,

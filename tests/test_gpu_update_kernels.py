@@ -73,6 +73,7 @@ def test_normalise_matches_oracle(ops, shape):
     assert np.allclose(gr.cpu().numpy().reshape(-1), want_r.numpy(), rtol=1e-5, atol=1e-5)
     s = stats.cpu().numpy()
     assert s[2] == adv.size and np.isclose(s[0], adv.astype(np.float64).sum(), rtol=1e-12, atol=1e-9)
+    assert np.isclose(s[1], (adv.astype(np.float64) ** 2).sum(), rtol=1e-12, atol=0)
 
 
 def test_normalise_constant_buffer_guard(ops):

@@ -203,7 +203,10 @@ __device__ __forceinline__ float ppo_sample(const float* z, float V, int a, floa
     if (s1 < s2) g_ratio = Ad;
     else if (s1 == s2) g_ratio = 0.5f * Ad + (in_rng ? 0.5f * Ad : 0.f);
     else g_ratio = in_rng ? Ad : 0.f;
-    const float g_logp = clamp_open ? (-inv_n * g_ratio * ratio) : 0.f;   // dL/dlogp
+    // dL/dlogp.  A ratio that overflowed to +inf (logp_old far below anything a policy assigns) whose sample is clipped away or
+    // has no advantage has the gradient 0, not 0 * inf = NaN; every other sample's bits are those of the plain product.
+    const bool dead_inf = (g_ratio == 0.f) && (ratio == __builtin_inff());
+    const float g_logp = (clamp_open && !dead_inf) ? (-inv_n * g_ratio * ratio) : 0.f;
 
     // value loss, train_ppo2.0.py:74-78
     const float dv = V - vo;
